@@ -11,6 +11,11 @@ Default workload = BASELINE.json configs[2], the largest single-GPU configuratio
 10 s mixtures per GPU (255,488 frame windows, 2.65 PFLOP per step).  `--clips-per-gpu 1` is
 configs[1].  Prints ONE JSON line on rank 0 (contract in the task statement).
 
+A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step`, `frames_per_s`,
+`per_rank` step times, `status_flags`).  Everything else it can measure or check runs only with --full: the
+clock / power sampling, `rccl_ranks`, `rms_vs_golden_10s`, the per-kernel pass, the power-cap ceiling, the CPU
+baseline and `rms_check`.  --dump-outputs DIR writes the waveforms the last timed step returned (dump_outputs()).
+
 The timed region runs with the library's per-launch profiling events OFF.  The per-kernel figures
 (`roofline`, `hbm_kernels`, `kernel_ms_per_step`) come from ONE extra pass run right after the timed
 region with hipEvents recorded by the library on the launch stream around every launch.
@@ -43,6 +48,8 @@ F16_MFMA_PEAK_TFLOPS = 2500.0     # dense f16 MFMA peak; the split mode executes
 HBM_PEAK_GBS = 8000.0             # spec; 6,290 GB/s is what a float4 copy achieves (same guide)
 HBM_ACHIEVABLE_GBS = 6290.0
 PMC_SUMMARY_NAME = "pmc_summary_bench_256clips.json"      # profiles/rNN/: the newest one whose kernel-source fingerprint is the tree's
+DUMP_BUDGET_BYTES = 48 << 20      # --dump-outputs stays under 64 MB: the default batch (164 MB of waveform) is sampled
+DUMP_SEED = 20240
 
 
 def parse(argv=None):
@@ -59,6 +66,12 @@ def parse(argv=None):
     p.add_argument("--precision", default="f16x3", choices=["f32", "f16x3"])
     p.add_argument("--option", action="append", default=[], metavar="KEY=VALUE",
                    help="nhans_set_option knob for an A/B run (e.g. winograd=0); recorded in config")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: clock/power sampling, rccl_ranks, the golden "
+                        "comparison, the per-kernel pass (roofline), the power-cap ceiling, the CPU baseline and rms_check")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the denoised waveforms of the last timed step to DIR/*.npy (float32; a seeded sample of "
+                        "whole clips when they exceed %d MiB)" % (DUMP_BUDGET_BYTES >> 20))
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-kernel-pass", action="store_true", help="skip the extra profiled pass (rocprofv3 runs)")
     p.add_argument("--ceiling-seconds", type=float, default=2.0,
@@ -66,7 +79,7 @@ def parse(argv=None):
     p.add_argument("--no-ceiling", action="store_true", help="skip that measurement (peak_at_power_cap is then null: no constant stands in)")
     p.add_argument("--cpu-frames", type=int, default=100,
                    help="frames of the CPU baseline sample: one minibatch of the reference's own size (SN/apply.py:398-450: 100), 10-15 s of CPU work")
-    p.add_argument("--cpu-threads", type=int, default=0, help="0 = min(host cores, 64)")
+    p.add_argument("--cpu-threads", type=int, default=0, help="0 = OMP_NUM_THREADS if set, else min(host cores, 64)")
     p.add_argument("--force-dist", action="store_true",
                    help="initialise the process group and run the all-gather and barriers even at world size 1 "
                         "(RCCL smoke on a one-GPU box; launch under torch.distributed.run --nproc-per-node 1)")
@@ -79,7 +92,10 @@ def parse(argv=None):
                    help="test hook: this rank exits with code 3 before it joins the process group")
     p.add_argument("--debug-hang-rank", type=int, default=-1,
                    help="test hook: this rank sleeps instead of starting (a rank stuck at communicator initialisation)")
-    return p.parse_args(argv)
+    a = p.parse_args(argv)
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
 
 
 def make_batch(kind, rank, clips, seconds, distinct):
@@ -100,10 +116,39 @@ def make_batch(kind, rank, clips, seconds, distinct):
     return rep(mixes), rep(ca), rep(cb), distinct
 
 
+def dump_outputs(out_dir, wav, off):
+    """--dump-outputs: what a caller of the timed path receives -- the denoised waveforms, one flat float32 tensor with
+    clip i at wav[off[i]:off[i + 1]] -- as DIR/denoised_wav.npy (the kept clips, whole, concatenated in clip order) and
+    DIR/denoised_wav_clips.npy (their indices, float64).  Every clip is kept while the batch fits DUMP_BUDGET_BYTES;
+    otherwise clips are taken in a fixed seeded order while they fit (a clip longer than the whole budget: its head)."""
+    n = len(off) - 1
+    order = np.random.default_rng(DUMP_SEED).permutation(n)
+    keep, room = [], DUMP_BUDGET_BYTES // 4
+    for i in order:
+        if off[i + 1] - off[i] <= room:
+            keep.append(int(i))
+            room -= off[i + 1] - off[i]
+    keep.sort()
+    if keep:
+        parts = [wav[off[i]:off[i + 1]] for i in keep]
+    else:
+        keep, parts = [int(order[0])], [wav[off[order[0]]:off[order[0]] + room]]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "denoised_wav.npy"), torch.cat(parts).cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "denoised_wav_clips.npy"), np.asarray(keep, dtype=np.float64))
+    return keep
+
+
+def _cpu_threads(threads):
+    """--cpu-threads, else the OMP_NUM_THREADS the process was given, else min(host cores, 64)."""
+    omp = os.environ.get("OMP_NUM_THREADS", "").split(",")[0]
+    return threads or (int(omp) if omp.isdigit() else 0) or min(os.cpu_count() or 1, 64)
+
+
 def cpu_baseline(W, kind, mix, ca, cb, frames, threads):
     """Reference-faithful float32 CPU path (oracle/torch_ref.py) on a bounded sample of the workload."""
     from oracle.torch_ref import TorchRef
-    torch.set_num_threads(threads or min(os.cpu_count() or 1, 64))
+    torch.set_num_threads(_cpu_threads(threads))
     ref = TorchRef(W, kind, torch.float32)
     t0 = time.time()
     out = ref.enhance(mix, ca, cb, faithful=True, mb=frames, max_batches=1)
@@ -222,7 +267,7 @@ def rms_check(W, kind, eng, threads):
     """Whole-waveform RMS of the HIP path against the float32 CPU restatement on a FULL short clip
     (0.5 s = 48 frames: every frame, both clip edges, the complete overlap-add)."""
     from oracle.torch_ref import TorchRef
-    torch.set_num_threads(threads or min(os.cpu_count() or 1, 64))
+    torch.set_num_threads(_cpu_threads(threads))
     cid = 4242
     mix = trim_to_frames(normalise(synth.mixture(cid, 0.5)))
     if kind == "denoiser":
@@ -235,6 +280,111 @@ def rms_check(W, kind, eng, threads):
     return {"rms": float(np.sqrt(np.mean((got - ref) ** 2))), "samples": int(len(ref)),
             "clip": "full 0.5 s synthetic clip (48 frames), HIP waveform vs float32 torch-CPU restatement",
             "tolerance": 1e-3}
+
+
+def kernel_figures(a, prof, kpass_ms, ceiling, ms_step):
+    """--full: `roofline`, `hbm_kernels` and `kernel_ms_per_step` of the line, from the per-kernel pass (prof: the
+    library's profile of that pass) and the power-cap ceiling measured after it."""
+    cap_tf = ceiling["sustained_tflops"] if ceiling else None
+    convs = {k: v for k, v in prof.items() if k.startswith(("conv_igemm", "conv_wino", "conv_1x1"))}
+    conv_ms = sum(v["ms"] for v in convs.values())
+    conv_fl = sum(v["flops"] for v in convs.values())
+    conv_calls = sum(v["calls"] for v in convs.values())
+    peak = F16_MFMA_PEAK_TFLOPS if a.precision == "f16x3" else F32_MFMA_PEAK_TFLOPS
+    tflops = conv_fl / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+    # FLOPs the matrix cores executed: 3 f16 products per MAC in split mode, and 2.5 x fewer MACs than the direct
+    # form for the convs that run as 1-D Winograd (the library counts them per launch)
+    exec_tflops = sum(v.get("mfma_flops", 0.0) for v in convs.values()) / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+    # HBM bytes per conv launch: PMC counters cannot be read from inside this process; the committed summary of the
+    # separate rocprofv3 --pmc passes over this very command (tools/gpu_session.sh pmc; profiles/rNN/README.md) is quoted when the workload is
+    # the one it was collected on AND the kernel sources are the ones it was collected from (the summary carries a
+    # fingerprint of n-hans_amd/csrc + fold.py, tools/pmc_summary.py): a kernel change makes `traffic` null instead of
+    # silently stale
+    traffic, traffic_src, dom_traffic = None, None, None
+    # the DOMINANT kernel of the step (most milliseconds among the conv launches): what `roofline`'s own fields describe;
+    # the aggregate over all conv launches stands beside it as `all_conv_launches`
+    dom = max(convs, key=lambda k: convs[k]["ms"]) if convs else None
+    # bench label -> does a PMC-summary kernel name belong to it
+    pmc_match = {"conv_wino<128>": lambda n: "conv_wino<" in n,
+                 "conv_igemm_halo<128>": lambda n: "conv_igemm_halo<128" in n and n.rstrip().endswith(", 0>"),
+                 "conv_igemm_halo_pw<128>": lambda n: "conv_igemm_halo<128" in n and n.rstrip().endswith(", 1>")}
+    import glob
+    pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9]*", PMC_SUMMARY_NAME)), reverse=True)
+    if a.precision == "f16x3" and a.clips_per_gpu == 256 and a.seconds == 10.0 and a.kind == "denoiser" and pmcs:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        from pmc_summary import kernel_source_sha16
+        sha = kernel_source_sha16(ROOT)
+        summary, meta, PMC_SUMMARY = None, {}, os.path.relpath(pmcs[0], ROOT)
+        for f in pmcs:                       # newest round first
+            cand = json.load(open(f))
+            m = cand.pop("_meta", {})
+            if m.get("kernel_source_sha16") == sha:
+                summary, meta, PMC_SUMMARY = cand, m, os.path.relpath(f, ROOT)
+                break
+        if summary is None:
+            traffic_src = "%s (the newest PMC summary) is of other kernel sources: not quoted" % PMC_SUMMARY
+        else:
+            per_launch = lambda rows: (sum((v.get("derived_hbm_read_bytes_per_launch", 0.0) + v.get("derived_hbm_write_bytes_per_launch", 0.0))
+                                           * v.get("dispatches_pass_c", 0) for v in rows) / max(1, sum(v.get("dispatches_pass_c", 0) for v in rows)))
+            rows = [v for k, v in summary.items() if "conv_igemm" in k or "conv_wino" in k]
+            if sum(v.get("dispatches_pass_c", 0) for v in rows):
+                traffic = per_launch(rows)
+                traffic_src = "%s (FETCH_SIZE x2 + WRITE_SIZE, bytes per launch; commit %s)" % (PMC_SUMMARY, meta.get("commit"))
+            drows = [v for k, v in summary.items() if dom in pmc_match and pmc_match[dom](k)]
+            if sum(v.get("dispatches_pass_c", 0) for v in drows):
+                dom_traffic = per_launch(drows)
+    gbs = lambda e: e["bytes"] / (e["ms"] * 1e-3) / 1e9 if e and e["ms"] > 0 else None
+    # stft_features = the mixture's STFT (log-magnitude + phase: the 2,248 B/frame of SURVEY 8d); the two
+    # context STFTs (200 frames per clip, log-magnitude only: 1,444 B/frame) are timed as their own entry
+    stft_gbs, istft_gbs = gbs(prof.get("stft_features")), gbs(prof.get("istft_ola"))
+    stft_ctx_gbs = gbs(prof.get("stft_context_features"))
+    step_flops = conv_fl + sum(v["flops"] for k, v in prof.items() if k.startswith("direct_conv"))
+    dtf = lambda k: convs[k]["flops"] / (convs[k]["ms"] * 1e-3) / 1e12 if k and convs[k]["ms"] > 0 else None
+    dexec = lambda k: convs[k].get("mfma_flops", 0.0) / (convs[k]["ms"] * 1e-3) / 1e12 if k and convs[k]["ms"] > 0 else None
+    return {
+        "roofline": {"bound": "mfma", "kernel": dom,
+                     "kernel_share_of_step": (convs[dom]["ms"] / ms_step) if dom else None,
+                     "achieved_basis": "ALGORITHMIC FLOPs of the direct convolutions this kernel's launches stand for (2*M*K*N per "
+                                       "launch, whichever form runs them) / the launches' summed duration",
+                     "achieved": dtf(dom), "peak": peak, "unit": "TFLOP/s", "frac": (dtf(dom) or 0.0) / peak,
+                     "traffic": dom_traffic, "traffic_source": traffic_src,
+                     "launches": convs[dom]["calls"] if dom else 0, "kernel_ms_per_step": convs[dom]["ms"] if dom else None,
+                     "avg_launch_ms": convs[dom]["ms"] / convs[dom]["calls"] if dom else None,
+                     "algorithmic_gflop_per_launch": convs[dom]["flops"] / convs[dom]["calls"] / 1e9 if dom else None,
+                     "executed_tflops": dexec(dom),
+                     "executed_frac": (dexec(dom) or 0.0) / peak,
+                     # every implicit-GEMM / Winograd conv launch of a step together (97 % of the step)
+                     "all_conv_launches": {"achieved": tflops, "frac": tflops / peak, "traffic": traffic, "launches": conv_calls,
+                                           "kernel_ms_per_step": conv_ms, "avg_launch_ms": conv_ms / conv_calls if conv_calls else None,
+                                           "algorithmic_gflop_per_launch": conv_fl / conv_calls / 1e9 if conv_calls else None,
+                                           "executed_tflops": exec_tflops, "executed_frac": exec_tflops / peak,
+                                           "executed_frac_of_peak_at_power_cap": exec_tflops / cap_tf if cap_tf else None},
+                     # what back-to-back f16 MFMAs on random register operands sustain at the socket power cap
+                     # (tools/ubench/mfma_power.hip, profiles/r02/mfma_power_ceiling.txt); the datasheet peak is
+                     # reached with all-zero operands only
+                     "peak_at_power_cap": cap_tf,
+                     "executed_frac_of_peak_at_power_cap": (dexec(dom) or 0.0) / cap_tf if cap_tf else None,
+                     "peak_at_power_cap_source": ("measured in this run on this device: %.1f s of back-to-back "
+                                                  "v_mfma_f32_32x32x16_f16 on random register operands after the timed "
+                                                  "region (nhans_debug_mfma_ceiling)" % a.ceiling_seconds) if ceiling
+                     else "not measured (--no-ceiling or f32 mode): no constant stands in for it",
+                     "peak_at_power_cap_run": ceiling,
+                     "source": "hipEvents around every launch in one extra pass after the timed region (%.1f ms wall)"
+                               % (kpass_ms or 0.0),
+                     # the same algorithmic FLOPs over the UNPROFILED timed step (all kernels, launch gaps): lower bound
+                     "step_level_tflops": step_flops / (ms_step * 1e-3) / 1e12 if step_flops else None,
+                     "per_kernel": {k: {"ms": v["ms"], "launches": v["calls"],
+                                        "tflops": v["flops"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] > 0 else None,
+                                        "executed_tflops": v.get("mfma_flops", 0.0) / (v["ms"] * 1e-3) / 1e12 if v["ms"] > 0 else None}
+                                    for k, v in sorted(convs.items())}},
+        "hbm_kernels": {"stft_features_GBs": stft_gbs, "istft_ola_GBs": istft_gbs, "stft_context_features_GBs": stft_ctx_gbs,
+                        "peak_GBs": HBM_PEAK_GBS,
+                        "achievable_GBs": HBM_ACHIEVABLE_GBS,
+                        "stft_frac_of_achievable": stft_gbs / HBM_ACHIEVABLE_GBS if stft_gbs else None,
+                        "istft_frac_of_achievable": istft_gbs / HBM_ACHIEVABLE_GBS if istft_gbs else None,
+                        "bytes_per_frame": 2248},
+        "kernel_ms_per_step": {k: v["ms"] for k, v in sorted(prof.items())},
+    }
 
 
 def launch_ranks(a, argv):
@@ -323,11 +473,11 @@ def main(argv=None):
             dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
-    # "did RCCL see N ranks, one per GPU?" answerable from the JSON line: the process group's backend, its size, this
+    # "did RCCL see N ranks, one per GPU?" answerable from the JSON line (--full): the process group's backend, its size, this
     # node's device count and every rank's (device index, PCI address) -- N > 1 without --share-device0 must show the
     # nccl (= RCCL on ROCm) backend and N distinct devices
     rccl_ranks = None
-    if use_dist:
+    if use_dist and a.full:
         p = torch.cuda.get_device_properties(local)
         mine = {"rank": rank, "device": local, "pci": "%04x:%02x:%02x" % (p.pci_domain_id, p.pci_bus_id, p.pci_device_id)}
         who = [None] * world
@@ -370,7 +520,7 @@ def main(argv=None):
     torch.cuda.synchronize()
     # (every rank samples its own socket: eight sockets at 1.3 kW do not hold the same clock, and the whole-job number
     # is the slowest rank's -- the per-rank figures travel to rank 0 after the timed region, see `per_rank` below)
-    sampler = DeviceSampler(local) if (rank == 0 or not a.share_device0) else None
+    sampler = DeviceSampler(local) if a.full and (rank == 0 or not a.share_device0) else None
     if sampler:
         sampler.start()
     t0 = time.perf_counter()
@@ -383,15 +533,19 @@ def main(argv=None):
     dt = time.perf_counter() - t0
     device_state = sampler.stop() if sampler else None
     status = eng.take_status()                  # sticky: covers every step above
-    golden_rms = rms_golden_10s(a.kind, rank, a, res["denoised_wav"], mix_off) if a.steps > 0 else None
+    golden_rms = rms_golden_10s(a.kind, rank, a, res["denoised_wav"], mix_off) if a.full else None
     if use_dist:
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if a.share_device0 else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if a.dump_outputs and rank == 0:
+        # (N > 1: the all-gathered batch of the whole job, rank r's clips after rank r - 1's)
+        out_off = [r * mix_off[-1] + o for r in range(world) for o in mix_off[:-1]] + [world * mix_off[-1]]
+        dump_outputs(a.dump_outputs, gathered if use_dist else res["denoised_wav"], out_off)
 
     # per-kernel pass: the same step once more with the library's hipEvent brackets on
     prof, kpass_ms = {}, None
-    if rank == 0 and not a.no_kernel_pass:
+    if rank == 0 and a.full and not a.no_kernel_pass:
         eng.set_option("profile", 1)
         eng.profile_reset()
         torch.cuda.synchronize()
@@ -406,7 +560,7 @@ def main(argv=None):
     # socket is still warm: register-only v_mfma_f32_32x32x16_f16 on random operands (nhans_debug_mfma_ceiling)
     # (N > 1: every rank measures its own socket, all at the same time -- the condition the timed region ran under)
     ceiling = None
-    if (rank == 0 or not a.share_device0) and a.precision == "f16x3" and not a.no_ceiling:
+    if a.full and (rank == 0 or not a.share_device0) and a.precision == "f16x3" and not a.no_ceiling:
         from nhans_amd import hip as nh
         if use_dist and not a.share_device0:
             dist.barrier()                      # (all sockets start together)
@@ -427,62 +581,6 @@ def main(argv=None):
 
     if rank == 0:
         ms_step = 1e3 * dt / a.steps
-        cap_tf = ceiling["sustained_tflops"] if ceiling else None
-        convs = {k: v for k, v in prof.items() if k.startswith(("conv_igemm", "conv_wino", "conv_1x1"))}
-        conv_ms = sum(v["ms"] for v in convs.values())
-        conv_fl = sum(v["flops"] for v in convs.values())
-        conv_calls = sum(v["calls"] for v in convs.values())
-        peak = F16_MFMA_PEAK_TFLOPS if a.precision == "f16x3" else F32_MFMA_PEAK_TFLOPS
-        tflops = conv_fl / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-        # FLOPs the matrix cores executed: 3 f16 products per MAC in split mode, and 2.5 x fewer MACs than the direct
-        # form for the convs that run as 1-D Winograd (the library counts them per launch)
-        exec_tflops = sum(v.get("mfma_flops", 0.0) for v in convs.values()) / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-        # HBM bytes per conv launch: PMC counters cannot be read from inside this process; the committed summary of the
-        # separate rocprofv3 --pmc passes over this very command (tools/gpu_session.sh pmc; profiles/rNN/README.md) is quoted when the workload is
-        # the one it was collected on AND the kernel sources are the ones it was collected from (the summary carries a
-        # fingerprint of n-hans_amd/csrc + fold.py, tools/pmc_summary.py): a kernel change makes `traffic` null instead of
-        # silently stale
-        traffic, traffic_src, dom_traffic = None, None, None
-        # the DOMINANT kernel of the step (most milliseconds among the conv launches): what `roofline`'s own fields describe;
-        # the aggregate over all conv launches stands beside it as `all_conv_launches`
-        dom = max(convs, key=lambda k: convs[k]["ms"]) if convs else None
-        # bench label -> does a PMC-summary kernel name belong to it
-        pmc_match = {"conv_wino<128>": lambda n: "conv_wino<" in n,
-                     "conv_igemm_halo<128>": lambda n: "conv_igemm_halo<128" in n and n.rstrip().endswith(", 0>"),
-                     "conv_igemm_halo_pw<128>": lambda n: "conv_igemm_halo<128" in n and n.rstrip().endswith(", 1>")}
-        import glob
-        pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9]*", PMC_SUMMARY_NAME)), reverse=True)
-        if a.precision == "f16x3" and a.clips_per_gpu == 256 and a.seconds == 10.0 and a.kind == "denoiser" and pmcs:
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            from pmc_summary import kernel_source_sha16
-            sha = kernel_source_sha16(ROOT)
-            summary, meta, PMC_SUMMARY = None, {}, os.path.relpath(pmcs[0], ROOT)
-            for f in pmcs:                       # newest round first
-                cand = json.load(open(f))
-                m = cand.pop("_meta", {})
-                if m.get("kernel_source_sha16") == sha:
-                    summary, meta, PMC_SUMMARY = cand, m, os.path.relpath(f, ROOT)
-                    break
-            if summary is None:
-                traffic_src = "%s (the newest PMC summary) is of other kernel sources: not quoted" % PMC_SUMMARY
-            else:
-                per_launch = lambda rows: (sum((v.get("derived_hbm_read_bytes_per_launch", 0.0) + v.get("derived_hbm_write_bytes_per_launch", 0.0))
-                                               * v.get("dispatches_pass_c", 0) for v in rows) / max(1, sum(v.get("dispatches_pass_c", 0) for v in rows)))
-                rows = [v for k, v in summary.items() if "conv_igemm" in k or "conv_wino" in k]
-                if sum(v.get("dispatches_pass_c", 0) for v in rows):
-                    traffic = per_launch(rows)
-                    traffic_src = "%s (FETCH_SIZE x2 + WRITE_SIZE, bytes per launch; commit %s)" % (PMC_SUMMARY, meta.get("commit"))
-                drows = [v for k, v in summary.items() if dom in pmc_match and pmc_match[dom](k)]
-                if sum(v.get("dispatches_pass_c", 0) for v in drows):
-                    dom_traffic = per_launch(drows)
-        gbs = lambda e: e["bytes"] / (e["ms"] * 1e-3) / 1e9 if e and e["ms"] > 0 else None
-        # stft_features = the mixture's STFT (log-magnitude + phase: the 2,248 B/frame of SURVEY 8d); the two
-        # context STFTs (200 frames per clip, log-magnitude only: 1,444 B/frame) are timed as their own entry
-        stft_gbs, istft_gbs = gbs(prof.get("stft_features")), gbs(prof.get("istft_ola"))
-        stft_ctx_gbs = gbs(prof.get("stft_context_features"))
-        step_flops = conv_fl + sum(v["flops"] for k, v in prof.items() if k.startswith("direct_conv"))
-        dtf = lambda k: convs[k]["flops"] / (convs[k]["ms"] * 1e-3) / 1e12 if k and convs[k]["ms"] > 0 else None
-        dexec = lambda k: convs[k].get("mfma_flops", 0.0) / (convs[k]["ms"] * 1e-3) / 1e12 if k and convs[k]["ms"] > 0 else None
         line = {
             "metric": "denoised audio seconds per second (16 kHz), whole job",
             "value": world * audio_s * a.steps / dt,
@@ -500,61 +598,19 @@ def main(argv=None):
             "frames_per_s": world * frames * a.steps / dt,
             "x_realtime_per_gpu": audio_s * a.steps / dt,
             "status_flags": status if per_rank is None else max(r["status_flags"] for r in per_rank),
-            "device_state": device_state,
             # N > 1: each rank's own time for its steps (the whole-job value above is the slowest rank's, barrier to
-            # barrier), the clock and power its socket held and the f16 matrix rate it sustains at its cap
+            # barrier); with --full also the clock and power its socket held and the f16 matrix rate it sustains at its cap
             "per_rank": per_rank,
-            "rccl_ranks": rccl_ranks,
-            # accuracy of the measured output itself: the golden 10 s clip is part of the timed batch
-            "rms_vs_golden_10s": golden_rms,
-            "roofline": {"bound": "mfma", "kernel": dom,
-                         "kernel_share_of_step": (convs[dom]["ms"] / ms_step) if dom else None,
-                         "achieved_basis": "ALGORITHMIC FLOPs of the direct convolutions this kernel's launches stand for (2*M*K*N per "
-                                           "launch, whichever form runs them) / the launches' summed duration",
-                         "achieved": dtf(dom), "peak": peak, "unit": "TFLOP/s", "frac": (dtf(dom) or 0.0) / peak,
-                         "traffic": dom_traffic, "traffic_source": traffic_src,
-                         "launches": convs[dom]["calls"] if dom else 0, "kernel_ms_per_step": convs[dom]["ms"] if dom else None,
-                         "avg_launch_ms": convs[dom]["ms"] / convs[dom]["calls"] if dom else None,
-                         "algorithmic_gflop_per_launch": convs[dom]["flops"] / convs[dom]["calls"] / 1e9 if dom else None,
-                         "executed_tflops": dexec(dom),
-                         "executed_frac": (dexec(dom) or 0.0) / peak,
-                         # every implicit-GEMM / Winograd conv launch of a step together (97 % of the step)
-                         "all_conv_launches": {"achieved": tflops, "frac": tflops / peak, "traffic": traffic, "launches": conv_calls,
-                                               "kernel_ms_per_step": conv_ms, "avg_launch_ms": conv_ms / conv_calls if conv_calls else None,
-                                               "algorithmic_gflop_per_launch": conv_fl / conv_calls / 1e9 if conv_calls else None,
-                                               "executed_tflops": exec_tflops, "executed_frac": exec_tflops / peak,
-                                               "executed_frac_of_peak_at_power_cap": exec_tflops / cap_tf if cap_tf else None},
-                         # what back-to-back f16 MFMAs on random register operands sustain at the socket power cap
-                         # (tools/ubench/mfma_power.hip, profiles/r02/mfma_power_ceiling.txt); the datasheet peak is
-                         # reached with all-zero operands only
-                         "peak_at_power_cap": cap_tf,
-                         "executed_frac_of_peak_at_power_cap": (dexec(dom) or 0.0) / cap_tf if cap_tf else None,
-                         "peak_at_power_cap_source": ("measured in this run on this device: %.1f s of back-to-back "
-                                                      "v_mfma_f32_32x32x16_f16 on random register operands after the timed "
-                                                      "region (nhans_debug_mfma_ceiling)" % a.ceiling_seconds) if ceiling
-                         else "not measured (--no-ceiling or f32 mode): no constant stands in for it",
-                         "peak_at_power_cap_run": ceiling,
-                         "source": "hipEvents around every launch in one extra pass after the timed region (%.1f ms wall)"
-                                   % (kpass_ms or 0.0),
-                         # the same algorithmic FLOPs over the UNPROFILED timed step (all kernels, launch gaps): lower bound
-                         "step_level_tflops": step_flops / (ms_step * 1e-3) / 1e12 if step_flops else None,
-                         "per_kernel": {k: {"ms": v["ms"], "launches": v["calls"],
-                                            "tflops": v["flops"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] > 0 else None,
-                                            "executed_tflops": v.get("mfma_flops", 0.0) / (v["ms"] * 1e-3) / 1e12 if v["ms"] > 0 else None}
-                                        for k, v in sorted(convs.items())}},
-            "hbm_kernels": {"stft_features_GBs": stft_gbs, "istft_ola_GBs": istft_gbs, "stft_context_features_GBs": stft_ctx_gbs,
-                            "peak_GBs": HBM_PEAK_GBS,
-                            "achievable_GBs": HBM_ACHIEVABLE_GBS,
-                            "stft_frac_of_achievable": stft_gbs / HBM_ACHIEVABLE_GBS if stft_gbs else None,
-                            "istft_frac_of_achievable": istft_gbs / HBM_ACHIEVABLE_GBS if istft_gbs else None,
-                            "bytes_per_frame": 2248},
-            "kernel_ms_per_step": {k: v["ms"] for k, v in sorted(prof.items())},
         }
-        if world == 1 and not a.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(W, a.kind, mixes[0], ca[0], cb[0], a.cpu_frames, a.cpu_threads)
-            chk = rms_check(W, a.kind, eng, a.cpu_threads)
-            line["rms_vs_cpu_f32"] = chk["rms"]
-            line["rms_check"] = chk
+        if a.full:
+            # accuracy of the measured output itself: the golden 10 s clip is part of the timed batch
+            line.update(device_state=device_state, rccl_ranks=rccl_ranks, rms_vs_golden_10s=golden_rms)
+            line.update(kernel_figures(a, prof, kpass_ms, ceiling, ms_step))
+            if world == 1 and not a.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(W, a.kind, mixes[0], ca[0], cb[0], a.cpu_frames, a.cpu_threads)
+                chk = rms_check(W, a.kind, eng, a.cpu_threads)
+                line["rms_vs_cpu_f32"] = chk["rms"]
+                line["rms_check"] = chk
         print(json.dumps(line), flush=True)
     if use_dist:
         dist.barrier()

@@ -410,10 +410,13 @@ def test_separator_mixing_and_trim_quirk():
 def test_bench_device_sampler_degrades_to_none_and_reads_hwmon(tmp_path, monkeypatch):
     """bench.py's clock/power sampler: no GPU / no hwmon files -> device_state null (never an exception); with
     hwmon-shaped files it averages freq1_input (Hz) and power1_input (uW)."""
+    import glob
     import sys
     import time
     sys.path.insert(0, ROOT)
     import bench
+    # (no amdgpu hwmon files to be found, also on a box that has them: a GPU box runs this test too)
+    monkeypatch.setattr(glob, "glob", lambda pattern: [])
     s = bench.DeviceSampler(0)
     s.start()
     assert s.stop() is None
@@ -468,6 +471,48 @@ def test_bench_self_launcher_ends_the_siblings_of_a_dead_rank(monkeypatch, capfd
     assert bench.main(["--gpus", "2", "--debug-hang-rank", "0", "--debug-fail-rank", "-1", "--rank-timeout", "2"]) == 1
     err = capfd.readouterr().err
     assert "rank(s) failed" in err and time.time() - t0 < 60
+
+
+def test_bench_options_full_dump_outputs_and_steps():
+    """--full is off by default, --dump-outputs takes a directory, --steps below 1 is refused."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_bench_dump_outputs_is_a_seeded_sample_of_whole_clips(tmp_path, monkeypatch):
+    """bench.dump_outputs: every clip while the batch fits the budget; above it, whole clips chosen in a fixed seeded
+    order while they fit (the same ones on every call), float32 waveform + float64 clip indices; a clip longer than the
+    whole budget is cut to it."""
+    import sys
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    bench._rank_imports()
+    lens = [100 + 7 * i for i in range(30)]
+    off = [0]
+    for n in lens:
+        off.append(off[-1] + n)
+    wav = torch.arange(off[-1], dtype=torch.float32)
+    keep = bench.dump_outputs(str(tmp_path / "all"), wav, off)
+    assert keep == list(range(30))
+    got = np.load(tmp_path / "all" / "denoised_wav.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, wav.numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 1000)
+    keep = bench.dump_outputs(str(tmp_path / "a"), wav, off)
+    assert keep == sorted(keep) and 0 < len(keep) < 30 and keep == bench.dump_outputs(str(tmp_path / "b"), wav, off)
+    got = np.load(tmp_path / "a" / "denoised_wav.npy")
+    clips = np.load(tmp_path / "a" / "denoised_wav_clips.npy")
+    assert clips.dtype == np.float64 and clips.tolist() == keep and got.nbytes <= 4 * 1000
+    assert np.array_equal(got, np.concatenate([wav.numpy()[off[i]:off[i + 1]] for i in keep]))
+    keep = bench.dump_outputs(str(tmp_path / "c"), wav, [0, 5000])
+    assert keep == [0] and np.array_equal(np.load(tmp_path / "c" / "denoised_wav.npy"), wav.numpy()[:1000])
 
 
 # ------------------------------------------------------------------------------ Winograd folding (conv_wino.hip)

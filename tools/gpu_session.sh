@@ -3,6 +3,7 @@
 # command.  Usage (from the repo root, through gpurun):  bash tools/gpu_session.sh <tag> [what...]
 #   what: tests bench bench1 prof pmc benchq dist1 cli cold soak fuzz recipes driver  (default: tests bench prof)
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-s}; shift || true
 WHAT=${*:-tests bench prof}
 OUT=gpurun_out/$TAG
@@ -14,15 +15,15 @@ if has tests; then
   tail -5 $OUT/pytest_gpu.log
 fi
 if has bench; then
-  timeout 1200 python bench.py --steps 3 --warmup 1 > $OUT/bench_256.json 2> $OUT/bench_256.err; echo "bench rc=$?"
+  timeout 1200 python bench.py --steps 3 --warmup 1 --full > $OUT/bench_256.json 2> $OUT/bench_256.err; echo "bench rc=$?"
   tail -c 3000 $OUT/bench_256.json
 fi
 if has bench1; then
-  timeout 600 python bench.py --steps 10 --warmup 3 --clips-per-gpu 1 --no-cpu-baseline > $OUT/bench_1clip.json 2> $OUT/bench_1clip.err; echo "bench1 rc=$?"
-  timeout 900 python bench.py --steps 2 --warmup 1 --kind separator --no-cpu-baseline > $OUT/bench_separator_256.json 2> $OUT/bench_separator.err; echo "benchsep rc=$?"
+  timeout 600 python bench.py --steps 10 --warmup 3 --clips-per-gpu 1 --full --no-cpu-baseline > $OUT/bench_1clip.json 2> $OUT/bench_1clip.err; echo "bench1 rc=$?"
+  timeout 900 python bench.py --steps 2 --warmup 1 --kind separator --full --no-cpu-baseline > $OUT/bench_separator_256.json 2> $OUT/bench_separator.err; echo "benchsep rc=$?"
 fi
 if has prof; then
-  (cd /tmp && timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -- python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline > $GRAFT_REPO_ROOT/$OUT/prof_bench.json 2> $GRAFT_REPO_ROOT/$OUT/prof_bench.err); echo "rocprof rc=$?"
+  (cd /tmp && timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -- python3 $ROOT/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline > $ROOT/$OUT/prof_bench.json 2> $ROOT/$OUT/prof_bench.err); echo "rocprof rc=$?"
   find /tmp/prof_kt -name "*kernel_stats.csv" -exec cp {} $OUT/rocprofv3_kernel_stats_bench_256clips.csv \;
   head -20 $OUT/rocprofv3_kernel_stats_bench_256clips.csv
 fi
@@ -36,17 +37,17 @@ fi
 if has benchq; then
   # the headline line once more, now that the PMC summary of THESE kernel sources exists: roofline.traffic is quoted
   mkdir -p profiles/$TAG && cp $OUT/pmc_summary_bench_256clips.json profiles/$TAG/pmc_summary_bench_256clips.json
-  timeout 1200 python bench.py --steps 3 --warmup 1 > $OUT/bench_256_with_traffic.json 2> $OUT/bench_256_with_traffic.err; echo "benchq rc=$?"
+  timeout 1200 python bench.py --steps 3 --warmup 1 --full > $OUT/bench_256_with_traffic.json 2> $OUT/bench_256_with_traffic.err; echo "benchq rc=$?"
   tail -c 1200 $OUT/bench_256_with_traffic.json
 fi
 if has dist1; then
   # the world > 1 branch of bench.py on the one GPU there is: 2 ranks share device 0, gloo all-gather
   timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-      bench.py --gpus 2 --steps 2 --warmup 1 --clips-per-gpu 8 --share-device0 --no-kernel-pass > $OUT/bench_2ranks_shared.json 2> $OUT/bench_2ranks_shared.err; echo "dist1 rc=$?"
+      bench.py --gpus 2 --steps 2 --warmup 1 --clips-per-gpu 8 --share-device0 --full --no-kernel-pass > $OUT/bench_2ranks_shared.json 2> $OUT/bench_2ranks_shared.err; echo "dist1 rc=$?"
   tail -c 1500 $OUT/bench_2ranks_shared.json
   # and its RCCL leg with the one rank a one-GPU box allows (communicator init, all-gather, barriers, all-reduce)
   timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 \
-      bench.py --gpus 1 --steps 2 --warmup 1 --clips-per-gpu 16 --force-dist --no-cpu-baseline > $OUT/bench_rccl_1rank.json 2> $OUT/bench_rccl_1rank.err; echo "rccl1 rc=$?"
+      bench.py --gpus 1 --steps 2 --warmup 1 --clips-per-gpu 16 --force-dist --full --no-cpu-baseline > $OUT/bench_rccl_1rank.json 2> $OUT/bench_rccl_1rank.err; echo "rccl1 rc=$?"
 fi
 if has cli; then      # files in -> files out through the command line, 256 wavs (first call and steady state)
   timeout 900 python tools/cli_e2e.py 256 10 > $OUT/cli_e2e_256clips.log 2>&1; tail -c 1200 $OUT/cli_e2e_256clips.log
