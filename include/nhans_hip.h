@@ -231,6 +231,57 @@ int nhans_debug_mfma_ceiling(double seconds, void* stream, double* sustained_tfl
  * verifies the 116 MB data shard with it (BundleEntryProto field 6 of the reference's shipped trained_model .index files). */
 uint32_t nhans_crc32c(uint32_t crc, const void* data_host, size_t nbytes);
 
+/* ---- Online enhancement: live recordings pushed piece by piece, bit-identical to offline ----------------------------
+ * One object holds S live recordings ("online streams", not to be confused with the hipStream_t `stream` argument) of
+ * one context; every push moves all S through the GPU together.  Every output frame depends only on its 35-frame window
+ * of the log-magnitude spectrogram (17 frames back, 17 ahead) and on the two conditioning embeddings, the STFT computes
+ * each frame on its own and the iSTFT sums each output sample from its <= 3 frames in a fixed order, so the online
+ * output is BIT FOR BIT what nhans_enhance_clips computes for the same samples trimmed by the offline rule.
+ *
+ * Output contract, per online stream.  N = samples pushed so far, T = nhans_num_frames(N), R = max(0, T - 17) (the
+ * frames whose window is complete), P = R rounded down to an even number.  Until the stream ends, the samples emitted
+ * so far number 160 * P; once it has ended they number (T - 1) * 160 + 400, or 0 if T = 0 -- the offline output length
+ * of the input trimmed to whole frames (the samples of an incomplete last hop are dropped, as offline).  P is even
+ * because the offline iSTFT transforms frames in pairs (2k, 2k+1) of the clip: a frame is synthesised with the offline
+ * bits once its partner exists or the stream has ended.  Algorithmic latency: the 17-frame look-ahead plus one window,
+ * 185 - 205 ms at 16 kHz.
+ *
+ * Calls on the context stay ordered as every other call is (see the top of this file): offline calls and other online
+ * objects of the same context may be interleaved with pushes.  A push whose ready frames exceed "frames_per_chunk" runs
+ * the stack in several passes inside the call.  The object owns its state (about 89 KB per online stream, twice: the
+ * slot a push reads and the slot it writes) and the embeddings; the context's workspace serves each push while it runs.
+ * Objects are closed (nhans_online_close) BEFORE nhans_destroy(ctx). */
+typedef struct nhans_online nhans_online;
+
+/* Opens an object of `nstreams` (>= 1) online streams.  Stream i is conditioned on clips i of ctx_a / ctx_b, with the
+ * rules of nhans_enhance_clips: at least 32,240 samples (else NHANS_ESHORT), only the first 200 frames used, the same
+ * (a, b) order.  The embedding towers run here, once per stream.  want_mixed != 0: pushes also write the
+ * *mixed_processed round trip. */
+int nhans_online_open(nhans_ctx* ctx, int nstreams, const float* ctx_a_wav_dev, const int64_t* ctx_a_offsets_host,
+                      const float* ctx_b_wav_dev, const int64_t* ctx_b_offsets_host, int want_mixed, void* stream,
+                      nhans_online** out);
+
+/* Appends in_offsets_host[i+1] - in_offsets_host[i] (>= 0) normalised float32 samples of in_dev to stream i; end_host
+ * (nullable) != 0 ends stream i after them.  Writes every output sample that is now final: out_counts_host[i] samples
+ * at den_out_dev + out_offsets_host[i] (and, with want_mixed, at mixed_out_dev + out_offsets_host[i]); the caller's
+ * room out_offsets_host[i+1] - out_offsets_host[i] must hold them (nhans_online_out_counts), else NHANS_EINVAL.
+ * Pushing to an ended stream, a negative count or a NULL that is needed: NHANS_EINVAL, and nothing changes. */
+int nhans_online_push(nhans_online* obj, const float* in_dev, const int64_t* in_offsets_host, const int* end_host,
+                      float* den_out_dev, float* mixed_out_dev, const int64_t* out_offsets_host,
+                      int64_t* out_counts_host, void* stream);
+
+/* The counts a push of in_counts_host[i] samples (end_host nullable) would report, on the host, without touching the
+ * device: what a caller sizes its output buffers with. */
+int nhans_online_out_counts(const nhans_online* obj, const int64_t* in_counts_host, const int* end_host,
+                            int64_t* out_counts_host);
+
+/* Undoes the most recent push -- device state, sample / frame counts and ended flags -- so that it can be redone (a push
+ * that raised NHANS_STATUS_SATURATED at precision 1 is redone at precision 0 inside a "calibrate" bracket).  Once per
+ * push: a second rewind, or one before any push, returns NHANS_EINVAL. */
+int nhans_online_rewind(nhans_online* obj);
+
+void nhans_online_close(nhans_online* obj);
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

@@ -59,6 +59,7 @@ class Flags(object):
     weights = os.environ.get("NHANS_WEIGHTS", "checkpoint")
     model_dir = os.environ.get("NHANS_MODEL_DIR", "./trained_model")
     cache = True         # folded-blob cache (blobcache.py); --no-cache folds the weights in this process
+    online_ms = None     # --online_ms: file mode through the online path (online.py) in pieces of this many ms
 
 
 FLAGS = Flags()
@@ -221,11 +222,36 @@ def _enhance_files(kind, mixedpath, ctx_a_path, ctx_b_path):
     t1 = time.perf_counter()
     eng = get_enhancer(kind)
     t2 = time.perf_counter()
-    res = eng.enhance([mixed], [ca], [cb], want_mixed=True)
+    if getattr(FLAGS, "online_ms", None):
+        res = _enhance_online(eng, mixedpath, ca, cb, FLAGS.online_ms)
+    else:
+        res = eng.enhance([mixed], [ca], [cb], want_mixed=True)
     if TIMING is not None:
         TIMING.update(read_wavs_s=t1 - t0, engine_s=t2 - t1, enhance_s=time.perf_counter() - t2,
                       engine=type(eng).__name__, audio_s=len(mixed) / float(FLAGS.Fs))
     return res["denoised_wav"][0], res["mixed_wav"][0]
+
+
+def _enhance_online(eng, mixedpath, ca, cb, piece_ms):
+    """--online_ms: the file normalised with its whole-file peak exactly as offline, then pushed in piece_ms pieces
+    through one online stream (online.py); the untrimmed tail is pushed too and dropped by the output contract."""
+    from . import online
+    x = _reader()(mixedpath)
+    with np.errstate(over="ignore"):
+        peak = np.max(np.abs(x)) if len(x) else 0
+    x = online.normalise_fixed(x, peak)
+    step = max(1, int(round(piece_ms * FLAGS.Fs / 1000.0)))
+    enh = online.OnlineEnhancer(eng, [ca], [cb], want_mixed=True)
+    try:
+        den, mix = [], []
+        for i in range(0, max(len(x), 1), step):
+            last = i + step >= len(x)
+            (d, m), = enh.push([x[i:i + step]], end=[last])
+            den.append(d)
+            mix.append(m)
+    finally:
+        enh.close()
+    return {"denoised_wav": [np.concatenate(den)], "mixed_wav": [np.concatenate(mix)]}
 
 
 def side_prefix(save_to):
@@ -473,7 +499,15 @@ def _parse(argv, prog):
     p.add_argument('--no-convert', dest='convert', action='store_false', default=True,
                    help='reject inputs that are not 16 kHz int16 PCM (in-tree reference behaviour) '
                         'instead of converting them (packaged-tool behaviour, README.md:42)')
+    p.add_argument('--online_ms', type=float, default=None,
+                   help='file mode only: push the input through the online (live-stream) path in pieces of this many '
+                        'milliseconds; the files written are byte-identical to the offline run')
     a = p.parse_args(argv)
+    if a.online_ms is not None:
+        if a.online_ms <= 0:
+            p.error('--online_ms must be positive')
+        if os.path.isdir(a.input):
+            p.error('--online_ms works on one input file; %s is a directory (directory mode is offline batches)' % a.input)
     for k, v in vars(a).items():
         setattr(FLAGS, k, v)
     return a

@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(256) direct_conv64_4x4(const DirectArgs a, int
         const int tr = q / tiles_c;
         const int hi = tr * D4_TR - a.pt + pi_h, wi = (q - tr * tiles_c) * 16 - a.pl + pi_w;
         if ((unsigned)hi >= (unsigned)a.H || (unsigned)wi >= (unsigned)a.W) return 0.f;
-        if (a.win.t) return win_row_ok(a.win, b, hi) ? a.src[((ptrdiff_t)a.win.row0 + b + hi) * a.W + wi] : 0.f;
+        if (a.win.t) return win_row_ok(a.win, b, hi) ? a.src[(ptrdiff_t)win_row(a.win, b, hi) * a.W + wi] : 0.f;
         return a.src[((size_t)b * a.H + hi) * a.W + wi];
     };
     // the table's time term for the rows of the strip (the launcher admits Ho <= D4_TR: one strip per image column block)

@@ -394,7 +394,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[T
         int ids;
         if (a.id_mode == 2 && a.id_win.t) {
             const int h = (int)ho * a.idsh;
-            ids = win_row_ok(a.id_win, (int)b, h) ? (a.id_win.row0 + (int)b + h) * a.idW + (int)wo * a.idsw : kNoRow;
+            ids = win_row_ok(a.id_win, (int)b, h) ? win_row(a.id_win, (int)b, h) * a.idW + (int)wo * a.idsw : kNoRow;
         } else {
             ids = (int)((b * a.idH + ho * a.idsh) * a.idW + wo * a.idsw);
         }

@@ -71,12 +71,13 @@ __device__ __forceinline__ void wino_epilogue(const ConvArgs& a, const f32x16 (*
 
     // (IDM 3 with a sliding-window image: the frame's position in its clip and the clip's length -- uniform, SCALAR loads,
     // here in front of the counted vector-memory requests; a plain image: every row valid)
-    int win_t = a.id_win.pad, win_T = 0x7fffffff;
+    int win_t = a.id_win.pad, win_T = 0x7fffffff, win_r0 = a.id_win.row0 + b;
     if constexpr (IDM == 3) {
         if (a.id_win.t) {
             const int bu = __builtin_amdgcn_readfirstlane(b);
             win_t = a.id_win.t[bu];
             win_T = a.id_win.T[bu];
+            if (a.id_win.rb) win_r0 = a.id_win.rb[bu];      // (online: per-image first row, WinRows)
         }
     }
 
@@ -176,7 +177,7 @@ __device__ __forceinline__ void wino_epilogue(const ConvArgs& a, const f32x16 (*
             // outside the clip is a row of zeros -- the address is selected (the zero page, stride 0), the load unconditional
             const int hrow = (okq ? ho : 0) * a.idsh;
             const bool rowok = (unsigned)(win_t + hrow - a.id_win.pad) < (unsigned)win_T;
-            const int ids0 = (a.id_win.t ? (a.id_win.row0 + b + hrow) : (b * a.idH + hrow)) * a.idW + (okq ? wo0 : 0) * a.idsw;
+            const int ids0 = (a.id_win.t ? (win_r0 + hrow) : (b * a.idH + hrow)) * a.idW + (okq ? wo0 : 0) * a.idsw;
             const float* const idp = rowok ? a.id + ids0 : a.zero;
             rsv[i] = idp[rowok ? (i < lastc ? i : lastc) * a.idsw : 0];
         }

@@ -457,7 +457,9 @@ void stack_take(nhans_ctx* c, int64_t total, int nclips, int64_t wf, StackBufs* 
 // Two passes over the same code: pass 0 builds every conv's arguments and records which of them the Winograd kernel
 // accepts (StackPlan), pass 1 builds them again with the tensor layouts and saturation limits that follow from the plan
 // and launches.  A launch whose eligibility differs between the passes is an error, not a fallback.
-float* run_stack_chunk(nhans_ctx* c, const float* logmag, const StackBufs& sb, int64_t g0, int n, int upto,
+// rb (nullable): per-frame first window row in `logmag` (online enhancement, WinRows::rb); null: frame g's window starts at
+// row g - 17
+float* run_stack_chunk(nhans_ctx* c, const float* logmag, const int* rb, const StackBufs& sb, int64_t g0, int n, int upto,
                        hipStream_t s) {
     StackPlan plan;
     float* result = nullptr;
@@ -482,8 +484,9 @@ float* run_stack_chunk(nhans_ctx* c, const float* logmag, const StackBufs& sb, i
     // resblock1_1 read the spectrogram where it lies)
     // (rows are counted from the chunk's first frame -- the tensor pointer handed to the kernels is logmag + g0 * 201 --, so the
     // kernels' 32-bit element indices stay below (frames_per_chunk + 35) * 201 however long the batch is)
-    const WinRows win{sb.f_t + g0, sb.f_T + g0, -kCenter, kCenter};
-    const float* const lm_chunk = logmag + (size_t)g0 * kBins;
+    // (online: rows are where the per-frame table rb says, in a tensor small enough for 32-bit indices, WinRows::rb)
+    const WinRows win{sb.f_t + g0, sb.f_T + g0, -kCenter, kCenter, rb ? rb + g0 : nullptr};
+    const float* const lm_chunk = rb ? logmag : logmag + (size_t)g0 * kBins;
     float *x = sb.X, *a1 = sb.A, *y = sb.Y;
     // pass 0 plans the WHOLE stack whatever `upto` is -- the layout of block b's output follows from block b + 1's
     // readers, and the debug entry point (upto = block + 1) must see the tensors the production call writes
@@ -607,12 +610,12 @@ float* run_stack_chunk(nhans_ctx* c, const float* logmag, const StackBufs& sb, i
     return result;
 }
 
-int mask_net_impl(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
-                  const float* eb, float* logits, float* denoised, const StackBufs& sb, int64_t wf,
-                  hipStream_t s) {
-    const int64_t total = foff[nclips];
-    { int rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc; }
-    launch_frame_index(sb.foff_dev, nclips, total, sb.f_clip, sb.f_t, sb.f_T, s);
+// The stack + head over `total` frame windows whose per-frame tables (sb.f_clip, f_t, f_T) are in place.  win_src / rb:
+// the window source (rb nullable, see run_stack_chunk); centre [total, 201]: the frames' own rows, the head's identity
+// term (mixed_central, SN/main.py:242) -- offline that is win_src itself.
+int mask_net_run(nhans_ctx* c, const float* win_src, const int* rb, const float* centre, int64_t total, int nclips,
+                 const float* ea, const float* eb, float* logits, float* denoised, const StackBufs& sb, int64_t wf,
+                 hipStream_t s) {
     {
         Prof pr(c, s, "cond_proj");
         launch_cond(ea, eb, nclips, c->A("cond.w"), c->A("cond.base"), c->cond_cols, sb.cb_all, s);
@@ -621,7 +624,7 @@ int mask_net_impl(nhans_ctx* c, const float* logmag, const int64_t* foff, int nc
     const BlockGeo& g = c->stack[7];
     for (int64_t g0 = 0; g0 < total; g0 += wf) {
         const int n = (int)std::min<int64_t>(wf, total - g0);
-        float* hc = run_stack_chunk(c, logmag, sb, g0, n, 9, s);
+        float* hc = run_stack_chunk(c, win_src, rb, sb, g0, n, 9, s);
         if (launch_error_pending()) break;      // (reported by the entry point: NHANS_EHIP naming the launch)
         // last_dense 13312 -> 201 (+bias) and denoised = mixed_central + out  (SN/main.py:237-242)
         ConvArgs a{};
@@ -634,12 +637,21 @@ int mask_net_impl(nhans_ctx* c, const float* logmag, const int64_t* foff, int nc
         a.out_split = 0;
         a.relu = 0;
         a.in_scale = c->up(kActHead);
-        a.id_mode = 1; a.id = logmag + g0 * kBins; a.id_ld = kBins; a.idw = c->A("head.dense.idw");
+        a.id_mode = 1; a.id = centre + g0 * kBins; a.id_ld = kBins; a.idw = c->A("head.dense.idw");
         if (logits) { a.aux = logits + g0 * kBins; a.aux_ld = kBins; }
         a.kgroup = -1;                          // K = 13312 over a few hundred frames: grouped sum, split-K when small
         run_conv(c, a, s);
     }
     return NHANS_OK;
+}
+
+int mask_net_impl(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
+                  const float* eb, float* logits, float* denoised, const StackBufs& sb, int64_t wf,
+                  hipStream_t s) {
+    const int64_t total = foff[nclips];
+    { int rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc; }
+    launch_frame_index(sb.foff_dev, nclips, total, sb.f_clip, sb.f_t, sb.f_T, s);
+    return mask_net_run(c, logmag, nullptr, logmag, total, nclips, ea, eb, logits, denoised, sb, wf, s);
 }
 
 // ---- STFT / iSTFT host-side block tables ----------------------------------------------------
@@ -650,7 +662,7 @@ struct HostTables {
 
 int stft_impl(nhans_ctx* c, const float* wav, const int64_t* soff, int nclips, int maxf, float* logmag,
               float* phase, int64_t* dev_tables /*3*(nclips+1)*/, int* dev_blocks, std::vector<int64_t>* foff_out,
-              hipStream_t s) {
+              hipStream_t s, const char* prof_name = nullptr) {
     std::vector<int64_t> foff(nclips + 1, 0);
     std::vector<int> bclip, bf0;
     for (int i = 0; i < nclips; ++i) {
@@ -671,7 +683,7 @@ int stft_impl(nhans_ctx* c, const float* wav, const int64_t* soff, int nclips, i
     rc = h2d(c, dev_blocks, bclip.data(), (size_t)nb * 4, s); if (rc) return rc;
     rc = h2d(c, dev_blocks + nb, bf0.data(), (size_t)nb * 4, s); if (rc) return rc;
     ClipTable t{dev_tables, dev_tables + (nclips + 1), nullptr};
-    Prof pr(c, s, phase ? "stft_features" : "stft_context_features");   // (contexts: log-magnitude only, 200 frames per clip)
+    Prof pr(c, s, prof_name ? prof_name : phase ? "stft_features" : "stft_context_features");   // (contexts: log-magnitude only, 200 frames per clip)
     launch_stft(wav, t, dev_blocks, dev_blocks + nb, nb, c->A("tw400"), c->A("window"), logmag, phase, s);
     pr.done(0, (double)foff[nclips] * (kHop * 4 + (phase ? 2 : 1) * kBins * 4));
     if (foff_out) *foff_out = foff;
@@ -689,7 +701,8 @@ size_t stft_blocks(const int64_t* soff, int nclips, int maxf) {
 }
 
 int istft_impl(nhans_ctx* c, const float* logmag, const float* phase, const int64_t* foff, int nclips,
-               const int64_t* ooff, float* wav_out, int64_t* dev_tables, int* dev_blocks, hipStream_t s) {
+               const int64_t* ooff, float* wav_out, int64_t* dev_tables, int* dev_blocks, hipStream_t s,
+               const char* prof_name = "istft_ola") {
     std::vector<int> bclip, bh0;
     for (int i = 0; i < nclips; ++i) {
         const int64_t t = foff[i + 1] - foff[i];
@@ -704,7 +717,7 @@ int istft_impl(nhans_ctx* c, const float* logmag, const float* phase, const int6
     rc = h2d(c, dev_blocks, bclip.data(), (size_t)nb * 4, s); if (rc) return rc;
     rc = h2d(c, dev_blocks + nb, bh0.data(), (size_t)nb * 4, s); if (rc) return rc;
     ClipTable t{nullptr, dev_tables, dev_tables + (nclips + 1)};
-    Prof pr(c, s, "istft_ola");
+    Prof pr(c, s, prof_name);
     launch_istft(logmag, phase, t, dev_blocks, dev_blocks + nb, nb, c->A("tw400"), c->A("wsyn"), wav_out, s);
     pr.done(0, (double)foff[nclips] * (kHop * 4 + 2 * kBins * 4));
     return NHANS_OK;
@@ -1151,7 +1164,7 @@ static int debug_block_output_body(nhans_ctx* c, const float* logmag, const int6
     rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc;
     launch_frame_index(sb.foff_dev, nclips, total, sb.f_clip, sb.f_t, sb.f_T, s);
     launch_cond(ea, eb, nclips, c->A("cond.w"), c->A("cond.base"), c->cond_cols, sb.cb_all, s);
-    const float* res = run_stack_chunk(c, logmag, sb, frame0, nframes, block + 1, s);
+    const float* res = run_stack_chunk(c, logmag, nullptr, sb, frame0, nframes, block + 1, s);
     size_t per;
     if (block == 8) per = (size_t)26 * 512;
     else per = (size_t)c->stack[block].hout * c->stack[block].wout * c->stack[block].cout;
@@ -1356,6 +1369,364 @@ int nhans_profile_json(nhans_ctx* c, char* buf, size_t buflen) {
         buf[n] = 0;
     }
     return (int)js.size();
+}
+
+}  // extern "C"
+
+// ---- online enhancement (include/nhans_hip.h: nhans_online_*) ----------------------------------------------------------
+// Synthesis restarts at frame S0(P): the offline iSTFT kernel's bits depend on where a frame pair falls in its run of
+// kIstftHopsPerBlock hops (the pairs of a run are different unrolled copies of the transform, which the compiler may
+// contract differently: ~1e-7), so the staged clip of a push starts on that grid of the stream's frames, at or before
+// P - 2 (the first frame under the first sample not emitted yet).
+// State of one online stream in one slot, floats: the unconsumed samples [160 T, N) (< 400), the log-magnitude and phase
+// rows of frames [lo, T), lo = max(0, min(R - 17, S0(P))) (<= 41: the history of the next ready frame's window, the
+// look-ahead rows that exist, every row the iSTFT still needs), and the denoised rows [S0(P), R) (<= 24: computed, not
+// yet synthesised, and those the next synthesis restarts from).  A push reads slot `cur` and writes the other slot
+// whole; nhans_online_rewind flips back.
+namespace {
+constexpr int kOnRows = 2 * kCenter + kIstftHopsPerBlock - 14;  // 42 >= 17 + 24
+constexpr int kOnDenRows = kIstftHopsPerBlock + 2;              // 24
+constexpr size_t kOnSamp = 0, kOnLm = kWin, kOnPh = kOnLm + (size_t)kOnRows * kBins, kOnDen = kOnPh + (size_t)kOnRows * kBins;
+constexpr size_t kOnSlot = (kOnDen + (size_t)kOnDenRows * kBins + 63) & ~(size_t)63;   // 22,144 floats = 88.6 KB
+int64_t on_s0(int64_t P) { return std::max<int64_t>(0, P - 2) / kIstftHopsPerBlock * kIstftHopsPerBlock; }
+int64_t on_lo(int64_t R, int64_t P) { return std::max<int64_t>(0, std::min<int64_t>(R - kCenter, on_s0(P))); }
+
+struct OnStream {
+    int64_t N = 0, T = 0;
+    bool ended = false;
+};
+// frames whose window is complete / frames whose samples are final, for a stream of T frames
+int64_t on_ready(int64_t T, bool ended) { return ended ? T : std::max<int64_t>(0, T - kCenter); }
+int64_t on_paired(int64_t T, bool ended) { return ended ? T : on_ready(T, false) & ~(int64_t)1; }
+int64_t on_emitted(int64_t T, bool ended) {
+    if (!ended) return (int64_t)kHop * on_paired(T, false);
+    return T == 0 ? 0 : (T - 1) * kHop + kWin;
+}
+}  // namespace
+
+struct nhans_online {
+    nhans_ctx* c = nullptr;
+    int device = 0, S = 0;
+    bool mixed = false;
+    float* emb = nullptr;       // [2S, 512]: a-rows then b-rows
+    float* state = nullptr;     // [2][S][kOnSlot]
+    int cur = 0;
+    std::vector<OnStream> st, prev;
+    bool can_rewind = false;
+    float* slot(int k, int i) const { return state + ((size_t)k * S + i) * kOnSlot; }
+};
+
+namespace {
+
+int online_open_body(nhans_ctx* c, int S, const float* ca, const int64_t* caoff, const float* cbw, const int64_t* cboff,
+                     int want_mixed, hipStream_t s, nhans_online** out) {
+    if (!out) return fail(NHANS_EINVAL, "null argument");
+    *out = nullptr;
+    if (S < 1) return fail(NHANS_EINVAL, "nhans_online_open: nstreams must be >= 1");
+    if (!ca || !caoff || !cbw || !cboff) return fail(NHANS_EINVAL, "null argument");
+    const size_t nb = std::max(stft_blocks(caoff, S, kCtxFrames), stft_blocks(cboff, S, kCtxFrames));
+    const size_t tb = tower_buf_floats(c);
+    int rc = ws_reserve(c, ws_size((size_t)2 * S * kCtxFrames * kBins, 4) + 2 * ws_size(2 * (S + 1), 8) +
+                               2 * ws_size(2 * nb, 4) + 3 * ws_size(tb, 4));
+    if (rc) return rc;
+    float* ctxlm = ws_take<float>(c, (size_t)2 * S * kCtxFrames * kBins);
+    int64_t* tabs[2]; int* blks[2];
+    for (int i = 0; i < 2; ++i) { tabs[i] = ws_take<int64_t>(c, 2 * (S + 1)); blks[i] = ws_take<int>(c, 2 * nb); }
+    float* X = ws_take<float>(c, tb); float* A = ws_take<float>(c, tb); float* Y = ws_take<float>(c, tb);
+    rc = stft_impl(c, ca, caoff, S, kCtxFrames, ctxlm, nullptr, tabs[0], blks[0], nullptr, s); if (rc) return rc;
+    rc = stft_impl(c, cbw, cboff, S, kCtxFrames, ctxlm + (size_t)S * kCtxFrames * kBins, nullptr, tabs[1], blks[1], nullptr, s);
+    if (rc) return rc;
+    nhans_online* o = new nhans_online();
+    o->c = c; o->device = c->device; o->S = S; o->mixed = want_mixed != 0;
+    o->st.assign(S, OnStream()); o->prev = o->st;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->emb), (size_t)2 * S * kEmb * 4);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&o->state), (size_t)2 * S * kOnSlot * 4);
+    if (e != hipSuccess) {
+        if (o->emb) (void)hipFree(o->emb);
+        delete o;
+        return fail(NHANS_ENOMEM, std::string("nhans_online_open: hipMalloc failed: ") + hipGetErrorString(e));
+    }
+    rc = embed_impl(c, ctxlm, 2 * S, o->emb, X, A, Y, s);
+    if (rc) { (void)hipFree(o->emb); (void)hipFree(o->state); delete o; return rc; }
+    *out = o;
+    return NHANS_OK;
+}
+
+// One push; see include/nhans_hip.h.  Host plan first (every count, offset and copy run), then the launches:
+//   online_ingest   carried samples + new input -> wav staging (compact, one clip per stream)
+//   online_stft     the newly complete frames -> new log-magnitude / phase rows (the offline STFT kernel)
+//   online_assemble window source [lo, T_new) per stream, the ready frames' centre rows, synthesis staging from the state
+//   stack + head    over the ready frames of all streams at once (per-frame first-row table: WinRows::rb)
+//   online_commit   denoised rows -> synthesis staging, and the next state slot
+//   online_istft    the offline iSTFT kernel on the synthesis staging (same pairs: the staging starts on an even frame)
+//   online_emit     the final samples -> the caller
+int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, const int* end, float* den_out,
+                     float* mix_out, const int64_t* outoff, int64_t* counts, hipStream_t s) {
+    nhans_ctx* c = o->c;
+    const int S = o->S;
+    if (!inoff || !outoff || !counts) return fail(NHANS_EINVAL, "null argument");
+    struct Plan {
+        int64_t cnt, Nn, Tn, Ro, Rn, Po, Pn, lo, s0, Pend, Eo, En, nsyn;
+        bool en;
+    };
+    std::vector<Plan> pl(S);
+    int64_t tot_in = 0, tot_out = 0;
+    for (int i = 0; i < S; ++i) {
+        const OnStream& q = o->st[i];
+        Plan& p = pl[i];
+        p.cnt = inoff[i + 1] - inoff[i];
+        if (p.cnt < 0) return fail(NHANS_EINVAL, "nhans_online_push: stream " + std::to_string(i) + " has a negative sample count");
+        p.en = end && end[i];
+        if (q.ended && (p.cnt > 0 || p.en))
+            return fail(NHANS_EINVAL, "nhans_online_push: stream " + std::to_string(i) + " has ended");
+        p.Nn = q.N + p.cnt;
+        p.Tn = nhans_num_frames(p.Nn);
+        if (p.Tn > kMaxFramesPerClip)
+            return fail(NHANS_EINVAL, "nhans_online_push: stream " + std::to_string(i) + " would exceed " +
+                                      std::to_string(kMaxFramesPerClip) + " frames");
+        p.Ro = on_ready(q.T, q.ended); p.Po = on_paired(q.T, q.ended);
+        p.Rn = on_ready(p.Tn, p.en || q.ended); p.Pn = on_paired(p.Tn, p.en || q.ended);
+        p.lo = on_lo(p.Ro, p.Po);
+        p.s0 = on_s0(p.Po);
+        p.Pend = p.Pn;
+        p.Eo = on_emitted(q.T, q.ended);
+        p.En = on_emitted(p.Tn, p.en || q.ended);
+        p.nsyn = p.En > p.Eo ? p.Pend - p.s0 : 0;
+        if (outoff[i + 1] - outoff[i] < p.En - p.Eo)
+            return fail(NHANS_EINVAL, "nhans_online_push: output room of stream " + std::to_string(i) + " is " +
+                                      std::to_string(outoff[i + 1] - outoff[i]) + " samples, " + std::to_string(p.En - p.Eo) +
+                                      " needed (nhans_online_out_counts)");
+        tot_in += p.cnt;
+        tot_out += p.En - p.Eo;
+    }
+    if (tot_in > 0 && !in) return fail(NHANS_EINVAL, "null argument: in_dev");
+    if (tot_out > 0 && (!den_out || (o->mixed && !mix_out))) return fail(NHANS_EINVAL, "null argument: output buffer");
+
+    // ---- staging layout (compact, stream after stream) ----
+    std::vector<int64_t> soff(S + 1, 0), nfoff(S + 1, 0), woff(S + 1, 0), foff(S + 1, 0), yoff(S + 1, 0), ooff(S + 1, 0);
+    for (int i = 0; i < S; ++i) {
+        const Plan& p = pl[i];
+        const OnStream& q = o->st[i];
+        soff[i + 1] = soff[i] + (q.N - (int64_t)kHop * q.T) + p.cnt;
+        nfoff[i + 1] = nfoff[i] + (p.Tn - q.T);
+        woff[i + 1] = woff[i] + (p.Rn > p.Ro ? p.Tn - p.lo : 0);
+        foff[i + 1] = foff[i] + (p.Rn - p.Ro);
+        yoff[i + 1] = yoff[i] + p.nsyn;
+        ooff[i + 1] = ooff[i] + (p.nsyn > 0 ? ((p.nsyn - 1) * kHop + kWin + 3) / 4 * 4 : 0);
+    }
+    const int64_t F = foff[S], NF = nfoff[S], WR = woff[S], Y = yoff[S];
+    if (WR * kBins >= ((int64_t)1 << 31) || soff[S] >= ((int64_t)1 << 31) * 4)
+        return fail(NHANS_EINVAL, "nhans_online_push: push too large for one call (split it)");
+    const int64_t wf = std::min<int64_t>(c->frames_per_chunk, std::max<int64_t>(F, 1));
+    const size_t nb_st = stft_blocks(soff.data(), S, 0), nb_is = istft_blocks(yoff.data(), S);
+    // (every run of n floats is ceil(n / kOnlineCopyMax) pieces; a stream has at most 19 runs per push)
+    const size_t nrun_cap = (size_t)S * 32 + (size_t)(soff[S] + (WR + F + 4 * Y) * kBins + 2 * tot_out) / kOnlineCopyMax + 64;
+    size_t bytes = ws_size(soff[S], 4) + 2 * ws_size(NF * kBins, 4) + ws_size(WR * kBins, 4) + 2 * ws_size(F * kBins, 4) +
+                   3 * ws_size(Y * kBins, 4) + (o->mixed ? 2 : 1) * ws_size(ooff[S], 4) + 2 * ws_size(2 * (S + 1), 8) +
+                   ws_size(2 * nb_st, 4) + ws_size(2 * nb_is, 4) + ws_size(F, 4) + ws_size(nrun_cap, sizeof(OnlineCopy));
+    if (F > 0) bytes += stack_ws_bytes(c, F, S, wf);
+    int rc = ws_reserve(c, bytes); if (rc) return rc;
+    float* wav = ws_take<float>(c, soff[S]);
+    float* nlm = ws_take<float>(c, NF * kBins);
+    float* nph = ws_take<float>(c, NF * kBins);
+    float* win = ws_take<float>(c, WR * kBins);
+    float* ctr = ws_take<float>(c, F * kBins);
+    float* dnew = ws_take<float>(c, F * kBins);
+    float* yden = ws_take<float>(c, Y * kBins);
+    float* yph = ws_take<float>(c, Y * kBins);
+    float* ylm = ws_take<float>(c, Y * kBins);
+    float* tden = ws_take<float>(c, ooff[S]);
+    float* tmix = o->mixed ? ws_take<float>(c, ooff[S]) : nullptr;
+    int64_t* tab_st = ws_take<int64_t>(c, 2 * (S + 1));
+    int64_t* tab_is = ws_take<int64_t>(c, 2 * (S + 1));
+    int* blk_st = ws_take<int>(c, 2 * nb_st);
+    int* blk_is = ws_take<int>(c, 2 * nb_is);
+    int* rb = ws_take<int>(c, F);
+    OnlineCopy* runs_dev = ws_take<OnlineCopy>(c, nrun_cap);
+    StackBufs sb{};
+    if (F > 0) stack_take(c, F, S, wf, &sb);
+
+    // ---- copy runs ----
+    std::vector<OnlineCopy> runs;
+    auto add = [&](const float* src, float* dst, int64_t n) {
+        for (int64_t k = 0; k < n; k += kOnlineCopyMax) runs.push_back({src + k, dst + k, std::min<int64_t>(kOnlineCopyMax, n - k)});
+    };
+    const int cur = o->cur, nxt = 1 - cur;
+    // rows [a, b) of stream i's log-magnitude (ph = false) or phase: the state holds [lo, T_old), the push [T_old, T_new)
+    auto add_rows = [&](int i, bool ph, int64_t a, int64_t b, float* dst) {
+        const OnStream& q = o->st[i];
+        const Plan& p = pl[i];
+        const int64_t m = std::min(b, q.T);
+        if (m > a) add(o->slot(cur, i) + (ph ? kOnPh : kOnLm) + (a - p.lo) * kBins, dst, (m - a) * kBins);
+        const int64_t a2 = std::max(a, q.T);
+        if (b > a2) add((ph ? nph : nlm) + (nfoff[i] + a2 - q.T) * kBins, dst + (a2 - a) * kBins, (b - a2) * kBins);
+    };
+    // denoised rows [a, b): the state holds [s0, R_old), the push [R_old, R_new)
+    auto add_den = [&](int i, int64_t a, int64_t b, float* dst, bool from_state) {
+        const Plan& p = pl[i];
+        if (from_state) {
+            const int64_t m = std::min(b, p.Ro);
+            if (m > a) add(o->slot(cur, i) + kOnDen + (a - p.s0) * kBins, dst, (m - a) * kBins);
+        } else {
+            const int64_t a2 = std::max(a, p.Ro);
+            if (b > a2) add(dnew + (foff[i] + a2 - p.Ro) * kBins, dst + (a2 - a) * kBins, (b - a2) * kBins);
+        }
+    };
+    std::vector<int> bounds(1, 0);
+    // ingest
+    for (int i = 0; i < S; ++i) {
+        const int64_t carry = o->st[i].N - (int64_t)kHop * o->st[i].T;
+        add(o->slot(cur, i) + kOnSamp, wav + soff[i], carry);
+        if (pl[i].cnt > 0) add(in + inoff[i], wav + soff[i] + carry, pl[i].cnt);
+    }
+    bounds.push_back((int)runs.size());
+    // assemble
+    std::vector<int> h_clip(F), h_t(F), h_T(F), h_rb(F);
+    for (int i = 0; i < S; ++i) {
+        const Plan& p = pl[i];
+        if (p.Rn > p.Ro) {
+            add_rows(i, false, p.lo, p.Tn, win + woff[i] * kBins);
+            add_rows(i, false, p.Ro, p.Rn, ctr + foff[i] * kBins);
+            for (int64_t t = p.Ro; t < p.Rn; ++t) {
+                const int64_t f = foff[i] + t - p.Ro;
+                h_clip[f] = i; h_t[f] = (int)t; h_T[f] = (int)p.Tn;
+                h_rb[f] = (int)(woff[i] + t - kCenter - p.lo);
+            }
+        }
+        if (p.nsyn > 0) {
+            add_rows(i, true, p.s0, p.Pend, yph + yoff[i] * kBins);
+            if (o->mixed) add_rows(i, false, p.s0, p.Pend, ylm + yoff[i] * kBins);
+            add_den(i, p.s0, p.Pend, yden + yoff[i] * kBins, true);
+        }
+    }
+    bounds.push_back((int)runs.size());
+    // commit: denoised rows of this push -> synthesis staging; the next slot
+    for (int i = 0; i < S; ++i) {
+        const Plan& p = pl[i];
+        const OnStream& q = o->st[i];
+        if (p.nsyn > 0) add_den(i, p.s0, p.Pend, yden + yoff[i] * kBins, false);
+        float* ns = o->slot(nxt, i);
+        add(wav + soff[i] + (int64_t)kHop * (p.Tn - q.T), ns + kOnSamp, p.Nn - (int64_t)kHop * p.Tn);
+        const int64_t lo_n = on_lo(p.Rn, p.Pn), s0_n = on_s0(p.Pn);
+        if (p.Tn - lo_n > kOnRows || p.Rn - s0_n > kOnDenRows) return fail(NHANS_EINVAL, "nhans_online_push: internal state bound");
+        add_rows(i, false, lo_n, p.Tn, ns + kOnLm);
+        add_rows(i, true, lo_n, p.Tn, ns + kOnPh);
+        add_den(i, s0_n, p.Rn, ns + kOnDen, true);
+        add_den(i, s0_n, p.Rn, ns + kOnDen, false);
+    }
+    bounds.push_back((int)runs.size());
+    // emit
+    for (int i = 0; i < S; ++i) {
+        const Plan& p = pl[i];
+        if (p.En <= p.Eo) continue;
+        const int64_t skip = (int64_t)kHop * (p.Po - p.s0);
+        add(tden + ooff[i] + skip, den_out + outoff[i], p.En - p.Eo);
+        if (o->mixed) add(tmix + ooff[i] + skip, mix_out + outoff[i], p.En - p.Eo);
+    }
+    bounds.push_back((int)runs.size());
+    if (runs.size() > nrun_cap) return fail(NHANS_EINVAL, "nhans_online_push: internal run bound");
+
+    // ---- launches ----
+    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(OnlineCopy), s); if (rc) return rc;
+    auto copies = [&](int k, const char* name) {
+        const int n = bounds[k + 1] - bounds[k];
+        if (n <= 0) return;
+        Prof pr(c, s, name);
+        launch_online_copy(name, runs_dev + bounds[k], n, s);
+        int64_t fl = 0;
+        for (int r = bounds[k]; r < bounds[k + 1]; ++r) fl += runs[r].n;
+        pr.done(0, 8.0 * (double)fl);
+    };
+    copies(0, "online_ingest");
+    if (NF > 0) {
+        std::vector<int64_t> fo;
+        rc = stft_impl(c, wav, soff.data(), S, 0, nlm, nph, tab_st, blk_st, &fo, s, "online_stft"); if (rc) return rc;
+    }
+    copies(1, "online_assemble");
+    if (F > 0) {
+        rc = h2d(c, sb.f_clip, h_clip.data(), F * 4, s); if (rc) return rc;
+        rc = h2d(c, sb.f_t, h_t.data(), F * 4, s); if (rc) return rc;
+        rc = h2d(c, sb.f_T, h_T.data(), F * 4, s); if (rc) return rc;
+        rc = h2d(c, rb, h_rb.data(), F * 4, s); if (rc) return rc;
+        rc = mask_net_run(c, win, rb, ctr, F, S, o->emb, o->emb + (size_t)S * kEmb, nullptr, dnew, sb, wf, s);
+        if (rc) return rc;
+        if (launch_error_pending()) return NHANS_OK;      // (reported by the entry point; nothing below runs on it)
+    }
+    copies(2, "online_commit");
+    if (Y > 0) {
+        rc = istft_impl(c, yden, yph, yoff.data(), S, ooff.data(), tden, tab_is, blk_is, s, "online_istft"); if (rc) return rc;
+        if (o->mixed) {
+            // (tab_is / blk_is reused: same stream, the first launch has consumed them in order)
+            rc = istft_impl(c, ylm, yph, yoff.data(), S, ooff.data(), tmix, tab_is, blk_is, s, "online_istft"); if (rc) return rc;
+        }
+    }
+    copies(3, "online_emit");
+    if (launch_error_pending()) return NHANS_OK;
+
+    // ---- host state ----
+    o->prev = o->st;
+    for (int i = 0; i < S; ++i) {
+        OnStream& q = o->st[i];
+        counts[i] = pl[i].En - pl[i].Eo;
+        q.N = pl[i].Nn; q.T = pl[i].Tn; q.ended = q.ended || pl[i].en;
+    }
+    o->cur = nxt;
+    o->can_rewind = true;
+    return NHANS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nhans_online_open(nhans_ctx* c, int nstreams, const float* ca, const int64_t* caoff, const float* cbw,
+                      const int64_t* cboff, int want_mixed, void* stream, nhans_online** out) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(online_open_body(c, nstreams, ca, caoff, cbw, cboff, want_mixed, call.s, out));
+}
+
+int nhans_online_push(nhans_online* o, const float* in, const int64_t* inoff, const int* end, float* den_out,
+                      float* mix_out, const int64_t* outoff, int64_t* counts, void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(online_push_body(o, in, inoff, end, den_out, mix_out, outoff, counts, call.s));
+}
+
+int nhans_online_out_counts(const nhans_online* o, const int64_t* in_counts, const int* end, int64_t* counts) {
+    if (!o || !in_counts || !counts) return fail(NHANS_EINVAL, "null argument");
+    for (int i = 0; i < o->S; ++i) {
+        const OnStream& q = o->st[i];
+        const bool en = end && end[i];
+        if (in_counts[i] < 0) return fail(NHANS_EINVAL, "nhans_online_out_counts: stream " + std::to_string(i) + " has a negative sample count");
+        if (q.ended && (in_counts[i] > 0 || en))
+            return fail(NHANS_EINVAL, "nhans_online_out_counts: stream " + std::to_string(i) + " has ended");
+    }
+    for (int i = 0; i < o->S; ++i) {
+        const OnStream& q = o->st[i];
+        const bool en = q.ended || (end && end[i]);
+        counts[i] = on_emitted(nhans_num_frames(q.N + in_counts[i]), en) - on_emitted(q.T, q.ended);
+    }
+    return NHANS_OK;
+}
+
+int nhans_online_rewind(nhans_online* o) {
+    if (!o) return fail(NHANS_EINVAL, "null object");
+    if (!o->can_rewind) return fail(NHANS_EINVAL, "nhans_online_rewind: no push to undo (one rewind per push)");
+    o->st = o->prev;
+    o->cur = 1 - o->cur;
+    o->can_rewind = false;
+    return NHANS_OK;
+}
+
+void nhans_online_close(nhans_online* o) {
+    if (!o) return;
+    (void)hipSetDevice(o->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(o->emb);
+    (void)hipFree(o->state);
+    delete o;
 }
 
 }  // extern "C"

@@ -82,14 +82,20 @@ __device__ __forceinline__ uint32_t fd_div(uint32_t n, const FastDiv& f) {
 // 0.0 otherwise -- strided_crop of SN/apply.py:170-186,378 (35-row windows of the log-magnitude spectrogram, zero rows
 // -- not the silence floor -- outside the clip) without ever materialising [T, 35, 201].
 // t == nullptr: plain images [B, H, W].
+// rb != nullptr (online enhancement, nhans_api.hip): image b's row h is tensor row rb[b] + h instead -- the frames of one
+// launch then need not be consecutive rows of one tensor (each online stream brings its own history and look-ahead rows)
 struct WinRows {
     const int* t;
     const int* T;
     int row0, pad;      // (row0 may be negative: nhans_api.hip counts rows from the launch's first frame, row0 = -pad)
+    const int* rb;      // nullable: per-image first row (row0 is then unused)
 };
 constexpr int kNoRow = -2147483647 - 1;      // "this row is a zero row" where an element index is stored (conv_epilogue.h)
 __device__ __forceinline__ bool win_row_ok(const WinRows& w, int b, int h) {
     return (unsigned)(w.t[b] + h - w.pad) < (unsigned)w.T[b];
+}
+__device__ __forceinline__ int win_row(const WinRows& w, int b, int h) {
+    return (w.rb ? w.rb[b] : w.row0 + b) + h;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -244,6 +250,17 @@ void launch_avgpool(const float* x, int B, int HW, int C, int split, float scale
 // cb[clip, n] = base[n] + sum_k ea[clip,k]*Wc[k, n] + sum_k eb[clip,k]*Wc[512+k, n]
 void launch_cond(const float* ea, const float* eb, int nclips, const float* Wc, const float* base,
                  int ncols, float* cb, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// Online enhancement (online.hip): the state, gather and commit moves of nhans_online_push are lists of contiguous float
+// runs, one workgroup per run (the host splits runs longer than kOnlineCopyMax)
+struct OnlineCopy {
+    const float* src;
+    float* dst;
+    long long n;        // floats, <= kOnlineCopyMax
+};
+constexpr int kOnlineCopyMax = 8192;
+void launch_online_copy(const char* kernel, const OnlineCopy* runs_dev, int nruns, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // STFT / iSTFT (stft.hip)

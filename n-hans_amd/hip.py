@@ -21,7 +21,8 @@ EXPORTS = [
     "nhans_mask_net", "nhans_istft", "nhans_enhance_clips", "nhans_debug_block_output",
     "nhans_profile_json", "nhans_profile_reset", "nhans_take_status", "nhans_debug_launch_probe", "nhans_crc32c",
     "nhans_debug_mfma_ceiling", "nhans_set_activation_exponents", "nhans_get_activation_exponents",
-    "nhans_get_activation_amax",
+    "nhans_get_activation_amax", "nhans_online_open", "nhans_online_push", "nhans_online_out_counts",
+    "nhans_online_rewind", "nhans_online_close",
 ]
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25
@@ -78,12 +79,24 @@ def load():
     lib.nhans_set_activation_exponents.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
     lib.nhans_get_activation_exponents.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
     lib.nhans_get_activation_amax.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.c_int]
+    # (online enhancement; a build from before it -- $NHANS_LIB in a same-box A/B -- has none of these: build() and
+    # tests/test_host.py check that the library in the tree exports every symbol of the header)
+    online = hasattr(lib, "nhans_online_open")
+    if online:
+        ip = ctypes.POINTER(ctypes.c_int)
+        lib.nhans_online_open.argtypes = [vp, ctypes.c_int, vp, i64p, vp, i64p, ctypes.c_int, vp, ctypes.POINTER(vp)]
+        lib.nhans_online_push.argtypes = [vp, vp, i64p, ip, vp, vp, i64p, i64p, vp]
+        lib.nhans_online_out_counts.argtypes = [vp, i64p, ip, i64p]
+        lib.nhans_online_rewind.argtypes = [vp]
+        lib.nhans_online_close.argtypes = [vp]
+        lib.nhans_online_close.restype = None
     lib.nhans_crc32c.argtypes = [ctypes.c_uint32, vp, ctypes.c_size_t]
     lib.nhans_crc32c.restype = ctypes.c_uint32
     for name in ("nhans_create", "nhans_create_ex", "nhans_set_option", "nhans_stft_features", "nhans_embed", "nhans_mask_net",
                  "nhans_istft", "nhans_enhance_clips", "nhans_debug_block_output", "nhans_profile_json",
                  "nhans_profile_reset", "nhans_take_status", "nhans_debug_launch_probe",
-                 "nhans_set_activation_exponents", "nhans_get_activation_exponents", "nhans_get_activation_amax"):
+                 "nhans_set_activation_exponents", "nhans_get_activation_exponents", "nhans_get_activation_amax") + (
+                 ("nhans_online_open", "nhans_online_push", "nhans_online_out_counts", "nhans_online_rewind") if online else ()):
         getattr(lib, name).restype = ctypes.c_int
     if lib.nhans_abi_version() != ABI_VERSION:
         raise NhansError("libnhans_hip.so ABI version mismatch")

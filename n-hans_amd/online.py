@@ -1,0 +1,201 @@
+"""Online enhancement: live recordings pushed piece by piece through nhans_online_* (include/nhans_hip.h), the output
+bit for bit that of the offline path on the same normalised, trimmed samples.
+
+OnlineEnhancer works over engine.Engine (torch device memory, the engine's current stream) and lite.LiteEngine
+(torch-free, hiprt memory, the null stream).  The output contract lives in the header; out_counts() restates it in
+Python so that it can be checked without a device."""
+import ctypes
+import warnings
+
+import numpy as np
+
+from . import hip, spec
+
+LOOKAHEAD = spec.MIX_WIN // 2          # 17 frames
+
+
+def num_frames(n):
+    return 0 if n < spec.WIN else 1 + (n - spec.WIN) // spec.HOP
+
+
+def emitted(n, ended):
+    """Samples a stream of n pushed samples has emitted in total (include/nhans_hip.h: the output contract)."""
+    T = num_frames(n)
+    if ended:
+        return 0 if T == 0 else (T - 1) * spec.HOP + spec.WIN
+    R = max(0, T - LOOKAHEAD)
+    return spec.HOP * (R - R % 2)
+
+
+def out_counts(n_before, n_push, end=None, ended_before=None):
+    """Per-stream sample counts a push of n_push[i] samples (end[i]: the stream ends after them) reports, for streams
+    that had n_before[i] samples (ended_before[i]: and had ended) -- what nhans_online_out_counts computes."""
+    S = len(n_before)
+    end = end if end is not None else [False] * S
+    ended_before = ended_before if ended_before is not None else [False] * S
+    return [emitted(n_before[i] + n_push[i], bool(end[i] or ended_before[i])) - emitted(n_before[i], bool(ended_before[i]))
+            for i in range(S)]
+
+
+def latency_ms(fs=spec.FS):
+    """Algorithmic latency (ms) from a sample's arrival to its output: the 17-frame look-ahead plus one window, less or
+    more one hop for where the sample falls in its hop and for the even-pair rule of the iSTFT -> (185, 205) at 16 kHz."""
+    mid = (LOOKAHEAD * spec.HOP + spec.WIN) * 1000.0 / fs
+    return mid - spec.HOP * 1000.0 / fs, mid + spec.HOP * 1000.0 / fs
+
+
+def normalise_fixed(samples, peak):
+    """samples / (peak + 1e-6) in float64 -> float32: apply.normalise with a peak the live caller picks (dividing, not
+    multiplying by a gain: the rounding is that of the offline normalisation when peak = max|x|)."""
+    return (np.asarray(samples, dtype=np.float64) / (peak + 0.000001)).astype(np.float32)
+
+
+class OnlineEnhancer:
+    """S live recordings conditioned on ctx_a[i] / ctx_b[i] (normalised float32, >= 32,240 samples each; resnet_block
+    argument order as everywhere: denoiser (pos, neg), separator (noise, clean))."""
+
+    def __init__(self, engine, ctx_a, ctx_b, want_mixed=False):
+        if len(ctx_a) != len(ctx_b):
+            raise ValueError("ctx_a and ctx_b must have one recording per stream")
+        self.eng = engine
+        self.lib = hip.load()
+        self.S = len(ctx_a)
+        self.want_mixed = bool(want_mixed)
+        self._torch = hasattr(engine, "_stream")
+        self.handle = None
+        a, aoff = self._flat(ctx_a)
+        b, boff = self._flat(ctx_b)
+        da, db = self._up(a), self._up(b)
+        h = ctypes.c_void_p()
+        hip.check(self.lib.nhans_online_open(engine.handle, self.S, self._p(da), hip.i64_array(aoff), self._p(db),
+                                             hip.i64_array(boff), int(self.want_mixed), self._stream(), ctypes.byref(h)))
+        self.handle = h
+        self._free(da, db)
+        self.pushed = [0] * self.S
+        self.ended = [False] * self.S
+
+    # ---- device memory of either engine --------------------------------------------------------
+    @staticmethod
+    def _flat(arrays):
+        off = [0]
+        for x in arrays:
+            off.append(off[-1] + len(x))
+        flat = np.concatenate([np.asarray(x, dtype=np.float32) for x in arrays]) if len(arrays) else np.zeros(0, np.float32)
+        return np.ascontiguousarray(flat, dtype=np.float32), off
+
+    def _stream(self):
+        return self.eng._stream() if self._torch else None
+
+    def _up(self, arr):
+        if self._torch:
+            import torch
+            return torch.from_numpy(arr).to(self.eng.device)
+        from . import hiprt
+        return hiprt.DevBuf.from_array(arr)
+
+    def _empty(self, n):
+        if self._torch:
+            import torch
+            return torch.empty(max(n, 1), dtype=torch.float32, device=self.eng.device)
+        from . import hiprt
+        return hiprt.DevBuf(4 * max(n, 1))
+
+    def _p(self, buf):
+        return hip.ptr(buf) if self._torch else buf.ptr
+
+    def _down(self, buf, n):
+        if self._torch:
+            return buf[:n].cpu().numpy()
+        return buf.to_array(np.empty(n, np.float32)) if n else np.zeros(0, np.float32)
+
+    def _free(self, *bufs):
+        if not self._torch:
+            for b in bufs:
+                if b is not None:
+                    b.free()
+
+    def _set_precision(self, p):
+        if hasattr(self.eng, "set_precision"):
+            self.eng.set_precision(p)
+        else:
+            self.eng.set_option("precision", {"f32": 0, "f16x3": 1}[p])
+
+    # ---- the C ABI ---------------------------------------------------------------------------
+    def out_counts(self, counts, end=None):
+        """nhans_online_out_counts: what a push of counts[i] samples would emit per stream."""
+        out = (ctypes.c_int64 * self.S)()
+        endv = (ctypes.c_int * self.S)(*[int(bool(e)) for e in end]) if end is not None else None
+        hip.check(self.lib.nhans_online_out_counts(self.handle, hip.i64_array(counts), endv, out))
+        return list(out)
+
+    def rewind(self):
+        hip.check(self.lib.nhans_online_rewind(self.handle))
+        self.pushed, self.ended = self._prev
+
+    def _push_once(self, din, inoff, endv, counts):
+        ooff = [0]
+        for n in counts:
+            ooff.append(ooff[-1] + n)
+        dden = self._empty(ooff[-1])
+        dmix = self._empty(ooff[-1]) if self.want_mixed else None
+        got = (ctypes.c_int64 * self.S)()
+        hip.check(self.lib.nhans_online_push(self.handle, self._p(din), hip.i64_array(inoff), endv, self._p(dden),
+                                             self._p(dmix) if dmix is not None else None, hip.i64_array(ooff), got,
+                                             self._stream()))
+        return dden, dmix, ooff, list(got)
+
+    def push(self, chunks, end=None):
+        """chunks: one 1-D float32 array per stream (may be empty); end[i]: stream i ends after its chunk.  Returns
+        [(denoised, mixed)] per stream -- the samples that became final (mixed is None without want_mixed).  A push
+        that saturates the f16x3 path is undone and redone in f32 inside a calibrate bracket, as Engine.enhance does
+        for a batch."""
+        if len(chunks) != self.S:
+            raise ValueError("push: one chunk per stream (%d)" % self.S)
+        flat, inoff = self._flat(chunks)
+        counts = [inoff[i + 1] - inoff[i] for i in range(self.S)]
+        endv = (ctypes.c_int * self.S)(*[int(bool(e)) for e in end]) if end is not None else None
+        outc = self.out_counts(counts, end)
+        din = self._up(flat)
+        dden, dmix, ooff, got = self._push_once(din, inoff, endv, outc)
+        self._prev = (list(self.pushed), list(self.ended))
+        if self.eng.take_status() & hip.STATUS_SATURATED and self.eng.precision == "f16x3":
+            warnings.warn("N-HANS f16x3 path: an activation left the f16 range; batch recomputed in f32 MFMA mode "
+                          "and the activation exponents raised")
+            hip.check(self.lib.nhans_online_rewind(self.handle))
+            self._free(dden, dmix)
+            self.eng.set_option("calibrate", 1)
+            try:
+                self._set_precision("f32")
+                dden, dmix, ooff, got = self._push_once(din, inoff, endv, outc)
+                self.eng.take_status()
+            except BaseException:
+                try:
+                    self.eng.set_option("calibrate", 3)
+                finally:
+                    self._set_precision("f16x3")
+                raise
+            try:
+                self.eng.set_option("calibrate", 2)
+            except hip.NhansError as err:
+                warnings.warn("N-HANS: activation exponents not updated after the f32 rerun: %s" % err)
+            finally:
+                self._set_precision("f16x3")
+        assert got == outc, (got, outc)
+        den = self._down(dden, ooff[-1])
+        mix = self._down(dmix, ooff[-1]) if dmix is not None else None
+        self._free(din, dden, dmix)
+        for i in range(self.S):
+            self.pushed[i] += counts[i]
+            self.ended[i] = self.ended[i] or bool(end is not None and end[i])
+        return [(den[ooff[i]:ooff[i + 1]], mix[ooff[i]:ooff[i + 1]] if mix is not None else None) for i in range(self.S)]
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.nhans_online_close(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
