@@ -250,7 +250,33 @@ uint32_t nhans_crc32c(uint32_t crc, const void* data_host, size_t nbytes);
  * objects of the same context may be interleaved with pushes.  A push whose ready frames exceed "frames_per_chunk" runs
  * the stack in several passes inside the call.  The object owns its state (about 89 KB per online stream, twice: the
  * slot a push reads and the slot it writes) and the embeddings; the context's workspace serves each push while it runs.
- * Objects are closed (nhans_online_close) BEFORE nhans_destroy(ctx). */
+ * Objects are closed (nhans_online_close) BEFORE nhans_destroy(ctx).
+ *
+ * Slots.  A slot is one of the S stream positions of an object, and it outlives the streams that pass through it:
+ *   open       nhans_online_open: S conditioned slots, each an open stream of 0 samples.  nhans_online_open_slots: S
+ *              unconditioned slots, no tower run (what a long-lived service object starts as).
+ *   join       nhans_online_restart (the slot becomes an open stream of 0 samples) + nhans_online_set_context or
+ *              nhans_online_set_embeddings (the slot's conditioning; the slot is "conditioned" from then on).
+ *   run        pushes.  A slot nobody uses gets 0 samples in every push and reports 0: it adds no frames, hence no STFT,
+ *              stack or iSTFT work; only the per-pass conditioning kernel still touches all S embedding row pairs.
+ *   leave      end_host in a push (the tail is flushed, the output has the offline length), or nhans_online_restart
+ *              (the samples not emitted yet are dropped: the output is the first 160 * P samples of the offline one).
+ *   again      a slot that has ended, or was abandoned, is taken over by the next join; conditioning survives a restart.
+ * Pushing samples or an end to an unconditioned slot is NHANS_EINVAL.  nhans_online_out_counts follows the slot's
+ * current stream.  The slot count is fixed when the object is opened.
+ *
+ * Changing the conditioning of a running stream (the set functions alone, no restart).  Let R be the number of frames of
+ * the slot's stream already computed when the call is made (R above; T once the stream has ended): the call reports it.
+ * Frames >= R are computed with the new conditioning, frames < R have used the old one.  The iSTFT packs frames
+ * (2k, 2k+1) of a stream into one complex transform, so a frame's waveform bits can depend on its partner's data
+ * (about 1e-7).  With B = R rounded down to even, B' = R rounded up to even, and den1 / den2 the outputs of
+ * nhans_enhance_clips for the whole trimmed recording under the old / the new conditioning:
+ *   - output samples [0, 160 * B) are bit for bit den1;
+ *   - output samples [160 * B' + 240, end) are bit for bit den2;
+ *   - R = 0: the whole output is den2.  R = the stream's final frame count: the whole output is den1;
+ *   - the at most 560 samples between are finite and otherwise unspecified (a cross-fade of the two by the synthesis
+ *     window, up to the pair effect);
+ *   - the mixed round trip does not depend on conditioning and stays bit for bit the offline one. */
 typedef struct nhans_online nhans_online;
 
 /* Opens an object of `nstreams` (>= 1) online streams.  Stream i is conditioned on clips i of ctx_a / ctx_b, with the
@@ -261,11 +287,38 @@ int nhans_online_open(nhans_ctx* ctx, int nstreams, const float* ctx_a_wav_dev, 
                       const float* ctx_b_wav_dev, const int64_t* ctx_b_offsets_host, int want_mixed, void* stream,
                       nhans_online** out);
 
+/* Opens an object of `nslots` (>= 1) slots without conditioning: every slot is an open stream of 0 samples that accepts
+ * only 0-sample pushes until one of the set functions below has given it conditioning.  No tower runs; the embedding
+ * rows are zero-filled. */
+int nhans_online_open_slots(nhans_ctx* ctx, int nslots, int want_mixed, void* stream, nhans_online** out);
+
+/* Host only.  Slot `slot` becomes an open stream of 0 samples, whatever it was: ended, or still running (its samples
+ * not emitted yet are dropped).  Its conditioning is kept.  Nothing is cleared on the device: a fresh stream reads none
+ * of the old state. */
+int nhans_online_restart(nhans_online* obj, int slot);
+
+/* Conditions slot `slot` on two recordings (rules of nhans_online_open: at least 32,240 samples each, else
+ * NHANS_ESHORT; the first 200 frames; the same (a, b) order): STFT and embedding tower for this slot alone.
+ * *first_frame_out (nullable) receives R of the section above: frames >= R of the slot's stream use the new
+ * conditioning.  On any error the slot's conditioning and stream are unchanged. */
+int nhans_online_set_context(nhans_online* obj, int slot, const float* ctx_a_wav_dev, int64_t na,
+                             const float* ctx_b_wav_dev, int64_t nb, void* stream, int64_t* first_frame_out);
+
+/* The same with two ready [512] rows (what nhans_embed returns), so that the towers can run elsewhere -- another
+ * context, another hipStream_t -- and a join does not stall this context's pushes. */
+int nhans_online_set_embeddings(nhans_online* obj, int slot, const float* emb_a_dev, const float* emb_b_dev,
+                                void* stream, int64_t* first_frame_out);
+
+/* nhans_online_restart and the two set functions make the last push final: nhans_online_rewind after one of them
+ * returns NHANS_EINVAL until the next push.  A slot out of range, a NULL object or a NULL pointer that is needed:
+ * NHANS_EINVAL with the function's name in nhans_last_error(). */
+
 /* Appends in_offsets_host[i+1] - in_offsets_host[i] (>= 0) normalised float32 samples of in_dev to stream i; end_host
  * (nullable) != 0 ends stream i after them.  Writes every output sample that is now final: out_counts_host[i] samples
  * at den_out_dev + out_offsets_host[i] (and, with want_mixed, at mixed_out_dev + out_offsets_host[i]); the caller's
  * room out_offsets_host[i+1] - out_offsets_host[i] must hold them (nhans_online_out_counts), else NHANS_EINVAL.
- * Pushing to an ended stream, a negative count or a NULL that is needed: NHANS_EINVAL, and nothing changes. */
+ * Pushing to an ended stream, samples or an end to an unconditioned slot, a negative count or a NULL that is needed:
+ * NHANS_EINVAL, and nothing changes. */
 int nhans_online_push(nhans_online* obj, const float* in_dev, const int64_t* in_offsets_host, const int* end_host,
                       float* den_out_dev, float* mixed_out_dev, const int64_t* out_offsets_host,
                       int64_t* out_counts_host, void* stream);
@@ -277,7 +330,8 @@ int nhans_online_out_counts(const nhans_online* obj, const int64_t* in_counts_ho
 
 /* Undoes the most recent push -- device state, sample / frame counts and ended flags -- so that it can be redone (a push
  * that raised NHANS_STATUS_SATURATED at precision 1 is redone at precision 0 inside a "calibrate" bracket).  Once per
- * push: a second rewind, or one before any push, returns NHANS_EINVAL. */
+ * push: a second rewind, one before any push, or one after a restart / set call that followed the push, returns
+ * NHANS_EINVAL.  A rewind never brings back a stream that nhans_online_restart replaced. */
 int nhans_online_rewind(nhans_online* obj);
 
 void nhans_online_close(nhans_online* obj);

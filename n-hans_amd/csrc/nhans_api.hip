@@ -1383,6 +1383,9 @@ int nhans_profile_json(nhans_ctx* c, char* buf, size_t buflen) {
 // look-ahead rows that exist, every row the iSTFT still needs), and the denoised rows [S0(P), R) (<= 24: computed, not
 // yet synthesised, and those the next synthesis restarts from).  A push reads slot `cur` and writes the other slot
 // whole; nhans_online_rewind flips back.
+// nhans_online_restart clears nothing on the device: a stream of N = 0, T = 0 has no carried samples, lo = S0 = R = 0 and
+// no row below T, so its first push reads nothing of slot `cur` (every run taken from the state is empty) and writes the
+// other slot from the push alone.  The same holds for the slots of nhans_online_open_slots, whose state is never filled.
 namespace {
 constexpr int kOnRows = 2 * kCenter + kIstftHopsPerBlock - 14;  // 42 >= 17 + 24
 constexpr int kOnDenRows = kIstftHopsPerBlock + 2;              // 24
@@ -1412,11 +1415,29 @@ struct nhans_online {
     float* state = nullptr;     // [2][S][kOnSlot]
     int cur = 0;
     std::vector<OnStream> st, prev;
+    std::vector<char> cond;     // slot has conditioning (nhans_online_open: all; nhans_online_open_slots: none yet)
     bool can_rewind = false;
     float* slot(int k, int i) const { return state + ((size_t)k * S + i) * kOnSlot; }
 };
 
 namespace {
+
+// The object and its device memory; on failure nothing is left allocated.
+int online_alloc(nhans_ctx* c, int S, int want_mixed, bool conditioned, const char* fn, nhans_online** out) {
+    nhans_online* o = new nhans_online();
+    o->c = c; o->device = c->device; o->S = S; o->mixed = want_mixed != 0;
+    o->st.assign(S, OnStream()); o->prev = o->st;
+    o->cond.assign(S, conditioned ? 1 : 0);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->emb), (size_t)2 * S * kEmb * 4);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&o->state), (size_t)2 * S * kOnSlot * 4);
+    if (e != hipSuccess) {
+        if (o->emb) (void)hipFree(o->emb);
+        delete o;
+        return fail(NHANS_ENOMEM, std::string(fn) + ": hipMalloc failed: " + hipGetErrorString(e));
+    }
+    *out = o;
+    return NHANS_OK;
+}
 
 int online_open_body(nhans_ctx* c, int S, const float* ca, const int64_t* caoff, const float* cbw, const int64_t* cboff,
                      int want_mixed, hipStream_t s, nhans_online** out) {
@@ -1436,20 +1457,77 @@ int online_open_body(nhans_ctx* c, int S, const float* ca, const int64_t* caoff,
     rc = stft_impl(c, ca, caoff, S, kCtxFrames, ctxlm, nullptr, tabs[0], blks[0], nullptr, s); if (rc) return rc;
     rc = stft_impl(c, cbw, cboff, S, kCtxFrames, ctxlm + (size_t)S * kCtxFrames * kBins, nullptr, tabs[1], blks[1], nullptr, s);
     if (rc) return rc;
-    nhans_online* o = new nhans_online();
-    o->c = c; o->device = c->device; o->S = S; o->mixed = want_mixed != 0;
-    o->st.assign(S, OnStream()); o->prev = o->st;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->emb), (size_t)2 * S * kEmb * 4);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&o->state), (size_t)2 * S * kOnSlot * 4);
-    if (e != hipSuccess) {
-        if (o->emb) (void)hipFree(o->emb);
-        delete o;
-        return fail(NHANS_ENOMEM, std::string("nhans_online_open: hipMalloc failed: ") + hipGetErrorString(e));
-    }
+    nhans_online* o = nullptr;
+    rc = online_alloc(c, S, want_mixed, true, "nhans_online_open", &o); if (rc) return rc;
     rc = embed_impl(c, ctxlm, 2 * S, o->emb, X, A, Y, s);
     if (rc) { (void)hipFree(o->emb); (void)hipFree(o->state); delete o; return rc; }
     *out = o;
     return NHANS_OK;
+}
+
+int online_open_slots_body(nhans_ctx* c, int S, int want_mixed, hipStream_t s, nhans_online** out) {
+    if (!out) return fail(NHANS_EINVAL, "nhans_online_open_slots: null argument");
+    *out = nullptr;
+    if (S < 1) return fail(NHANS_EINVAL, "nhans_online_open_slots: nslots must be >= 1");
+    nhans_online* o = nullptr;
+    int rc = online_alloc(c, S, want_mixed, false, "nhans_online_open_slots", &o); if (rc) return rc;
+    // (the conditioning kernel of every pass reads all S row pairs: idle rows are zeros, not uninitialised memory)
+    const hipError_t e = hipMemsetAsync(o->emb, 0, (size_t)2 * S * kEmb * 4, s);
+    if (e != hipSuccess) {
+        (void)hipFree(o->emb); (void)hipFree(o->state); delete o;
+        return fail(NHANS_EHIP, std::string("nhans_online_open_slots: hipMemsetAsync: ") + hipGetErrorString(e));
+    }
+    *out = o;
+    return NHANS_OK;
+}
+
+int online_slot_check(const nhans_online* o, int slot, const char* fn) {
+    if (slot < 0 || slot >= o->S)
+        return fail(NHANS_EINVAL, std::string(fn) + ": slot " + std::to_string(slot) + " outside [0, " + std::to_string(o->S) + ")");
+    return NHANS_OK;
+}
+
+// Rows `slot` (a) and S + `slot` (b) of the embeddings <- two [512] device rows, ordered on s after whatever made them.
+// Frames already computed keep the conditioning they were computed with: *first_frame is the first that will not.
+int online_set_rows(nhans_online* o, int slot, const float* row_a, const float* row_b, hipStream_t s, int64_t* first_frame) {
+    HIP_TRY(hipMemcpyAsync(o->emb + (size_t)slot * kEmb, row_a, kEmb * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(o->emb + (size_t)(o->S + slot) * kEmb, row_b, kEmb * 4, hipMemcpyDeviceToDevice, s));
+    o->cond[slot] = 1;
+    o->can_rewind = false;
+    if (first_frame) *first_frame = on_ready(o->st[slot].T, o->st[slot].ended);
+    return NHANS_OK;
+}
+
+int online_set_context_body(nhans_online* o, int slot, const float* ca, int64_t na, const float* cbw, int64_t nb_,
+                            hipStream_t s, int64_t* first_frame) {
+    nhans_ctx* c = o->c;
+    int rc = online_slot_check(o, slot, "nhans_online_set_context"); if (rc) return rc;
+    if (!ca || !cbw) return fail(NHANS_EINVAL, "nhans_online_set_context: null argument");
+    if (na < 0 || nb_ < 0) return fail(NHANS_EINVAL, "nhans_online_set_context: negative sample count");
+    const int64_t aoff[2] = {0, na}, boff[2] = {0, nb_};
+    const size_t nb = std::max(stft_blocks(aoff, 1, kCtxFrames), stft_blocks(boff, 1, kCtxFrames));
+    const size_t tb = tower_buf_floats(c);
+    rc = ws_reserve(c, ws_size((size_t)2 * kCtxFrames * kBins, 4) + ws_size(2 * kEmb, 4) + 2 * ws_size(4, 8) +
+                           2 * ws_size(2 * nb, 4) + 3 * ws_size(tb, 4));
+    if (rc) return rc;
+    float* ctxlm = ws_take<float>(c, (size_t)2 * kCtxFrames * kBins);
+    float* rows = ws_take<float>(c, 2 * kEmb);
+    int64_t* tabs[2]; int* blks[2];
+    for (int i = 0; i < 2; ++i) { tabs[i] = ws_take<int64_t>(c, 4); blks[i] = ws_take<int>(c, 2 * nb); }
+    float* X = ws_take<float>(c, tb); float* A = ws_take<float>(c, tb); float* Y = ws_take<float>(c, tb);
+    rc = stft_impl(c, ca, aoff, 1, kCtxFrames, ctxlm, nullptr, tabs[0], blks[0], nullptr, s); if (rc) return rc;
+    rc = stft_impl(c, cbw, boff, 1, kCtxFrames, ctxlm + (size_t)kCtxFrames * kBins, nullptr, tabs[1], blks[1], nullptr, s);
+    if (rc) return rc;
+    // (the tower writes workspace rows, not the object's: a failure leaves the slot's conditioning as it was)
+    rc = embed_impl(c, ctxlm, 2, rows, X, A, Y, s); if (rc) return rc;
+    if (launch_error_pending()) return NHANS_OK;          // (reported by the entry point; the slot keeps its rows)
+    return online_set_rows(o, slot, rows, rows + kEmb, s, first_frame);
+}
+
+int online_set_embeddings_body(nhans_online* o, int slot, const float* ea, const float* eb, hipStream_t s, int64_t* first_frame) {
+    const int rc = online_slot_check(o, slot, "nhans_online_set_embeddings"); if (rc) return rc;
+    if (!ea || !eb) return fail(NHANS_EINVAL, "nhans_online_set_embeddings: null argument");
+    return online_set_rows(o, slot, ea, eb, s, first_frame);
 }
 
 // One push; see include/nhans_hip.h.  Host plan first (every count, offset and copy run), then the launches:
@@ -1479,6 +1557,9 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
         p.en = end && end[i];
         if (q.ended && (p.cnt > 0 || p.en))
             return fail(NHANS_EINVAL, "nhans_online_push: stream " + std::to_string(i) + " has ended");
+        if (!o->cond[i] && (p.cnt > 0 || p.en))
+            return fail(NHANS_EINVAL, "nhans_online_push: slot " + std::to_string(i) + " has no conditioning yet " +
+                                      "(nhans_online_set_context / nhans_online_set_embeddings)");
         p.Nn = q.N + p.cnt;
         p.Tn = nhans_num_frames(p.Nn);
         if (p.Tn > kMaxFramesPerClip)
@@ -1684,6 +1765,36 @@ int nhans_online_open(nhans_ctx* c, int nstreams, const float* ca, const int64_t
     Call call(c, stream);
     if (call.rc) return call.rc;
     return call.finish(online_open_body(c, nstreams, ca, caoff, cbw, cboff, want_mixed, call.s, out));
+}
+
+int nhans_online_open_slots(nhans_ctx* c, int nslots, int want_mixed, void* stream, nhans_online** out) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(online_open_slots_body(c, nslots, want_mixed, call.s, out));
+}
+
+int nhans_online_restart(nhans_online* o, int slot) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_online_restart: null object");
+    const int rc = online_slot_check(o, slot, "nhans_online_restart"); if (rc) return rc;
+    o->st[slot] = OnStream();
+    o->can_rewind = false;
+    return NHANS_OK;
+}
+
+int nhans_online_set_context(nhans_online* o, int slot, const float* ca, int64_t na, const float* cbw, int64_t nb,
+                             void* stream, int64_t* first_frame_out) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_online_set_context: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(online_set_context_body(o, slot, ca, na, cbw, nb, call.s, first_frame_out));
+}
+
+int nhans_online_set_embeddings(nhans_online* o, int slot, const float* ea, const float* eb, void* stream,
+                                int64_t* first_frame_out) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_online_set_embeddings: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(online_set_embeddings_body(o, slot, ea, eb, call.s, first_frame_out));
 }
 
 int nhans_online_push(nhans_online* o, const float* in, const int64_t* inoff, const int* end, float* den_out,

@@ -22,7 +22,8 @@ EXPORTS = [
     "nhans_profile_json", "nhans_profile_reset", "nhans_take_status", "nhans_debug_launch_probe", "nhans_crc32c",
     "nhans_debug_mfma_ceiling", "nhans_set_activation_exponents", "nhans_get_activation_exponents",
     "nhans_get_activation_amax", "nhans_online_open", "nhans_online_push", "nhans_online_out_counts",
-    "nhans_online_rewind", "nhans_online_close",
+    "nhans_online_rewind", "nhans_online_close", "nhans_online_open_slots", "nhans_online_restart",
+    "nhans_online_set_context", "nhans_online_set_embeddings",
 ]
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25
@@ -90,13 +91,23 @@ def load():
         lib.nhans_online_rewind.argtypes = [vp]
         lib.nhans_online_close.argtypes = [vp]
         lib.nhans_online_close.restype = None
+    # (slot reuse and live conditioning came one change after the online functions: the library of that one commit,
+    # as $NHANS_LIB in an A/B against it, has the five above and not these)
+    slots = online and hasattr(lib, "nhans_online_open_slots")
+    if slots:
+        lib.nhans_online_open_slots.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(vp)]
+        lib.nhans_online_restart.argtypes = [vp, ctypes.c_int]
+        lib.nhans_online_set_context.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, i64p]
+        lib.nhans_online_set_embeddings.argtypes = [vp, ctypes.c_int, vp, vp, vp, i64p]
     lib.nhans_crc32c.argtypes = [ctypes.c_uint32, vp, ctypes.c_size_t]
     lib.nhans_crc32c.restype = ctypes.c_uint32
     for name in ("nhans_create", "nhans_create_ex", "nhans_set_option", "nhans_stft_features", "nhans_embed", "nhans_mask_net",
                  "nhans_istft", "nhans_enhance_clips", "nhans_debug_block_output", "nhans_profile_json",
                  "nhans_profile_reset", "nhans_take_status", "nhans_debug_launch_probe",
                  "nhans_set_activation_exponents", "nhans_get_activation_exponents", "nhans_get_activation_amax") + (
-                 ("nhans_online_open", "nhans_online_push", "nhans_online_out_counts", "nhans_online_rewind") if online else ()):
+                 ("nhans_online_open", "nhans_online_push", "nhans_online_out_counts", "nhans_online_rewind") if online else ()) + (
+                 ("nhans_online_open_slots", "nhans_online_restart", "nhans_online_set_context",
+                  "nhans_online_set_embeddings") if slots else ()):
         getattr(lib, name).restype = ctypes.c_int
     if lib.nhans_abi_version() != ABI_VERSION:
         raise NhansError("libnhans_hip.so ABI version mismatch")

@@ -37,6 +37,15 @@ def out_counts(n_before, n_push, end=None, ended_before=None):
             for i in range(S)]
 
 
+def change_bounds(R):
+    """(last_old_sample_excl, first_new_sample) of a change of conditioning that reported first frame R (include/
+    nhans_hip.h, the mid-stream contract): output samples below the first are bit for bit the offline output under the
+    old conditioning, samples from the second on that under the new one.  The iSTFT transforms frames in pairs
+    (2k, 2k+1), so the old side stops at the pair that holds frame R and the new side starts after it, one window
+    overlap (400 - 160) later.  R = 0 and R = the final frame count are whole-output cases the caller knows about."""
+    return spec.HOP * (R - R % 2), spec.HOP * (R + R % 2) + spec.WIN - spec.HOP
+
+
 def latency_ms(fs=spec.FS):
     """Algorithmic latency (ms) from a sample's arrival to its output: the 17-frame look-ahead plus one window, less or
     more one hop for where the sample falls in its hop and for the even-pair rule of the iSTFT -> (185, 205) at 16 kHz."""
@@ -52,17 +61,28 @@ def normalise_fixed(samples, peak):
 
 class OnlineEnhancer:
     """S live recordings conditioned on ctx_a[i] / ctx_b[i] (normalised float32, >= 32,240 samples each; resnet_block
-    argument order as everywhere: denoiser (pos, neg), separator (noise, clean))."""
+    argument order as everywhere: denoiser (pos, neg), separator (noise, clean)).
+
+    The S positions are slots that outlive their streams (include/nhans_hip.h, "Slots"): open_slots() makes an object of
+    unconditioned slots, restart(i) + set_context(i, a, b) lets a new recording join in slot i, end in a push or
+    restart(i) lets it leave, set_context / set_embeddings alone change the conditioning of a running stream."""
+
+    def _begin(self, engine, S, want_mixed):
+        self.eng = engine
+        self.lib = hip.load()
+        self.S = S
+        self.want_mixed = bool(want_mixed)
+        self._torch = hasattr(engine, "_stream")
+        self.handle = None
+        self.pushed = [0] * S
+        self.ended = [False] * S
+        self._prev = None
 
     def __init__(self, engine, ctx_a, ctx_b, want_mixed=False):
         if len(ctx_a) != len(ctx_b):
             raise ValueError("ctx_a and ctx_b must have one recording per stream")
-        self.eng = engine
-        self.lib = hip.load()
-        self.S = len(ctx_a)
-        self.want_mixed = bool(want_mixed)
-        self._torch = hasattr(engine, "_stream")
-        self.handle = None
+        self._begin(engine, len(ctx_a), want_mixed)
+        self.conditioned = [True] * self.S
         a, aoff = self._flat(ctx_a)
         b, boff = self._flat(ctx_b)
         da, db = self._up(a), self._up(b)
@@ -71,8 +91,17 @@ class OnlineEnhancer:
                                              hip.i64_array(boff), int(self.want_mixed), self._stream(), ctypes.byref(h)))
         self.handle = h
         self._free(da, db)
-        self.pushed = [0] * self.S
-        self.ended = [False] * self.S
+
+    @classmethod
+    def open_slots(cls, engine, nslots, want_mixed=False):
+        """An object of nslots unconditioned slots (nhans_online_open_slots): no tower runs until a set_context."""
+        self = cls.__new__(cls)
+        self._begin(engine, int(nslots), want_mixed)
+        self.conditioned = [False] * self.S
+        h = ctypes.c_void_p()
+        hip.check(self.lib.nhans_online_open_slots(engine.handle, self.S, int(self.want_mixed), self._stream(), ctypes.byref(h)))
+        self.handle = h
+        return self
 
     # ---- device memory of either engine --------------------------------------------------------
     @staticmethod
@@ -131,6 +160,54 @@ class OnlineEnhancer:
     def rewind(self):
         hip.check(self.lib.nhans_online_rewind(self.handle))
         self.pushed, self.ended = self._prev
+
+    def restart(self, i):
+        """Slot i becomes an open stream of 0 samples (nhans_online_restart); conditioning is kept."""
+        hip.check(self.lib.nhans_online_restart(self.handle, int(i)))
+        self.pushed[i], self.ended[i] = 0, False
+
+    def first_new_frame(self, i):
+        """R of slot i: the frames of its stream already computed, which a change of conditioning leaves as they are."""
+        T = num_frames(self.pushed[i])
+        return T if self.ended[i] else max(0, T - LOOKAHEAD)
+
+    def set_context(self, i, ctx_a, ctx_b):
+        """Conditions slot i on two recordings (nhans_online_set_context).  Returns R: frames >= R of the slot's stream
+        use the new conditioning (change_bounds(R) for what that means in samples)."""
+        a = np.ascontiguousarray(ctx_a, dtype=np.float32)
+        b = np.ascontiguousarray(ctx_b, dtype=np.float32)
+        da, db = self._up(a), self._up(b)
+        R = ctypes.c_int64(-1)
+        try:
+            hip.check(self.lib.nhans_online_set_context(self.handle, int(i), self._p(da), len(a), self._p(db), len(b),
+                                                        self._stream(), ctypes.byref(R)))
+        finally:
+            self._free(da, db)
+        self.conditioned[i] = True
+        return int(R.value)
+
+    def set_embeddings(self, i, emb_a, emb_b):
+        """The same with two ready [512] rows (Engine.embed; host arrays or, over Engine, device tensors)."""
+        rows = []
+        for e in (emb_a, emb_b):
+            if self._torch and hasattr(e, "data_ptr"):
+                import torch
+                e = e.detach().to(device=self.eng.device, dtype=torch.float32).contiguous().reshape(-1)
+            else:
+                e = self._up(np.ascontiguousarray(e, dtype=np.float32).reshape(-1))
+            rows.append(e)
+        n = [r.numel() if hasattr(r, "numel") else r.nbytes // 4 for r in rows]
+        if n != [spec.EMB, spec.EMB]:
+            self._free(*[r for r in rows if not hasattr(r, "numel")])
+            raise ValueError("set_embeddings: two rows of %d floats" % spec.EMB)
+        R = ctypes.c_int64(-1)
+        try:
+            hip.check(self.lib.nhans_online_set_embeddings(self.handle, int(i), self._p(rows[0]), self._p(rows[1]),
+                                                           self._stream(), ctypes.byref(R)))
+        finally:
+            self._free(*[r for r in rows if not hasattr(r, "numel")])
+        self.conditioned[i] = True
+        return int(R.value)
 
     def _push_once(self, din, inoff, endv, counts):
         ooff = [0]

@@ -4,7 +4,18 @@ H hops (H x 10 ms of audio per stream), f16x3, synthetic weights.  One JSON line
   kernel_ms_per_push  sum of the per-kernel hipEvent times of nhans_profile_json over a separate profiled pass
   realtime_factor     S x pushed audio seconds / p50 push time (streams one GPU keeps up with per ... of real time)
   latency_ms          the algorithmic latency range from the output contract (look-ahead + one window, +- one hop)
-    python tools/online_bench.py [--streams 1,8,64,256] [--hops 1,4,16] [--pushes 60]"""
+    python tools/online_bench.py [--streams 1,8,64,256] [--hops 1,4,16] [--pushes 60]
+
+--churn: a long-lived object whose callers come and go (nhans_online_open_slots).  Per (slots S, active k) it prints
+three lines, each with push p50 / p99 over the same pushes of H hops per active stream:
+  mode "fixed"   a k-stream nhans_online_open object (what k callers cost when nobody joins or leaves; this mode also
+                 runs on a library from before the slot functions: $NHANS_LIB, for a same-box A/B)
+  mode "slots"   S slots, k of them active, nobody joins or leaves (idle slots should be free)
+                 (both with kernel_ms_per_push, cond_proj_ms_per_push and launches_per_push from a profiled pass)
+  mode "churn"   the same, and every J-th push one stream leaves with `end` and one joins an idle slot (restart + by
+                 turns set_context and set_embeddings); the wall time of the two set calls, each followed by a device
+                 synchronise, is reported on its own (p50 over the joins; set_embeddings gets rows computed beforehand)
+    python tools/online_bench.py --churn [--slots 64,256] [--active 16] [--every 8] [--hops 1] [--pushes 240] [--out F]"""
 import argparse
 import json
 import os
@@ -20,12 +31,121 @@ import nhans_amd  # noqa: E402,F401
 from nhans_amd import apply, engine, hip, online, spec, synth  # noqa: E402
 
 
+def _timed(fn):
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def churn(a):
+    eng = engine.Engine("denoiser", precision="f16x3")
+    ca, cb = apply.normalise(synth.silent()), apply.normalise(synth.noise_context(1))
+    audio = apply.normalise(synth.mixture(1, 30.0))
+    H = int(a.hops.split(",")[0])
+    n = H * spec.HOP
+    k = a.active
+    empty = np.zeros(0, np.float32)
+    has_slots = hasattr(hip.load(), "nhans_online_open_slots")
+    rows = None
+    if has_slots:
+        wav = torch.from_numpy(np.concatenate([ca, cb])).to(eng.device)
+        lm, _ = eng.stft_features(wav, [0, len(ca), len(ca) + len(cb)], max_frames=spec.NOISE_WIN, want_phase=False)
+        rows = eng.embed(lm.reshape(2, spec.NOISE_WIN, spec.BINS))
+    out = open(a.out, "a") if a.out else None
+
+    def report(mode, S, ts, extra):
+        p50, p99 = float(np.percentile(ts, 50)), float(np.percentile(ts, 99))
+        line = {"mode": mode, "slots": S, "active": k, "hops_per_push": H, "push_audio_ms": H * 10,
+                "push_ms_p50": round(p50, 3), "push_ms_p99": round(p99, 3), "pushes": len(ts),
+                "realtime_factor": round(k * H * 0.010 / (p50 / 1e3), 2)}
+        line.update(extra)
+        line.update({"lib": os.path.basename(os.environ.get("NHANS_LIB") or "tree"), "precision": "f16x3",
+                     "weights": "synthetic seed 7"})
+        print(json.dumps(line), flush=True)
+        if out:
+            out.write(json.dumps(line) + "\n")
+            out.flush()
+
+    for S in [int(s) for s in a.slots.split(",")]:
+        for mode in ("fixed", "slots", "churn"):
+            if mode != "fixed" and not has_slots:
+                continue
+            if mode == "fixed":
+                enh = online.OnlineEnhancer(eng, [ca] * k, [cb] * k)
+                active, idle = list(range(k)), []
+            else:
+                enh = online.OnlineEnhancer.open_slots(eng, S)
+                active, idle = list(range(k)), list(range(k, S))
+                for i in active:
+                    enh.set_context(i, ca, cb)
+            pos = [0]
+
+            def push(leaver=None):
+                i = pos[0] % (len(audio) - n)
+                pos[0] += n
+                chunks, end = [empty] * enh.S, [False] * enh.S
+                for j in active:
+                    chunks[j] = audio[i:i + n]
+                if leaver is not None:
+                    end[leaver] = True
+                enh.push(chunks, end)
+
+            for _ in range(40):
+                push()
+            torch.cuda.synchronize()
+            ts, t_ctx, t_emb = [], [], []
+            for it in range(a.pushes):
+                leaver = active[0] if mode == "churn" and it % a.every == a.every - 1 else None
+                ts.append(_timed(lambda: push(leaver)))
+                if leaver is not None:
+                    active.pop(0)
+                    idle.append(leaver)
+                    j = idle.pop(0)
+                    enh.restart(j)
+                    if len(t_ctx) <= len(t_emb):
+                        t_ctx.append(_timed(lambda: enh.set_context(j, ca, cb)))
+                    else:
+                        t_emb.append(_timed(lambda: enh.set_embeddings(j, rows[0], rows[1])))
+                    active.append(j)
+            extra = {}
+            if mode != "churn":
+                # where a difference between "fixed" and "slots" comes from: device time (and cond_proj's share of it,
+                # the one kernel whose grid follows the slot count) against the host side of a push
+                eng.set_option("profile", 1)
+                eng.profile_reset()
+                for _ in range(10):
+                    push()
+                prof = eng.profile()
+                eng.set_option("profile", 0)
+                extra = {"kernel_ms_per_push": round(sum(v["ms"] for v in prof.values()) / 10, 3),
+                         "cond_proj_ms_per_push": round(prof.get("cond_proj", {"ms": 0.0})["ms"] / 10, 4),
+                         "launches_per_push": sum(v["calls"] for v in prof.values()) / 10}
+            enh.close()
+            if mode == "churn":
+                extra = {"churn_every": a.every, "joins": len(t_ctx) + len(t_emb),
+                         "set_context_ms_p50": round(float(np.percentile(t_ctx, 50)), 3) if t_ctx else None,
+                         "set_context_ms_max": round(float(np.max(t_ctx)), 3) if t_ctx else None,
+                         "set_embeddings_ms_p50": round(float(np.percentile(t_emb, 50)), 3) if t_emb else None,
+                         "set_embeddings_ms_max": round(float(np.max(t_emb)), 3) if t_emb else None}
+            report(mode, S, ts, extra)
+    eng.close()
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--churn", action="store_true", help="slots that callers join and leave (see the top of this file)")
+    ap.add_argument("--slots", default="64,256")
+    ap.add_argument("--active", type=int, default=16)
+    ap.add_argument("--every", type=int, default=8, help="--churn: one stream leaves and one joins every this many pushes")
+    ap.add_argument("--out", default=None, help="--churn: also append the JSON lines to this file")
     ap.add_argument("--streams", default="1,8,64,256")
     ap.add_argument("--hops", default="1,4,16")
     ap.add_argument("--pushes", type=int, default=60, help="timed pushes per shape (after 40 warm-up pushes)")
     a = ap.parse_args()
+    if a.churn:
+        return churn(a)
     eng = engine.Engine("denoiser", precision="f16x3")
     ca, cb = apply.normalise(synth.silent()), apply.normalise(synth.noise_context(1))
     audio = apply.normalise(synth.mixture(1, 30.0))
