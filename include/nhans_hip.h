@@ -336,6 +336,79 @@ int nhans_online_rewind(nhans_online* obj);
 
 void nhans_online_close(nhans_online* obj);
 
+/* ---- Sample-rate conversion and the file front end -------------------------------------------------------------------
+ * Everything above takes 16 kHz, already normalised float32.  Capture devices deliver int16 PCM at 48 or 44.1 kHz; the
+ * reference's packaged tool converts other formats with sox before it starts (its README.md:42).  The functions below
+ * are that converter on the device: stateless for files (nhans_resample), with carried state for live streams
+ * (nhans_resampler_*), and the reference's peak normalisation (nhans_peak_normalise <- normalise(), SN/apply.py:150-155).
+ * They were added without moving NHANS_ABI_VERSION; a caller that may meet an older library looks them up by symbol.
+ *
+ * For rate_in -> rate_out: g = gcd, L = rate_out / g, M = rate_in / g, half = 10 * max(L, M).  The filter is the one
+ * scipy.signal.resample_poly(x, L, M) designs by default: h = firwin(2 * half + 1, 1 / max(L, M), window = ('kaiser',
+ * 5.0)) * L, computed inside the library in double.  Output m of an n-sample clip is
+ *     y[m] = sum_k h[m * M + half - k * L] * x[k]       0 <= m < ceil(n * L / M),   x outside [0, n) reads as 0
+ * with the taps rounded to float32 once and every output ONE chain of fmaf in float32 in a fixed tap order -- the same
+ * instructions whether the samples arrive in one call or piece by piece.
+ * Supported pairs: one side 16000 Hz, the other 8000, 11025, 12000, 22050, 24000, 32000, 44100, 48000, 88200 or 96000 Hz;
+ * 16000 -> 16000 is accepted and copies.  Any other pair: NHANS_EINVAL with the two rates in nhans_last_error(). */
+#define NHANS_PCM_INT16 0
+#define NHANS_PCM_FLOAT32 1
+#define NHANS_RESAMPLE_QUANTISE 1     /* outputs rounded to the int16 grid (ties to even, as np.round) and clipped to
+                                         [-32768, 32767], still stored as float32: what a converter that writes a 16-bit
+                                         file, then reads it, hands on */
+#define NHANS_NORMALISE_WRAP_INT16 1  /* the peak search takes |-32768| as -32768: np.abs of an int16 array, which is what
+                                         the reference's normalise() sees for a mono 16-bit file */
+
+/* Host only.  ceil(n * L / M), the output length of an n-sample clip; negative (NHANS_EINVAL) for an unsupported pair. */
+int64_t nhans_resample_out_count(int64_t nsamples, int rate_in, int rate_out);
+/* Host only.  Samples a live stream has emitted in total after nsamples inputs (the output contract below). */
+int64_t nhans_resample_emitted(int64_t nsamples, int ended, int rate_in, int rate_out);
+/* Host only.  The 2 * half + 1 float64 taps h (1 tap for 16000 -> 16000); returns their number, also with out == NULL. */
+int nhans_resample_taps(int rate_in, int rate_out, double* out_host, int cap);
+
+/* Ragged batch, stateless.  Clip c owns elements [in_offsets_host[c], in_offsets_host[c+1]) of in_dev (int16 or float32
+ * elements by in_format) and writes its ceil(n_c * L / M) outputs at out_dev + out_offsets_host[c]; the room
+ * out_offsets_host[c+1] - out_offsets_host[c] must hold them, else NHANS_EINVAL.  Clips of 0 samples are allowed. */
+int nhans_resample(nhans_ctx* ctx, const void* in_dev, int in_format, const int64_t* in_offsets_host, int nclips,
+                   int rate_in, int rate_out, int flags, float* out_dev, const int64_t* out_offsets_host, void* stream);
+
+/* out = float32(double(x) / (double(peak_c) + 1e-6)) per clip, peak_c = max |x| over the clip (0 for an empty one): IEEE
+ * double division, bit for bit the reference's normalise() on the same values.  out_dev == in_dev is allowed. */
+int nhans_peak_normalise(nhans_ctx* ctx, const float* in_dev, const int64_t* offsets_host, int nclips, int flags,
+                         float* out_dev, void* stream);
+
+/* Down-mix of a multi-channel file: in_dev holds nchannels planes of nsamples (channel c at in_dev + c * nsamples);
+ * out[i] = float32 of the mean of the planes at i, summed in double (the host converter's x.mean(axis = 1)).
+ * out_dev == in_dev is allowed. */
+int nhans_channel_mean(nhans_ctx* ctx, const float* in_dev, int nchannels, int64_t nsamples, float* out_dev, void* stream);
+
+/* Live streams.  One object converts `nstreams` streams rate_in -> rate_out; per stream it keeps the last J =
+ * ceil((2 * half + 1) / L) input samples and two counters.
+ * Output contract: an output is emitted once every input it reads exists.  After N inputs a stream has emitted
+ *     E(N) = min(ceil(N * L / M), max(0, floor((N * L - 1 - half) / M) + 1))
+ * samples, and ceil(N * L / M) once it has ended (the missing inputs read as 0, as at the end of a clip).  The
+ * concatenated pushes are BIT FOR BIT nhans_resample of the whole input, however it was cut, 0- and 1-sample pushes
+ * included.  Added latency: half / (L * rate_in) seconds = 10 periods of the lower rate, 0.625 ms beside 16 kHz.
+ * nhans_resampler_set_peak: every output becomes float32(double(y) / (peak + 1e-6)) -- the fixed-peak normalisation of a
+ * live stream (there is no whole-recording peak to divide by), applied to the (quantised, with the flag) output.  It
+ * holds for the outputs of the pushes that follow the call; outputs already emitted are not touched.
+ * Errors follow the online functions: a stream out of range, a push after the end, a negative count, too little room
+ * or a NULL that is needed: NHANS_EINVAL, and nothing changes.  Close the object BEFORE nhans_destroy(ctx). */
+typedef struct nhans_resampler nhans_resampler;
+int nhans_resampler_open(nhans_ctx* ctx, int nstreams, int rate_in, int rate_out, int in_format, int flags,
+                         nhans_resampler** out);
+int nhans_resampler_set_peak(nhans_resampler* obj, double peak);
+/* Appends in_offsets_host[i+1] - in_offsets_host[i] elements to stream i (end_host nullable; != 0 ends the stream after
+ * them) and writes the out_counts_host[i] samples that became final at out_dev + out_offsets_host[i]. */
+int nhans_resampler_push(nhans_resampler* obj, const void* in_dev, const int64_t* in_offsets_host, const int* end_host,
+                         float* out_dev, const int64_t* out_offsets_host, int64_t* out_counts_host, void* stream);
+/* Host only: the counts such a push would report. */
+int nhans_resampler_out_counts(const nhans_resampler* obj, const int64_t* in_counts_host, const int* end_host,
+                               int64_t* out_counts_host);
+/* Host only: stream i becomes an open stream of 0 samples, whatever it was. */
+int nhans_resampler_restart(nhans_resampler* obj, int i);
+void nhans_resampler_close(nhans_resampler* obj);
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

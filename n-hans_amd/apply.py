@@ -60,6 +60,8 @@ class Flags(object):
     model_dir = os.environ.get("NHANS_MODEL_DIR", "./trained_model")
     cache = True         # folded-blob cache (blobcache.py); --no-cache folds the weights in this process
     online_ms = None     # --online_ms: file mode through the online path (online.py) in pieces of this many ms
+    convert_on = "host"  # --convert_on gpu: format / rate conversion and normalisation of the files on the device (resample.py)
+    output_rate = "16000"    # --output_rate input: the output files at the input file's rate (converted back on the device)
 
 
 FLAGS = Flags()
@@ -134,10 +136,34 @@ def extend_context(samples):
     return out
 
 
-def handle_signals(mixedpath, noisepospath, noisenegpath):
+def _front_end_gpu(eng, path):
+    """--convert_on gpu: apply.normalise(read_wav_any(path)) computed on the device (resample.front_end)."""
+    from . import resample
+    rate, samples = wavread(path)
+    return resample.front_end(eng, samples, rate, FLAGS.Fs)
+
+
+def _handle_signals_gpu(kind, mixedpath, a_path, b_path):
+    eng = get_enhancer(kind)
+
+    def context(path):
+        if path is None or (os.path.basename(path) == "Silent.wav" and not os.path.exists(path)):
+            return np.zeros(spec.MIN_CTX_SAMPLES, dtype=np.float32)
+        return extend_context(_front_end_gpu(eng, path))       # (repeating a recording does not change its peak)
+
+    mixed = trim_to_frames(_front_end_gpu(eng, mixedpath))
+    if len(mixed) < spec.WIN:
+        raise ValueError("%s: shorter than one %d-sample STFT window" % (mixedpath, spec.WIN))
+    return context(a_path), context(b_path), mixed
+
+
+def handle_signals(mixedpath, noisepospath, noisenegpath, kind=None):
     """SN/apply.py:142-167: returns (pos, neg, mixed) float32; wav problems print
-    'error in threads' and yield None, like the reference's bare except."""
+    'error in threads' and yield None, like the reference's bare except.  kind: the model whose engine converts the
+    files with --convert_on gpu (without it, and by default, everything here is host code)."""
     try:
+        if kind is not None and FLAGS.convert_on == "gpu" and getattr(FLAGS, 'convert', False):
+            return _handle_signals_gpu(kind, mixedpath, noisepospath, noisenegpath)
         mixedsamples = _reader()(mixedpath)
         noisepossamples = _read_context(noisepospath)
         noisenegsamples = _read_context(noisenegpath)
@@ -215,7 +241,7 @@ def _enhance_files(kind, mixedpath, ctx_a_path, ctx_b_path):
     resnet_block argument order."""
     import time
     t0 = time.perf_counter()
-    sig = handle_signals(mixedpath, ctx_a_path, ctx_b_path)
+    sig = handle_signals(mixedpath, ctx_a_path, ctx_b_path, kind)
     if sig is None:
         raise RuntimeError("could not read %s / %s / %s" % (mixedpath, ctx_a_path, ctx_b_path))
     ca, cb, mixed = sig
@@ -223,7 +249,7 @@ def _enhance_files(kind, mixedpath, ctx_a_path, ctx_b_path):
     eng = get_enhancer(kind)
     t2 = time.perf_counter()
     if getattr(FLAGS, "online_ms", None):
-        res = _enhance_online(eng, mixedpath, ca, cb, FLAGS.online_ms)
+        res = _enhance_online(eng, mixedpath, ca, cb, FLAGS.online_ms, mixed if FLAGS.convert_on == "gpu" else None)
     else:
         res = eng.enhance([mixed], [ca], [cb], want_mixed=True)
     if TIMING is not None:
@@ -232,14 +258,18 @@ def _enhance_files(kind, mixedpath, ctx_a_path, ctx_b_path):
     return res["denoised_wav"][0], res["mixed_wav"][0]
 
 
-def _enhance_online(eng, mixedpath, ca, cb, piece_ms):
+def _enhance_online(eng, mixedpath, ca, cb, piece_ms, normalised=None):
     """--online_ms: the file normalised with its whole-file peak exactly as offline, then pushed in piece_ms pieces
-    through one online stream (online.py); the untrimmed tail is pushed too and dropped by the output contract."""
+    through one online stream (online.py); the untrimmed tail is pushed too and dropped by the output contract.
+    normalised: the signal the device front end has already converted and normalised (--convert_on gpu)."""
     from . import online
-    x = _reader()(mixedpath)
-    with np.errstate(over="ignore"):
-        peak = np.max(np.abs(x)) if len(x) else 0
-    x = online.normalise_fixed(x, peak)
+    if normalised is not None:
+        x = normalised
+    else:
+        x = _reader()(mixedpath)
+        with np.errstate(over="ignore"):
+            peak = np.max(np.abs(x)) if len(x) else 0
+        x = online.normalise_fixed(x, peak)
     step = max(1, int(round(piece_ms * FLAGS.Fs / 1000.0)))
     enh = online.OnlineEnhancer(eng, [ca], [cb], want_mixed=True)
     try:
@@ -265,22 +295,45 @@ def side_prefix(save_to):
     return os.path.splitext(save_to)[0] + '_'
 
 
+_job_rate = {}           # save_to -> (input file's rate, kind): what --output_rate input writes at
+
+
+def _note_job(kind, mixedpath, save_to):
+    if FLAGS.output_rate == "input":
+        try:
+            _job_rate[save_to] = (int(wavread(mixedpath, mmap=True)[0]), kind)
+        except Exception:
+            pass                                             # (an unreadable input is reported where it is read)
+
+
+def _out_rate(save_to):
+    """-> (rate, convert): the rate the files of this job are written at and what brings a 16 kHz signal there --
+    nothing by default, nhans_resample on the device with --output_rate input and an input at another rate."""
+    rate, kind = _job_rate.pop(save_to, (FLAGS.Fs, None)) if FLAGS.output_rate == "input" else (FLAGS.Fs, None)
+    if rate == FLAGS.Fs:
+        return FLAGS.Fs, lambda x: x
+    from . import resample
+    eng = get_enhancer(kind)
+    return rate, lambda x: resample.resample(eng, [np.asarray(x, dtype=np.float32)], FLAGS.Fs, rate)[0]
+
+
 def write_snc_outputs(save_to, denoised_samples, mixed_samples):
     """The four files of SN/apply.py:456-472: denoised, mixed_processed (STFT->iSTFT round trip of
     the input), removed = mixed - denoised, compensated = denoised + removed * factor with the
     factor FLAGS.compensate or, under --ac, snr_est / 20.  Returns (snr_est, factor)."""
     pre = side_prefix(save_to)
-    wavwrite(save_to, FLAGS.Fs, denoised_samples)
-    wavwrite(pre + 'mixed_processed.wav', FLAGS.Fs, mixed_samples)
+    rate, conv = _out_rate(save_to)
+    wavwrite(save_to, rate, conv(denoised_samples))
+    wavwrite(pre + 'mixed_processed.wav', rate, conv(mixed_samples))
     removed_samples = mixed_samples - denoised_samples
-    wavwrite(pre + 'removed.wav', FLAGS.Fs, removed_samples)
+    wavwrite(pre + 'removed.wav', rate, conv(removed_samples))
     with np.errstate(divide="ignore", invalid="ignore"):
         snr_est = np.mean(np.square(denoised_samples)) / np.mean(np.square(removed_samples))
     print(snr_est)
     print('---------------------------')
     factor = snr_est / 20 if FLAGS.ac else FLAGS.compensate
     compensated_samples = denoised_samples + removed_samples * factor
-    wavwrite(pre + 'compensated.wav', FLAGS.Fs, compensated_samples.astype(np.float32))
+    wavwrite(pre + 'compensated.wav', rate, conv(compensated_samples.astype(np.float32)))
     return snr_est, factor
 
 
@@ -288,6 +341,7 @@ def apply_snc(mixedpath, pospath, negpath, save_to):
     """Selective noise suppression: keep `pos`-like noise, remove `neg`-like noise
     (SN/apply.py:339-472).  Writes save_to plus the *mixed_processed / *removed / *compensated
     side files (naming: side_prefix)."""
+    _note_job(spec.DENOISER, mixedpath, save_to)
     denoised_samples, mixed_samples = _enhance_files(spec.DENOISER, mixedpath, pospath, negpath)
     write_snc_outputs(save_to, denoised_samples, mixed_samples)
 
@@ -302,14 +356,16 @@ def apply_denoiser(mixedpath, negpath, save_to):
 def apply_separator(mixedpath, cleanpath, noisepath, save_to):
     """SS/apply.py:288-397: keep the `cleanpath` (target, --pos) speaker, remove the `noisepath`
     (interferer, --neg) speaker.  resnet_block order is (noise, clean), SS/main.py:205-242."""
+    _note_job(spec.SEPARATOR, mixedpath, save_to)
     denoised_samples, mixed_samples = _enhance_files(spec.SEPARATOR, mixedpath, noisepath, cleanpath)
     write_separator_outputs(save_to, denoised_samples, mixed_samples)
 
 
 def write_separator_outputs(save_to, denoised_samples, mixed_samples):
     """SS/apply.py:391-397: the separated target and the round trip of the input."""
-    wavwrite(save_to, FLAGS.Fs, denoised_samples)
-    wavwrite(side_prefix(save_to) + 'mixed_processed.wav', FLAGS.Fs, mixed_samples)
+    rate, conv = _out_rate(save_to)
+    wavwrite(save_to, rate, conv(denoised_samples))
+    wavwrite(side_prefix(save_to) + 'mixed_processed.wav', rate, conv(mixed_samples))
 
 
 # Audio per nhans_enhance_clips call in directory mode: 4,096 s = 410 ten-second clips = 1.4 GB of
@@ -351,7 +407,7 @@ def apply_batch(kind, jobs):
     sigs = []
     for mixedpath, pospath, negpath, _ in jobs[lo:hi]:
         a_path, b_path = (pospath, negpath) if kind == spec.DENOISER else (negpath, pospath)
-        sigs.append(handle_signals(mixedpath, a_path, b_path))      # None: unreadable triple, reported there, skipped
+        sigs.append(handle_signals(mixedpath, a_path, b_path, kind))    # None: unreadable triple, reported there, skipped
     good = [s for s in sigs if s is not None]
     if world == 1 and not good:
         return 0
@@ -373,9 +429,10 @@ def apply_batch(kind, jobs):
         outs = [None if t is None else (t[:t.numel() // 2].cpu().numpy(), t[t.numel() // 2:].cpu().numpy())
                 for t in both]
     written = 0
-    for (_, _, _, save_to), o in zip(jobs, outs):
+    for (mixedpath, _, _, save_to), o in zip(jobs, outs):
         if o is None:
             continue
+        _note_job(kind, mixedpath, save_to)
         if kind == spec.DENOISER:
             write_snc_outputs(save_to, o[0], o[1])
         else:
@@ -502,6 +559,11 @@ def _parse(argv, prog):
     p.add_argument('--online_ms', type=float, default=None,
                    help='file mode only: push the input through the online (live-stream) path in pieces of this many '
                         'milliseconds; the files written are byte-identical to the offline run')
+    p.add_argument('--convert_on', default='host', choices=['host', 'gpu'],
+                   help='where files that are not 16 kHz int16 PCM are converted and all files normalised: host (scipy, '
+                        'the default) or gpu (the device rate converter, rates of nhans_amd.resample.RATES)')
+    p.add_argument('--output_rate', default='16000', choices=['16000', 'input'],
+                   help='input: write the output files at the input file\'s rate (converted back on the device)')
     a = p.parse_args(argv)
     if a.online_ms is not None:
         if a.online_ms <= 0:

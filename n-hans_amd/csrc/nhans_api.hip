@@ -152,6 +152,7 @@ struct nhans_ctx {
     int wino_f32 = 1;           // tensors that only Winograd launches read are stored f32 NHWC (stored_f32())
     long long* dbg = nullptr;   // NHANS_DEV builds: per-workgroup cycle stamps of the last conv launch
     int* status_dev = nullptr;  // sticky NHANS_STATUS_* bits set by kernels (nhans_take_status)
+    std::map<std::pair<int, int>, float*> rs_tab;   // device copies of the rate converter's phase tables, by (rate_in, rate_out)
     // Activation exponents: a split-f16 tensor is stored as x * 2^-e with one e per tensor of the network, chosen from
     // the largest |x| a calibration pass saw so that the stored maximum is <= 2^kActTargetLog2 -- 2^8 below the f16
     // limit (and the 1-D Winograd transform's worst-case gain of ~20 still fits).  Tensors: tower block b conv1/conv2
@@ -1002,6 +1003,7 @@ void nhans_destroy(nhans_ctx* c) {
     if (c->tail_ev) (void)hipEventDestroy(c->tail_ev);
     if (c->status_dev) (void)hipFree(c->status_dev);
     if (c->amax_dev) (void)hipFree(c->amax_dev);
+    for (auto& kv : c->rs_tab) (void)hipFree(kv.second);
     if (c->ws) (void)hipFree(c->ws);
     if (c->kscratch) (void)hipFree(c->kscratch);
     if (c->kcounter) (void)hipFree(c->kcounter);
@@ -1837,6 +1839,311 @@ void nhans_online_close(nhans_online* o) {
     (void)hipDeviceSynchronize();
     (void)hipFree(o->emb);
     (void)hipFree(o->state);
+    delete o;
+}
+
+}  // extern "C"
+
+// ---- sample-rate conversion and the file front end (include/nhans_hip.h: nhans_resample*, nhans_peak_normalise) --------
+struct nhans_resampler {
+    nhans_ctx* c = nullptr;
+    int device = 0, S = 0, in_format = 0, flags = 0;
+    const ResampleFilter* f = nullptr;
+    const float* tab = nullptr;
+    double denom = 0.0;             // nhans_resampler_set_peak: peak + 1e-6; 0 = outputs as they are
+    // [2][S][J]: the J samples before each stream's next one; cur[i] = the half that holds them.  A push reads half cur[i]
+    // and writes the other one; the NEXT push reads what this one wrote and overwrites what it read.  That is race-free
+    // because consecutive calls on a context are ordered on the device (same stream, or Call's tail event across streams).
+    float* hist = nullptr;
+    std::vector<int64_t> N;         // samples pushed per stream
+    std::vector<char> ended, cur;
+    float* h(int k, int i) const { return hist + ((size_t)k * S + i) * f->J; }
+};
+
+namespace {
+
+int rs_filter(const char* fn, int rate_in, int rate_out, const ResampleFilter** f) {
+    *f = resample_filter(rate_in, rate_out);
+    if (!*f)
+        return fail(NHANS_EINVAL, std::string(fn) + ": " + std::to_string(rate_in) + " Hz -> " + std::to_string(rate_out) +
+                                  " Hz is not supported (one side 16000 Hz, the other 8000, 11025, 12000, 16000, 22050, "
+                                  "24000, 32000, 44100, 48000, 88200 or 96000 Hz)");
+    return NHANS_OK;
+}
+
+int rs_table(nhans_ctx* c, const ResampleFilter* f, const float** tab) {
+    float*& t = c->rs_tab[{f->rate_in, f->rate_out}];
+    if (!t) {
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t), f->tab.size() * 4));
+        const hipError_t e = hipMemcpy(t, f->tab.data(), f->tab.size() * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(t); t = nullptr;
+            return fail(NHANS_EHIP, std::string("hipMemcpy of the phase table: ") + hipGetErrorString(e));
+        }
+    }
+    *tab = t;
+    return NHANS_OK;
+}
+
+size_t rs_elem(int fmt) { return fmt == kResampleInt16 ? 2 : 4; }
+
+// runs for outputs [m_begin, m_end) of one stream; with hist_out also an empty run when there is no output, so that the
+// carried samples follow every push that brought some
+void rs_add_runs(std::vector<ResampleRun>& runs, size_t* lds, const ResampleFilter& f, const void* src, const float* hist,
+                 float* dst, float* hist_out, int64_t k0, int n_new, int64_t m_begin, int64_t m_end) {
+    bool first = true;
+    for (int64_t m = m_begin; m < m_end || (first && hist_out); m += kResampleRun) {
+        const int cnt = (int)std::max<int64_t>(0, std::min<int64_t>(kResampleRun, m_end - m));
+        const int64_t t0 = m * f.M + f.half, q0 = t0 / f.L;
+        const int p0 = (int)(t0 - q0 * f.L);
+        runs.push_back({src, hist, dst ? dst + (m - m_begin) : nullptr, first ? hist_out : nullptr, (long long)k0,
+                        (long long)(q0 - k0), p0, n_new, cnt});
+        *lds = std::max(*lds, resample_run_lds_bytes(f, p0, cnt));
+        first = false;
+        if (cnt == 0) break;
+    }
+}
+
+int rs_launch(nhans_ctx* c, const char* name, const std::vector<ResampleRun>& runs, const float* tab, const ResampleFilter& f,
+              int fmt, int quantise, double denom, size_t lds, int64_t in_samples, int64_t out_samples, hipStream_t s) {
+    if (runs.empty()) return NHANS_OK;
+    int rc = ws_reserve(c, ws_size(runs.size(), sizeof(ResampleRun))); if (rc) return rc;
+    ResampleRun* runs_dev = ws_take<ResampleRun>(c, runs.size());
+    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(ResampleRun), s); if (rc) return rc;
+    Prof pr(c, s, name);
+    launch_resample(name, runs_dev, (int)runs.size(), tab, f, fmt, quantise, denom, lds, s);
+    pr.done(2.0 * f.J * (double)out_samples, (double)in_samples * rs_elem(fmt) + 4.0 * out_samples + 4.0 * runs.size() * f.tab.size());
+    return NHANS_OK;
+}
+
+constexpr int64_t kMaxResampleClip = ((int64_t)1 << 31) - 1;
+
+int resample_body(nhans_ctx* c, const void* in, int fmt, const int64_t* inoff, int nclips, int rate_in, int rate_out,
+                  int flags, float* out, const int64_t* outoff, hipStream_t s) {
+    if (!inoff || !outoff || nclips < 0) return fail(NHANS_EINVAL, "nhans_resample: null argument");
+    if (fmt != kResampleInt16 && fmt != kResampleFloat32) return fail(NHANS_EINVAL, "nhans_resample: in_format must be NHANS_PCM_INT16 or NHANS_PCM_FLOAT32");
+    if (flags & ~NHANS_RESAMPLE_QUANTISE) return fail(NHANS_EINVAL, "nhans_resample: unknown flag");
+    const ResampleFilter* f = nullptr;
+    int rc = rs_filter("nhans_resample", rate_in, rate_out, &f); if (rc) return rc;
+    std::vector<ResampleRun> runs;
+    size_t lds = 0;
+    int64_t tin = 0, tout = 0;
+    for (int i = 0; i < nclips; ++i) {
+        const int64_t n = inoff[i + 1] - inoff[i];
+        if (n < 0 || n > kMaxResampleClip)
+            return fail(NHANS_EINVAL, "nhans_resample: clip " + std::to_string(i) + " has " + std::to_string(n) + " samples (0 ... 2^31 - 1)");
+        const int64_t no = resample_out_count(*f, n);
+        if (outoff[i + 1] - outoff[i] < no)
+            return fail(NHANS_EINVAL, "nhans_resample: output room of clip " + std::to_string(i) + " is " +
+                                      std::to_string(outoff[i + 1] - outoff[i]) + " samples, " + std::to_string(no) +
+                                      " needed (nhans_resample_out_count)");
+        tin += n; tout += no;
+    }
+    if ((tin > 0 && !in) || (tout > 0 && !out)) return fail(NHANS_EINVAL, "nhans_resample: null buffer");
+    for (int i = 0; i < nclips; ++i) {
+        const int64_t n = inoff[i + 1] - inoff[i];
+        rs_add_runs(runs, &lds, *f, static_cast<const char*>(in) + inoff[i] * rs_elem(fmt), nullptr, out + outoff[i], nullptr, 0,
+                    (int)n, 0, resample_out_count(*f, n));
+    }
+    if (runs.empty()) return NHANS_OK;
+    const float* tab = nullptr;
+    rc = rs_table(c, f, &tab); if (rc) return rc;
+    return rs_launch(c, "resample", runs, tab, *f, fmt, flags & NHANS_RESAMPLE_QUANTISE, 0.0, lds, tin, tout, s);
+}
+
+int peak_normalise_body(nhans_ctx* c, const float* in, const int64_t* off, int nclips, int flags, float* out, hipStream_t s) {
+    if (!off || nclips < 0) return fail(NHANS_EINVAL, "nhans_peak_normalise: null argument");
+    if (flags & ~NHANS_NORMALISE_WRAP_INT16) return fail(NHANS_EINVAL, "nhans_peak_normalise: unknown flag");
+    std::vector<NormBlock> blocks;
+    for (int i = 0; i < nclips; ++i) {
+        const int64_t n = off[i + 1] - off[i];
+        if (n < 0) return fail(NHANS_EINVAL, "nhans_peak_normalise: clip " + std::to_string(i) + " has a negative sample count");
+        const int64_t nb = (n + kNormBlock - 1) / kNormBlock;
+        if ((int64_t)blocks.size() + nb > (int64_t)1 << 30) return fail(NHANS_EINVAL, "nhans_peak_normalise: batch too large for one call");
+        const int pb0 = (int)blocks.size();
+        for (int64_t b = 0; b < nb; ++b)
+            blocks.push_back({(long long)(off[i] + b * kNormBlock), (int)std::min<int64_t>(kNormBlock, n - b * kNormBlock), pb0, (int)nb});
+    }
+    if (blocks.empty()) return NHANS_OK;
+    if (!in || !out) return fail(NHANS_EINVAL, "nhans_peak_normalise: null buffer");
+    int rc = ws_reserve(c, ws_size(blocks.size(), sizeof(NormBlock)) + ws_size(blocks.size(), 4)); if (rc) return rc;
+    NormBlock* bd = ws_take<NormBlock>(c, blocks.size());
+    float* partial = ws_take<float>(c, blocks.size());
+    rc = h2d(c, bd, blocks.data(), blocks.size() * sizeof(NormBlock), s); if (rc) return rc;
+    const double n = (double)(off[nclips] - off[0]);
+    { Prof pr(c, s, "peak_partial"); launch_peak_partial(in, bd, (int)blocks.size(), flags & NHANS_NORMALISE_WRAP_INT16, partial, s); pr.done(0, 4.0 * n); }
+    if (launch_error_pending()) return NHANS_OK;
+    { Prof pr(c, s, "peak_normalise"); launch_peak_normalise(in, bd, (int)blocks.size(), partial, out, s); pr.done(0, 8.0 * n); }
+    return NHANS_OK;
+}
+
+int resampler_check_push(const nhans_resampler* o, const char* fn, int i, int64_t cnt, bool en) {
+    if (cnt < 0) return fail(NHANS_EINVAL, std::string(fn) + ": stream " + std::to_string(i) + " has a negative sample count");
+    if (o->ended[i] && (cnt > 0 || en)) return fail(NHANS_EINVAL, std::string(fn) + ": stream " + std::to_string(i) + " has ended");
+    if (cnt > kMaxResampleClip) return fail(NHANS_EINVAL, std::string(fn) + ": push too large for one call (split it)");
+    return NHANS_OK;
+}
+
+int resampler_push_body(nhans_resampler* o, const void* in, const int64_t* inoff, const int* end, float* out,
+                        const int64_t* outoff, int64_t* counts, hipStream_t s) {
+    if (!inoff || !outoff || !counts) return fail(NHANS_EINVAL, "nhans_resampler_push: null argument");
+    const ResampleFilter& f = *o->f;
+    const int S = o->S;
+    std::vector<int64_t> Eo(S), En(S);
+    int64_t tin = 0, tout = 0;
+    for (int i = 0; i < S; ++i) {
+        const int64_t cnt = inoff[i + 1] - inoff[i];
+        const bool en = end && end[i];
+        const int rc = resampler_check_push(o, "nhans_resampler_push", i, cnt, en); if (rc) return rc;
+        Eo[i] = resample_emitted(f, o->N[i], o->ended[i]);
+        En[i] = resample_emitted(f, o->N[i] + cnt, o->ended[i] || en);
+        if (outoff[i + 1] - outoff[i] < En[i] - Eo[i])
+            return fail(NHANS_EINVAL, "nhans_resampler_push: output room of stream " + std::to_string(i) + " is " +
+                                      std::to_string(outoff[i + 1] - outoff[i]) + " samples, " + std::to_string(En[i] - Eo[i]) +
+                                      " needed (nhans_resampler_out_counts)");
+        tin += cnt; tout += En[i] - Eo[i];
+    }
+    if ((tin > 0 && !in) || (tout > 0 && !out)) return fail(NHANS_EINVAL, "nhans_resampler_push: null buffer");
+    std::vector<ResampleRun> runs;
+    std::vector<char> flip(S, 0);
+    size_t lds = 0;
+    for (int i = 0; i < S; ++i) {
+        const int64_t cnt = inoff[i + 1] - inoff[i];
+        if (cnt == 0 && En[i] == Eo[i]) continue;
+        flip[i] = cnt > 0;
+        rs_add_runs(runs, &lds, f, static_cast<const char*>(in) + inoff[i] * rs_elem(o->in_format), o->h(o->cur[i], i),
+                    out ? out + outoff[i] : nullptr, cnt > 0 ? o->h(1 - o->cur[i], i) : nullptr, o->N[i], (int)cnt, Eo[i], En[i]);
+    }
+    const int rc = rs_launch(o->c, "resampler_push", runs, o->tab, f, o->in_format, o->flags & NHANS_RESAMPLE_QUANTISE, o->denom,
+                             lds, tin, tout, s);
+    if (rc) return rc;
+    if (launch_error_pending()) return NHANS_OK;
+    for (int i = 0; i < S; ++i) {
+        counts[i] = En[i] - Eo[i];
+        o->N[i] += inoff[i + 1] - inoff[i];
+        o->ended[i] = o->ended[i] || (end && end[i]);
+        if (flip[i]) o->cur[i] = 1 - o->cur[i];
+    }
+    return NHANS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nhans_resample_out_count(int64_t n, int rate_in, int rate_out) {
+    const ResampleFilter* f = nullptr;
+    if (rs_filter("nhans_resample_out_count", rate_in, rate_out, &f)) return NHANS_EINVAL;
+    if (n < 0) return fail(NHANS_EINVAL, "nhans_resample_out_count: negative sample count");
+    return resample_out_count(*f, n);
+}
+
+int64_t nhans_resample_emitted(int64_t n, int ended, int rate_in, int rate_out) {
+    const ResampleFilter* f = nullptr;
+    if (rs_filter("nhans_resample_emitted", rate_in, rate_out, &f)) return NHANS_EINVAL;
+    if (n < 0) return fail(NHANS_EINVAL, "nhans_resample_emitted: negative sample count");
+    return resample_emitted(*f, n, ended != 0);
+}
+
+int nhans_resample_taps(int rate_in, int rate_out, double* out, int cap) {
+    const ResampleFilter* f = nullptr;
+    const int rc = rs_filter("nhans_resample_taps", rate_in, rate_out, &f); if (rc) return rc;
+    const int n = (int)f->h.size();
+    if (out) {
+        if (cap < n) return fail(NHANS_EINVAL, "nhans_resample_taps: room for " + std::to_string(cap) + " taps, " + std::to_string(n) + " needed");
+        std::memcpy(out, f->h.data(), (size_t)n * sizeof(double));
+    }
+    return n;
+}
+
+int nhans_resample(nhans_ctx* c, const void* in, int in_format, const int64_t* inoff, int nclips, int rate_in, int rate_out,
+                   int flags, float* out, const int64_t* outoff, void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(resample_body(c, in, in_format, inoff, nclips, rate_in, rate_out, flags, out, outoff, call.s));
+}
+
+int nhans_peak_normalise(nhans_ctx* c, const float* in, const int64_t* off, int nclips, int flags, float* out, void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(peak_normalise_body(c, in, off, nclips, flags, out, call.s));
+}
+
+int nhans_channel_mean(nhans_ctx* c, const float* in, int nchan, int64_t n, float* out, void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    if (nchan < 1 || n < 0 || n >= ((int64_t)1 << 39)) return call.finish(fail(NHANS_EINVAL, "nhans_channel_mean: nchannels must be >= 1 and 0 <= nsamples < 2^39"));
+    if (n > 0 && (!in || !out)) return call.finish(fail(NHANS_EINVAL, "nhans_channel_mean: null buffer"));
+    Prof pr(c, call.s, "channel_mean");
+    launch_channel_mean(in, nchan, n, out, call.s);
+    pr.done(0, 4.0 * (double)n * (nchan + 1));
+    return call.finish(NHANS_OK);
+}
+
+int nhans_resampler_open(nhans_ctx* c, int nstreams, int rate_in, int rate_out, int in_format, int flags, nhans_resampler** out) {
+    if (!out) return fail(NHANS_EINVAL, "nhans_resampler_open: null argument");
+    *out = nullptr;
+    int rc = check_ctx(c); if (rc) return rc;
+    if (nstreams < 1) return fail(NHANS_EINVAL, "nhans_resampler_open: nstreams must be >= 1");
+    if (in_format != kResampleInt16 && in_format != kResampleFloat32)
+        return fail(NHANS_EINVAL, "nhans_resampler_open: in_format must be NHANS_PCM_INT16 or NHANS_PCM_FLOAT32");
+    if (flags & ~NHANS_RESAMPLE_QUANTISE) return fail(NHANS_EINVAL, "nhans_resampler_open: unknown flag");
+    const ResampleFilter* f = nullptr;
+    rc = rs_filter("nhans_resampler_open", rate_in, rate_out, &f); if (rc) return rc;
+    const float* tab = nullptr;
+    rc = rs_table(c, f, &tab); if (rc) return rc;
+    nhans_resampler* o = new nhans_resampler();
+    o->c = c; o->device = c->device; o->S = nstreams; o->in_format = in_format; o->flags = flags; o->f = f; o->tab = tab;
+    o->N.assign(nstreams, 0); o->ended.assign(nstreams, 0); o->cur.assign(nstreams, 0);
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->hist), (size_t)2 * nstreams * f->J * 4);
+    if (e != hipSuccess) {
+        delete o;
+        return fail(NHANS_ENOMEM, std::string("nhans_resampler_open: hipMalloc failed: ") + hipGetErrorString(e));
+    }
+    *out = o;
+    return NHANS_OK;
+}
+
+int nhans_resampler_set_peak(nhans_resampler* o, double peak) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_resampler_set_peak: null object");
+    if (!(peak >= 0.0) || !std::isfinite(peak)) return fail(NHANS_EINVAL, "nhans_resampler_set_peak: the peak must be finite and >= 0");
+    o->denom = peak + 0.000001;
+    return NHANS_OK;
+}
+
+int nhans_resampler_push(nhans_resampler* o, const void* in, const int64_t* inoff, const int* end, float* out,
+                         const int64_t* outoff, int64_t* counts, void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_resampler_push: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(resampler_push_body(o, in, inoff, end, out, outoff, counts, call.s));
+}
+
+int nhans_resampler_out_counts(const nhans_resampler* o, const int64_t* in_counts, const int* end, int64_t* counts) {
+    if (!o || !in_counts || !counts) return fail(NHANS_EINVAL, "nhans_resampler_out_counts: null argument");
+    for (int i = 0; i < o->S; ++i) {
+        const int rc = resampler_check_push(o, "nhans_resampler_out_counts", i, in_counts[i], end && end[i]); if (rc) return rc;
+    }
+    for (int i = 0; i < o->S; ++i)
+        counts[i] = resample_emitted(*o->f, o->N[i] + in_counts[i], o->ended[i] || (end && end[i])) -
+                    resample_emitted(*o->f, o->N[i], o->ended[i]);
+    return NHANS_OK;
+}
+
+int nhans_resampler_restart(nhans_resampler* o, int i) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_resampler_restart: null object");
+    if (i < 0 || i >= o->S)
+        return fail(NHANS_EINVAL, "nhans_resampler_restart: stream " + std::to_string(i) + " out of range (0 ... " + std::to_string(o->S - 1) + ")");
+    // (nothing is cleared on the device: a stream of 0 samples reads none of the carried ones -- their absolute index is negative)
+    o->N[i] = 0; o->ended[i] = 0;
+    return NHANS_OK;
+}
+
+void nhans_resampler_close(nhans_resampler* o) {
+    if (!o) return;
+    (void)hipSetDevice(o->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(o->hist);
     delete o;
 }
 

@@ -5,6 +5,7 @@
 
 #include <tuple>
 #include <utility>
+#include <vector>
 
 namespace nhans {
 
@@ -279,5 +280,49 @@ void launch_istft(const float* logmag, const float* phase, ClipTable t, const in
 constexpr int kStftFramesPerBlock = 23;   // frames per run: 460 pass-1 tasks (256 + 204) and 253 pass-2 tasks on 256 lanes
 constexpr int64_t kMaxFramesPerClip = 5000000;   // 13.9 h: the STFT / iSTFT kernels address a clip with 32-bit byte offsets
 constexpr int kIstftHopsPerBlock = 22;    // output hops per block; needs 24 frames
+
+// ---------------------------------------------------------------------------------------------
+// Sample-rate conversion and the file front end (resample.hip; include/nhans_hip.h: nhans_resample*)
+// The filter of scipy.signal.resample_poly(x, L, M), designed on the host in double.  tab = the taps rounded to float32,
+// phase-minor: tab[j * L + p] = h[p + j * L] (0 beyond the last tap), padded to a multiple of 4 floats.
+struct ResampleFilter {
+    int rate_in = 0, rate_out = 0, L = 1, M = 1, half = 0, J = 1;
+    std::vector<double> h;      // 2 * half + 1 taps
+    std::vector<float> tab;     // L * J floats, padded
+};
+// nullptr for a pair that is not supported; the design of a pair is computed once per process (thread-safe)
+const ResampleFilter* resample_filter(int rate_in, int rate_out);
+int64_t resample_out_count(const ResampleFilter& f, int64_t n);                 // ceil(n L / M)
+int64_t resample_emitted(const ResampleFilter& f, int64_t n, bool ended);      // the streaming output contract
+
+// One workgroup: outputs [m0, m0 + cnt) of one clip or stream, m0 * M + half = q0 * L + p0.  The input is the stream's
+// samples from absolute index k0 on (n_new of them at src, int16 or float32) preceded by `hist`, the J samples before k0
+// as float32 (entries of negative absolute index are never read); everything else reads as 0.0f.
+struct ResampleRun {
+    const void* src;
+    const float* hist;      // nullable: nothing before k0
+    float* dst;
+    float* hist_out;        // non-null: this workgroup also writes the J samples before k0 + n_new (the stream's next history)
+    long long k0;
+    long long qrel0;        // q0 - k0
+    int p0, n_new, cnt;
+};
+constexpr int kResampleRun = 1024;      // outputs per workgroup at most
+constexpr int kResampleInt16 = 0, kResampleFloat32 = 1;
+size_t resample_run_lds_bytes(const ResampleFilter& f, int p0, int cnt);
+// denom != 0: every output is then float32(double(y) / denom) (the fixed-peak normalisation of a live stream)
+void launch_resample(const char* kernel, const ResampleRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
+                     int in_format, int quantise, double denom, size_t lds_bytes, hipStream_t s);
+
+// peak + normalise: blocks of <= kNormBlock samples; block b belongs to a clip whose blocks are [pb0, pb0 + pbn)
+struct NormBlock {
+    long long off;
+    int n, pb0, pbn;
+};
+constexpr int kNormBlock = 8192;
+void launch_peak_partial(const float* x, const NormBlock* blocks_dev, int nblocks, int wrap, float* partial, hipStream_t s);
+void launch_peak_normalise(const float* x, const NormBlock* blocks_dev, int nblocks, const float* partial, float* out, hipStream_t s);
+// out[i] = mean_c in[c * n + i] (channel-major planes of n samples; out may be plane 0)
+void launch_channel_mean(const float* in, int nchan, int64_t n, float* out, hipStream_t s);
 
 }  // namespace nhans

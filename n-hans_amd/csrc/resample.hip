@@ -1,0 +1,235 @@
+// Sample-rate conversion between 16 kHz and the rates capture devices deliver, and the peak normalisation of the file
+// front end (include/nhans_hip.h: nhans_resample*, nhans_resampler_*, nhans_peak_normalise).
+//
+// The filter is the one scipy.signal.resample_poly(x, L, M) designs by default -- sinc times Kaiser(5) window of
+// 2 * half + 1 taps, half = 10 max(L, M), unit sum, times L -- computed here in double so that a C caller needs no Python.
+// Output m of a clip is
+//     y[m] = sum_k h[m M + half - k L] x[k]  =  sum_{j < J} h[p + j L] x[q - j],   m M + half = q L + p,  0 <= p < L
+// -- ONE chain of J fmaf in float32, j ascending, absent inputs as 0.0f (fir_chain below).  The offline call and the live
+// push run the SAME kernel on run descriptors the host builds, so a stream's output cannot depend on how it was cut: a
+// push only changes where an input sample is fetched from (the caller's new samples or the J carried ones), never the
+// arithmetic on it.
+#include "nhans_kernels.h"
+
+#include <cmath>
+#include <map>
+#include <mutex>
+
+namespace nhans {
+
+// ---- design (host, double) ------------------------------------------------------------------------------------------
+namespace {
+
+double bessel_i0(double x) {
+    // power series sum_k ((x/2)^k / k!)^2: every term positive, converges in < 30 terms for the x <= 5 used here
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 200; ++k) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < sum * 1e-18) break;
+    }
+    return sum;
+}
+
+bool rate_supported(int r) {
+    static const int ok[] = {8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000};
+    for (int v : ok)
+        if (v == r) return true;
+    return false;
+}
+
+int gcd_int(int a, int b) {
+    while (b) { const int t = a % b; a = b; b = t; }
+    return a;
+}
+
+ResampleFilter* design(int rate_in, int rate_out) {
+    ResampleFilter* f = new ResampleFilter();
+    f->rate_in = rate_in; f->rate_out = rate_out;
+    const int g = gcd_int(rate_in, rate_out);
+    f->L = rate_out / g; f->M = rate_in / g;
+    if (f->L == 1 && f->M == 1) {       // a copy: fmaf(1, x, 0) = x
+        f->half = 0; f->J = 1; f->h.assign(1, 1.0);
+    } else {
+        const int mx = std::max(f->L, f->M);
+        f->half = 10 * mx;
+        const int N = 2 * f->half + 1;
+        const double cutoff = 1.0 / mx, alpha = 0.5 * (N - 1), beta = 5.0, pi = 3.14159265358979323846;
+        const double i0b = bessel_i0(beta);
+        f->h.resize(N);
+        double sum = 0.0;
+        for (int n = 0; n < N; ++n) {
+            const double m = n - alpha, a = pi * cutoff * m;
+            const double sinc = m == 0.0 ? 1.0 : std::sin(a) / a;
+            const double r = m / alpha;
+            const double w = bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
+            f->h[n] = cutoff * sinc * w;
+            sum += f->h[n];
+        }
+        for (int n = 0; n < N; ++n) f->h[n] = f->h[n] / sum * f->L;
+        f->J = (N + f->L - 1) / f->L;
+    }
+    const size_t n = (size_t)f->L * f->J;
+    f->tab.assign((n + 3) / 4 * 4, 0.f);
+    for (int j = 0; j < f->J; ++j)
+        for (int p = 0; p < f->L; ++p) {
+            const size_t t = (size_t)p + (size_t)j * f->L;
+            if (t < f->h.size()) f->tab[(size_t)j * f->L + p] = (float)f->h[t];
+        }
+    return f;
+}
+
+}  // namespace
+
+const ResampleFilter* resample_filter(int rate_in, int rate_out) {
+    if ((rate_in != 16000 && rate_out != 16000) || !rate_supported(rate_in) || !rate_supported(rate_out)) return nullptr;
+    static std::mutex mu;
+    static std::map<std::pair<int, int>, ResampleFilter*> cache;    // (lives as long as the process)
+    std::lock_guard<std::mutex> lock(mu);
+    ResampleFilter*& f = cache[{rate_in, rate_out}];
+    if (!f) f = design(rate_in, rate_out);
+    return f;
+}
+
+int64_t resample_out_count(const ResampleFilter& f, int64_t n) { return (n * f.L + f.M - 1) / f.M; }
+
+// Output m is final once input q(m) = floor((m M + half) / L) exists: m M + half < N L.
+int64_t resample_emitted(const ResampleFilter& f, int64_t n, bool ended) {
+    const int64_t all = resample_out_count(f, n);
+    if (ended) return all;
+    const int64_t a = n * f.L - 1 - f.half;
+    return std::min(all, a < 0 ? (int64_t)0 : a / f.M + 1);
+}
+
+size_t resample_run_lds_bytes(const ResampleFilter& f, int p0, int cnt) {
+    const size_t span = cnt > 0 ? (size_t)((p0 + (int64_t)(cnt - 1) * f.M) / f.L + f.J) : 0;
+    return (f.tab.size() + span) * sizeof(float);
+}
+
+// ---- kernels --------------------------------------------------------------------------------------------------------
+namespace {
+
+// The one accumulation every output of the library's rate conversion goes through: taps h[p + j L] at tab_p[j * L]
+// (LDS), inputs x[q - j] at x_q[-j] (LDS), j ascending.
+__device__ __forceinline__ float fir_chain(const float* tab_p, int L, const float* x_q, int J) {
+    float acc = 0.f;
+    for (int j = 0; j < J; ++j) acc = fmaf(tab_p[j * L], x_q[-j], acc);
+    return acc;
+}
+
+// sample k0 + rel of the run's stream as float32 (rel < n_new; int16 -> float32 is exact)
+template <typename TIn>
+__device__ __forceinline__ float run_sample(const TIn* src, const ResampleRun& r, long long rel, int J) {
+    if (rel >= r.n_new) return 0.f;
+    if (rel >= 0) return (float)src[rel];
+    const long long a = rel + J;
+    if (a >= 0 && r.k0 + rel >= 0 && r.hist) return r.hist[a];
+    return 0.f;
+}
+
+// One workgroup per run, one lane per output (4 rounds of 256 for a full run).  LDS: the phase table (phase-minor, so
+// that for L = 1 every lane reads one address -- a broadcast --, for L = 2, 3, 6 the 64 lanes share that many addresses,
+// and for the large L neighbouring lanes, whose phases differ by M mod L, land M mod L banks apart: conflict-free where
+// that step is odd (44.1 -> 16 kHz: 121), 2-way and more where it is even (16 -> 44.1 kHz: 160 -- the price of one
+// layout for every pair), then the input span of the run (<= 58.5 KB together, 88.2 kHz in).  Lane i reads x at stride
+// M / L: 2-way bank conflicts for the even ratios (32 and 96 kHz in), none for 48 kHz in and for every upsampling pair.
+template <typename TIn>
+__global__ void __launch_bounds__(256) resample_kernel(const ResampleRun* __restrict__ runs, const float* __restrict__ tab,
+                                                       int L, int M, int J, int tab4, int quantise, double denom) {
+    extern __shared__ float4 rs_lds[];
+    float* tl = reinterpret_cast<float*>(rs_lds);
+    float* xs = tl + 4 * tab4;
+    const ResampleRun r = runs[blockIdx.x];
+    const int tid = threadIdx.x;
+    const TIn* src = static_cast<const TIn*>(r.src);
+    for (int i = tid; i < tab4; i += 256) rs_lds[i] = reinterpret_cast<const float4*>(tab)[i];
+    const int span = r.cnt > 0 ? (r.p0 + (r.cnt - 1) * M) / L + J : 0;
+    const long long lo = r.qrel0 - (J - 1);
+    for (int s = tid; s < span; s += 256) xs[s] = run_sample(src, r, lo + s, J);
+    __syncthreads();
+    for (int i = tid; i < r.cnt; i += 256) {
+        const int t = r.p0 + i * M;
+        const int q = t / L, p = t - q * L;
+        float v = fir_chain(tl + p, L, xs + (J - 1) + q, J);
+        if (quantise) v = fminf(fmaxf(rintf(v), -32768.f), 32767.f);
+        if (denom != 0.0) v = (float)((double)v / denom);
+        r.dst[i] = v;
+    }
+    if (r.hist_out)
+        for (int t = tid; t < J; t += 256) r.hist_out[t] = run_sample(src, r, (long long)r.n_new - J + t, J);
+}
+
+__device__ __forceinline__ float block_max(float m) {
+    __shared__ float part[4];
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+    __syncthreads();
+    return fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
+}
+
+// wrap: |-32768| counts as -32768, what np.abs of an int16 array gives (the reference's normalise on a mono file)
+__global__ void __launch_bounds__(256) peak_partial_kernel(const float* __restrict__ x, const NormBlock* __restrict__ blocks,
+                                                           int wrap, float* __restrict__ partial) {
+    const NormBlock b = blocks[blockIdx.x];
+    const float* p = x + b.off;
+    float m = -INFINITY;
+    for (int i = threadIdx.x; i < b.n; i += 256) {
+        const float v = p[i];
+        m = fmaxf(m, (wrap && v == -32768.f) ? v : fabsf(v));
+    }
+    m = block_max(m);
+    if (threadIdx.x == 0) partial[blockIdx.x] = m;
+}
+
+__global__ void __launch_bounds__(256) peak_normalise_kernel(const float* x, const NormBlock* __restrict__ blocks,
+                                                             const float* __restrict__ partial, float* out) {
+    const NormBlock b = blocks[blockIdx.x];
+    float m = -INFINITY;
+    for (int i = threadIdx.x; i < b.pbn; i += 256) m = fmaxf(m, partial[b.pb0 + i]);
+    m = block_max(m);
+    const double den = (double)m + 0.000001;
+    for (int i = threadIdx.x; i < b.n; i += 256) out[b.off + i] = (float)((double)x[b.off + i] / den);
+}
+
+// out[i] = float32(mean over the channels of in[c * n + i], summed in double): the host converter's x.mean(axis = 1)
+__global__ void __launch_bounds__(256) channel_mean_kernel(const float* in, int nchan, long long n, float* out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double acc = 0.0;
+    for (int c = 0; c < nchan; ++c) acc += (double)in[(long long)c * n + i];
+    out[i] = (float)(acc / (double)nchan);
+}
+
+}  // namespace
+
+void launch_channel_mean(const float* in, int nchan, int64_t n, float* out, hipStream_t s) {
+    if (n <= 0) return;
+    NHANS_LAUNCH("channel_mean", channel_mean_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, nchan, (long long)n, out);
+}
+
+void launch_resample(const char* kernel, const ResampleRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
+                     int in_format, int quantise, double denom, size_t lds_bytes, hipStream_t s) {
+    if (nruns <= 0) return;
+    if (lds_bytes > (size_t)64 << 10) { note_refusal(kernel); return; }
+    const int tab4 = (int)(f.tab.size() / 4);
+    if (in_format == kResampleInt16)
+        NHANS_LAUNCH(kernel, resample_kernel<int16_t>, dim3(nruns), dim3(256), lds_bytes, s, runs_dev, tab_dev, f.L, f.M, f.J,
+                     tab4, quantise, denom);
+    else
+        NHANS_LAUNCH(kernel, resample_kernel<float>, dim3(nruns), dim3(256), lds_bytes, s, runs_dev, tab_dev, f.L, f.M, f.J,
+                     tab4, quantise, denom);
+}
+
+void launch_peak_partial(const float* x, const NormBlock* blocks_dev, int nblocks, int wrap, float* partial, hipStream_t s) {
+    if (nblocks <= 0) return;
+    NHANS_LAUNCH("peak_partial", peak_partial_kernel, dim3(nblocks), dim3(256), 0, s, x, blocks_dev, wrap, partial);
+}
+
+void launch_peak_normalise(const float* x, const NormBlock* blocks_dev, int nblocks, const float* partial, float* out,
+                           hipStream_t s) {
+    if (nblocks <= 0) return;
+    NHANS_LAUNCH("peak_normalise", peak_normalise_kernel, dim3(nblocks), dim3(256), 0, s, x, blocks_dev, partial, out);
+}
+
+}  // namespace nhans

@@ -23,8 +23,13 @@ EXPORTS = [
     "nhans_debug_mfma_ceiling", "nhans_set_activation_exponents", "nhans_get_activation_exponents",
     "nhans_get_activation_amax", "nhans_online_open", "nhans_online_push", "nhans_online_out_counts",
     "nhans_online_rewind", "nhans_online_close", "nhans_online_open_slots", "nhans_online_restart",
-    "nhans_online_set_context", "nhans_online_set_embeddings",
+    "nhans_online_set_context", "nhans_online_set_embeddings", "nhans_resample_out_count", "nhans_resample_emitted",
+    "nhans_resample_taps", "nhans_resample", "nhans_peak_normalise", "nhans_channel_mean", "nhans_resampler_open", "nhans_resampler_set_peak",
+    "nhans_resampler_push", "nhans_resampler_out_counts", "nhans_resampler_restart", "nhans_resampler_close",
 ]
+PCM_INT16, PCM_FLOAT32 = 0, 1
+RESAMPLE_QUANTISE = 1
+NORMALISE_WRAP_INT16 = 1
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25
 ABI_VERSION = 5
@@ -99,6 +104,32 @@ def load():
         lib.nhans_online_restart.argtypes = [vp, ctypes.c_int]
         lib.nhans_online_set_context.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, i64p]
         lib.nhans_online_set_embeddings.argtypes = [vp, ctypes.c_int, vp, vp, vp, i64p]
+    # (sample-rate conversion came after the slots; the library of an earlier commit as $NHANS_LIB has none of these)
+    rates = hasattr(lib, "nhans_resample")
+    if rates:
+        ip = ctypes.POINTER(ctypes.c_int)
+        lib.nhans_resample_out_count.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int]
+        lib.nhans_resample_out_count.restype = ctypes.c_int64
+        lib.nhans_resample_emitted.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        lib.nhans_resample_emitted.restype = ctypes.c_int64
+        lib.nhans_resample_taps.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+        lib.nhans_resample.argtypes = [vp, vp, ctypes.c_int, i64p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp,
+                                       i64p, vp]
+        lib.nhans_peak_normalise.argtypes = [vp, vp, i64p, ctypes.c_int, ctypes.c_int, vp, vp]
+        lib.nhans_channel_mean.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int64, vp, vp]
+        lib.nhans_channel_mean.restype = ctypes.c_int
+        lib.nhans_resampler_open.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(vp)]
+        lib.nhans_resampler_set_peak.argtypes = [vp, ctypes.c_double]
+        lib.nhans_resampler_push.argtypes = [vp, vp, i64p, ip, vp, i64p, i64p, vp]
+        lib.nhans_resampler_out_counts.argtypes = [vp, i64p, ip, i64p]
+        lib.nhans_resampler_restart.argtypes = [vp, ctypes.c_int]
+        lib.nhans_resampler_close.argtypes = [vp]
+        lib.nhans_resampler_close.restype = None
+        for name in ("nhans_resample_taps", "nhans_resample", "nhans_peak_normalise", "nhans_resampler_open",
+                     "nhans_resampler_set_peak", "nhans_resampler_push", "nhans_resampler_out_counts",
+                     "nhans_resampler_restart"):
+            getattr(lib, name).restype = ctypes.c_int
     lib.nhans_crc32c.argtypes = [ctypes.c_uint32, vp, ctypes.c_size_t]
     lib.nhans_crc32c.restype = ctypes.c_uint32
     for name in ("nhans_create", "nhans_create_ex", "nhans_set_option", "nhans_stft_features", "nhans_embed", "nhans_mask_net",

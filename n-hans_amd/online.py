@@ -46,10 +46,15 @@ def change_bounds(R):
     return spec.HOP * (R - R % 2), spec.HOP * (R + R % 2) + spec.WIN - spec.HOP
 
 
-def latency_ms(fs=spec.FS):
+def latency_ms(fs=spec.FS, in_rate=None, out_rate=None):
     """Algorithmic latency (ms) from a sample's arrival to its output: the 17-frame look-ahead plus one window, less or
-    more one hop for where the sample falls in its hop and for the even-pair rule of the iSTFT -> (185, 205) at 16 kHz."""
+    more one hop for where the sample falls in its hop and for the even-pair rule of the iSTFT -> (185, 205) at 16 kHz.
+    in_rate / out_rate: plus the filter delay of each rate conversion (resample.latency_ms: 0.625 ms beside 16 kHz)."""
     mid = (LOOKAHEAD * spec.HOP + spec.WIN) * 1000.0 / fs
+    if in_rate is not None or out_rate is not None:
+        from . import resample
+        mid += resample.latency_ms(in_rate, fs) if in_rate is not None else 0.0
+        mid += resample.latency_ms(fs, out_rate) if out_rate is not None else 0.0
     return mid - spec.HOP * 1000.0 / fs, mid + spec.HOP * 1000.0 / fs
 
 
@@ -65,7 +70,13 @@ class OnlineEnhancer:
 
     The S positions are slots that outlive their streams (include/nhans_hip.h, "Slots"): open_slots() makes an object of
     unconditioned slots, restart(i) + set_context(i, a, b) lets a new recording join in slot i, end in a push or
-    restart(i) lets it leave, set_context / set_embeddings alone change the conditioning of a running stream."""
+    restart(i) lets it leave, set_context / set_embeddings alone change the conditioning of a running stream.
+
+    in_rate / out_rate (Hz, resample.RATES): push() then takes pieces at in_rate -- in_dtype int16 or float32; peak: every
+    converted sample is divided by (peak + 1e-6) on the device, normalise_fixed -- and returns pieces at out_rate, each
+    through a resample.Resampler of its own (a second outgoing one for the mixed round trip).  The output is bit for bit
+    resample -> normalise_fixed -> offline enhance -> resample of the whole recording.  With both None the object is
+    the 16 kHz one and none of this exists."""
 
     def _begin(self, engine, S, want_mixed):
         self.eng = engine
@@ -77,8 +88,24 @@ class OnlineEnhancer:
         self.pushed = [0] * S
         self.ended = [False] * S
         self._prev = None
+        self._rs_in = self._rs_out = self._rs_mix = None
 
-    def __init__(self, engine, ctx_a, ctx_b, want_mixed=False):
+    def _rates(self, in_rate, out_rate, peak, in_dtype):
+        if in_rate is None and out_rate is None:
+            if peak is not None:
+                raise ValueError("peak= normalises the converted input: it needs in_rate")
+            return
+        from . import resample
+        if in_rate is not None:
+            self._rs_in = resample.Resampler(self.eng, self.S, in_rate, spec.FS, dtype=in_dtype, peak=peak)
+        elif peak is not None:
+            raise ValueError("peak= normalises the converted input: it needs in_rate")
+        if out_rate is not None:
+            self._rs_out = resample.Resampler(self.eng, self.S, spec.FS, out_rate)
+            if self.want_mixed:
+                self._rs_mix = resample.Resampler(self.eng, self.S, spec.FS, out_rate)
+
+    def __init__(self, engine, ctx_a, ctx_b, want_mixed=False, in_rate=None, out_rate=None, peak=None, in_dtype=np.int16):
         if len(ctx_a) != len(ctx_b):
             raise ValueError("ctx_a and ctx_b must have one recording per stream")
         self._begin(engine, len(ctx_a), want_mixed)
@@ -91,9 +118,10 @@ class OnlineEnhancer:
                                              hip.i64_array(boff), int(self.want_mixed), self._stream(), ctypes.byref(h)))
         self.handle = h
         self._free(da, db)
+        self._rates(in_rate, out_rate, peak, in_dtype)
 
     @classmethod
-    def open_slots(cls, engine, nslots, want_mixed=False):
+    def open_slots(cls, engine, nslots, want_mixed=False, in_rate=None, out_rate=None, peak=None, in_dtype=np.int16):
         """An object of nslots unconditioned slots (nhans_online_open_slots): no tower runs until a set_context."""
         self = cls.__new__(cls)
         self._begin(engine, int(nslots), want_mixed)
@@ -101,6 +129,7 @@ class OnlineEnhancer:
         h = ctypes.c_void_p()
         hip.check(self.lib.nhans_online_open_slots(engine.handle, self.S, int(self.want_mixed), self._stream(), ctypes.byref(h)))
         self.handle = h
+        self._rates(in_rate, out_rate, peak, in_dtype)
         return self
 
     # ---- device memory of either engine --------------------------------------------------------
@@ -165,6 +194,9 @@ class OnlineEnhancer:
         """Slot i becomes an open stream of 0 samples (nhans_online_restart); conditioning is kept."""
         hip.check(self.lib.nhans_online_restart(self.handle, int(i)))
         self.pushed[i], self.ended[i] = 0, False
+        for rs in (self._rs_in, self._rs_out, self._rs_mix):
+            if rs is not None:
+                rs.restart(i)
 
     def first_new_frame(self, i):
         """R of slot i: the frames of its stream already computed, which a change of conditioning leaves as they are."""
@@ -225,7 +257,20 @@ class OnlineEnhancer:
         """chunks: one 1-D float32 array per stream (may be empty); end[i]: stream i ends after its chunk.  Returns
         [(denoised, mixed)] per stream -- the samples that became final (mixed is None without want_mixed).  A push
         that saturates the f16x3 path is undone and redone in f32 inside a calibrate bracket, as Engine.enhance does
-        for a batch."""
+        for a batch.  With in_rate / out_rate the chunks are pieces at in_rate and the results pieces at out_rate; the
+        outgoing converters see only the final result of a push."""
+        if self._rs_in is None and self._rs_out is None:
+            return self._push16(chunks, end)
+        if len(chunks) != self.S:
+            raise ValueError("push: one chunk per stream (%d)" % self.S)
+        res = self._push16(self._rs_in.push(chunks, end) if self._rs_in is not None else chunks, end)
+        if self._rs_out is None:
+            return res
+        den = self._rs_out.push([d for d, _ in res], end)
+        mix = self._rs_mix.push([m for _, m in res], end) if self._rs_mix is not None else [None] * self.S
+        return list(zip(den, mix))
+
+    def _push16(self, chunks, end=None):
         if len(chunks) != self.S:
             raise ValueError("push: one chunk per stream (%d)" % self.S)
         flat, inoff = self._flat(chunks)
@@ -267,6 +312,11 @@ class OnlineEnhancer:
         return [(den[ooff[i]:ooff[i + 1]], mix[ooff[i]:ooff[i + 1]] if mix is not None else None) for i in range(self.S)]
 
     def close(self):
+        for name in ("_rs_in", "_rs_out", "_rs_mix"):
+            rs = getattr(self, name, None)
+            if rs is not None:
+                rs.close()
+                setattr(self, name, None)
         if getattr(self, "handle", None):
             self.lib.nhans_online_close(self.handle)
             self.handle = None

@@ -4,7 +4,9 @@ H hops (H x 10 ms of audio per stream), f16x3, synthetic weights.  One JSON line
   kernel_ms_per_push  sum of the per-kernel hipEvent times of nhans_profile_json over a separate profiled pass
   realtime_factor     S x pushed audio seconds / p50 push time (streams one GPU keeps up with per ... of real time)
   latency_ms          the algorithmic latency range from the output contract (look-ahead + one window, +- one hop)
-    python tools/online_bench.py [--streams 1,8,64,256] [--hops 1,4,16] [--pushes 60]
+    python tools/online_bench.py [--streams 1,8,64,256] [--hops 1,4,16] [--pushes 60] [--in_rate 48000] [--out_rate 48000]
+  (--in_rate / --out_rate: the pieces are int16 at in_rate and come back at out_rate, each through a device rate
+   converter of its own -- nhans_amd/resample.py; the line then carries "in_rate" / "out_rate" and the longer latency)
 
 --churn: a long-lived object whose callers come and go (nhans_online_open_slots).  Per (slots S, active k) it prints
 three lines, each with push p50 / p99 over the same pushes of H hops per active stream:
@@ -143,17 +145,27 @@ def main():
     ap.add_argument("--streams", default="1,8,64,256")
     ap.add_argument("--hops", default="1,4,16")
     ap.add_argument("--pushes", type=int, default=60, help="timed pushes per shape (after 40 warm-up pushes)")
+    ap.add_argument("--in_rate", type=int, default=None, help="pieces arrive as int16 at this rate (default: 16 kHz float32)")
+    ap.add_argument("--out_rate", type=int, default=None, help="pieces are returned at this rate (default: 16 kHz)")
     a = ap.parse_args()
     if a.churn:
         return churn(a)
     eng = engine.Engine("denoiser", precision="f16x3")
     ca, cb = apply.normalise(synth.silent()), apply.normalise(synth.noise_context(1))
     audio = apply.normalise(synth.mixture(1, 30.0))
-    lat = online.latency_ms()
+    lat = online.latency_ms(in_rate=a.in_rate, out_rate=a.out_rate)
+    rates = {}
+    if a.in_rate or a.out_rate:
+        rates = {"in_rate": a.in_rate, "out_rate": a.out_rate}
+    if a.in_rate:
+        # the same recording held at the input rate (nearest sample), as int16 with a fixed peak
+        idx = (np.arange(int(30.0 * a.in_rate)) * float(spec.FS) / a.in_rate).astype(np.int64)
+        audio = synth.mixture(1, 30.0)[np.minimum(idx, int(30.0 * spec.FS) - 1)]
+        rates["peak"] = 32768
     for S in [int(s) for s in a.streams.split(",")]:
         for H in [int(h) for h in a.hops.split(",")]:
-            n = H * spec.HOP
-            enh = online.OnlineEnhancer(eng, [ca] * S, [cb] * S)
+            n = H * spec.HOP if not a.in_rate else int(round(H * 0.010 * a.in_rate))
+            enh = online.OnlineEnhancer(eng, [ca] * S, [cb] * S, **rates)
             pos = [0]
 
             def push():
@@ -183,7 +195,8 @@ def main():
                               "push_ms_p99": round(p99, 3), "kernel_ms_per_push": round(kern, 3),
                               "launches_per_push": sum(v["calls"] for v in prof.values()) / 10,
                               "realtime_factor": round(S * H * 0.010 / (p50 / 1e3), 2),
-                              "latency_ms": [lat[0], lat[1]], "precision": "f16x3", "weights": "synthetic seed 7"}),
+                              "latency_ms": [lat[0], lat[1]], "precision": "f16x3", "weights": "synthetic seed 7",
+                              **{k: v for k, v in rates.items() if k != "peak"}}),
                   flush=True)
     eng.close()
     return 0
