@@ -204,6 +204,21 @@ int nhans_debug_block_output(nhans_ctx* ctx, const float* logmag_dev, const int6
                              int nclips, const float* emb_a_dev, const float* emb_b_dev,
                              int64_t frame0, int nframes, int block, float* out_dev, void* stream);
 
+/* Debug taps on every stored tensor, in the numbering of NHANS_NUM_ACTIVATIONS, as plain f32 NHWC.  Both run the
+ * production launch sequence (same plan for the whole stack, same layouts, chunking, variant, Winograd and split-K
+ * choices as nhans_mask_net / nhans_embed with the options in effect) and only convert the finished buffer.
+ * nhans_debug_activation: stack tensors, index 8 .. 24 (block b conv1 output -- after conditioning, BatchNorm and ReLU --
+ * at 8+2b, block output at 8+2b+1, last_conv at 24), for frames [frame0, frame0 + nframes) of the ragged batch, in passes of
+ * "frames_per_chunk" frame windows counted from frame0; out_dev [nframes, Ho, Wo, C].
+ * nhans_debug_tower_activation: tower tensors, index 0 .. 7 (block b conv1 output at 2b, block output at 2b+1), for n
+ * context images [n,200,201] in passes of "contexts_per_chunk"; out_dev [n, Ho, Wo, C].
+ * An index outside the range, nframes < 1, n < 1, a frame range outside the batch or a null pointer: NHANS_EINVAL. */
+int nhans_debug_activation(nhans_ctx* ctx, const float* logmag_dev, const int64_t* frame_offsets_host,
+                           int nclips, const float* emb_a_dev, const float* emb_b_dev,
+                           int64_t frame0, int nframes, int index, float* out_dev, void* stream);
+int nhans_debug_tower_activation(nhans_ctx* ctx, const float* ctx_logmag_dev, int n, int index, float* out_dev,
+                                 void* stream);
+
 /* Waits for `stream`, then returns the context's sticky status bits (NHANS_STATUS_*) in
  * *flags_out and clears them.  The hot-path calls are asynchronous, so conditions detected on the
  * device (split-f16 activation overflow) cannot be part of their return code; a caller that uses

@@ -162,6 +162,10 @@ struct nhans_ctx {
     float act_amax[kNumAct] = {};       // what the last calibration saw (diagnostics)
     unsigned* amax_dev = nullptr;       // running maxima (float bits) while calibrating
     bool calibrating = false;
+    // debug capture (nhans_debug_activation / nhans_debug_tower_activation): the tensor whose finished buffer the tap()
+    // points of the production launch sequences copy out as plain f32 NHWC, chunk after chunk; -1: none (every other call)
+    int cap_idx = -1;
+    float* cap_out = nullptr;
     float up(int i) const { return prec ? ldexpf(1.f, act_exp[i]) : 1.f; }
     float down(int i) const { return prec ? ldexpf(1.f, -act_exp[i]) : 1.f; }
     // ordering of consecutive calls that share the workspace (see include/nhans_hip.h)
@@ -341,9 +345,16 @@ bool stored_f32(const nhans_ctx* c, const StackPlan& p, int b, int cv) {
     return p.wino[b][2] && p.wino[b + 1][1] && nx.cin == nx.cout && p.wino[b + 1][2];
 }
 
-// Calibration tap: the running |x| maximum of tensor `idx` (`words` values, stored in the active precision's layout).
-void tap(nhans_ctx* c, int idx, const float* buf, size_t words, hipStream_t s, bool f32_layout = false) {
+// Tap on the finished tensor `idx` (`words` values of `chan` channels, stored in the active precision's layout).
+// Calibration: its running |x| maximum.  Debug capture: the tensor itself as f32 NHWC, out of its layout and exponent
+// (the chunks of a call follow one another in cap_out).
+void tap(nhans_ctx* c, int idx, const float* buf, size_t words, int chan, hipStream_t s, bool f32_layout = false) {
     if (c->calibrating) launch_absmax(buf, words, c->prec && !f32_layout, c->up(idx), c->amax_dev + idx, s);
+    if (c->cap_idx != idx) return;
+    if (!c->prec) note_launch("activation tap copy", hipMemcpyAsync(c->cap_out, buf, words * 4, hipMemcpyDeviceToDevice, s));
+    else if (f32_layout) launch_scale_copy(buf, words, c->up(idx), c->cap_out, s);
+    else launch_unsplit(buf, (int64_t)(words / chan), chan, c->up(idx), c->cap_out, s);
+    c->cap_out += words;
 }
 
 // ---- embedding tower for `n` context images already in HBM ----------------------------------
@@ -381,7 +392,7 @@ int embed_impl(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, float* 
                 a.kgroup = -1;                  // a handful of context images: grouped sum, split-K when small
                 run_conv(c, a, s);
             }
-            tap(c, TA(b, 0), a1, (size_t)nc * g.hout * g.wout * g.cout, s);
+            tap(c, TA(b, 0), a1, (size_t)nc * g.hout * g.wout * g.cout, g.cout, s);
             ConvArgs a{};
             fill_epilogue_defaults(c, a);
             a.nseg = 1;
@@ -399,7 +410,7 @@ int embed_impl(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, float* 
             // (the `_transform` segment reads x, whose exponent tie_exponents() keeps equal to a1's: one accumulator)
             a.in_scale = c->up(TA(b, 0)); a.out_scale = c->down(TA(b, 1));
             run_conv(c, a, s);                  // (stride 1: halo kernel; measured faster than split-K here)
-            tap(c, TA(b, 1), y, (size_t)nc * g.hout * g.wout * g.cout, s);
+            tap(c, TA(b, 1), y, (size_t)nc * g.hout * g.wout * g.cout, g.cout, s);
             std::swap(x, y);
         }
         const BlockGeo& g = T[3];
@@ -528,7 +539,7 @@ float* run_stack_chunk(nhans_ctx* c, const float* logmag, const int* rb, const S
             a.in_f32 = stored_f32(c, plan, b - 1, 1); a.out_split = c->prec && !stored_f32(c, plan, b, 0);
             conv(b, 1, a);
         }
-        if (go) tap(c, SA(b, 0), a1, (size_t)n * g.hout * g.wout * g.cout, s, stored_f32(c, plan, b, 0));
+        if (go) tap(c, SA(b, 0), a1, (size_t)n * g.hout * g.wout * g.cout, g.cout, s, stored_f32(c, plan, b, 0));
         ConvArgs a{};
         fill_epilogue_defaults(c, a);
         a.nseg = 1;
@@ -588,7 +599,7 @@ float* run_stack_chunk(nhans_ctx* c, const float* logmag, const int* rb, const S
         }
         set_out_geometry(a, n, g.hout, g.wout, g.cout, g.cout, g.cout, out);
         conv(b, 2, a);
-        if (go) tap(c, SA(b, 1), out, (size_t)n * g.hout * g.wout * g.cout, s, stored_f32(c, plan, b, 1));
+        if (go) tap(c, SA(b, 1), out, (size_t)n * g.hout * g.wout * g.cout, g.cout, s, stored_f32(c, plan, b, 1));
         if (out == y) std::swap(x, y);
     }
     result = x;
@@ -603,7 +614,7 @@ float* run_stack_chunk(nhans_ctx* c, const float* logmag, const int* rb, const S
         a.ws = c->WS("head.conv");
         a.in_scale = c->up(SA(7, 1)); a.out_scale = c->down(kActHead);
         run_conv(c, a, s);
-        tap(c, kActHead, a1, (size_t)n * g.wout * 512, s);
+        tap(c, kActHead, a1, (size_t)n * g.wout * 512, 512, s);
         result = a1;
     }
     }
@@ -1182,6 +1193,66 @@ int nhans_debug_block_output(nhans_ctx* c, const float* logmag, const int64_t* f
     Call call(c, stream);
     if (call.rc) return call.rc;
     return call.finish(debug_block_output_body(c, logmag, foff, nclips, ea, eb, frame0, nframes, block, out, stream));
+}
+
+// Any stored tensor of the stack + head (index 8 .. 24) for frames [frame0, frame0 + nframes): the production launch
+// sequence -- one plan for the whole stack, frames_per_chunk frame windows per pass counted from frame0 -- up to the block
+// that writes it; the tap() point of that tensor converts every chunk's finished buffer.
+static int debug_activation_body(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
+                                 const float* eb, int64_t frame0, int nframes, int index, float* out, void* stream) {
+    int rc = NHANS_OK;
+    if (!logmag || !foff || !ea || !eb || !out || nclips < 1 || nframes < 1) return fail(NHANS_EINVAL, "bad argument");
+    if (index < SA(0, 0) || index >= kNumAct)
+        return fail(NHANS_EINVAL, "activation index outside the stack's 8 .. " + std::to_string(kNumAct - 1) + " (tower tensors: nhans_debug_tower_activation)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t total = foff[nclips];
+    if (frame0 < 0 || frame0 + nframes > total) return fail(NHANS_EINVAL, "frame range outside batch");
+    const int64_t wf = std::min<int64_t>(c->frames_per_chunk, nframes);
+    rc = ws_reserve(c, stack_ws_bytes(c, total, nclips, wf)); if (rc) return rc;
+    StackBufs sb;
+    stack_take(c, total, nclips, wf, &sb);
+    rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc;
+    launch_frame_index(sb.foff_dev, nclips, total, sb.f_clip, sb.f_t, sb.f_T, s);
+    launch_cond(ea, eb, nclips, c->A("cond.w"), c->A("cond.base"), c->cond_cols, sb.cb_all, s);
+    const int upto = index == kActHead ? 9 : (index - SA(0, 0)) / 2 + 1;
+    c->cap_idx = index; c->cap_out = out;
+    for (int64_t g0 = frame0; g0 < frame0 + nframes; g0 += wf) {
+        run_stack_chunk(c, logmag, nullptr, sb, g0, (int)std::min<int64_t>(wf, frame0 + nframes - g0), upto, s);
+        if (launch_error_pending()) break;
+    }
+    c->cap_idx = -1; c->cap_out = nullptr;
+    return NHANS_OK;
+}
+
+int nhans_debug_activation(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
+                           const float* eb, int64_t frame0, int nframes, int index, float* out, void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(debug_activation_body(c, logmag, foff, nclips, ea, eb, frame0, nframes, index, out, stream));
+}
+
+// Any stored tensor of the embedding tower (index 0 .. 7) for n context images: nhans_embed's own launches (chunks of
+// contexts_per_chunk images, the pooled embeddings go to the workspace) with the tap() point of that tensor copying out.
+static int debug_tower_activation_body(nhans_ctx* c, const float* ctx_lm, int n, int index, float* out, void* stream) {
+    int rc = NHANS_OK;
+    if (!ctx_lm || !out || n < 1) return fail(NHANS_EINVAL, "bad argument");
+    if (index < 0 || index >= SA(0, 0))
+        return fail(NHANS_EINVAL, "activation index outside the tower's 0 .. 7 (stack tensors: nhans_debug_activation)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t nb = tower_buf_floats(c);
+    rc = ws_reserve(c, 3 * ws_size(nb, 4) + ws_size((size_t)n * kEmb, 4)); if (rc) return rc;
+    float* X = ws_take<float>(c, nb); float* A = ws_take<float>(c, nb); float* Y = ws_take<float>(c, nb);
+    float* emb = ws_take<float>(c, (size_t)n * kEmb);
+    c->cap_idx = index; c->cap_out = out;
+    rc = embed_impl(c, ctx_lm, n, emb, X, A, Y, s);
+    c->cap_idx = -1; c->cap_out = nullptr;
+    return rc;
+}
+
+int nhans_debug_tower_activation(nhans_ctx* c, const float* ctx_lm, int n, int index, float* out, void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(debug_tower_activation_body(c, ctx_lm, n, index, out, stream));
 }
 
 static int istft_body(nhans_ctx* c, const float* logmag, const float* phase, const int64_t* foff, int nclips,

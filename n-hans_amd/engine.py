@@ -158,6 +158,26 @@ class Engine:
             hip.ptr(emb_b.contiguous()), frame0, nframes, block, hip.ptr(out), self._stream()))
         return out
 
+    def activation(self, index, logmag, frame_off, emb_a, emb_b, frame0, nframes):
+        """Stored tensor `index` (8 .. 24, hip.NUM_ACTIVATIONS numbering) of the stack for frames [frame0, frame0 + nframes),
+        f32 NHWC, written by the production launches in passes of frames_per_chunk (nhans_debug_activation)."""
+        g = spec.activation_geometry()[index] if 8 <= index < hip.NUM_ACTIVATIONS else dict(hout=1, wout=1, cout=1)
+        out = torch.empty((max(nframes, 0), g["hout"], g["wout"], g["cout"]), dtype=torch.float32, device=self.device)
+        hip.check(self.lib.nhans_debug_activation(
+            self.handle, hip.ptr(logmag), hip.i64_array(frame_off), len(frame_off) - 1, hip.ptr(emb_a.contiguous()),
+            hip.ptr(emb_b.contiguous()), frame0, nframes, index, hip.ptr(out), self._stream()))
+        return out
+
+    def tower_activation(self, index, ctx_lm):
+        """Stored tensor `index` (0 .. 7) of the embedding tower for the context images ctx_lm [n,200,201], f32 NHWC
+        (nhans_debug_tower_activation: nhans_embed's launches)."""
+        n = ctx_lm.shape[0]
+        g = spec.activation_geometry()[index] if 0 <= index < 8 else dict(hout=1, wout=1, cout=1)
+        out = torch.empty((n, g["hout"], g["wout"], g["cout"]), dtype=torch.float32, device=self.device)
+        hip.check(self.lib.nhans_debug_tower_activation(self.handle, hip.ptr(ctx_lm.contiguous()), n, index, hip.ptr(out),
+                                                        self._stream()))
+        return out
+
     def istft(self, logmag, phase, frame_off):
         lens = [(frame_off[i + 1] - frame_off[i] - 1) * spec.HOP + spec.WIN if frame_off[i + 1] > frame_off[i] else 0
                 for i in range(len(frame_off) - 1)]

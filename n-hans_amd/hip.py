@@ -26,6 +26,7 @@ EXPORTS = [
     "nhans_online_set_context", "nhans_online_set_embeddings", "nhans_resample_out_count", "nhans_resample_emitted",
     "nhans_resample_taps", "nhans_resample", "nhans_peak_normalise", "nhans_channel_mean", "nhans_resampler_open", "nhans_resampler_set_peak",
     "nhans_resampler_push", "nhans_resampler_out_counts", "nhans_resampler_restart", "nhans_resampler_close",
+    "nhans_debug_activation", "nhans_debug_tower_activation",
 ]
 PCM_INT16, PCM_FLOAT32 = 0, 1
 RESAMPLE_QUANTISE = 1
@@ -130,6 +131,12 @@ def load():
                      "nhans_resampler_set_peak", "nhans_resampler_push", "nhans_resampler_out_counts",
                      "nhans_resampler_restart"):
             getattr(lib, name).restype = ctypes.c_int
+    # (the taps on every stored tensor came after the rate converter: looked up by symbol like the groups above)
+    if hasattr(lib, "nhans_debug_activation"):
+        lib.nhans_debug_activation.argtypes = [vp, vp, i64p, ctypes.c_int, vp, vp, ctypes.c_int64, ctypes.c_int,
+                                               ctypes.c_int, vp, vp]
+        lib.nhans_debug_tower_activation.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
+        lib.nhans_debug_activation.restype = lib.nhans_debug_tower_activation.restype = ctypes.c_int
     lib.nhans_crc32c.argtypes = [ctypes.c_uint32, vp, ctypes.c_size_t]
     lib.nhans_crc32c.restype = ctypes.c_uint32
     for name in ("nhans_create", "nhans_create_ex", "nhans_set_option", "nhans_stft_features", "nhans_embed", "nhans_mask_net",

@@ -96,6 +96,17 @@ def head_geometry():
                 flat=g["wout"] * 512, nout=BINS)
 
 
+def activation_geometry():
+    """dict(hout, wout, cout) of the 25 stored tensors in the library's numbering (NHANS_NUM_ACTIVATIONS): tower block b
+    conv1 output / block output at 2b / 2b+1, stack block b at 8+2b / 8+2b+1, last_conv at 24.  A block's two tensors
+    have one shape."""
+    out = []
+    for g in tower_geometry() + main_geometry():
+        out += [dict(hout=g["hout"], wout=g["wout"], cout=g["cout"])] * 2
+    h = head_geometry()
+    return out + [dict(hout=1, wout=h["win"], cout=h["cout"])]
+
+
 def variable_shapes(kind):
     """Ordered {checkpoint variable name: shape} of every float tensor the inference graph
     reads (verified against the shipped .index files in tests)."""

@@ -157,10 +157,13 @@ STACK = [("resblock1_1", 1), ("resblock1_2", 1), ("resblock2_1", 2), ("resblock2
          ("resblock3_1", 2), ("resblock3_2", 1), ("resblock4_1", 2), ("resblock4_2", 1)]  # :221-229
 
 
-def noise_resnet_block(x, W, scope, stride):
-    """SN/main.py:102-124 (channels always change in the tower, so the identity is a 1x1 conv)."""
+def noise_resnet_block(x, W, scope, stride, acts=None, idx=0):
+    """SN/main.py:102-124 (channels always change in the tower, so the identity is a 1x1 conv).
+    acts (nullable dict): receives the conv1 tensor -- after BatchNorm and ReLU -- under key idx (see embed_tower)."""
     p1 = conv(x, W, scope + "_conv1", stride, "SAME", False)
     p1 = relu(batch_norm(p1, W, scope + "_conv1"))
+    if acts is not None:
+        acts[idx] = p1
     p1 = conv(p1, W, scope + "_conv2", (1, 1), "SAME", True)
     if x.shape[3] == p1.shape[3]:
         p2 = x
@@ -169,13 +172,17 @@ def noise_resnet_block(x, W, scope, stride):
     return relu(batch_norm(p1 + p2, W, scope + "_addition"))
 
 
-def embed_tower(ctx, W, taps=None):
-    """SN/main.py:190-216 -- ctx [B,200,201] -> [B,512]; variables under 'embedding/'."""
+def embed_tower(ctx, W, taps=None, acts=None):
+    """SN/main.py:190-216 -- ctx [B,200,201] -> [B,512]; variables under 'embedding/'.
+    acts (nullable dict): receives the stored tensors of the HIP library in its numbering (NHANS_NUM_ACTIVATIONS), NHWC:
+    block b's conv1 tensor at 2b, its output at 2b+1."""
     x = np.asarray(ctx, dtype=F64)[..., None]
-    for name, stride in TOWER:
-        x = noise_resnet_block(x, W, "embedding/" + name, stride)
+    for b, (name, stride) in enumerate(TOWER):
+        x = noise_resnet_block(x, W, "embedding/" + name, stride, acts, 2 * b)
         if taps is not None:
             taps[name] = x
+        if acts is not None:
+            acts[2 * b + 1] = x
     return x.mean(axis=(1, 2))              # avg_pool over the whole map, VALID
 
 
@@ -193,8 +200,9 @@ def emb_scopes(kind):
     return ("_noise_pos_emb", "_noise_neg_emb") if kind == "denoiser" else ("_noise_emb", "_clean_emb")
 
 
-def resnet_block(x, emb_a, emb_b, W, scope, stride, kind):
-    """SN/main.py:126-187."""
+def resnet_block(x, emb_a, emb_b, W, scope, stride, kind, acts=None, idx=0):
+    """SN/main.py:126-187.  acts (nullable dict): receives the conv1 tensor -- after conditioning, BatchNorm and ReLU --
+    under key idx (see mask_net)."""
     sa, sb = emb_scopes(kind)
 
     def cond(match, s):                                   # process_noise_t_f, :139-159
@@ -208,6 +216,8 @@ def resnet_block(x, emb_a, emb_b, W, scope, stride, kind):
     pa, pb, t, f = cond(p1, scope + "_conv1")
     p1 = p1 + pa + pb + t + f
     p1 = relu(batch_norm(p1, W, scope + "_conv1"))
+    if acts is not None:
+        acts[idx] = p1
     p1 = conv(p1, W, scope + "_conv2", (1, 1), "SAME", True)
     pa, pb, t, f = cond(p1, scope + "_conv2")
     p1 = p1 + pa + pb + t + f
@@ -218,19 +228,25 @@ def resnet_block(x, emb_a, emb_b, W, scope, stride, kind):
     return relu(batch_norm(p1 + p2, W, scope + "_addition"))
 
 
-def mask_net(mixed, emb_a, emb_b, W, kind="denoiser", taps=None):
+def mask_net(mixed, emb_a, emb_b, W, kind="denoiser", taps=None, acts=None):
     """SN/main.py:219-242 given the two embeddings.  mixed [B,35,201]; emb_* [B,512].
-    Returns (out, denoised): `out` = last_dense output (the "mask logits"), denoised = add_72."""
+    Returns (out, denoised): `out` = last_dense output (the "mask logits"), denoised = add_72.
+    acts (nullable dict): receives the stored tensors of the HIP library in its numbering, NHWC: block b's conv1 tensor
+    at 8+2b, its output at 8+2b+1, last_conv (after BatchNorm and ReLU) at 24."""
     mixed = np.asarray(mixed, dtype=F64)
     x = mixed[..., None]
-    for name, stride in STACK:
-        x = resnet_block(x, emb_a, emb_b, W, name, stride, kind)
+    for b, (name, stride) in enumerate(STACK):
+        x = resnet_block(x, emb_a, emb_b, W, name, stride, kind, acts, 8 + 2 * b)
         if taps is not None:
             taps[name] = x
+        if acts is not None:
+            acts[8 + 2 * b + 1] = x
     x = conv(x, W, "last_conv", (1, 1), "VALID", False)
     x = relu(batch_norm(x, W, "last_conv"))
     if taps is not None:
         taps["last_conv"] = x
+    if acts is not None:
+        acts[24] = x
     x = x.reshape(x.shape[0], -1)                          # flatten, SN/blocks.py:64-69
     out = dense(x, W, "last_dense", True)
     return out, mixed[:, MIX_WIN // 2, :] + out

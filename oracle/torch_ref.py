@@ -68,14 +68,23 @@ class TorchRef:
         return (x - m) * (g * torch.rsqrt(v + 1e-3)) + b
 
     # -- embedding tower (SN/main.py:102-124,190-216)
-    def tower(self, ctx):
+    @staticmethod
+    def _tap(acts, idx, t):
+        if acts is not None:
+            acts[idx] = t.permute(0, 2, 3, 1).contiguous()          # NHWC, as the library stores it
+
+    def tower(self, ctx, acts=None):
+        """acts (nullable dict): receives the stored tensors of the HIP library in its numbering (NHANS_NUM_ACTIVATIONS),
+        NHWC: block b's conv1 tensor (after BatchNorm and ReLU) at 2b, its output at 2b+1."""
         x = ctx[:, None]
-        for name, st in TOWER:
+        for b, (name, st) in enumerate(TOWER):
             s = "embedding/" + name
             p1 = torch.relu(self.bn(self.conv(x, s + "_conv1", st, "SAME", False), s + "_conv1"))
+            self._tap(acts, 2 * b, p1)
             p1 = self.conv(p1, s + "_conv2", (1, 1), "SAME", True)
             p2 = self.conv(x, s + "_transform", st, "SAME", True)
             x = torch.relu(self.bn(p1 + p2, s + "_addition"))
+            self._tap(acts, 2 * b + 1, x)
         return x.mean(dim=(2, 3))
 
     def cont_embed(self, n, scope):
@@ -85,11 +94,13 @@ class TorchRef:
         return z @ self.W[scope + "_dense3/w"]
 
     # -- conditioned stack + head (SN/main.py:126-187,219-242)
-    def mask_net(self, mixed, ea, eb):
+    def mask_net(self, mixed, ea, eb, acts=None):
+        """acts (nullable dict): stored tensors in the library's numbering, NHWC: block b's conv1 tensor (after
+        conditioning, BatchNorm and ReLU) at 8+2b, its output at 8+2b+1, last_conv (after BatchNorm and ReLU) at 24."""
         sa, sb = (("_noise_pos_emb", "_noise_neg_emb") if self.kind == "denoiser"
                   else ("_noise_emb", "_clean_emb"))
         x = mixed[:, None]
-        for name, st in STACK:
+        for b, (name, st) in enumerate(STACK):
             def cond(t, s):
                 pa = ea @ self.W[s + sa + "/w"] + self.W[s + sa + "/b"]
                 pb = eb @ self.W[s + sb + "/w"] + self.W[s + sb + "/b"]
@@ -98,10 +109,13 @@ class TorchRef:
                 return t + pa[:, :, None, None] + pb[:, :, None, None] + te + fe
             p1 = self.conv(x, name + "_conv1", (st, st), "SAME", False)
             p1 = torch.relu(self.bn(cond(p1, name + "_conv1"), name + "_conv1"))
+            self._tap(acts, 8 + 2 * b, p1)
             p1 = cond(self.conv(p1, name + "_conv2", (1, 1), "SAME", True), name + "_conv2")
             p2 = x if x.shape[1] == p1.shape[1] else self.conv(x, name + "_transform", (st, st), "SAME", True)
             x = torch.relu(self.bn(p1 + p2, name + "_addition"))
+            self._tap(acts, 8 + 2 * b + 1, x)
         x = torch.relu(self.bn(self.conv(x, "last_conv", (1, 1), "VALID", False), "last_conv"))
+        self._tap(acts, 24, x)
         x = x.permute(0, 2, 3, 1).reshape(x.shape[0], -1)       # NHWC flatten: idx = w*512 + c
         out = x @ self.W["last_dense/w"] + self.W["last_dense/b"]
         return out, mixed[:, MIX_WIN // 2, :] + out

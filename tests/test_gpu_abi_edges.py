@@ -75,6 +75,31 @@ def test_argument_errors_come_back_as_codes_with_a_message(eng):
     assert eng.take_status() == 0
 
 
+def test_activation_taps_refuse_bad_arguments(eng):
+    """nhans_debug_activation / nhans_debug_tower_activation: NHANS_EINVAL like their neighbours, nothing launched."""
+    lib = eng.lib
+    lm = torch.zeros((4, 201), device="cuda")
+    emb = torch.zeros((1, 512), device="cuda")
+    ctx = torch.zeros((1, 200, 201), device="cuda")
+    out = torch.zeros(4 * 35 * 201 * 64, device="cuda")
+    foff = hip.i64_array([0, 4])
+    args = lambda frame0, n, idx: (eng.handle, hip.ptr(lm), foff, 1, hip.ptr(emb), hip.ptr(emb), frame0, n, idx, hip.ptr(out), None)
+    for idx in (-1, 7, hip.NUM_ACTIVATIONS):                  # (0 .. 7 are the tower's)
+        assert lib.nhans_debug_activation(*args(0, 4, idx)) == -1 and b"index" in lib.nhans_last_error()
+    assert lib.nhans_debug_activation(*args(2, 3, 8)) == -1 and b"frame range" in lib.nhans_last_error()
+    assert lib.nhans_debug_activation(*args(0, 0, 8)) == -1
+    assert lib.nhans_debug_activation(eng.handle, None, foff, 1, hip.ptr(emb), hip.ptr(emb), 0, 4, 8, hip.ptr(out), None) == -1
+    for idx in (-1, 8, 24):
+        assert lib.nhans_debug_tower_activation(eng.handle, hip.ptr(ctx), 1, idx, hip.ptr(out), None) == -1 and b"index" in lib.nhans_last_error()
+    assert lib.nhans_debug_tower_activation(eng.handle, hip.ptr(ctx), 0, 0, hip.ptr(out), None) == -1
+    assert lib.nhans_debug_tower_activation(eng.handle, hip.ptr(ctx), 1, 0, None, None) == -1
+    assert not out.any() and eng.take_status() == 0
+    # and the good call next to them: frames [1, 4) of tensor 8 equal those rows of the whole batch
+    whole = eng.activation(8, lm, [0, 4], emb, emb, 0, 4)
+    part = eng.activation(8, lm, [0, 4], emb, emb, 1, 3)
+    assert torch.equal(whole[1:], part) and eng.take_status() == 0
+
+
 def test_clip_without_a_frame_inside_a_batch_leaves_its_neighbours_alone(eng):
     """Straight at the ABI (the Python engine refuses such a clip): a 300-sample clip between two real ones has no
     STFT frame; its neighbours must come out exactly as they do without it, its own output stays untouched."""

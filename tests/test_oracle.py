@@ -115,6 +115,60 @@ def test_oracle_matches_torch_restatement(weights_denoiser, weights_separator):
         assert np.abs(w - r["denoised_wav"]).max() < 1e-12
 
 
+def test_torch_taps_equal_numpy_taps(weights_denoiser, weights_separator):
+    """The 25 stored tensors of the HIP library, in its numbering, as both oracles tap them (float64): conv1 tap = after
+    conditioning, BatchNorm and ReLU; block tap = after the `_addition` BatchNorm and ReLU; 24 = last_conv.  Three frames
+    (a clip's first, an inner one, its last) and one context, both models, equal to 1e-9 of each tensor's maximum -- and the
+    taps change nothing of what either computes."""
+    mix = O.trim_to_frames(O.normalise(synth.mixture(5, 0.6)))
+    lm = O.logmag_phase(O.stft(mix))[0]
+    frames = [0, 30, lm.shape[0] - 1]
+    ctx = O.context(O.logmag_phase(O.stft(O.normalise(synth.noise_context(5))))[0])[None]
+    geo = spec.activation_geometry()
+    for kind, W in (("denoiser", weights_denoiser), ("separator", weights_separator)):
+        a_np, a_t = {}, {}
+        emb = O.embed_tower(ctx, W, acts=a_np)
+        ea = np.repeat(emb, len(frames), 0)
+        eb = np.repeat(emb[:, ::-1], len(frames), 0)
+        out = O.mask_net(O.strided_crop(lm, 35)[frames], ea, eb, W, kind, acts=a_np)[0]
+        assert np.array_equal(emb, O.embed_tower(ctx, W)) and np.array_equal(out, O.mask_net(O.strided_crop(lm, 35)[frames], ea, eb, W, kind)[0])
+        R = TorchRef(W, kind, torch.float64)
+        with torch.no_grad():
+            win = R.windows(torch.from_numpy(lm))[frames]
+            emb_t = R.tower(torch.from_numpy(ctx), a_t)
+            out_t = R.mask_net(win, torch.from_numpy(ea), torch.from_numpy(eb), a_t)[0]
+            assert torch.equal(emb_t, R.tower(torch.from_numpy(ctx))) and torch.equal(out_t, R.mask_net(win, torch.from_numpy(ea), torch.from_numpy(eb))[0])
+        assert sorted(a_np) == sorted(a_t) == list(range(25))
+        for i in range(25):
+            g = geo[i]
+            assert a_np[i].shape == tuple(a_t[i].shape) == ((1 if i < 8 else len(frames)), g["hout"], g["wout"], g["cout"]), i
+            assert a_np[i].min() >= 0.0 and a_np[i].max() > 0.0                                   # every one is post-ReLU
+            assert np.abs(a_t[i].numpy() - a_np[i]).max() <= 1e-9 * np.abs(a_np[i]).max(), (kind, i)
+
+
+def test_planted_faults_are_valid_witnesses():
+    """CPU half of tests/test_gpu_layers.py::test_planted_fault_is_caught_at_its_layer.  A slice of one weight tensor
+    rounded to f16 (layer_checks.FAULTS) is a valid witness of what the layer tests add if, in float64 on their batch, it
+    (1) leaves every earlier tensor alone, (2) moves the logits / embeddings by less than the bar the suite had before --
+    the old checks are blind to it --, and (3) moves its own tensor by at least five times the layer bar of either mode,
+    which itself stays below the cap of 2e-5 of the tensor's maximum."""
+    import layer_checks as L
+    L.check_batch_geometry()
+    t64 = L.reference(L.FAULT_KIND, L.FAULT_RECIPE)[4]
+    logit_bar = L.LOGIT_TOL * max(1.0, float(t64.logits.abs().max()) / 5.0)
+    for fault, (name, sl, idx, chan) in L.FAULTS.items():
+        g = L.fault_cpu_figures(fault)
+        bar = max(K * g["err_cpu32"] + F * g["m"] for K, F in L.BAR.values())
+        old = L.EMB_TOL if idx < 8 else logit_bar
+        print("%s: tensor %d moves by %.2e of its max (layer bar %.2e of max, float32 level %.2e); %s move by %.2e (old bar %.1e)" % (
+            fault, idx, g["own"] / g["m"], bar / g["m"], g["err_cpu32"] / g["m"], "embeddings" if idx < 8 else "logits", g["averaged"], old))
+        assert g["before"] == 0.0, fault
+        assert g["averaged"] < old, (fault, g["averaged"], old)
+        assert bar < L.CAP * g["m"] and g["own"] >= 5 * bar, (fault, g["own"] / g["m"], bar / g["m"])
+        moved = torch.nonzero(g["own_by_channel"] > 0).flatten().tolist()
+        assert (moved == [chan]) if chan is not None else len(moved) > 1, (fault, moved[:8])
+
+
 def test_reference_faithful_mode_equals_deduplicated(weights_denoiser):
     """Tiling the contexts and re-running the tower per frame (reference) == embeddings once (F7)."""
     W = weights_denoiser
