@@ -424,6 +424,86 @@ int nhans_resampler_out_counts(const nhans_resampler* obj, const int64_t* in_cou
 int nhans_resampler_restart(nhans_resampler* obj, int i);
 void nhans_resampler_close(nhans_resampler* obj);
 
+/* ---- Live PCM sessions: device-rate audio in and out, one call per push ----------------------------------------------
+ * One object owns an incoming converter (rate_in -> 16000, in_format int16 or float32 elements, every converted sample
+ * divided by peak + 1e-6 as nhans_resampler_set_peak does), an online object of `nslots` slots (the section "Online
+ * enhancement" above: slots, joining, leaving, conditioning) and an outgoing stage (16000 -> rate_out), with the 16 kHz
+ * pieces between them in device buffers of its own -- grown on demand, at least doubling, so not inside the steady state of
+ * equal-sized pushes.  One push is ONE call on the context: the three stages are enqueued on the call's stream, nothing
+ * is synchronised and no sample passes through the host; every count is computed on the host.  Added without moving
+ * NHANS_ABI_VERSION; a caller that may meet an older library looks the functions up by symbol.
+ *
+ * Rates: rate_in and rate_out are each one of the rates nhans_resample converts from / to 16000 Hz, 16000 included (the
+ * one-tap copy: the object always has both stages).  Anything else: NHANS_EINVAL with both rates in nhans_last_error().
+ * out_format is NHANS_PCM_INT16 or NHANS_PCM_FLOAT32; out_scale is a finite double > 0.
+ *
+ * Output arithmetic.  den[k], mix[k]: the 16 kHz samples the online push made final (mix: the *mixed_processed round
+ * trip); w: the wet factor in effect for the push that made sample k final (0 until nhans_live_set_wet).
+ *   1. c[k] = den[k] + (mix[k] - den[k]) * float(w): three separately rounded float32 operations, never contracted --
+ *      numpy's float32 `denoised + removed * factor` of the reference's write_snc_outputs (SN/apply.py, --compensate).
+ *      With w == 0, c[k] = den[k] and mix is never read.
+ *   2. y[m] = the library's one fmaf chain over c: the taps, tap order and arithmetic of nhans_resample (16000 -> rate_out).
+ *   3. v = float32(double(y[m]) * out_scale).
+ *   4. int16 output: rintf (ties to even), clamped to [-32768, 32767], stored as int16; float32 output: v stored.
+ * The outgoing stage carries the last J values of c per slot, as a nhans_resampler carries its input: a change of w
+ * applies to the 16 kHz samples later pushes make final, and the output is the conversion of the piecewise c, bit for bit.
+ *
+ * Output contract.  After N input samples a slot's stream has emitted nhans_live_emitted (N, ended, rate_in, rate_out) =
+ *     E_out(online_emitted(E_in(N, ended), ended), ended)
+ * samples: E_in / E_out are nhans_resample_emitted for rate_in -> 16000 and 16000 -> rate_out, online_emitted is the
+ * online contract above (160 * P, or the offline length once ended).  The concatenated outputs of a stream are BIT FOR
+ * BIT this offline chain, however the input was cut, 0- and 1-sample pushes included: nhans_resample (rate_in -> 16000)
+ * of the whole recording; division by the fixed peak; trim to whole frames; nhans_enhance_clips with the mixed round
+ * trip; steps 1 - 4 above on the whole clip.
+ *
+ * Errors follow the online functions: a slot out of range, a push to an ended or unconditioned slot, a negative count,
+ * too little room, a NULL that is needed, a non-zero wet factor without NHANS_LIVE_WET: NHANS_EINVAL with the function's
+ * name in nhans_last_error(), and nothing changes.  After a kernel launch the runtime rejects (NHANS_EHIP) the stages
+ * behind it are not launched and no stage's host state has moved: the push can be repeated.
+ * Close the object BEFORE nhans_destroy(ctx). */
+#define NHANS_LIVE_WET 1   /* the online object also runs the mixed round trip, so that a wet/dry mix can be set */
+typedef struct nhans_live nhans_live;
+
+/* Host only.  The contract above; negative (NHANS_EINVAL) for unsupported rates or nsamples < 0. */
+int64_t nhans_live_emitted(int64_t nsamples, int ended, int rate_in, int rate_out);
+
+/* Opens `nslots` (>= 1) unconditioned slots, each an open stream of 0 samples (nhans_online_open_slots).  peak: finite,
+ * >= 0.  flags: 0 or NHANS_LIVE_WET. */
+int nhans_live_open_slots(nhans_ctx* ctx, int nslots, int rate_in, int in_format, double peak, int rate_out, int out_format,
+                          double out_scale, int flags, void* stream, nhans_live** out);
+
+/* Host only.  Slot `slot` becomes an open stream of 0 samples in all three stages, whatever it was; its conditioning
+ * is kept (nhans_online_restart). */
+int nhans_live_restart(nhans_live* obj, int slot);
+
+/* The slot's conditioning, with the rules and the *first_frame_out of nhans_online_set_context /
+ * nhans_online_set_embeddings (the context recordings are 16 kHz normalised float32).  The slot's streams keep running:
+ * a join is nhans_live_restart + one of these, and one of these alone changes the conditioning of a running stream. */
+int nhans_live_set_context(nhans_live* obj, int slot, const float* ctx_a_wav_dev, int64_t na, const float* ctx_b_wav_dev,
+                           int64_t nb, void* stream, int64_t* first_frame_out);
+int nhans_live_set_embeddings(nhans_live* obj, int slot, const float* emb_a_dev, const float* emb_b_dev, void* stream,
+                              int64_t* first_frame_out);
+
+/* Host only.  The wet factor w of the pushes that follow (finite; != 0 needs NHANS_LIVE_WET). */
+int nhans_live_set_wet(nhans_live* obj, double wet);
+
+/* Host only: the counts a push of in_counts_host[i] elements (end_host nullable) would report. */
+int nhans_live_out_counts(const nhans_live* obj, const int64_t* in_counts_host, const int* end_host, int64_t* out_counts_host);
+
+/* Appends in_offsets_host[i+1] - in_offsets_host[i] (>= 0) elements of in_dev (in_format) to slot i; end_host
+ * (nullable) != 0 ends the slot's stream after them.  Writes the out_counts_host[i] samples that became final, as
+ * out_format elements, at element out_offsets_host[i] of out_dev; the room out_offsets_host[i+1] - out_offsets_host[i]
+ * must hold them (nhans_live_out_counts). */
+int nhans_live_push(nhans_live* obj, const void* in_dev, const int64_t* in_offsets_host, const int* end_host, void* out_dev,
+                    const int64_t* out_offsets_host, int64_t* out_counts_host, void* stream);
+
+/* Host only.  Undoes the most recent push in all three stages -- every stage wrote the half of its carried state that it
+ * did not read -- so that it can be redone (nhans_online_rewind: a saturated push).  Once per push: a second rewind, one
+ * before any push, or one after a restart / set call that followed the push, returns NHANS_EINVAL. */
+int nhans_live_rewind(nhans_live* obj);
+
+void nhans_live_close(nhans_live* obj);
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

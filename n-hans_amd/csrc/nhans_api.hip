@@ -2056,7 +2056,7 @@ int resampler_check_push(const nhans_resampler* o, const char* fn, int i, int64_
 }
 
 int resampler_push_body(nhans_resampler* o, const void* in, const int64_t* inoff, const int* end, float* out,
-                        const int64_t* outoff, int64_t* counts, hipStream_t s) {
+                        const int64_t* outoff, int64_t* counts, hipStream_t s, const char* kernel = "resampler_push") {
     if (!inoff || !outoff || !counts) return fail(NHANS_EINVAL, "nhans_resampler_push: null argument");
     const ResampleFilter& f = *o->f;
     const int S = o->S;
@@ -2085,7 +2085,7 @@ int resampler_push_body(nhans_resampler* o, const void* in, const int64_t* inoff
         rs_add_runs(runs, &lds, f, static_cast<const char*>(in) + inoff[i] * rs_elem(o->in_format), o->h(o->cur[i], i),
                     out ? out + outoff[i] : nullptr, cnt > 0 ? o->h(1 - o->cur[i], i) : nullptr, o->N[i], (int)cnt, Eo[i], En[i]);
     }
-    const int rc = rs_launch(o->c, "resampler_push", runs, o->tab, f, o->in_format, o->flags & NHANS_RESAMPLE_QUANTISE, o->denom,
+    const int rc = rs_launch(o->c, kernel, runs, o->tab, f, o->in_format, o->flags & NHANS_RESAMPLE_QUANTISE, o->denom,
                              lds, tin, tout, s);
     if (rc) return rc;
     if (launch_error_pending()) return NHANS_OK;
@@ -2216,6 +2216,341 @@ void nhans_resampler_close(nhans_resampler* o) {
     (void)hipDeviceSynchronize();
     (void)hipFree(o->hist);
     delete o;
+}
+
+}  // extern "C"
+
+// ---- live PCM sessions (include/nhans_hip.h: nhans_live_*) -----------------------------------------------------------
+// One object = an incoming converter (a nhans_resampler rate_in -> 16 kHz with the fixed peak), an online object and the
+// outgoing stage (16 kHz -> rate_out, resample.hip: live_out_kernel), with the 16 kHz pieces between them in device
+// buffers of the object.  A push runs the three stages inside ONE Call on one stream; the stages' own workspace needs
+// (run tables, the online staging) follow each other in the context's workspace, which stream order makes safe, and
+// nothing a later stage reads lives there.
+struct nhans_live {
+    nhans_ctx* c = nullptr;
+    int device = 0, S = 0, out_format = 0;
+    bool has_wet = false;           // NHANS_LIVE_WET: the online object also makes the mixed round trip
+    float wet = 0.f;
+    double out_scale = 1.0;
+    nhans_resampler* in = nullptr;
+    nhans_online* on = nullptr;
+    // outgoing stage: the state of a nhans_resampler whose input is c (hist: [2][S][J], cur[i] = the half a push reads)
+    const ResampleFilter* fo = nullptr;
+    const float* tab_o = nullptr;
+    float* hist = nullptr;
+    struct Conv {
+        std::vector<int64_t> N;
+        std::vector<char> ended, cur;
+    } out, prev_in, prev_out;       // out.N: 16 kHz samples taken per slot; prev_*: the converters before the last push
+    float *mid = nullptr, *den = nullptr, *mix = nullptr;   // the push's 16 kHz input / denoised / mixed pieces
+    size_t mid_cap = 0, out_cap = 0;                        // (floats)
+    bool can_rewind = false;
+    float* h(int k, int i) const { return hist + ((size_t)k * S + i) * fo->J; }
+};
+
+namespace {
+
+int live_filters(const char* fn, int rate_in, int rate_out, const ResampleFilter** fi, const ResampleFilter** fo) {
+    *fi = resample_filter(rate_in, 16000);
+    *fo = resample_filter(16000, rate_out);
+    if (!*fi || !*fo)
+        return fail(NHANS_EINVAL, std::string(fn) + ": " + std::to_string(rate_in) + " Hz in / " + std::to_string(rate_out) +
+                                  " Hz out is not supported (each one of 8000, 11025, 12000, 16000, 22050, 24000, 32000, "
+                                  "44100, 48000, 88200 or 96000 Hz)");
+    return NHANS_OK;
+}
+
+int live_slot_check(const nhans_live* o, int slot, const char* fn) {
+    if (slot < 0 || slot >= o->S)
+        return fail(NHANS_EINVAL, std::string(fn) + ": slot " + std::to_string(slot) + " outside [0, " + std::to_string(o->S) + ")");
+    return NHANS_OK;
+}
+
+int live_check_push(const nhans_live* o, const char* fn, int i, int64_t cnt, bool en) {
+    if (cnt < 0) return fail(NHANS_EINVAL, std::string(fn) + ": slot " + std::to_string(i) + " has a negative sample count");
+    if (o->in->ended[i] && (cnt > 0 || en)) return fail(NHANS_EINVAL, std::string(fn) + ": slot " + std::to_string(i) + " has ended");
+    if (!o->on->cond[i] && (cnt > 0 || en))
+        return fail(NHANS_EINVAL, std::string(fn) + ": slot " + std::to_string(i) + " has no conditioning yet " +
+                                  "(nhans_live_set_context / nhans_live_set_embeddings)");
+    if (cnt > kMaxResampleClip) return fail(NHANS_EINVAL, std::string(fn) + ": push too large for one call (split it)");
+    return NHANS_OK;
+}
+
+// what a push of cnt samples (en: and the end) to slot i moves between the stages: n16 samples into the online object,
+// d16 final samples out of it, outputs [Eo, En) of the outgoing stream
+struct LivePlan {
+    int64_t cnt, n16, d16, Eo, En;
+    bool en;
+};
+LivePlan live_plan(const nhans_live* o, int i, int64_t cnt, bool en) {
+    const nhans_resampler* r = o->in;
+    const OnStream& q = o->on->st[i];
+    LivePlan p{};
+    p.cnt = cnt; p.en = en;
+    p.n16 = resample_emitted(*r->f, r->N[i] + cnt, r->ended[i] || en) - resample_emitted(*r->f, r->N[i], r->ended[i]);
+    p.d16 = on_emitted(nhans_num_frames(q.N + p.n16), q.ended || en) - on_emitted(q.T, q.ended);
+    p.Eo = resample_emitted(*o->fo, o->out.N[i], o->out.ended[i]);
+    p.En = resample_emitted(*o->fo, o->out.N[i] + p.d16, o->out.ended[i] || en);
+    return p;
+}
+
+// Grows on demand, at least doubling: equal-sized pushes stop growing after their first few.  (hipFree waits for the
+// device, so a buffer an earlier push still uses is not taken from under it.)
+int live_grow(float** p, size_t want) {
+    float* q = nullptr;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), want * 4);
+    if (e != hipSuccess) return fail(NHANS_ENOMEM, std::string("nhans_live_push: hipMalloc failed: ") + hipGetErrorString(e));
+    if (*p) (void)hipFree(*p);
+    *p = q;
+    return NHANS_OK;
+}
+
+int live_reserve(nhans_live* o, size_t n_mid, size_t n_out) {
+    if (n_mid > o->mid_cap) {
+        const size_t want = std::max<size_t>({n_mid, 2 * o->mid_cap, 4096});
+        const int rc = live_grow(&o->mid, want); if (rc) return rc;
+        o->mid_cap = want;
+    }
+    if (n_out > o->out_cap) {
+        const size_t want = std::max<size_t>({n_out, 2 * o->out_cap, 4096});
+        // (out_cap moves last: after a failure the next push tries again)
+        int rc = live_grow(&o->den, want); if (rc) return rc;
+        if (o->has_wet) { rc = live_grow(&o->mix, want); if (rc) return rc; }
+        o->out_cap = want;
+    }
+    return NHANS_OK;
+}
+
+void live_restore_in(nhans_live* o) {
+    o->in->N = o->prev_in.N; o->in->ended = o->prev_in.ended; o->in->cur = o->prev_in.cur;
+}
+
+void live_undo_online(nhans_live* o) {
+    o->on->st = o->on->prev;
+    o->on->cur = 1 - o->on->cur;
+    o->on->can_rewind = false;
+}
+
+int live_push_body(nhans_live* o, const void* in, const int64_t* inoff, const int* end, void* out, const int64_t* outoff,
+                   int64_t* counts, hipStream_t s) {
+    if (!inoff || !outoff || !counts) return fail(NHANS_EINVAL, "nhans_live_push: null argument");
+    nhans_ctx* c = o->c;
+    const int S = o->S;
+    const ResampleFilter& f = *o->fo;
+    std::vector<LivePlan> pl(S);
+    std::vector<int64_t> moff(S + 1, 0), ooff(S + 1, 0);
+    int64_t tin = 0, tout = 0;
+    for (int i = 0; i < S; ++i) {
+        const int64_t cnt = inoff[i + 1] - inoff[i];
+        const bool en = end && end[i];
+        const int rc = live_check_push(o, "nhans_live_push", i, cnt, en); if (rc) return rc;
+        pl[i] = live_plan(o, i, cnt, en);
+        if (outoff[i + 1] - outoff[i] < pl[i].En - pl[i].Eo)
+            return fail(NHANS_EINVAL, "nhans_live_push: output room of slot " + std::to_string(i) + " is " +
+                                      std::to_string(outoff[i + 1] - outoff[i]) + " samples, " +
+                                      std::to_string(pl[i].En - pl[i].Eo) + " needed (nhans_live_out_counts)");
+        moff[i + 1] = moff[i] + pl[i].n16;
+        ooff[i + 1] = ooff[i] + pl[i].d16;
+        tin += cnt; tout += pl[i].En - pl[i].Eo;
+    }
+    if ((tin > 0 && !in) || (tout > 0 && !out)) return fail(NHANS_EINVAL, "nhans_live_push: null buffer");
+    int rc = live_reserve(o, (size_t)moff[S], (size_t)ooff[S]); if (rc) return rc;
+
+    // ---- incoming stage, online push: their own bodies, each committing its host state when its launches went out ----
+    o->prev_in.N = o->in->N; o->prev_in.ended = o->in->ended; o->prev_in.cur = o->in->cur;
+    std::vector<int64_t> got(S, 0);
+    rc = resampler_push_body(o->in, in, inoff, end, o->mid, moff.data(), got.data(), s, "live_in"); if (rc) return rc;
+    if (launch_error_pending()) return NHANS_OK;          // (reported by the entry point; no stage has committed)
+    rc = online_push_body(o->on, o->mid, moff.data(), end, o->den, o->mix, ooff.data(), got.data(), s);
+    if (rc || launch_error_pending()) { live_restore_in(o); return rc; }
+
+    // ---- outgoing stage ----
+    std::vector<LiveOutRun> runs;
+    std::vector<char> flip(S, 0);
+    size_t lds = 0;
+    const size_t elem = rs_elem(o->out_format);
+    const bool wet = o->wet != 0.f;
+    for (int i = 0; i < S; ++i) {
+        const LivePlan& p = pl[i];
+        if (p.d16 == 0 && p.En == p.Eo) continue;
+        flip[i] = p.d16 > 0;
+        float* hist_out = p.d16 > 0 ? o->h(1 - o->out.cur[i], i) : nullptr;
+        char* dst = static_cast<char*>(out) + outoff[i] * elem;
+        bool first = true;
+        for (int64_t m = p.Eo; m < p.En || (first && hist_out); m += kResampleRun) {
+            const int cnt = (int)std::max<int64_t>(0, std::min<int64_t>(kResampleRun, p.En - m));
+            const int64_t t0 = m * f.M + f.half, q0 = t0 / f.L;
+            const int p0 = (int)(t0 - q0 * f.L);
+            runs.push_back({o->den + ooff[i], wet ? o->mix + ooff[i] : nullptr, o->h(o->out.cur[i], i),
+                            out ? dst + (m - p.Eo) * elem : nullptr, first ? hist_out : nullptr, (long long)o->out.N[i],
+                            (long long)(q0 - o->out.N[i]), p0, (int)p.d16, cnt});
+            lds = std::max(lds, resample_run_lds_bytes(f, p0, cnt));
+            first = false;
+            if (cnt == 0) break;
+        }
+    }
+    if (!runs.empty()) {
+        rc = ws_reserve(c, ws_size(runs.size(), sizeof(LiveOutRun)));
+        LiveOutRun* runs_dev = nullptr;
+        if (!rc) {
+            runs_dev = ws_take<LiveOutRun>(c, runs.size());
+            rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(LiveOutRun), s);
+        }
+        if (rc) { live_restore_in(o); live_undo_online(o); return rc; }
+        Prof pr(c, s, "live_out");
+        launch_live_out("live_out", runs_dev, (int)runs.size(), o->tab_o, f, o->out_format, o->wet, o->out_scale, lds, s);
+        pr.done(2.0 * f.J * (double)tout, (wet ? 8.0 : 4.0) * (double)ooff[S] + (double)elem * tout + 4.0 * runs.size() * f.tab.size());
+        if (launch_error_pending()) { live_restore_in(o); live_undo_online(o); return NHANS_OK; }
+    }
+
+    // ---- host state of the outgoing stage ----
+    o->prev_out = o->out;
+    for (int i = 0; i < S; ++i) {
+        counts[i] = pl[i].En - pl[i].Eo;
+        o->out.N[i] += pl[i].d16;
+        o->out.ended[i] = o->out.ended[i] || pl[i].en;
+        if (flip[i]) o->out.cur[i] = 1 - o->out.cur[i];
+    }
+    o->can_rewind = true;
+    return NHANS_OK;
+}
+
+void live_free(nhans_live* o) {
+    if (o->in) nhans_resampler_close(o->in);
+    if (o->on) nhans_online_close(o->on);
+    for (float* p : {o->hist, o->mid, o->den, o->mix})
+        if (p) (void)hipFree(p);
+    delete o;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nhans_live_emitted(int64_t n, int ended, int rate_in, int rate_out) {
+    const ResampleFilter *fi = nullptr, *fo = nullptr;
+    if (live_filters("nhans_live_emitted", rate_in, rate_out, &fi, &fo)) return NHANS_EINVAL;
+    if (n < 0) return fail(NHANS_EINVAL, "nhans_live_emitted: negative sample count");
+    const int64_t n16 = resample_emitted(*fi, n, ended != 0);
+    return resample_emitted(*fo, on_emitted(nhans_num_frames(n16), ended != 0), ended != 0);
+}
+
+int nhans_live_open_slots(nhans_ctx* c, int nslots, int rate_in, int in_format, double peak, int rate_out, int out_format,
+                          double out_scale, int flags, void* stream, nhans_live** out) {
+    if (!out) return fail(NHANS_EINVAL, "nhans_live_open_slots: null argument");
+    *out = nullptr;
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    if (nslots < 1) return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: nslots must be >= 1"));
+    for (int fmt : {in_format, out_format})
+        if (fmt != kResampleInt16 && fmt != kResampleFloat32)
+            return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: in_format and out_format must be NHANS_PCM_INT16 or NHANS_PCM_FLOAT32"));
+    if (!(peak >= 0.0) || !std::isfinite(peak))
+        return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: the peak must be finite and >= 0"));
+    if (!(out_scale > 0.0) || !std::isfinite(out_scale))
+        return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: out_scale must be finite and > 0"));
+    if (flags & ~NHANS_LIVE_WET) return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: unknown flag"));
+    const ResampleFilter *fi = nullptr, *fo = nullptr;
+    int rc = live_filters("nhans_live_open_slots", rate_in, rate_out, &fi, &fo); if (rc) return call.finish(rc);
+    nhans_live* o = new nhans_live();
+    o->c = c; o->device = c->device; o->S = nslots; o->out_format = out_format; o->has_wet = (flags & NHANS_LIVE_WET) != 0;
+    o->out_scale = out_scale; o->fo = fo;
+    o->out.N.assign(nslots, 0); o->out.ended.assign(nslots, 0); o->out.cur.assign(nslots, 0);
+    o->prev_out = o->out;
+    rc = rs_table(c, fo, &o->tab_o);
+    if (!rc) rc = nhans_resampler_open(c, nslots, rate_in, 16000, in_format, 0, &o->in);
+    if (!rc) rc = nhans_resampler_set_peak(o->in, peak);
+    if (!rc) rc = online_open_slots_body(c, nslots, o->has_wet, call.s, &o->on);
+    if (!rc) {
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->hist), (size_t)2 * nslots * fo->J * 4);
+        if (e != hipSuccess) rc = fail(NHANS_ENOMEM, std::string("nhans_live_open_slots: hipMalloc failed: ") + hipGetErrorString(e));
+    }
+    if (rc) { live_free(o); return call.finish(rc); }
+    *out = o;
+    return call.finish(NHANS_OK);
+}
+
+int nhans_live_restart(nhans_live* o, int slot) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_live_restart: null object");
+    const int rc = live_slot_check(o, slot, "nhans_live_restart"); if (rc) return rc;
+    // (nothing is cleared on the device: streams of 0 samples read none of the carried state, in any of the stages)
+    o->on->st[slot] = OnStream();
+    o->on->can_rewind = false;
+    o->in->N[slot] = 0; o->in->ended[slot] = 0;
+    o->out.N[slot] = 0; o->out.ended[slot] = 0;
+    o->can_rewind = false;
+    return NHANS_OK;
+}
+
+int nhans_live_set_context(nhans_live* o, int slot, const float* ca, int64_t na, const float* cbw, int64_t nb, void* stream,
+                           int64_t* first_frame_out) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_live_set_context: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    int rc = live_slot_check(o, slot, "nhans_live_set_context"); if (rc) return call.finish(rc);
+    if (!ca || !cbw) return call.finish(fail(NHANS_EINVAL, "nhans_live_set_context: null argument"));
+    if (na < 0 || nb < 0) return call.finish(fail(NHANS_EINVAL, "nhans_live_set_context: negative sample count"));
+    rc = online_set_context_body(o->on, slot, ca, na, cbw, nb, call.s, first_frame_out);
+    if (!rc && !launch_error_pending()) o->can_rewind = false;
+    return call.finish(rc);
+}
+
+int nhans_live_set_embeddings(nhans_live* o, int slot, const float* ea, const float* eb, void* stream, int64_t* first_frame_out) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_live_set_embeddings: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    int rc = live_slot_check(o, slot, "nhans_live_set_embeddings"); if (rc) return call.finish(rc);
+    if (!ea || !eb) return call.finish(fail(NHANS_EINVAL, "nhans_live_set_embeddings: null argument"));
+    rc = online_set_embeddings_body(o->on, slot, ea, eb, call.s, first_frame_out);
+    if (!rc) o->can_rewind = false;
+    return call.finish(rc);
+}
+
+int nhans_live_set_wet(nhans_live* o, double wet) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_live_set_wet: null object");
+    if (!std::isfinite(wet)) return fail(NHANS_EINVAL, "nhans_live_set_wet: the factor must be finite");
+    if ((float)wet != 0.f && !o->has_wet)
+        return fail(NHANS_EINVAL, "nhans_live_set_wet: the object was opened without NHANS_LIVE_WET, only 0 can be set");
+    o->wet = (float)wet;
+    return NHANS_OK;
+}
+
+int nhans_live_out_counts(const nhans_live* o, const int64_t* in_counts, const int* end, int64_t* counts) {
+    if (!o || !in_counts || !counts) return fail(NHANS_EINVAL, "nhans_live_out_counts: null argument");
+    for (int i = 0; i < o->S; ++i) {
+        const int rc = live_check_push(o, "nhans_live_out_counts", i, in_counts[i], end && end[i]); if (rc) return rc;
+    }
+    for (int i = 0; i < o->S; ++i) {
+        const LivePlan p = live_plan(o, i, in_counts[i], end && end[i]);
+        counts[i] = p.En - p.Eo;
+    }
+    return NHANS_OK;
+}
+
+int nhans_live_push(nhans_live* o, const void* in, const int64_t* inoff, const int* end, void* out, const int64_t* outoff,
+                    int64_t* counts, void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_live_push: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(live_push_body(o, in, inoff, end, out, outoff, counts, call.s));
+}
+
+int nhans_live_rewind(nhans_live* o) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_live_rewind: null object");
+    if (!o->can_rewind) return fail(NHANS_EINVAL, "nhans_live_rewind: no push to undo (one rewind per push)");
+    // (every stage wrote the half of its carried state that it did not read: the halves of before the push are intact)
+    live_restore_in(o);
+    live_undo_online(o);
+    o->out = o->prev_out;
+    o->can_rewind = false;
+    return NHANS_OK;
+}
+
+void nhans_live_close(nhans_live* o) {
+    if (!o) return;
+    (void)hipSetDevice(o->device);
+    (void)hipDeviceSynchronize();
+    live_free(o);
 }
 
 }  // extern "C"

@@ -314,6 +314,23 @@ size_t resample_run_lds_bytes(const ResampleFilter& f, int p0, int cnt);
 void launch_resample(const char* kernel, const ResampleRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
                      int in_format, int quantise, double denom, size_t lds_bytes, hipStream_t s);
 
+// The outgoing stage of a live PCM session (include/nhans_hip.h: nhans_live_*): a ResampleRun whose input is not stored
+// anywhere -- sample k0 + rel of the stream is c = den[rel] + (mix[rel] - den[rel]) * wet, formed while the span is
+// staged (mix == nullptr: c = den[rel], the wet factor is 0) -- and whose outputs are scaled and stored as int16 or
+// float32.  `hist` / `hist_out` carry c, as ResampleRun's carry x.
+struct LiveOutRun {
+    const float* den;
+    const float* mix;       // nullable: wet == 0
+    const float* hist;      // the J values of c before k0
+    void* dst;              // int16 or float32 elements, by the launch's out_format
+    float* hist_out;        // non-null: this workgroup also writes the J values of c before k0 + n_new
+    long long k0;
+    long long qrel0;        // q0 - k0
+    int p0, n_new, cnt;
+};
+void launch_live_out(const char* kernel, const LiveOutRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
+                     int out_format, float wet, double out_scale, size_t lds_bytes, hipStream_t s);
+
 // peak + normalise: blocks of <= kNormBlock samples; block b belongs to a clip whose blocks are [pb0, pb0 + pbn)
 struct NormBlock {
     long long off;

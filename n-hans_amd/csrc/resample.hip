@@ -160,6 +160,53 @@ __global__ void __launch_bounds__(256) resample_kernel(const ResampleRun* __rest
         for (int t = tid; t < J; t += 256) r.hist_out[t] = run_sample(src, r, (long long)r.n_new - J + t, J);
 }
 
+// value k0 + rel of a live session's combined stream c: three separately rounded float32 operations (numpy's
+// `den + (mix - den) * factor`), never contracted; with mix == nullptr (wet factor 0) c is den and mix is not read
+__device__ __forceinline__ float live_sample(const LiveOutRun& r, long long rel, int J, float wet) {
+    if (rel >= r.n_new) return 0.f;
+    if (rel >= 0) {
+        const float d = r.den[rel];
+        if (!r.mix) return d;
+        return __fadd_rn(d, __fmul_rn(__fsub_rn(r.mix[rel], d), wet));
+    }
+    const long long a = rel + J;
+    if (a >= 0 && r.k0 + rel >= 0 && r.hist) return r.hist[a];
+    return 0.f;
+}
+
+__device__ __forceinline__ void live_store(int16_t* dst, int i, float v) {
+    dst[i] = (int16_t)fminf(fmaxf(rintf(v), -32768.f), 32767.f);
+}
+__device__ __forceinline__ void live_store(float* dst, int i, float v) { dst[i] = v; }
+
+// resample_kernel with both ends changed: the span is formed from den / mix / the carried c while it is staged, and the
+// epilogue scales in double, then rounds and clamps (int16) and stores PCM.  The LDS layout, the lane -> output map and
+// the chain (fir_chain) are resample_kernel's, so y is bit for bit nhans_resample of c.  The int16 stores are plain
+// 2-byte stores: a slot's destination is only 2-byte aligned, and the 64 lanes of a wave write 128 consecutive bytes.
+template <typename TOut>
+__global__ void __launch_bounds__(256) live_out_kernel(const LiveOutRun* __restrict__ runs, const float* __restrict__ tab,
+                                                       int L, int M, int J, int tab4, float wet, double scale) {
+    extern __shared__ float4 rs_lds[];
+    float* tl = reinterpret_cast<float*>(rs_lds);
+    float* xs = tl + 4 * tab4;
+    const LiveOutRun r = runs[blockIdx.x];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < tab4; i += 256) rs_lds[i] = reinterpret_cast<const float4*>(tab)[i];
+    const int span = r.cnt > 0 ? (r.p0 + (r.cnt - 1) * M) / L + J : 0;
+    const long long lo = r.qrel0 - (J - 1);
+    for (int s = tid; s < span; s += 256) xs[s] = live_sample(r, lo + s, J, wet);
+    __syncthreads();
+    TOut* dst = static_cast<TOut*>(r.dst);
+    for (int i = tid; i < r.cnt; i += 256) {
+        const int t = r.p0 + i * M;
+        const int q = t / L, p = t - q * L;
+        const float y = fir_chain(tl + p, L, xs + (J - 1) + q, J);
+        live_store(dst, i, (float)((double)y * scale));
+    }
+    if (r.hist_out)
+        for (int t = tid; t < J; t += 256) r.hist_out[t] = live_sample(r, (long long)r.n_new - J + t, J, wet);
+}
+
 __device__ __forceinline__ float block_max(float m) {
     __shared__ float part[4];
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off));
@@ -219,6 +266,19 @@ void launch_resample(const char* kernel, const ResampleRun* runs_dev, int nruns,
     else
         NHANS_LAUNCH(kernel, resample_kernel<float>, dim3(nruns), dim3(256), lds_bytes, s, runs_dev, tab_dev, f.L, f.M, f.J,
                      tab4, quantise, denom);
+}
+
+void launch_live_out(const char* kernel, const LiveOutRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
+                     int out_format, float wet, double out_scale, size_t lds_bytes, hipStream_t s) {
+    if (nruns <= 0) return;
+    if (lds_bytes > (size_t)64 << 10) { note_refusal(kernel); return; }
+    const int tab4 = (int)(f.tab.size() / 4);
+    if (out_format == kResampleInt16)
+        NHANS_LAUNCH(kernel, live_out_kernel<int16_t>, dim3(nruns), dim3(256), lds_bytes, s, runs_dev, tab_dev, f.L, f.M, f.J,
+                     tab4, wet, out_scale);
+    else
+        NHANS_LAUNCH(kernel, live_out_kernel<float>, dim3(nruns), dim3(256), lds_bytes, s, runs_dev, tab_dev, f.L, f.M, f.J,
+                     tab4, wet, out_scale);
 }
 
 void launch_peak_partial(const float* x, const NormBlock* blocks_dev, int nblocks, int wrap, float* partial, hipStream_t s) {

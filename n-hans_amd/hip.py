@@ -27,10 +27,14 @@ EXPORTS = [
     "nhans_resample_taps", "nhans_resample", "nhans_peak_normalise", "nhans_channel_mean", "nhans_resampler_open", "nhans_resampler_set_peak",
     "nhans_resampler_push", "nhans_resampler_out_counts", "nhans_resampler_restart", "nhans_resampler_close",
     "nhans_debug_activation", "nhans_debug_tower_activation",
+    "nhans_live_emitted", "nhans_live_open_slots", "nhans_live_restart", "nhans_live_set_context",
+    "nhans_live_set_embeddings", "nhans_live_set_wet", "nhans_live_out_counts", "nhans_live_push", "nhans_live_rewind",
+    "nhans_live_close",
 ]
 PCM_INT16, PCM_FLOAT32 = 0, 1
 RESAMPLE_QUANTISE = 1
 NORMALISE_WRAP_INT16 = 1
+LIVE_WET = 1
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25
 ABI_VERSION = 5
@@ -137,6 +141,25 @@ def load():
                                                ctypes.c_int, vp, vp]
         lib.nhans_debug_tower_activation.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
         lib.nhans_debug_activation.restype = lib.nhans_debug_tower_activation.restype = ctypes.c_int
+    # (live PCM sessions came after those: looked up by symbol as well)
+    if hasattr(lib, "nhans_live_push"):
+        ip = ctypes.POINTER(ctypes.c_int)
+        lib.nhans_live_emitted.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        lib.nhans_live_emitted.restype = ctypes.c_int64
+        lib.nhans_live_open_slots.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_double, ctypes.c_int, vp, ctypes.POINTER(vp)]
+        lib.nhans_live_restart.argtypes = [vp, ctypes.c_int]
+        lib.nhans_live_set_context.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, i64p]
+        lib.nhans_live_set_embeddings.argtypes = [vp, ctypes.c_int, vp, vp, vp, i64p]
+        lib.nhans_live_set_wet.argtypes = [vp, ctypes.c_double]
+        lib.nhans_live_out_counts.argtypes = [vp, i64p, ip, i64p]
+        lib.nhans_live_push.argtypes = [vp, vp, i64p, ip, vp, i64p, i64p, vp]
+        lib.nhans_live_rewind.argtypes = [vp]
+        lib.nhans_live_close.argtypes = [vp]
+        lib.nhans_live_close.restype = None
+        for name in ("nhans_live_open_slots", "nhans_live_restart", "nhans_live_set_context", "nhans_live_set_embeddings",
+                     "nhans_live_set_wet", "nhans_live_out_counts", "nhans_live_push", "nhans_live_rewind"):
+            getattr(lib, name).restype = ctypes.c_int
     lib.nhans_crc32c.argtypes = [ctypes.c_uint32, vp, ctypes.c_size_t]
     lib.nhans_crc32c.restype = ctypes.c_uint32
     for name in ("nhans_create", "nhans_create_ex", "nhans_set_option", "nhans_stft_features", "nhans_embed", "nhans_mask_net",

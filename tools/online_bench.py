@@ -7,6 +7,9 @@ H hops (H x 10 ms of audio per stream), f16x3, synthetic weights.  One JSON line
     python tools/online_bench.py [--streams 1,8,64,256] [--hops 1,4,16] [--pushes 60] [--in_rate 48000] [--out_rate 48000]
   (--in_rate / --out_rate: the pieces are int16 at in_rate and come back at out_rate, each through a device rate
    converter of its own -- nhans_amd/resample.py; the line then carries "in_rate" / "out_rate" and the longer latency)
+  (--live, with both rates: the same pushes through a live.LiveSession -- nhans_live_push, one C call per push, the
+   16 kHz pieces handed over on the device, int16 in and int16 out -- instead of OnlineEnhancer; the line carries
+   "mode": "live".  --out F appends the lines to F)
 
 --churn: a long-lived object whose callers come and go (nhans_online_open_slots).  Per (slots S, active k) it prints
 three lines, each with push p50 / p99 over the same pushes of H hops per active stream:
@@ -30,7 +33,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import nhans_amd  # noqa: E402,F401
-from nhans_amd import apply, engine, hip, online, spec, synth  # noqa: E402
+from nhans_amd import apply, engine, hip, live, online, spec, synth  # noqa: E402
 
 
 def _timed(fn):
@@ -147,9 +150,13 @@ def main():
     ap.add_argument("--pushes", type=int, default=60, help="timed pushes per shape (after 40 warm-up pushes)")
     ap.add_argument("--in_rate", type=int, default=None, help="pieces arrive as int16 at this rate (default: 16 kHz float32)")
     ap.add_argument("--out_rate", type=int, default=None, help="pieces are returned at this rate (default: 16 kHz)")
+    ap.add_argument("--live", action="store_true", help="drive a live.LiveSession (needs --in_rate and --out_rate)")
     a = ap.parse_args()
     if a.churn:
         return churn(a)
+    if a.live and not (a.in_rate and a.out_rate):
+        ap.error("--live needs --in_rate and --out_rate")
+    out = open(a.out, "a") if a.out else None
     eng = engine.Engine("denoiser", precision="f16x3")
     ca, cb = apply.normalise(synth.silent()), apply.normalise(synth.noise_context(1))
     audio = apply.normalise(synth.mixture(1, 30.0))
@@ -165,7 +172,16 @@ def main():
     for S in [int(s) for s in a.streams.split(",")]:
         for H in [int(h) for h in a.hops.split(",")]:
             n = H * spec.HOP if not a.in_rate else int(round(H * 0.010 * a.in_rate))
-            enh = online.OnlineEnhancer(eng, [ca] * S, [cb] * S, **rates)
+            if a.live:
+                enh = live.LiveSession(eng, S, a.in_rate, a.out_rate, rates["peak"])
+                # (one tower run; every slot gets its rows)
+                emb = eng.embed(eng.stft_features(torch.from_numpy(np.concatenate([ca, cb])).to(eng.device),
+                                                  [0, len(ca), len(ca) + len(cb)], max_frames=spec.NOISE_WIN,
+                                                  want_phase=False)[0].reshape(2, spec.NOISE_WIN, spec.BINS))
+                for i in range(S):
+                    enh.set_embeddings(i, emb[0], emb[1])
+            else:
+                enh = online.OnlineEnhancer(eng, [ca] * S, [cb] * S, **rates)
             pos = [0]
 
             def push():
@@ -191,13 +207,17 @@ def main():
             enh.close()
             kern = sum(v["ms"] for v in prof.values()) / 10
             p50, p99 = float(np.percentile(ts, 50)), float(np.percentile(ts, 99))
-            print(json.dumps({"streams": S, "hops_per_push": H, "push_audio_ms": H * 10, "push_ms_p50": round(p50, 3),
-                              "push_ms_p99": round(p99, 3), "kernel_ms_per_push": round(kern, 3),
-                              "launches_per_push": sum(v["calls"] for v in prof.values()) / 10,
-                              "realtime_factor": round(S * H * 0.010 / (p50 / 1e3), 2),
-                              "latency_ms": [lat[0], lat[1]], "precision": "f16x3", "weights": "synthetic seed 7",
-                              **{k: v for k, v in rates.items() if k != "peak"}}),
-                  flush=True)
+            line = json.dumps({"mode": "live" if a.live else "online", "streams": S, "hops_per_push": H,
+                               "push_audio_ms": H * 10, "push_ms_p50": round(p50, 3),
+                               "push_ms_p99": round(p99, 3), "kernel_ms_per_push": round(kern, 3),
+                               "launches_per_push": sum(v["calls"] for v in prof.values()) / 10,
+                               "realtime_factor": round(S * H * 0.010 / (p50 / 1e3), 2),
+                               "latency_ms": [lat[0], lat[1]], "precision": "f16x3", "weights": "synthetic seed 7",
+                               **{k: v for k, v in rates.items() if k != "peak"}})
+            print(line, flush=True)
+            if out:
+                out.write(line + "\n")
+                out.flush()
     eng.close()
     return 0
 
