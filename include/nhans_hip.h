@@ -97,7 +97,14 @@ int nhans_create_ex(int model_kind, const void* folded_blob, size_t nbytes, int 
                     nhans_ctx** out);
 void nhans_destroy(nhans_ctx* ctx);
 
-/* Options: "frames_per_chunk" (mask-net frame windows per pass, 1..4769 -- the conv kernels address a pass's
+/* Options: "lookahead" (L, 0..17 frames, default 17: what every release so far computed, bit for bit.  Frame g of a clip
+ *           of T frames is computed with its clip length taken as T_g = min(T, g + L + 1): the rows of its 35-row window
+ *           at clip positions >= T_g read as 0.0, the network's own end-of-clip behaviour -- strided_crop, SN/apply.py:
+ *           170-186 -- applied L frames behind the frame; centre row, phase, iSTFT and pairing are unchanged.  Applies to
+ *           nhans_mask_net, nhans_enhance_clips and the three debug taps of the stack; the only device-side difference is
+ *           the per-frame length table.  This is the offline twin of a live stream's look-ahead, "Look-ahead" below:
+ *           online and live objects carry their own L and ignore this option.  Outside 0..17: NHANS_EINVAL),
+ *          "frames_per_chunk" (mask-net frame windows per pass, 1..4769 -- the conv kernels address a pass's
  *           largest tensor, frames x 35 x 201 x 64 elements, with 32-bit offsets; default 3776: 24 GB of workspace
  *           for batches that large, 6.4 MB per frame, chosen so that the launches fill whole waves of 256 workgroups),
  *          "contexts_per_chunk" (embedding-tower images per pass, default 64),
@@ -253,13 +260,22 @@ uint32_t nhans_crc32c(uint32_t crc, const void* data_host, size_t nbytes);
  * each frame on its own and the iSTFT sums each output sample from its <= 3 frames in a fixed order, so the online
  * output is BIT FOR BIT what nhans_enhance_clips computes for the same samples trimmed by the offline rule.
  *
- * Output contract, per online stream.  N = samples pushed so far, T = nhans_num_frames(N), R = max(0, T - 17) (the
- * frames whose window is complete), P = R rounded down to an even number.  Until the stream ends, the samples emitted
+ * Output contract, per online stream.  N = samples pushed so far, T = nhans_num_frames(N), L = the slot's look-ahead (17
+ * unless nhans_online_set_lookahead said otherwise), R = max(0, T - L) (the frames whose L look-ahead rows exist; T once
+ * the stream has ended), P = R rounded down to an even number.  Until the stream ends, the samples emitted
  * so far number 160 * P; once it has ended they number (T - 1) * 160 + 400, or 0 if T = 0 -- the offline output length
  * of the input trimmed to whole frames (the samples of an incomplete last hop are dropped, as offline).  P is even
  * because the offline iSTFT transforms frames in pairs (2k, 2k+1) of the clip: a frame is synthesised with the offline
- * bits once its partner exists or the stream has ended.  Algorithmic latency: the 17-frame look-ahead plus one window,
- * 185 - 205 ms at 16 kHz.
+ * bits once its partner exists or the stream has ended.  Algorithmic latency: the L-frame look-ahead plus one window,
+ * (160 L + 400) / 16 kHz = 10 L + 25 ms, +- 10 ms for where a sample falls in its hop and for the pair rule: 185 - 205 ms
+ * at the default L = 17, 35 - 55 ms at L = 2, 15 - 35 ms at L = 0.
+ *
+ * Look-ahead.  With L < 17 frame g is computed as soon as frame g + L exists, with its clip length taken as g + L + 1 (or
+ * the stream's final length, if that is smaller): the output is BIT FOR BIT nhans_enhance_clips under option "lookahead"
+ * = L ("den_L").  den_L is a function of the recording and L alone, never of the cutting: a frame computed in a push that
+ * already holds more than L rows behind it still reads them as 0.0.  What a small L costs in quality is a property of the
+ * trained model; nothing in this library measures it.  The carried state needs no more room: T - lo <= L + 24 <= 41 rows
+ * of spectrogram and R - S0 <= 24 denoised rows for every L <= 17.
  *
  * Calls on the context stay ordered as every other call is (see the top of this file): offline calls and other online
  * objects of the same context may be interleaved with pushes.  A push whose ready frames exceed "frames_per_chunk" runs
@@ -278,7 +294,8 @@ uint32_t nhans_crc32c(uint32_t crc, const void* data_host, size_t nbytes);
  *              (the samples not emitted yet are dropped: the output is the first 160 * P samples of the offline one).
  *   again      a slot that has ended, or was abandoned, is taken over by the next join; conditioning survives a restart.
  * Pushing samples or an end to an unconditioned slot is NHANS_EINVAL.  nhans_online_out_counts follows the slot's
- * current stream.  The slot count is fixed when the object is opened.
+ * current stream.  The slot count is fixed when the object is opened.  A slot's look-ahead survives a restart, as its
+ * conditioning does.
  *
  * Changing the conditioning of a running stream (the set functions alone, no restart).  Let R be the number of frames of
  * the slot's stream already computed when the call is made (R above; T once the stream has ended): the call reports it.
@@ -348,6 +365,12 @@ int nhans_online_out_counts(const nhans_online* obj, const int64_t* in_counts_ho
  * push: a second rewind, one before any push, or one after a restart / set call that followed the push, returns
  * NHANS_EINVAL.  A rewind never brings back a stream that nhans_online_restart replaced. */
 int nhans_online_rewind(nhans_online* obj);
+
+/* Host only.  The look-ahead L (0..17 frames) of slot `slot`, for its current stream and those that follow it in the slot.
+ * Allowed while the slot's stream is open with 0 samples pushed (after open, or after nhans_online_restart); on a stream
+ * with samples, an ended one, or L outside 0..17: NHANS_EINVAL and nothing changes.  Makes the last push final, as a
+ * restart does (nhans_online_rewind).  nhans_online_out_counts and the *first_frame_out of the set calls follow it. */
+int nhans_online_set_lookahead(nhans_online* obj, int slot, int lookahead);
 
 void nhans_online_close(nhans_online* obj);
 
@@ -449,7 +472,7 @@ void nhans_resampler_close(nhans_resampler* obj);
  * applies to the 16 kHz samples later pushes make final, and the output is the conversion of the piecewise c, bit for bit.
  *
  * Output contract.  After N input samples a slot's stream has emitted nhans_live_emitted (N, ended, rate_in, rate_out) =
- *     E_out(online_emitted(E_in(N, ended), ended), ended)
+ *     E_out(online_emitted(E_in(N, ended), ended), ended)        (slots of look-ahead L < 17: nhans_lookahead_live_emitted)
  * samples: E_in / E_out are nhans_resample_emitted for rate_in -> 16000 and 16000 -> rate_out, online_emitted is the
  * online contract above (160 * P, or the offline length once ended).  The concatenated outputs of a stream are BIT FOR
  * BIT this offline chain, however the input was cut, 0- and 1-sample pushes included: nhans_resample (rate_in -> 16000)
@@ -496,6 +519,17 @@ int nhans_live_out_counts(const nhans_live* obj, const int64_t* in_counts_host, 
  * must hold them (nhans_live_out_counts). */
 int nhans_live_push(nhans_live* obj, const void* in_dev, const int64_t* in_offsets_host, const int* end_host, void* out_dev,
                     const int64_t* out_offsets_host, int64_t* out_counts_host, void* stream);
+
+/* Look-ahead of a live slot.  (The two names do not begin with nhans_live_: the ten functions above are the whole set of
+ * that prefix a binding of this section's first release checks for.)
+ * nhans_lookahead_live_emitted: host only, no object -- the output contract above with the online stage at look-ahead L;
+ * nhans_live_emitted is this function at L = 17.  Negative (NHANS_EINVAL) also for L outside 0..17.
+ * nhans_lookahead_live_set: host only -- nhans_online_set_lookahead for the slot's online stage, allowed while the slot's
+ * stream has 0 samples in all three stages (after open, or after nhans_live_restart), else NHANS_EINVAL and nothing
+ * changes; L survives nhans_live_restart; the last push becomes final (nhans_live_rewind).  The output is then bit for
+ * bit the offline chain above with nhans_enhance_clips under option "lookahead" = L. */
+int64_t nhans_lookahead_live_emitted(int64_t nsamples, int ended, int rate_in, int rate_out, int lookahead);
+int nhans_lookahead_live_set(nhans_live* obj, int slot, int lookahead);
 
 /* Host only.  Undoes the most recent push in all three stages -- every stage wrote the half of its carried state that it
  * did not read -- so that it can be redone (nhans_online_rewind: a saturated push).  Once per push: a second rewind, one

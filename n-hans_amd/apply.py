@@ -62,6 +62,7 @@ class Flags(object):
     online_ms = None     # --online_ms: file mode through the online path (online.py) in pieces of this many ms
     convert_on = "host"  # --convert_on gpu: format / rate conversion and normalisation of the files on the device (resample.py)
     output_rate = "16000"    # --output_rate input: the output files at the input file's rate (converted back on the device)
+    lookahead_ms = 10 * spec.LOOKAHEAD   # --lookahead_ms: 10 ms per frame of look-ahead (include/nhans_hip.h: "lookahead"), 170 = all 17
 
 
 FLAGS = Flags()
@@ -236,6 +237,12 @@ def set_engine(kind, eng):
 
 
 # ------------------------------------------------------------------------------ apply_*
+def _lookahead_kw():
+    """{} at the default, so that an installed engine without the keyword (set_engine) keeps working unasked."""
+    L = int(getattr(FLAGS, "lookahead_ms", 10 * spec.LOOKAHEAD)) // 10
+    return {} if L == spec.LOOKAHEAD else {"lookahead": L}
+
+
 def _enhance_files(kind, mixedpath, ctx_a_path, ctx_b_path):
     """-> (denoised_samples, mixed_processed_samples) float32 for one file triple; ctx order is
     resnet_block argument order."""
@@ -251,7 +258,7 @@ def _enhance_files(kind, mixedpath, ctx_a_path, ctx_b_path):
     if getattr(FLAGS, "online_ms", None):
         res = _enhance_online(eng, mixedpath, ca, cb, FLAGS.online_ms, mixed if FLAGS.convert_on == "gpu" else None)
     else:
-        res = eng.enhance([mixed], [ca], [cb], want_mixed=True)
+        res = eng.enhance([mixed], [ca], [cb], want_mixed=True, **_lookahead_kw())
     if TIMING is not None:
         TIMING.update(read_wavs_s=t1 - t0, engine_s=t2 - t1, enhance_s=time.perf_counter() - t2,
                       engine=type(eng).__name__, audio_s=len(mixed) / float(FLAGS.Fs))
@@ -271,7 +278,7 @@ def _enhance_online(eng, mixedpath, ca, cb, piece_ms, normalised=None):
             peak = np.max(np.abs(x)) if len(x) else 0
         x = online.normalise_fixed(x, peak)
     step = max(1, int(round(piece_ms * FLAGS.Fs / 1000.0)))
-    enh = online.OnlineEnhancer(eng, [ca], [cb], want_mixed=True)
+    enh = online.OnlineEnhancer(eng, [ca], [cb], want_mixed=True, **_lookahead_kw())
     try:
         den, mix = [], []
         for i in range(0, max(len(x), 1), step):
@@ -384,7 +391,7 @@ def _enhance_in_calls(eng, mixes, ca, cb):
         while j < len(mixes) and (j == i or tot + len(mixes[j]) <= MAX_CALL_SAMPLES):
             tot += len(mixes[j])
             j += 1
-        res = eng.enhance(mixes[i:j], ca[i:j], cb[i:j], want_mixed=True)
+        res = eng.enhance(mixes[i:j], ca[i:j], cb[i:j], want_mixed=True, **_lookahead_kw())
         outs.extend(zip(res["denoised_wav"], res["mixed_wav"]))
         i = j
     return outs
@@ -564,7 +571,15 @@ def _parse(argv, prog):
                         'the default) or gpu (the device rate converter, rates of nhans_amd.resample.RATES)')
     p.add_argument('--output_rate', default='16000', choices=['16000', 'input'],
                    help='input: write the output files at the input file\'s rate (converted back on the device)')
+    p.add_argument('--lookahead_ms', type=float, default=10.0 * spec.LOOKAHEAD,
+                   help='future audio every output frame may use: a multiple of 10 in 0 ... 170 (default 170, all 17 frames '
+                        'of the window).  Less is what a live stream of that look-ahead would have produced -- latency '
+                        '10 ms per frame + 25 ms -- at a cost in quality that depends on the trained model')
     a = p.parse_args(argv)
+    if not 0 <= a.lookahead_ms <= 10 * spec.LOOKAHEAD or a.lookahead_ms != 10 * int(a.lookahead_ms // 10):
+        p.error('--lookahead_ms must be a multiple of 10 in 0 ... %d (one 10 ms frame of look-ahead each); got %g'
+                % (10 * spec.LOOKAHEAD, a.lookahead_ms))
+    a.lookahead_ms = int(a.lookahead_ms)
     if a.online_ms is not None:
         if a.online_ms <= 0:
             p.error('--online_ms must be positive')

@@ -288,7 +288,7 @@ void launch_direct_conv64(const DirectArgs& a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------
-__global__ void frame_index_kernel(const int64_t* off, int nclips, int64_t total, int* f_clip, int* f_t,
+__global__ void frame_index_kernel(const int64_t* off, int nclips, int64_t total, int lookahead, int* f_clip, int* f_t,
                                    int* f_T) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= total) return;
@@ -298,15 +298,17 @@ __global__ void frame_index_kernel(const int64_t* off, int nclips, int64_t total
         if (off[mid] <= g) lo = mid; else hi = mid;
     }
     f_clip[g] = lo;
-    f_t[g] = (int)(g - off[lo]);
-    f_T[g] = (int)(off[lo + 1] - off[lo]);
+    const int64_t t = g - off[lo], len = off[lo + 1] - off[lo];
+    f_t[g] = (int)t;
+    // (the clip as this frame sees it: with a look-ahead below 17 the recording "ends" lookahead frames after the frame)
+    f_T[g] = (int)(len < t + lookahead + 1 ? len : t + lookahead + 1);
 }
 
-void launch_frame_index(const int64_t* frame_offsets_dev, int nclips, int64_t total, int* f_clip, int* f_t,
+void launch_frame_index(const int64_t* frame_offsets_dev, int nclips, int64_t total, int lookahead, int* f_clip, int* f_t,
                         int* f_T, hipStream_t s) {
     if (total <= 0) return;
     NHANS_LAUNCH("frame_index", frame_index_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                       frame_offsets_dev, nclips, total, f_clip, f_t, f_T);
+                       frame_offsets_dev, nclips, total, lookahead, f_clip, f_t, f_T);
 }
 
 // ---------------------------------------------------------------------------------------------

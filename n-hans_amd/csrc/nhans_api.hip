@@ -134,6 +134,7 @@ struct nhans_ctx {
     // still fits the kernels' 32-bit element offsets; the three ping-pong buffers are then 20 GB of the 288.
     int64_t frames_per_chunk = 3776;
     int contexts_per_chunk = 64;
+    int lookahead = kCenter;    // option lookahead: frame t of a clip sees the clip end at min(len, t + lookahead + 1) (offline calls)
     // pinned staging ring for the small host tables (offsets, block lists) copied per call
     char* pin = nullptr;
     size_t pin_bytes = (size_t)16 << 20, pin_top = 0;
@@ -662,7 +663,7 @@ int mask_net_impl(nhans_ctx* c, const float* logmag, const int64_t* foff, int nc
                   hipStream_t s) {
     const int64_t total = foff[nclips];
     { int rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc; }
-    launch_frame_index(sb.foff_dev, nclips, total, sb.f_clip, sb.f_t, sb.f_T, s);
+    launch_frame_index(sb.foff_dev, nclips, total, c->lookahead, sb.f_clip, sb.f_t, sb.f_T, s);
     return mask_net_run(c, logmag, nullptr, logmag, total, nclips, ea, eb, logits, denoised, sb, wf, s);
 }
 
@@ -1035,6 +1036,10 @@ int nhans_set_option(nhans_ctx* c, const char* key, int64_t value) {
         c->frames_per_chunk = value;
     }
     else if (k == "contexts_per_chunk") { if (value < 1) return fail(NHANS_EINVAL, "contexts_per_chunk < 1"); c->contexts_per_chunk = (int)value; }
+    else if (k == "lookahead") {
+        if (value < 0 || value > kCenter) return fail(NHANS_EINVAL, "lookahead must be in [0, " + std::to_string(kCenter) + "] frames");
+        c->lookahead = (int)value;
+    }
     else if (k == "profile") c->profile = value != 0;
     else if (k == "debug_cycles_ptr") {
         if (!kDev) return fail(NHANS_EINVAL, "debug_cycles_ptr exists only in a NHANS_DEV build (make DEV=1)");
@@ -1175,7 +1180,7 @@ static int debug_block_output_body(nhans_ctx* c, const float* logmag, const int6
     StackBufs sb;
     stack_take(c, total, nclips, nframes, &sb);
     rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc;
-    launch_frame_index(sb.foff_dev, nclips, total, sb.f_clip, sb.f_t, sb.f_T, s);
+    launch_frame_index(sb.foff_dev, nclips, total, c->lookahead, sb.f_clip, sb.f_t, sb.f_T, s);
     launch_cond(ea, eb, nclips, c->A("cond.w"), c->A("cond.base"), c->cond_cols, sb.cb_all, s);
     const float* res = run_stack_chunk(c, logmag, nullptr, sb, frame0, nframes, block + 1, s);
     size_t per;
@@ -1212,7 +1217,7 @@ static int debug_activation_body(nhans_ctx* c, const float* logmag, const int64_
     StackBufs sb;
     stack_take(c, total, nclips, wf, &sb);
     rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc;
-    launch_frame_index(sb.foff_dev, nclips, total, sb.f_clip, sb.f_t, sb.f_T, s);
+    launch_frame_index(sb.foff_dev, nclips, total, c->lookahead, sb.f_clip, sb.f_t, sb.f_T, s);
     launch_cond(ea, eb, nclips, c->A("cond.w"), c->A("cond.base"), c->cond_cols, sb.cb_all, s);
     const int upto = index == kActHead ? 9 : (index - SA(0, 0)) / 2 + 1;
     c->cap_idx = index; c->cap_out = out;
@@ -1471,11 +1476,13 @@ struct OnStream {
     int64_t N = 0, T = 0;
     bool ended = false;
 };
-// frames whose window is complete / frames whose samples are final, for a stream of T frames
-int64_t on_ready(int64_t T, bool ended) { return ended ? T : std::max<int64_t>(0, T - kCenter); }
-int64_t on_paired(int64_t T, bool ended) { return ended ? T : on_ready(T, false) & ~(int64_t)1; }
-int64_t on_emitted(int64_t T, bool ended) {
-    if (!ended) return (int64_t)kHop * on_paired(T, false);
+// frames that are computed (their L look-ahead rows exist) / frames whose samples are final, for a stream of T frames with
+// look-ahead L.  on_lo keeps its form: the window still reaches 17 rows BACK from the next ready frame R = T - L, so
+// T - lo = L + (R - lo) <= L + max(17, R - S0) <= 41 rows and R - S0 <= 24 for every L <= 17.
+int64_t on_ready(int64_t T, bool ended, int L) { return ended ? T : std::max<int64_t>(0, T - L); }
+int64_t on_paired(int64_t T, bool ended, int L) { return ended ? T : on_ready(T, false, L) & ~(int64_t)1; }
+int64_t on_emitted(int64_t T, bool ended, int L) {
+    if (!ended) return (int64_t)kHop * on_paired(T, false, L);
     return T == 0 ? 0 : (T - 1) * kHop + kWin;
 }
 }  // namespace
@@ -1489,6 +1496,7 @@ struct nhans_online {
     int cur = 0;
     std::vector<OnStream> st, prev;
     std::vector<char> cond;     // slot has conditioning (nhans_online_open: all; nhans_online_open_slots: none yet)
+    std::vector<int> la;        // slot's look-ahead L (nhans_online_set_lookahead; survives a restart, as conditioning does)
     bool can_rewind = false;
     float* slot(int k, int i) const { return state + ((size_t)k * S + i) * kOnSlot; }
 };
@@ -1501,6 +1509,7 @@ int online_alloc(nhans_ctx* c, int S, int want_mixed, bool conditioned, const ch
     o->c = c; o->device = c->device; o->S = S; o->mixed = want_mixed != 0;
     o->st.assign(S, OnStream()); o->prev = o->st;
     o->cond.assign(S, conditioned ? 1 : 0);
+    o->la.assign(S, kCenter);
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->emb), (size_t)2 * S * kEmb * 4);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&o->state), (size_t)2 * S * kOnSlot * 4);
     if (e != hipSuccess) {
@@ -1567,7 +1576,7 @@ int online_set_rows(nhans_online* o, int slot, const float* row_a, const float* 
     HIP_TRY(hipMemcpyAsync(o->emb + (size_t)(o->S + slot) * kEmb, row_b, kEmb * 4, hipMemcpyDeviceToDevice, s));
     o->cond[slot] = 1;
     o->can_rewind = false;
-    if (first_frame) *first_frame = on_ready(o->st[slot].T, o->st[slot].ended);
+    if (first_frame) *first_frame = on_ready(o->st[slot].T, o->st[slot].ended, o->la[slot]);
     return NHANS_OK;
 }
 
@@ -1638,13 +1647,14 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
         if (p.Tn > kMaxFramesPerClip)
             return fail(NHANS_EINVAL, "nhans_online_push: stream " + std::to_string(i) + " would exceed " +
                                       std::to_string(kMaxFramesPerClip) + " frames");
-        p.Ro = on_ready(q.T, q.ended); p.Po = on_paired(q.T, q.ended);
-        p.Rn = on_ready(p.Tn, p.en || q.ended); p.Pn = on_paired(p.Tn, p.en || q.ended);
+        const int L = o->la[i];
+        p.Ro = on_ready(q.T, q.ended, L); p.Po = on_paired(q.T, q.ended, L);
+        p.Rn = on_ready(p.Tn, p.en || q.ended, L); p.Pn = on_paired(p.Tn, p.en || q.ended, L);
         p.lo = on_lo(p.Ro, p.Po);
         p.s0 = on_s0(p.Po);
         p.Pend = p.Pn;
-        p.Eo = on_emitted(q.T, q.ended);
-        p.En = on_emitted(p.Tn, p.en || q.ended);
+        p.Eo = on_emitted(q.T, q.ended, L);
+        p.En = on_emitted(p.Tn, p.en || q.ended, L);
         p.nsyn = p.En > p.Eo ? p.Pend - p.s0 : 0;
         if (outoff[i + 1] - outoff[i] < p.En - p.Eo)
             return fail(NHANS_EINVAL, "nhans_online_push: output room of stream " + std::to_string(i) + " is " +
@@ -1743,7 +1753,9 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
             add_rows(i, false, p.Ro, p.Rn, ctr + foff[i] * kBins);
             for (int64_t t = p.Ro; t < p.Rn; ++t) {
                 const int64_t f = foff[i] + t - p.Ro;
-                h_clip[f] = i; h_t[f] = (int)t; h_T[f] = (int)p.Tn;
+                // (the stream as frame t sees it ends L frames after t, however many rows this push already has: the
+                // rows from there on are zero rows to the window readers, WinRows, and may lie past the end of `win`)
+                h_clip[f] = i; h_t[f] = (int)t; h_T[f] = (int)std::min<int64_t>(p.Tn, t + o->la[i] + 1);
                 h_rb[f] = (int)(woff[i] + t - kCenter - p.lo);
             }
         }
@@ -1890,8 +1902,21 @@ int nhans_online_out_counts(const nhans_online* o, const int64_t* in_counts, con
     for (int i = 0; i < o->S; ++i) {
         const OnStream& q = o->st[i];
         const bool en = q.ended || (end && end[i]);
-        counts[i] = on_emitted(nhans_num_frames(q.N + in_counts[i]), en) - on_emitted(q.T, q.ended);
+        counts[i] = on_emitted(nhans_num_frames(q.N + in_counts[i]), en, o->la[i]) - on_emitted(q.T, q.ended, o->la[i]);
     }
+    return NHANS_OK;
+}
+
+int nhans_online_set_lookahead(nhans_online* o, int slot, int lookahead) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_online_set_lookahead: null object");
+    const int rc = online_slot_check(o, slot, "nhans_online_set_lookahead"); if (rc) return rc;
+    if (lookahead < 0 || lookahead > kCenter)
+        return fail(NHANS_EINVAL, "nhans_online_set_lookahead: lookahead must be in [0, " + std::to_string(kCenter) + "] frames");
+    if (o->st[slot].N != 0 || o->st[slot].ended)
+        return fail(NHANS_EINVAL, "nhans_online_set_lookahead: slot " + std::to_string(slot) + " has a stream under way " +
+                                  "(the look-ahead is set on an open stream of 0 samples: after open or nhans_online_restart)");
+    o->la[slot] = lookahead;
+    o->can_rewind = false;
     return NHANS_OK;
 }
 
@@ -2288,7 +2313,7 @@ LivePlan live_plan(const nhans_live* o, int i, int64_t cnt, bool en) {
     LivePlan p{};
     p.cnt = cnt; p.en = en;
     p.n16 = resample_emitted(*r->f, r->N[i] + cnt, r->ended[i] || en) - resample_emitted(*r->f, r->N[i], r->ended[i]);
-    p.d16 = on_emitted(nhans_num_frames(q.N + p.n16), q.ended || en) - on_emitted(q.T, q.ended);
+    p.d16 = on_emitted(nhans_num_frames(q.N + p.n16), q.ended || en, o->on->la[i]) - on_emitted(q.T, q.ended, o->on->la[i]);
     p.Eo = resample_emitted(*o->fo, o->out.N[i], o->out.ended[i]);
     p.En = resample_emitted(*o->fo, o->out.N[i] + p.d16, o->out.ended[i] || en);
     return p;
@@ -2427,12 +2452,35 @@ void live_free(nhans_live* o) {
 
 extern "C" {
 
-int64_t nhans_live_emitted(int64_t n, int ended, int rate_in, int rate_out) {
+namespace {
+int64_t live_emitted(const char* fn, int64_t n, int ended, int rate_in, int rate_out, int L) {
     const ResampleFilter *fi = nullptr, *fo = nullptr;
-    if (live_filters("nhans_live_emitted", rate_in, rate_out, &fi, &fo)) return NHANS_EINVAL;
-    if (n < 0) return fail(NHANS_EINVAL, "nhans_live_emitted: negative sample count");
+    if (live_filters(fn, rate_in, rate_out, &fi, &fo)) return NHANS_EINVAL;
+    if (n < 0) return fail(NHANS_EINVAL, std::string(fn) + ": negative sample count");
+    if (L < 0 || L > kCenter) return fail(NHANS_EINVAL, std::string(fn) + ": lookahead must be in [0, " + std::to_string(kCenter) + "] frames");
     const int64_t n16 = resample_emitted(*fi, n, ended != 0);
-    return resample_emitted(*fo, on_emitted(nhans_num_frames(n16), ended != 0), ended != 0);
+    return resample_emitted(*fo, on_emitted(nhans_num_frames(n16), ended != 0, L), ended != 0);
+}
+}  // namespace
+
+int64_t nhans_live_emitted(int64_t n, int ended, int rate_in, int rate_out) {
+    return live_emitted("nhans_live_emitted", n, ended, rate_in, rate_out, kCenter);
+}
+
+int64_t nhans_lookahead_live_emitted(int64_t n, int ended, int rate_in, int rate_out, int lookahead) {
+    return live_emitted("nhans_lookahead_live_emitted", n, ended, rate_in, rate_out, lookahead);
+}
+
+int nhans_lookahead_live_set(nhans_live* o, int slot, int lookahead) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_lookahead_live_set: null object");
+    int rc = live_slot_check(o, slot, "nhans_lookahead_live_set"); if (rc) return rc;
+    // (a stream of 0 samples in all three stages: the converter may hold samples the online stage has not seen yet)
+    if (o->in->N[slot] != 0 || o->in->ended[slot])
+        return fail(NHANS_EINVAL, "nhans_lookahead_live_set: slot " + std::to_string(slot) + " has a stream under way " +
+                                  "(the look-ahead is set on an open stream of 0 samples: after open or nhans_live_restart)");
+    rc = nhans_online_set_lookahead(o->on, slot, lookahead); if (rc) return rc;
+    o->can_rewind = false;
+    return NHANS_OK;
 }
 
 int nhans_live_open_slots(nhans_ctx* c, int nslots, int rate_in, int in_format, double peak, int rate_out, int out_format,

@@ -243,8 +243,9 @@ void launch_scale_copy(const float* src, size_t n, float scale, float* dst, hipS
 // split-NHWC tensor: the hi halfs dominate); *slot holds the bits of a non-negative float.  Calibration only.
 void launch_absmax(const float* x, size_t nwords, int split, float scale, unsigned* slot, hipStream_t s);
 
-// frame index: for global frame g -> clip, t within clip, T of clip
-void launch_frame_index(const int64_t* frame_offsets_dev, int nclips, int64_t total, int* f_clip,
+// frame index: for global frame g -> clip, t within clip, T of clip as frame g sees it: min(len, t + lookahead + 1) --
+// the window rows from there on read as 0.0 (WinRows).  lookahead = 17 (half the window): T = len for every frame.
+void launch_frame_index(const int64_t* frame_offsets_dev, int nclips, int64_t total, int lookahead, int* f_clip,
                         int* f_t, int* f_T, hipStream_t s);
 // mean over HW positions, times `scale`: x [B, HW, C] -> out [B, C]
 void launch_avgpool(const float* x, int B, int HW, int C, int split, float scale, float* out, hipStream_t s);

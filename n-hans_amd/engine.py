@@ -209,8 +209,20 @@ class Engine:
             hip.ptr(res.get("emb")), self._stream()))
         return res
 
-    def enhance(self, mixes, ctx_a, ctx_b, want_mixed=True, taps=False):
-        """Lists of normalised float32 waveforms (mixtures trimmed) -> per-clip numpy results."""
+    def enhance(self, mixes, ctx_a, ctx_b, want_mixed=True, taps=False, lookahead=spec.LOOKAHEAD):
+        """Lists of normalised float32 waveforms (mixtures trimmed) -> per-clip numpy results.  lookahead: L frames,
+        0 .. 17 (include/nhans_hip.h, option "lookahead": frame g sees its clip end at g + L + 1) -- what a live stream
+        of that look-ahead emits for the same samples; the saturation redo runs with the same L."""
+        if lookahead == spec.LOOKAHEAD:
+            return self._enhance(mixes, ctx_a, ctx_b, want_mixed, taps)
+        spec.check_lookahead(lookahead)
+        self.set_option("lookahead", lookahead)
+        try:
+            return self._enhance(mixes, ctx_a, ctx_b, want_mixed, taps)
+        finally:
+            self.set_option("lookahead", spec.LOOKAHEAD)
+
+    def _enhance(self, mixes, ctx_a, ctx_b, want_mixed, taps):
         mix_t, mix_off = self._dev(mixes)
         ca_t, ca_off = self._dev(ctx_a)
         cb_t, cb_off = self._dev(ctx_b)

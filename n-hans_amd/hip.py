@@ -29,7 +29,7 @@ EXPORTS = [
     "nhans_debug_activation", "nhans_debug_tower_activation",
     "nhans_live_emitted", "nhans_live_open_slots", "nhans_live_restart", "nhans_live_set_context",
     "nhans_live_set_embeddings", "nhans_live_set_wet", "nhans_live_out_counts", "nhans_live_push", "nhans_live_rewind",
-    "nhans_live_close",
+    "nhans_live_close", "nhans_online_set_lookahead", "nhans_lookahead_live_emitted", "nhans_lookahead_live_set",
 ]
 PCM_INT16, PCM_FLOAT32 = 0, 1
 RESAMPLE_QUANTISE = 1
@@ -160,6 +160,15 @@ def load():
         for name in ("nhans_live_open_slots", "nhans_live_restart", "nhans_live_set_context", "nhans_live_set_embeddings",
                      "nhans_live_set_wet", "nhans_live_out_counts", "nhans_live_push", "nhans_live_rewind"):
             getattr(lib, name).restype = ctypes.c_int
+    # (the selectable look-ahead came after the live sessions: looked up by symbol; the option "lookahead" of such an
+    # older library is unknown to it and nhans_set_option says so)
+    if hasattr(lib, "nhans_online_set_lookahead"):
+        lib.nhans_online_set_lookahead.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+        lib.nhans_online_set_lookahead.restype = ctypes.c_int
+        lib.nhans_lookahead_live_set.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+        lib.nhans_lookahead_live_set.restype = ctypes.c_int
+        lib.nhans_lookahead_live_emitted.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        lib.nhans_lookahead_live_emitted.restype = ctypes.c_int64
     lib.nhans_crc32c.argtypes = [ctypes.c_uint32, vp, ctypes.c_size_t]
     lib.nhans_crc32c.restype = ctypes.c_uint32
     for name in ("nhans_create", "nhans_create_ex", "nhans_set_option", "nhans_stft_features", "nhans_embed", "nhans_mask_net",

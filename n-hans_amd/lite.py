@@ -86,9 +86,20 @@ class LiteEngine:
                 b.free()
         return den, rt, moff, status
 
-    def enhance(self, mixes, ctx_a, ctx_b, want_mixed=True):
+    def enhance(self, mixes, ctx_a, ctx_b, want_mixed=True, lookahead=spec.LOOKAHEAD):
         """Lists of normalised float32 waveforms (mixtures trimmed) -> {"denoised_wav": [...], "mixed_wav": [...]}; the same
-        saturation fallback as engine.Engine.enhance (the batch redone on the exact-f32 matrix path, exponents raised)."""
+        saturation fallback as engine.Engine.enhance (the batch redone on the exact-f32 matrix path, exponents raised) and
+        the same lookahead (L frames, 0 .. 17; the redo runs with the same L)."""
+        if lookahead == spec.LOOKAHEAD:
+            return self._enhance(mixes, ctx_a, ctx_b, want_mixed)
+        spec.check_lookahead(lookahead)
+        self.set_option("lookahead", lookahead)
+        try:
+            return self._enhance(mixes, ctx_a, ctx_b, want_mixed)
+        finally:
+            self.set_option("lookahead", spec.LOOKAHEAD)
+
+    def _enhance(self, mixes, ctx_a, ctx_b, want_mixed):
         den, rt, off, status = self._run(mixes, ctx_a, ctx_b, want_mixed)
         if status & hip.STATUS_SATURATED and self.precision == "f16x3":
             warnings.warn("N-HANS f16x3 path: an activation left the f16 range; batch recomputed in f32 MFMA mode "

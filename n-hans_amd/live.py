@@ -14,15 +14,15 @@ import numpy as np
 from . import hip, online, resample, spec
 
 
-def emitted(n, ended, in_rate, out_rate):
+def emitted(n, ended, in_rate, out_rate, lookahead=online.LOOKAHEAD):
     """Samples at out_rate a stream of n pushed samples at in_rate has emitted in total: the three stages' contracts
-    chained (resample.emitted, online.emitted, resample.emitted)."""
+    chained (resample.emitted, online.emitted at the slot's look-ahead, resample.emitted)."""
     for r in (in_rate, out_rate):
         if r not in resample.RATES:
             raise ValueError("%d Hz in / %d Hz out is not supported (each one of %s)"
                              % (in_rate, out_rate, ", ".join(str(v) for v in resample.RATES)))
     n16 = resample.emitted(n, ended, in_rate, spec.FS)
-    return resample.emitted(online.emitted(n16, ended), ended, spec.FS, out_rate)
+    return resample.emitted(online.emitted(n16, ended, lookahead), ended, spec.FS, out_rate)
 
 
 def default_out_scale(peak, out_dtype):
@@ -38,10 +38,13 @@ class LiveSession:
     denoised + (mixed - denoised) * w, the reference's --compensate mix.
 
     Slots are the online object's (online.OnlineEnhancer): all start unconditioned; restart(i) + set_context(i, a, b)
-    lets a recording join in slot i, end in a push or restart(i) lets it leave."""
+    lets a recording join in slot i, end in a push or restart(i) lets it leave.
+
+    lookahead: L frames, 0 .. 17, one for all slots or one per slot (set_lookahead(i, L) later, on a slot whose stream
+    has no samples yet): the 16 kHz stage then computes the offline output of that L, Engine.enhance(..., lookahead=L)."""
 
     def __init__(self, engine, nslots, in_rate, out_rate, peak, in_dtype=np.int16, out_dtype=np.int16, out_scale=None,
-                 wet=False):
+                 wet=False, lookahead=online.LOOKAHEAD):
         emitted(0, False, in_rate, out_rate)
         self.mem = resample._Mem(engine)
         self.eng = engine
@@ -62,6 +65,13 @@ class LiveSession:
         self.ended = [False] * self.S
         self.conditioned = [False] * self.S
         self._prev = None
+        self.lookahead = [online.LOOKAHEAD] * self.S
+        la = list(lookahead) if hasattr(lookahead, "__len__") else [lookahead] * self.S
+        if len(la) != self.S:
+            raise ValueError("lookahead: one value, or one per slot (%d)" % self.S)
+        for i, L in enumerate(la):
+            if L != online.LOOKAHEAD:
+                self.set_lookahead(i, L)
 
     # ---- slots ---------------------------------------------------------------------------------
     def restart(self, i):
@@ -109,6 +119,13 @@ class LiveSession:
             self.mem.free(*own)
         self.conditioned[i] = True
         return int(R.value)
+
+    def set_lookahead(self, i, L):
+        """The look-ahead of slot i, L frames in 0 .. 17 (nhans_lookahead_live_set): allowed while the slot's stream has
+        no samples yet -- after open or restart(i) --, kept across restarts."""
+        L = spec.check_lookahead(L)
+        hip.check(self.lib.nhans_lookahead_live_set(self.handle, int(i), L))
+        self.lookahead[i] = L
 
     def set_wet(self, w):
         """The wet factor of the pushes that follow (non-zero needs wet=True at construction)."""

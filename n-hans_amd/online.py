@@ -18,23 +18,33 @@ def num_frames(n):
     return 0 if n < spec.WIN else 1 + (n - spec.WIN) // spec.HOP
 
 
-def emitted(n, ended):
-    """Samples a stream of n pushed samples has emitted in total (include/nhans_hip.h: the output contract)."""
+def ready_frames(n, ended, lookahead=LOOKAHEAD):
+    """R of the header's contract: the frames of a stream of n pushed samples that are computed -- those whose
+    `lookahead` future rows exist, all of them once the stream has ended."""
+    T = num_frames(n)
+    return T if ended else max(0, T - lookahead)
+
+
+def emitted(n, ended, lookahead=LOOKAHEAD):
+    """Samples a stream of n pushed samples has emitted in total (include/nhans_hip.h: the output contract): 160 * P with
+    P = R rounded down to even, R = ready_frames; the offline length once ended."""
     T = num_frames(n)
     if ended:
         return 0 if T == 0 else (T - 1) * spec.HOP + spec.WIN
-    R = max(0, T - LOOKAHEAD)
+    R = max(0, T - lookahead)
     return spec.HOP * (R - R % 2)
 
 
-def out_counts(n_before, n_push, end=None, ended_before=None):
+def out_counts(n_before, n_push, end=None, ended_before=None, lookahead=LOOKAHEAD):
     """Per-stream sample counts a push of n_push[i] samples (end[i]: the stream ends after them) reports, for streams
-    that had n_before[i] samples (ended_before[i]: and had ended) -- what nhans_online_out_counts computes."""
+    that had n_before[i] samples (ended_before[i]: and had ended) -- what nhans_online_out_counts computes.  lookahead:
+    one L for all streams, or one per stream."""
     S = len(n_before)
     end = end if end is not None else [False] * S
     ended_before = ended_before if ended_before is not None else [False] * S
-    return [emitted(n_before[i] + n_push[i], bool(end[i] or ended_before[i])) - emitted(n_before[i], bool(ended_before[i]))
-            for i in range(S)]
+    la = list(lookahead) if hasattr(lookahead, "__len__") else [lookahead] * S
+    return [emitted(n_before[i] + n_push[i], bool(end[i] or ended_before[i]), la[i])
+            - emitted(n_before[i], bool(ended_before[i]), la[i]) for i in range(S)]
 
 
 def change_bounds(R):
@@ -42,15 +52,18 @@ def change_bounds(R):
     nhans_hip.h, the mid-stream contract): output samples below the first are bit for bit the offline output under the
     old conditioning, samples from the second on that under the new one.  The iSTFT transforms frames in pairs
     (2k, 2k+1), so the old side stops at the pair that holds frame R and the new side starts after it, one window
-    overlap (400 - 160) later.  R = 0 and R = the final frame count are whole-output cases the caller knows about."""
+    overlap (400 - 160) later.  R = 0 and R = the final frame count are whole-output cases the caller knows about.
+    R is ready_frames(n, ended, L) of the slot at the time of the change -- T - L for a running stream of look-ahead L --,
+    and "the offline output" is that of the same L (Engine.enhance(..., lookahead=L))."""
     return spec.HOP * (R - R % 2), spec.HOP * (R + R % 2) + spec.WIN - spec.HOP
 
 
-def latency_ms(fs=spec.FS, in_rate=None, out_rate=None):
-    """Algorithmic latency (ms) from a sample's arrival to its output: the 17-frame look-ahead plus one window, less or
-    more one hop for where the sample falls in its hop and for the even-pair rule of the iSTFT -> (185, 205) at 16 kHz.
+def latency_ms(fs=spec.FS, in_rate=None, out_rate=None, lookahead=LOOKAHEAD):
+    """Algorithmic latency (ms) from a sample's arrival to its output: the look-ahead of `lookahead` frames plus one
+    window, less or more one hop for where the sample falls in its hop and for the even-pair rule of the iSTFT:
+    10 L + 25 +- 10 ms at 16 kHz -> (185, 205) at the default 17, (35, 55) at 2, (15, 35) at 0.
     in_rate / out_rate: plus the filter delay of each rate conversion (resample.latency_ms: 0.625 ms beside 16 kHz)."""
-    mid = (LOOKAHEAD * spec.HOP + spec.WIN) * 1000.0 / fs
+    mid = (lookahead * spec.HOP + spec.WIN) * 1000.0 / fs
     if in_rate is not None or out_rate is not None:
         from . import resample
         mid += resample.latency_ms(in_rate, fs) if in_rate is not None else 0.0
@@ -76,7 +89,10 @@ class OnlineEnhancer:
     converted sample is divided by (peak + 1e-6) on the device, normalise_fixed -- and returns pieces at out_rate, each
     through a resample.Resampler of its own (a second outgoing one for the mixed round trip).  The output is bit for bit
     resample -> normalise_fixed -> offline enhance -> resample of the whole recording.  With both None the object is
-    the 16 kHz one and none of this exists."""
+    the 16 kHz one and none of this exists.
+
+    lookahead: L frames, 0 .. 17, one for all slots or one per slot (set_lookahead(i, L) later, on a slot whose stream
+    has no samples yet).  The output is then bit for bit the offline one of that L: Engine.enhance(..., lookahead=L)."""
 
     def _begin(self, engine, S, want_mixed):
         self.eng = engine
@@ -89,6 +105,15 @@ class OnlineEnhancer:
         self.ended = [False] * S
         self._prev = None
         self._rs_in = self._rs_out = self._rs_mix = None
+        self.lookahead = [LOOKAHEAD] * S
+
+    def _lookaheads(self, lookahead):
+        la = list(lookahead) if hasattr(lookahead, "__len__") else [lookahead] * self.S
+        if len(la) != self.S:
+            raise ValueError("lookahead: one value, or one per slot (%d)" % self.S)
+        for i, L in enumerate(la):
+            if L != LOOKAHEAD:
+                self.set_lookahead(i, L)
 
     def _rates(self, in_rate, out_rate, peak, in_dtype):
         if in_rate is None and out_rate is None:
@@ -105,7 +130,8 @@ class OnlineEnhancer:
             if self.want_mixed:
                 self._rs_mix = resample.Resampler(self.eng, self.S, spec.FS, out_rate)
 
-    def __init__(self, engine, ctx_a, ctx_b, want_mixed=False, in_rate=None, out_rate=None, peak=None, in_dtype=np.int16):
+    def __init__(self, engine, ctx_a, ctx_b, want_mixed=False, in_rate=None, out_rate=None, peak=None, in_dtype=np.int16,
+                 lookahead=LOOKAHEAD):
         if len(ctx_a) != len(ctx_b):
             raise ValueError("ctx_a and ctx_b must have one recording per stream")
         self._begin(engine, len(ctx_a), want_mixed)
@@ -119,9 +145,11 @@ class OnlineEnhancer:
         self.handle = h
         self._free(da, db)
         self._rates(in_rate, out_rate, peak, in_dtype)
+        self._lookaheads(lookahead)
 
     @classmethod
-    def open_slots(cls, engine, nslots, want_mixed=False, in_rate=None, out_rate=None, peak=None, in_dtype=np.int16):
+    def open_slots(cls, engine, nslots, want_mixed=False, in_rate=None, out_rate=None, peak=None, in_dtype=np.int16,
+                   lookahead=LOOKAHEAD):
         """An object of nslots unconditioned slots (nhans_online_open_slots): no tower runs until a set_context."""
         self = cls.__new__(cls)
         self._begin(engine, int(nslots), want_mixed)
@@ -130,6 +158,7 @@ class OnlineEnhancer:
         hip.check(self.lib.nhans_online_open_slots(engine.handle, self.S, int(self.want_mixed), self._stream(), ctypes.byref(h)))
         self.handle = h
         self._rates(in_rate, out_rate, peak, in_dtype)
+        self._lookaheads(lookahead)
         return self
 
     # ---- device memory of either engine --------------------------------------------------------
@@ -198,10 +227,16 @@ class OnlineEnhancer:
             if rs is not None:
                 rs.restart(i)
 
+    def set_lookahead(self, i, L):
+        """The look-ahead of slot i, L frames in 0 .. 17 (nhans_online_set_lookahead): allowed while the slot's stream has
+        no samples yet -- after open or restart(i) --, kept across restarts."""
+        L = spec.check_lookahead(L)
+        hip.check(self.lib.nhans_online_set_lookahead(self.handle, int(i), L))
+        self.lookahead[i] = L
+
     def first_new_frame(self, i):
         """R of slot i: the frames of its stream already computed, which a change of conditioning leaves as they are."""
-        T = num_frames(self.pushed[i])
-        return T if self.ended[i] else max(0, T - LOOKAHEAD)
+        return ready_frames(self.pushed[i], self.ended[i], self.lookahead[i])
 
     def set_context(self, i, ctx_a, ctx_b):
         """Conditions slot i on two recordings (nhans_online_set_context).  Returns R: frames >= R of the slot's stream

@@ -21,6 +21,14 @@ EMB = 512
 BN_EPS = 1e-3
 LOG_EPS = 1e-5
 MIN_CTX_SAMPLES = WIN + HOP * (NOISE_WIN - 1)   # 32240: shortest context giving 200 frames
+LOOKAHEAD = CENTER  # default look-ahead L in frames: the whole future half of the window (include/nhans_hip.h: "lookahead")
+
+
+def check_lookahead(L):
+    """L as an int if it is a whole number of frames in 0 .. 17, else ValueError."""
+    if int(L) != L or not 0 <= L <= LOOKAHEAD:
+        raise ValueError("lookahead must be a whole number of frames in 0 .. %d (got %r)" % (LOOKAHEAD, L))
+    return int(L)
 
 DENOISER = "denoiser"
 SEPARATOR = "separator"

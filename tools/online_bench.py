@@ -5,6 +5,9 @@ H hops (H x 10 ms of audio per stream), f16x3, synthetic weights.  One JSON line
   realtime_factor     S x pushed audio seconds / p50 push time (streams one GPU keeps up with per ... of real time)
   latency_ms          the algorithmic latency range from the output contract (look-ahead + one window, +- one hop)
     python tools/online_bench.py [--streams 1,8,64,256] [--hops 1,4,16] [--pushes 60] [--in_rate 48000] [--out_rate 48000]
+                                 [--lookahead L]
+  (--lookahead L, 0 ... 17: every stream at look-ahead L -- the line carries "lookahead" and the latency_ms of that L; the
+   default 17 makes no look-ahead call at all, so it also runs on a library from before the option: $NHANS_LIB)
   (--in_rate / --out_rate: the pieces are int16 at in_rate and come back at out_rate, each through a device rate
    converter of its own -- nhans_amd/resample.py; the line then carries "in_rate" / "out_rate" and the longer latency)
   (--live, with both rates: the same pushes through a live.LiveSession -- nhans_live_push, one C call per push, the
@@ -151,16 +154,19 @@ def main():
     ap.add_argument("--in_rate", type=int, default=None, help="pieces arrive as int16 at this rate (default: 16 kHz float32)")
     ap.add_argument("--out_rate", type=int, default=None, help="pieces are returned at this rate (default: 16 kHz)")
     ap.add_argument("--live", action="store_true", help="drive a live.LiveSession (needs --in_rate and --out_rate)")
+    ap.add_argument("--lookahead", type=int, default=spec.LOOKAHEAD, help="look-ahead L of every stream, 0 ... 17 frames")
     a = ap.parse_args()
     if a.churn:
         return churn(a)
     if a.live and not (a.in_rate and a.out_rate):
         ap.error("--live needs --in_rate and --out_rate")
+    if not 0 <= a.lookahead <= spec.LOOKAHEAD:
+        ap.error("--lookahead is 0 ... %d frames" % spec.LOOKAHEAD)
     out = open(a.out, "a") if a.out else None
     eng = engine.Engine("denoiser", precision="f16x3")
     ca, cb = apply.normalise(synth.silent()), apply.normalise(synth.noise_context(1))
     audio = apply.normalise(synth.mixture(1, 30.0))
-    lat = online.latency_ms(in_rate=a.in_rate, out_rate=a.out_rate)
+    lat = online.latency_ms(in_rate=a.in_rate, out_rate=a.out_rate, lookahead=a.lookahead)
     rates = {}
     if a.in_rate or a.out_rate:
         rates = {"in_rate": a.in_rate, "out_rate": a.out_rate}
@@ -173,7 +179,7 @@ def main():
         for H in [int(h) for h in a.hops.split(",")]:
             n = H * spec.HOP if not a.in_rate else int(round(H * 0.010 * a.in_rate))
             if a.live:
-                enh = live.LiveSession(eng, S, a.in_rate, a.out_rate, rates["peak"])
+                enh = live.LiveSession(eng, S, a.in_rate, a.out_rate, rates["peak"], lookahead=a.lookahead)
                 # (one tower run; every slot gets its rows)
                 emb = eng.embed(eng.stft_features(torch.from_numpy(np.concatenate([ca, cb])).to(eng.device),
                                                   [0, len(ca), len(ca) + len(cb)], max_frames=spec.NOISE_WIN,
@@ -181,7 +187,7 @@ def main():
                 for i in range(S):
                     enh.set_embeddings(i, emb[0], emb[1])
             else:
-                enh = online.OnlineEnhancer(eng, [ca] * S, [cb] * S, **rates)
+                enh = online.OnlineEnhancer(eng, [ca] * S, [cb] * S, lookahead=a.lookahead, **rates)
             pos = [0]
 
             def push():
@@ -189,7 +195,7 @@ def main():
                 pos[0] += n
                 enh.push([audio[i:i + n]] * S)
 
-            for _ in range(40):              # past the 17-frame look-ahead: every push then runs the whole path
+            for _ in range(40):              # past the look-ahead (17 frames at most): every push then runs the whole path
                 push()
             torch.cuda.synchronize()
             ts = []
@@ -212,7 +218,9 @@ def main():
                                "push_ms_p99": round(p99, 3), "kernel_ms_per_push": round(kern, 3),
                                "launches_per_push": sum(v["calls"] for v in prof.values()) / 10,
                                "realtime_factor": round(S * H * 0.010 / (p50 / 1e3), 2),
-                               "latency_ms": [lat[0], lat[1]], "precision": "f16x3", "weights": "synthetic seed 7",
+                               "lookahead": a.lookahead, "latency_ms": [lat[0], lat[1]],
+                               "lib": os.path.basename(os.path.dirname(os.environ["NHANS_LIB"])) if os.environ.get("NHANS_LIB") else "tree",
+                               "precision": "f16x3", "weights": "synthetic seed 7",
                                **{k: v for k, v in rates.items() if k != "peak"}})
             print(line, flush=True)
             if out:
