@@ -538,6 +538,65 @@ int nhans_live_rewind(nhans_live* obj);
 
 void nhans_live_close(nhans_live* obj);
 
+/* ---- Conditioning captured from a slot's own stream -------------------------------------------------------------------
+ * The set functions above take two 16 kHz, already normalised recordings that the caller owns.  A live caller has neither:
+ * its audio is device-rate PCM, the 16 kHz version exists only inside the object, and the noise it wants removed is what
+ * the microphone hears now -- the reference's own use is to record a piece of the environment and pass it as --neg
+ * (its README.md).  The functions below condition slot i, side a or b, on the last NHANS_CAPTURE_SAMPLES samples slot i
+ * itself has received, without a sample leaving the device.  Added without moving NHANS_ABI_VERSION; a caller that may meet
+ * an older library looks them up by symbol.  (The names of the live pass-throughs begin with nhans_capture_, not with the
+ * live prefix, whose set of names is closed.)
+ *
+ * Sample history.  nhans_capture_enable gives every slot a ring of NHANS_CAPTURE_SAMPLES floats (129 KB per slot, allocated
+ * once; any time; idempotent; NHANS_ENOMEM and nothing changed if the allocation fails).  From then on every push also
+ * copies each slot's new 16 kHz samples into its ring, sample k of the stream at position k mod NHANS_CAPTURE_SAMPLES
+ * -- extra copy runs of the push's first launch (nhans_capture_plan), no launch more, and only the last
+ * NHANS_CAPTURE_SAMPLES samples of a larger push.  Without the enable call a push is what it was, launch for launch.
+ * The ring is not double-buffered as the carried state is.  The library keeps, per slot, vlo: the oldest sample of the
+ * slot's current stream that the ring still holds -- N at enable time, 0 after nhans_online_restart, and after every push
+ * max(vlo, N - NHANS_CAPTURE_SAMPLES), also when the push is then undone by nhans_online_rewind (its samples stay in the
+ * ring, over older ones).  A capture needs N - NHANS_CAPTURE_SAMPLES >= vlo, else NHANS_ESHORT: too few samples yet, history
+ * enabled too recently, or a rewound push not yet repeated (the message says which).  Repeating the rewound push with the
+ * same input -- the redo of a saturated push -- makes the history valid again.
+ *
+ * Capture.  For entry k let x be the 16 kHz samples slot slots_host[k]'s stream has received and N their number.  The
+ * context clip is x[N - NHANS_CAPTURE_SAMPLES : N] as stored; with NHANS_CAPTURE_NORMALISE it goes through the arithmetic of
+ * nhans_peak_normalise with flags 0: float32(double(x) / (double(max|x|) + 1e-6)).  Row which_host[k] of the slot's embedding
+ * pair becomes nhans_embed(nhans_stft_features(clip, max 200 frames)), BIT FOR BIT the row nhans_online_set_context would
+ * store for that clip -- whatever the cutting of the stream into pushes, n, and the other entries of the call; the slot's
+ * other row is untouched.  One gather kernel, ONE STFT and ONE tower pass over the n clips, then n row copies.
+ * Semantics of the set functions: first_frame_out[k] (array nullable) receives R of entry k's slot, frames >= R use the
+ * new row, the last push becomes final (nhans_online_rewind).  Ended streams may be captured (R = T; the rows serve the
+ * slot's next stream, as conditioning survives a restart).  Capture does not make an unconditioned slot conditioned (such a
+ * slot cannot have samples).  For a live object x is what the incoming converter handed on -- already divided by
+ * peak + 1e-6 -- and N = nhans_resample_emitted(pushed, ended, rate_in, 16000); the converters keep running.
+ * Errors (nothing changes, the function's name in nhans_last_error()): NHANS_EINVAL for history not enabled, n < 1, a slot
+ * out of range, which not 0 or 1, a (slot, which) pair named twice, unknown flag bits, a NULL that is needed; NHANS_ESHORT as
+ * above.  What the captured conditioning is worth is a property of the trained model; nothing in this library measures it. */
+#define NHANS_CAPTURE_SAMPLES 32240   /* 199 * 160 + 400: the 200 context frames */
+#define NHANS_CAPTURE_A 0
+#define NHANS_CAPTURE_B 1
+#define NHANS_CAPTURE_NORMALISE 1
+
+/* Host only, no object.  The copy runs that append `count` samples to a ring that has seen n_before: runs_out[r] = {offset
+ * in the push, ring position, length}, r < the returned number of runs (0 .. 2; 0 for count == 0).  The push uses this very
+ * function.  Negative counts, or runs_out == NULL with count > 0: NHANS_EINVAL. */
+int nhans_capture_plan(int64_t n_before, int64_t count, int64_t* runs_out /* [2][3] */);
+
+int nhans_capture_enable(nhans_online* obj, void* stream);
+int nhans_capture_context(nhans_online* obj, int n, const int* slots_host, const int* which_host, int flags, void* stream,
+                          int64_t* first_frame_out /* [n], nullable */);
+/* Copies the slot's current rows out ([512] floats each, either nullable): a learnt noise profile can be kept and handed
+ * to nhans_online_set_embeddings elsewhere. */
+int nhans_capture_embeddings(const nhans_online* obj, int slot, float* emb_a_out_dev, float* emb_b_out_dev, void* stream);
+
+/* The same for the online stage of a live object.  The capture call makes the last live push final, as the live set
+ * functions do; nhans_live_rewind and nhans_live_restart follow the vlo rules above. */
+int nhans_capture_live_enable(nhans_live* obj, void* stream);
+int nhans_capture_live_context(nhans_live* obj, int n, const int* slots_host, const int* which_host, int flags, void* stream,
+                               int64_t* first_frame_out /* [n], nullable */);
+int nhans_capture_live_embeddings(const nhans_live* obj, int slot, float* emb_a_out_dev, float* emb_b_out_dev, void* stream);
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

@@ -1498,6 +1498,12 @@ struct nhans_online {
     std::vector<char> cond;     // slot has conditioning (nhans_online_open: all; nhans_online_open_slots: none yet)
     std::vector<int> la;        // slot's look-ahead L (nhans_online_set_lookahead; survives a restart, as conditioning does)
     bool can_rewind = false;
+    // nhans_capture_enable: per slot the last kCaptureSamples samples pushed, sample k at position k mod kCaptureSamples
+    // (nullptr until enabled), and vlo: the oldest sample of the slot's current timeline the ring still holds.  The ring is
+    // not double-buffered as `state` is, so vlo only moves forward with what a push writes -- a rewound push has written too
+    // -- and goes back only where a new timeline starts (restart: 0) or the ring does (enable: N).
+    float* ring = nullptr;      // [S][kCaptureSamples]
+    std::vector<int64_t> vlo, whi;  // whi: how far a push has written the slot's timeline (> N after a rewind; for messages)
     float* slot(int k, int i) const { return state + ((size_t)k * S + i) * kOnSlot; }
 };
 
@@ -1561,6 +1567,14 @@ int online_open_slots_body(nhans_ctx* c, int S, int want_mixed, hipStream_t s, n
     }
     *out = o;
     return NHANS_OK;
+}
+
+// Slot `slot` becomes an open stream of 0 samples (nhans_online_restart, nhans_live_restart): a new timeline, of which the
+// ring holds nothing yet.
+void online_restart_slot(nhans_online* o, int slot) {
+    o->st[slot] = OnStream();
+    if (o->ring) o->vlo[slot] = o->whi[slot] = 0;
+    o->can_rewind = false;
 }
 
 int online_slot_check(const nhans_online* o, int slot, const char* fn) {
@@ -1683,8 +1697,10 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
         return fail(NHANS_EINVAL, "nhans_online_push: push too large for one call (split it)");
     const int64_t wf = std::min<int64_t>(c->frames_per_chunk, std::max<int64_t>(F, 1));
     const size_t nb_st = stft_blocks(soff.data(), S, 0), nb_is = istft_blocks(yoff.data(), S);
-    // (every run of n floats is ceil(n / kOnlineCopyMax) pieces; a stream has at most 19 runs per push)
-    const size_t nrun_cap = (size_t)S * 32 + (size_t)(soff[S] + (WR + F + 4 * Y) * kBins + 2 * tot_out) / kOnlineCopyMax + 64;
+    // (every run of n floats is ceil(n / kOnlineCopyMax) pieces; a stream has at most 19 runs per push, and with the
+    // sample history two more into its ring, of kCaptureSamples floats together)
+    const size_t nrun_cap = (size_t)S * 32 + (size_t)(soff[S] + (WR + F + 4 * Y) * kBins + 2 * tot_out) / kOnlineCopyMax + 64 +
+                            (o->ring ? (size_t)S * (2 + kCaptureSamples / kOnlineCopyMax + 1) : 0);
     size_t bytes = ws_size(soff[S], 4) + 2 * ws_size(NF * kBins, 4) + ws_size(WR * kBins, 4) + 2 * ws_size(F * kBins, 4) +
                    3 * ws_size(Y * kBins, 4) + (o->mixed ? 2 : 1) * ws_size(ooff[S], 4) + 2 * ws_size(2 * (S + 1), 8) +
                    ws_size(2 * nb_st, 4) + ws_size(2 * nb_is, 4) + ws_size(F, 4) + ws_size(nrun_cap, sizeof(OnlineCopy));
@@ -1742,6 +1758,13 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
         const int64_t carry = o->st[i].N - (int64_t)kHop * o->st[i].T;
         add(o->slot(cur, i) + kOnSamp, wav + soff[i], carry);
         if (pl[i].cnt > 0) add(in + inoff[i], wav + soff[i] + carry, pl[i].cnt);
+        if (o->ring) {
+            // (the sample history: the same launch, the caller's piece -> the slot's ring)
+            int64_t cr[2][3];
+            const int nr = nhans_capture_plan(o->st[i].N, pl[i].cnt, &cr[0][0]);
+            for (int r = 0; r < nr; ++r)
+                add(in + inoff[i] + cr[r][0], o->ring + (size_t)i * kCaptureSamples + cr[r][1], cr[r][2]);
+        }
     }
     bounds.push_back((int)runs.size());
     // assemble
@@ -1804,6 +1827,12 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
         pr.done(0, 8.0 * (double)fl);
     };
     copies(0, "online_ingest");
+    // (from here on the rings hold this push's samples, whether the push completes, fails or is rewound)
+    if (o->ring)
+        for (int i = 0; i < S; ++i) {
+            o->vlo[i] = std::max(o->vlo[i], pl[i].Nn - kCaptureSamples);
+            o->whi[i] = std::max(o->whi[i], pl[i].Nn);
+        }
     if (NF > 0) {
         std::vector<int64_t> fo;
         rc = stft_impl(c, wav, soff.data(), S, 0, nlm, nph, tab_st, blk_st, &fo, s, "online_stft"); if (rc) return rc;
@@ -1861,8 +1890,7 @@ int nhans_online_open_slots(nhans_ctx* c, int nslots, int want_mixed, void* stre
 int nhans_online_restart(nhans_online* o, int slot) {
     if (!o) return fail(NHANS_EINVAL, "nhans_online_restart: null object");
     const int rc = online_slot_check(o, slot, "nhans_online_restart"); if (rc) return rc;
-    o->st[slot] = OnStream();
-    o->can_rewind = false;
+    online_restart_slot(o, slot);
     return NHANS_OK;
 }
 
@@ -1923,6 +1951,7 @@ int nhans_online_set_lookahead(nhans_online* o, int slot, int lookahead) {
 int nhans_online_rewind(nhans_online* o) {
     if (!o) return fail(NHANS_EINVAL, "null object");
     if (!o->can_rewind) return fail(NHANS_EINVAL, "nhans_online_rewind: no push to undo (one rewind per push)");
+    // (the rings keep what the undone push wrote: vlo moved to max(vlo, N - 32,240) when its copies went out and stays)
     o->st = o->prev;
     o->cur = 1 - o->cur;
     o->can_rewind = false;
@@ -1935,7 +1964,148 @@ void nhans_online_close(nhans_online* o) {
     (void)hipDeviceSynchronize();
     (void)hipFree(o->emb);
     (void)hipFree(o->state);
+    if (o->ring) (void)hipFree(o->ring);
     delete o;
+}
+
+}  // extern "C"
+
+// ---- conditioning captured from a slot's own stream (include/nhans_hip.h: nhans_capture_*) --------------------------------
+namespace {
+static_assert(kCaptureSamples == NHANS_CAPTURE_SAMPLES, "the ring holds the 200 context frames");
+
+int capture_enable_body(nhans_online* o, const char* fn, hipStream_t s) {
+    if (o->ring) return NHANS_OK;
+    float* ring = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&ring), (size_t)o->S * kCaptureSamples * 4);
+    if (e != hipSuccess) return fail(NHANS_ENOMEM, std::string(fn) + ": hipMalloc failed: " + hipGetErrorString(e));
+    // (no capture reads a position before a push has written it -- vlo --: the zeros only keep the memory defined)
+    e = hipMemsetAsync(ring, 0, (size_t)o->S * kCaptureSamples * 4, s);
+    if (e != hipSuccess) {
+        (void)hipFree(ring);
+        return fail(NHANS_EHIP, std::string(fn) + ": hipMemsetAsync: " + hipGetErrorString(e));
+    }
+    o->ring = ring;
+    o->vlo.resize(o->S); o->whi.resize(o->S);
+    for (int i = 0; i < o->S; ++i) o->vlo[i] = o->whi[i] = o->st[i].N;
+    return NHANS_OK;
+}
+
+// n entries (slot, which): ring -> clip (capture_clip_kernel), ONE STFT over the n clips, ONE tower pass over the n
+// images, then the n rows into the object -- set_context's sequence with the clips taken from the device.
+int capture_context_body(nhans_online* o, const char* fn_, int n, const int* slots, const int* which, int flags,
+                         hipStream_t s, int64_t* first_frame) {
+    nhans_ctx* c = o->c;
+    const std::string fn(fn_);
+    if (!o->ring) return fail(NHANS_EINVAL, fn + ": the sample history is not enabled (nhans_capture_enable)");
+    if (n < 1) return fail(NHANS_EINVAL, fn + ": n must be >= 1");
+    if (!slots || !which) return fail(NHANS_EINVAL, fn + ": null argument");
+    if (flags & ~NHANS_CAPTURE_NORMALISE) return fail(NHANS_EINVAL, fn + ": unknown flag");
+    std::vector<char> seen((size_t)2 * o->S, 0);
+    for (int k = 0; k < n; ++k) {
+        const int rc = online_slot_check(o, slots[k], fn_); if (rc) return rc;
+        if (which[k] != NHANS_CAPTURE_A && which[k] != NHANS_CAPTURE_B)
+            return fail(NHANS_EINVAL, fn + ": entry " + std::to_string(k) + ": which must be NHANS_CAPTURE_A or NHANS_CAPTURE_B");
+        char& m = seen[(size_t)which[k] * o->S + slots[k]];
+        if (m) return fail(NHANS_EINVAL, fn + ": slot " + std::to_string(slots[k]) + ", side " + (which[k] ? "b" : "a") + " is named twice");
+        m = 1;
+    }
+    for (int k = 0; k < n; ++k) {
+        const int i = slots[k];
+        const int64_t N = o->st[i].N, lo = N - kCaptureSamples;
+        if (lo >= o->vlo[i]) continue;
+        const std::string head = fn + ": slot " + std::to_string(i) + ": ";
+        if (lo < 0)
+            return fail(NHANS_ESHORT, head + "its stream has " + std::to_string(N) + " samples so far, " +
+                                      std::to_string(kCaptureSamples) + " needed");
+        if (N < o->whi[i])
+            return fail(NHANS_ESHORT, head + "a push was rewound and has not been repeated yet: it wrote the sample history up to sample " +
+                                      std::to_string(o->whi[i]) + ", the stream stands at " + std::to_string(N));
+        return fail(NHANS_ESHORT, head + "the sample history was enabled at sample " + std::to_string(o->vlo[i]) + " of its stream: " +
+                                  std::to_string(N - o->vlo[i]) + " of the " + std::to_string(kCaptureSamples) + " samples needed");
+    }
+
+    std::vector<int64_t> soff(n + 1);
+    for (int k = 0; k <= n; ++k) soff[k] = (int64_t)k * kCaptureSamples;
+    const size_t nb = stft_blocks(soff.data(), n, kCtxFrames);
+    const size_t tb = tower_buf_floats(c);
+    int rc = ws_reserve(c, ws_size((size_t)n * kCaptureSamples, 4) + ws_size((size_t)n * kCtxFrames * kBins, 4) +
+                               ws_size((size_t)n * kEmb, 4) + ws_size(2 * (n + 1), 8) + ws_size(2 * nb, 4) +
+                               ws_size(n, sizeof(CaptureEntry)) + 3 * ws_size(tb, 4));
+    if (rc) return rc;
+    float* clips = ws_take<float>(c, (size_t)n * kCaptureSamples);
+    float* ctxlm = ws_take<float>(c, (size_t)n * kCtxFrames * kBins);
+    float* rows = ws_take<float>(c, (size_t)n * kEmb);
+    int64_t* tabs = ws_take<int64_t>(c, 2 * (n + 1));
+    int* blks = ws_take<int>(c, 2 * nb);
+    CaptureEntry* ent_dev = ws_take<CaptureEntry>(c, n);
+    float* X = ws_take<float>(c, tb); float* A = ws_take<float>(c, tb); float* Y = ws_take<float>(c, tb);
+    std::vector<CaptureEntry> ent(n);
+    for (int k = 0; k < n; ++k)
+        ent[k] = {o->ring + (size_t)slots[k] * kCaptureSamples, clips + (size_t)k * kCaptureSamples,
+                  (int)(o->st[slots[k]].N % kCaptureSamples), flags & NHANS_CAPTURE_NORMALISE};
+    rc = h2d(c, ent_dev, ent.data(), (size_t)n * sizeof(CaptureEntry), s); if (rc) return rc;
+    {
+        Prof pr(c, s, "capture_clip_kernel");
+        launch_capture_clip(ent_dev, n, s);
+        pr.done(0, ((flags & NHANS_CAPTURE_NORMALISE) ? 12.0 : 8.0) * n * kCaptureSamples);
+    }
+    rc = stft_impl(c, clips, soff.data(), n, kCtxFrames, ctxlm, nullptr, tabs, blks, nullptr, s); if (rc) return rc;
+    // (the tower writes workspace rows, not the object's: a failure leaves every slot's conditioning as it was)
+    rc = embed_impl(c, ctxlm, n, rows, X, A, Y, s); if (rc) return rc;
+    if (launch_error_pending()) return NHANS_OK;          // (reported by the entry point; the slots keep their rows)
+    for (int k = 0; k < n; ++k)
+        HIP_TRY(hipMemcpyAsync(o->emb + ((size_t)which[k] * o->S + slots[k]) * kEmb, rows + (size_t)k * kEmb, kEmb * 4,
+                               hipMemcpyDeviceToDevice, s));
+    o->can_rewind = false;
+    if (first_frame)
+        for (int k = 0; k < n; ++k) first_frame[k] = on_ready(o->st[slots[k]].T, o->st[slots[k]].ended, o->la[slots[k]]);
+    return NHANS_OK;
+}
+
+int capture_embeddings_body(const nhans_online* o, const char* fn, int slot, float* ea, float* eb, hipStream_t s) {
+    const int rc = online_slot_check(o, slot, fn); if (rc) return rc;
+    if (ea) HIP_TRY(hipMemcpyAsync(ea, o->emb + (size_t)slot * kEmb, kEmb * 4, hipMemcpyDeviceToDevice, s));
+    if (eb) HIP_TRY(hipMemcpyAsync(eb, o->emb + (size_t)(o->S + slot) * kEmb, kEmb * 4, hipMemcpyDeviceToDevice, s));
+    return NHANS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nhans_capture_plan(int64_t n_before, int64_t count, int64_t* runs_out) {
+    if (n_before < 0 || count < 0) return fail(NHANS_EINVAL, "nhans_capture_plan: negative sample count");
+    if (count == 0) return 0;
+    if (!runs_out) return fail(NHANS_EINVAL, "nhans_capture_plan: null argument");
+    const int64_t skip = std::max<int64_t>(0, count - kCaptureSamples), len = count - skip;
+    const int64_t pos = (n_before + skip) % kCaptureSamples, first = std::min(len, kCaptureSamples - pos);
+    runs_out[0] = skip; runs_out[1] = pos; runs_out[2] = first;
+    if (first == len) return 1;
+    runs_out[3] = skip + first; runs_out[4] = 0; runs_out[5] = len - first;
+    return 2;
+}
+
+int nhans_capture_enable(nhans_online* o, void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_capture_enable: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(capture_enable_body(o, "nhans_capture_enable", call.s));
+}
+
+int nhans_capture_context(nhans_online* o, int n, const int* slots, const int* which, int flags, void* stream,
+                          int64_t* first_frame_out) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_capture_context: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(capture_context_body(o, "nhans_capture_context", n, slots, which, flags, call.s, first_frame_out));
+}
+
+int nhans_capture_embeddings(const nhans_online* o, int slot, float* ea, float* eb, void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_capture_embeddings: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(capture_embeddings_body(o, "nhans_capture_embeddings", slot, ea, eb, call.s));
 }
 
 }  // extern "C"
@@ -2350,6 +2520,7 @@ void live_restore_in(nhans_live* o) {
     o->in->N = o->prev_in.N; o->in->ended = o->prev_in.ended; o->in->cur = o->prev_in.cur;
 }
 
+// (as nhans_online_rewind: the sample rings keep what the undone push wrote, and vlo already says so)
 void live_undo_online(nhans_live* o) {
     o->on->st = o->on->prev;
     o->on->cur = 1 - o->on->cur;
@@ -2522,8 +2693,7 @@ int nhans_live_restart(nhans_live* o, int slot) {
     if (!o) return fail(NHANS_EINVAL, "nhans_live_restart: null object");
     const int rc = live_slot_check(o, slot, "nhans_live_restart"); if (rc) return rc;
     // (nothing is cleared on the device: streams of 0 samples read none of the carried state, in any of the stages)
-    o->on->st[slot] = OnStream();
-    o->on->can_rewind = false;
+    online_restart_slot(o->on, slot);
     o->in->N[slot] = 0; o->in->ended[slot] = 0;
     o->out.N[slot] = 0; o->out.ended[slot] = 0;
     o->can_rewind = false;
@@ -2592,6 +2762,30 @@ int nhans_live_rewind(nhans_live* o) {
     o->out = o->prev_out;
     o->can_rewind = false;
     return NHANS_OK;
+}
+
+int nhans_capture_live_enable(nhans_live* o, void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_capture_live_enable: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(capture_enable_body(o->on, "nhans_capture_live_enable", call.s));
+}
+
+int nhans_capture_live_context(nhans_live* o, int n, const int* slots, const int* which, int flags, void* stream,
+                               int64_t* first_frame_out) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_capture_live_context: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    const int rc = capture_context_body(o->on, "nhans_capture_live_context", n, slots, which, flags, call.s, first_frame_out);
+    if (!rc && !launch_error_pending()) o->can_rewind = false;
+    return call.finish(rc);
+}
+
+int nhans_capture_live_embeddings(const nhans_live* o, int slot, float* ea, float* eb, void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_capture_live_embeddings: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(capture_embeddings_body(o->on, "nhans_capture_live_embeddings", slot, ea, eb, call.s));
 }
 
 void nhans_live_close(nhans_live* o) {

@@ -263,6 +263,17 @@ struct OnlineCopy {
 };
 constexpr int kOnlineCopyMax = 8192;
 void launch_online_copy(const char* kernel, const OnlineCopy* runs_dev, int nruns, hipStream_t s);
+// Conditioning captured from a slot's own stream (include/nhans_hip.h: nhans_capture_*): per slot a ring of the last
+// kCaptureSamples 16 kHz samples, sample k of the stream at position k mod kCaptureSamples; one entry = one context clip
+struct CaptureEntry {
+    const float* ring;  // the slot's ring, kCaptureSamples floats, every one of them valid
+    float* clip;        // kCaptureSamples floats out, oldest sample first
+    int start;          // ring position of the oldest sample: N mod kCaptureSamples
+    int normalise;      // != 0: through the arithmetic of nhans_peak_normalise (flags 0)
+};
+constexpr int kCaptureSamples = (kCtxFrames - 1) * kHop + kWin;     // 32,240: the 200 context frames
+constexpr int kCaptureThreads = 1024;
+void launch_capture_clip(const CaptureEntry* entries_dev, int n, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // STFT / iSTFT (stft.hip)

@@ -30,11 +30,17 @@ EXPORTS = [
     "nhans_live_emitted", "nhans_live_open_slots", "nhans_live_restart", "nhans_live_set_context",
     "nhans_live_set_embeddings", "nhans_live_set_wet", "nhans_live_out_counts", "nhans_live_push", "nhans_live_rewind",
     "nhans_live_close", "nhans_online_set_lookahead", "nhans_lookahead_live_emitted", "nhans_lookahead_live_set",
+    "nhans_capture_plan", "nhans_capture_enable", "nhans_capture_context", "nhans_capture_embeddings",
+    "nhans_capture_live_enable", "nhans_capture_live_context", "nhans_capture_live_embeddings",
 ]
 PCM_INT16, PCM_FLOAT32 = 0, 1
 RESAMPLE_QUANTISE = 1
 NORMALISE_WRAP_INT16 = 1
 LIVE_WET = 1
+CAPTURE_SAMPLES = 32240
+CAPTURE_A, CAPTURE_B = 0, 1
+CAPTURE_NORMALISE = 1
+ESHORT = -4
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25
 ABI_VERSION = 5
@@ -169,6 +175,17 @@ def load():
         lib.nhans_lookahead_live_set.restype = ctypes.c_int
         lib.nhans_lookahead_live_emitted.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         lib.nhans_lookahead_live_emitted.restype = ctypes.c_int64
+    # (conditioning captured from a slot's own stream came after the look-ahead: looked up by symbol)
+    if hasattr(lib, "nhans_capture_context"):
+        ip = ctypes.POINTER(ctypes.c_int)
+        lib.nhans_capture_plan.argtypes = [ctypes.c_int64, ctypes.c_int64, i64p]
+        for obj in ("", "live_"):
+            getattr(lib, "nhans_capture_%senable" % obj).argtypes = [vp, vp]
+            getattr(lib, "nhans_capture_%scontext" % obj).argtypes = [vp, ctypes.c_int, ip, ip, ctypes.c_int, vp, i64p]
+            getattr(lib, "nhans_capture_%sembeddings" % obj).argtypes = [vp, ctypes.c_int, vp, vp, vp]
+        for name in EXPORTS:
+            if name.startswith("nhans_capture_"):
+                getattr(lib, name).restype = ctypes.c_int
     lib.nhans_crc32c.argtypes = [ctypes.c_uint32, vp, ctypes.c_size_t]
     lib.nhans_crc32c.restype = ctypes.c_uint32
     for name in ("nhans_create", "nhans_create_ex", "nhans_set_option", "nhans_stft_features", "nhans_embed", "nhans_mask_net",
@@ -187,7 +204,9 @@ def load():
 
 def check(rc):
     if rc < 0:
-        raise NhansError("libnhans_hip: %s (code %d)" % (load().nhans_last_error().decode(), rc))
+        err = NhansError("libnhans_hip: %s (code %d)" % (load().nhans_last_error().decode(), rc))
+        err.code = rc
+        raise err
     return rc
 
 

@@ -127,6 +127,23 @@ class LiveSession:
         hip.check(self.lib.nhans_lookahead_live_set(self.handle, int(i), L))
         self.lookahead[i] = L
 
+    # ---- conditioning captured from the slot's own stream -------------------------------------
+    def enable_capture(self):
+        """Every slot gets its 16 kHz sample history (nhans_capture_live_enable; idempotent)."""
+        hip.check(self.lib.nhans_capture_live_enable(self.handle, self.mem.stream()))
+
+    def capture_contexts(self, pairs, normalise=True):
+        """online.OnlineEnhancer.capture_contexts for the 16 kHz stage: the samples are what the incoming converter handed
+        on (already divided by peak + 1e-6), resample.emitted(pushed, ended, in_rate, 16000) of them so far."""
+        return online._capture_contexts(self, self.lib.nhans_capture_live_context, pairs, normalise, self.mem.stream())
+
+    def capture_context(self, i, which, normalise=True):
+        return self.capture_contexts([(i, which)], normalise)[0]
+
+    def embeddings(self, i):
+        """(a, b): slot i's current conditioning rows as two float32[512] arrays (nhans_capture_live_embeddings)."""
+        return online._embeddings(self.mem, self.lib.nhans_capture_live_embeddings, self.handle, i)
+
     def set_wet(self, w):
         """The wet factor of the pushes that follow (non-zero needs wet=True at construction)."""
         hip.check(self.lib.nhans_live_set_wet(self.handle, float(w)))

@@ -77,6 +77,82 @@ def normalise_fixed(samples, peak):
     return (np.asarray(samples, dtype=np.float64) / (peak + 0.000001)).astype(np.float32)
 
 
+CAPTURE_SAMPLES = hip.CAPTURE_SAMPLES      # 32,240 = 199 * 160 + 400: the 200 context frames
+
+
+def ring_runs(n_before, count):
+    """nhans_capture_plan restated: the copy runs (offset in the push, ring position, length) that append `count` samples
+    to a slot's ring of CAPTURE_SAMPLES floats which has seen n_before -- sample k of the stream goes to position
+    k mod CAPTURE_SAMPLES, only the last CAPTURE_SAMPLES of a larger push are kept, at most two runs, none for count 0."""
+    if n_before < 0 or count < 0:
+        raise ValueError("ring_runs: negative sample count")
+    if count == 0:
+        return []
+    skip = max(0, count - CAPTURE_SAMPLES)
+    n = count - skip
+    pos = (n_before + skip) % CAPTURE_SAMPLES
+    first = min(n, CAPTURE_SAMPLES - pos)
+    runs = [(skip, pos, first)]
+    if first < n:
+        runs.append((skip + first, 0, n - first))
+    return runs
+
+
+def capture_vlo(vlo, event, n):
+    """vlo of a slot -- the oldest sample of its current stream that the ring still holds (include/nhans_hip.h) -- after
+    `event`: 'enable' (n: the slot's sample count then) -> n; 'restart' -> 0; 'push' (n: the count the push reached) and
+    'rewind' (n: the count the UNDONE push had reached; its samples stay in the ring) -> max(vlo, n - CAPTURE_SAMPLES)."""
+    if event == "enable":
+        return n
+    if event == "restart":
+        return 0
+    if event in ("push", "rewind"):
+        return max(vlo, n - CAPTURE_SAMPLES)
+    raise ValueError("capture_vlo: event %r" % (event,))
+
+
+def capture_span(n_pushed_16k, vlo):
+    """(first, last + 1) of the 16 kHz samples a capture would take from a slot that has received n_pushed_16k samples and
+    whose ring holds its stream from sample vlo on -- or None where the library answers NHANS_ESHORT: too few samples yet,
+    history enabled too recently, a rewound push not yet repeated."""
+    lo = n_pushed_16k - CAPTURE_SAMPLES
+    return (lo, n_pushed_16k) if lo >= vlo else None
+
+
+def capture_side(kind, which):
+    """'a' / 'b' / 'neg' / 'pos' -> NHANS_CAPTURE_A / _B.  'neg' and 'pos' follow the model kind as the header defines the
+    (a, b) order: denoiser a = pos, b = neg; separator a = neg (the interferer), b = pos (the target)."""
+    if which in (hip.CAPTURE_A, "a"):
+        return hip.CAPTURE_A
+    if which in (hip.CAPTURE_B, "b"):
+        return hip.CAPTURE_B
+    if which in ("neg", "pos") and kind in hip.KIND_CODE:
+        a_is = "pos" if hip.KIND_CODE[kind] == hip.DENOISER else "neg"
+        return hip.CAPTURE_A if which == a_is else hip.CAPTURE_B
+    raise ValueError("which: 'a', 'b', 'neg' or 'pos' (got %r for a %s)" % (which, kind))
+
+
+def _capture_contexts(obj, fn, pairs, normalise, stream):
+    pairs = list(pairs)
+    n = len(pairs)
+    slots = (ctypes.c_int * max(n, 1))(*[int(i) for i, _ in pairs])
+    sides = (ctypes.c_int * max(n, 1))(*[capture_side(obj.eng.kind, w) for _, w in pairs])
+    R = (ctypes.c_int64 * max(n, 1))()
+    hip.check(fn(obj.handle, n, slots, sides, hip.CAPTURE_NORMALISE if normalise else 0, stream, R))
+    return [int(R[k]) for k in range(n)]
+
+
+def _embeddings(mem, fn, handle, i):
+    rows = mem.empty(2 * spec.EMB)
+    try:
+        base = mem.p(rows).value
+        hip.check(fn(handle, int(i), ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * spec.EMB), mem.stream()))
+        out = np.array(mem.down(rows, 2 * spec.EMB), dtype=np.float32)
+    finally:
+        mem.free(rows)
+    return out[:spec.EMB].copy(), out[spec.EMB:].copy()
+
+
 class OnlineEnhancer:
     """S live recordings conditioned on ctx_a[i] / ctx_b[i] (normalised float32, >= 32,240 samples each; resnet_block
     argument order as everywhere: denoiser (pos, neg), separator (noise, clean)).
@@ -92,7 +168,11 @@ class OnlineEnhancer:
     the 16 kHz one and none of this exists.
 
     lookahead: L frames, 0 .. 17, one for all slots or one per slot (set_lookahead(i, L) later, on a slot whose stream
-    has no samples yet).  The output is then bit for bit the offline one of that L: Engine.enhance(..., lookahead=L)."""
+    has no samples yet).  The output is then bit for bit the offline one of that L: Engine.enhance(..., lookahead=L).
+
+    enable_capture() + capture_context(i, which): slot i's conditioning, side `which`, taken from the last 2.015 s the
+    slot itself has received at 16 kHz (include/nhans_hip.h, "Conditioning captured from a slot's own stream") -- with
+    in_rate, from what the incoming converter handed on."""
 
     def _begin(self, engine, S, want_mixed):
         self.eng = engine
@@ -275,6 +355,27 @@ class OnlineEnhancer:
             self._free(*[r for r in rows if not hasattr(r, "numel")])
         self.conditioned[i] = True
         return int(R.value)
+
+    # ---- conditioning captured from the slot's own stream -------------------------------------
+    def enable_capture(self):
+        """Every slot gets its sample history (nhans_capture_enable; idempotent): pushes from now on feed it."""
+        hip.check(self.lib.nhans_capture_enable(self.handle, self._stream()))
+
+    def capture_contexts(self, pairs, normalise=True):
+        """pairs: [(slot, which), ...], which 'a' / 'b' / 'neg' / 'pos' (capture_side).  Each slot's row `which` becomes
+        the embedding of the last CAPTURE_SAMPLES samples of its own stream (peak-normalised as apply.normalise does, or as
+        stored); one tower pass for all of them.  Returns [R, ...] as set_context does.  NhansError with .code ==
+        hip.ESHORT where capture_span is None."""
+        return _capture_contexts(self, self.lib.nhans_capture_context, pairs, normalise, self._stream())
+
+    def capture_context(self, i, which, normalise=True):
+        return self.capture_contexts([(i, which)], normalise)[0]
+
+    def embeddings(self, i):
+        """(a, b): slot i's current conditioning rows as two float32[512] arrays (nhans_capture_embeddings) -- a learnt
+        noise profile that set_embeddings accepts elsewhere."""
+        from . import resample
+        return _embeddings(resample._Mem(self.eng), self.lib.nhans_capture_embeddings, self.handle, i)
 
     def _push_once(self, din, inoff, endv, counts):
         ooff = [0]

@@ -23,7 +23,15 @@ three lines, each with push p50 / p99 over the same pushes of H hops per active 
   mode "churn"   the same, and every J-th push one stream leaves with `end` and one joins an idle slot (restart + by
                  turns set_context and set_embeddings); the wall time of the two set calls, each followed by a device
                  synchronise, is reported on its own (p50 over the joins; set_embeddings gets rows computed beforehand)
-    python tools/online_bench.py --churn [--slots 64,256] [--active 16] [--every 8] [--hops 1] [--pushes 240] [--out F]"""
+    python tools/online_bench.py --churn [--slots 64,256] [--active 16] [--every 8] [--hops 1] [--pushes 240] [--out F]
+
+--capture: what the sample history (nhans_capture_enable) costs a push and what a capture costs.  Per (S, H) one line
+with mode "capture": push p50 / p99 of an S-slot object with the history disabled and of its twin with it enabled, the
+same pushes by turns (launches_per_push of both from a profiled pass), and the wall time, device synchronise included,
+of a one-entry capture_context beside a set_context of the same slot (p50 / max over --captures calls of each).  On a
+library from before the capture functions ($NHANS_LIB, for a same-box A/B) the enabled and capture figures are null and
+the line still carries the disabled push and set_context.
+    python tools/online_bench.py --capture [--streams 1,8] [--hops 1,4] [--pushes 200] [--captures 20] [--out F]"""
 import argparse
 import json
 import os
@@ -141,6 +149,70 @@ def churn(a):
     return 0
 
 
+def capture(a):
+    eng = engine.Engine("denoiser", precision="f16x3")
+    ca, cb = apply.normalise(synth.silent()), apply.normalise(synth.noise_context(1))
+    audio = apply.normalise(synth.mixture(1, 30.0))
+    has = hasattr(hip.load(), "nhans_capture_context")
+    out = open(a.out, "a") if a.out else None
+    pct = lambda v, q: round(float(np.percentile(v, q)), 3) if len(v) else None
+    for S in [int(s) for s in a.streams.split(",")]:
+        for H in [int(h) for h in a.hops.split(",")]:
+            n = H * spec.HOP
+            objs = {"disabled": online.OnlineEnhancer(eng, [ca] * S, [cb] * S)}
+            if has:
+                objs["enabled"] = online.OnlineEnhancer(eng, [ca] * S, [cb] * S)
+                objs["enabled"].enable_capture()
+            pos = {k: 0 for k in objs}
+
+            def push(k):
+                i = pos[k] % (len(audio) - n)
+                pos[k] += n
+                objs[k].push([audio[i:i + n]] * S)
+
+            # (past the look-ahead, and past the 32,240 samples a capture needs)
+            for k in objs:
+                objs[k].push([audio[:online.CAPTURE_SAMPLES]] * S)
+                pos[k] = online.CAPTURE_SAMPLES
+                for _ in range(40):
+                    push(k)
+            torch.cuda.synchronize()
+            ts = {k: [] for k in objs}
+            for _ in range(a.pushes):
+                for k in objs:
+                    ts[k].append(_timed(lambda: push(k)))
+            launches = {}
+            for k in objs:
+                eng.set_option("profile", 1)
+                eng.profile_reset()
+                for _ in range(10):
+                    push(k)
+                launches[k] = sum(v["calls"] for v in eng.profile().values()) / 10
+                eng.set_option("profile", 0)
+            t_set, t_cap = [], []
+            for _ in range(a.captures):
+                t_set.append(_timed(lambda: objs["disabled"].set_context(0, ca, cb)))
+                if has:
+                    t_cap.append(_timed(lambda: objs["enabled"].capture_context(0, "b")))
+            for o in objs.values():
+                o.close()
+            line = {"mode": "capture", "streams": S, "hops_per_push": H, "push_audio_ms": H * 10, "pushes": a.pushes}
+            for k in ("disabled", "enabled"):
+                line["push_ms_p50_" + k] = pct(ts.get(k, []), 50)
+                line["push_ms_p99_" + k] = pct(ts.get(k, []), 99)
+                line["launches_per_push_" + k] = launches.get(k)
+            line.update({"set_context_ms_p50": pct(t_set, 50), "set_context_ms_max": pct(t_set, 100),
+                         "capture_context_ms_p50": pct(t_cap, 50), "capture_context_ms_max": pct(t_cap, 100),
+                         "captures": a.captures, "lib": os.path.basename(os.environ.get("NHANS_LIB") or "tree"),
+                         "precision": "f16x3", "weights": "synthetic seed 7"})
+            print(json.dumps(line), flush=True)
+            if out:
+                out.write(json.dumps(line) + "\n")
+                out.flush()
+    eng.close()
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--churn", action="store_true", help="slots that callers join and leave (see the top of this file)")
@@ -155,9 +227,13 @@ def main():
     ap.add_argument("--out_rate", type=int, default=None, help="pieces are returned at this rate (default: 16 kHz)")
     ap.add_argument("--live", action="store_true", help="drive a live.LiveSession (needs --in_rate and --out_rate)")
     ap.add_argument("--lookahead", type=int, default=spec.LOOKAHEAD, help="look-ahead L of every stream, 0 ... 17 frames")
+    ap.add_argument("--capture", action="store_true", help="cost of the sample history and of a capture (see the top of this file)")
+    ap.add_argument("--captures", type=int, default=20, help="--capture: timed capture_context / set_context calls")
     a = ap.parse_args()
     if a.churn:
         return churn(a)
+    if a.capture:
+        return capture(a)
     if a.live and not (a.in_rate and a.out_rate):
         ap.error("--live needs --in_rate and --out_rate")
     if not 0 <= a.lookahead <= spec.LOOKAHEAD:
