@@ -170,7 +170,12 @@ size_t nhans_workspace_bytes(nhans_ctx* ctx, int64_t total_frames, int nclips);
 
 /* wav -> log-magnitude and phase.  max_frames_per_clip > 0 truncates every clip to its first
  * frames (used for the 200-frame conditioning contexts, SN/apply.py:381).  Outputs are
- * [sum_c min(T_c, max), 201] float32; phase_dev may be NULL. */
+ * [sum_c min(T_c, max), 201] float32; phase_dev may be NULL.  With max_frames_per_clip > 0 a clip that has fewer frames
+ * is refused with NHANS_ESHORT and nothing is written.  A clip may carry up to 159 samples behind its last frame
+ * (they are not read into any frame).  Any finite float32 samples: every log-magnitude is finite and every phase lies in
+ * [-pi, pi]; atan2(0, 0) = 0.  A bin whose real and imaginary parts are both below the smallest normal float32 (1.18e-38)
+ * has zero magnitude to the hardware reciprocal: its phase is that of the axis of its larger part (0, +-pi/2 or +-pi), not
+ * the angle between the two -- under the 1e-5 floor such a bin's log-magnitude is ln 1e-5 either way. */
 int nhans_stft_features(nhans_ctx* ctx, const float* wav_dev, const int64_t* sample_offsets_host,
                         int nclips, int max_frames_per_clip, float* logmag_dev, float* phase_dev,
                         void* stream);
@@ -188,7 +193,12 @@ int nhans_mask_net(nhans_ctx* ctx, const float* logmag_dev, const int64_t* frame
                    float* logits_out_dev, float* denoised_out_dev, void* stream);
 
 /* exp/polar -> 400-point inverse real FFT -> synthesis window -> overlap-add.  Clip c writes
- * (T_c-1)*160+400 samples at wav_out_dev + out_offsets_host[c]. */
+ * (T_c-1)*160+400 samples at wav_out_dev + out_offsets_host[c] (out_offsets_host has nclips + 1 entries).  The phases
+ * at bins 0 and 200 are used through their cosine only, as a real inverse FFT does.  Phases are expected in [-pi, pi],
+ * both ends included: there the output is within float32 rounding of the float64 result.  Larger angles are accepted and
+ * not reduced first; the angle goes to the hardware sine in revolutions rounded to float32, so each phase is off by up to
+ * half an ulp of |phase / 2 pi| -- 2^-23 revolutions = 7.5e-7 rad between 4 pi and 8 pi.  Log-magnitudes from ln 1e-5 - 20 to 16 are covered by the
+ * tests; exp(logmag) must stay a finite float32. */
 int nhans_istft(nhans_ctx* ctx, const float* logmag_dev, const float* phase_dev,
                 const int64_t* frame_offsets_host, int nclips, const int64_t* out_offsets_host,
                 float* wav_out_dev, void* stream);

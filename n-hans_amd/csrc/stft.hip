@@ -37,7 +37,10 @@ constexpr int kTFrame = 20 * kTRow;     // 420 complex per frame
 __device__ __forceinline__ float fast_atan2(float y, float x) {
     const float ax = fabsf(x), ay = fabsf(y);
     const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    const float r = mx > 0.f ? mn * __builtin_amdgcn_rcpf(mx) : 0.f;     // atan2(0, 0) = 0 like libm
+    // v_rcp_f32 takes no denormal input: it answers inf, and mn * inf is inf or NaN.  A bin whose larger component is below
+    // the smallest normal number (a magnitude under 1.7e-38 beside the 1e-5 floor) counts as zero magnitude on the axis of
+    // that component: 0, +-pi/2 or +-pi.  Normal inputs take the same instructions as before, bit for bit.
+    const float r = mx >= 1.17549435e-38f ? mn * __builtin_amdgcn_rcpf(mx) : 0.f;     // atan2(0, 0) = 0 like libm
     const float t = r * r;
     // minimax fit of atan(r)/r in r^2 on [0, 1]: 1.7e-7 rad in float32 arithmetic
     float p = -0.004733146633952856f;
