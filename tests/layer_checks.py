@@ -99,7 +99,7 @@ def clip_embeddings(emb):
 
 
 class Taps:
-    """acts: {index: torch tensor NHWC} for all 25 tensors; emb [3,512]; logits [21,201] -- of one dtype."""
+    """acts: {index: torch tensor NHWC} for all 25 tensors; emb [3,512]; logits and denoised [21,201] -- of one dtype."""
 
 
 def cpu_taps(W, kind, dtype, lms, ctx, emb_in=None, want=("tower", "stack")):
@@ -107,7 +107,7 @@ def cpu_taps(W, kind, dtype, lms, ctx, emb_in=None, want=("tower", "stack")):
     embeddings rounded to float32) so that stack errors are not the tower's."""
     ref = TorchRef(W, kind, dtype)
     t = Taps()
-    t.acts, t.emb, t.logits = {}, None, None
+    t.acts, t.emb, t.logits, t.denoised = {}, None, None, None
     with torch.no_grad():
         if "tower" in want:
             t.emb = ref.tower(torch.from_numpy(ctx).to(dtype), t.acts)
@@ -115,16 +115,18 @@ def cpu_taps(W, kind, dtype, lms, ctx, emb_in=None, want=("tower", "stack")):
             if emb_in is None:
                 emb_in = t.emb.to(torch.float32).numpy()
             ea, eb = clip_embeddings(torch.from_numpy(np.asarray(emb_in, dtype=np.float32)).to(dtype))
-            per_clip, outs = [], []
+            per_clip, outs, dens = [], [], []
             for i, lm in enumerate(lms):
                 a = {}
                 win = ref.windows(torch.from_numpy(lm).to(dtype))
-                o, _ = ref.mask_net(win, ea[i][None].expand(len(lm), -1), eb[i][None].expand(len(lm), -1), a)
+                o, d = ref.mask_net(win, ea[i][None].expand(len(lm), -1), eb[i][None].expand(len(lm), -1), a)
                 per_clip.append(a)
                 outs.append(o)
+                dens.append(d)
             for idx in STACK_IDX:
                 t.acts[idx] = torch.cat([a[idx] for a in per_clip])
             t.logits = torch.cat(outs)
+            t.denoised = torch.cat(dens)
     return t
 
 
@@ -150,8 +152,9 @@ class Verdict:
         self.__dict__.update(kw)
 
     def row(self):
+        name = getattr(self, "name", None) or NAMES[self.idx]
         return "%2d %-34s %-12s err_hip %.3e  err_cpu32 %.3e  max %.3e  hip/cpu32 %6.2f  hip/max %.2e  bar/max %.2e %s" % (
-            self.idx, NAMES[self.idx], self.mode, self.err_hip, self.err_cpu32, self.m,
+            self.idx, name, self.mode, self.err_hip, self.err_cpu32, self.m,
             self.err_hip / max(self.err_cpu32, 1e-300), self.err_hip / self.m, self.bar / self.m, "" if self.ok else "FAIL")
 
 
@@ -216,6 +219,82 @@ def check_tensor(idx, hip, t64, t32, mode, label=""):
                          _where(idx, n, h, w, shape, n * H * W_ + h * W_ + w, N * H * W_), len(over), C,
                          ", ".join("c%d %.2e" % (int(i), float(e)) for e, i in zip(topc.values, topc.indices)),
                          ", ".join("w%d %.2e" % (int(i), float(e)) for e, i in zip(topw.values, topw.indices))))
+    return v
+
+
+# ---- the three arrays a caller receives: same bar, same verdict, same table ------------------------------------------
+# (numbered after the 25 stored tensors in the table of rows)
+HEADS = {"embeddings": (25, "head embeddings [n,512]"), "logits": (26, "head logits [T,201]"),
+         "denoised": (27, "head denoised [T,201]")}
+
+
+def _where_row(name, r, rows, foff, chunk):
+    if name == "embeddings":
+        tags = [t for t, hit in (("first image", r == 0), ("last image", r == rows - 1)) if hit]
+        if chunk and r % chunk == 0: tags.append("first image of a pass of %d" % chunk)
+        return ", ".join(tags) or "interior"
+    tags = []
+    for i in range(len(foff) - 1):
+        if foff[i] <= r < foff[i + 1]:
+            tags.append("clip %d" % i)
+            if r == foff[i]: tags.append("first frame of clip %d" % i)
+            if r == foff[i + 1] - 1: tags.append("last frame of clip %d" % i)
+    if r == rows - 1 or (chunk and r % chunk == chunk - 1):
+        tags.append("last row of a pass")
+    for t in TILES:
+        if r >= (rows // t) * t:
+            tags.append("last partial %d-row tile of the launch" % t)
+    return ", ".join(tags)
+
+
+def check_head(name, hip, ref64, cpu32, mode, label="", foff=None, chunk=0):
+    """One of the arrays a caller receives -- name: "embeddings" [n,512], "logits" or "denoised" [T,201] -- against float64,
+    ALL elements, at check_tensor's bar: K x max|cpu32 - f64| + F x max|f64|, (K, F) = BAR[mode], below CAP x max|f64|.
+    hip: the device's array; ref64 / cpu32: the float64 reference and its float32 CPU restatement (the yardstick).
+    foff: frame offsets of the clips (default: the layer tests' batch when the row count is its 21, else one clip);
+    chunk: rows per pass, for the message.  Returns a Verdict like check_tensor's: worst = (row, column), col_err per
+    embedding channel / bin, channels_over = the channels / bins above the bar."""
+    K, F = BAR[mode]
+    idx, title = HEADS[name]
+    unit_r, unit_c = ("image", "channel") if name == "embeddings" else ("frame", "bin")
+    ref = torch.as_tensor(ref64).to(torch.float64)
+    c32 = torch.as_tensor(cpu32)
+    hip = torch.as_tensor(hip).detach().cpu()
+    assert hip.ndim == 2 and tuple(hip.shape) == tuple(ref.shape) == tuple(c32.shape), (name, hip.shape, ref.shape, c32.shape)
+    assert c32.dtype == torch.float32 and hip.dtype in (torch.float32, torch.float64), (c32.dtype, hip.dtype)
+    rows, cols = ref.shape
+    if foff is None:
+        foff = FOFF if (name != "embeddings" and rows == TOTAL) else [0, rows]
+    d = (hip.to(torch.float64) - ref).abs_()
+    err_cpu32 = float((c32.to(torch.float64) - ref).abs_().max())
+    m = float(ref.abs().max())
+    err_hip = float(d.max()) if bool(torch.isfinite(hip).all()) else float("inf")
+    bar = K * err_cpu32 + F * m
+    col = d.amax(dim=0)
+    row = d.amax(dim=1)
+    r, c = divmod(int(d.argmax()), cols)
+    problems = []
+    if not err_hip <= bar:
+        problems.append("max|hip - f64| %.3e above the bar %.3e (= %g x err_cpu32 %.3e + %g x max %.3e)" % (err_hip, bar, K, err_cpu32, F, m))
+    if not bar < CAP * m:
+        problems.append("the bar %.3e is not below the cap %g x max = %.3e (err_cpu32 %.3e)" % (bar, CAP, CAP * m, err_cpu32))
+    if not err_cpu32 <= CAP * m:
+        problems.append("float32 CPU against float64 %.3e above %g x max: the yardstick itself is off" % (err_cpu32, CAP))
+    if name == "embeddings" and not float(hip.min()) >= 0.0:
+        problems.append("a mean of a post-ReLU tensor is %.3e" % float(hip.min()))
+    over = torch.nonzero(col > bar).flatten().tolist()
+    v = Verdict(idx=idx, name=title, mode=mode, ok=not problems, err_hip=err_hip, err_cpu32=err_cpu32, m=m, bar=bar, worst=(r, c),
+                col_err=col, row_err=row, chan_err=col, channels_over=over, message="")
+    if problems:
+        topc = torch.topk(col, min(5, cols))
+        topr = torch.topk(row, min(5, rows))
+        v.message = ("%s %s %s: %s; worst element (%s %d, %s %d) of %s: hip %.9g f64 %.9g cpu32 %.9g [%s]; %d of %d %ss above the "
+                     "bar%s; %s maxima %s; %s maxima %s" % (
+                         title, mode, label, "; ".join(problems), unit_r, r, unit_c, c, (rows, cols), float(hip[r, c]), float(ref[r, c]),
+                         float(c32[r, c]), _where_row(name, r, rows, foff, chunk), len(over), cols, unit_c,
+                         (": " + ", ".join("%s %d" % (unit_c, i) for i in over[:8]) + (" ..." if len(over) > 8 else "")) if over else "",
+                         unit_c, ", ".join("%s%d %.2e" % (unit_c[0], int(i), float(e)) for e, i in zip(topc.values, topc.indices)),
+                         unit_r, ", ".join("%s%d %.2e" % (unit_r[0], int(i), float(e)) for e, i in zip(topr.values, topr.indices))))
     return v
 
 

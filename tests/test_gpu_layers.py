@@ -22,7 +22,9 @@ its worst rows (MI355X, max|hip - f64| as a multiple of max|cpu32 - f64| and as 
 Besides the bar: no negative value in a post-ReLU tensor, dead channels of `trained_bn` constant over pixels, and bit for
 bit: one launch of all frames == passes of 8 frames, nhans_debug_block_output == the new tap, the tower for
 contexts_per_chunk 64 / 1 / 2 and split_k 1 / 0; take_status() == 0 after every fetch; embeddings and logits of the same
-engine at the existing bars.
+engine at the existing bars -- and, element by element at the bar of the stored tensors, the three arrays a caller
+receives: nhans_embed's embeddings, nhans_mask_net's logits and denoised rows (layer_checks.check_head; the code
+between tensor 7 / 24 and them is tested alone in tests/test_gpu_heads.py).
 
 test_planted_fault_is_caught_at_its_layer: the sensitivity of this file is itself under test.  A slice of one weight
 tensor handed to the LIBRARY is rounded to f16 (for the arithmetic: a kernel that lost the `lo` half of that slice; no
@@ -97,6 +99,12 @@ class _Device:
         e = self.eng.embed(self.ctx)
         return e, self.eng.take_status()
 
+    def heads(self, frames_per_chunk=3776):
+        """(logits, denoised) of one nhans_mask_net call."""
+        self.eng.set_option("frames_per_chunk", frames_per_chunk)
+        lg, den = self.eng.mask_net(self.lm, L.FOFF, self.ea, self.eb)
+        return lg, den, self.eng.take_status()
+
 
 def _averaged_bars(t64):
     return (L.LOGIT_TOL * max(1.0, float(t64.logits.abs().max()) / 5.0), L.EMB_TOL * max(1.0, float(t64.emb.abs().max())))
@@ -166,6 +174,19 @@ def test_every_stored_tensor(lib_built, kind, recipe):
             if st_e or st_l or not e_err < emb_tol or not l_err < logit_tol or not _same_bits(lg, lg_b):
                 failures.append("%s: averaged outputs: embeddings %.3e (bar %.1e), logits %.3e (bar %.1e), status %d / %d, chunked logits same bits: %s" % (
                     tag, e_err, emb_tol, l_err, logit_tol, st_e, st_l, _same_bits(lg, lg_b)))
+            # ---- the same three arrays, every element, at the bar of the stored tensors (layer_checks.check_head): one
+            # launch of the ragged batch, which passes of 8 frames must repeat bit for bit -- the denoised rows too
+            lg_h, den_h, st_h = dev.heads()
+            lg_c, den_c, st_c = dev.heads(L.CHUNK)
+            if st_h or st_c or not (_same_bits(lg_h, lg) and _same_bits(lg_c, lg_h) and _same_bits(den_c, den_h)):
+                failures.append("%s: heads: one launch and passes of %d frames differ (logits %s, denoised %s, status %d / %d)" % (
+                    tag, L.CHUNK, _same_bits(lg_c, lg_h) and _same_bits(lg_h, lg), _same_bits(den_c, den_h), st_h, st_c))
+            for name, t, r64, r32 in (("embeddings", e, t64.emb, t32.emb), ("logits", lg_h, t64.logits, t32.logits),
+                                      ("denoised", den_h, t64.denoised, t32.denoised)):
+                v = L.check_head(name, t, r64, r32, mode, tag)
+                rows.append("%-40s %s" % (tag, v.row()))
+                if not v.ok:
+                    failures.append(v.message)
     finally:
         dev.eng.close()
     print("\n%s %s: CPU references %.1f s, whole case %.1f s" % (kind, recipe, t_ref, time.time() - t0))
