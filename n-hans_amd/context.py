@@ -1,0 +1,183 @@
+"""What every Python class over the C ABI (include/nhans_hip.h) shares, written once: the context that engine.Engine and
+lite.LiteEngine both are, the f32 redo of work that saturated the f16x3 path, the device memory of either engine, and
+the ragged-batch helpers.  No torch at module level: the single-process command line (lite.py) imports this."""
+import ctypes
+import warnings
+
+import numpy as np
+
+from . import hip, hiprt, spec
+
+
+class Context:
+    """One nhans_ctx.  A subclass's constructor sets `lib` and `handle` and says with `torch_memory` where its device
+    memory and stream come from: torch (engine.Engine), or hiprt and the null stream (lite.LiteEngine)."""
+
+    PRECISIONS = {"f32": 0, "f16x3": 1}
+    torch_memory = False
+    handle = None
+
+    def set_option(self, key, value):
+        hip.check(self.lib.nhans_set_option(self.handle, key.encode(), int(value)))
+
+    def set_precision(self, precision):
+        """'f32': exact f32 matrix-core path.  'f16x3': split-f16 (hi+lo, three products) on the f16
+        matrix cores -- FP32-class accuracy, needs |activations| < 65504."""
+        self.set_option("precision", self.PRECISIONS[precision])
+        self.precision = precision
+
+    def close(self):
+        if self.handle:
+            self.lib.nhans_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- activation exponents of the f16x3 mode (include/nhans_hip.h: "calibrate") ----------
+    def activation_exponents(self):
+        e = (ctypes.c_int * hip.NUM_ACTIVATIONS)()
+        hip.check(self.lib.nhans_get_activation_exponents(self.handle, e, hip.NUM_ACTIVATIONS))
+        return list(e)
+
+    def set_activation_exponents(self, exps):
+        e = (ctypes.c_int * hip.NUM_ACTIVATIONS)(*[int(v) for v in exps])
+        hip.check(self.lib.nhans_set_activation_exponents(self.handle, e, hip.NUM_ACTIVATIONS))
+
+    def activation_amax(self):
+        """Largest |x| of every exponent-carrying tensor in the last finished calibration."""
+        a = (ctypes.c_float * hip.NUM_ACTIVATIONS)()
+        hip.check(self.lib.nhans_get_activation_amax(self.handle, a, hip.NUM_ACTIVATIONS))
+        return list(a)
+
+    def _stream(self):
+        return None
+
+    def take_status(self):
+        """Waits for the current stream; returns and clears the sticky device status bits
+        (hip.STATUS_SATURATED: a split-f16 activation did not fit f16 and was clamped)."""
+        flags = ctypes.c_int(0)
+        hip.check(self.lib.nhans_take_status(self.handle, ctypes.byref(flags), self._stream()))
+        return flags.value
+
+    def _with_lookahead(self, L, run):
+        """run() with the option "lookahead" at L frames and back at the default afterwards, whatever run() did."""
+        if L == spec.LOOKAHEAD:
+            return run()
+        spec.check_lookahead(L)
+        self.set_option("lookahead", L)
+        try:
+            return run()
+        finally:
+            self.set_option("lookahead", spec.LOOKAHEAD)
+
+
+def redo_saturated_in_f32(eng, run, undo=None):
+    """run() -- the launches of one batch or push -- and its result; where they saturated the f16x3 path, run() again on
+    the exact f32 path.  The split-f16 layout holds |activation * 2^-e| < 65504 and such work is further from the
+    calibration than the 2^8 of headroom: undo() takes it back (a push: the rewind), then the same library does it in
+    f32 MFMA mode (no CPU involved) with the tensors' maxima recorded, and the exponents are raised so that the work
+    after it fits."""
+    res = run()
+    if not (eng.take_status() & hip.STATUS_SATURATED and eng.precision == "f16x3"):
+        return res
+    warnings.warn("N-HANS f16x3 path: an activation left the f16 range; batch recomputed in f32 MFMA mode "
+                  "and the activation exponents raised")
+    if undo is not None:
+        undo()
+    eng.set_option("calibrate", 1)
+    try:
+        eng.set_precision("f32")
+        res = run()
+        eng.take_status()
+    except BaseException:
+        # close the bracket FIRST (3 = keep the exponents, learn nothing) -- an open bracket keeps recording maxima on
+        # every later call --, then put the precision back; neither may mask the original error
+        try:
+            eng.set_option("calibrate", 3)
+        finally:
+            eng.set_precision("f16x3")
+        raise
+    try:
+        # (raise-only; maxima that are not finite -- the flag is also raised by a NaN / Inf INPUT -- are skipped)
+        eng.set_option("calibrate", 2)
+    except hip.NhansError as err:          # the f32 result stands whatever the exponent update says
+        warnings.warn("N-HANS: activation exponents not updated after the f32 rerun: %s" % err)
+    finally:
+        eng.set_precision("f16x3")
+    return res
+
+
+class Mem:
+    """Device memory and stream of either engine: the package's one branch between torch and hiprt.  A buffer of 0
+    elements is one allocated element, so that its pointer is never null."""
+
+    def __init__(self, engine):
+        self.eng = engine
+        self.torch = engine.torch_memory
+
+    def stream(self):
+        return self.eng._stream()
+
+    def up(self, arr):
+        """contiguous numpy array -> device copy"""
+        if not self.torch:
+            return hiprt.DevBuf.from_array(arr)
+        if not arr.size:
+            return self.empty(0, arr.dtype)
+        import torch
+        return torch.from_numpy(arr).to(self.eng.device)
+
+    def up_f32(self, x):
+        """A host array -- or, over torch memory, a tensor -- as (flat float32 device buffer, its elements, whether the
+        buffer was allocated here and is the caller's to free)."""
+        if self.torch and hasattr(x, "data_ptr"):
+            import torch
+            t = x.detach().to(device=self.eng.device, dtype=torch.float32).contiguous().reshape(-1)
+            return t, t.numel(), False
+        a = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        return self.up(a), a.size, True
+
+    def empty(self, n, dtype=np.float32):
+        if self.torch:
+            import torch
+            return torch.empty(max(n, 1), dtype=getattr(torch, np.dtype(dtype).name), device=self.eng.device)
+        return hiprt.DevBuf(np.dtype(dtype).itemsize * max(n, 1))
+
+    def p(self, buf):
+        if buf is None:
+            return None
+        return hip.ptr(buf) if self.torch else buf.ptr
+
+    def down(self, buf, n, dtype=np.float32):
+        if self.torch:
+            return buf[:n].cpu().numpy()
+        return buf.to_array(np.empty(n, dtype))
+
+    def free(self, *bufs):
+        if not self.torch:
+            for b in bufs:
+                if b is not None:
+                    b.free()
+
+
+def offsets(counts):
+    off = [0]
+    for n in counts:
+        off.append(off[-1] + int(n))
+    return off
+
+
+def flat(arrays, dtype=np.float32):
+    """1-D arrays -> (one contiguous array of dtype holding them one after the other, offsets)."""
+    off = offsets(len(a) for a in arrays)
+    out = np.concatenate([np.asarray(a, dtype=dtype) for a in arrays]) if len(arrays) else np.zeros(0, dtype)
+    return np.ascontiguousarray(out, dtype=dtype), off
+
+
+def end_flags(end, n):
+    """end[i]: stream i ends after this push -> the int array the push entry points take (None: no stream ends)."""
+    return (ctypes.c_int * n)(*[int(bool(e)) for e in end]) if end is not None else None

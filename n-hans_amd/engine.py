@@ -2,27 +2,18 @@
 PyTorch is used only for device memory and streams; all arithmetic runs in the HIP library."""
 import ctypes
 import os
-import warnings
 
-import numpy as np
 import torch
 
-from . import fold, hip, spec, weights as weights_mod
+from . import context, fold, hip, spec, weights as weights_mod
 
 
-def _offsets(lengths):
-    off = [0]
-    for n in lengths:
-        off.append(off[-1] + int(n))
-    return off
-
-
-class Engine:
+class Engine(context.Context):
     """kind: 'denoiser' | 'separator'.  weights: checkpoint dict (name -> float32 array) or None for
     the seeded synthetic weights.  Conditioning order everywhere is (a, b) = resnet_block argument
     order: denoiser (pos, neg); separator (noise = --neg, clean = --pos)."""
 
-    PRECISIONS = {"f32": 0, "f16x3": 1}
+    torch_memory = True
 
     def __init__(self, kind=spec.DENOISER, weights=None, device=0, seed=7, frames_per_chunk=None,
                  precision=None):
@@ -45,42 +36,10 @@ class Engine:
             self.set_option("conv_variant", int(os.environ["NHANS_CONV_VARIANT"]))
 
     def set_precision(self, precision):
-        """'f32': exact f32 matrix-core path.  'f16x3': split-f16 (hi+lo, three products) on the f16
-        matrix cores -- FP32-class accuracy, needs |activations| < 65504."""
+        """context.Context.set_precision; None: $NHANS_PRECISION, else 'f16x3'."""
         if precision is None:
             precision = os.environ.get("NHANS_PRECISION", "f16x3")
-        self.set_option("precision", self.PRECISIONS[precision])
-        self.precision = precision
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.nhans_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_option(self, key, value):
-        hip.check(self.lib.nhans_set_option(self.handle, key.encode(), int(value)))
-
-    # ---- activation exponents of the f16x3 mode (include/nhans_hip.h: "calibrate") ----------
-    def activation_exponents(self):
-        e = (ctypes.c_int * hip.NUM_ACTIVATIONS)()
-        hip.check(self.lib.nhans_get_activation_exponents(self.handle, e, hip.NUM_ACTIVATIONS))
-        return list(e)
-
-    def set_activation_exponents(self, exps):
-        e = (ctypes.c_int * hip.NUM_ACTIVATIONS)(*[int(v) for v in exps])
-        hip.check(self.lib.nhans_set_activation_exponents(self.handle, e, hip.NUM_ACTIVATIONS))
-
-    def activation_amax(self):
-        """Largest |x| of every exponent-carrying tensor in the last finished calibration."""
-        a = (ctypes.c_float * hip.NUM_ACTIVATIONS)()
-        hip.check(self.lib.nhans_get_activation_amax(self.handle, a, hip.NUM_ACTIVATIONS))
-        return list(a)
+        super().set_precision(precision)
 
     def calibrate(self, mixes, ctx_a, ctx_b, raise_only=False):
         """Sets the activation exponents from the caller's own clips (nhans_create has calibrated on a built-in
@@ -107,20 +66,12 @@ class Engine:
             self.set_precision(before)
         return self.activation_exponents()
 
-    def take_status(self):
-        """Waits for the current stream; returns and clears the sticky device status bits
-        (hip.STATUS_SATURATED: a split-f16 activation left the f16 range and was clamped)."""
-        flags = ctypes.c_int(0)
-        hip.check(self.lib.nhans_take_status(self.handle, ctypes.byref(flags), self._stream()))
-        return flags.value
-
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _dev(self, arrays):
         """list of 1-D float32 numpy arrays -> (concatenated device tensor, offsets)."""
-        off = _offsets([len(a) for a in arrays])
-        flat = np.concatenate([np.asarray(a, dtype=np.float32) for a in arrays]) if arrays else np.zeros(0, np.float32)
+        flat, off = context.flat(arrays)
         return torch.from_numpy(flat).to(self.device), off
 
     # ---- stage-level entry points (used by the parity tests) --------------------------------
@@ -181,7 +132,7 @@ class Engine:
     def istft(self, logmag, phase, frame_off):
         lens = [(frame_off[i + 1] - frame_off[i] - 1) * spec.HOP + spec.WIN if frame_off[i + 1] > frame_off[i] else 0
                 for i in range(len(frame_off) - 1)]
-        ooff = _offsets(lens)
+        ooff = context.offsets(lens)
         out = torch.zeros(ooff[-1], dtype=torch.float32, device=self.device)
         hip.check(self.lib.nhans_istft(self.handle, hip.ptr(logmag), hip.ptr(phase), hip.i64_array(frame_off),
                                        len(frame_off) - 1, hip.i64_array(ooff), hip.ptr(out), self._stream()))
@@ -213,44 +164,14 @@ class Engine:
         """Lists of normalised float32 waveforms (mixtures trimmed) -> per-clip numpy results.  lookahead: L frames,
         0 .. 17 (include/nhans_hip.h, option "lookahead": frame g sees its clip end at g + L + 1) -- what a live stream
         of that look-ahead emits for the same samples; the saturation redo runs with the same L."""
-        if lookahead == spec.LOOKAHEAD:
-            return self._enhance(mixes, ctx_a, ctx_b, want_mixed, taps)
-        spec.check_lookahead(lookahead)
-        self.set_option("lookahead", lookahead)
-        try:
-            return self._enhance(mixes, ctx_a, ctx_b, want_mixed, taps)
-        finally:
-            self.set_option("lookahead", spec.LOOKAHEAD)
+        return self._with_lookahead(lookahead, lambda: self._enhance(mixes, ctx_a, ctx_b, want_mixed, taps))
 
     def _enhance(self, mixes, ctx_a, ctx_b, want_mixed, taps):
         mix_t, mix_off = self._dev(mixes)
         ca_t, ca_off = self._dev(ctx_a)
         cb_t, cb_off = self._dev(ctx_b)
-        res = self.enhance_device(mix_t, mix_off, ca_t, ca_off, cb_t, cb_off, want_mixed, taps)
-        if self.take_status() & hip.STATUS_SATURATED and self.precision == "f16x3":
-            # the split-f16 layout holds |activation * 2^-e| < 65504 and this batch is further from the calibration
-            # than the 2^8 of headroom: redo it on the exact f32 matrix-core path (same library, no CPU involved)
-            # with the tensors' maxima recorded, and raise the exponents so that the batches after it fit
-            warnings.warn("N-HANS f16x3 path: an activation left the f16 range; batch recomputed in f32 MFMA mode "
-                          "and the activation exponents raised")
-            self.set_option("calibrate", 1)
-            try:
-                self.set_precision("f32")
-                res = self.enhance_device(mix_t, mix_off, ca_t, ca_off, cb_t, cb_off, want_mixed, taps)
-                self.take_status()
-            except BaseException:
-                try:
-                    self.set_option("calibrate", 3)      # close the bracket first, then restore the precision
-                finally:
-                    self.set_precision("f16x3")
-                raise
-            try:
-                # (raise-only; maxima that are not finite -- the flag is also raised by a NaN / Inf INPUT -- are skipped)
-                self.set_option("calibrate", 2)
-            except hip.NhansError as err:          # the f32 result stands whatever the exponent update says
-                warnings.warn("N-HANS: activation exponents not updated after the f32 rerun: %s" % err)
-            finally:
-                self.set_precision("f16x3")
+        res = context.redo_saturated_in_f32(
+            self, lambda: self.enhance_device(mix_t, mix_off, ca_t, ca_off, cb_t, cb_off, want_mixed, taps))
         torch.cuda.synchronize(self.device)
         out = {"denoised_wav": [], "mixed_wav": []}
         den = res["denoised_wav"].cpu().numpy()

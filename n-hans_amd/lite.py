@@ -5,14 +5,13 @@ torch alone costs more wall clock than the rest of a one-file call.  Same librar
 engine.Engine.enhance (tests/test_gpu_cold_call.py); everything else -- stage-level entry points, streams, the sharded
 multi-GPU path -- stays on engine.Engine.  No CPU fallback here either: no HIP device, no library -> an error."""
 import ctypes
-import warnings
 
 import numpy as np
 
-from . import blobcache, fold, hip, hiprt, spec
+from . import blobcache, context, fold, hip, hiprt, spec
 
 
-class LiteEngine:
+class LiteEngine(context.Context):
     def __init__(self, kind, weights=None, device=0, blob=None, exponents=None, precision="f16x3"):
         """weights: checkpoint dict (folded here) -- or `blob`: an already folded blob (bytes / uint8 array, e.g. from
         blobcache) with, optionally, the activation exponents a previous context calibrated for it (the calibration
@@ -31,95 +30,33 @@ class LiteEngine:
         hip.check(self.lib.nhans_create_ex(hip.KIND_CODE[kind], arr.ctypes.data_as(ctypes.c_void_p), arr.size, device,
                                            exps, hip.NUM_ACTIVATIONS if exps is not None else 0, ctypes.byref(handle)))
         self.handle = handle
-        self.precision = precision
-        self.set_option("precision", {"f32": 0, "f16x3": 1}[precision])
-
-    def set_option(self, key, value):
-        hip.check(self.lib.nhans_set_option(self.handle, key.encode(), int(value)))
-
-    def activation_exponents(self):
-        e = (ctypes.c_int * hip.NUM_ACTIVATIONS)()
-        hip.check(self.lib.nhans_get_activation_exponents(self.handle, e, hip.NUM_ACTIVATIONS))
-        return list(e)
-
-    def take_status(self):
-        flags = ctypes.c_int(0)
-        hip.check(self.lib.nhans_take_status(self.handle, ctypes.byref(flags), None))
-        return flags.value
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.nhans_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @staticmethod
-    def _flat(arrays):
-        off = [0]
-        for a in arrays:
-            off.append(off[-1] + len(a))
-        flat = np.concatenate([np.asarray(a, dtype=np.float32) for a in arrays]) if arrays else np.zeros(0, np.float32)
-        return np.ascontiguousarray(flat), off
-
-    def _run(self, mix, ca, cb, want_mixed):
-        (mf, moff), (af, aoff), (bf, boff) = self._flat(mix), self._flat(ca), self._flat(cb)
-        n = len(mix)
-        for i in range(n):
-            if int(self.lib.nhans_num_frames(moff[i + 1] - moff[i])) == 0:
-                raise ValueError("mixture clip %d has fewer than %d samples: no STFT frame" % (i, spec.WIN))
-        d_mix, d_ca, d_cb = hiprt.DevBuf.from_array(mf), hiprt.DevBuf.from_array(af), hiprt.DevBuf.from_array(bf)
-        d_den = hiprt.DevBuf(mf.nbytes, zero=True)
-        d_rt = hiprt.DevBuf(mf.nbytes, zero=True) if want_mixed else None
-        hip.check(self.lib.nhans_enhance_clips(
-            self.handle, d_mix.ptr, hip.i64_array(moff), n, d_ca.ptr, hip.i64_array(aoff), d_cb.ptr, hip.i64_array(boff),
-            d_den.ptr, d_rt.ptr if d_rt else None, None, None, None, None, None))
-        status = self.take_status()                       # (waits for the null stream)
-        den = d_den.to_array(np.empty_like(mf))
-        rt = d_rt.to_array(np.empty_like(mf)) if want_mixed else None
-        for b in (d_mix, d_ca, d_cb, d_den, d_rt):
-            if b is not None:
-                b.free()
-        return den, rt, moff, status
+        self.set_precision(precision)
 
     def enhance(self, mixes, ctx_a, ctx_b, want_mixed=True, lookahead=spec.LOOKAHEAD):
         """Lists of normalised float32 waveforms (mixtures trimmed) -> {"denoised_wav": [...], "mixed_wav": [...]}; the same
         saturation fallback as engine.Engine.enhance (the batch redone on the exact-f32 matrix path, exponents raised) and
         the same lookahead (L frames, 0 .. 17; the redo runs with the same L)."""
-        if lookahead == spec.LOOKAHEAD:
-            return self._enhance(mixes, ctx_a, ctx_b, want_mixed)
-        spec.check_lookahead(lookahead)
-        self.set_option("lookahead", lookahead)
-        try:
-            return self._enhance(mixes, ctx_a, ctx_b, want_mixed)
-        finally:
-            self.set_option("lookahead", spec.LOOKAHEAD)
+        return self._with_lookahead(lookahead, lambda: self._enhance(mixes, ctx_a, ctx_b, want_mixed))
 
     def _enhance(self, mixes, ctx_a, ctx_b, want_mixed):
-        den, rt, off, status = self._run(mixes, ctx_a, ctx_b, want_mixed)
-        if status & hip.STATUS_SATURATED and self.precision == "f16x3":
-            warnings.warn("N-HANS f16x3 path: an activation left the f16 range; batch recomputed in f32 MFMA mode "
-                          "and the activation exponents raised")
-            self.set_option("calibrate", 1)
-            try:
-                self.set_option("precision", 0)
-                den, rt, off, _ = self._run(mixes, ctx_a, ctx_b, want_mixed)
-            except BaseException:
-                try:
-                    self.set_option("calibrate", 3)
-                finally:
-                    self.set_option("precision", 1)
-                raise
-            try:
-                self.set_option("calibrate", 2)
-            except hip.NhansError as err:
-                warnings.warn("N-HANS: activation exponents not updated after the f32 rerun: %s" % err)
-            finally:
-                self.set_option("precision", 1)
+        (mf, off), (af, aoff), (bf, boff) = context.flat(mixes), context.flat(ctx_a), context.flat(ctx_b)
+        for i in range(len(mixes)):
+            if int(self.lib.nhans_num_frames(off[i + 1] - off[i])) == 0:
+                raise ValueError("mixture clip %d has fewer than %d samples: no STFT frame" % (i, spec.WIN))
+        mem = context.Mem(self)
+        ins = [mem.up(x) for x in (mf, af, bf)]
+        outs = []                                         # denoised, mixed round trip: those of the attempt that stands
+
+        def launch():
+            outs[:] = [hiprt.DevBuf(mf.nbytes, zero=True), hiprt.DevBuf(mf.nbytes, zero=True) if want_mixed else None]
+            hip.check(self.lib.nhans_enhance_clips(
+                self.handle, mem.p(ins[0]), hip.i64_array(off), len(mixes), mem.p(ins[1]), hip.i64_array(aoff),
+                mem.p(ins[2]), hip.i64_array(boff), mem.p(outs[0]), mem.p(outs[1]), None, None, None, None, None))
+
+        context.redo_saturated_in_f32(self, launch, lambda: mem.free(*outs))     # (take_status waits for the null stream)
+        den = mem.down(outs[0], len(mf))
+        rt = mem.down(outs[1], len(mf)) if want_mixed else None
+        mem.free(*ins, *outs)
         out = {"denoised_wav": [den[off[i]:off[i + 1]] for i in range(len(mixes))], "mixed_wav": []}
         if want_mixed:
             out["mixed_wav"] = [rt[off[i]:off[i + 1]] for i in range(len(mixes))]

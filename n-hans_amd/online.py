@@ -5,11 +5,10 @@ OnlineEnhancer works over engine.Engine (torch device memory, the engine's curre
 (torch-free, hiprt memory, the null stream).  The output contract lives in the header; out_counts() restates it in
 Python so that it can be checked without a device."""
 import ctypes
-import warnings
 
 import numpy as np
 
-from . import hip, spec
+from . import context, hip, spec
 
 LOOKAHEAD = spec.MIX_WIN // 2          # 17 frames
 
@@ -132,28 +131,152 @@ def capture_side(kind, which):
     raise ValueError("which: 'a', 'b', 'neg' or 'pos' (got %r for a %s)" % (which, kind))
 
 
-def _capture_contexts(obj, fn, pairs, normalise, stream):
-    pairs = list(pairs)
-    n = len(pairs)
-    slots = (ctypes.c_int * max(n, 1))(*[int(i) for i, _ in pairs])
-    sides = (ctypes.c_int * max(n, 1))(*[capture_side(obj.eng.kind, w) for _, w in pairs])
-    R = (ctypes.c_int64 * max(n, 1))()
-    hip.check(fn(obj.handle, n, slots, sides, hip.CAPTURE_NORMALISE if normalise else 0, stream, R))
-    return [int(R[k]) for k in range(n)]
+class Slots:
+    """What OnlineEnhancer and live.LiveSession share: S slots that outlive their streams (include/nhans_hip.h, "Slots")
+    behind one C object `handle` over the context `eng`.  C names the object's entry points -- spelt out, the two
+    families are not named alike -- and they are looked up when called: a library from before a feature ($NHANS_LIB)
+    lacks its symbols, and only using the feature is an error."""
+
+    C = {}
+    handle = None
+
+    def _begin(self, engine, S, conditioned):
+        self.eng = engine
+        self.mem = context.Mem(engine)
+        self.lib = hip.load()
+        self.S = int(S)
+        self.handle = None
+        self.pushed = [0] * self.S
+        self.ended = [False] * self.S
+        self.conditioned = [conditioned] * self.S
+        self._prev = None
+        self.lookahead = [LOOKAHEAD] * self.S
+
+    def _c(self, what, *args):
+        return hip.check(getattr(self.lib, self.C[what])(self.handle, *args))
+
+    def _lookaheads(self, lookahead):
+        la = list(lookahead) if hasattr(lookahead, "__len__") else [lookahead] * self.S
+        if len(la) != self.S:
+            raise ValueError("lookahead: one value, or one per slot (%d)" % self.S)
+        for i, L in enumerate(la):
+            if L != LOOKAHEAD:
+                self.set_lookahead(i, L)
+
+    def out_counts(self, counts, end=None):
+        """What a push of counts[i] samples would emit per slot."""
+        out = (ctypes.c_int64 * self.S)()
+        self._c("out_counts", hip.i64_array(counts), context.end_flags(end, self.S), out)
+        return list(out)
+
+    def rewind(self):
+        self._c("rewind")
+        self.pushed, self.ended = self._prev
+
+    def restart(self, i):
+        """Slot i becomes an open stream of 0 samples, in every stage; conditioning is kept."""
+        self._c("restart", int(i))
+        self.pushed[i], self.ended[i] = 0, False
+
+    def set_lookahead(self, i, L):
+        """The look-ahead of slot i, L frames in 0 .. 17: allowed while the slot's stream has no samples yet -- after open
+        or restart(i) --, kept across restarts."""
+        L = spec.check_lookahead(L)
+        self._c("set_lookahead", int(i), L)
+        self.lookahead[i] = L
+
+    def set_context(self, i, ctx_a, ctx_b):
+        """Conditions slot i on two normalised 16 kHz recordings.  Returns R: frames >= R of the slot's 16 kHz stream use
+        the new conditioning (change_bounds(R) for what that means in samples)."""
+        a = np.ascontiguousarray(ctx_a, dtype=np.float32)
+        b = np.ascontiguousarray(ctx_b, dtype=np.float32)
+        da, db = self.mem.up(a), self.mem.up(b)
+        R = ctypes.c_int64(-1)
+        try:
+            self._c("set_context", int(i), self.mem.p(da), len(a), self.mem.p(db), len(b), self.mem.stream(), ctypes.byref(R))
+        finally:
+            self.mem.free(da, db)
+        self.conditioned[i] = True
+        return int(R.value)
+
+    def set_embeddings(self, i, emb_a, emb_b):
+        """The same with two ready [512] rows (Engine.embed; host arrays or, over Engine, device tensors)."""
+        rows, own = [], []
+        R = ctypes.c_int64(-1)
+        try:
+            for e in (emb_a, emb_b):
+                buf, n, ours = self.mem.up_f32(e)
+                if ours:
+                    own.append(buf)
+                if n != spec.EMB:
+                    raise ValueError("set_embeddings: two rows of %d floats" % spec.EMB)
+                rows.append(buf)
+            self._c("set_embeddings", int(i), self.mem.p(rows[0]), self.mem.p(rows[1]), self.mem.stream(), ctypes.byref(R))
+        finally:
+            self.mem.free(*own)       # (what was uploaded here; a caller's tensor stays the caller's)
+        self.conditioned[i] = True
+        return int(R.value)
+
+    # ---- conditioning captured from the slot's own stream -------------------------------------
+    def enable_capture(self):
+        """Every slot gets its 16 kHz sample history (idempotent): pushes from now on feed it."""
+        self._c("capture_enable", self.mem.stream())
+
+    def capture_contexts(self, pairs, normalise=True):
+        """pairs: [(slot, which), ...], which 'a' / 'b' / 'neg' / 'pos' (capture_side).  Each slot's row `which` becomes
+        the embedding of the last CAPTURE_SAMPLES samples of its own 16 kHz stream -- with an incoming rate, of what the
+        converter handed on -- (peak-normalised as apply.normalise does, or as stored); one tower pass for all of them.
+        Returns [R, ...] as set_context does.  NhansError with .code == hip.ESHORT where capture_span is None."""
+        pairs = list(pairs)
+        n = len(pairs)
+        slots = (ctypes.c_int * max(n, 1))(*[int(i) for i, _ in pairs])
+        sides = (ctypes.c_int * max(n, 1))(*[capture_side(self.eng.kind, w) for _, w in pairs])
+        R = (ctypes.c_int64 * max(n, 1))()
+        self._c("capture_context", n, slots, sides, hip.CAPTURE_NORMALISE if normalise else 0, self.mem.stream(), R)
+        return [int(R[k]) for k in range(n)]
+
+    def capture_context(self, i, which, normalise=True):
+        return self.capture_contexts([(i, which)], normalise)[0]
+
+    def embeddings(self, i):
+        """(a, b): slot i's current conditioning rows as two float32[512] arrays -- a learnt noise profile that
+        set_embeddings accepts elsewhere."""
+        rows = self.mem.empty(2 * spec.EMB)
+        try:
+            base = self.mem.p(rows).value
+            self._c("capture_embeddings", int(i), ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * spec.EMB), self.mem.stream())
+            out = np.array(self.mem.down(rows, 2 * spec.EMB), dtype=np.float32)
+        finally:
+            self.mem.free(rows)
+        return out[:spec.EMB].copy(), out[spec.EMB:].copy()
+
+    def _push_checked(self, push, counts, end, outc):
+        """push(): one call of the push entry point, returning the counts it reported.  A push that saturates the f16x3
+        path is undone and redone in f32 (context.redo_saturated_in_f32); then the host's view of the slots moves on."""
+        def run():
+            got = push()
+            self._prev = (list(self.pushed), list(self.ended))
+            return got
+
+        got = context.redo_saturated_in_f32(self.eng, run, lambda: self._c("rewind"))
+        assert got == outc, (got, outc)
+        for i in range(self.S):
+            self.pushed[i] += counts[i]
+            self.ended[i] = self.ended[i] or bool(end is not None and end[i])
+
+    def close(self):
+        if self.handle:
+            getattr(self.lib, self.C["close"])(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
-def _embeddings(mem, fn, handle, i):
-    rows = mem.empty(2 * spec.EMB)
-    try:
-        base = mem.p(rows).value
-        hip.check(fn(handle, int(i), ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * spec.EMB), mem.stream()))
-        out = np.array(mem.down(rows, 2 * spec.EMB), dtype=np.float32)
-    finally:
-        mem.free(rows)
-    return out[:spec.EMB].copy(), out[spec.EMB:].copy()
-
-
-class OnlineEnhancer:
+class OnlineEnhancer(Slots):
     """S live recordings conditioned on ctx_a[i] / ctx_b[i] (normalised float32, >= 32,240 samples each; resnet_block
     argument order as everywhere: denoiser (pos, neg), separator (noise, clean)).
 
@@ -174,26 +297,16 @@ class OnlineEnhancer:
     slot itself has received at 16 kHz (include/nhans_hip.h, "Conditioning captured from a slot's own stream") -- with
     in_rate, from what the incoming converter handed on."""
 
-    def _begin(self, engine, S, want_mixed):
-        self.eng = engine
-        self.lib = hip.load()
-        self.S = S
-        self.want_mixed = bool(want_mixed)
-        self._torch = hasattr(engine, "_stream")
-        self.handle = None
-        self.pushed = [0] * S
-        self.ended = [False] * S
-        self._prev = None
-        self._rs_in = self._rs_out = self._rs_mix = None
-        self.lookahead = [LOOKAHEAD] * S
+    C = dict(restart="nhans_online_restart", rewind="nhans_online_rewind", out_counts="nhans_online_out_counts",
+             set_context="nhans_online_set_context", set_embeddings="nhans_online_set_embeddings",
+             set_lookahead="nhans_online_set_lookahead", capture_enable="nhans_capture_enable",
+             capture_context="nhans_capture_context", capture_embeddings="nhans_capture_embeddings",
+             close="nhans_online_close")
 
-    def _lookaheads(self, lookahead):
-        la = list(lookahead) if hasattr(lookahead, "__len__") else [lookahead] * self.S
-        if len(la) != self.S:
-            raise ValueError("lookahead: one value, or one per slot (%d)" % self.S)
-        for i, L in enumerate(la):
-            if L != LOOKAHEAD:
-                self.set_lookahead(i, L)
+    def _begin(self, engine, S, conditioned, want_mixed):
+        super()._begin(engine, S, conditioned)
+        self.want_mixed = bool(want_mixed)
+        self._rs_in = self._rs_out = self._rs_mix = None
 
     def _rates(self, in_rate, out_rate, peak, in_dtype):
         if in_rate is None and out_rate is None:
@@ -214,16 +327,15 @@ class OnlineEnhancer:
                  lookahead=LOOKAHEAD):
         if len(ctx_a) != len(ctx_b):
             raise ValueError("ctx_a and ctx_b must have one recording per stream")
-        self._begin(engine, len(ctx_a), want_mixed)
-        self.conditioned = [True] * self.S
-        a, aoff = self._flat(ctx_a)
-        b, boff = self._flat(ctx_b)
-        da, db = self._up(a), self._up(b)
+        self._begin(engine, len(ctx_a), True, want_mixed)
+        a, aoff = context.flat(ctx_a)
+        b, boff = context.flat(ctx_b)
+        da, db = self.mem.up(a), self.mem.up(b)
         h = ctypes.c_void_p()
-        hip.check(self.lib.nhans_online_open(engine.handle, self.S, self._p(da), hip.i64_array(aoff), self._p(db),
-                                             hip.i64_array(boff), int(self.want_mixed), self._stream(), ctypes.byref(h)))
+        hip.check(self.lib.nhans_online_open(engine.handle, self.S, self.mem.p(da), hip.i64_array(aoff), self.mem.p(db),
+                                             hip.i64_array(boff), int(self.want_mixed), self.mem.stream(), ctypes.byref(h)))
         self.handle = h
-        self._free(da, db)
+        self.mem.free(da, db)
         self._rates(in_rate, out_rate, peak, in_dtype)
         self._lookaheads(lookahead)
 
@@ -232,162 +344,24 @@ class OnlineEnhancer:
                    lookahead=LOOKAHEAD):
         """An object of nslots unconditioned slots (nhans_online_open_slots): no tower runs until a set_context."""
         self = cls.__new__(cls)
-        self._begin(engine, int(nslots), want_mixed)
-        self.conditioned = [False] * self.S
+        self._begin(engine, nslots, False, want_mixed)
         h = ctypes.c_void_p()
-        hip.check(self.lib.nhans_online_open_slots(engine.handle, self.S, int(self.want_mixed), self._stream(), ctypes.byref(h)))
+        hip.check(self.lib.nhans_online_open_slots(engine.handle, self.S, int(self.want_mixed), self.mem.stream(),
+                                                   ctypes.byref(h)))
         self.handle = h
         self._rates(in_rate, out_rate, peak, in_dtype)
         self._lookaheads(lookahead)
         return self
 
-    # ---- device memory of either engine --------------------------------------------------------
-    @staticmethod
-    def _flat(arrays):
-        off = [0]
-        for x in arrays:
-            off.append(off[-1] + len(x))
-        flat = np.concatenate([np.asarray(x, dtype=np.float32) for x in arrays]) if len(arrays) else np.zeros(0, np.float32)
-        return np.ascontiguousarray(flat, dtype=np.float32), off
-
-    def _stream(self):
-        return self.eng._stream() if self._torch else None
-
-    def _up(self, arr):
-        if self._torch:
-            import torch
-            return torch.from_numpy(arr).to(self.eng.device)
-        from . import hiprt
-        return hiprt.DevBuf.from_array(arr)
-
-    def _empty(self, n):
-        if self._torch:
-            import torch
-            return torch.empty(max(n, 1), dtype=torch.float32, device=self.eng.device)
-        from . import hiprt
-        return hiprt.DevBuf(4 * max(n, 1))
-
-    def _p(self, buf):
-        return hip.ptr(buf) if self._torch else buf.ptr
-
-    def _down(self, buf, n):
-        if self._torch:
-            return buf[:n].cpu().numpy()
-        return buf.to_array(np.empty(n, np.float32)) if n else np.zeros(0, np.float32)
-
-    def _free(self, *bufs):
-        if not self._torch:
-            for b in bufs:
-                if b is not None:
-                    b.free()
-
-    def _set_precision(self, p):
-        if hasattr(self.eng, "set_precision"):
-            self.eng.set_precision(p)
-        else:
-            self.eng.set_option("precision", {"f32": 0, "f16x3": 1}[p])
-
-    # ---- the C ABI ---------------------------------------------------------------------------
-    def out_counts(self, counts, end=None):
-        """nhans_online_out_counts: what a push of counts[i] samples would emit per stream."""
-        out = (ctypes.c_int64 * self.S)()
-        endv = (ctypes.c_int * self.S)(*[int(bool(e)) for e in end]) if end is not None else None
-        hip.check(self.lib.nhans_online_out_counts(self.handle, hip.i64_array(counts), endv, out))
-        return list(out)
-
-    def rewind(self):
-        hip.check(self.lib.nhans_online_rewind(self.handle))
-        self.pushed, self.ended = self._prev
-
     def restart(self, i):
-        """Slot i becomes an open stream of 0 samples (nhans_online_restart); conditioning is kept."""
-        hip.check(self.lib.nhans_online_restart(self.handle, int(i)))
-        self.pushed[i], self.ended[i] = 0, False
+        super().restart(i)
         for rs in (self._rs_in, self._rs_out, self._rs_mix):
             if rs is not None:
                 rs.restart(i)
 
-    def set_lookahead(self, i, L):
-        """The look-ahead of slot i, L frames in 0 .. 17 (nhans_online_set_lookahead): allowed while the slot's stream has
-        no samples yet -- after open or restart(i) --, kept across restarts."""
-        L = spec.check_lookahead(L)
-        hip.check(self.lib.nhans_online_set_lookahead(self.handle, int(i), L))
-        self.lookahead[i] = L
-
     def first_new_frame(self, i):
         """R of slot i: the frames of its stream already computed, which a change of conditioning leaves as they are."""
         return ready_frames(self.pushed[i], self.ended[i], self.lookahead[i])
-
-    def set_context(self, i, ctx_a, ctx_b):
-        """Conditions slot i on two recordings (nhans_online_set_context).  Returns R: frames >= R of the slot's stream
-        use the new conditioning (change_bounds(R) for what that means in samples)."""
-        a = np.ascontiguousarray(ctx_a, dtype=np.float32)
-        b = np.ascontiguousarray(ctx_b, dtype=np.float32)
-        da, db = self._up(a), self._up(b)
-        R = ctypes.c_int64(-1)
-        try:
-            hip.check(self.lib.nhans_online_set_context(self.handle, int(i), self._p(da), len(a), self._p(db), len(b),
-                                                        self._stream(), ctypes.byref(R)))
-        finally:
-            self._free(da, db)
-        self.conditioned[i] = True
-        return int(R.value)
-
-    def set_embeddings(self, i, emb_a, emb_b):
-        """The same with two ready [512] rows (Engine.embed; host arrays or, over Engine, device tensors)."""
-        rows = []
-        for e in (emb_a, emb_b):
-            if self._torch and hasattr(e, "data_ptr"):
-                import torch
-                e = e.detach().to(device=self.eng.device, dtype=torch.float32).contiguous().reshape(-1)
-            else:
-                e = self._up(np.ascontiguousarray(e, dtype=np.float32).reshape(-1))
-            rows.append(e)
-        n = [r.numel() if hasattr(r, "numel") else r.nbytes // 4 for r in rows]
-        if n != [spec.EMB, spec.EMB]:
-            self._free(*[r for r in rows if not hasattr(r, "numel")])
-            raise ValueError("set_embeddings: two rows of %d floats" % spec.EMB)
-        R = ctypes.c_int64(-1)
-        try:
-            hip.check(self.lib.nhans_online_set_embeddings(self.handle, int(i), self._p(rows[0]), self._p(rows[1]),
-                                                           self._stream(), ctypes.byref(R)))
-        finally:
-            self._free(*[r for r in rows if not hasattr(r, "numel")])
-        self.conditioned[i] = True
-        return int(R.value)
-
-    # ---- conditioning captured from the slot's own stream -------------------------------------
-    def enable_capture(self):
-        """Every slot gets its sample history (nhans_capture_enable; idempotent): pushes from now on feed it."""
-        hip.check(self.lib.nhans_capture_enable(self.handle, self._stream()))
-
-    def capture_contexts(self, pairs, normalise=True):
-        """pairs: [(slot, which), ...], which 'a' / 'b' / 'neg' / 'pos' (capture_side).  Each slot's row `which` becomes
-        the embedding of the last CAPTURE_SAMPLES samples of its own stream (peak-normalised as apply.normalise does, or as
-        stored); one tower pass for all of them.  Returns [R, ...] as set_context does.  NhansError with .code ==
-        hip.ESHORT where capture_span is None."""
-        return _capture_contexts(self, self.lib.nhans_capture_context, pairs, normalise, self._stream())
-
-    def capture_context(self, i, which, normalise=True):
-        return self.capture_contexts([(i, which)], normalise)[0]
-
-    def embeddings(self, i):
-        """(a, b): slot i's current conditioning rows as two float32[512] arrays (nhans_capture_embeddings) -- a learnt
-        noise profile that set_embeddings accepts elsewhere."""
-        from . import resample
-        return _embeddings(resample._Mem(self.eng), self.lib.nhans_capture_embeddings, self.handle, i)
-
-    def _push_once(self, din, inoff, endv, counts):
-        ooff = [0]
-        for n in counts:
-            ooff.append(ooff[-1] + n)
-        dden = self._empty(ooff[-1])
-        dmix = self._empty(ooff[-1]) if self.want_mixed else None
-        got = (ctypes.c_int64 * self.S)()
-        hip.check(self.lib.nhans_online_push(self.handle, self._p(din), hip.i64_array(inoff), endv, self._p(dden),
-                                             self._p(dmix) if dmix is not None else None, hip.i64_array(ooff), got,
-                                             self._stream()))
-        return dden, dmix, ooff, list(got)
 
     def push(self, chunks, end=None):
         """chunks: one 1-D float32 array per stream (may be empty); end[i]: stream i ends after its chunk.  Returns
@@ -409,42 +383,24 @@ class OnlineEnhancer:
     def _push16(self, chunks, end=None):
         if len(chunks) != self.S:
             raise ValueError("push: one chunk per stream (%d)" % self.S)
-        flat, inoff = self._flat(chunks)
+        x, inoff = context.flat(chunks)
         counts = [inoff[i + 1] - inoff[i] for i in range(self.S)]
-        endv = (ctypes.c_int * self.S)(*[int(bool(e)) for e in end]) if end is not None else None
         outc = self.out_counts(counts, end)
-        din = self._up(flat)
-        dden, dmix, ooff, got = self._push_once(din, inoff, endv, outc)
-        self._prev = (list(self.pushed), list(self.ended))
-        if self.eng.take_status() & hip.STATUS_SATURATED and self.eng.precision == "f16x3":
-            warnings.warn("N-HANS f16x3 path: an activation left the f16 range; batch recomputed in f32 MFMA mode "
-                          "and the activation exponents raised")
-            hip.check(self.lib.nhans_online_rewind(self.handle))
-            self._free(dden, dmix)
-            self.eng.set_option("calibrate", 1)
-            try:
-                self._set_precision("f32")
-                dden, dmix, ooff, got = self._push_once(din, inoff, endv, outc)
-                self.eng.take_status()
-            except BaseException:
-                try:
-                    self.eng.set_option("calibrate", 3)
-                finally:
-                    self._set_precision("f16x3")
-                raise
-            try:
-                self.eng.set_option("calibrate", 2)
-            except hip.NhansError as err:
-                warnings.warn("N-HANS: activation exponents not updated after the f32 rerun: %s" % err)
-            finally:
-                self._set_precision("f16x3")
-        assert got == outc, (got, outc)
-        den = self._down(dden, ooff[-1])
-        mix = self._down(dmix, ooff[-1]) if dmix is not None else None
-        self._free(din, dden, dmix)
-        for i in range(self.S):
-            self.pushed[i] += counts[i]
-            self.ended[i] = self.ended[i] or bool(end is not None and end[i])
+        ooff = context.offsets(outc)
+        mem = self.mem
+        din, dden = mem.up(x), mem.empty(ooff[-1])
+        dmix = mem.empty(ooff[-1]) if self.want_mixed else None
+
+        def push():
+            got = (ctypes.c_int64 * self.S)()
+            hip.check(self.lib.nhans_online_push(self.handle, mem.p(din), hip.i64_array(inoff), context.end_flags(end, self.S),
+                                                 mem.p(dden), mem.p(dmix), hip.i64_array(ooff), got, mem.stream()))
+            return list(got)
+
+        self._push_checked(push, counts, end, outc)
+        den = mem.down(dden, ooff[-1])
+        mix = mem.down(dmix, ooff[-1]) if dmix is not None else None
+        mem.free(din, dden, dmix)
         return [(den[ooff[i]:ooff[i + 1]], mix[ooff[i]:ooff[i + 1]] if mix is not None else None) for i in range(self.S)]
 
     def close(self):
@@ -453,12 +409,4 @@ class OnlineEnhancer:
             if rs is not None:
                 rs.close()
                 setattr(self, name, None)
-        if getattr(self, "handle", None):
-            self.lib.nhans_online_close(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()

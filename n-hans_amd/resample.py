@@ -11,7 +11,7 @@ from math import gcd
 
 import numpy as np
 
-from . import hip
+from . import context, hip
 
 BASE = 16000
 RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000)
@@ -74,53 +74,6 @@ def _format(dtype):
     raise ValueError("samples must be int16 or float32, not %s" % dtype)
 
 
-class _Mem:
-    """Device memory of either engine."""
-
-    def __init__(self, engine):
-        self.eng = engine
-        self.torch = hasattr(engine, "_stream")
-
-    def stream(self):
-        return self.eng._stream() if self.torch else None
-
-    def up(self, arr):
-        if self.torch:
-            import torch
-            return torch.from_numpy(arr).to(self.eng.device) if arr.size else torch.empty(1, dtype=torch.float32, device=self.eng.device)
-        from . import hiprt
-        return hiprt.DevBuf.from_array(arr)
-
-    def empty(self, n):
-        if self.torch:
-            import torch
-            return torch.empty(max(n, 1), dtype=torch.float32, device=self.eng.device)
-        from . import hiprt
-        return hiprt.DevBuf(4 * max(n, 1))
-
-    def p(self, buf):
-        return hip.ptr(buf) if self.torch else buf.ptr
-
-    def down(self, buf, n):
-        if self.torch:
-            return buf[:n].cpu().numpy()
-        return buf.to_array(np.empty(n, np.float32)) if n else np.zeros(0, np.float32)
-
-    def free(self, *bufs):
-        if not self.torch:
-            for b in bufs:
-                if b is not None:
-                    b.free()
-
-
-def _flat(arrays, dtype):
-    off = [0]
-    for x in arrays:
-        off.append(off[-1] + len(x))
-    flat = np.concatenate([np.asarray(x, dtype=dtype) for x in arrays]) if len(arrays) else np.zeros(0, dtype)
-    return np.ascontiguousarray(flat, dtype=dtype), off
-
-
 def _common_dtype(arrays, dtype=None):
     if dtype is not None:
         return np.dtype(dtype)
@@ -133,12 +86,10 @@ def resample(engine, clips, rate_in, rate_out, quantise=False):
     else float32) -> list of float32 arrays of out_count(len) samples.  quantise: outputs on the int16 grid."""
     geometry(rate_in, rate_out)
     dtype = _common_dtype(clips)
-    flat, ioff = _flat(clips, dtype)
-    ooff = [0]
-    for i in range(len(clips)):
-        ooff.append(ooff[-1] + out_count(ioff[i + 1] - ioff[i], rate_in, rate_out))
-    mem = _Mem(engine)
-    din, dout = mem.up(flat), mem.empty(ooff[-1])
+    x, ioff = context.flat(clips, dtype)
+    ooff = context.offsets(out_count(ioff[i + 1] - ioff[i], rate_in, rate_out) for i in range(len(clips)))
+    mem = context.Mem(engine)
+    din, dout = mem.up(x), mem.empty(ooff[-1])
     try:
         hip.check(hip.load().nhans_resample(engine.handle, mem.p(din), _format(dtype), hip.i64_array(ioff), len(clips),
                                             int(rate_in), int(rate_out), hip.RESAMPLE_QUANTISE if quantise else 0,
@@ -152,9 +103,9 @@ def resample(engine, clips, rate_in, rate_out, quantise=False):
 def peak_normalise(engine, clips, wrap_int16=False):
     """x / (max|x| + 1e-6) per clip in float64 -> float32 on the device: apply.normalise bit for bit.  wrap_int16: the
     peak search takes |-32768| as -32768, as np.abs of an int16 array does."""
-    flat, off = _flat(clips, np.float32)
-    mem = _Mem(engine)
-    d = mem.up(flat)
+    x, off = context.flat(clips)
+    mem = context.Mem(engine)
+    d = mem.up(x)
     try:
         hip.check(hip.load().nhans_peak_normalise(engine.handle, mem.p(d), hip.i64_array(off), len(clips),
                                                   hip.NORMALISE_WRAP_INT16 if wrap_int16 else 0, mem.p(d), mem.stream()))
@@ -191,7 +142,7 @@ def front_end(engine, samples, rate, base=BASE):
     planes = decode_pcm(samples)
     C, n = planes.shape
     no = out_count(n, rate, base)
-    mem = _Mem(engine)
+    mem = context.Mem(engine)
     lib = hip.load()
     din, dout = mem.up(planes.reshape(-1)), mem.empty(C * no)
     try:
@@ -214,7 +165,7 @@ class Resampler:
 
     def __init__(self, engine, nstreams, rate_in, rate_out, dtype=np.float32, quantise=False, peak=None):
         geometry(rate_in, rate_out)
-        self.mem = _Mem(engine)
+        self.mem = context.Mem(engine)
         self.lib = hip.load()
         self.S = int(nstreams)
         self.rate_in, self.rate_out = int(rate_in), int(rate_out)
@@ -232,12 +183,9 @@ class Resampler:
     def set_peak(self, peak):
         hip.check(self.lib.nhans_resampler_set_peak(self.handle, float(peak)))
 
-    def _endv(self, end):
-        return (ctypes.c_int * self.S)(*[int(bool(e)) for e in end]) if end is not None else None
-
     def out_counts(self, counts, end=None):
         out = (ctypes.c_int64 * self.S)()
-        hip.check(self.lib.nhans_resampler_out_counts(self.handle, hip.i64_array(counts), self._endv(end), out))
+        hip.check(self.lib.nhans_resampler_out_counts(self.handle, hip.i64_array(counts), context.end_flags(end, self.S), out))
         return list(out)
 
     def restart(self, i):
@@ -249,16 +197,14 @@ class Resampler:
         samples of every stream that became final."""
         if len(chunks) != self.S:
             raise ValueError("push: one chunk per stream (%d)" % self.S)
-        flat, ioff = _flat(chunks, self.dtype)
+        x, ioff = context.flat(chunks, self.dtype)
         counts = [ioff[i + 1] - ioff[i] for i in range(self.S)]
         outc = self.out_counts(counts, end)
-        ooff = [0]
-        for n in outc:
-            ooff.append(ooff[-1] + n)
-        din, dout = self.mem.up(flat), self.mem.empty(ooff[-1])
+        ooff = context.offsets(outc)
+        din, dout = self.mem.up(x), self.mem.empty(ooff[-1])
         got = (ctypes.c_int64 * self.S)()
         try:
-            hip.check(self.lib.nhans_resampler_push(self.handle, self.mem.p(din), hip.i64_array(ioff), self._endv(end),
+            hip.check(self.lib.nhans_resampler_push(self.handle, self.mem.p(din), hip.i64_array(ioff), context.end_flags(end, self.S),
                                                     self.mem.p(dout), hip.i64_array(ooff), got, self.mem.stream()))
             out = self.mem.down(dout, ooff[-1])
         finally:

@@ -310,7 +310,7 @@ def test_slot_errors_come_back_as_codes_and_change_nothing(lib_built, weights_de
     x = _stream(951, _samples(64))
     ref = _offline(e, x, ca, cb)[0]
     enh = online.OnlineEnhancer.open_slots(e, 2)
-    dev = enh._up(np.concatenate([ca2, cb2]))
+    dev = enh.mem.up(np.concatenate([ca2, cb2]))
     pa = ctypes.c_void_p(dev.data_ptr())
     pb = ctypes.c_void_p(dev.data_ptr() + 4 * len(ca2))
     R = ctypes.c_int64(-7)

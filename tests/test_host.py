@@ -797,10 +797,11 @@ def test_blob_cache_round_trip_and_staleness(tmp_path, monkeypatch):
 
 
 def test_the_command_line_modules_do_not_import_torch():
-    """lite.py / hiprt.py / blobcache.py / apply.py must stay importable without PyTorch: the one-file command line never
-    pays for `import torch` (checked end to end on the GPU box: tests/test_gpu_cold_call.py)."""
+    """lite.py / context.py / hiprt.py / blobcache.py / apply.py must stay importable without PyTorch: the one-file command
+    line never pays for `import torch` (checked end to end on the GPU box: tests/test_gpu_cold_call.py)."""
     import subprocess
-    code = ("import sys; sys.path.insert(0, %r); import nhans_amd; from nhans_amd import apply, blobcache, hiprt, lite; "
+    code = ("import sys; sys.path.insert(0, %r); import nhans_amd; "
+            "from nhans_amd import apply, blobcache, context, hiprt, lite; "
             "assert 'torch' not in sys.modules, 'torch imported'; print('ok')" % ROOT)
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.strip() == "ok", out.stderr
