@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <string>
 #include <vector>
@@ -1465,6 +1466,27 @@ int nhans_profile_json(nhans_ctx* c, char* buf, size_t buflen) {
 // no row below T, so its first push reads nothing of slot `cur` (every run taken from the state is empty) and writes the
 // other slot from the push alone.  The same holds for the slots of nhans_online_open_slots, whose state is never filled.
 namespace {
+int slot_check(int S, int slot, const char* fn) {
+    if (slot < 0 || slot >= S)
+        return fail(NHANS_EINVAL, std::string(fn) + ": slot " + std::to_string(slot) + " outside [0, " + std::to_string(S) + ")");
+    return NHANS_OK;
+}
+
+// What a push of cnt samples (en: and the end) to stream i may not be, for the three streaming objects and their
+// out_counts: `noun` is what the object calls a stream ("stream" / "slot"), `ended` the stream's flag, `uncond` non-null
+// where the slot has no conditioning and the call refuses samples for such a slot (it names the calls that set one),
+// max_cnt the most samples one push of the object takes.
+constexpr int64_t kMaxResampleClip = ((int64_t)1 << 31) - 1, kNoPushCap = std::numeric_limits<int64_t>::max();
+int push_check(const char* fn, const char* noun, int i, int64_t cnt, bool en, bool ended, const char* uncond, int64_t max_cnt) {
+    const std::string who = std::string(fn) + ": " + noun + " " + std::to_string(i);
+    if (cnt < 0) return fail(NHANS_EINVAL, who + " has a negative sample count");
+    if (ended && (cnt > 0 || en)) return fail(NHANS_EINVAL, who + " has ended");
+    if (uncond && (cnt > 0 || en))
+        return fail(NHANS_EINVAL, std::string(fn) + ": slot " + std::to_string(i) + " has no conditioning yet (" + uncond + ")");
+    if (cnt > max_cnt) return fail(NHANS_EINVAL, std::string(fn) + ": push too large for one call (split it)");
+    return NHANS_OK;
+}
+
 constexpr int kOnRows = 2 * kCenter + kIstftHopsPerBlock - 14;  // 42 >= 17 + 24
 constexpr int kOnDenRows = kIstftHopsPerBlock + 2;              // 24
 constexpr size_t kOnSamp = 0, kOnLm = kWin, kOnPh = kOnLm + (size_t)kOnRows * kBins, kOnDen = kOnPh + (size_t)kOnRows * kBins;
@@ -1508,6 +1530,20 @@ struct nhans_online {
 };
 
 namespace {
+
+// final samples a push of cnt samples (en: and the end) to stream i makes
+int64_t online_emit_count(const nhans_online* o, int i, int64_t cnt, bool en) {
+    const OnStream& q = o->st[i];
+    return on_emitted(nhans_num_frames(q.N + cnt), q.ended || en, o->la[i]) - on_emitted(q.T, q.ended, o->la[i]);
+}
+
+// The last push undone (nhans_online_rewind, and a live push whose later stage did not go out).  The rings keep what the
+// undone push wrote: vlo moved to max(vlo, N - 32,240) when its copies went out and stays.
+void online_undo(nhans_online* o) {
+    o->st = o->prev;
+    o->cur = 1 - o->cur;
+    o->can_rewind = false;
+}
 
 // The object and its device memory; on failure nothing is left allocated.
 int online_alloc(nhans_ctx* c, int S, int want_mixed, bool conditioned, const char* fn, nhans_online** out) {
@@ -1577,12 +1613,6 @@ void online_restart_slot(nhans_online* o, int slot) {
     o->can_rewind = false;
 }
 
-int online_slot_check(const nhans_online* o, int slot, const char* fn) {
-    if (slot < 0 || slot >= o->S)
-        return fail(NHANS_EINVAL, std::string(fn) + ": slot " + std::to_string(slot) + " outside [0, " + std::to_string(o->S) + ")");
-    return NHANS_OK;
-}
-
 // Rows `slot` (a) and S + `slot` (b) of the embeddings <- two [512] device rows, ordered on s after whatever made them.
 // Frames already computed keep the conditioning they were computed with: *first_frame is the first that will not.
 int online_set_rows(nhans_online* o, int slot, const float* row_a, const float* row_b, hipStream_t s, int64_t* first_frame) {
@@ -1597,7 +1627,7 @@ int online_set_rows(nhans_online* o, int slot, const float* row_a, const float* 
 int online_set_context_body(nhans_online* o, int slot, const float* ca, int64_t na, const float* cbw, int64_t nb_,
                             hipStream_t s, int64_t* first_frame) {
     nhans_ctx* c = o->c;
-    int rc = online_slot_check(o, slot, "nhans_online_set_context"); if (rc) return rc;
+    int rc = slot_check(o->S, slot, "nhans_online_set_context"); if (rc) return rc;
     if (!ca || !cbw) return fail(NHANS_EINVAL, "nhans_online_set_context: null argument");
     if (na < 0 || nb_ < 0) return fail(NHANS_EINVAL, "nhans_online_set_context: negative sample count");
     const int64_t aoff[2] = {0, na}, boff[2] = {0, nb_};
@@ -1621,7 +1651,7 @@ int online_set_context_body(nhans_online* o, int slot, const float* ca, int64_t 
 }
 
 int online_set_embeddings_body(nhans_online* o, int slot, const float* ea, const float* eb, hipStream_t s, int64_t* first_frame) {
-    const int rc = online_slot_check(o, slot, "nhans_online_set_embeddings"); if (rc) return rc;
+    const int rc = slot_check(o->S, slot, "nhans_online_set_embeddings"); if (rc) return rc;
     if (!ea || !eb) return fail(NHANS_EINVAL, "nhans_online_set_embeddings: null argument");
     return online_set_rows(o, slot, ea, eb, s, first_frame);
 }
@@ -1640,7 +1670,7 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
     const int S = o->S;
     if (!inoff || !outoff || !counts) return fail(NHANS_EINVAL, "null argument");
     struct Plan {
-        int64_t cnt, Nn, Tn, Ro, Rn, Po, Pn, lo, s0, Pend, Eo, En, nsyn;
+        int64_t cnt, Nn, Tn, Ro, Rn, Po, Pn, lo, s0, Pend, E, nsyn;
         bool en;
     };
     std::vector<Plan> pl(S);
@@ -1649,13 +1679,10 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
         const OnStream& q = o->st[i];
         Plan& p = pl[i];
         p.cnt = inoff[i + 1] - inoff[i];
-        if (p.cnt < 0) return fail(NHANS_EINVAL, "nhans_online_push: stream " + std::to_string(i) + " has a negative sample count");
         p.en = end && end[i];
-        if (q.ended && (p.cnt > 0 || p.en))
-            return fail(NHANS_EINVAL, "nhans_online_push: stream " + std::to_string(i) + " has ended");
-        if (!o->cond[i] && (p.cnt > 0 || p.en))
-            return fail(NHANS_EINVAL, "nhans_online_push: slot " + std::to_string(i) + " has no conditioning yet " +
-                                      "(nhans_online_set_context / nhans_online_set_embeddings)");
+        const int rc = push_check("nhans_online_push", "stream", i, p.cnt, p.en, q.ended,
+                                  o->cond[i] ? nullptr : "nhans_online_set_context / nhans_online_set_embeddings", kNoPushCap);
+        if (rc) return rc;
         p.Nn = q.N + p.cnt;
         p.Tn = nhans_num_frames(p.Nn);
         if (p.Tn > kMaxFramesPerClip)
@@ -1667,15 +1694,14 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
         p.lo = on_lo(p.Ro, p.Po);
         p.s0 = on_s0(p.Po);
         p.Pend = p.Pn;
-        p.Eo = on_emitted(q.T, q.ended, L);
-        p.En = on_emitted(p.Tn, p.en || q.ended, L);
-        p.nsyn = p.En > p.Eo ? p.Pend - p.s0 : 0;
-        if (outoff[i + 1] - outoff[i] < p.En - p.Eo)
+        p.E = online_emit_count(o, i, p.cnt, p.en);
+        p.nsyn = p.E > 0 ? p.Pend - p.s0 : 0;
+        if (outoff[i + 1] - outoff[i] < p.E)
             return fail(NHANS_EINVAL, "nhans_online_push: output room of stream " + std::to_string(i) + " is " +
-                                      std::to_string(outoff[i + 1] - outoff[i]) + " samples, " + std::to_string(p.En - p.Eo) +
+                                      std::to_string(outoff[i + 1] - outoff[i]) + " samples, " + std::to_string(p.E) +
                                       " needed (nhans_online_out_counts)");
         tot_in += p.cnt;
-        tot_out += p.En - p.Eo;
+        tot_out += p.E;
     }
     if (tot_in > 0 && !in) return fail(NHANS_EINVAL, "null argument: in_dev");
     if (tot_out > 0 && (!den_out || (o->mixed && !mix_out))) return fail(NHANS_EINVAL, "null argument: output buffer");
@@ -1807,10 +1833,10 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
     // emit
     for (int i = 0; i < S; ++i) {
         const Plan& p = pl[i];
-        if (p.En <= p.Eo) continue;
+        if (p.E <= 0) continue;
         const int64_t skip = (int64_t)kHop * (p.Po - p.s0);
-        add(tden + ooff[i] + skip, den_out + outoff[i], p.En - p.Eo);
-        if (o->mixed) add(tmix + ooff[i] + skip, mix_out + outoff[i], p.En - p.Eo);
+        add(tden + ooff[i] + skip, den_out + outoff[i], p.E);
+        if (o->mixed) add(tmix + ooff[i] + skip, mix_out + outoff[i], p.E);
     }
     bounds.push_back((int)runs.size());
     if (runs.size() > nrun_cap) return fail(NHANS_EINVAL, "nhans_online_push: internal run bound");
@@ -1862,7 +1888,7 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
     o->prev = o->st;
     for (int i = 0; i < S; ++i) {
         OnStream& q = o->st[i];
-        counts[i] = pl[i].En - pl[i].Eo;
+        counts[i] = pl[i].E;
         q.N = pl[i].Nn; q.T = pl[i].Tn; q.ended = q.ended || pl[i].en;
     }
     o->cur = nxt;
@@ -1889,7 +1915,7 @@ int nhans_online_open_slots(nhans_ctx* c, int nslots, int want_mixed, void* stre
 
 int nhans_online_restart(nhans_online* o, int slot) {
     if (!o) return fail(NHANS_EINVAL, "nhans_online_restart: null object");
-    const int rc = online_slot_check(o, slot, "nhans_online_restart"); if (rc) return rc;
+    const int rc = slot_check(o->S, slot, "nhans_online_restart"); if (rc) return rc;
     online_restart_slot(o, slot);
     return NHANS_OK;
 }
@@ -1921,23 +1947,16 @@ int nhans_online_push(nhans_online* o, const float* in, const int64_t* inoff, co
 int nhans_online_out_counts(const nhans_online* o, const int64_t* in_counts, const int* end, int64_t* counts) {
     if (!o || !in_counts || !counts) return fail(NHANS_EINVAL, "null argument");
     for (int i = 0; i < o->S; ++i) {
-        const OnStream& q = o->st[i];
-        const bool en = end && end[i];
-        if (in_counts[i] < 0) return fail(NHANS_EINVAL, "nhans_online_out_counts: stream " + std::to_string(i) + " has a negative sample count");
-        if (q.ended && (in_counts[i] > 0 || en))
-            return fail(NHANS_EINVAL, "nhans_online_out_counts: stream " + std::to_string(i) + " has ended");
+        const int rc = push_check("nhans_online_out_counts", "stream", i, in_counts[i], end && end[i], o->st[i].ended, nullptr, kNoPushCap);
+        if (rc) return rc;
     }
-    for (int i = 0; i < o->S; ++i) {
-        const OnStream& q = o->st[i];
-        const bool en = q.ended || (end && end[i]);
-        counts[i] = on_emitted(nhans_num_frames(q.N + in_counts[i]), en, o->la[i]) - on_emitted(q.T, q.ended, o->la[i]);
-    }
+    for (int i = 0; i < o->S; ++i) counts[i] = online_emit_count(o, i, in_counts[i], end && end[i]);
     return NHANS_OK;
 }
 
 int nhans_online_set_lookahead(nhans_online* o, int slot, int lookahead) {
     if (!o) return fail(NHANS_EINVAL, "nhans_online_set_lookahead: null object");
-    const int rc = online_slot_check(o, slot, "nhans_online_set_lookahead"); if (rc) return rc;
+    const int rc = slot_check(o->S, slot, "nhans_online_set_lookahead"); if (rc) return rc;
     if (lookahead < 0 || lookahead > kCenter)
         return fail(NHANS_EINVAL, "nhans_online_set_lookahead: lookahead must be in [0, " + std::to_string(kCenter) + "] frames");
     if (o->st[slot].N != 0 || o->st[slot].ended)
@@ -1951,10 +1970,7 @@ int nhans_online_set_lookahead(nhans_online* o, int slot, int lookahead) {
 int nhans_online_rewind(nhans_online* o) {
     if (!o) return fail(NHANS_EINVAL, "null object");
     if (!o->can_rewind) return fail(NHANS_EINVAL, "nhans_online_rewind: no push to undo (one rewind per push)");
-    // (the rings keep what the undone push wrote: vlo moved to max(vlo, N - 32,240) when its copies went out and stays)
-    o->st = o->prev;
-    o->cur = 1 - o->cur;
-    o->can_rewind = false;
+    online_undo(o);
     return NHANS_OK;
 }
 
@@ -2003,7 +2019,7 @@ int capture_context_body(nhans_online* o, const char* fn_, int n, const int* slo
     if (flags & ~NHANS_CAPTURE_NORMALISE) return fail(NHANS_EINVAL, fn + ": unknown flag");
     std::vector<char> seen((size_t)2 * o->S, 0);
     for (int k = 0; k < n; ++k) {
-        const int rc = online_slot_check(o, slots[k], fn_); if (rc) return rc;
+        const int rc = slot_check(o->S, slots[k], fn_); if (rc) return rc;
         if (which[k] != NHANS_CAPTURE_A && which[k] != NHANS_CAPTURE_B)
             return fail(NHANS_EINVAL, fn + ": entry " + std::to_string(k) + ": which must be NHANS_CAPTURE_A or NHANS_CAPTURE_B");
         char& m = seen[(size_t)which[k] * o->S + slots[k]];
@@ -2064,7 +2080,7 @@ int capture_context_body(nhans_online* o, const char* fn_, int n, const int* slo
 }
 
 int capture_embeddings_body(const nhans_online* o, const char* fn, int slot, float* ea, float* eb, hipStream_t s) {
-    const int rc = online_slot_check(o, slot, fn); if (rc) return rc;
+    const int rc = slot_check(o->S, slot, fn); if (rc) return rc;
     if (ea) HIP_TRY(hipMemcpyAsync(ea, o->emb + (size_t)slot * kEmb, kEmb * 4, hipMemcpyDeviceToDevice, s));
     if (eb) HIP_TRY(hipMemcpyAsync(eb, o->emb + (size_t)(o->S + slot) * kEmb, kEmb * 4, hipMemcpyDeviceToDevice, s));
     return NHANS_OK;
@@ -2111,21 +2127,6 @@ int nhans_capture_embeddings(const nhans_online* o, int slot, float* ea, float* 
 }  // extern "C"
 
 // ---- sample-rate conversion and the file front end (include/nhans_hip.h: nhans_resample*, nhans_peak_normalise) --------
-struct nhans_resampler {
-    nhans_ctx* c = nullptr;
-    int device = 0, S = 0, in_format = 0, flags = 0;
-    const ResampleFilter* f = nullptr;
-    const float* tab = nullptr;
-    double denom = 0.0;             // nhans_resampler_set_peak: peak + 1e-6; 0 = outputs as they are
-    // [2][S][J]: the J samples before each stream's next one; cur[i] = the half that holds them.  A push reads half cur[i]
-    // and writes the other one; the NEXT push reads what this one wrote and overwrites what it read.  That is race-free
-    // because consecutive calls on a context are ordered on the device (same stream, or Call's tail event across streams).
-    float* hist = nullptr;
-    std::vector<int64_t> N;         // samples pushed per stream
-    std::vector<char> ended, cur;
-    float* h(int k, int i) const { return hist + ((size_t)k * S + i) * f->J; }
-};
-
 namespace {
 
 int rs_filter(const char* fn, int rate_in, int rate_out, const ResampleFilter** f) {
@@ -2153,16 +2154,17 @@ int rs_table(nhans_ctx* c, const ResampleFilter* f, const float** tab) {
 
 size_t rs_elem(int fmt) { return fmt == kResampleInt16 ? 2 : 4; }
 
-// runs for outputs [m_begin, m_end) of one stream; with hist_out also an empty run when there is no output, so that the
-// carried samples follow every push that brought some
-void rs_add_runs(std::vector<ResampleRun>& runs, size_t* lds, const ResampleFilter& f, const void* src, const float* hist,
-                 float* dst, float* hist_out, int64_t k0, int n_new, int64_t m_begin, int64_t m_end) {
+// THE run geometry: runs for outputs [m_begin, m_end) of one clip or stream whose n_new new samples are at src (mix: see
+// ResampleRun) and follow absolute index k0, stored from dst on in elements of `elem` bytes; with hist_out also an
+// empty run when there is no output, so that the carried samples follow every push that brought some
+void rs_add_runs(std::vector<ResampleRun>& runs, size_t* lds, const ResampleFilter& f, const void* src, const float* mix,
+                 const float* hist, char* dst, size_t elem, float* hist_out, int64_t k0, int n_new, int64_t m_begin, int64_t m_end) {
     bool first = true;
     for (int64_t m = m_begin; m < m_end || (first && hist_out); m += kResampleRun) {
         const int cnt = (int)std::max<int64_t>(0, std::min<int64_t>(kResampleRun, m_end - m));
         const int64_t t0 = m * f.M + f.half, q0 = t0 / f.L;
         const int p0 = (int)(t0 - q0 * f.L);
-        runs.push_back({src, hist, dst ? dst + (m - m_begin) : nullptr, first ? hist_out : nullptr, (long long)k0,
+        runs.push_back({src, mix, hist, dst ? dst + (m - m_begin) * elem : nullptr, first ? hist_out : nullptr, (long long)k0,
                         (long long)(q0 - k0), p0, n_new, cnt});
         *lds = std::max(*lds, resample_run_lds_bytes(f, p0, cnt));
         first = false;
@@ -2170,19 +2172,113 @@ void rs_add_runs(std::vector<ResampleRun>& runs, size_t* lds, const ResampleFilt
     }
 }
 
+// what the kernel reads and stores (launch_resample): PCM of pcm_format -> float32, or the wet/dry mix -> PCM of pcm_format
+struct RateIo {
+    bool from_mix;
+    int pcm_format, quantise;
+    float wet;
+    double factor;
+    size_t in_elem() const { return from_mix ? 4 : rs_elem(pcm_format); }
+    size_t out_elem() const { return from_mix ? rs_elem(pcm_format) : 4; }
+};
+
 int rs_launch(nhans_ctx* c, const char* name, const std::vector<ResampleRun>& runs, const float* tab, const ResampleFilter& f,
-              int fmt, int quantise, double denom, size_t lds, int64_t in_samples, int64_t out_samples, hipStream_t s) {
+              const RateIo& io, size_t lds, double in_bytes, int64_t out_samples, hipStream_t s) {
     if (runs.empty()) return NHANS_OK;
     int rc = ws_reserve(c, ws_size(runs.size(), sizeof(ResampleRun))); if (rc) return rc;
     ResampleRun* runs_dev = ws_take<ResampleRun>(c, runs.size());
     rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(ResampleRun), s); if (rc) return rc;
     Prof pr(c, s, name);
-    launch_resample(name, runs_dev, (int)runs.size(), tab, f, fmt, quantise, denom, lds, s);
-    pr.done(2.0 * f.J * (double)out_samples, (double)in_samples * rs_elem(fmt) + 4.0 * out_samples + 4.0 * runs.size() * f.tab.size());
+    launch_resample(name, runs_dev, (int)runs.size(), tab, f, io.from_mix, io.pcm_format, io.quantise, io.wet, io.factor, lds, s);
+    pr.done(2.0 * f.J * (double)out_samples, in_bytes + (double)io.out_elem() * out_samples + 4.0 * runs.size() * f.tab.size());
     return NHANS_OK;
 }
 
-constexpr int64_t kMaxResampleClip = ((int64_t)1 << 31) - 1;
+// What a streaming converter carries: the filter, its device table, the carried samples and per stream how far it is.
+struct RateStage {
+    const ResampleFilter* f = nullptr;
+    const float* tab = nullptr;
+    int S = 0;
+    // [2][S][J]: the J samples before each stream's next one; cur[i] = the half that holds them.  A push reads half cur[i]
+    // and writes the other one; the NEXT push reads what this one wrote and overwrites what it read.  That is race-free
+    // because consecutive calls on a context are ordered on the device (same stream, or Call's tail event across streams).
+    // A rewind is therefore host-only: the half of before the push is intact, and restore() points at it again.
+    float* hist = nullptr;
+    struct Streams {
+        std::vector<int64_t> N;         // samples taken per stream
+        std::vector<char> ended, cur;
+    } st;
+    struct Span { int64_t Eo, En; };    // outputs [Eo, En) of a stream
+
+    int alloc(nhans_ctx* c, const char* fn, const ResampleFilter* filter, int nstreams) {
+        const int rc = rs_table(c, filter, &tab); if (rc) return rc;
+        f = filter; S = nstreams;
+        st.N.assign(S, 0); st.ended.assign(S, 0); st.cur.assign(S, 0);
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&hist), (size_t)2 * S * f->J * 4);
+        if (e != hipSuccess) return fail(NHANS_ENOMEM, std::string(fn) + ": hipMalloc failed: " + hipGetErrorString(e));
+        return NHANS_OK;
+    }
+    void release() { if (hist) (void)hipFree(hist); hist = nullptr; }
+    float* h(int k, int i) const { return hist + ((size_t)k * S + i) * f->J; }
+    // what cnt more samples (en: and the end) make final of stream i
+    Span plan(int i, int64_t cnt, bool en) const {
+        return {resample_emitted(*f, st.N[i], st.ended[i]), resample_emitted(*f, st.N[i] + cnt, st.ended[i] || en)};
+    }
+    // the runs of such a push, its cnt samples at src (mix: see ResampleRun), outputs e stored from dst on
+    void add_runs(std::vector<ResampleRun>& runs, size_t* lds, int i, const void* src, const float* mix, char* dst, size_t elem,
+                  int64_t cnt, Span e) const {
+        if (cnt == 0 && e.En == e.Eo) return;
+        rs_add_runs(runs, lds, *f, src, mix, h(st.cur[i], i), dst, elem, cnt > 0 ? h(1 - st.cur[i], i) : nullptr, st.N[i], (int)cnt,
+                    e.Eo, e.En);
+    }
+    void commit(int i, int64_t cnt, bool en) {
+        st.N[i] += cnt;
+        st.ended[i] = st.ended[i] || en;
+        if (cnt > 0) st.cur[i] = 1 - st.cur[i];
+    }
+    // (nothing is cleared on the device: a stream of 0 samples reads none of the carried ones -- their absolute index is negative)
+    void restart(int i) { st.N[i] = 0; st.ended[i] = 0; }
+    Streams save() const { return st; }
+    void restore(const Streams& saved) { st = saved; }
+};
+
+// One push through a stage, its arguments checked by the caller: the runs of every stream (stream i brings the samples
+// [inoff[i], inoff[i + 1]) of `in` -- and of `mix`, where the kernel reads the mix --), ONE launch under `kernel`, then the
+// commit.  Where the launch did not go out (a return code, or launch_error_pending()) nothing is committed.
+int stage_push(nhans_ctx* c, RateStage& g, const char* kernel, const RateIo& io, const void* in, const float* mix,
+               const int64_t* inoff, const int* end, void* out, const int64_t* outoff, int64_t* counts, hipStream_t s) {
+    std::vector<ResampleRun> runs;
+    std::vector<RateStage::Span> e(g.S);
+    size_t lds = 0;
+    int64_t tin = 0, tout = 0;
+    for (int i = 0; i < g.S; ++i) {
+        const int64_t cnt = inoff[i + 1] - inoff[i];
+        e[i] = g.plan(i, cnt, end && end[i]);
+        g.add_runs(runs, &lds, i, static_cast<const char*>(in) + inoff[i] * io.in_elem(), mix ? mix + inoff[i] : nullptr,
+                   out ? static_cast<char*>(out) + outoff[i] * io.out_elem() : nullptr, io.out_elem(), cnt, e[i]);
+        tin += cnt; tout += e[i].En - e[i].Eo;
+    }
+    const int rc = rs_launch(c, kernel, runs, g.tab, *g.f, io, lds, (double)tin * (io.in_elem() + (mix ? 4 : 0)), tout, s);
+    if (rc) return rc;
+    if (launch_error_pending()) return NHANS_OK;
+    for (int i = 0; i < g.S; ++i) {
+        counts[i] = e[i].En - e[i].Eo;
+        g.commit(i, inoff[i + 1] - inoff[i], end && end[i]);
+    }
+    return NHANS_OK;
+}
+
+}  // namespace
+
+struct nhans_resampler {
+    nhans_ctx* c = nullptr;
+    int device = 0, in_format = 0, flags = 0;
+    double denom = 0.0;             // nhans_resampler_set_peak: peak + 1e-6; 0 = outputs as they are
+    RateStage g;
+    RateIo io() const { return {false, in_format, flags & NHANS_RESAMPLE_QUANTISE, 0.f, denom}; }
+};
+
+namespace {
 
 int resample_body(nhans_ctx* c, const void* in, int fmt, const int64_t* inoff, int nclips, int rate_in, int rate_out,
                   int flags, float* out, const int64_t* outoff, hipStream_t s) {
@@ -2208,13 +2304,14 @@ int resample_body(nhans_ctx* c, const void* in, int fmt, const int64_t* inoff, i
     if ((tin > 0 && !in) || (tout > 0 && !out)) return fail(NHANS_EINVAL, "nhans_resample: null buffer");
     for (int i = 0; i < nclips; ++i) {
         const int64_t n = inoff[i + 1] - inoff[i];
-        rs_add_runs(runs, &lds, *f, static_cast<const char*>(in) + inoff[i] * rs_elem(fmt), nullptr, out + outoff[i], nullptr, 0,
-                    (int)n, 0, resample_out_count(*f, n));
+        rs_add_runs(runs, &lds, *f, static_cast<const char*>(in) + inoff[i] * rs_elem(fmt), nullptr, nullptr,
+                    reinterpret_cast<char*>(out + outoff[i]), 4, nullptr, 0, (int)n, 0, resample_out_count(*f, n));
     }
     if (runs.empty()) return NHANS_OK;
     const float* tab = nullptr;
     rc = rs_table(c, f, &tab); if (rc) return rc;
-    return rs_launch(c, "resample", runs, tab, *f, fmt, flags & NHANS_RESAMPLE_QUANTISE, 0.0, lds, tin, tout, s);
+    return rs_launch(c, "resample", runs, tab, *f, {false, fmt, flags & NHANS_RESAMPLE_QUANTISE, 0.f, 0.0}, lds,
+                     (double)tin * rs_elem(fmt), tout, s);
 }
 
 int peak_normalise_body(nhans_ctx* c, const float* in, const int64_t* off, int nclips, int flags, float* out, hipStream_t s) {
@@ -2244,53 +2341,26 @@ int peak_normalise_body(nhans_ctx* c, const float* in, const int64_t* off, int n
 }
 
 int resampler_check_push(const nhans_resampler* o, const char* fn, int i, int64_t cnt, bool en) {
-    if (cnt < 0) return fail(NHANS_EINVAL, std::string(fn) + ": stream " + std::to_string(i) + " has a negative sample count");
-    if (o->ended[i] && (cnt > 0 || en)) return fail(NHANS_EINVAL, std::string(fn) + ": stream " + std::to_string(i) + " has ended");
-    if (cnt > kMaxResampleClip) return fail(NHANS_EINVAL, std::string(fn) + ": push too large for one call (split it)");
-    return NHANS_OK;
+    return push_check(fn, "stream", i, cnt, en, o->g.st.ended[i], nullptr, kMaxResampleClip);
 }
 
 int resampler_push_body(nhans_resampler* o, const void* in, const int64_t* inoff, const int* end, float* out,
-                        const int64_t* outoff, int64_t* counts, hipStream_t s, const char* kernel = "resampler_push") {
+                        const int64_t* outoff, int64_t* counts, hipStream_t s) {
     if (!inoff || !outoff || !counts) return fail(NHANS_EINVAL, "nhans_resampler_push: null argument");
-    const ResampleFilter& f = *o->f;
-    const int S = o->S;
-    std::vector<int64_t> Eo(S), En(S);
     int64_t tin = 0, tout = 0;
-    for (int i = 0; i < S; ++i) {
+    for (int i = 0; i < o->g.S; ++i) {
         const int64_t cnt = inoff[i + 1] - inoff[i];
         const bool en = end && end[i];
         const int rc = resampler_check_push(o, "nhans_resampler_push", i, cnt, en); if (rc) return rc;
-        Eo[i] = resample_emitted(f, o->N[i], o->ended[i]);
-        En[i] = resample_emitted(f, o->N[i] + cnt, o->ended[i] || en);
-        if (outoff[i + 1] - outoff[i] < En[i] - Eo[i])
+        const RateStage::Span e = o->g.plan(i, cnt, en);
+        if (outoff[i + 1] - outoff[i] < e.En - e.Eo)
             return fail(NHANS_EINVAL, "nhans_resampler_push: output room of stream " + std::to_string(i) + " is " +
-                                      std::to_string(outoff[i + 1] - outoff[i]) + " samples, " + std::to_string(En[i] - Eo[i]) +
+                                      std::to_string(outoff[i + 1] - outoff[i]) + " samples, " + std::to_string(e.En - e.Eo) +
                                       " needed (nhans_resampler_out_counts)");
-        tin += cnt; tout += En[i] - Eo[i];
+        tin += cnt; tout += e.En - e.Eo;
     }
     if ((tin > 0 && !in) || (tout > 0 && !out)) return fail(NHANS_EINVAL, "nhans_resampler_push: null buffer");
-    std::vector<ResampleRun> runs;
-    std::vector<char> flip(S, 0);
-    size_t lds = 0;
-    for (int i = 0; i < S; ++i) {
-        const int64_t cnt = inoff[i + 1] - inoff[i];
-        if (cnt == 0 && En[i] == Eo[i]) continue;
-        flip[i] = cnt > 0;
-        rs_add_runs(runs, &lds, f, static_cast<const char*>(in) + inoff[i] * rs_elem(o->in_format), o->h(o->cur[i], i),
-                    out ? out + outoff[i] : nullptr, cnt > 0 ? o->h(1 - o->cur[i], i) : nullptr, o->N[i], (int)cnt, Eo[i], En[i]);
-    }
-    const int rc = rs_launch(o->c, kernel, runs, o->tab, f, o->in_format, o->flags & NHANS_RESAMPLE_QUANTISE, o->denom,
-                             lds, tin, tout, s);
-    if (rc) return rc;
-    if (launch_error_pending()) return NHANS_OK;
-    for (int i = 0; i < S; ++i) {
-        counts[i] = En[i] - Eo[i];
-        o->N[i] += inoff[i + 1] - inoff[i];
-        o->ended[i] = o->ended[i] || (end && end[i]);
-        if (flip[i]) o->cur[i] = 1 - o->cur[i];
-    }
-    return NHANS_OK;
+    return stage_push(o->c, o->g, "resampler_push", o->io(), in, nullptr, inoff, end, out, outoff, counts, s);
 }
 
 }  // namespace
@@ -2356,16 +2426,10 @@ int nhans_resampler_open(nhans_ctx* c, int nstreams, int rate_in, int rate_out, 
     if (flags & ~NHANS_RESAMPLE_QUANTISE) return fail(NHANS_EINVAL, "nhans_resampler_open: unknown flag");
     const ResampleFilter* f = nullptr;
     rc = rs_filter("nhans_resampler_open", rate_in, rate_out, &f); if (rc) return rc;
-    const float* tab = nullptr;
-    rc = rs_table(c, f, &tab); if (rc) return rc;
     nhans_resampler* o = new nhans_resampler();
-    o->c = c; o->device = c->device; o->S = nstreams; o->in_format = in_format; o->flags = flags; o->f = f; o->tab = tab;
-    o->N.assign(nstreams, 0); o->ended.assign(nstreams, 0); o->cur.assign(nstreams, 0);
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->hist), (size_t)2 * nstreams * f->J * 4);
-    if (e != hipSuccess) {
-        delete o;
-        return fail(NHANS_ENOMEM, std::string("nhans_resampler_open: hipMalloc failed: ") + hipGetErrorString(e));
-    }
+    o->c = c; o->device = c->device; o->in_format = in_format; o->flags = flags;
+    rc = o->g.alloc(c, "nhans_resampler_open", f, nstreams);
+    if (rc) { delete o; return rc; }
     *out = o;
     return NHANS_OK;
 }
@@ -2387,21 +2451,21 @@ int nhans_resampler_push(nhans_resampler* o, const void* in, const int64_t* inof
 
 int nhans_resampler_out_counts(const nhans_resampler* o, const int64_t* in_counts, const int* end, int64_t* counts) {
     if (!o || !in_counts || !counts) return fail(NHANS_EINVAL, "nhans_resampler_out_counts: null argument");
-    for (int i = 0; i < o->S; ++i) {
+    for (int i = 0; i < o->g.S; ++i) {
         const int rc = resampler_check_push(o, "nhans_resampler_out_counts", i, in_counts[i], end && end[i]); if (rc) return rc;
     }
-    for (int i = 0; i < o->S; ++i)
-        counts[i] = resample_emitted(*o->f, o->N[i] + in_counts[i], o->ended[i] || (end && end[i])) -
-                    resample_emitted(*o->f, o->N[i], o->ended[i]);
+    for (int i = 0; i < o->g.S; ++i) {
+        const RateStage::Span e = o->g.plan(i, in_counts[i], end && end[i]);
+        counts[i] = e.En - e.Eo;
+    }
     return NHANS_OK;
 }
 
 int nhans_resampler_restart(nhans_resampler* o, int i) {
     if (!o) return fail(NHANS_EINVAL, "nhans_resampler_restart: null object");
-    if (i < 0 || i >= o->S)
-        return fail(NHANS_EINVAL, "nhans_resampler_restart: stream " + std::to_string(i) + " out of range (0 ... " + std::to_string(o->S - 1) + ")");
-    // (nothing is cleared on the device: a stream of 0 samples reads none of the carried ones -- their absolute index is negative)
-    o->N[i] = 0; o->ended[i] = 0;
+    if (i < 0 || i >= o->g.S)
+        return fail(NHANS_EINVAL, "nhans_resampler_restart: stream " + std::to_string(i) + " out of range (0 ... " + std::to_string(o->g.S - 1) + ")");
+    o->g.restart(i);
     return NHANS_OK;
 }
 
@@ -2409,38 +2473,30 @@ void nhans_resampler_close(nhans_resampler* o) {
     if (!o) return;
     (void)hipSetDevice(o->device);
     (void)hipDeviceSynchronize();
-    (void)hipFree(o->hist);
+    o->g.release();
     delete o;
 }
 
 }  // extern "C"
 
 // ---- live PCM sessions (include/nhans_hip.h: nhans_live_*) -----------------------------------------------------------
-// One object = an incoming converter (a nhans_resampler rate_in -> 16 kHz with the fixed peak), an online object and the
-// outgoing stage (16 kHz -> rate_out, resample.hip: live_out_kernel), with the 16 kHz pieces between them in device
-// buffers of the object.  A push runs the three stages inside ONE Call on one stream; the stages' own workspace needs
-// (run tables, the online staging) follow each other in the context's workspace, which stream order makes safe, and
-// nothing a later stage reads lives there.
+// One object = an incoming converter (rate_in -> 16 kHz with the fixed peak), an online object and an outgoing converter
+// (16 kHz -> rate_out, fed by the wet/dry mix), with the 16 kHz pieces between them in device buffers of the object.  A
+// push runs the three stages inside ONE Call on one stream; the stages' own workspace needs (run tables, the online
+// staging) follow each other in the context's workspace, which stream order makes safe, and nothing a later stage reads
+// lives there.
 struct nhans_live {
     nhans_ctx* c = nullptr;
-    int device = 0, S = 0, out_format = 0;
+    int device = 0, S = 0, in_format = 0, out_format = 0;
     bool has_wet = false;           // NHANS_LIVE_WET: the online object also makes the mixed round trip
     float wet = 0.f;
-    double out_scale = 1.0;
-    nhans_resampler* in = nullptr;
+    double in_denom = 0.0, out_scale = 1.0;     // the fixed peak + 1e-6
+    RateStage in, out;              // out's stream is c = den + (mix - den) * wet; out.st.N: 16 kHz samples taken per slot
     nhans_online* on = nullptr;
-    // outgoing stage: the state of a nhans_resampler whose input is c (hist: [2][S][J], cur[i] = the half a push reads)
-    const ResampleFilter* fo = nullptr;
-    const float* tab_o = nullptr;
-    float* hist = nullptr;
-    struct Conv {
-        std::vector<int64_t> N;
-        std::vector<char> ended, cur;
-    } out, prev_in, prev_out;       // out.N: 16 kHz samples taken per slot; prev_*: the converters before the last push
+    RateStage::Streams undo_in, undo_out;       // the converters before the last push
     float *mid = nullptr, *den = nullptr, *mix = nullptr;   // the push's 16 kHz input / denoised / mixed pieces
     size_t mid_cap = 0, out_cap = 0;                        // (floats)
     bool can_rewind = false;
-    float* h(int k, int i) const { return hist + ((size_t)k * S + i) * fo->J; }
 };
 
 namespace {
@@ -2455,37 +2511,23 @@ int live_filters(const char* fn, int rate_in, int rate_out, const ResampleFilter
     return NHANS_OK;
 }
 
-int live_slot_check(const nhans_live* o, int slot, const char* fn) {
-    if (slot < 0 || slot >= o->S)
-        return fail(NHANS_EINVAL, std::string(fn) + ": slot " + std::to_string(slot) + " outside [0, " + std::to_string(o->S) + ")");
-    return NHANS_OK;
-}
-
 int live_check_push(const nhans_live* o, const char* fn, int i, int64_t cnt, bool en) {
-    if (cnt < 0) return fail(NHANS_EINVAL, std::string(fn) + ": slot " + std::to_string(i) + " has a negative sample count");
-    if (o->in->ended[i] && (cnt > 0 || en)) return fail(NHANS_EINVAL, std::string(fn) + ": slot " + std::to_string(i) + " has ended");
-    if (!o->on->cond[i] && (cnt > 0 || en))
-        return fail(NHANS_EINVAL, std::string(fn) + ": slot " + std::to_string(i) + " has no conditioning yet " +
-                                  "(nhans_live_set_context / nhans_live_set_embeddings)");
-    if (cnt > kMaxResampleClip) return fail(NHANS_EINVAL, std::string(fn) + ": push too large for one call (split it)");
-    return NHANS_OK;
+    return push_check(fn, "slot", i, cnt, en, o->in.st.ended[i],
+                      o->on->cond[i] ? nullptr : "nhans_live_set_context / nhans_live_set_embeddings", kMaxResampleClip);
 }
 
 // what a push of cnt samples (en: and the end) to slot i moves between the stages: n16 samples into the online object,
 // d16 final samples out of it, outputs [Eo, En) of the outgoing stream
 struct LivePlan {
-    int64_t cnt, n16, d16, Eo, En;
-    bool en;
+    int64_t n16, d16, Eo, En;
 };
 LivePlan live_plan(const nhans_live* o, int i, int64_t cnt, bool en) {
-    const nhans_resampler* r = o->in;
-    const OnStream& q = o->on->st[i];
     LivePlan p{};
-    p.cnt = cnt; p.en = en;
-    p.n16 = resample_emitted(*r->f, r->N[i] + cnt, r->ended[i] || en) - resample_emitted(*r->f, r->N[i], r->ended[i]);
-    p.d16 = on_emitted(nhans_num_frames(q.N + p.n16), q.ended || en, o->on->la[i]) - on_emitted(q.T, q.ended, o->on->la[i]);
-    p.Eo = resample_emitted(*o->fo, o->out.N[i], o->out.ended[i]);
-    p.En = resample_emitted(*o->fo, o->out.N[i] + p.d16, o->out.ended[i] || en);
+    const RateStage::Span e16 = o->in.plan(i, cnt, en);
+    p.n16 = e16.En - e16.Eo;
+    p.d16 = online_emit_count(o->on, i, p.n16, en);
+    const RateStage::Span e = o->out.plan(i, p.d16, en);
+    p.Eo = e.Eo; p.En = e.En;
     return p;
 }
 
@@ -2516,105 +2558,50 @@ int live_reserve(nhans_live* o, size_t n_mid, size_t n_out) {
     return NHANS_OK;
 }
 
-void live_restore_in(nhans_live* o) {
-    o->in->N = o->prev_in.N; o->in->ended = o->prev_in.ended; o->in->cur = o->prev_in.cur;
-}
-
-// (as nhans_online_rewind: the sample rings keep what the undone push wrote, and vlo already says so)
-void live_undo_online(nhans_live* o) {
-    o->on->st = o->on->prev;
-    o->on->cur = 1 - o->on->cur;
-    o->on->can_rewind = false;
-}
-
 int live_push_body(nhans_live* o, const void* in, const int64_t* inoff, const int* end, void* out, const int64_t* outoff,
                    int64_t* counts, hipStream_t s) {
     if (!inoff || !outoff || !counts) return fail(NHANS_EINVAL, "nhans_live_push: null argument");
     nhans_ctx* c = o->c;
     const int S = o->S;
-    const ResampleFilter& f = *o->fo;
-    std::vector<LivePlan> pl(S);
     std::vector<int64_t> moff(S + 1, 0), ooff(S + 1, 0);
     int64_t tin = 0, tout = 0;
     for (int i = 0; i < S; ++i) {
         const int64_t cnt = inoff[i + 1] - inoff[i];
         const bool en = end && end[i];
         const int rc = live_check_push(o, "nhans_live_push", i, cnt, en); if (rc) return rc;
-        pl[i] = live_plan(o, i, cnt, en);
-        if (outoff[i + 1] - outoff[i] < pl[i].En - pl[i].Eo)
+        const LivePlan p = live_plan(o, i, cnt, en);
+        if (outoff[i + 1] - outoff[i] < p.En - p.Eo)
             return fail(NHANS_EINVAL, "nhans_live_push: output room of slot " + std::to_string(i) + " is " +
                                       std::to_string(outoff[i + 1] - outoff[i]) + " samples, " +
-                                      std::to_string(pl[i].En - pl[i].Eo) + " needed (nhans_live_out_counts)");
-        moff[i + 1] = moff[i] + pl[i].n16;
-        ooff[i + 1] = ooff[i] + pl[i].d16;
-        tin += cnt; tout += pl[i].En - pl[i].Eo;
+                                      std::to_string(p.En - p.Eo) + " needed (nhans_live_out_counts)");
+        moff[i + 1] = moff[i] + p.n16;
+        ooff[i + 1] = ooff[i] + p.d16;
+        tin += cnt; tout += p.En - p.Eo;
     }
     if ((tin > 0 && !in) || (tout > 0 && !out)) return fail(NHANS_EINVAL, "nhans_live_push: null buffer");
     int rc = live_reserve(o, (size_t)moff[S], (size_t)ooff[S]); if (rc) return rc;
 
-    // ---- incoming stage, online push: their own bodies, each committing its host state when its launches went out ----
-    o->prev_in.N = o->in->N; o->prev_in.ended = o->in->ended; o->prev_in.cur = o->in->cur;
+    // ---- the three stages, the pieces [moff) and [ooff) between them: each commits its host state when its launches
+    // went out, and a failure behind it puts it back (an online push undone leaves nothing for nhans_live_rewind) ----
+    const RateStage::Streams was_in = o->in.save(), was_out = o->out.save();
     std::vector<int64_t> got(S, 0);
-    rc = resampler_push_body(o->in, in, inoff, end, o->mid, moff.data(), got.data(), s, "live_in"); if (rc) return rc;
-    if (launch_error_pending()) return NHANS_OK;          // (reported by the entry point; no stage has committed)
+    rc = stage_push(c, o->in, "live_in", {false, o->in_format, 0, 0.f, o->in_denom}, in, nullptr, inoff, end, o->mid, moff.data(),
+                    got.data(), s);
+    if (rc || launch_error_pending()) return rc;          // (a launch error is reported by the entry point; no stage has committed)
     rc = online_push_body(o->on, o->mid, moff.data(), end, o->den, o->mix, ooff.data(), got.data(), s);
-    if (rc || launch_error_pending()) { live_restore_in(o); return rc; }
-
-    // ---- outgoing stage ----
-    std::vector<LiveOutRun> runs;
-    std::vector<char> flip(S, 0);
-    size_t lds = 0;
-    const size_t elem = rs_elem(o->out_format);
-    const bool wet = o->wet != 0.f;
-    for (int i = 0; i < S; ++i) {
-        const LivePlan& p = pl[i];
-        if (p.d16 == 0 && p.En == p.Eo) continue;
-        flip[i] = p.d16 > 0;
-        float* hist_out = p.d16 > 0 ? o->h(1 - o->out.cur[i], i) : nullptr;
-        char* dst = static_cast<char*>(out) + outoff[i] * elem;
-        bool first = true;
-        for (int64_t m = p.Eo; m < p.En || (first && hist_out); m += kResampleRun) {
-            const int cnt = (int)std::max<int64_t>(0, std::min<int64_t>(kResampleRun, p.En - m));
-            const int64_t t0 = m * f.M + f.half, q0 = t0 / f.L;
-            const int p0 = (int)(t0 - q0 * f.L);
-            runs.push_back({o->den + ooff[i], wet ? o->mix + ooff[i] : nullptr, o->h(o->out.cur[i], i),
-                            out ? dst + (m - p.Eo) * elem : nullptr, first ? hist_out : nullptr, (long long)o->out.N[i],
-                            (long long)(q0 - o->out.N[i]), p0, (int)p.d16, cnt});
-            lds = std::max(lds, resample_run_lds_bytes(f, p0, cnt));
-            first = false;
-            if (cnt == 0) break;
-        }
-    }
-    if (!runs.empty()) {
-        rc = ws_reserve(c, ws_size(runs.size(), sizeof(LiveOutRun)));
-        LiveOutRun* runs_dev = nullptr;
-        if (!rc) {
-            runs_dev = ws_take<LiveOutRun>(c, runs.size());
-            rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(LiveOutRun), s);
-        }
-        if (rc) { live_restore_in(o); live_undo_online(o); return rc; }
-        Prof pr(c, s, "live_out");
-        launch_live_out("live_out", runs_dev, (int)runs.size(), o->tab_o, f, o->out_format, o->wet, o->out_scale, lds, s);
-        pr.done(2.0 * f.J * (double)tout, (wet ? 8.0 : 4.0) * (double)ooff[S] + (double)elem * tout + 4.0 * runs.size() * f.tab.size());
-        if (launch_error_pending()) { live_restore_in(o); live_undo_online(o); return NHANS_OK; }
-    }
-
-    // ---- host state of the outgoing stage ----
-    o->prev_out = o->out;
-    for (int i = 0; i < S; ++i) {
-        counts[i] = pl[i].En - pl[i].Eo;
-        o->out.N[i] += pl[i].d16;
-        o->out.ended[i] = o->out.ended[i] || pl[i].en;
-        if (flip[i]) o->out.cur[i] = 1 - o->out.cur[i];
-    }
+    if (rc || launch_error_pending()) { o->in.restore(was_in); return rc; }
+    rc = stage_push(c, o->out, "live_out", {true, o->out_format, 0, o->wet, o->out_scale}, o->den, o->wet != 0.f ? o->mix : nullptr,
+                    ooff.data(), end, out, outoff, counts, s);
+    if (rc || launch_error_pending()) { o->in.restore(was_in); online_undo(o->on); o->can_rewind = false; return rc; }
+    o->undo_in = was_in; o->undo_out = was_out;
     o->can_rewind = true;
     return NHANS_OK;
 }
 
 void live_free(nhans_live* o) {
-    if (o->in) nhans_resampler_close(o->in);
     if (o->on) nhans_online_close(o->on);
-    for (float* p : {o->hist, o->mid, o->den, o->mix})
+    o->in.release(); o->out.release();
+    for (float* p : {o->mid, o->den, o->mix})
         if (p) (void)hipFree(p);
     delete o;
 }
@@ -2644,9 +2631,9 @@ int64_t nhans_lookahead_live_emitted(int64_t n, int ended, int rate_in, int rate
 
 int nhans_lookahead_live_set(nhans_live* o, int slot, int lookahead) {
     if (!o) return fail(NHANS_EINVAL, "nhans_lookahead_live_set: null object");
-    int rc = live_slot_check(o, slot, "nhans_lookahead_live_set"); if (rc) return rc;
+    int rc = slot_check(o->S, slot, "nhans_lookahead_live_set"); if (rc) return rc;
     // (a stream of 0 samples in all three stages: the converter may hold samples the online stage has not seen yet)
-    if (o->in->N[slot] != 0 || o->in->ended[slot])
+    if (o->in.st.N[slot] != 0 || o->in.st.ended[slot])
         return fail(NHANS_EINVAL, "nhans_lookahead_live_set: slot " + std::to_string(slot) + " has a stream under way " +
                                   "(the look-ahead is set on an open stream of 0 samples: after open or nhans_live_restart)");
     rc = nhans_online_set_lookahead(o->on, slot, lookahead); if (rc) return rc;
@@ -2672,18 +2659,12 @@ int nhans_live_open_slots(nhans_ctx* c, int nslots, int rate_in, int in_format, 
     const ResampleFilter *fi = nullptr, *fo = nullptr;
     int rc = live_filters("nhans_live_open_slots", rate_in, rate_out, &fi, &fo); if (rc) return call.finish(rc);
     nhans_live* o = new nhans_live();
-    o->c = c; o->device = c->device; o->S = nslots; o->out_format = out_format; o->has_wet = (flags & NHANS_LIVE_WET) != 0;
-    o->out_scale = out_scale; o->fo = fo;
-    o->out.N.assign(nslots, 0); o->out.ended.assign(nslots, 0); o->out.cur.assign(nslots, 0);
-    o->prev_out = o->out;
-    rc = rs_table(c, fo, &o->tab_o);
-    if (!rc) rc = nhans_resampler_open(c, nslots, rate_in, 16000, in_format, 0, &o->in);
-    if (!rc) rc = nhans_resampler_set_peak(o->in, peak);
+    o->c = c; o->device = c->device; o->S = nslots; o->in_format = in_format; o->out_format = out_format;
+    o->has_wet = (flags & NHANS_LIVE_WET) != 0;
+    o->in_denom = peak + 0.000001; o->out_scale = out_scale;
+    rc = o->in.alloc(c, "nhans_live_open_slots", fi, nslots);
+    if (!rc) rc = o->out.alloc(c, "nhans_live_open_slots", fo, nslots);
     if (!rc) rc = online_open_slots_body(c, nslots, o->has_wet, call.s, &o->on);
-    if (!rc) {
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->hist), (size_t)2 * nslots * fo->J * 4);
-        if (e != hipSuccess) rc = fail(NHANS_ENOMEM, std::string("nhans_live_open_slots: hipMalloc failed: ") + hipGetErrorString(e));
-    }
     if (rc) { live_free(o); return call.finish(rc); }
     *out = o;
     return call.finish(NHANS_OK);
@@ -2691,11 +2672,10 @@ int nhans_live_open_slots(nhans_ctx* c, int nslots, int rate_in, int in_format, 
 
 int nhans_live_restart(nhans_live* o, int slot) {
     if (!o) return fail(NHANS_EINVAL, "nhans_live_restart: null object");
-    const int rc = live_slot_check(o, slot, "nhans_live_restart"); if (rc) return rc;
+    const int rc = slot_check(o->S, slot, "nhans_live_restart"); if (rc) return rc;
     // (nothing is cleared on the device: streams of 0 samples read none of the carried state, in any of the stages)
     online_restart_slot(o->on, slot);
-    o->in->N[slot] = 0; o->in->ended[slot] = 0;
-    o->out.N[slot] = 0; o->out.ended[slot] = 0;
+    o->in.restart(slot); o->out.restart(slot);
     o->can_rewind = false;
     return NHANS_OK;
 }
@@ -2705,7 +2685,7 @@ int nhans_live_set_context(nhans_live* o, int slot, const float* ca, int64_t na,
     if (!o) return fail(NHANS_EINVAL, "nhans_live_set_context: null object");
     Call call(o->c, stream);
     if (call.rc) return call.rc;
-    int rc = live_slot_check(o, slot, "nhans_live_set_context"); if (rc) return call.finish(rc);
+    int rc = slot_check(o->S, slot, "nhans_live_set_context"); if (rc) return call.finish(rc);
     if (!ca || !cbw) return call.finish(fail(NHANS_EINVAL, "nhans_live_set_context: null argument"));
     if (na < 0 || nb < 0) return call.finish(fail(NHANS_EINVAL, "nhans_live_set_context: negative sample count"));
     rc = online_set_context_body(o->on, slot, ca, na, cbw, nb, call.s, first_frame_out);
@@ -2717,7 +2697,7 @@ int nhans_live_set_embeddings(nhans_live* o, int slot, const float* ea, const fl
     if (!o) return fail(NHANS_EINVAL, "nhans_live_set_embeddings: null object");
     Call call(o->c, stream);
     if (call.rc) return call.rc;
-    int rc = live_slot_check(o, slot, "nhans_live_set_embeddings"); if (rc) return call.finish(rc);
+    int rc = slot_check(o->S, slot, "nhans_live_set_embeddings"); if (rc) return call.finish(rc);
     if (!ea || !eb) return call.finish(fail(NHANS_EINVAL, "nhans_live_set_embeddings: null argument"));
     rc = online_set_embeddings_body(o->on, slot, ea, eb, call.s, first_frame_out);
     if (!rc) o->can_rewind = false;
@@ -2757,9 +2737,9 @@ int nhans_live_rewind(nhans_live* o) {
     if (!o) return fail(NHANS_EINVAL, "nhans_live_rewind: null object");
     if (!o->can_rewind) return fail(NHANS_EINVAL, "nhans_live_rewind: no push to undo (one rewind per push)");
     // (every stage wrote the half of its carried state that it did not read: the halves of before the push are intact)
-    live_restore_in(o);
-    live_undo_online(o);
-    o->out = o->prev_out;
+    o->in.restore(o->undo_in);
+    online_undo(o->on);
+    o->out.restore(o->undo_out);
     o->can_rewind = false;
     return NHANS_OK;
 }

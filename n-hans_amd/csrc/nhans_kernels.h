@@ -308,12 +308,16 @@ int64_t resample_out_count(const ResampleFilter& f, int64_t n);                 
 int64_t resample_emitted(const ResampleFilter& f, int64_t n, bool ended);      // the streaming output contract
 
 // One workgroup: outputs [m0, m0 + cnt) of one clip or stream, m0 * M + half = q0 * L + p0.  The input is the stream's
-// samples from absolute index k0 on (n_new of them at src, int16 or float32) preceded by `hist`, the J samples before k0
-// as float32 (entries of negative absolute index are never read); everything else reads as 0.0f.
+// samples from absolute index k0 on (n_new of them) preceded by `hist`, the J samples before k0 as float32 (entries of
+// negative absolute index are never read); everything else reads as 0.0f.  The new samples are either PCM at src (int16
+// or float32) or, for the outgoing stage of a live PCM session, stored nowhere: sample k0 + rel is
+// c = den[rel] + (mix[rel] - den[rel]) * wet with den at src, formed while the span is staged (mix == nullptr: c = den,
+// the wet factor is 0).  `hist` / `hist_out` carry what the source gives: x, or c.
 struct ResampleRun {
     const void* src;
+    const float* mix;       // the mix source only, nullable; the PCM source ignores it
     const float* hist;      // nullable: nothing before k0
-    float* dst;
+    void* dst;              // float32 from PCM; int16 or float32 elements, by the launch's format, from the mix
     float* hist_out;        // non-null: this workgroup also writes the J samples before k0 + n_new (the stream's next history)
     long long k0;
     long long qrel0;        // q0 - k0
@@ -322,26 +326,11 @@ struct ResampleRun {
 constexpr int kResampleRun = 1024;      // outputs per workgroup at most
 constexpr int kResampleInt16 = 0, kResampleFloat32 = 1;
 size_t resample_run_lds_bytes(const ResampleFilter& f, int p0, int cnt);
-// denom != 0: every output is then float32(double(y) / denom) (the fixed-peak normalisation of a live stream)
+// from_mix false: PCM of pcm_format -> float32, rounded to the int16 grid with `quantise`, then float32(double(y) / factor)
+// when factor != 0 (the fixed-peak normalisation of a live stream).  from_mix true: the wet/dry mix -> PCM of pcm_format,
+// float32(double(y) * factor) before the rounding.  A run table that needs more than 64 KB of LDS is refused.
 void launch_resample(const char* kernel, const ResampleRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
-                     int in_format, int quantise, double denom, size_t lds_bytes, hipStream_t s);
-
-// The outgoing stage of a live PCM session (include/nhans_hip.h: nhans_live_*): a ResampleRun whose input is not stored
-// anywhere -- sample k0 + rel of the stream is c = den[rel] + (mix[rel] - den[rel]) * wet, formed while the span is
-// staged (mix == nullptr: c = den[rel], the wet factor is 0) -- and whose outputs are scaled and stored as int16 or
-// float32.  `hist` / `hist_out` carry c, as ResampleRun's carry x.
-struct LiveOutRun {
-    const float* den;
-    const float* mix;       // nullable: wet == 0
-    const float* hist;      // the J values of c before k0
-    void* dst;              // int16 or float32 elements, by the launch's out_format
-    float* hist_out;        // non-null: this workgroup also writes the J values of c before k0 + n_new
-    long long k0;
-    long long qrel0;        // q0 - k0
-    int p0, n_new, cnt;
-};
-void launch_live_out(const char* kernel, const LiveOutRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
-                     int out_format, float wet, double out_scale, size_t lds_bytes, hipStream_t s);
+                     bool from_mix, int pcm_format, int quantise, float wet, double factor, size_t lds_bytes, hipStream_t s);
 
 // peak + normalise: blocks of <= kNormBlock samples; block b belongs to a clip whose blocks are [pb0, pb0 + pbn)
 struct NormBlock {

@@ -5,10 +5,13 @@
 // 2 * half + 1 taps, half = 10 max(L, M), unit sum, times L -- computed here in double so that a C caller needs no Python.
 // Output m of a clip is
 //     y[m] = sum_k h[m M + half - k L] x[k]  =  sum_{j < J} h[p + j L] x[q - j],   m M + half = q L + p,  0 <= p < L
-// -- ONE chain of J fmaf in float32, j ascending, absent inputs as 0.0f (fir_chain below).  The offline call and the live
-// push run the SAME kernel on run descriptors the host builds, so a stream's output cannot depend on how it was cut: a
-// push only changes where an input sample is fetched from (the caller's new samples or the J carried ones), never the
-// arithmetic on it.
+// -- ONE chain of J fmaf in float32, j ascending, absent inputs as 0.0f (fir_chain below).  The offline call, the
+// streaming push and both converters of a live session run ONE kernel body (resample_kernel) on run descriptors the
+// host builds in one place (RateStage::add_runs, nhans_api.hip), so a stream's output cannot depend on how it was cut:
+// a push only changes where an input sample is fetched from (the caller's new samples or the J carried ones), never the
+// arithmetic on it.  The body is a template over a source (PCM int16 / float32, or the wet/dry mix of a live session
+// formed while the span is staged) and a sink (float32 with the optional int16 grid and fixed peak, or scaled PCM);
+// the four pairs in use are instantiated: int16 -> float, float32 -> float, mix -> int16, mix -> float32.
 #include "nhans_kernels.h"
 
 #include <cmath>
@@ -118,11 +121,49 @@ __device__ __forceinline__ float fir_chain(const float* tab_p, int L, const floa
     return acc;
 }
 
-// sample k0 + rel of the run's stream as float32 (rel < n_new; int16 -> float32 is exact)
-template <typename TIn>
-__device__ __forceinline__ float run_sample(const TIn* src, const ResampleRun& r, long long rel, int J) {
+// Source policies: sample k0 + rel of the run's stream, 0 <= rel < n_new, as float32.
+// PCM at src (int16 -> float32 is exact):
+template <typename T>
+struct PcmSource {
+    static __device__ __forceinline__ float at(const ResampleRun& r, long long rel, float) {
+        return (float)static_cast<const T*>(r.src)[rel];
+    }
+};
+// the combined stream c of a live session, stored nowhere: three separately rounded float32 operations (numpy's
+// `den + (mix - den) * factor`), never contracted; with mix == nullptr (wet factor 0) c is den and mix is not read
+struct MixSource {
+    static __device__ __forceinline__ float at(const ResampleRun& r, long long rel, float wet) {
+        const float d = static_cast<const float*>(r.src)[rel];
+        if (!r.mix) return d;
+        return __fadd_rn(d, __fmul_rn(__fsub_rn(r.mix[rel], d), wet));
+    }
+};
+
+// Sink policies: what becomes of output i of the run, y = its chain.
+// float32, optionally rounded to the int16 grid, then float32(double(v) / factor) when factor != 0 (the fixed peak):
+struct FloatSink {
+    static __device__ __forceinline__ void put(void* dst, int i, float v, int quantise, double factor) {
+        if (quantise) v = fminf(fmaxf(rintf(v), -32768.f), 32767.f);
+        if (factor != 0.0) v = (float)((double)v / factor);
+        static_cast<float*>(dst)[i] = v;
+    }
+};
+// PCM: float32(double(y) * factor), then rounded and clamped for int16.  The int16 stores are plain 2-byte stores: a
+// slot's destination is only 2-byte aligned, and the 64 lanes of a wave write 128 consecutive bytes.
+template <typename T>
+struct PcmSink {
+    static __device__ __forceinline__ void put(void* dst, int i, float y, int, double factor) {
+        const float v = (float)((double)y * factor);
+        if constexpr (sizeof(T) == 2) static_cast<int16_t*>(dst)[i] = (int16_t)fminf(fmaxf(rintf(v), -32768.f), 32767.f);
+        else static_cast<float*>(dst)[i] = v;
+    }
+};
+
+// sample k0 + rel of the run's stream: the source's where the push brought it, the carried one before that, else 0.0f
+template <typename Src>
+__device__ __forceinline__ float run_sample(const ResampleRun& r, long long rel, int J, float wet) {
     if (rel >= r.n_new) return 0.f;
-    if (rel >= 0) return (float)src[rel];
+    if (rel >= 0) return Src::at(r, rel, wet);
     const long long a = rel + J;
     if (a >= 0 && r.k0 + rel >= 0 && r.hist) return r.hist[a];
     return 0.f;
@@ -134,77 +175,28 @@ __device__ __forceinline__ float run_sample(const TIn* src, const ResampleRun& r
 // that step is odd (44.1 -> 16 kHz: 121), 2-way and more where it is even (16 -> 44.1 kHz: 160 -- the price of one
 // layout for every pair), then the input span of the run (<= 58.5 KB together, 88.2 kHz in).  Lane i reads x at stride
 // M / L: 2-way bank conflicts for the even ratios (32 and 96 kHz in), none for 48 kHz in and for every upsampling pair.
-template <typename TIn>
+// Src and Sink change only where a sample of the span comes from and what is stored; wet is the source's argument,
+// quantise and factor are the sink's.
+template <typename Src, typename Sink>
 __global__ void __launch_bounds__(256) resample_kernel(const ResampleRun* __restrict__ runs, const float* __restrict__ tab,
-                                                       int L, int M, int J, int tab4, int quantise, double denom) {
+                                                       int L, int M, int J, int tab4, int quantise, float wet, double factor) {
     extern __shared__ float4 rs_lds[];
     float* tl = reinterpret_cast<float*>(rs_lds);
     float* xs = tl + 4 * tab4;
     const ResampleRun r = runs[blockIdx.x];
     const int tid = threadIdx.x;
-    const TIn* src = static_cast<const TIn*>(r.src);
     for (int i = tid; i < tab4; i += 256) rs_lds[i] = reinterpret_cast<const float4*>(tab)[i];
     const int span = r.cnt > 0 ? (r.p0 + (r.cnt - 1) * M) / L + J : 0;
     const long long lo = r.qrel0 - (J - 1);
-    for (int s = tid; s < span; s += 256) xs[s] = run_sample(src, r, lo + s, J);
+    for (int s = tid; s < span; s += 256) xs[s] = run_sample<Src>(r, lo + s, J, wet);
     __syncthreads();
     for (int i = tid; i < r.cnt; i += 256) {
         const int t = r.p0 + i * M;
         const int q = t / L, p = t - q * L;
-        float v = fir_chain(tl + p, L, xs + (J - 1) + q, J);
-        if (quantise) v = fminf(fmaxf(rintf(v), -32768.f), 32767.f);
-        if (denom != 0.0) v = (float)((double)v / denom);
-        r.dst[i] = v;
+        Sink::put(r.dst, i, fir_chain(tl + p, L, xs + (J - 1) + q, J), quantise, factor);
     }
     if (r.hist_out)
-        for (int t = tid; t < J; t += 256) r.hist_out[t] = run_sample(src, r, (long long)r.n_new - J + t, J);
-}
-
-// value k0 + rel of a live session's combined stream c: three separately rounded float32 operations (numpy's
-// `den + (mix - den) * factor`), never contracted; with mix == nullptr (wet factor 0) c is den and mix is not read
-__device__ __forceinline__ float live_sample(const LiveOutRun& r, long long rel, int J, float wet) {
-    if (rel >= r.n_new) return 0.f;
-    if (rel >= 0) {
-        const float d = r.den[rel];
-        if (!r.mix) return d;
-        return __fadd_rn(d, __fmul_rn(__fsub_rn(r.mix[rel], d), wet));
-    }
-    const long long a = rel + J;
-    if (a >= 0 && r.k0 + rel >= 0 && r.hist) return r.hist[a];
-    return 0.f;
-}
-
-__device__ __forceinline__ void live_store(int16_t* dst, int i, float v) {
-    dst[i] = (int16_t)fminf(fmaxf(rintf(v), -32768.f), 32767.f);
-}
-__device__ __forceinline__ void live_store(float* dst, int i, float v) { dst[i] = v; }
-
-// resample_kernel with both ends changed: the span is formed from den / mix / the carried c while it is staged, and the
-// epilogue scales in double, then rounds and clamps (int16) and stores PCM.  The LDS layout, the lane -> output map and
-// the chain (fir_chain) are resample_kernel's, so y is bit for bit nhans_resample of c.  The int16 stores are plain
-// 2-byte stores: a slot's destination is only 2-byte aligned, and the 64 lanes of a wave write 128 consecutive bytes.
-template <typename TOut>
-__global__ void __launch_bounds__(256) live_out_kernel(const LiveOutRun* __restrict__ runs, const float* __restrict__ tab,
-                                                       int L, int M, int J, int tab4, float wet, double scale) {
-    extern __shared__ float4 rs_lds[];
-    float* tl = reinterpret_cast<float*>(rs_lds);
-    float* xs = tl + 4 * tab4;
-    const LiveOutRun r = runs[blockIdx.x];
-    const int tid = threadIdx.x;
-    for (int i = tid; i < tab4; i += 256) rs_lds[i] = reinterpret_cast<const float4*>(tab)[i];
-    const int span = r.cnt > 0 ? (r.p0 + (r.cnt - 1) * M) / L + J : 0;
-    const long long lo = r.qrel0 - (J - 1);
-    for (int s = tid; s < span; s += 256) xs[s] = live_sample(r, lo + s, J, wet);
-    __syncthreads();
-    TOut* dst = static_cast<TOut*>(r.dst);
-    for (int i = tid; i < r.cnt; i += 256) {
-        const int t = r.p0 + i * M;
-        const int q = t / L, p = t - q * L;
-        const float y = fir_chain(tl + p, L, xs + (J - 1) + q, J);
-        live_store(dst, i, (float)((double)y * scale));
-    }
-    if (r.hist_out)
-        for (int t = tid; t < J; t += 256) r.hist_out[t] = live_sample(r, (long long)r.n_new - J + t, J, wet);
+        for (int t = tid; t < J; t += 256) r.hist_out[t] = run_sample<Src>(r, (long long)r.n_new - J + t, J, wet);
 }
 
 __device__ __forceinline__ float block_max(float m) {
@@ -256,29 +248,14 @@ void launch_channel_mean(const float* in, int nchan, int64_t n, float* out, hipS
 }
 
 void launch_resample(const char* kernel, const ResampleRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
-                     int in_format, int quantise, double denom, size_t lds_bytes, hipStream_t s) {
+                     bool from_mix, int pcm_format, int quantise, float wet, double factor, size_t lds_bytes, hipStream_t s) {
     if (nruns <= 0) return;
     if (lds_bytes > (size_t)64 << 10) { note_refusal(kernel); return; }
     const int tab4 = (int)(f.tab.size() / 4);
-    if (in_format == kResampleInt16)
-        NHANS_LAUNCH(kernel, resample_kernel<int16_t>, dim3(nruns), dim3(256), lds_bytes, s, runs_dev, tab_dev, f.L, f.M, f.J,
-                     tab4, quantise, denom);
-    else
-        NHANS_LAUNCH(kernel, resample_kernel<float>, dim3(nruns), dim3(256), lds_bytes, s, runs_dev, tab_dev, f.L, f.M, f.J,
-                     tab4, quantise, denom);
-}
-
-void launch_live_out(const char* kernel, const LiveOutRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
-                     int out_format, float wet, double out_scale, size_t lds_bytes, hipStream_t s) {
-    if (nruns <= 0) return;
-    if (lds_bytes > (size_t)64 << 10) { note_refusal(kernel); return; }
-    const int tab4 = (int)(f.tab.size() / 4);
-    if (out_format == kResampleInt16)
-        NHANS_LAUNCH(kernel, live_out_kernel<int16_t>, dim3(nruns), dim3(256), lds_bytes, s, runs_dev, tab_dev, f.L, f.M, f.J,
-                     tab4, wet, out_scale);
-    else
-        NHANS_LAUNCH(kernel, live_out_kernel<float>, dim3(nruns), dim3(256), lds_bytes, s, runs_dev, tab_dev, f.L, f.M, f.J,
-                     tab4, wet, out_scale);
+    const bool i16 = pcm_format == kResampleInt16;
+    auto* fn = !from_mix ? (i16 ? resample_kernel<PcmSource<int16_t>, FloatSink> : resample_kernel<PcmSource<float>, FloatSink>)
+                         : (i16 ? resample_kernel<MixSource, PcmSink<int16_t>> : resample_kernel<MixSource, PcmSink<float>>);
+    NHANS_LAUNCH(kernel, fn, dim3(nruns), dim3(256), lds_bytes, s, runs_dev, tab_dev, f.L, f.M, f.J, tab4, quantise, wet, factor);
 }
 
 void launch_peak_partial(const float* x, const NormBlock* blocks_dev, int nblocks, int wrap, float* partial, hipStream_t s) {

@@ -262,6 +262,57 @@ def test_rewind(eng):
         sess.close()
 
 
+def test_rewind_where_the_stages_differ_per_slot(eng):
+    """Three slots, 44.1 kHz float32 in, 48 kHz int16 out, wet 0.25.  The pushes that are rewound bring 0 samples to one
+    slot, 1 to another and 4,410 to the third, the roles turning: the 1-sample slot's incoming converter flips its carried
+    half while its outgoing one, which got nothing, does not, so the three stages' snapshots must each be the slot's own.
+    The last push ends all three slots (with 4,410, 1 and 0 samples) and is rewound too.  The push after a rewind gives
+    the same bytes, and every slot's stream is bit for bit its offline chain (the `want` of
+    test_bit_for_bit_the_offline_chain)."""
+    seeds = [911, 912, 913]
+    xs = [_recording(44100, s, np.float32) for s in seeds]
+    ys = [_converted(eng, _combine(*_den_mix(eng, 44100, np.float32, s), 0.25), 48000) for s in seeds]
+    scale = 2.0 * 32767.0 / min(min(float(y.max()), float(-y.min())) for y in ys)
+    want = [_pcm(y, np.int16, scale) for y in ys]
+    roles, tail = [4410, 1, 0], [4410, 1, 0]
+    left = [len(x) - t for x, t in zip(xs, tail)]         # what a slot brings before the last push
+    steps = []                                            # (counts, end, rewound)
+    while any(left):
+        k = len(steps)
+        counts = [roles[(i + k) % 3] for i in range(3)] if k in (0, 4, 8) else [4410] * 3
+        counts = [min(c, l) for c, l in zip(counts, left)]
+        assert k not in (0, 4, 8) or sorted(counts) == [0, 1, 4410]
+        left = [l - c for l, c in zip(left, counts)]
+        steps.append((counts, [False] * 3, k in (0, 4, 8)))
+    assert len(steps) > 9
+    steps.append((tail, [True] * 3, True))
+    sess = live.LiveSession(eng, 3, 44100, 48000, PEAK, in_dtype=np.float32, out_scale=scale, wet=True)
+    try:
+        sess.set_wet(0.25)
+        for i, s in enumerate(seeds):
+            sess.set_context(i, *_ctx(s))
+        outs, pos = [[] for _ in range(3)], [0, 0, 0]
+        for k, (counts, end, rewound) in enumerate(steps):
+            pieces = [x[p:p + n] for x, p, n in zip(xs, pos, counts)]
+            got = sess.push(pieces, end)
+            if rewound:
+                sess.rewind()
+                again = sess.push(pieces, end)
+                for i in range(3):
+                    assert again[i].tobytes() == got[i].tobytes(), (k, i)
+            for i in range(3):
+                outs[i].append(got[i])
+                pos[i] += counts[i]
+        assert pos == [len(x) for x in xs] and sess.ended == [True] * 3
+    finally:
+        sess.close()
+    assert any(len(o) for o in outs[0][4:5] + outs[1][4:5] + outs[2][4:5])       # (the rewound pushes are not all silent)
+    for i in range(3):
+        got = np.concatenate(outs[i])
+        assert got.dtype == np.int16 and len(got) == live.emitted(len(xs[i]), True, 44100, 48000)
+        assert np.array_equal(got, want[i]), i
+
+
 def _scaled_block1(weights_denoiser):           # (as tests/test_gpu_online.py)
     W = dict(weights_denoiser)
     W["resblock1_1_conv1/w"] = (W["resblock1_1_conv1/w"] * np.float32(3.0e5)).astype(np.float32)
