@@ -607,6 +607,68 @@ int nhans_capture_live_context(nhans_live* obj, int n, const int* slots_host, co
                                int64_t* first_frame_out /* [n], nullable */);
 int nhans_capture_live_embeddings(const nhans_live* obj, int slot, float* emb_a_out_dev, float* emb_b_out_dev, void* stream);
 
+/* ---- Live sessions: level meter and automatic compensation --------------------------------------------------------------
+ * The reference's --ac picks the wet factor itself: factor = snr_est / 20 with snr_est = mean(denoised^2) / mean(removed^2)
+ * (SN/apply.py write_snc_outputs), three numpy lines once the whole file is known.  A live object has the 16 kHz denoised
+ * and mixed pieces only on the device, so the functions below keep per-hop powers of each slot's 16 kHz output there and
+ * derive from them a wet factor that follows that law over a trailing window -- applied inside the outgoing launch -- and
+ * a meter the host can read.  Added without moving NHANS_ABI_VERSION; a caller that may meet an older library looks them up
+ * by symbol.  (The names begin with nhans_level_: the live prefix's set of names is closed.)
+ *
+ * Definitions, for one slot.  d[n], m[n]: the final 16 kHz denoised and mixed samples of its stream, bit for bit those of
+ * nhans_enhance_clips; r[n] = float32(m[n] - d[n]).  Hop h is samples [160 h, 160 h + 160).  A running stream's final
+ * samples are a multiple of 320, so its hops are whole; an ended stream of T frames has 160 (T + 1) + 80 samples and its
+ * last hop, of 80 samples, counts as a hop: nhans_level_hops(emitted, ended) hops are final.
+ *   Powers (double; a product of two float32 is exact):  Pd[h] = sum double(d)^2, Pr[h] = sum double(r)^2,
+ *     Pm[h] = sum double(m)^2, each hop summed by one wavefront in one fixed order (lane k: samples k, k + 64, k + 128,
+ *     then the shuffle tree 32, 16, ... 1) whatever push made it final.
+ *   Window sums, window W hops, 1 <= W <= 256:  Sd(h) = sum of Pd[j], j = max(h0, h - W + 1) ... h, ascending; Sr, Sm alike.
+ *     W = 0: every hop since h0, a sequential running sum -- the reference's whole-file figure to date.  h0 is the first
+ *     hop the state knows: 0 after open or nhans_live_restart, or the hop at which the meter was enabled.
+ *   Gain of hop h:  g = (Sd / Sr) / 20 in double;  w_h = float32(min(max(g, 0), wmax));  w_h = 0 where Sr == 0 or g is NaN.
+ *     The gain is constant over a hop and steps between hops; how large a step can be is the caller's choice of W.
+ *   Mix:  sample n of hop h becomes c[n] = d + r * w_h, the three separately rounded float32 operations of step 1 of the
+ *     live output arithmetic with w_h in place of the scalar, and the outgoing stream is the conversion of c, bit for bit.
+ * Every figure depends on the recording (and on h0) only, never on how the stream was cut into pushes.
+ *
+ * Launches.  A push of an object whose meter was never enabled is launch for launch what it was.  With the meter enabled
+ * a push that makes a hop final issues one launch more, "live_level", between the online stage and "live_out", one
+ * workgroup per slot with new hops; a failure behind it puts every stage back as a failed live_out does.  The state is
+ * double-buffered like the converters' carried samples: nhans_live_rewind is host-only here too.
+ * What automatic compensation is worth is a property of the trained model; nothing in this library measures it. */
+
+/* Host only, no object.  Final hops of a stream that has emitted `emitted` 16 kHz samples: emitted / 160, rounded up once
+ * ended.  Negative (NHANS_EINVAL) for emitted < 0. */
+int64_t nhans_level_hops(int64_t emitted, int ended);
+
+/* Gives every slot its level state (6.3 KB per slot and half; idempotent).  Needs an object opened with NHANS_LIVE_WET,
+ * else NHANS_EINVAL naming the flag.  h0 of a slot is the number of hops its stream has then; the last push becomes
+ * final (nhans_live_rewind).  Pushes from now on also meter. */
+int nhans_level_live_enable(nhans_live* obj, void* stream);
+
+/* Host only.  window_hops 0 .. 256: the hops later pushes make final are mixed with their own w_h (window W = window_hops,
+ * clamp wmax: finite, >= 0) instead of the factor of nhans_live_set_wet, which stays stored and can still be set;
+ * the meter uses the same W and wmax (0 and 1.0 until the first such call).  window_hops -1: back to the stored fixed
+ * factor from the next final hop on (wmax is checked and otherwise unused; the meter keeps its window).  Anything else,
+ * or a meter not enabled: NHANS_EINVAL and nothing changes.  The last push becomes final (nhans_live_rewind). */
+int nhans_level_live_auto(nhans_live* obj, int window_hops, double wmax);
+
+/* The meter of a slot after its last final hop h: out[0..2] = Sd(h), Sr(h), Sm(h), out[3] = hops known (h + 1 - h0),
+ * out[4] = w_h -- the law's gain, applied or not --, out[5] = snr_est = Sd / Sr (inf or NaN where Sr == 0), out[6..7] = 0.
+ * One copy of 64 bytes and one synchronisation of the stream.  NHANS_ESHORT before the slot's first hop since h0. */
+int nhans_level_live_read(nhans_live* obj, int slot, double* out_host /* [8] */, void* stream);
+
+/* The gains w_h of the hops the last push made final for the slot, in hop order, to out_host (room for `cap`); returns
+ * their number (out_host NULL: the number alone; 0 after a rewind or restart).  One copy, one synchronisation. */
+int64_t nhans_level_live_gains(nhans_live* obj, int slot, float* out_host, int64_t cap, void* stream);
+
+/* The whole-clip statement of the definitions, by the same kernel: clip i is samples [offsets_host[i], offsets_host[i+1])
+ * of den_dev / mix_dev, an ended stream with h0 = 0 -- ceil(n / 160) hops, the last one as short as it is.  Writes one
+ * gain per hop to w_out_dev, clip after clip, and (sums_out_dev nullable) the eight doubles of nhans_level_live_read
+ * after each clip's last hop at sums_out_dev[8 i] (nothing for an empty clip).  window_hops 0 .. 256. */
+int nhans_level_gains(nhans_ctx* ctx, const float* den_dev, const float* mix_dev, const int64_t* offsets_host, int nclips,
+                      int window_hops, double wmax, float* w_out_dev, double* sums_out_dev, void* stream);
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

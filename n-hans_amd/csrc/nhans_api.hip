@@ -2178,6 +2178,7 @@ struct RateIo {
     int pcm_format, quantise;
     float wet;
     double factor;
+    bool auto_wet = false;      // from_mix: each hop's factor comes from the runs' gain table (GainTab) instead of `wet`
     size_t in_elem() const { return from_mix ? 4 : rs_elem(pcm_format); }
     size_t out_elem() const { return from_mix ? rs_elem(pcm_format) : 4; }
 };
@@ -2189,7 +2190,8 @@ int rs_launch(nhans_ctx* c, const char* name, const std::vector<ResampleRun>& ru
     ResampleRun* runs_dev = ws_take<ResampleRun>(c, runs.size());
     rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(ResampleRun), s); if (rc) return rc;
     Prof pr(c, s, name);
-    launch_resample(name, runs_dev, (int)runs.size(), tab, f, io.from_mix, io.pcm_format, io.quantise, io.wet, io.factor, lds, s);
+    launch_resample(name, runs_dev, (int)runs.size(), tab, f, io.from_mix, io.auto_wet, io.pcm_format, io.quantise, io.wet, io.factor, lds,
+                    s);
     pr.done(2.0 * f.J * (double)out_samples, in_bytes + (double)io.out_elem() * out_samples + 4.0 * runs.size() * f.tab.size());
     return NHANS_OK;
 }
@@ -2242,11 +2244,20 @@ struct RateStage {
     void restore(const Streams& saved) { st = saved; }
 };
 
+// The per-hop wet factors of a live push (level.hip wrote them): slot i's begin at w[off[i]], its first one being that of
+// the first hop the push makes final, hop N / 160 of a stream that had N samples.
+struct GainTab {
+    const float* w;
+    const int64_t* off;
+};
+
 // One push through a stage, its arguments checked by the caller: the runs of every stream (stream i brings the samples
 // [inoff[i], inoff[i + 1]) of `in` -- and of `mix`, where the kernel reads the mix --), ONE launch under `kernel`, then the
-// commit.  Where the launch did not go out (a return code, or launch_error_pending()) nothing is committed.
+// commit.  Where the launch did not go out (a return code, or launch_error_pending()) nothing is committed.  gains
+// (io.auto_wet): the table the runs of each stream read their hops' factors from.
 int stage_push(nhans_ctx* c, RateStage& g, const char* kernel, const RateIo& io, const void* in, const float* mix,
-               const int64_t* inoff, const int* end, void* out, const int64_t* outoff, int64_t* counts, hipStream_t s) {
+               const int64_t* inoff, const int* end, void* out, const int64_t* outoff, int64_t* counts, hipStream_t s,
+               const GainTab* gains = nullptr) {
     std::vector<ResampleRun> runs;
     std::vector<RateStage::Span> e(g.S);
     size_t lds = 0;
@@ -2254,8 +2265,13 @@ int stage_push(nhans_ctx* c, RateStage& g, const char* kernel, const RateIo& io,
     for (int i = 0; i < g.S; ++i) {
         const int64_t cnt = inoff[i + 1] - inoff[i];
         e[i] = g.plan(i, cnt, end && end[i]);
+        const size_t first = runs.size();
         g.add_runs(runs, &lds, i, static_cast<const char*>(in) + inoff[i] * io.in_elem(), mix ? mix + inoff[i] : nullptr,
                    out ? static_cast<char*>(out) + outoff[i] * io.out_elem() : nullptr, io.out_elem(), cnt, e[i]);
+        for (size_t k = first; gains && k < runs.size(); ++k) {
+            runs[k].wtab = gains->w + gains->off[i];
+            runs[k].hop0 = g.st.N[i] / kHop;
+        }
         tin += cnt; tout += e[i].En - e[i].Eo;
     }
     const int rc = rs_launch(c, kernel, runs, g.tab, *g.f, io, lds, (double)tin * (io.in_elem() + (mix ? 4 : 0)), tout, s);
@@ -2485,6 +2501,25 @@ void nhans_resampler_close(nhans_resampler* o) {
 // push runs the three stages inside ONE Call on one stream; the stages' own workspace needs (run tables, the online
 // staging) follow each other in the context's workspace, which stream order makes safe, and nothing a later stage reads
 // lives there.
+
+// The level meter of a live object (nhans_level_live_enable; level.hip): per slot a double-buffered state of kLevelState
+// doubles -- a push reads half cur[i] and writes the other one, as RateStage::hist --, and the gain table of the last
+// push, which the outgoing stage reads and which therefore is a buffer of the object, not workspace.  The hops a slot's
+// stream has are those of the outgoing stage's sample count (level_hops), so the snapshot of a push is h0 and cur alone.
+struct LevelMeter {
+    bool on = false, auto_wet = false;
+    int W = 0;                      // the window of the meter and of the automatic factor (0: cumulative)
+    double wmax = 1.0;
+    double* state = nullptr;        // [2][S][kLevelState]
+    float* wtab = nullptr;
+    size_t wtab_cap = 0;            // (floats)
+    struct Slots {
+        std::vector<int64_t> h0;    // the first hop of the slot's stream the state knows
+        std::vector<char> cur;
+    } st;
+    std::vector<int64_t> woff;      // the last push's hops per slot, as offsets into wtab ([S + 1]; empty: none to read)
+};
+
 struct nhans_live {
     nhans_ctx* c = nullptr;
     int device = 0, S = 0, in_format = 0, out_format = 0;
@@ -2497,6 +2532,9 @@ struct nhans_live {
     float *mid = nullptr, *den = nullptr, *mix = nullptr;   // the push's 16 kHz input / denoised / mixed pieces
     size_t mid_cap = 0, out_cap = 0;                        // (floats)
     bool can_rewind = false;
+    LevelMeter lv;
+    LevelMeter::Slots undo_lv;
+    double* lv_half(int k, int i) const { return lv.state + ((size_t)k * S + i) * kLevelState; }
 };
 
 namespace {
@@ -2558,6 +2596,49 @@ int live_reserve(nhans_live* o, size_t n_mid, size_t n_out) {
     return NHANS_OK;
 }
 
+int64_t level_hops(int64_t emitted, bool ended) { return ended ? (emitted + kHop - 1) / kHop : emitted / kHop; }
+
+// The level launch of a push whose online stage has put the pieces [ooff) into den / mix: one run per slot with new hops,
+// the gains into lv.wtab from woff[i] on, the state into the half the slot's next push will read.  Host state does not
+// move here: *next is what lv.st becomes once the whole push has gone out.
+int live_level(nhans_live* o, const int64_t* ooff, const int* end, hipStream_t s, std::vector<int64_t>* woff,
+               LevelMeter::Slots* next) {
+    nhans_ctx* c = o->c;
+    LevelMeter& lv = o->lv;
+    const int S = o->S;
+    woff->assign(S + 1, 0);
+    *next = lv.st;
+    for (int i = 0; i < S; ++i) {
+        const int64_t N = o->out.st.N[i];
+        const bool was = o->out.st.ended[i];
+        (*woff)[i + 1] = (*woff)[i] + level_hops(N + ooff[i + 1] - ooff[i], was || (end && end[i])) - level_hops(N, was);
+    }
+    if ((size_t)(*woff)[S] > lv.wtab_cap) {
+        const size_t want = std::max<size_t>({(size_t)(*woff)[S], 2 * lv.wtab_cap, 256});
+        const int rc = live_grow(&lv.wtab, want); if (rc) return rc;
+        lv.wtab_cap = want;
+    }
+    std::vector<LevelRun> runs;
+    for (int i = 0; i < S; ++i) {
+        const int64_t nh = (*woff)[i + 1] - (*woff)[i];
+        if (nh == 0) continue;
+        const int64_t first = o->out.st.N[i] / kHop;     // (new hops: the stream had not ended, its hops were whole)
+        const int k = lv.st.cur[i];
+        runs.push_back({o->den + ooff[i], o->mix + ooff[i], first > lv.st.h0[i] ? o->lv_half(k, i) : nullptr, o->lv_half(1 - k, i),
+                        o->lv_half(1 - k, i) + kLevelMeter, lv.wtab + (*woff)[i], (long long)(ooff[i + 1] - ooff[i]),
+                        (long long)first, (long long)nh, (long long)lv.st.h0[i], lv.W, lv.wmax});
+        next->cur[i] = (char)(1 - k);
+    }
+    if (runs.empty()) return NHANS_OK;
+    int rc = ws_reserve(c, ws_size(runs.size(), sizeof(LevelRun))); if (rc) return rc;
+    LevelRun* runs_dev = ws_take<LevelRun>(c, runs.size());
+    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(LevelRun), s); if (rc) return rc;
+    Prof pr(c, s, "live_level");
+    launch_level("live_level", runs_dev, (int)runs.size(), s);
+    pr.done(9.0 * (double)(ooff[S] - ooff[0]), 8.0 * (double)(ooff[S] - ooff[0]) + (double)runs.size() * 2 * kLevelState * 8);
+    return NHANS_OK;
+}
+
 int live_push_body(nhans_live* o, const void* in, const int64_t* inoff, const int* end, void* out, const int64_t* outoff,
                    int64_t* counts, hipStream_t s) {
     if (!inoff || !outoff || !counts) return fail(NHANS_EINVAL, "nhans_live_push: null argument");
@@ -2590,10 +2671,24 @@ int live_push_body(nhans_live* o, const void* in, const int64_t* inoff, const in
     if (rc || launch_error_pending()) return rc;          // (a launch error is reported by the entry point; no stage has committed)
     rc = online_push_body(o->on, o->mid, moff.data(), end, o->den, o->mix, ooff.data(), got.data(), s);
     if (rc || launch_error_pending()) { o->in.restore(was_in); return rc; }
-    rc = stage_push(c, o->out, "live_out", {true, o->out_format, 0, o->wet, o->out_scale}, o->den, o->wet != 0.f ? o->mix : nullptr,
-                    ooff.data(), end, out, outoff, counts, s);
+    // (an object that never enabled its meter takes none of the branches below: launch for launch the push it was)
+    std::vector<int64_t> woff;
+    LevelMeter::Slots lv_next;
+    if (o->lv.on) {
+        rc = live_level(o, ooff.data(), end, s, &woff, &lv_next);
+        if (rc || launch_error_pending()) { o->in.restore(was_in); online_undo(o->on); o->can_rewind = false; return rc; }
+    }
+    const bool auto_wet = o->lv.on && o->lv.auto_wet;
+    const GainTab gains{o->lv.wtab, woff.data()};
+    rc = stage_push(c, o->out, "live_out", {true, o->out_format, 0, o->wet, o->out_scale, auto_wet}, o->den,
+                    auto_wet || o->wet != 0.f ? o->mix : nullptr, ooff.data(), end, out, outoff, counts, s, auto_wet ? &gains : nullptr);
     if (rc || launch_error_pending()) { o->in.restore(was_in); online_undo(o->on); o->can_rewind = false; return rc; }
     o->undo_in = was_in; o->undo_out = was_out;
+    if (o->lv.on) {
+        o->undo_lv = o->lv.st;
+        o->lv.st = lv_next;
+        o->lv.woff = woff;
+    }
     o->can_rewind = true;
     return NHANS_OK;
 }
@@ -2601,8 +2696,9 @@ int live_push_body(nhans_live* o, const void* in, const int64_t* inoff, const in
 void live_free(nhans_live* o) {
     if (o->on) nhans_online_close(o->on);
     o->in.release(); o->out.release();
-    for (float* p : {o->mid, o->den, o->mix})
+    for (float* p : {o->mid, o->den, o->mix, o->lv.wtab})
         if (p) (void)hipFree(p);
+    if (o->lv.state) (void)hipFree(o->lv.state);
     delete o;
 }
 
@@ -2676,6 +2772,7 @@ int nhans_live_restart(nhans_live* o, int slot) {
     // (nothing is cleared on the device: streams of 0 samples read none of the carried state, in any of the stages)
     online_restart_slot(o->on, slot);
     o->in.restart(slot); o->out.restart(slot);
+    if (o->lv.on) { o->lv.st.h0[slot] = 0; o->lv.woff.clear(); }     // (hop 0 reads none of the carried level state)
     o->can_rewind = false;
     return NHANS_OK;
 }
@@ -2740,6 +2837,7 @@ int nhans_live_rewind(nhans_live* o) {
     o->in.restore(o->undo_in);
     online_undo(o->on);
     o->out.restore(o->undo_out);
+    if (o->lv.on) { o->lv.st = o->undo_lv; o->lv.woff.clear(); }
     o->can_rewind = false;
     return NHANS_OK;
 }
@@ -2766,6 +2864,114 @@ int nhans_capture_live_embeddings(const nhans_live* o, int slot, float* ea, floa
     Call call(o->c, stream);
     if (call.rc) return call.rc;
     return call.finish(capture_embeddings_body(o->on, "nhans_capture_live_embeddings", slot, ea, eb, call.s));
+}
+
+// ---- level meter and automatic compensation (include/nhans_hip.h: nhans_level_*) ----
+int64_t nhans_level_hops(int64_t emitted, int ended) {
+    if (emitted < 0) return fail(NHANS_EINVAL, "nhans_level_hops: negative sample count");
+    return level_hops(emitted, ended != 0);
+}
+
+int nhans_level_live_enable(nhans_live* o, void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_level_live_enable: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    if (!o->has_wet)
+        return call.finish(fail(NHANS_EINVAL, "nhans_level_live_enable: the object was opened without NHANS_LIVE_WET "
+                                              "(the meter reads the mixed round trip)"));
+    if (o->lv.on) return call.finish(NHANS_OK);
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->lv.state), (size_t)2 * o->S * kLevelState * sizeof(double));
+    if (e != hipSuccess)
+        return call.finish(fail(NHANS_ENOMEM, std::string("nhans_level_live_enable: hipMalloc failed: ") + hipGetErrorString(e)));
+    // (nothing is cleared: a slot's first hop h0 reads none of the state)
+    o->lv.st.h0.resize(o->S);
+    for (int i = 0; i < o->S; ++i) o->lv.st.h0[i] = level_hops(o->out.st.N[i], o->out.st.ended[i]);
+    o->lv.st.cur.assign(o->S, 0);
+    o->lv.on = true;
+    o->can_rewind = false;
+    return call.finish(NHANS_OK);
+}
+
+namespace {
+int level_check(const char* fn, int window_hops, int lowest, double wmax) {
+    if (window_hops < lowest || window_hops > kLevelRing)
+        return fail(NHANS_EINVAL, std::string(fn) + ": window_hops " + std::to_string(window_hops) + " outside [" +
+                                  std::to_string(lowest) + ", " + std::to_string(kLevelRing) + "]");
+    if (!(wmax >= 0.0) || !std::isfinite(wmax)) return fail(NHANS_EINVAL, std::string(fn) + ": wmax must be finite and >= 0");
+    return NHANS_OK;
+}
+}  // namespace
+
+int nhans_level_live_auto(nhans_live* o, int window_hops, double wmax) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_level_live_auto: null object");
+    if (!o->lv.on) return fail(NHANS_EINVAL, "nhans_level_live_auto: the meter is not enabled (nhans_level_live_enable)");
+    const int rc = level_check("nhans_level_live_auto", window_hops, -1, wmax); if (rc) return rc;
+    o->lv.auto_wet = window_hops >= 0;
+    if (window_hops >= 0) { o->lv.W = window_hops; o->lv.wmax = wmax; }
+    o->can_rewind = false;
+    return NHANS_OK;
+}
+
+int nhans_level_live_read(nhans_live* o, int slot, double* out, void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_level_live_read: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    int rc = slot_check(o->S, slot, "nhans_level_live_read"); if (rc) return call.finish(rc);
+    if (!out) return call.finish(fail(NHANS_EINVAL, "nhans_level_live_read: null argument"));
+    if (!o->lv.on) return call.finish(fail(NHANS_EINVAL, "nhans_level_live_read: the meter is not enabled (nhans_level_live_enable)"));
+    if (level_hops(o->out.st.N[slot], o->out.st.ended[slot]) <= o->lv.st.h0[slot])
+        return call.finish(fail(NHANS_ESHORT, "nhans_level_live_read: slot " + std::to_string(slot) + " has no final hop yet"));
+    hipError_t e = hipMemcpyAsync(out, o->lv_half(o->lv.st.cur[slot], slot) + kLevelMeter, 8 * sizeof(double), hipMemcpyDeviceToHost, call.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(call.s);
+    if (e != hipSuccess) return call.finish(fail(NHANS_EHIP, std::string("nhans_level_live_read: ") + hipGetErrorString(e)));
+    return call.finish(NHANS_OK);
+}
+
+int64_t nhans_level_live_gains(nhans_live* o, int slot, float* out, int64_t cap, void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_level_live_gains: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    int rc = slot_check(o->S, slot, "nhans_level_live_gains"); if (rc) return call.finish(rc);
+    if (!o->lv.on) return call.finish(fail(NHANS_EINVAL, "nhans_level_live_gains: the meter is not enabled (nhans_level_live_enable)"));
+    const int64_t n = o->lv.woff.empty() ? 0 : o->lv.woff[slot + 1] - o->lv.woff[slot];
+    if (!out || n == 0) { rc = call.finish(NHANS_OK); return rc ? rc : n; }
+    if (cap < n)
+        return call.finish(fail(NHANS_EINVAL, "nhans_level_live_gains: room for " + std::to_string(cap) + " gains, " +
+                                              std::to_string(n) + " needed"));
+    hipError_t e = hipMemcpyAsync(out, o->lv.wtab + o->lv.woff[slot], (size_t)n * sizeof(float), hipMemcpyDeviceToHost, call.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(call.s);
+    if (e != hipSuccess) return call.finish(fail(NHANS_EHIP, std::string("nhans_level_live_gains: ") + hipGetErrorString(e)));
+    rc = call.finish(NHANS_OK);
+    return rc ? rc : n;
+}
+
+int nhans_level_gains(nhans_ctx* c, const float* den, const float* mix, const int64_t* off, int nclips, int window_hops,
+                      double wmax, float* w_out, double* sums_out, void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    if (!off || nclips < 0) return call.finish(fail(NHANS_EINVAL, "nhans_level_gains: null argument"));
+    int rc = level_check("nhans_level_gains", window_hops, 0, wmax); if (rc) return call.finish(rc);
+    std::vector<LevelRun> runs;
+    int64_t hops = 0;
+    for (int i = 0; i < nclips; ++i) {
+        const int64_t n = off[i + 1] - off[i];
+        if (n < 0) return call.finish(fail(NHANS_EINVAL, "nhans_level_gains: clip " + std::to_string(i) + " has a negative sample count"));
+        const int64_t nh = level_hops(n, true);
+        if (nh > 0 && (!den || !mix || !w_out)) return call.finish(fail(NHANS_EINVAL, "nhans_level_gains: null buffer"));
+        if (nh > 0)
+            runs.push_back({den + off[i], mix + off[i], nullptr, nullptr, sums_out ? sums_out + 8 * (size_t)i : nullptr, w_out + hops,
+                            (long long)n, 0, (long long)nh, 0, window_hops, wmax});
+        hops += nh;
+    }
+    if (runs.empty()) return call.finish(NHANS_OK);
+    rc = ws_reserve(c, ws_size(runs.size(), sizeof(LevelRun))); if (rc) return call.finish(rc);
+    LevelRun* runs_dev = ws_take<LevelRun>(c, runs.size());
+    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(LevelRun), call.s); if (rc) return call.finish(rc);
+    const double n = (double)(off[nclips] - off[0]);
+    Prof pr(c, call.s, "level_gains");
+    launch_level("level_gains", runs_dev, (int)runs.size(), call.s);
+    pr.done(9.0 * n, 8.0 * n + 4.0 * (double)hops);
+    return call.finish(NHANS_OK);
 }
 
 void nhans_live_close(nhans_live* o) {

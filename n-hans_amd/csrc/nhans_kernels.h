@@ -322,6 +322,10 @@ struct ResampleRun {
     long long k0;
     long long qrel0;        // q0 - k0
     int p0, n_new, cnt;
+    // the automatic mix source only (level.hip), left zero by the run builder: the push's per-hop wet factors, entry 0
+    // that of hop `hop0` of the stream -- sample k0 + rel takes wtab[(k0 + rel) / 160 - hop0] where the fixed mix takes wet
+    const float* wtab;
+    long long hop0;
 };
 constexpr int kResampleRun = 1024;      // outputs per workgroup at most
 constexpr int kResampleInt16 = 0, kResampleFloat32 = 1;
@@ -329,8 +333,10 @@ size_t resample_run_lds_bytes(const ResampleFilter& f, int p0, int cnt);
 // from_mix false: PCM of pcm_format -> float32, rounded to the int16 grid with `quantise`, then float32(double(y) / factor)
 // when factor != 0 (the fixed-peak normalisation of a live stream).  from_mix true: the wet/dry mix -> PCM of pcm_format,
 // float32(double(y) * factor) before the rounding.  A run table that needs more than 64 KB of LDS is refused.
+// auto_wet (from_mix only): the wet factor of a sample is its hop's entry of the run's gain table, not `wet`.
 void launch_resample(const char* kernel, const ResampleRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
-                     bool from_mix, int pcm_format, int quantise, float wet, double factor, size_t lds_bytes, hipStream_t s);
+                     bool from_mix, bool auto_wet, int pcm_format, int quantise, float wet, double factor, size_t lds_bytes,
+                     hipStream_t s);
 
 // peak + normalise: blocks of <= kNormBlock samples; block b belongs to a clip whose blocks are [pb0, pb0 + pbn)
 struct NormBlock {
@@ -342,5 +348,26 @@ void launch_peak_partial(const float* x, const NormBlock* blocks_dev, int nblock
 void launch_peak_normalise(const float* x, const NormBlock* blocks_dev, int nblocks, const float* partial, float* out, hipStream_t s);
 // out[i] = mean_c in[c * n + i] (channel-major planes of n samples; out may be plane 0)
 void launch_channel_mean(const float* in, int nchan, int64_t n, float* out, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// Level meter and automatic compensation (level.hip; include/nhans_hip.h: nhans_level_*).  One workgroup: the hops
+// [hop_first, hop_first + nh) of one stream or clip -- hop h = samples [160 h, 160 h + 160), the last one of an ended
+// stream shorter -- whose samples are at den / mix from sample 160 * hop_first on, n_new of them.  It writes one gain per
+// hop to wtab and, where asked, the carried state and the meter.
+// State of a stream, kLevelState doubles: [3][256] the powers Pd, Pr, Pm of the last <= 256 hops (hop j at j mod 256),
+// [3] the running sums since hop h0, [8] the meter (nhans_level_live_read).
+struct LevelRun {
+    const float* den;
+    const float* mix;
+    const double* in;       // the state before hop_first; nullable: there is none (hop_first == h0)
+    double* out;            // nullable: the state after the last hop is not kept
+    double* meter;          // nullable: 8 doubles, the meter after the last hop
+    float* wtab;            // nh gains
+    long long n_new, hop_first, nh, h0;
+    int W;                  // window in hops, 1 .. 256; 0: cumulative since h0
+    double wmax;
+};
+constexpr int kLevelRing = 256, kLevelSums = 3 * kLevelRing, kLevelMeter = kLevelSums + 3, kLevelState = kLevelMeter + 8 + 5;
+void launch_level(const char* kernel, const LevelRun* runs_dev, int nruns, hipStream_t s);
 
 }  // namespace nhans

@@ -11,7 +11,8 @@
 // a push only changes where an input sample is fetched from (the caller's new samples or the J carried ones), never the
 // arithmetic on it.  The body is a template over a source (PCM int16 / float32, or the wet/dry mix of a live session
 // formed while the span is staged) and a sink (float32 with the optional int16 grid and fixed peak, or scaled PCM);
-// the four pairs in use are instantiated: int16 -> float, float32 -> float, mix -> int16, mix -> float32.
+// the six pairs in use are instantiated: int16 -> float, float32 -> float, and the fixed and the automatic mix -> int16 and
+// -> float32.
 #include "nhans_kernels.h"
 
 #include <cmath>
@@ -129,13 +130,32 @@ struct PcmSource {
         return (float)static_cast<const T*>(r.src)[rel];
     }
 };
-// the combined stream c of a live session, stored nowhere: three separately rounded float32 operations (numpy's
-// `den + (mix - den) * factor`), never contracted; with mix == nullptr (wet factor 0) c is den and mix is not read
+// d + (m - d) * w in three separately rounded float32 operations (numpy's `den + (mix - den) * factor`).  The pragma is
+// what keeps them apart: the _rn intrinsics are plain operators compiled under the translation unit's contraction mode,
+// and the compiler fuses their product into the sum -- one rounding instead of two, a last-bit difference for every
+// factor that is not a power of two.
+__device__ __forceinline__ float mix_sample(float d, float m, float w) {
+#pragma clang fp contract(off)
+    const float r = m - d;
+    const float p = r * w;
+    return d + p;
+}
+
+// the combined stream c of a live session, stored nowhere: mix_sample of the push's two pieces, never contracted; with
+// mix == nullptr (wet factor 0) c is den and mix is not read
 struct MixSource {
     static __device__ __forceinline__ float at(const ResampleRun& r, long long rel, float wet) {
         const float d = static_cast<const float*>(r.src)[rel];
         if (!r.mix) return d;
-        return __fadd_rn(d, __fmul_rn(__fsub_rn(r.mix[rel], d), wet));
+        return mix_sample(d, r.mix[rel], wet);
+    }
+};
+// the same with the hop's own factor from the push's gain table (level.hip wrote it, one launch earlier on the stream)
+// where MixSource takes the scalar: hop (k0 + rel) / 160 of the stream, entry 0 of the table being hop r.hop0
+struct AutoMixSource {
+    static __device__ __forceinline__ float at(const ResampleRun& r, long long rel, float) {
+        const float d = static_cast<const float*>(r.src)[rel];
+        return mix_sample(d, r.mix[rel], r.wtab[(r.k0 + rel) / kHop - r.hop0]);
     }
 };
 
@@ -248,13 +268,15 @@ void launch_channel_mean(const float* in, int nchan, int64_t n, float* out, hipS
 }
 
 void launch_resample(const char* kernel, const ResampleRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
-                     bool from_mix, int pcm_format, int quantise, float wet, double factor, size_t lds_bytes, hipStream_t s) {
+                     bool from_mix, bool auto_wet, int pcm_format, int quantise, float wet, double factor, size_t lds_bytes,
+                     hipStream_t s) {
     if (nruns <= 0) return;
     if (lds_bytes > (size_t)64 << 10) { note_refusal(kernel); return; }
     const int tab4 = (int)(f.tab.size() / 4);
     const bool i16 = pcm_format == kResampleInt16;
     auto* fn = !from_mix ? (i16 ? resample_kernel<PcmSource<int16_t>, FloatSink> : resample_kernel<PcmSource<float>, FloatSink>)
-                         : (i16 ? resample_kernel<MixSource, PcmSink<int16_t>> : resample_kernel<MixSource, PcmSink<float>>);
+               : !auto_wet ? (i16 ? resample_kernel<MixSource, PcmSink<int16_t>> : resample_kernel<MixSource, PcmSink<float>>)
+                           : (i16 ? resample_kernel<AutoMixSource, PcmSink<int16_t>> : resample_kernel<AutoMixSource, PcmSink<float>>);
     NHANS_LAUNCH(kernel, fn, dim3(nruns), dim3(256), lds_bytes, s, runs_dev, tab_dev, f.L, f.M, f.J, tab4, quantise, wet, factor);
 }
 

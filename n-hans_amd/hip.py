@@ -32,6 +32,8 @@ EXPORTS = [
     "nhans_live_close", "nhans_online_set_lookahead", "nhans_lookahead_live_emitted", "nhans_lookahead_live_set",
     "nhans_capture_plan", "nhans_capture_enable", "nhans_capture_context", "nhans_capture_embeddings",
     "nhans_capture_live_enable", "nhans_capture_live_context", "nhans_capture_live_embeddings",
+    "nhans_level_hops", "nhans_level_live_enable", "nhans_level_live_auto", "nhans_level_live_read",
+    "nhans_level_live_gains", "nhans_level_gains",
 ]
 PCM_INT16, PCM_FLOAT32 = 0, 1
 RESAMPLE_QUANTISE = 1
@@ -41,6 +43,7 @@ CAPTURE_SAMPLES = 32240
 CAPTURE_A, CAPTURE_B = 0, 1
 CAPTURE_NORMALISE = 1
 ESHORT = -4
+LEVEL_MAX_WINDOW = 256
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25
 ABI_VERSION = 5
@@ -186,6 +189,18 @@ def load():
         for name in EXPORTS:
             if name.startswith("nhans_capture_"):
                 getattr(lib, name).restype = ctypes.c_int
+    # (the level meter of a live session came after the captured conditioning: looked up by symbol)
+    if hasattr(lib, "nhans_level_hops"):
+        lib.nhans_level_hops.argtypes = [ctypes.c_int64, ctypes.c_int]
+        lib.nhans_level_live_enable.argtypes = [vp, vp]
+        lib.nhans_level_live_auto.argtypes = [vp, ctypes.c_int, ctypes.c_double]
+        lib.nhans_level_live_read.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), vp]
+        lib.nhans_level_live_gains.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.c_int64, vp]
+        lib.nhans_level_gains.argtypes = [vp, vp, vp, i64p, ctypes.c_int, ctypes.c_int, ctypes.c_double, vp, vp, vp]
+        for name in EXPORTS:
+            if name.startswith("nhans_level_"):
+                getattr(lib, name).restype = ctypes.c_int
+        lib.nhans_level_hops.restype = lib.nhans_level_live_gains.restype = ctypes.c_int64
     lib.nhans_crc32c.argtypes = [ctypes.c_uint32, vp, ctypes.c_size_t]
     lib.nhans_crc32c.restype = ctypes.c_uint32
     for name in ("nhans_create", "nhans_create_ex", "nhans_set_option", "nhans_stft_features", "nhans_embed", "nhans_mask_net",

@@ -7,6 +7,7 @@ LiveSession works over engine.Engine (torch device memory, the engine's current 
 hiprt memory, the null stream).  emitted() restates the output contract of the header in Python so that it can be checked
 without a device."""
 import ctypes
+import math
 
 import numpy as np
 
@@ -22,6 +23,47 @@ def emitted(n, ended, in_rate, out_rate, lookahead=online.LOOKAHEAD):
                              % (in_rate, out_rate, ", ".join(str(v) for v in resample.RATES)))
     n16 = resample.emitted(n, ended, in_rate, spec.FS)
     return resample.emitted(online.emitted(n16, ended, lookahead), ended, spec.FS, out_rate)
+
+
+def level_hops(emitted, ended):
+    """nhans_level_hops restated: final hops of a stream that has emitted `emitted` 16 kHz samples."""
+    if emitted < 0:
+        raise ValueError("level_hops: negative sample count")
+    return -(-emitted // spec.HOP) if ended else emitted // spec.HOP
+
+
+def _dbfs(power, samples):
+    """10 log10 of the mean square of `samples` samples whose squares sum to `power` (-inf for silence)."""
+    return 10.0 * math.log10(power / samples) if power > 0 and samples > 0 else -math.inf
+
+
+def level_gains(engine, den, mix, window_hops=200, wmax=1.0, sums=False):
+    """The per-hop automatic wet factors of whole 16 kHz clips (nhans_level_gains: the kernel of a live session's meter
+    over ended streams that start at hop 0): den / mix one float32 array or a list of them, window_hops 0 .. 256 (0:
+    cumulative, the reference's --ac figure to date), wmax the clamp.  Returns one float32 array of ceil(n / 160) gains
+    per clip (a single array for a single array); with sums=True also the eight doubles nhans_level_live_read defines,
+    per clip."""
+    single = isinstance(den, np.ndarray) and den.ndim == 1
+    dens, mixes = ([den], [mix]) if single else (list(den), list(mix))
+    if len(dens) != len(mixes) or any(len(d) != len(m) for d, m in zip(dens, mixes)):
+        raise ValueError("level_gains: den and mix are the same clips, sample for sample")
+    mem = context.Mem(engine)
+    d, off = context.flat(dens)
+    m, _ = context.flat(mixes)
+    hoff = context.offsets(level_hops(len(x), True) for x in dens)
+    dd, dm = mem.up(d), mem.up(m)
+    dw, ds = mem.empty(hoff[-1]), mem.empty(8 * len(dens), np.float64)
+    try:
+        hip.check(hip.load().nhans_level_gains(engine.handle, mem.p(dd), mem.p(dm), hip.i64_array(off), len(dens),
+                                               int(window_hops), float(wmax), mem.p(dw), mem.p(ds), mem.stream()))
+        w = np.array(mem.down(dw, hoff[-1]), dtype=np.float32)
+        s = np.array(mem.down(ds, 8 * len(dens), np.float64), dtype=np.float64).reshape(len(dens), 8)
+    finally:
+        mem.free(dd, dm, dw, ds)
+    gains = [w[hoff[i]:hoff[i + 1]].copy() for i in range(len(dens))]
+    if single:
+        return (gains[0], s[0]) if sums else gains[0]
+    return (gains, s) if sums else gains
 
 
 def default_out_scale(peak, out_dtype):
@@ -60,6 +102,7 @@ class LiveSession(online.Slots):
         self.peak = float(peak)
         self.out_scale = default_out_scale(peak, out_dtype) if out_scale is None else float(out_scale)
         self.has_wet = bool(wet)
+        self._level_window = 0          # (the meter's window: cumulative until set_auto_wet names one)
         h = ctypes.c_void_p()
         hip.check(self.lib.nhans_live_open_slots(engine.handle, self.S, self.in_rate, resample._format(self.in_dtype),
                                                  self.peak, self.out_rate, resample._format(self.out_dtype), self.out_scale,
@@ -70,6 +113,44 @@ class LiveSession(online.Slots):
     def set_wet(self, w):
         """The wet factor of the pushes that follow (non-zero needs wet=True at construction)."""
         hip.check(self.lib.nhans_live_set_wet(self.handle, float(w)))
+
+    # ---- level meter and automatic compensation (include/nhans_hip.h: nhans_level_*) -----------
+    def enable_levels(self):
+        """Every slot gets its level state (needs wet=True; idempotent): pushes from now on also meter the hops they
+        make final, one small launch more per push."""
+        hip.check(self.lib.nhans_level_live_enable(self.handle, self.mem.stream()))
+
+    def set_auto_wet(self, window_hops=200, wmax=1.0):
+        """The reference's --ac, live: the hops later pushes make final are mixed with
+        w = clip((Sd / Sr) / 20, 0, wmax), Sd and Sr the denoised and the removed power of the last window_hops hops
+        (10 ms each, 1 .. 256; 0: of the whole stream so far).  The factor is constant over a hop and steps between
+        hops: a short window follows the signal and steps more.  None switches back to the factor of set_wet, which
+        stays stored (and can be set) meanwhile.  Needs enable_levels()."""
+        if window_hops is None:
+            hip.check(self.lib.nhans_level_live_auto(self.handle, -1, 0.0))
+        else:
+            hip.check(self.lib.nhans_level_live_auto(self.handle, int(window_hops), float(wmax)))
+            self._level_window = int(window_hops)
+
+    def levels(self, slot):
+        """The meter of `slot` after its last final hop (one small copy, one stream sync): the window sums sd / sr / sm
+        (denoised, removed, mixed), hops, the law's gain w of that hop, snr_est = sd / sr, and the three levels in dBFS
+        over the window's samples -- derived here from the sums, taking every hop as 160 samples.  NhansError with
+        .code == hip.ESHORT before the slot's first hop."""
+        out = (ctypes.c_double * 8)()
+        hip.check(self.lib.nhans_level_live_read(self.handle, int(slot), out, self.mem.stream()))
+        sd, sr, sm, hops, w, snr = (float(v) for v in out[:6])
+        n = spec.HOP * (min(self._level_window, int(hops)) if self._level_window else int(hops))
+        return dict(sd=sd, sr=sr, sm=sm, hops=int(hops), w=w, snr_est=snr, denoised_dbfs=_dbfs(sd, n),
+                    removed_dbfs=_dbfs(sr, n), mixed_dbfs=_dbfs(sm, n))
+
+    def last_gains(self, slot):
+        """The gains of the hops the last push made final for `slot` (float32, hop order; empty after a rewind)."""
+        n = hip.check(self.lib.nhans_level_live_gains(self.handle, int(slot), None, 0, self.mem.stream()))
+        out = (ctypes.c_float * max(n, 1))()
+        if n:
+            hip.check(self.lib.nhans_level_live_gains(self.handle, int(slot), out, n, self.mem.stream()))
+        return np.array(out[:n], dtype=np.float32)
 
     # ---- pushes --------------------------------------------------------------------------------
     def _push(self, pin, ioff, end, dout, ooff, outc):

@@ -31,7 +31,15 @@ same pushes by turns (launches_per_push of both from a profiled pass), and the w
 of a one-entry capture_context beside a set_context of the same slot (p50 / max over --captures calls of each).  On a
 library from before the capture functions ($NHANS_LIB, for a same-box A/B) the enabled and capture figures are null and
 the line still carries the disabled push and set_context.
-    python tools/online_bench.py --capture [--streams 1,8] [--hops 1,4] [--pushes 200] [--captures 20] [--out F]"""
+    python tools/online_bench.py --capture [--streams 1,8] [--hops 1,4] [--pushes 200] [--captures 20] [--out F]
+
+--levels: what the level meter and the automatic wet factor (nhans_level_*) cost a live push.  Per (S, H) one line with
+mode "levels": push p50 / p99 of three S-slot live.LiveSession objects opened with the mixed round trip (48 kHz int16 in
+and out unless --in_rate / --out_rate say otherwise), the same pushes by turns -- "never" (no level call at all),
+"enabled" (enable_levels(), fixed factor 0.25) and "auto" (set_auto_wet(200, 1.0)) --, and launches_per_push and the
+live_level kernel time of each from a profiled pass.  On a library from before the level functions ($NHANS_LIB, for a
+same-box A/B) only "never" is there and the other figures are null.
+    python tools/online_bench.py --levels [--streams 1,16,64] [--hops 2] [--pushes 200] [--out F]"""
 import argparse
 import json
 import os
@@ -213,6 +221,76 @@ def capture(a):
     return 0
 
 
+def levels(a):
+    eng = engine.Engine("denoiser", precision="f16x3")
+    ca, cb = apply.normalise(synth.silent()), apply.normalise(synth.noise_context(1))
+    rate_in, rate_out = a.in_rate or 48000, a.out_rate or 48000
+    idx = (np.arange(int(30.0 * rate_in)) * float(spec.FS) / rate_in).astype(np.int64)
+    audio = synth.mixture(1, 30.0)[np.minimum(idx, int(30.0 * spec.FS) - 1)]
+    has = hasattr(hip.load(), "nhans_level_hops")
+    out = open(a.out, "a") if a.out else None
+    pct = lambda v, q: round(float(np.percentile(v, q)), 3) if len(v) else None
+    emb = eng.embed(eng.stft_features(torch.from_numpy(np.concatenate([ca, cb])).to(eng.device),
+                                      [0, len(ca), len(ca) + len(cb)], max_frames=spec.NOISE_WIN,
+                                      want_phase=False)[0].reshape(2, spec.NOISE_WIN, spec.BINS))
+    for S in [int(s) for s in a.streams.split(",")]:
+        for H in [int(h) for h in a.hops.split(",")]:
+            n = int(round(H * 0.010 * rate_in))
+            objs = {}
+            for k in ("never", "enabled", "auto") if has else ("never",):
+                o = live.LiveSession(eng, S, rate_in, rate_out, 32768, wet=True, lookahead=a.lookahead)
+                for i in range(S):
+                    o.set_embeddings(i, emb[0], emb[1])
+                o.set_wet(0.25)
+                if k != "never":
+                    o.enable_levels()
+                if k == "auto":
+                    o.set_auto_wet(200, 1.0)
+                objs[k] = o
+            pos = {k: 0 for k in objs}
+
+            def push(k):
+                i = pos[k] % (len(audio) - n)
+                pos[k] += n
+                objs[k].push([audio[i:i + n]] * S)
+
+            for k in objs:
+                for _ in range(40):
+                    push(k)
+            torch.cuda.synchronize()
+            ts = {k: [] for k in objs}
+            for _ in range(a.pushes):
+                for k in objs:
+                    ts[k].append(_timed(lambda: push(k)))
+            launches, level_ms = {}, {}
+            for k in objs:
+                eng.set_option("profile", 1)
+                eng.profile_reset()
+                for _ in range(10):
+                    push(k)
+                prof = eng.profile()
+                eng.set_option("profile", 0)
+                launches[k] = sum(v["calls"] for v in prof.values()) / 10
+                level_ms[k] = round(prof["live_level"]["ms"] / 10, 4) if "live_level" in prof else 0.0
+            for o in objs.values():
+                o.close()
+            line = {"mode": "levels", "streams": S, "hops_per_push": H, "push_audio_ms": H * 10, "pushes": a.pushes,
+                    "in_rate": rate_in, "out_rate": rate_out, "lookahead": a.lookahead}
+            for k in ("never", "enabled", "auto"):
+                line["push_ms_p50_" + k] = pct(ts.get(k, []), 50)
+                line["push_ms_p99_" + k] = pct(ts.get(k, []), 99)
+                line["launches_per_push_" + k] = launches.get(k)
+                line["live_level_ms_per_push_" + k] = level_ms.get(k)
+            line.update({"lib": os.path.basename(os.environ.get("NHANS_LIB") or "tree"), "precision": "f16x3",
+                         "weights": "synthetic seed 7"})
+            print(json.dumps(line), flush=True)
+            if out:
+                out.write(json.dumps(line) + "\n")
+                out.flush()
+    eng.close()
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--churn", action="store_true", help="slots that callers join and leave (see the top of this file)")
@@ -229,9 +307,12 @@ def main():
     ap.add_argument("--lookahead", type=int, default=spec.LOOKAHEAD, help="look-ahead L of every stream, 0 ... 17 frames")
     ap.add_argument("--capture", action="store_true", help="cost of the sample history and of a capture (see the top of this file)")
     ap.add_argument("--captures", type=int, default=20, help="--capture: timed capture_context / set_context calls")
+    ap.add_argument("--levels", action="store_true", help="cost of the level meter and the automatic wet factor (see the top of this file)")
     a = ap.parse_args()
     if a.churn:
         return churn(a)
+    if a.levels:
+        return levels(a)
     if a.capture:
         return capture(a)
     if a.live and not (a.in_rate and a.out_rate):
