@@ -237,7 +237,7 @@ void launch_scale_copy(const float* src, size_t n, float scale, float* dst, hipS
     NHANS_LAUNCH("scale_copy", scale_copy_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, n, scale, dst);
 }
 
-// Calibration tap (nhans_api.hip: activation exponents): running maximum of |x| * scale over a tensor.  Split tensors
+// Calibration tap (host_internal.h: activation exponents): running maximum of |x| * scale over a tensor.  Split tensors
 // are read as plain halfs -- the hi half of a value bounds it to 2^-11, and a lo half is never larger than its hi.
 __global__ void __launch_bounds__(256) absmax_kernel(const uint32_t* x, size_t nwords, int split, float scale, unsigned* slot) {
     float m = 0.f;

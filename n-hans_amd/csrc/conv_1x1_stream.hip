@@ -1,5 +1,5 @@
 // The stand-alone 1 x 1 strided `_transform` convolution of a channel-changing residual block whose conv2 runs in its
-// Winograd form (resblock2_1: 64 -> 128 channels, stride 2, SN/main.py:176-181; nhans_api.hip run_stack_chunk) as what it
+// Winograd form (resblock2_1: 64 -> 128 channels, stride 2, SN/main.py:176-181; host_net.hip run_stack_chunk) as what it
 // is: a STREAM.  1.75 GB read (every other pixel of every other image row of the block input, split NHWC) and 3.5 GB
 // written (f32 NHWC, added like a residual by conv2's epilogue) per pass of 3,776 frames against 2 x 64 x 128 MACs per
 // output element: the generic implicit-GEMM kernels -- 256-pixel tiles, one workgroup per CU, load -> multiply -> epilogue

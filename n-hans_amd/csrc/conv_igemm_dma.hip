@@ -569,7 +569,7 @@ SplitKPlan splitk_plan(const ConvArgs& a, int BN) {
 }
 }  // namespace
 
-// scratch bytes the split-K form of this launch needs (0: the launch does not split) -- nhans_api.hip sizes the
+// scratch bytes the split-K form of this launch needs (0: the launch does not split) -- host_net.hip sizes the
 // context's scratch from it, lazily
 size_t conv_splitk_scratch_bytes(const ConvArgs& a) {
     if (a.variant < 1) return 0;

@@ -543,7 +543,7 @@ void wino_geometry(ConvArgs& a) {
 }  // namespace
 
 // INVARIANT (round-5 advisor): this predicate must NOT read a tensor-LAYOUT field -- in_f32, out_split, id_split,
-// sat_limit.  nhans_api.hip (run_stack_chunk) asks it in a planning pass in which those fields are not final yet (block
+// sat_limit.  host_net.hip (run_stack_chunk) asks it in a planning pass in which those fields are not final yet (block
 // b is planned before block b + 1's readers are known) and derives the layouts from the answers; an answer that
 // depended on a layout would turn every call into the "eligibility changed between planning and launch" refusal.  A
 // layout combination the kernel does not implement is refused by launch_conv_wino() instead.
@@ -572,7 +572,7 @@ void launch_conv_wino(const ConvArgs& a0, hipStream_t s) {
     // A split-NHWC residual with an f32-NHWC output: the f32 channel assignment of the epilogue (a thread owns channels
     // 4 c8 .. + 3 and 32 + 4 c8 .. + 3, conv_wino_common.h) fetches its residual as two 16-byte pieces of THOSE channels,
     // which a split pixel does not hold contiguously (round-5 advisor: the instantiation existed and added channels
-    // 4 c8 + 4 .. + 7 to outputs 32 + 4 c8 .. + 3).  No plan of nhans_api.hip produces the pair -- an identity block's
+    // 4 c8 + 4 .. + 7 to outputs 32 + 4 c8 .. + 3).  No plan of host_net.hip produces the pair -- an identity block's
     // input and output are stored alike or the output is split --; should one ever, it is refused, not misread.
     if (a0.id_mode == 1 && a0.id_split && !a0.out_split) {
         note_refusal("conv_wino (split residual with an f32-stored output)");

@@ -1,0 +1,375 @@
+// What the host units of libnhans_hip.so share (the C ABI itself: include/nhans_hip.h).  One unit per subsystem:
+//   host_ctx.hip      error channel, blob, context, options, calibration, workspace growth, Call, status, profiling
+//   host_net.hip      conv launch sequences (tower, stack, head), STFT / iSTFT block tables, the offline entry points
+//   host_online.hip   nhans_online_*, nhans_capture_*
+//   host_rate.hip     rate-conversion stages, nhans_resample*, nhans_peak_normalise, nhans_channel_mean, nhans_resampler_*
+//   host_live.hip     nhans_live_*, nhans_lookahead_live_*, nhans_capture_live_*, nhans_level_*
+// A unit calls down only: ctx <- net <- online <- live and ctx <- rate <- live.  (One call goes up: the built-in calibration
+// of nhans_create runs the whole offline path, enhance_clips_body.)  Only what crosses a unit boundary is declared here;
+// everything else stays in its unit's anonymous namespace.
+// Nothing declared here joins the library's dynamic symbols (visibility hidden) except the object types the C header
+// names, which keep the default visibility they have always had.
+#pragma once
+#include "../../include/nhans_hip.h"
+#include "nhans_kernels.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <map>
+#include <string>
+#include <vector>
+
+using namespace nhans;
+
+#pragma GCC visibility push(hidden)
+
+// ---- host_ctx.hip ---------------------------------------------------------------------------------
+int fail(int code, const std::string& msg);       // sets nhans_last_error() (thread-local), returns code
+
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return fail(NHANS_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
+    } while (0)
+
+struct BlockGeo {
+    int kh, kw, sh, sw, cin, cout, hin, win, hout, wout;
+};
+
+constexpr int kNumAct = NHANS_NUM_ACTIVATIONS;
+constexpr int TA(int b, int j) { return 2 * b + j; }            // tower block b, conv j+1
+constexpr int SA(int b, int j) { return 8 + 2 * b + j; }        // stack block b, conv j+1
+constexpr int kActHead = 24;                                    // last_conv
+
+struct ProfEntry {
+    int calls = 0;
+    double flops = 0, bytes = 0, mfma = 0;      // algorithmic FLOPs / bytes; FLOPs the matrix cores executed
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+    double ms = 0;
+};
+
+#pragma GCC visibility pop
+
+// which convs of the stack ran in their Winograd form in the last chunk (run_stack_chunk)
+struct StackPlan {
+    bool wino[8][3] = {};      // [block][conv 1 | 2]
+};
+
+struct nhans_ctx {
+    int kind = 0, device = 0;
+    StackPlan last_plan;
+    float* blob_dev = nullptr;
+    size_t blob_bytes = 0;
+    std::map<std::string, const float*> arr;
+    std::map<std::string, size_t> arr_n;
+    std::vector<BlockGeo> tower, stack;
+    int cond_cols = 0;
+    std::vector<int> cond_off;      // column offset of conv j (= 2*block + {0,1})
+    // workspace
+    char* ws = nullptr;
+    size_t ws_bytes = 0, ws_top = 0;
+    // split-K scratch of the conv kernel (small launches only)
+    // Allocated LAZILY, sized by the launches that actually split (run_conv: conv_splitk_scratch_bytes) and grown up to
+    // 96 tiles x 32 groups x 128 KB = 384 MB, all the split-K rule of conv_igemm_dma.hip admits (round-5 advisor: 384 MB
+    // taken unconditionally at nhans_create was 3 GB for eight ranks sharing a device, and its failure failed the
+    // create).  A failed allocation is not an error: the launch walks its groups unsplit -- same bits, fewer CUs.
+    float* kscratch = nullptr;
+    size_t kscratch_bytes = 0;
+    static constexpr size_t kscratch_cap = (size_t)384 << 20;
+    bool kscratch_failed = false;
+    int stream_1x1 = 1;         // option stream_1x1: the stand-alone `_transform` conv on conv_1x1_stream.hip (0: the generic conv kernel; same bits)
+    int split_k = 1;            // option split_k: 0 = never split (the grouped walk inside one workgroup: same bits)
+    int* kcounter = nullptr;
+    int kcounter_n = 1024;
+    // Frame windows per pass of the stack.  Every launch runs whole "waves" of one workgroup per CU and all
+    // workgroups of a launch take the same time, so a launch whose tile count is not a multiple of 256
+    // leaves CUs idle for a tile time at its end: 1,024 frames give resblock4 (130 pixels per frame, 256-pixel
+    // x 4 channel tiles) 8.1 waves = 9.7 % lost, 3.9 % over the whole stack.  3,776 = 59 x 64 frames minimise
+    // the FLOP-weighted loss (0.18 %) among the sizes whose largest tensor (3,776 x 35 x 201 x 64 elements)
+    // still fits the kernels' 32-bit element offsets; the three ping-pong buffers are then 20 GB of the 288.
+    int64_t frames_per_chunk = 3776;
+    int contexts_per_chunk = 64;
+    int lookahead = kCenter;    // option lookahead: frame t of a clip sees the clip end at min(len, t + lookahead + 1) (offline calls)
+    // pinned staging ring for the small host tables (offsets, block lists) copied per call
+    char* pin = nullptr;
+    size_t pin_bytes = (size_t)16 << 20, pin_top = 0;
+    // profiling
+    bool profile = false;
+    std::map<std::string, ProfEntry> prof;
+    std::vector<hipEvent_t> event_pool;
+
+    int prec = 0;           // 0: f32 MFMA, 1: split-f16 x3 MFMA (activations in split NHWC)
+    int conv_variant = -1;  // 0: 128-pixel register-staged conv kernel, 1: 256-pixel LDS-DMA kernel,
+                            // 2: halo-reuse / wave-specialised LDS-DMA kernel where the conv allows it, else 1;
+                            // -1: automatic (measured best: 2 for split-f16, register-staged for f32)
+    int epi8 = 1;               // ConvArgs::epi8
+    int ilv = 1;                // ConvArgs::ilv
+    int wino = 1;               // ConvArgs::wino: 1-D Winograd form of the stride-1 stack convs (conv_wino.hip)
+    int wino_f32 = 1;           // tensors that only Winograd launches read are stored f32 NHWC (stored_f32())
+    long long* dbg = nullptr;   // NHANS_DEV builds: per-workgroup cycle stamps of the last conv launch
+    int* status_dev = nullptr;  // sticky NHANS_STATUS_* bits set by kernels (nhans_take_status)
+    std::map<std::pair<int, int>, float*> rs_tab;   // device copies of the rate converter's phase tables, by (rate_in, rate_out)
+    // Activation exponents: a split-f16 tensor is stored as x * 2^-e with one e per tensor of the network, chosen from
+    // the largest |x| a calibration pass saw so that the stored maximum is <= 2^kActTargetLog2 -- 2^8 below the f16
+    // limit (and the 1-D Winograd transform's worst-case gain of ~20 still fits).  Tensors: tower block b conv1/conv2
+    // outputs (2b, 2b+1), stack block b conv1/conv2 outputs (8+2b, 8+2b+1), last_conv output (24).  f32 tensors carry
+    // no exponent.  The flag of nhans_take_status stays as the backstop for inputs far outside the calibration.
+    int act_exp[kNumAct] = {};
+    float act_amax[kNumAct] = {};       // what the last calibration saw (diagnostics)
+    unsigned* amax_dev = nullptr;       // running maxima (float bits) while calibrating
+    bool calibrating = false;
+    // debug capture (nhans_debug_activation / nhans_debug_tower_activation): the tensor whose finished buffer the tap()
+    // points of the production launch sequences copy out as plain f32 NHWC, chunk after chunk; -1: none (every other call)
+    int cap_idx = -1;
+    float* cap_out = nullptr;
+    float up(int i) const { return prec ? ldexpf(1.f, act_exp[i]) : 1.f; }
+    float down(int i) const { return prec ? ldexpf(1.f, -act_exp[i]) : 1.f; }
+    // ordering of consecutive calls that share the workspace (see include/nhans_hip.h)
+    hipEvent_t tail_ev = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool have_tail = false;
+
+    const float* A(const std::string& n) const {
+        auto it = arr.find(n);
+        return it == arr.end() ? nullptr : it->second;
+    }
+    // packed conv weights / per-channel unscale vector of the active precision
+    const float* WP(const std::string& n) const { return A(prec ? n + "_h" : n); }
+    const float* WS(const std::string& conv) const { return prec ? A(conv + ".ws") : nullptr; }
+};
+
+#pragma GCC visibility push(hidden)
+
+int ws_reserve(nhans_ctx* c, size_t bytes);
+// Host -> device copy of a small table through the pinned ring, so the caller's (pageable, soon
+// destroyed) buffer is never the source of an in-flight asynchronous copy.
+int h2d(nhans_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t s);
+
+template <typename T> T* ws_take(nhans_ctx* c, size_t count) {
+    size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
+    T* p = reinterpret_cast<T*>(c->ws + c->ws_top);
+    c->ws_top += bytes;
+    return p;
+}
+inline size_t ws_size(size_t count, size_t elem) { return (count * elem + 255) & ~(size_t)255; }
+
+// RAII-less profiling bracket around one launch
+struct Prof {
+    nhans_ctx* c;
+    hipStream_t s;
+    ProfEntry* e = nullptr;
+    hipEvent_t a{}, b{};
+    static hipEvent_t take(nhans_ctx* c) {
+        hipEvent_t ev = nullptr;
+        if (!c->event_pool.empty()) { ev = c->event_pool.back(); c->event_pool.pop_back(); }
+        else (void)hipEventCreate(&ev);
+        return ev;
+    }
+    Prof(nhans_ctx* c_, hipStream_t s_, const char* name) : c(c_), s(s_) {
+        if (!c->profile) return;
+        if (name) e = &c->prof[name];
+        a = take(c);
+        b = take(c);
+        (void)hipEventRecord(a, s);
+    }
+    void done(double flops, double bytes, const char* late_name = nullptr, double mfma = 0) {
+        if (!c->profile) return;
+        if (late_name) e = &c->prof[late_name];
+        if (!e) return;
+        (void)hipEventRecord(b, s);
+        e->pending.emplace_back(a, b);
+        e->calls += 1;
+        e->flops += flops;
+        e->bytes += bytes;
+        e->mfma += mfma;
+    }
+};
+
+int check_ctx(nhans_ctx* c);
+// A launch the runtime rejected anywhere in the sequence just issued -> NHANS_EHIP.
+int launch_status();
+
+// Bracket of one hot-path entry point: selects the device, orders the call behind the previous
+// call on this context when that one ran on another stream (they share workspace, pinned tables
+// and split-K tickets), and on the way out collects launch failures and marks the new tail.
+struct Call {
+    nhans_ctx* c;
+    hipStream_t s;
+    int rc;
+    Call(nhans_ctx* c_, void* stream);
+    int finish(int body_rc);
+};
+
+// The same bracket for an entry point of an object that holds its context (nhans_online, nhans_resampler, nhans_live):
+// the null check with the entry point's own message first, then body(stream) inside the Call.
+template <typename Obj, typename Body>
+int object_call(Obj* o, const char* null_msg, void* stream, Body body) {
+    if (!o) return fail(NHANS_EINVAL, null_msg);
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(body(call.s));
+}
+
+// argument checks the streaming objects share
+int slot_check(int S, int slot, const char* fn);
+constexpr int64_t kMaxResampleClip = ((int64_t)1 << 31) - 1, kNoPushCap = std::numeric_limits<int64_t>::max();
+int push_check(const char* fn, const char* noun, int i, int64_t cnt, bool en, bool ended, const char* uncond, int64_t max_cnt);
+
+// ---- host_net.hip ---------------------------------------------------------------------------------
+struct StackBufs {
+    int* f_clip; int* f_t; int* f_T; int64_t* foff_dev; float* cb_all;
+    float* X; float* A; float* Y;
+    float* T;       // f32 output of a block's 1x1 `_transform` conv when its conv2 runs in Winograd form
+};
+size_t stack_ws_bytes(const nhans_ctx* c, int64_t total, int nclips, int64_t wf);
+void stack_take(nhans_ctx* c, int64_t total, int nclips, int64_t wf, StackBufs* sb);
+size_t tower_buf_floats(const nhans_ctx* c);
+size_t stft_blocks(const int64_t* soff, int nclips, int maxf);
+size_t istft_blocks(const int64_t* foff, int nclips);
+int stft_impl(nhans_ctx* c, const float* wav, const int64_t* soff, int nclips, int maxf, float* logmag,
+              float* phase, int64_t* dev_tables /*3*(nclips+1)*/, int* dev_blocks, std::vector<int64_t>* foff_out,
+              hipStream_t s, const char* prof_name = nullptr);
+int istft_impl(nhans_ctx* c, const float* logmag, const float* phase, const int64_t* foff, int nclips,
+               const int64_t* ooff, float* wav_out, int64_t* dev_tables, int* dev_blocks, hipStream_t s,
+               const char* prof_name = "istft_ola");
+int embed_impl(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, float* X, float* Ab, float* Y,
+               hipStream_t s);
+int mask_net_run(nhans_ctx* c, const float* win_src, const int* rb, const float* centre, int64_t total, int nclips,
+                 const float* ea, const float* eb, float* logits, float* denoised, const StackBufs& sb, int64_t wf,
+                 hipStream_t s);
+int enhance_clips_body(nhans_ctx* c, const float* mix, const int64_t* moff, int nclips, const float* ca,
+                       const int64_t* caoff, const float* cbw, const int64_t* cboff, float* den_wav,
+                       float* mixed_wav, float* logmag_out, float* phase_out, float* logits_out, float* emb_out,
+                       void* stream);
+
+// ---- host_online.hip (the layout of a slot's state: there) -------------------------------------------
+constexpr int kOnRows = 2 * kCenter + kIstftHopsPerBlock - 14;  // 42 >= 17 + 24
+constexpr int kOnDenRows = kIstftHopsPerBlock + 2;              // 24
+constexpr size_t kOnSamp = 0, kOnLm = kWin, kOnPh = kOnLm + (size_t)kOnRows * kBins, kOnDen = kOnPh + (size_t)kOnRows * kBins;
+constexpr size_t kOnSlot = (kOnDen + (size_t)kOnDenRows * kBins + 63) & ~(size_t)63;   // 22,144 floats = 88.6 KB
+struct OnStream {
+    int64_t N = 0, T = 0;
+    bool ended = false;
+};
+
+#pragma GCC visibility pop
+
+struct nhans_online {
+    nhans_ctx* c = nullptr;
+    int device = 0, S = 0;
+    bool mixed = false;
+    float* emb = nullptr;       // [2S, 512]: a-rows then b-rows
+    float* state = nullptr;     // [2][S][kOnSlot]
+    int cur = 0;
+    std::vector<OnStream> st, prev;
+    std::vector<char> cond;     // slot has conditioning (nhans_online_open: all; nhans_online_open_slots: none yet)
+    std::vector<int> la;        // slot's look-ahead L (nhans_online_set_lookahead; survives a restart, as conditioning does)
+    bool can_rewind = false;
+    // nhans_capture_enable: per slot the last kCaptureSamples samples pushed, sample k at position k mod kCaptureSamples
+    // (nullptr until enabled), and vlo: the oldest sample of the slot's current timeline the ring still holds.  The ring is
+    // not double-buffered as `state` is, so vlo only moves forward with what a push writes -- a rewound push has written too
+    // -- and goes back only where a new timeline starts (restart: 0) or the ring does (enable: N).
+    float* ring = nullptr;      // [S][kCaptureSamples]
+    std::vector<int64_t> vlo, whi;  // whi: how far a push has written the slot's timeline (> N after a rewind; for messages)
+    float* slot(int k, int i) const { return state + ((size_t)k * S + i) * kOnSlot; }
+};
+
+#pragma GCC visibility push(hidden)
+
+int64_t on_emitted(int64_t T, bool ended, int L);
+int64_t online_emit_count(const nhans_online* o, int i, int64_t cnt, bool en);
+void online_undo(nhans_online* o);
+int online_open_slots_body(nhans_ctx* c, int S, int want_mixed, hipStream_t s, nhans_online** out);
+void online_restart_slot(nhans_online* o, int slot);
+int online_set_context_body(nhans_online* o, int slot, const float* ca, int64_t na, const float* cbw, int64_t nb_,
+                            hipStream_t s, int64_t* first_frame);
+int online_set_embeddings_body(nhans_online* o, int slot, const float* ea, const float* eb, hipStream_t s, int64_t* first_frame);
+int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, const int* end, float* den_out,
+                     float* mix_out, const int64_t* outoff, int64_t* counts, hipStream_t s);
+int capture_enable_body(nhans_online* o, const char* fn, hipStream_t s);
+int capture_context_body(nhans_online* o, const char* fn_, int n, const int* slots, const int* which, int flags,
+                         hipStream_t s, int64_t* first_frame);
+int capture_embeddings_body(const nhans_online* o, const char* fn, int slot, float* ea, float* eb, hipStream_t s);
+
+// ---- host_rate.hip (rs_table and rs_add_runs: RateStage's inline members call them) -----------------------
+int rs_table(nhans_ctx* c, const ResampleFilter* f, const float** tab);
+inline size_t rs_elem(int fmt) { return fmt == kResampleInt16 ? 2 : 4; }
+void rs_add_runs(std::vector<ResampleRun>& runs, size_t* lds, const ResampleFilter& f, const void* src, const float* mix,
+                 const float* hist, char* dst, size_t elem, float* hist_out, int64_t k0, int n_new, int64_t m_begin, int64_t m_end);
+
+// what the kernel reads and stores (launch_resample): PCM of pcm_format -> float32, or the wet/dry mix -> PCM of pcm_format
+struct RateIo {
+    bool from_mix;
+    int pcm_format, quantise;
+    float wet;
+    double factor;
+    bool auto_wet = false;      // from_mix: each hop's factor comes from the runs' gain table (GainTab) instead of `wet`
+    size_t in_elem() const { return from_mix ? 4 : rs_elem(pcm_format); }
+    size_t out_elem() const { return from_mix ? rs_elem(pcm_format) : 4; }
+};
+
+// What a streaming converter carries: the filter, its device table, the carried samples and per stream how far it is.
+struct RateStage {
+    const ResampleFilter* f = nullptr;
+    const float* tab = nullptr;
+    int S = 0;
+    // [2][S][J]: the J samples before each stream's next one; cur[i] = the half that holds them.  A push reads half cur[i]
+    // and writes the other one; the NEXT push reads what this one wrote and overwrites what it read.  That is race-free
+    // because consecutive calls on a context are ordered on the device (same stream, or Call's tail event across streams).
+    // A rewind is therefore host-only: the half of before the push is intact, and restore() points at it again.
+    float* hist = nullptr;
+    struct Streams {
+        std::vector<int64_t> N;         // samples taken per stream
+        std::vector<char> ended, cur;
+    } st;
+    struct Span { int64_t Eo, En; };    // outputs [Eo, En) of a stream
+
+    int alloc(nhans_ctx* c, const char* fn, const ResampleFilter* filter, int nstreams) {
+        const int rc = rs_table(c, filter, &tab); if (rc) return rc;
+        f = filter; S = nstreams;
+        st.N.assign(S, 0); st.ended.assign(S, 0); st.cur.assign(S, 0);
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&hist), (size_t)2 * S * f->J * 4);
+        if (e != hipSuccess) return fail(NHANS_ENOMEM, std::string(fn) + ": hipMalloc failed: " + hipGetErrorString(e));
+        return NHANS_OK;
+    }
+    void release() { if (hist) (void)hipFree(hist); hist = nullptr; }
+    float* h(int k, int i) const { return hist + ((size_t)k * S + i) * f->J; }
+    // what cnt more samples (en: and the end) make final of stream i
+    Span plan(int i, int64_t cnt, bool en) const {
+        return {resample_emitted(*f, st.N[i], st.ended[i]), resample_emitted(*f, st.N[i] + cnt, st.ended[i] || en)};
+    }
+    // the runs of such a push, its cnt samples at src (mix: see ResampleRun), outputs e stored from dst on
+    void add_runs(std::vector<ResampleRun>& runs, size_t* lds, int i, const void* src, const float* mix, char* dst, size_t elem,
+                  int64_t cnt, Span e) const {
+        if (cnt == 0 && e.En == e.Eo) return;
+        rs_add_runs(runs, lds, *f, src, mix, h(st.cur[i], i), dst, elem, cnt > 0 ? h(1 - st.cur[i], i) : nullptr, st.N[i], (int)cnt,
+                    e.Eo, e.En);
+    }
+    void commit(int i, int64_t cnt, bool en) {
+        st.N[i] += cnt;
+        st.ended[i] = st.ended[i] || en;
+        if (cnt > 0) st.cur[i] = 1 - st.cur[i];
+    }
+    // (nothing is cleared on the device: a stream of 0 samples reads none of the carried ones -- their absolute index is negative)
+    void restart(int i) { st.N[i] = 0; st.ended[i] = 0; }
+    Streams save() const { return st; }
+    void restore(const Streams& saved) { st = saved; }
+};
+
+// The per-hop wet factors of a live push (level.hip wrote them): slot i's begin at w[off[i]], its first one being that of
+// the first hop the push makes final, hop N / 160 of a stream that had N samples.
+struct GainTab {
+    const float* w;
+    const int64_t* off;
+};
+
+int stage_push(nhans_ctx* c, RateStage& g, const char* kernel, const RateIo& io, const void* in, const float* mix,
+               const int64_t* inoff, const int* end, void* out, const int64_t* outoff, int64_t* counts, hipStream_t s,
+               const GainTab* gains = nullptr);
+
+#pragma GCC visibility pop

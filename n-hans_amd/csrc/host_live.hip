@@ -1,0 +1,482 @@
+// ---- live PCM sessions (include/nhans_hip.h: nhans_live_*) -----------------------------------------------------------
+// One object = an incoming converter (rate_in -> 16 kHz with the fixed peak), an online object and an outgoing converter
+// (16 kHz -> rate_out, fed by the wet/dry mix), with the 16 kHz pieces between them in device buffers of the object.  A
+// push runs the three stages inside ONE Call on one stream; the stages' own workspace needs (run tables, the online
+// staging) follow each other in the context's workspace, which stream order makes safe, and nothing a later stage reads
+// lives there.
+#include "host_internal.h"
+
+// The level meter of a live object (nhans_level_live_enable; level.hip): per slot a double-buffered state of kLevelState
+// doubles -- a push reads half cur[i] and writes the other one, as RateStage::hist --, and the gain table of the last
+// push, which the outgoing stage reads and which therefore is a buffer of the object, not workspace.  The hops a slot's
+// stream has are those of the outgoing stage's sample count (level_hops), so the snapshot of a push is h0 and cur alone.
+struct LevelMeter {
+    bool on = false, auto_wet = false;
+    int W = 0;                      // the window of the meter and of the automatic factor (0: cumulative)
+    double wmax = 1.0;
+    double* state = nullptr;        // [2][S][kLevelState]
+    float* wtab = nullptr;
+    size_t wtab_cap = 0;            // (floats)
+    struct Slots {
+        std::vector<int64_t> h0;    // the first hop of the slot's stream the state knows
+        std::vector<char> cur;
+    } st;
+    std::vector<int64_t> woff;      // the last push's hops per slot, as offsets into wtab ([S + 1]; empty: none to read)
+};
+
+struct nhans_live {
+    nhans_ctx* c = nullptr;
+    int device = 0, S = 0, in_format = 0, out_format = 0;
+    bool has_wet = false;           // NHANS_LIVE_WET: the online object also makes the mixed round trip
+    float wet = 0.f;
+    double in_denom = 0.0, out_scale = 1.0;     // the fixed peak + 1e-6
+    RateStage in, out;              // out's stream is c = den + (mix - den) * wet; out.st.N: 16 kHz samples taken per slot
+    nhans_online* on = nullptr;
+    RateStage::Streams undo_in, undo_out;       // the converters before the last push
+    float *mid = nullptr, *den = nullptr, *mix = nullptr;   // the push's 16 kHz input / denoised / mixed pieces
+    size_t mid_cap = 0, out_cap = 0;                        // (floats)
+    bool can_rewind = false;
+    LevelMeter lv;
+    LevelMeter::Slots undo_lv;
+    double* lv_half(int k, int i) const { return lv.state + ((size_t)k * S + i) * kLevelState; }
+};
+
+namespace {
+
+int live_filters(const char* fn, int rate_in, int rate_out, const ResampleFilter** fi, const ResampleFilter** fo) {
+    *fi = resample_filter(rate_in, 16000);
+    *fo = resample_filter(16000, rate_out);
+    if (!*fi || !*fo)
+        return fail(NHANS_EINVAL, std::string(fn) + ": " + std::to_string(rate_in) + " Hz in / " + std::to_string(rate_out) +
+                                  " Hz out is not supported (each one of 8000, 11025, 12000, 16000, 22050, 24000, 32000, "
+                                  "44100, 48000, 88200 or 96000 Hz)");
+    return NHANS_OK;
+}
+
+int live_check_push(const nhans_live* o, const char* fn, int i, int64_t cnt, bool en) {
+    return push_check(fn, "slot", i, cnt, en, o->in.st.ended[i],
+                      o->on->cond[i] ? nullptr : "nhans_live_set_context / nhans_live_set_embeddings", kMaxResampleClip);
+}
+
+// what a push of cnt samples (en: and the end) to slot i moves between the stages: n16 samples into the online object,
+// d16 final samples out of it, outputs [Eo, En) of the outgoing stream
+struct LivePlan {
+    int64_t n16, d16, Eo, En;
+};
+LivePlan live_plan(const nhans_live* o, int i, int64_t cnt, bool en) {
+    LivePlan p{};
+    const RateStage::Span e16 = o->in.plan(i, cnt, en);
+    p.n16 = e16.En - e16.Eo;
+    p.d16 = online_emit_count(o->on, i, p.n16, en);
+    const RateStage::Span e = o->out.plan(i, p.d16, en);
+    p.Eo = e.Eo; p.En = e.En;
+    return p;
+}
+
+// Grows on demand, at least doubling: equal-sized pushes stop growing after their first few.  (hipFree waits for the
+// device, so a buffer an earlier push still uses is not taken from under it.)
+int live_grow(float** p, size_t want) {
+    float* q = nullptr;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), want * 4);
+    if (e != hipSuccess) return fail(NHANS_ENOMEM, std::string("nhans_live_push: hipMalloc failed: ") + hipGetErrorString(e));
+    if (*p) (void)hipFree(*p);
+    *p = q;
+    return NHANS_OK;
+}
+
+int live_reserve(nhans_live* o, size_t n_mid, size_t n_out) {
+    if (n_mid > o->mid_cap) {
+        const size_t want = std::max<size_t>({n_mid, 2 * o->mid_cap, 4096});
+        const int rc = live_grow(&o->mid, want); if (rc) return rc;
+        o->mid_cap = want;
+    }
+    if (n_out > o->out_cap) {
+        const size_t want = std::max<size_t>({n_out, 2 * o->out_cap, 4096});
+        // (out_cap moves last: after a failure the next push tries again)
+        int rc = live_grow(&o->den, want); if (rc) return rc;
+        if (o->has_wet) { rc = live_grow(&o->mix, want); if (rc) return rc; }
+        o->out_cap = want;
+    }
+    return NHANS_OK;
+}
+
+int64_t level_hops(int64_t emitted, bool ended) { return ended ? (emitted + kHop - 1) / kHop : emitted / kHop; }
+
+// The level launch of a push whose online stage has put the pieces [ooff) into den / mix: one run per slot with new hops,
+// the gains into lv.wtab from woff[i] on, the state into the half the slot's next push will read.  Host state does not
+// move here: *next is what lv.st becomes once the whole push has gone out.
+int live_level(nhans_live* o, const int64_t* ooff, const int* end, hipStream_t s, std::vector<int64_t>* woff,
+               LevelMeter::Slots* next) {
+    nhans_ctx* c = o->c;
+    LevelMeter& lv = o->lv;
+    const int S = o->S;
+    woff->assign(S + 1, 0);
+    *next = lv.st;
+    for (int i = 0; i < S; ++i) {
+        const int64_t N = o->out.st.N[i];
+        const bool was = o->out.st.ended[i];
+        (*woff)[i + 1] = (*woff)[i] + level_hops(N + ooff[i + 1] - ooff[i], was || (end && end[i])) - level_hops(N, was);
+    }
+    if ((size_t)(*woff)[S] > lv.wtab_cap) {
+        const size_t want = std::max<size_t>({(size_t)(*woff)[S], 2 * lv.wtab_cap, 256});
+        const int rc = live_grow(&lv.wtab, want); if (rc) return rc;
+        lv.wtab_cap = want;
+    }
+    std::vector<LevelRun> runs;
+    for (int i = 0; i < S; ++i) {
+        const int64_t nh = (*woff)[i + 1] - (*woff)[i];
+        if (nh == 0) continue;
+        const int64_t first = o->out.st.N[i] / kHop;     // (new hops: the stream had not ended, its hops were whole)
+        const int k = lv.st.cur[i];
+        runs.push_back({o->den + ooff[i], o->mix + ooff[i], first > lv.st.h0[i] ? o->lv_half(k, i) : nullptr, o->lv_half(1 - k, i),
+                        o->lv_half(1 - k, i) + kLevelMeter, lv.wtab + (*woff)[i], (long long)(ooff[i + 1] - ooff[i]),
+                        (long long)first, (long long)nh, (long long)lv.st.h0[i], lv.W, lv.wmax});
+        next->cur[i] = (char)(1 - k);
+    }
+    if (runs.empty()) return NHANS_OK;
+    int rc = ws_reserve(c, ws_size(runs.size(), sizeof(LevelRun))); if (rc) return rc;
+    LevelRun* runs_dev = ws_take<LevelRun>(c, runs.size());
+    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(LevelRun), s); if (rc) return rc;
+    Prof pr(c, s, "live_level");
+    launch_level("live_level", runs_dev, (int)runs.size(), s);
+    pr.done(9.0 * (double)(ooff[S] - ooff[0]), 8.0 * (double)(ooff[S] - ooff[0]) + (double)runs.size() * 2 * kLevelState * 8);
+    return NHANS_OK;
+}
+
+int live_push_body(nhans_live* o, const void* in, const int64_t* inoff, const int* end, void* out, const int64_t* outoff,
+                   int64_t* counts, hipStream_t s) {
+    if (!inoff || !outoff || !counts) return fail(NHANS_EINVAL, "nhans_live_push: null argument");
+    nhans_ctx* c = o->c;
+    const int S = o->S;
+    std::vector<int64_t> moff(S + 1, 0), ooff(S + 1, 0);
+    int64_t tin = 0, tout = 0;
+    for (int i = 0; i < S; ++i) {
+        const int64_t cnt = inoff[i + 1] - inoff[i];
+        const bool en = end && end[i];
+        const int rc = live_check_push(o, "nhans_live_push", i, cnt, en); if (rc) return rc;
+        const LivePlan p = live_plan(o, i, cnt, en);
+        if (outoff[i + 1] - outoff[i] < p.En - p.Eo)
+            return fail(NHANS_EINVAL, "nhans_live_push: output room of slot " + std::to_string(i) + " is " +
+                                      std::to_string(outoff[i + 1] - outoff[i]) + " samples, " +
+                                      std::to_string(p.En - p.Eo) + " needed (nhans_live_out_counts)");
+        moff[i + 1] = moff[i] + p.n16;
+        ooff[i + 1] = ooff[i] + p.d16;
+        tin += cnt; tout += p.En - p.Eo;
+    }
+    if ((tin > 0 && !in) || (tout > 0 && !out)) return fail(NHANS_EINVAL, "nhans_live_push: null buffer");
+    int rc = live_reserve(o, (size_t)moff[S], (size_t)ooff[S]); if (rc) return rc;
+
+    // ---- the three stages, the pieces [moff) and [ooff) between them: each commits its host state when its launches
+    // went out, and a failure behind it puts it back (an online push undone leaves nothing for nhans_live_rewind) ----
+    const RateStage::Streams was_in = o->in.save(), was_out = o->out.save();
+    std::vector<int64_t> got(S, 0);
+    rc = stage_push(c, o->in, "live_in", {false, o->in_format, 0, 0.f, o->in_denom}, in, nullptr, inoff, end, o->mid, moff.data(),
+                    got.data(), s);
+    if (rc || launch_error_pending()) return rc;          // (a launch error is reported by the entry point; no stage has committed)
+    rc = online_push_body(o->on, o->mid, moff.data(), end, o->den, o->mix, ooff.data(), got.data(), s);
+    if (rc || launch_error_pending()) { o->in.restore(was_in); return rc; }
+    // (an object that never enabled its meter takes none of the branches below: launch for launch the push it was)
+    std::vector<int64_t> woff;
+    LevelMeter::Slots lv_next;
+    if (o->lv.on) {
+        rc = live_level(o, ooff.data(), end, s, &woff, &lv_next);
+        if (rc || launch_error_pending()) { o->in.restore(was_in); online_undo(o->on); o->can_rewind = false; return rc; }
+    }
+    const bool auto_wet = o->lv.on && o->lv.auto_wet;
+    const GainTab gains{o->lv.wtab, woff.data()};
+    rc = stage_push(c, o->out, "live_out", {true, o->out_format, 0, o->wet, o->out_scale, auto_wet}, o->den,
+                    auto_wet || o->wet != 0.f ? o->mix : nullptr, ooff.data(), end, out, outoff, counts, s, auto_wet ? &gains : nullptr);
+    if (rc || launch_error_pending()) { o->in.restore(was_in); online_undo(o->on); o->can_rewind = false; return rc; }
+    o->undo_in = was_in; o->undo_out = was_out;
+    if (o->lv.on) {
+        o->undo_lv = o->lv.st;
+        o->lv.st = lv_next;
+        o->lv.woff = woff;
+    }
+    o->can_rewind = true;
+    return NHANS_OK;
+}
+
+void live_free(nhans_live* o) {
+    if (o->on) nhans_online_close(o->on);
+    o->in.release(); o->out.release();
+    for (float* p : {o->mid, o->den, o->mix, o->lv.wtab})
+        if (p) (void)hipFree(p);
+    if (o->lv.state) (void)hipFree(o->lv.state);
+    delete o;
+}
+
+}  // namespace
+
+extern "C" {
+
+namespace {
+int64_t live_emitted(const char* fn, int64_t n, int ended, int rate_in, int rate_out, int L) {
+    const ResampleFilter *fi = nullptr, *fo = nullptr;
+    if (live_filters(fn, rate_in, rate_out, &fi, &fo)) return NHANS_EINVAL;
+    if (n < 0) return fail(NHANS_EINVAL, std::string(fn) + ": negative sample count");
+    if (L < 0 || L > kCenter) return fail(NHANS_EINVAL, std::string(fn) + ": lookahead must be in [0, " + std::to_string(kCenter) + "] frames");
+    const int64_t n16 = resample_emitted(*fi, n, ended != 0);
+    return resample_emitted(*fo, on_emitted(nhans_num_frames(n16), ended != 0, L), ended != 0);
+}
+}  // namespace
+
+int64_t nhans_live_emitted(int64_t n, int ended, int rate_in, int rate_out) {
+    return live_emitted("nhans_live_emitted", n, ended, rate_in, rate_out, kCenter);
+}
+
+int64_t nhans_lookahead_live_emitted(int64_t n, int ended, int rate_in, int rate_out, int lookahead) {
+    return live_emitted("nhans_lookahead_live_emitted", n, ended, rate_in, rate_out, lookahead);
+}
+
+int nhans_lookahead_live_set(nhans_live* o, int slot, int lookahead) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_lookahead_live_set: null object");
+    int rc = slot_check(o->S, slot, "nhans_lookahead_live_set"); if (rc) return rc;
+    // (a stream of 0 samples in all three stages: the converter may hold samples the online stage has not seen yet)
+    if (o->in.st.N[slot] != 0 || o->in.st.ended[slot])
+        return fail(NHANS_EINVAL, "nhans_lookahead_live_set: slot " + std::to_string(slot) + " has a stream under way " +
+                                  "(the look-ahead is set on an open stream of 0 samples: after open or nhans_live_restart)");
+    rc = nhans_online_set_lookahead(o->on, slot, lookahead); if (rc) return rc;
+    o->can_rewind = false;
+    return NHANS_OK;
+}
+
+int nhans_live_open_slots(nhans_ctx* c, int nslots, int rate_in, int in_format, double peak, int rate_out, int out_format,
+                          double out_scale, int flags, void* stream, nhans_live** out) {
+    if (!out) return fail(NHANS_EINVAL, "nhans_live_open_slots: null argument");
+    *out = nullptr;
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    if (nslots < 1) return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: nslots must be >= 1"));
+    for (int fmt : {in_format, out_format})
+        if (fmt != kResampleInt16 && fmt != kResampleFloat32)
+            return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: in_format and out_format must be NHANS_PCM_INT16 or NHANS_PCM_FLOAT32"));
+    if (!(peak >= 0.0) || !std::isfinite(peak))
+        return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: the peak must be finite and >= 0"));
+    if (!(out_scale > 0.0) || !std::isfinite(out_scale))
+        return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: out_scale must be finite and > 0"));
+    if (flags & ~NHANS_LIVE_WET) return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: unknown flag"));
+    const ResampleFilter *fi = nullptr, *fo = nullptr;
+    int rc = live_filters("nhans_live_open_slots", rate_in, rate_out, &fi, &fo); if (rc) return call.finish(rc);
+    nhans_live* o = new nhans_live();
+    o->c = c; o->device = c->device; o->S = nslots; o->in_format = in_format; o->out_format = out_format;
+    o->has_wet = (flags & NHANS_LIVE_WET) != 0;
+    o->in_denom = peak + 0.000001; o->out_scale = out_scale;
+    rc = o->in.alloc(c, "nhans_live_open_slots", fi, nslots);
+    if (!rc) rc = o->out.alloc(c, "nhans_live_open_slots", fo, nslots);
+    if (!rc) rc = online_open_slots_body(c, nslots, o->has_wet, call.s, &o->on);
+    if (rc) { live_free(o); return call.finish(rc); }
+    *out = o;
+    return call.finish(NHANS_OK);
+}
+
+int nhans_live_restart(nhans_live* o, int slot) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_live_restart: null object");
+    const int rc = slot_check(o->S, slot, "nhans_live_restart"); if (rc) return rc;
+    // (nothing is cleared on the device: streams of 0 samples read none of the carried state, in any of the stages)
+    online_restart_slot(o->on, slot);
+    o->in.restart(slot); o->out.restart(slot);
+    if (o->lv.on) { o->lv.st.h0[slot] = 0; o->lv.woff.clear(); }     // (hop 0 reads none of the carried level state)
+    o->can_rewind = false;
+    return NHANS_OK;
+}
+
+int nhans_live_set_context(nhans_live* o, int slot, const float* ca, int64_t na, const float* cbw, int64_t nb, void* stream,
+                           int64_t* first_frame_out) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_live_set_context: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    int rc = slot_check(o->S, slot, "nhans_live_set_context"); if (rc) return call.finish(rc);
+    if (!ca || !cbw) return call.finish(fail(NHANS_EINVAL, "nhans_live_set_context: null argument"));
+    if (na < 0 || nb < 0) return call.finish(fail(NHANS_EINVAL, "nhans_live_set_context: negative sample count"));
+    rc = online_set_context_body(o->on, slot, ca, na, cbw, nb, call.s, first_frame_out);
+    if (!rc && !launch_error_pending()) o->can_rewind = false;
+    return call.finish(rc);
+}
+
+int nhans_live_set_embeddings(nhans_live* o, int slot, const float* ea, const float* eb, void* stream, int64_t* first_frame_out) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_live_set_embeddings: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    int rc = slot_check(o->S, slot, "nhans_live_set_embeddings"); if (rc) return call.finish(rc);
+    if (!ea || !eb) return call.finish(fail(NHANS_EINVAL, "nhans_live_set_embeddings: null argument"));
+    rc = online_set_embeddings_body(o->on, slot, ea, eb, call.s, first_frame_out);
+    if (!rc) o->can_rewind = false;
+    return call.finish(rc);
+}
+
+int nhans_live_set_wet(nhans_live* o, double wet) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_live_set_wet: null object");
+    if (!std::isfinite(wet)) return fail(NHANS_EINVAL, "nhans_live_set_wet: the factor must be finite");
+    if ((float)wet != 0.f && !o->has_wet)
+        return fail(NHANS_EINVAL, "nhans_live_set_wet: the object was opened without NHANS_LIVE_WET, only 0 can be set");
+    o->wet = (float)wet;
+    return NHANS_OK;
+}
+
+int nhans_live_out_counts(const nhans_live* o, const int64_t* in_counts, const int* end, int64_t* counts) {
+    if (!o || !in_counts || !counts) return fail(NHANS_EINVAL, "nhans_live_out_counts: null argument");
+    for (int i = 0; i < o->S; ++i) {
+        const int rc = live_check_push(o, "nhans_live_out_counts", i, in_counts[i], end && end[i]); if (rc) return rc;
+    }
+    for (int i = 0; i < o->S; ++i) {
+        const LivePlan p = live_plan(o, i, in_counts[i], end && end[i]);
+        counts[i] = p.En - p.Eo;
+    }
+    return NHANS_OK;
+}
+
+int nhans_live_push(nhans_live* o, const void* in, const int64_t* inoff, const int* end, void* out, const int64_t* outoff,
+                    int64_t* counts, void* stream) {
+    return object_call(o, "nhans_live_push: null object", stream,
+                       [&](hipStream_t s) { return live_push_body(o, in, inoff, end, out, outoff, counts, s); });
+}
+
+int nhans_live_rewind(nhans_live* o) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_live_rewind: null object");
+    if (!o->can_rewind) return fail(NHANS_EINVAL, "nhans_live_rewind: no push to undo (one rewind per push)");
+    // (every stage wrote the half of its carried state that it did not read: the halves of before the push are intact)
+    o->in.restore(o->undo_in);
+    online_undo(o->on);
+    o->out.restore(o->undo_out);
+    if (o->lv.on) { o->lv.st = o->undo_lv; o->lv.woff.clear(); }
+    o->can_rewind = false;
+    return NHANS_OK;
+}
+
+int nhans_capture_live_enable(nhans_live* o, void* stream) {
+    return object_call(o, "nhans_capture_live_enable: null object", stream,
+                       [&](hipStream_t s) { return capture_enable_body(o->on, "nhans_capture_live_enable", s); });
+}
+
+int nhans_capture_live_context(nhans_live* o, int n, const int* slots, const int* which, int flags, void* stream,
+                               int64_t* first_frame_out) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_capture_live_context: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    const int rc = capture_context_body(o->on, "nhans_capture_live_context", n, slots, which, flags, call.s, first_frame_out);
+    if (!rc && !launch_error_pending()) o->can_rewind = false;
+    return call.finish(rc);
+}
+
+int nhans_capture_live_embeddings(const nhans_live* o, int slot, float* ea, float* eb, void* stream) {
+    return object_call(o, "nhans_capture_live_embeddings: null object", stream,
+                       [&](hipStream_t s) { return capture_embeddings_body(o->on, "nhans_capture_live_embeddings", slot, ea, eb, s); });
+}
+
+// ---- level meter and automatic compensation (include/nhans_hip.h: nhans_level_*) ----
+int64_t nhans_level_hops(int64_t emitted, int ended) {
+    if (emitted < 0) return fail(NHANS_EINVAL, "nhans_level_hops: negative sample count");
+    return level_hops(emitted, ended != 0);
+}
+
+int nhans_level_live_enable(nhans_live* o, void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_level_live_enable: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    if (!o->has_wet)
+        return call.finish(fail(NHANS_EINVAL, "nhans_level_live_enable: the object was opened without NHANS_LIVE_WET "
+                                              "(the meter reads the mixed round trip)"));
+    if (o->lv.on) return call.finish(NHANS_OK);
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->lv.state), (size_t)2 * o->S * kLevelState * sizeof(double));
+    if (e != hipSuccess)
+        return call.finish(fail(NHANS_ENOMEM, std::string("nhans_level_live_enable: hipMalloc failed: ") + hipGetErrorString(e)));
+    // (nothing is cleared: a slot's first hop h0 reads none of the state)
+    o->lv.st.h0.resize(o->S);
+    for (int i = 0; i < o->S; ++i) o->lv.st.h0[i] = level_hops(o->out.st.N[i], o->out.st.ended[i]);
+    o->lv.st.cur.assign(o->S, 0);
+    o->lv.on = true;
+    o->can_rewind = false;
+    return call.finish(NHANS_OK);
+}
+
+namespace {
+int level_check(const char* fn, int window_hops, int lowest, double wmax) {
+    if (window_hops < lowest || window_hops > kLevelRing)
+        return fail(NHANS_EINVAL, std::string(fn) + ": window_hops " + std::to_string(window_hops) + " outside [" +
+                                  std::to_string(lowest) + ", " + std::to_string(kLevelRing) + "]");
+    if (!(wmax >= 0.0) || !std::isfinite(wmax)) return fail(NHANS_EINVAL, std::string(fn) + ": wmax must be finite and >= 0");
+    return NHANS_OK;
+}
+}  // namespace
+
+int nhans_level_live_auto(nhans_live* o, int window_hops, double wmax) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_level_live_auto: null object");
+    if (!o->lv.on) return fail(NHANS_EINVAL, "nhans_level_live_auto: the meter is not enabled (nhans_level_live_enable)");
+    const int rc = level_check("nhans_level_live_auto", window_hops, -1, wmax); if (rc) return rc;
+    o->lv.auto_wet = window_hops >= 0;
+    if (window_hops >= 0) { o->lv.W = window_hops; o->lv.wmax = wmax; }
+    o->can_rewind = false;
+    return NHANS_OK;
+}
+
+int nhans_level_live_read(nhans_live* o, int slot, double* out, void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_level_live_read: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    int rc = slot_check(o->S, slot, "nhans_level_live_read"); if (rc) return call.finish(rc);
+    if (!out) return call.finish(fail(NHANS_EINVAL, "nhans_level_live_read: null argument"));
+    if (!o->lv.on) return call.finish(fail(NHANS_EINVAL, "nhans_level_live_read: the meter is not enabled (nhans_level_live_enable)"));
+    if (level_hops(o->out.st.N[slot], o->out.st.ended[slot]) <= o->lv.st.h0[slot])
+        return call.finish(fail(NHANS_ESHORT, "nhans_level_live_read: slot " + std::to_string(slot) + " has no final hop yet"));
+    hipError_t e = hipMemcpyAsync(out, o->lv_half(o->lv.st.cur[slot], slot) + kLevelMeter, 8 * sizeof(double), hipMemcpyDeviceToHost, call.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(call.s);
+    if (e != hipSuccess) return call.finish(fail(NHANS_EHIP, std::string("nhans_level_live_read: ") + hipGetErrorString(e)));
+    return call.finish(NHANS_OK);
+}
+
+int64_t nhans_level_live_gains(nhans_live* o, int slot, float* out, int64_t cap, void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_level_live_gains: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    int rc = slot_check(o->S, slot, "nhans_level_live_gains"); if (rc) return call.finish(rc);
+    if (!o->lv.on) return call.finish(fail(NHANS_EINVAL, "nhans_level_live_gains: the meter is not enabled (nhans_level_live_enable)"));
+    const int64_t n = o->lv.woff.empty() ? 0 : o->lv.woff[slot + 1] - o->lv.woff[slot];
+    if (!out || n == 0) { rc = call.finish(NHANS_OK); return rc ? rc : n; }
+    if (cap < n)
+        return call.finish(fail(NHANS_EINVAL, "nhans_level_live_gains: room for " + std::to_string(cap) + " gains, " +
+                                              std::to_string(n) + " needed"));
+    hipError_t e = hipMemcpyAsync(out, o->lv.wtab + o->lv.woff[slot], (size_t)n * sizeof(float), hipMemcpyDeviceToHost, call.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(call.s);
+    if (e != hipSuccess) return call.finish(fail(NHANS_EHIP, std::string("nhans_level_live_gains: ") + hipGetErrorString(e)));
+    rc = call.finish(NHANS_OK);
+    return rc ? rc : n;
+}
+
+int nhans_level_gains(nhans_ctx* c, const float* den, const float* mix, const int64_t* off, int nclips, int window_hops,
+                      double wmax, float* w_out, double* sums_out, void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    if (!off || nclips < 0) return call.finish(fail(NHANS_EINVAL, "nhans_level_gains: null argument"));
+    int rc = level_check("nhans_level_gains", window_hops, 0, wmax); if (rc) return call.finish(rc);
+    std::vector<LevelRun> runs;
+    int64_t hops = 0;
+    for (int i = 0; i < nclips; ++i) {
+        const int64_t n = off[i + 1] - off[i];
+        if (n < 0) return call.finish(fail(NHANS_EINVAL, "nhans_level_gains: clip " + std::to_string(i) + " has a negative sample count"));
+        const int64_t nh = level_hops(n, true);
+        if (nh > 0 && (!den || !mix || !w_out)) return call.finish(fail(NHANS_EINVAL, "nhans_level_gains: null buffer"));
+        if (nh > 0)
+            runs.push_back({den + off[i], mix + off[i], nullptr, nullptr, sums_out ? sums_out + 8 * (size_t)i : nullptr, w_out + hops,
+                            (long long)n, 0, (long long)nh, 0, window_hops, wmax});
+        hops += nh;
+    }
+    if (runs.empty()) return call.finish(NHANS_OK);
+    rc = ws_reserve(c, ws_size(runs.size(), sizeof(LevelRun))); if (rc) return call.finish(rc);
+    LevelRun* runs_dev = ws_take<LevelRun>(c, runs.size());
+    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(LevelRun), call.s); if (rc) return call.finish(rc);
+    const double n = (double)(off[nclips] - off[0]);
+    Prof pr(c, call.s, "level_gains");
+    launch_level("level_gains", runs_dev, (int)runs.size(), call.s);
+    pr.done(9.0 * n, 8.0 * n + 4.0 * (double)hops);
+    return call.finish(NHANS_OK);
+}
+
+void nhans_live_close(nhans_live* o) {
+    if (!o) return;
+    (void)hipSetDevice(o->device);
+    (void)hipDeviceSynchronize();
+    live_free(o);
+}
+
+}  // extern "C"

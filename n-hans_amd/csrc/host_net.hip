@@ -1,0 +1,749 @@
+// The network on the host side: conv launch helpers, the embedding tower, the conditioned stack and head, the STFT /
+// iSTFT block tables, and the offline entry points of include/nhans_hip.h that run them.
+#include "host_internal.h"
+
+namespace {
+
+void same_pad(int n, int k, int s, int* out, int* before) {
+    *out = (n + s - 1) / s;
+    int total = std::max((*out - 1) * s + k - n, 0);
+    *before = total / 2;
+}
+
+void fill_epilogue_defaults(nhans_ctx* c, ConvArgs& a) {
+    a.zero = c->A("zero");
+    a.sat = c->status_dev;
+    a.img_clip = nullptr; a.tf = nullptr; a.tt = nullptr; a.ff = nullptr; a.id_mode = 0; a.id = nullptr; a.id_ld = 0;
+    a.idw = nullptr; a.idH = a.idW = 0; a.idsh = a.idsw = 1; a.relu = 1; a.aux = nullptr; a.aux_ld = 0;
+    a.cb_stride = 0;
+    a.prec = c->prec; a.out_split = c->prec; a.id_split = 0; a.ws = nullptr;
+    a.in_scale = a.id_scale = a.out_scale = 1.f;
+    a.sat_limit = kSatLimitF16;
+    a.variant = c->conv_variant >= 0 ? c->conv_variant : (c->prec == 1 ? 2 : 0);
+    a.dbg = kDev ? c->dbg : nullptr;
+    a.epi8 = c->epi8;
+    a.ilv = c->ilv;
+    a.wino = c->wino; a.wino_u = nullptr; a.wino_ws = nullptr;
+    a.kscratch = c->kscratch; a.kscratch_bytes = c->kscratch_bytes; a.kcounter = c->kcounter; a.kcounter_n = c->kcounter_n; a.kgroup = 0;
+}
+
+ConvSeg make_seg(const float* src, const float* wpk, int H, int W, int C, int KH, int KW, int sh, int sw,
+                 bool same) {
+    ConvSeg g;
+    g.src = src; g.wpk = wpk; g.H = H; g.W = W; g.C = C; g.KH = KH; g.KW = KW; g.sh = sh; g.sw = sw;
+    int o, pb;
+    if (same) { same_pad(H, KH, sh, &o, &pb); g.pt = pb; same_pad(W, KW, sw, &o, &pb); g.pl = pb; }
+    else { g.pt = 0; g.pl = 0; }
+    g.nchunks = KH * KW * C / 32;
+    return g;
+}
+
+void set_out_geometry(ConvArgs& a, int B, int Ho, int Wo, int N, int Nreal, int ldo, float* out) {
+    a.Ho = Ho; a.Wo = Wo; a.M = B * Ho * Wo; a.N = N; a.Nreal = Nreal; a.ldo = ldo; a.out = out;
+    a.fdHoWo = make_fastdiv((uint32_t)(Ho * Wo));
+    a.fdWo = make_fastdiv((uint32_t)Wo);
+}
+
+void run_conv(nhans_ctx* c, const ConvArgs& a0, hipStream_t s) {
+    ConvArgs a = a0;
+    if (kDev) {      // timing experiment (wrong results): NHANS_ABLATE_TF=1 -> no position table at all
+        static const bool no_tf = [] { const char* e = getenv("NHANS_ABLATE_TF"); return e && atoi(e) != 0; }();
+        if (no_tf) { a.tf = nullptr; a.tt = nullptr; a.ff = nullptr; }
+    }
+    if (a.kgroup < 0) {
+        // split-K scratch on demand (hipFree / hipMalloc wait for the device: a handful of times per context at most)
+        const size_t need = c->split_k ? conv_splitk_scratch_bytes(a) : 0;
+        if (need > c->kscratch_bytes && need <= nhans_ctx::kscratch_cap && !c->kscratch_failed) {
+            if (c->kscratch) { (void)hipFree(c->kscratch); c->kscratch = nullptr; c->kscratch_bytes = 0; }
+            const size_t want = std::min(nhans_ctx::kscratch_cap, std::max(need, (size_t)32 << 20));
+            if (hipMalloc(reinterpret_cast<void**>(&c->kscratch), want) == hipSuccess) c->kscratch_bytes = want;
+            else { (void)hipGetLastError(); c->kscratch = nullptr; c->kscratch_failed = true; }
+        }
+        a.kscratch = c->split_k ? c->kscratch : nullptr;
+        a.kscratch_bytes = c->kscratch_bytes;
+    }
+    // profiled under the name of the kernel variant that ran (the variant is chosen per layer)
+    Prof p(c, s, nullptr);
+    const char* name = "conv_igemm";
+    double mfma = 0;
+    double fl = launch_conv_igemm(a, s, &name, &mfma);
+    p.done(fl, 0, name, mfma);
+}
+
+// Which convs of the stack run in their Winograd form (conv_wino.hip), for one chunk of frame windows.  NOT a restatement
+// of the kernel's conditions: run_stack_chunk() builds every launch's ConvArgs twice -- a planning pass that asks
+// conv_wino_eligible() about those very arguments, then the launching pass that takes layouts and saturation limits
+// from the answers (round-4 advisor finding: a second predicate that left out the 32-bit offset bound, aux, kgroup ...
+// could disagree with the kernel, and the producer would already have written the other layout).
+bool wino_form(const ConvArgs& a) { return a.variant >= 2 && a.kgroup >= 0 && conv_wino_eligible(a); }
+float sat_limit_for(const StackPlan& p, int b, int cv) { return b >= 0 && b < 8 && p.wino[b][cv] ? kSatLimitWinoInput : kSatLimitF16; }
+
+// Is stack tensor (block b; cv 0: conv1's output, 1: the block's output) stored as f32 NHWC in the split-f16 mode?  Yes if
+// every launch that reads it is a Winograd launch -- conv_wino.hip reads either layout (its transform works in f32 and
+// re-splits: with an f32 input it has no hi + lo to add up, 64 of its ~215 instructions per chunk), the direct kernels
+// stage split pieces straight into MFMA operands -- and the launch that writes it is direct_conv64 or a Winograd launch.
+// The values are the same scaled, clamped ones a split store would hold to 22 bits; 4 bytes per element either way.
+// (wino_f32 == 2, a test value: f32 whatever the readers are -- launch_conv_igemm() must then refuse the reader.
+//  wino_f32 == 3, a test value: ONLY the output of resblock1_2 is f32 -- its conv2 then has a split residual and an f32
+//  output, the one layout pair conv_wino's epilogue does not implement: launch_conv_wino() must refuse it.)
+bool stored_f32(const nhans_ctx* c, const StackPlan& p, int b, int cv) {
+    if (c->prec != 1 || !c->wino_f32 || b < 0 || b > 7) return false;
+    if (c->wino_f32 == 2) return b < 4 && !(b == 3 && cv == 1);
+    if (c->wino_f32 == 3) return b == 1 && cv == 1;
+    if (cv == 0) return p.wino[b][2] && (b == 0 || p.wino[b][1]);
+    if (b == 7) return false;
+    const BlockGeo& nx = c->stack[b + 1];             // read by conv1 of the next block and, in an identity block, by its conv2's epilogue
+    return p.wino[b][2] && p.wino[b + 1][1] && nx.cin == nx.cout && p.wino[b + 1][2];
+}
+
+// Tap on the finished tensor `idx` (`words` values of `chan` channels, stored in the active precision's layout).
+// Calibration: its running |x| maximum.  Debug capture: the tensor itself as f32 NHWC, out of its layout and exponent
+// (the chunks of a call follow one another in cap_out).
+void tap(nhans_ctx* c, int idx, const float* buf, size_t words, int chan, hipStream_t s, bool f32_layout = false) {
+    if (c->calibrating) launch_absmax(buf, words, c->prec && !f32_layout, c->up(idx), c->amax_dev + idx, s);
+    if (c->cap_idx != idx) return;
+    if (!c->prec) note_launch("activation tap copy", hipMemcpyAsync(c->cap_out, buf, words * 4, hipMemcpyDeviceToDevice, s));
+    else if (f32_layout) launch_scale_copy(buf, words, c->up(idx), c->cap_out, s);
+    else launch_unsplit(buf, (int64_t)(words / chan), chan, c->up(idx), c->cap_out, s);
+    c->cap_out += words;
+}
+
+size_t stack_buf_floats(const nhans_ctx* c, int64_t wf) {
+    size_t m = 0;
+    for (const auto& g : c->stack) m = std::max(m, (size_t)g.hout * g.wout * g.cout);
+    return m * (size_t)wf;
+}
+
+// floats per frame window of StackBufs::T: the largest conv2 output among the channel-changing blocks whose conv2
+// has a Winograd form (4x4 filters: resblock2_1)
+size_t transform_buf_floats(const nhans_ctx* c, int64_t wf) {
+    size_t m = 0;
+    for (const auto& g : c->stack)
+        if (g.cin != g.cout && g.cin > 1 && g.kh == 4) m = std::max(m, (size_t)g.hout * g.wout * g.cout);
+    return m * (size_t)wf;
+}
+
+// Runs blocks [0, upto) for frames [g0, g0+n); returns the buffer holding the last output.
+// upto = 8: whole stack; upto = 9: + last_conv (output in sb.A).
+// Two passes over the same code: pass 0 builds every conv's arguments and records which of them the Winograd kernel
+// accepts (StackPlan), pass 1 builds them again with the tensor layouts and saturation limits that follow from the plan
+// and launches.  A launch whose eligibility differs between the passes is an error, not a fallback.
+// rb (nullable): per-frame first window row in `logmag` (online enhancement, WinRows::rb); null: frame g's window starts at
+// row g - 17
+float* run_stack_chunk(nhans_ctx* c, const float* logmag, const int* rb, const StackBufs& sb, int64_t g0, int n, int upto,
+                       hipStream_t s) {
+    StackPlan plan;
+    float* result = nullptr;
+    const int* clipmap = sb.f_clip + g0;
+    for (int pass = 0; pass < 2; ++pass) {
+    const bool go = pass == 1;
+    // (pass 0: record; pass 1: the launch must be the one that was planned)
+    // (a launch that failed or was refused ends the chunk: nothing later may run on a buffer that was never written)
+    auto dead = [&] { return go && launch_error_pending(); };
+    auto conv = [&](int b, int cv, const ConvArgs& a) {
+        const bool w = wino_form(a);
+        if (!go) { plan.wino[b][cv] = w; return; }
+        if (dead()) return;
+        if (w != plan.wino[b][cv]) {
+            note_refusal("stack conv whose Winograd eligibility changed between planning and launch");
+            return;
+        }
+        run_conv(c, a, s);
+    };
+    // frame b's 35 x 201 image = rows g0 + b - 17 ... of the log-magnitude spectrogram, zero rows outside its clip
+    // (SN/apply.py:170-186,378: strided_crop, never materialised -- the first conv and the 1 -> 64 residual of
+    // resblock1_1 read the spectrogram where it lies)
+    // (rows are counted from the chunk's first frame -- the tensor pointer handed to the kernels is logmag + g0 * 201 --, so the
+    // kernels' 32-bit element indices stay below (frames_per_chunk + 35) * 201 however long the batch is)
+    // (online: rows are where the per-frame table rb says, in a tensor small enough for 32-bit indices, WinRows::rb)
+    const WinRows win{sb.f_t + g0, sb.f_T + g0, -kCenter, kCenter, rb ? rb + g0 : nullptr};
+    const float* const lm_chunk = rb ? logmag : logmag + (size_t)g0 * kBins;
+    float *x = sb.X, *a1 = sb.A, *y = sb.Y;
+    // pass 0 plans the WHOLE stack whatever `upto` is -- the layout of block b's output follows from block b + 1's
+    // readers, and the debug entry point (upto = block + 1) must see the tensors the production call writes
+    for (int b = 0; b < 8 && (b < upto || !go); ++b) {
+        const BlockGeo& g = c->stack[b];
+        const std::string p = "m" + std::to_string(b);
+        const float* cb1 = sb.cb_all + c->cond_off[2 * b];
+        const float* cb2 = sb.cb_all + c->cond_off[2 * b + 1];
+        if (b == 0) {
+            DirectArgs d{};
+            d.src = lm_chunk; d.win = win; d.w = c->A(p + ".c1.w"); d.H = g.hin; d.W = g.win; d.KH = g.kh; d.KW = g.kw;
+            d.sh = 1; d.sw = 1;
+            int o; same_pad(g.hin, g.kh, 1, &o, &d.pt); same_pad(g.win, g.kw, 1, &o, &d.pl);
+            d.Ho = g.hout; d.Wo = g.wout; d.M = n * g.hout * g.wout; d.out = a1;
+            d.cb = cb1; d.cb_stride = c->cond_cols; d.img_clip = clipmap;
+            d.tf = c->A(p + ".c1.tf"); d.tt = c->A(p + ".c1.tt"); d.ff = c->A(p + ".c1.ff");
+            if (!d.tt || !d.ff) d.tt = d.ff = nullptr;
+            d.relu = 1; d.out_split = c->prec && !stored_f32(c, plan, 0, 0); d.sat = c->prec ? c->status_dev : nullptr;
+            d.out_scale = c->down(SA(0, 0)); d.sat_limit = sat_limit_for(plan, 0, 2);
+            d.fdHoWo = make_fastdiv(g.hout * g.wout); d.fdWo = make_fastdiv(g.wout);
+            if (go && !dead()) {
+                Prof pr(c, s, "direct_conv64");
+                launch_direct_conv64(d, s);
+                pr.done(2.0 * d.M * g.kh * g.kw * 64, 0);
+            }
+        } else {
+            ConvArgs a{};
+            fill_epilogue_defaults(c, a);
+            a.nseg = 1;
+            a.seg[0] = make_seg(x, c->WP(p + ".c1.wpk"), g.hin, g.win, g.cin, g.kh, g.kw, g.sh, g.sw, true);
+            set_out_geometry(a, n, g.hout, g.wout, g.cout, g.cout, g.cout, a1);
+            a.cb = cb1; a.cb_stride = c->cond_cols; a.img_clip = clipmap;
+            a.tf = c->A(p + ".c1.tf"); a.tt = c->A(p + ".c1.tt"); a.ff = c->A(p + ".c1.ff");
+            a.ws = c->WS(p + ".c1");
+            a.wino_u = c->A(p + ".c1.wino"); a.wino_ws = c->A(p + ".c1.wino.ws");
+            a.in_scale = c->up(SA(b - 1, 1)); a.out_scale = c->down(SA(b, 0));
+            a.sat_limit = sat_limit_for(plan, b, 2);
+            a.in_f32 = stored_f32(c, plan, b - 1, 1); a.out_split = c->prec && !stored_f32(c, plan, b, 0);
+            conv(b, 1, a);
+        }
+        if (go) tap(c, SA(b, 0), a1, (size_t)n * g.hout * g.wout * g.cout, g.cout, s, stored_f32(c, plan, b, 0));
+        ConvArgs a{};
+        fill_epilogue_defaults(c, a);
+        a.nseg = 1;
+        a.seg[0] = make_seg(a1, c->WP(p + ".c2.wpk"), g.hout, g.wout, g.cout, g.kh, g.kw, 1, 1, true);
+        a.cb = cb2; a.cb_stride = c->cond_cols; a.img_clip = clipmap;
+        a.tf = c->A(p + ".c2.tf"); a.tt = c->A(p + ".c2.tt"); a.ff = c->A(p + ".c2.ff");
+        a.idw = c->A(p + ".c2.idw");
+        a.ws = c->WS(p + ".c2");
+        a.wino_u = c->A(p + ".c2.wino"); a.wino_ws = c->A(p + ".c2.wino.ws");
+        a.in_scale = c->up(SA(b, 0)); a.out_scale = c->down(SA(b, 1));
+        a.sat_limit = sat_limit_for(plan, b + 1, 1);
+        a.in_f32 = stored_f32(c, plan, b, 0); a.out_split = c->prec && !stored_f32(c, plan, b, 1);
+        float* out;
+        if (b == 0) {                       // 1 -> 64 transform on the window image itself
+            a.id_mode = 2; a.id = lm_chunk; a.id_win = win; a.idH = g.hin; a.idW = g.win; a.idsh = 1; a.idsw = 1;
+            out = x;
+        } else if (g.cin == g.cout) {       // identity shortcut, written in place over the block input
+            a.id_mode = 1; a.id = x; a.id_ld = g.cout; a.id_split = c->prec && !stored_f32(c, plan, b - 1, 1);
+            a.id_scale = c->up(SA(b - 1, 1));
+            // (in place only if input and output share a layout: a thread's output bytes are its residual bytes then)
+            out = stored_f32(c, plan, b - 1, 1) == stored_f32(c, plan, b, 1) ? x : y;
+        } else {
+            // Channel-changing block.  If its conv2 -- as a one-segment conv with an f32 residual tensor -- has a
+            // Winograd form, the 1x1 strided `_transform` conv (which cannot ride in the K loop of the transformed
+            // domain; 3 % of the block's MACs) runs first on its own into an f32 tensor that conv2's epilogue then adds
+            // like a residual (the bias of both is in conv2's bias row).  Otherwise it is extra K columns of conv2.
+            ConvArgs w = a;
+            w.id_mode = 1; w.id = sb.T; w.id_ld = g.cout; w.id_split = 0;
+            w.idw = c->A("head.dense.idw");     // ones
+            set_out_geometry(w, n, g.hout, g.wout, g.cout, g.cout, g.cout, y);
+            if (go ? plan.wino[b][2] : wino_form(w)) {
+                ConvArgs t{};
+                fill_epilogue_defaults(c, t);
+                t.nseg = 1;
+                t.seg[0] = make_seg(x, c->WP(p + ".c2.wpk_t"), g.hin, g.win, g.cin, 1, 1, g.sh, g.sw, false);
+                set_out_geometry(t, n, g.hout, g.wout, g.cout, g.cout, g.cout, sb.T);
+                t.cb = c->A("zero"); t.cb_stride = 0;
+                t.ws = c->WS(p + ".c2");            // (conv2 and the transform share one column scale: fold.py emit())
+                t.relu = 0; t.out_split = 0;
+                t.in_scale = c->up(SA(b - 1, 1));   // (f32 output: no exponent)
+                if (go && !dead()) {
+                    if (c->stream_1x1 && conv_1x1_stream_eligible(t)) {       // 1.75 GB in, 3.5 GB out, 16 KFLOP per output pixel: a stream
+                        Prof pr(c, s, "conv_1x1_stream");
+                        launch_conv_1x1_stream(t, s);
+                        const double fl = 2.0 * (double)t.M * g.cin * g.cout;
+                        pr.done(fl, (double)t.M * (g.cin + g.cout) * 4.0, nullptr, 3.0 * fl);
+                    } else {
+                        run_conv(c, t, s);
+                    }
+                }
+                a = w;
+            } else {                        // (x and a1 share one exponent)
+                a.nseg = 2;
+                a.seg[1] = make_seg(x, c->WP(p + ".c2.wpk_t"), g.hin, g.win, g.cin, 1, 1, g.sh, g.sw, false);
+            }
+            out = y;
+        }
+        set_out_geometry(a, n, g.hout, g.wout, g.cout, g.cout, g.cout, out);
+        conv(b, 2, a);
+        if (go) tap(c, SA(b, 1), out, (size_t)n * g.hout * g.wout * g.cout, g.cout, s, stored_f32(c, plan, b, 1));
+        if (out == y) std::swap(x, y);
+    }
+    result = x;
+    if (upto >= 9 && go && !dead()) {       // last_conv [5,1] VALID + BN + ReLU  (SN/main.py:232-236)
+        const BlockGeo& g = c->stack[7];
+        ConvArgs a{};
+        fill_epilogue_defaults(c, a);
+        a.nseg = 1;
+        a.seg[0] = make_seg(x, c->WP("head.conv.wpk"), g.hout, g.wout, g.cout, g.hout, 1, 1, 1, false);
+        set_out_geometry(a, n, 1, g.wout, 512, 512, 512, a1);
+        a.cb = c->A("head.conv.cb");
+        a.ws = c->WS("head.conv");
+        a.in_scale = c->up(SA(7, 1)); a.out_scale = c->down(kActHead);
+        run_conv(c, a, s);
+        tap(c, kActHead, a1, (size_t)n * g.wout * 512, 512, s);
+        result = a1;
+    }
+    }
+    c->last_plan = plan;
+    return result;
+}
+
+int mask_net_impl(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
+                  const float* eb, float* logits, float* denoised, const StackBufs& sb, int64_t wf,
+                  hipStream_t s) {
+    const int64_t total = foff[nclips];
+    { int rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc; }
+    launch_frame_index(sb.foff_dev, nclips, total, c->lookahead, sb.f_clip, sb.f_t, sb.f_T, s);
+    return mask_net_run(c, logmag, nullptr, logmag, total, nclips, ea, eb, logits, denoised, sb, wf, s);
+}
+
+struct HostTables {
+    std::vector<int64_t> soff, foff, ooff;
+    std::vector<int> bclip, bpos;
+};
+
+}  // namespace
+
+// ---- embedding tower for `n` context images already in HBM ----------------------------------
+int embed_impl(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, float* X, float* Ab, float* Y,
+               hipStream_t s) {
+    const auto& T = c->tower;
+    for (int i0 = 0; i0 < n; i0 += c->contexts_per_chunk) {
+        const int nc = std::min(c->contexts_per_chunk, n - i0);
+        const float* img = ctx_lm + (size_t)i0 * kCtxFrames * kBins;
+        float *x = X, *a1 = Ab, *y = Y;
+        for (int b = 0; b < 4; ++b) {
+            const BlockGeo& g = T[b];
+            const std::string p = "t" + std::to_string(b);
+            if (b == 0) {
+                DirectArgs d{};
+                d.src = img; d.w = c->A(p + ".c1.w"); d.H = g.hin; d.W = g.win; d.KH = g.kh; d.KW = g.kw;
+                d.sh = g.sh; d.sw = g.sw;
+                int o; same_pad(g.hin, g.kh, g.sh, &o, &d.pt); same_pad(g.win, g.kw, g.sw, &o, &d.pl);
+                d.Ho = g.hout; d.Wo = g.wout; d.M = nc * g.hout * g.wout; d.out = a1;
+                d.cb = c->A(p + ".c1.cb"); d.cb_stride = 0; d.img_clip = nullptr; d.tf = nullptr; d.tt = nullptr; d.ff = nullptr;
+                d.relu = 1; d.fdHoWo = make_fastdiv(g.hout * g.wout); d.fdWo = make_fastdiv(g.wout);
+                d.out_split = c->prec; d.sat = c->prec ? c->status_dev : nullptr; d.out_scale = c->down(TA(0, 0)); d.sat_limit = kSatLimitF16;
+                Prof pr(c, s, "direct_conv64");
+                launch_direct_conv64(d, s);
+                pr.done(2.0 * d.M * g.kh * g.kw * 64, 0);
+            } else {
+                ConvArgs a{};
+                fill_epilogue_defaults(c, a);
+                a.nseg = 1;
+                a.seg[0] = make_seg(x, c->WP(p + ".c1.wpk"), g.hin, g.win, g.cin, g.kh, g.kw, g.sh, g.sw, true);
+                set_out_geometry(a, nc, g.hout, g.wout, g.cout, g.cout, g.cout, a1);
+                a.cb = c->A(p + ".c1.cb");
+                a.ws = c->WS(p + ".c1");
+                a.in_scale = c->up(TA(b - 1, 1)); a.out_scale = c->down(TA(b, 0));
+                a.kgroup = -1;                  // a handful of context images: grouped sum, split-K when small
+                run_conv(c, a, s);
+            }
+            tap(c, TA(b, 0), a1, (size_t)nc * g.hout * g.wout * g.cout, g.cout, s);
+            ConvArgs a{};
+            fill_epilogue_defaults(c, a);
+            a.nseg = 1;
+            a.seg[0] = make_seg(a1, c->WP(p + ".c2.wpk"), g.hout, g.wout, g.cout, g.kh, g.kw, 1, 1, true);
+            if (b == 0) {
+                a.id_mode = 2; a.id = img; a.idH = g.hin; a.idW = g.win; a.idsh = g.sh; a.idsw = g.sw;
+                a.idw = c->A(p + ".c2.idw");
+            } else {
+                a.nseg = 2;
+                a.seg[1] = make_seg(x, c->WP(p + ".c2.wpk_t"), g.hin, g.win, g.cin, 1, 1, g.sh, g.sw, false);
+            }
+            set_out_geometry(a, nc, g.hout, g.wout, g.cout, g.cout, g.cout, y);
+            a.cb = c->A(p + ".c2.cb");
+            a.ws = c->WS(p + ".c2");
+            // (the `_transform` segment reads x, whose exponent tie_exponents() keeps equal to a1's: one accumulator)
+            a.in_scale = c->up(TA(b, 0)); a.out_scale = c->down(TA(b, 1));
+            run_conv(c, a, s);                  // (stride 1: halo kernel; measured faster than split-K here)
+            tap(c, TA(b, 1), y, (size_t)nc * g.hout * g.wout * g.cout, g.cout, s);
+            std::swap(x, y);
+        }
+        const BlockGeo& g = T[3];
+        Prof pr(c, s, "avgpool");
+        launch_avgpool(x, nc, g.hout * g.wout, g.cout, c->prec, c->up(TA(3, 1)), emb_out + (size_t)i0 * kEmb, s);
+        pr.done(0, (double)nc * g.hout * g.wout * g.cout * 4);
+    }
+    return NHANS_OK;
+}
+
+size_t tower_buf_floats(const nhans_ctx* c) {
+    size_t m = 0;
+    for (const auto& g : c->tower) m = std::max(m, (size_t)g.hout * g.wout * g.cout);
+    return m * (size_t)c->contexts_per_chunk;
+}
+
+// ---- conditioned stack + head ---------------------------------------------------------------
+size_t stack_ws_bytes(const nhans_ctx* c, int64_t total, int nclips, int64_t wf) {
+    size_t b = 3 * ws_size(total, 4) + ws_size(nclips + 1, 8) + ws_size((size_t)nclips * c->cond_cols, 4);
+    b += 3 * ws_size(stack_buf_floats(c, wf), 4);
+    b += ws_size(transform_buf_floats(c, wf), 4);
+    return b;
+}
+
+void stack_take(nhans_ctx* c, int64_t total, int nclips, int64_t wf, StackBufs* sb) {
+    sb->f_clip = ws_take<int>(c, total); sb->f_t = ws_take<int>(c, total); sb->f_T = ws_take<int>(c, total);
+    sb->foff_dev = ws_take<int64_t>(c, nclips + 1);
+    sb->cb_all = ws_take<float>(c, (size_t)nclips * c->cond_cols);
+    const size_t nb = stack_buf_floats(c, wf);
+    sb->X = ws_take<float>(c, nb); sb->A = ws_take<float>(c, nb); sb->Y = ws_take<float>(c, nb);
+    sb->T = ws_take<float>(c, transform_buf_floats(c, wf));
+}
+
+// The stack + head over `total` frame windows whose per-frame tables (sb.f_clip, f_t, f_T) are in place.  win_src / rb:
+// the window source (rb nullable, see run_stack_chunk); centre [total, 201]: the frames' own rows, the head's identity
+// term (mixed_central, SN/main.py:242) -- offline that is win_src itself.
+int mask_net_run(nhans_ctx* c, const float* win_src, const int* rb, const float* centre, int64_t total, int nclips,
+                 const float* ea, const float* eb, float* logits, float* denoised, const StackBufs& sb, int64_t wf,
+                 hipStream_t s) {
+    {
+        Prof pr(c, s, "cond_proj");
+        launch_cond(ea, eb, nclips, c->A("cond.w"), c->A("cond.base"), c->cond_cols, sb.cb_all, s);
+        pr.done(2.0 * nclips * 2 * kEmb * c->cond_cols, 0);
+    }
+    const BlockGeo& g = c->stack[7];
+    for (int64_t g0 = 0; g0 < total; g0 += wf) {
+        const int n = (int)std::min<int64_t>(wf, total - g0);
+        float* hc = run_stack_chunk(c, win_src, rb, sb, g0, n, 9, s);
+        if (launch_error_pending()) break;      // (reported by the entry point: NHANS_EHIP naming the launch)
+        // last_dense 13312 -> 201 (+bias) and denoised = mixed_central + out  (SN/main.py:237-242)
+        ConvArgs a{};
+        fill_epilogue_defaults(c, a);
+        a.nseg = 1;
+        a.seg[0] = make_seg(hc, c->WP("head.dense.wpk"), 1, 1, g.wout * 512, 1, 1, 1, 1, false);
+        set_out_geometry(a, n, 1, 1, 256, kBins, kBins, denoised + g0 * kBins);
+        a.cb = c->A("head.dense.cb");
+        a.ws = c->WS("head.dense");
+        a.out_split = 0;
+        a.relu = 0;
+        a.in_scale = c->up(kActHead);
+        a.id_mode = 1; a.id = centre + g0 * kBins; a.id_ld = kBins; a.idw = c->A("head.dense.idw");
+        if (logits) { a.aux = logits + g0 * kBins; a.aux_ld = kBins; }
+        a.kgroup = -1;                          // K = 13312 over a few hundred frames: grouped sum, split-K when small
+        run_conv(c, a, s);
+    }
+    return NHANS_OK;
+}
+
+// ---- STFT / iSTFT host-side block tables ----------------------------------------------------
+int stft_impl(nhans_ctx* c, const float* wav, const int64_t* soff, int nclips, int maxf, float* logmag,
+              float* phase, int64_t* dev_tables /*3*(nclips+1)*/, int* dev_blocks, std::vector<int64_t>* foff_out,
+              hipStream_t s, const char* prof_name) {
+    std::vector<int64_t> foff(nclips + 1, 0);
+    std::vector<int> bclip, bf0;
+    for (int i = 0; i < nclips; ++i) {
+        int64_t t = nhans_num_frames(soff[i + 1] - soff[i]);
+        if (t > kMaxFramesPerClip) return fail(NHANS_EINVAL, "clip " + std::to_string(i) + " has more than " +
+                                               std::to_string(kMaxFramesPerClip) + " frames (32-bit offsets within a clip)");
+        if (maxf > 0) {
+            if (t < maxf) return fail(NHANS_ESHORT, "conditioning clip " + std::to_string(i) + " has " +
+                                      std::to_string(t) + " frames; " + std::to_string(maxf) + " needed");
+            t = maxf;
+        }
+        foff[i + 1] = foff[i] + t;
+        for (int f0 = 0; f0 < t; f0 += kStftFramesPerBlock) { bclip.push_back(i); bf0.push_back(f0); }
+    }
+    const int nb = (int)bclip.size();
+    int rc = h2d(c, dev_tables, soff, (nclips + 1) * 8, s); if (rc) return rc;
+    rc = h2d(c, dev_tables + (nclips + 1), foff.data(), (nclips + 1) * 8, s); if (rc) return rc;
+    rc = h2d(c, dev_blocks, bclip.data(), (size_t)nb * 4, s); if (rc) return rc;
+    rc = h2d(c, dev_blocks + nb, bf0.data(), (size_t)nb * 4, s); if (rc) return rc;
+    ClipTable t{dev_tables, dev_tables + (nclips + 1), nullptr};
+    Prof pr(c, s, prof_name ? prof_name : phase ? "stft_features" : "stft_context_features");   // (contexts: log-magnitude only, 200 frames per clip)
+    launch_stft(wav, t, dev_blocks, dev_blocks + nb, nb, c->A("tw400"), c->A("window"), logmag, phase, s);
+    pr.done(0, (double)foff[nclips] * (kHop * 4 + (phase ? 2 : 1) * kBins * 4));
+    if (foff_out) *foff_out = foff;
+    return NHANS_OK;
+}
+
+size_t stft_blocks(const int64_t* soff, int nclips, int maxf) {
+    size_t nb = 0;
+    for (int i = 0; i < nclips; ++i) {
+        int64_t t = nhans_num_frames(soff[i + 1] - soff[i]);
+        if (maxf > 0 && t > maxf) t = maxf;
+        nb += (size_t)((t + kStftFramesPerBlock - 1) / kStftFramesPerBlock);
+    }
+    return nb;
+}
+
+int istft_impl(nhans_ctx* c, const float* logmag, const float* phase, const int64_t* foff, int nclips,
+               const int64_t* ooff, float* wav_out, int64_t* dev_tables, int* dev_blocks, hipStream_t s,
+               const char* prof_name) {
+    std::vector<int> bclip, bh0;
+    for (int i = 0; i < nclips; ++i) {
+        const int64_t t = foff[i + 1] - foff[i];
+        if (t > kMaxFramesPerClip) return fail(NHANS_EINVAL, "clip " + std::to_string(i) + " has more than " +
+                                               std::to_string(kMaxFramesPerClip) + " frames (32-bit offsets within a clip)");
+        if (t <= 0) continue;
+        for (int h0 = 0; h0 < t + 2; h0 += kIstftHopsPerBlock) { bclip.push_back(i); bh0.push_back(h0); }
+    }
+    const int nb = (int)bclip.size();
+    int rc = h2d(c, dev_tables, foff, (nclips + 1) * 8, s); if (rc) return rc;
+    rc = h2d(c, dev_tables + (nclips + 1), ooff, (nclips + 1) * 8, s); if (rc) return rc;
+    rc = h2d(c, dev_blocks, bclip.data(), (size_t)nb * 4, s); if (rc) return rc;
+    rc = h2d(c, dev_blocks + nb, bh0.data(), (size_t)nb * 4, s); if (rc) return rc;
+    ClipTable t{nullptr, dev_tables, dev_tables + (nclips + 1)};
+    Prof pr(c, s, prof_name);
+    launch_istft(logmag, phase, t, dev_blocks, dev_blocks + nb, nb, c->A("tw400"), c->A("wsyn"), wav_out, s);
+    pr.done(0, (double)foff[nclips] * (kHop * 4 + 2 * kBins * 4));
+    return NHANS_OK;
+}
+
+size_t istft_blocks(const int64_t* foff, int nclips) {
+    size_t nb = 0;
+    for (int i = 0; i < nclips; ++i) {
+        const int64_t t = foff[i + 1] - foff[i];
+        if (t > 0) nb += (size_t)((t + 2 + kIstftHopsPerBlock - 1) / kIstftHopsPerBlock);
+    }
+    return nb;
+}
+
+// ---- the whole offline path (nhans_enhance_clips; the built-in calibration of nhans_create: host_ctx.hip) ---------
+int enhance_clips_body(nhans_ctx* c, const float* mix, const int64_t* moff, int nclips, const float* ca,
+                        const int64_t* caoff, const float* cbw, const int64_t* cboff, float* den_wav,
+                        float* mixed_wav, float* logmag_out, float* phase_out, float* logits_out, float* emb_out,
+                        void* stream) {
+    int rc = NHANS_OK;
+    if (!mix || !moff || !ca || !caoff || !cbw || !cboff || !den_wav || nclips < 1)
+        return fail(NHANS_EINVAL, "null argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<int64_t> foff(nclips + 1, 0);
+    for (int i = 0; i < nclips; ++i) {
+        const int64_t n = moff[i + 1] - moff[i];
+        if (n >= kWin && (n - kWin) % kHop != 0)
+            return fail(NHANS_EINVAL, "mixture clip " + std::to_string(i) + " is not trimmed to a whole frame count");
+        foff[i + 1] = foff[i] + nhans_num_frames(n);
+    }
+    const int64_t total = foff[nclips];
+    const int64_t wf = std::min<int64_t>(c->frames_per_chunk, std::max<int64_t>(total, 1));
+    // workspace plan
+    const size_t nb_mix = stft_blocks(moff, nclips, 0), nb_ca = stft_blocks(caoff, nclips, kCtxFrames),
+                 nb_cb = stft_blocks(cboff, nclips, kCtxFrames), nb_is = istft_blocks(foff.data(), nclips);
+    const size_t nblk = std::max(std::max(nb_mix, nb_ca), std::max(nb_cb, nb_is));
+    size_t bytes = 4 * ws_size((size_t)total * kBins, 4) + ws_size((size_t)2 * nclips * kCtxFrames * kBins, 4) +
+                   ws_size((size_t)2 * nclips * kEmb, 4) + 4 * ws_size(2 * (nclips + 1), 8) + 4 * ws_size(2 * nblk, 4);
+    bytes += std::max(stack_ws_bytes(c, total, nclips, wf), 3 * ws_size(tower_buf_floats(c), 4));
+    rc = ws_reserve(c, bytes); if (rc) return rc;
+    float* lm = ws_take<float>(c, (size_t)total * kBins);
+    float* ph = ws_take<float>(c, (size_t)total * kBins);
+    float* den = ws_take<float>(c, (size_t)total * kBins);
+    float* lg = ws_take<float>(c, (size_t)total * kBins);
+    float* ctxlm = ws_take<float>(c, (size_t)2 * nclips * kCtxFrames * kBins);
+    float* emb = ws_take<float>(c, (size_t)2 * nclips * kEmb);
+    int64_t* tabs[4]; int* blks[4];
+    for (int i = 0; i < 4; ++i) { tabs[i] = ws_take<int64_t>(c, 2 * (nclips + 1)); blks[i] = ws_take<int>(c, 2 * nblk); }
+    const size_t mark = c->ws_top;
+
+    rc = stft_impl(c, mix, moff, nclips, 0, lm, ph, tabs[0], blks[0], nullptr, s); if (rc) return rc;
+    rc = stft_impl(c, ca, caoff, nclips, kCtxFrames, ctxlm, nullptr, tabs[1], blks[1], nullptr, s); if (rc) return rc;
+    rc = stft_impl(c, cbw, cboff, nclips, kCtxFrames, ctxlm + (size_t)nclips * kCtxFrames * kBins, nullptr, tabs[2],
+                   blks[2], nullptr, s);
+    if (rc) return rc;
+    {
+        const size_t nb = tower_buf_floats(c);
+        float* X = ws_take<float>(c, nb); float* A = ws_take<float>(c, nb); float* Y = ws_take<float>(c, nb);
+        rc = embed_impl(c, ctxlm, 2 * nclips, emb, X, A, Y, s); if (rc) return rc;
+    }
+    if (total > 0) {
+        c->ws_top = mark;
+        StackBufs sb;
+        stack_take(c, total, nclips, wf, &sb);
+        rc = mask_net_impl(c, lm, foff.data(), nclips, emb, emb + (size_t)nclips * kEmb, lg, den, sb, wf, s);
+        if (rc) return rc;
+        rc = istft_impl(c, den, ph, foff.data(), nclips, moff, den_wav, tabs[3], blks[3], s); if (rc) return rc;
+        if (mixed_wav) {
+            // tabs/blks[3] are reused: same stream, so the first launch has consumed them in order
+            rc = istft_impl(c, lm, ph, foff.data(), nclips, moff, mixed_wav, tabs[3], blks[3], s); if (rc) return rc;
+        }
+        if (logmag_out) HIP_TRY(hipMemcpyAsync(logmag_out, lm, (size_t)total * kBins * 4, hipMemcpyDeviceToDevice, s));
+        if (phase_out) HIP_TRY(hipMemcpyAsync(phase_out, ph, (size_t)total * kBins * 4, hipMemcpyDeviceToDevice, s));
+        if (logits_out) HIP_TRY(hipMemcpyAsync(logits_out, lg, (size_t)total * kBins * 4, hipMemcpyDeviceToDevice, s));
+    }
+    if (emb_out) HIP_TRY(hipMemcpyAsync(emb_out, emb, (size_t)2 * nclips * kEmb * 4, hipMemcpyDeviceToDevice, s));
+    return NHANS_OK;
+}
+
+// ================================================================================================
+extern "C" {
+
+size_t nhans_workspace_bytes(nhans_ctx* c, int64_t total_frames, int nclips) {
+    if (!c) return 0;
+    const int64_t wf = std::min<int64_t>(c->frames_per_chunk, std::max<int64_t>(total_frames, 1));
+    size_t b = stack_ws_bytes(c, total_frames, nclips, wf);
+    b = std::max(b, 3 * ws_size(tower_buf_floats(c), 4));
+    b += 4 * ws_size((size_t)total_frames * kBins, 4);                       // logmag, phase, denoised, logits
+    b += ws_size((size_t)2 * nclips * kCtxFrames * kBins, 4) + ws_size((size_t)2 * nclips * kEmb, 4);
+    b += 1 << 20;
+    return b;
+}
+
+static int stft_features_body(nhans_ctx* c, const float* wav, const int64_t* soff, int nclips, int maxf,
+                        float* logmag, float* phase, void* stream) {
+    int rc = NHANS_OK;
+    if (!wav || !soff || !logmag || nclips < 0) return fail(NHANS_EINVAL, "null argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t nb = stft_blocks(soff, nclips, maxf);
+    rc = ws_reserve(c, ws_size(2 * (nclips + 1), 8) + ws_size(2 * nb, 4)); if (rc) return rc;
+    int64_t* tabs = ws_take<int64_t>(c, 2 * (nclips + 1));
+    int* blocks = ws_take<int>(c, 2 * nb);
+    return stft_impl(c, wav, soff, nclips, maxf, logmag, phase, tabs, blocks, nullptr, s);
+}
+
+int nhans_stft_features(nhans_ctx* c, const float* wav, const int64_t* soff, int nclips, int maxf,
+                        float* logmag, float* phase, void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(stft_features_body(c, wav, soff, nclips, maxf, logmag, phase, stream));
+}
+
+static int embed_body(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, void* stream) {
+    int rc = NHANS_OK;
+    if (!ctx_lm || !emb_out || n < 0) return fail(NHANS_EINVAL, "null argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t nb = tower_buf_floats(c);
+    rc = ws_reserve(c, 3 * ws_size(nb, 4)); if (rc) return rc;
+    float* X = ws_take<float>(c, nb); float* A = ws_take<float>(c, nb); float* Y = ws_take<float>(c, nb);
+    return embed_impl(c, ctx_lm, n, emb_out, X, A, Y, s);
+}
+
+int nhans_embed(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(embed_body(c, ctx_lm, n, emb_out, stream));
+}
+
+static int mask_net_body(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
+                   const float* eb, float* logits, float* denoised, void* stream) {
+    int rc = NHANS_OK;
+    if (!logmag || !foff || !ea || !eb || !denoised || nclips < 1) return fail(NHANS_EINVAL, "null argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t total = foff[nclips];
+    if (total <= 0) return NHANS_OK;
+    const int64_t wf = std::min<int64_t>(c->frames_per_chunk, total);
+    rc = ws_reserve(c, stack_ws_bytes(c, total, nclips, wf)); if (rc) return rc;
+    StackBufs sb;
+    stack_take(c, total, nclips, wf, &sb);
+    return mask_net_impl(c, logmag, foff, nclips, ea, eb, logits, denoised, sb, wf, s);
+}
+
+int nhans_mask_net(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
+                   const float* eb, float* logits, float* denoised, void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(mask_net_body(c, logmag, foff, nclips, ea, eb, logits, denoised, stream));
+}
+
+static int debug_block_output_body(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
+                             const float* eb, int64_t frame0, int nframes, int block, float* out, void* stream) {
+    int rc = NHANS_OK;
+    if (!logmag || !foff || !ea || !eb || !out || block < 0 || block > 8) return fail(NHANS_EINVAL, "bad argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t total = foff[nclips];
+    if (frame0 < 0 || frame0 + nframes > total) return fail(NHANS_EINVAL, "frame range outside batch");
+    rc = ws_reserve(c, stack_ws_bytes(c, total, nclips, nframes)); if (rc) return rc;
+    StackBufs sb;
+    stack_take(c, total, nclips, nframes, &sb);
+    rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc;
+    launch_frame_index(sb.foff_dev, nclips, total, c->lookahead, sb.f_clip, sb.f_t, sb.f_T, s);
+    launch_cond(ea, eb, nclips, c->A("cond.w"), c->A("cond.base"), c->cond_cols, sb.cb_all, s);
+    const float* res = run_stack_chunk(c, logmag, nullptr, sb, frame0, nframes, block + 1, s);
+    size_t per;
+    if (block == 8) per = (size_t)26 * 512;
+    else per = (size_t)c->stack[block].hout * c->stack[block].wout * c->stack[block].cout;
+    if (c->prec && block < 8 && stored_f32(c, c->last_plan, block, 1)) launch_scale_copy(res, per * nframes, c->up(SA(block, 1)), out, s);
+    else if (c->prec) launch_unsplit(res, (int64_t)nframes * (int64_t)(per / (block == 8 ? 512 : c->stack[block].cout)),
+                                block == 8 ? 512 : c->stack[block].cout, c->up(block == 8 ? kActHead : SA(block, 1)), out, s);
+    else HIP_TRY(hipMemcpyAsync(out, res, per * nframes * 4, hipMemcpyDeviceToDevice, s));
+    return NHANS_OK;
+}
+
+int nhans_debug_block_output(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
+                             const float* eb, int64_t frame0, int nframes, int block, float* out, void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(debug_block_output_body(c, logmag, foff, nclips, ea, eb, frame0, nframes, block, out, stream));
+}
+
+// Any stored tensor of the stack + head (index 8 .. 24) for frames [frame0, frame0 + nframes): the production launch
+// sequence -- one plan for the whole stack, frames_per_chunk frame windows per pass counted from frame0 -- up to the block
+// that writes it; the tap() point of that tensor converts every chunk's finished buffer.
+static int debug_activation_body(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
+                                 const float* eb, int64_t frame0, int nframes, int index, float* out, void* stream) {
+    int rc = NHANS_OK;
+    if (!logmag || !foff || !ea || !eb || !out || nclips < 1 || nframes < 1) return fail(NHANS_EINVAL, "bad argument");
+    if (index < SA(0, 0) || index >= kNumAct)
+        return fail(NHANS_EINVAL, "activation index outside the stack's 8 .. " + std::to_string(kNumAct - 1) + " (tower tensors: nhans_debug_tower_activation)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t total = foff[nclips];
+    if (frame0 < 0 || frame0 + nframes > total) return fail(NHANS_EINVAL, "frame range outside batch");
+    const int64_t wf = std::min<int64_t>(c->frames_per_chunk, nframes);
+    rc = ws_reserve(c, stack_ws_bytes(c, total, nclips, wf)); if (rc) return rc;
+    StackBufs sb;
+    stack_take(c, total, nclips, wf, &sb);
+    rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc;
+    launch_frame_index(sb.foff_dev, nclips, total, c->lookahead, sb.f_clip, sb.f_t, sb.f_T, s);
+    launch_cond(ea, eb, nclips, c->A("cond.w"), c->A("cond.base"), c->cond_cols, sb.cb_all, s);
+    const int upto = index == kActHead ? 9 : (index - SA(0, 0)) / 2 + 1;
+    c->cap_idx = index; c->cap_out = out;
+    for (int64_t g0 = frame0; g0 < frame0 + nframes; g0 += wf) {
+        run_stack_chunk(c, logmag, nullptr, sb, g0, (int)std::min<int64_t>(wf, frame0 + nframes - g0), upto, s);
+        if (launch_error_pending()) break;
+    }
+    c->cap_idx = -1; c->cap_out = nullptr;
+    return NHANS_OK;
+}
+
+int nhans_debug_activation(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
+                           const float* eb, int64_t frame0, int nframes, int index, float* out, void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(debug_activation_body(c, logmag, foff, nclips, ea, eb, frame0, nframes, index, out, stream));
+}
+
+// Any stored tensor of the embedding tower (index 0 .. 7) for n context images: nhans_embed's own launches (chunks of
+// contexts_per_chunk images, the pooled embeddings go to the workspace) with the tap() point of that tensor copying out.
+static int debug_tower_activation_body(nhans_ctx* c, const float* ctx_lm, int n, int index, float* out, void* stream) {
+    int rc = NHANS_OK;
+    if (!ctx_lm || !out || n < 1) return fail(NHANS_EINVAL, "bad argument");
+    if (index < 0 || index >= SA(0, 0))
+        return fail(NHANS_EINVAL, "activation index outside the tower's 0 .. 7 (stack tensors: nhans_debug_activation)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t nb = tower_buf_floats(c);
+    rc = ws_reserve(c, 3 * ws_size(nb, 4) + ws_size((size_t)n * kEmb, 4)); if (rc) return rc;
+    float* X = ws_take<float>(c, nb); float* A = ws_take<float>(c, nb); float* Y = ws_take<float>(c, nb);
+    float* emb = ws_take<float>(c, (size_t)n * kEmb);
+    c->cap_idx = index; c->cap_out = out;
+    rc = embed_impl(c, ctx_lm, n, emb, X, A, Y, s);
+    c->cap_idx = -1; c->cap_out = nullptr;
+    return rc;
+}
+
+int nhans_debug_tower_activation(nhans_ctx* c, const float* ctx_lm, int n, int index, float* out, void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(debug_tower_activation_body(c, ctx_lm, n, index, out, stream));
+}
+
+static int istft_body(nhans_ctx* c, const float* logmag, const float* phase, const int64_t* foff, int nclips,
+                const int64_t* ooff, float* wav_out, void* stream) {
+    int rc = NHANS_OK;
+    if (!logmag || !phase || !foff || !ooff || !wav_out) return fail(NHANS_EINVAL, "null argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t nb = istft_blocks(foff, nclips);
+    rc = ws_reserve(c, ws_size(2 * (nclips + 1), 8) + ws_size(2 * nb, 4)); if (rc) return rc;
+    int64_t* tabs = ws_take<int64_t>(c, 2 * (nclips + 1));
+    int* blocks = ws_take<int>(c, 2 * nb);
+    return istft_impl(c, logmag, phase, foff, nclips, ooff, wav_out, tabs, blocks, s);
+}
+
+int nhans_istft(nhans_ctx* c, const float* logmag, const float* phase, const int64_t* foff, int nclips,
+                const int64_t* ooff, float* wav_out, void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(istft_body(c, logmag, phase, foff, nclips, ooff, wav_out, stream));
+}
+
+int nhans_enhance_clips(nhans_ctx* c, const float* mix, const int64_t* moff, int nclips, const float* ca,
+                        const int64_t* caoff, const float* cbw, const int64_t* cboff, float* den_wav,
+                        float* mixed_wav, float* logmag_out, float* phase_out, float* logits_out, float* emb_out,
+                        void* stream) {
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(enhance_clips_body(c, mix, moff, nclips, ca, caoff, cbw, cboff, den_wav, mixed_wav, logmag_out, phase_out, logits_out, emb_out, stream));
+}
+
+}  // extern "C"

@@ -83,12 +83,12 @@ __device__ __forceinline__ uint32_t fd_div(uint32_t n, const FastDiv& f) {
 // 0.0 otherwise -- strided_crop of SN/apply.py:170-186,378 (35-row windows of the log-magnitude spectrogram, zero rows
 // -- not the silence floor -- outside the clip) without ever materialising [T, 35, 201].
 // t == nullptr: plain images [B, H, W].
-// rb != nullptr (online enhancement, nhans_api.hip): image b's row h is tensor row rb[b] + h instead -- the frames of one
+// rb != nullptr (online enhancement, host_online.hip): image b's row h is tensor row rb[b] + h instead -- the frames of one
 // launch then need not be consecutive rows of one tensor (each online stream brings its own history and look-ahead rows)
 struct WinRows {
     const int* t;
     const int* T;
-    int row0, pad;      // (row0 may be negative: nhans_api.hip counts rows from the launch's first frame, row0 = -pad)
+    int row0, pad;      // (row0 may be negative: host_net.hip counts rows from the launch's first frame, row0 = -pad)
     const int* rb;      // nullable: per-image first row (row0 is then unused)
 };
 constexpr int kNoRow = -2147483647 - 1;      // "this row is a zero row" where an element index is stored (conv_epilogue.h)
@@ -148,7 +148,7 @@ struct ConvArgs {
     int in_f32;            // prec 1 only: seg[0].src is f32 NHWC (scaled like a split tensor) -- a tensor that only Winograd
                            // launches read (conv_wino.hip, the one kernel that takes it)
     const float* ws;       // prec 1: per-channel power-of-two that undoes the weight pre-scaling
-    // Split-f16 tensors are STORED times a per-tensor power of two 2^-e (nhans_api.hip: activation exponents), so that
+    // Split-f16 tensors are STORED times a per-tensor power of two 2^-e (host_internal.h: activation exponents), so that
     // what a trained or an odd model produces stays inside the f16 range.  The epilogue computes in the unscaled
     // domain, bit for bit what it computes with e = 0: ws is multiplied by in_scale = 2^e(input), idw by id_scale =
     // 2^e(residual), and the result by out_scale = 2^-e(output) on its way to memory.  All three are 1 for f32 tensors.

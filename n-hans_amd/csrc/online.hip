@@ -1,4 +1,4 @@
-// Data movement of online enhancement (nhans_online_push, nhans_api.hip): carried samples + new input -> the STFT's
+// Data movement of online enhancement (nhans_online_push, host_online.hip): carried samples + new input -> the STFT's
 // staging buffer, history rows of the state + the push's new rows -> the window source of the stack, synthesis staging
 // for the iSTFT, final samples -> the caller, and the next state slot.  Every move is a list of contiguous runs built on
 // the host; one launch per list, one workgroup per run.  Pure copies: the bits are those of the kernels that made them.

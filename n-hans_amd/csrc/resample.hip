@@ -7,7 +7,7 @@
 //     y[m] = sum_k h[m M + half - k L] x[k]  =  sum_{j < J} h[p + j L] x[q - j],   m M + half = q L + p,  0 <= p < L
 // -- ONE chain of J fmaf in float32, j ascending, absent inputs as 0.0f (fir_chain below).  The offline call, the
 // streaming push and both converters of a live session run ONE kernel body (resample_kernel) on run descriptors the
-// host builds in one place (RateStage::add_runs, nhans_api.hip), so a stream's output cannot depend on how it was cut:
+// host builds in one place (RateStage::add_runs, host_internal.h), so a stream's output cannot depend on how it was cut:
 // a push only changes where an input sample is fetched from (the caller's new samples or the J carried ones), never the
 // arithmetic on it.  The body is a template over a source (PCM int16 / float32, or the wet/dry mix of a live session
 // formed while the span is staged) and a sink (float32 with the optional int16 grid and fixed peak, or scaled PCM);

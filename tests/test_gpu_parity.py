@@ -428,7 +428,7 @@ def test_winograd_convs_against_golden_logits(_eng_d, case, n):
 def test_f32_stored_winograd_tensors(_eng_d):
     """Option winograd_f32_tensors (default 1): the five stack tensors that only Winograd launches read -- conv1's output
     of resblock1_1 / 1_2 / 2_2 and the block outputs of resblock1_1 / 2_1 -- are stored f32 NHWC instead of split NHWC
-    (nhans_api.hip: stored_f32); 0 = every tensor split.  Same golden logits at the same bar either way, the block
+    (host_net.hip: stored_f32); 0 = every tensor split.  Same golden logits at the same bar either way, the block
     outputs of the debug entry point (which has to know each tensor's layout) agree between the two to the split
     format's 22 bits.  (The refusal of a wrong-layout reader: the next test.)"""
     _eng_d.set_precision("f16x3")
@@ -456,7 +456,7 @@ def test_f32_stored_winograd_tensors(_eng_d):
 
 
 def test_an_f32_stored_tensor_without_a_winograd_reader_is_refused_not_misread(_eng_d):
-    """The layouts follow from what conv_wino_eligible() says about each launch's own arguments (nhans_api.hip:
+    """The layouts follow from what conv_wino_eligible() says about each launch's own arguments (host_net.hip:
     run_stack_chunk plans, then launches).  Should plan and kernel ever disagree, the reader of an f32-stored tensor must
     refuse -- a direct kernel would stage f32 words as split halves.  winograd_f32_tensors = 2 is the test value that
     forces the disagreement (f32 storage whatever the readers are); with the Winograd form off every reader is a direct

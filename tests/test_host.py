@@ -259,6 +259,24 @@ def test_library_exports_every_declared_symbol(lib_built):
     assert h.nhans_create_ex(0, bad, 64, 0, None, 0, ctypes.byref(out)) == -1 and b"magic" in h.nhans_last_error()
 
 
+def test_signature_table_matches_header():
+    """hip.SIGNATURES against every declaration of include/nhans_hip.h: the argument count (`(void)` is 0) and the return
+    type -- None for void, the ctypes twin of every other one the header uses."""
+    header = open(os.path.join(ROOT, "include", "nhans_hip.h")).read()
+    code = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    restypes = {"void": None, "int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
+                "uint32_t": ctypes.c_uint32, "const char*": ctypes.c_char_p}
+    decls = re.findall(r"([A-Za-z_][A-Za-z_0-9 ]*\*?)\s*\b(nhans_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", code)
+    assert [name for _, name, _ in decls] == list(hip.SIGNATURES)          # every function once, in the header's order
+    for ret, name, params in decls:
+        restype, argtypes = hip.SIGNATURES[name]
+        params = " ".join(params.split())
+        assert len(argtypes) == (0 if params == "void" else params.count(",") + 1), name
+        ret = " ".join(ret.split()).replace(" *", "*")
+        assert ret in restypes, (name, ret)
+        assert restype is restypes[ret], name
+
+
 def test_launch_failure_returns_negative_code(lib_built):
     """The launch-error channel end to end: a kernel launch that cannot happen (here: no device at
     all on the CPU box; on the GPU box tests/test_gpu_scale.py asks for 1 MB of LDS) must come back

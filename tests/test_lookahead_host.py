@@ -1,6 +1,6 @@
 """Selectable look-ahead, the parts that need no device: the output contract with look-ahead L (include/nhans_hip.h) as
 online.emitted / out_counts / latency_ms restate it, brute force over every T <= 60 x L in 0 ... 17 x ended / not; the
-bounds of the carried state of a push (nhans_api.hip: kOnRows = 42, kOnDenRows = 24) with on_lo / on_s0 restated here;
+bounds of the carried state of a push (host_internal.h: kOnRows = 42, kOnDenRows = 24) with on_lo / on_s0 restated here;
 the live chain against the C function; the header, the binding and the command line's refusals."""
 import os
 import re
