@@ -148,6 +148,13 @@ void nhans_destroy(nhans_ctx* ctx);
  *          "stream_1x1" (1, default: the stand-alone 1x1 strided `_transform` conv of resblock2_1 -- an HBM stream, 1.75 GB in and
  *           3.5 GB out per pass -- runs on its own streaming kernel, conv_1x1_stream.hip; 0: on the generic implicit-GEMM kernel.
  *           Identical bits),
+ *          "row_split" (1, default: in split-f16 mode the 3x3 convs of resblock3 and resblock4 -- 9 x 51 and 5 x 26 images, where
+ *           the top filter row of the first output row and the bottom filter row of the last read nothing but SAME padding --
+ *           run as one launch per class of output rows (top, interior, bottom), each with only the filter rows that touch the
+ *           image: 7 % and 13 % fewer matrix-core MACs in those convs.  0: one launch per conv.  2: a measurement value --
+ *           every conv of the stack that can be split is, the strided ones with 4 % to gain included.  Identical bits:
+ *           the filter rows left out added exact zeros; the profile's `flops` of the class launches sum to the single
+ *           launch's, `mfma_flops` is what ran),
  *          "split_k" (1, default: the launches too small to fill the chip -- the head's dense layer, the embedding tower
  *           at a few clips -- run one workgroup per (tile, K group) through a scratch buffer; 0: every workgroup walks
  *           its K groups itself.  The groups and the order of the additions depend on the layer only: identical bits),
@@ -257,6 +264,14 @@ int nhans_debug_launch_probe(size_t dynamic_lds_bytes, void* stream);
  * that do not toggle the multipliers.  Replaces nothing in the reference: measurement. */
 int nhans_debug_mfma_ceiling(double seconds, void* stream, double* sustained_tflops, double* first_tflops,
                              int* launches);
+
+/* Host helper (no device involved): the row classes "row_split" launches a conv segment by.  Input height H, filter height
+ * KH, row stride and top padding pt (output height ceil(H / stride)): output row ho reads input rows ho*stride - pt + kh, and
+ * consecutive output rows with the same range of kh inside [0, H) form a class.  Writes (oh0, rows, kh0, KH') per class to
+ * out[4 * cap] in row order and returns their number -- a class launch has Ho = rows, KH = KH' and pt' = pt - kh0 -
+ * oh0*stride.  0: some output row reads padding only, such a conv is not split.  Bad arguments or more classes than
+ * `cap`: NHANS_EINVAL. */
+int nhans_debug_row_classes(int H, int KH, int stride, int pt, int* out, int cap);
 
 /* Host helper (no device involved): CRC-32C (Castagnoli) of a host buffer continued from `crc`
  * (0 to start).  TensorFlow checkpoint bundles store crc32c::Mask() of it per tensor; tfbundle.py

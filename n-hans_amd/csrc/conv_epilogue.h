@@ -388,17 +388,22 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[T
         const uint32_t ho = fd_div(rem, a.fdWo);
         const uint32_t wo = rem - ho * a.fdWo.d;
         const int clip = a.img_clip ? a.img_clip[b] : 0;
+        // output view of a row-class launch (ConvArgs::oh0, Ho_full; identity for every other launch): (b, ho, wo) is the
+        // class's own pixel, the tensor's is row oh0 + ho of an image of Ho_full rows
+        const uint32_t hov = ho + (uint32_t)a.oh0;
+        const int remv = (int)(hov * a.fdWo.d + wo);
+        const int mv = mz < 0 ? mz : (int)(b * (uint32_t)a.Ho_full * a.fdWo.d) + remv;
         // (1-channel residual image: element index into a.id, or kNoRow = a zero row of a sliding-window image, WinRows; a
         // window's rows are counted from the launch's first frame, so a VALID index may be negative: the rows of a clip that
         // began before this chunk of frames)
         int ids;
         if (a.id_mode == 2 && a.id_win.t) {
-            const int h = (int)ho * a.idsh;
+            const int h = (int)hov * a.idsh;
             ids = win_row_ok(a.id_win, (int)b, h) ? win_row(a.id_win, (int)b, h) * a.idW + (int)wo * a.idsw : kNoRow;
         } else {
-            ids = (int)((b * a.idH + ho * a.idsh) * a.idW + wo * a.idsw);
+            ids = (int)((b * a.idH + hov * a.idsh) * a.idW + wo * a.idsw);
         }
-        rowinfo[tid] = make_int4(clip * a.cb_stride, (int)rem * a.N, mz, ids);
+        rowinfo[tid] = make_int4(clip * a.cb_stride, remv * a.N, mv, ids);
     }
     if (kDev && es) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); es[0] = (long long)__builtin_amdgcn_s_memtime(); }
     __syncthreads();

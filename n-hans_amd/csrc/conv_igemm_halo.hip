@@ -247,11 +247,21 @@ __global__ void __launch_bounds__((NCW + NPW) * 64) conv_igemm_halo(const ConvAr
         const __amdgpu_buffer_rsrc_t wr1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(nseg > 1 ? a.seg[1].wpk : a.seg[0].wpk) + (size_t)nt0 * 1024, 0, 0x7FFFFFFF, 0x00020000);
         const unsigned wvo = (unsigned)ptid * 16u;
         const int bstride_b = (int)(bstride * 4);
-        int wtap = -1, wseg = 0;                        // tap within its segment's array (the last one again past the end)
+        // Row-class launches (ConvSeg::kh0, KHfull) walk KH of the filter's KHfull rows: block cc*KHfull*KW + (kh0 + kh)*KW + kw
+        // of the array fold.py packed for the whole filter -- after the KH*KW taps of a chunk the cursor steps over the
+        // rows that are not applied.  kh0 = 0, KHfull = KH: every step is the plain ++wtap.
+        int wper = KH0 * KW0, wskip = (a.seg[0].KHfull - KH0) * KW0, wrun = 0;
+        int wtap = a.seg[0].kh0 * KW0 - 1, wseg = 0;    // tap within its segment's array (the last one again past the end)
 #define NH_ISSUE_B(ST)                                                                             \
     {                                                                                              \
         if (tapB < total && !(ABL & 4)) {                                                          \
-            if (tapB == ntap0) { wseg = 1; wtap = 0; } else ++wtap;                                \
+            if (tapB == ntap0) {                                                                   \
+                wseg = 1; wtap = a.seg[1].kh0 * a.seg[1].KW; wrun = 1;                             \
+                wper = KH1 * a.seg[1].KW; wskip = (a.seg[1].KHfull - KH1) * a.seg[1].KW;           \
+            } else {                                                                               \
+                if (wrun == wper) { wrun = 0; wtap += wskip; }                                     \
+                ++wtap; ++wrun;                                                                    \
+            }                                                                                      \
         }                                                                                          \
         ++tapB;                                                                                    \
         float* sb_ = smem + B_BASE + (ST) * B_STAGE;                                               \

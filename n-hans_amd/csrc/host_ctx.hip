@@ -422,6 +422,10 @@ int nhans_set_option(nhans_ctx* c, const char* key, int64_t value) {
     else if (k == "winograd_f32_tensors") c->wino_f32 = (value == 2 || value == 3) ? (int)value : value != 0;
     else if (k == "split_k") c->split_k = value != 0;
     else if (k == "stream_1x1") c->stream_1x1 = value != 0;
+    else if (k == "row_split") {
+        if (value < 0 || value > 2) return fail(NHANS_EINVAL, "row_split must be 0, 1 or 2 (2: every conv that can be split, a measurement value)");
+        c->row_split = (int)value;
+    }
     else if (k == "precision") {
         if (value != 0 && value != 1) return fail(NHANS_EINVAL, "precision must be 0 (f32) or 1 (f16x3)");
         if (value == 1 && !c->A("head.dense.wpk_h"))

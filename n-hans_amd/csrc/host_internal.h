@@ -83,6 +83,7 @@ struct nhans_ctx {
     static constexpr size_t kscratch_cap = (size_t)384 << 20;
     bool kscratch_failed = false;
     int stream_1x1 = 1;         // option stream_1x1: the stand-alone `_transform` conv on conv_1x1_stream.hip (0: the generic conv kernel; same bits)
+    int row_split = 1;          // option row_split: convs on small images as one launch per row class (host_net.hip: run_conv_row_classes; 0: one launch; same bits)
     int split_k = 1;            // option split_k: 0 = never split (the grouped walk inside one workgroup: same bits)
     int* kcounter = nullptr;
     int kcounter_n = 1024;

@@ -35,16 +35,19 @@ ConvSeg make_seg(const float* src, const float* wpk, int H, int W, int C, int KH
     if (same) { same_pad(H, KH, sh, &o, &pb); g.pt = pb; same_pad(W, KW, sw, &o, &pb); g.pl = pb; }
     else { g.pt = 0; g.pl = 0; }
     g.nchunks = KH * KW * C / 32;
+    g.kh0 = 0; g.KHfull = KH;
     return g;
 }
 
 void set_out_geometry(ConvArgs& a, int B, int Ho, int Wo, int N, int Nreal, int ldo, float* out) {
     a.Ho = Ho; a.Wo = Wo; a.M = B * Ho * Wo; a.N = N; a.Nreal = Nreal; a.ldo = ldo; a.out = out;
+    a.oh0 = 0; a.Ho_full = Ho;
     a.fdHoWo = make_fastdiv((uint32_t)(Ho * Wo));
     a.fdWo = make_fastdiv((uint32_t)Wo);
 }
 
-void run_conv(nhans_ctx* c, const ConvArgs& a0, hipStream_t s) {
+// -> the name of the kernel variant that ran
+const char* run_conv(nhans_ctx* c, const ConvArgs& a0, hipStream_t s) {
     ConvArgs a = a0;
     if (kDev) {      // timing experiment (wrong results): NHANS_ABLATE_TF=1 -> no position table at all
         static const bool no_tf = [] { const char* e = getenv("NHANS_ABLATE_TF"); return e && atoi(e) != 0; }();
@@ -67,7 +70,95 @@ void run_conv(nhans_ctx* c, const ConvArgs& a0, hipStream_t s) {
     const char* name = "conv_igemm";
     double mfma = 0;
     double fl = launch_conv_igemm(a, s, &name, &mfma);
+    if (a.Ho_full != a.Ho) {
+        // a row-class launch stands for its rows of the direct convolution with the WHOLE filter (the rows it leaves out
+        // multiply padding): `flops` stays on that basis and sums to the unsplit launch's, `mfma` is what was executed
+        double kfull = 0;
+        for (int i = 0; i < a.nseg; ++i) kfull += (double)a.seg[i].KHfull * a.seg[i].KW * a.seg[i].C;
+        fl = 2.0 * (double)a.M * kfull * (double)a.Nreal;
+    }
     p.done(fl, 0, name, mfma);
+    return name;
+}
+
+struct RowClass { int oh0, rows, kh0, kh; };    // output rows [oh0, oh0 + rows) use the filter rows [kh0, kh0 + kh)
+
+// ---- row classes: 3x3 / 4x4 convs on small images without the filter rows that read only padding -------------------
+// Output row ho of a conv segment (input height H, filter height KH, row stride s, top padding pt) reads input rows
+// ho*s - pt + kh; the filter rows kh whose input row lies outside [0, H) multiply zeros.  Consecutive output rows with the
+// same range of useful kh form a class.  3 x 3, stride 1, pt 1: top (row 0, kh 1..2), interior (kh 0..2), bottom (row
+// H - 1, kh 0..1).  -> number of classes, 0 if some output row has no useful filter row at all (such a conv is not
+// split), -1 if `cap` is too small.  Ho = ceil(H / s), the output height of every conv of the network.
+int row_classes(int H, int KH, int s, int pt, RowClass* out, int cap) {
+    const int Ho = (H + s - 1) / s;
+    int n = 0;
+    for (int ho = 0; ho < Ho; ++ho) {
+        const int hi0 = ho * s - pt;
+        const int lo = std::max(0, -hi0), hi = std::min(KH, H - hi0);      // useful kh: [lo, hi)
+        if (hi <= lo) return 0;
+        if (n && out[n - 1].kh0 == lo && out[n - 1].kh == hi - lo) { ++out[n - 1].rows; continue; }
+        if (n == cap) return -1;
+        out[n++] = RowClass{ho, 1, lo, hi - lo};
+    }
+    return n;
+}
+
+// Which convs run as one launch per row class (option row_split = 1): those whose class launches together measured faster
+// than the single launch in the per-kernel pass of one box -- keyed on the share of filter-row applications that multiply
+// only padding, the one thing a class launch removes; what it adds is a tile's fixed cost (prologue + epilogue) for the
+// partial tiles at the end of two more launches and two launch gaps.  profiles/rowsplit/README.md has the table.
+//   convs (one chunk of 3,776 frame windows, ms)         H -> Ho  rows applied  share    single   classes
+//   resblock4 3x3 stride 1 (x 3), conv_igemm_halo<128>     5 ->  5   15 -> 13    13.3 %   14.70    13.31   split
+//   resblock4_1 conv1 3x3 stride 2, pointwise mode         9 ->  5   15 -> 13    13.3 %    2.54     2.27   split
+//   resblock3 3x3 stride 1 (x 3), conv_igemm_halo<128>     9 ->  9   27 -> 25     7.4 %   13.91    13.56   split
+//   resblock2_1 conv1 4x4 stride 2, pointwise mode        35 -> 18   72 -> 69     4.2 %    4.35     4.30   single launch (within the spread)
+//   resblock3_1 conv1 3x3 stride 2, pointwise mode        18 ->  9   27 -> 26     3.7 %    2.36     2.44   single launch
+// (not measured, single launch: resblock2's 4x4 stride-1 convs without their Winograd form, 5.6 %)
+bool row_split_pays(const ConvSeg& g, const RowClass* rc, int n) {
+    int applied = 0, rows = 0;
+    for (int i = 0; i < n; ++i) { applied += rc[i].rows * rc[i].kh; rows += rc[i].rows; }
+    return 100 * (rows * g.KH - applied) >= 7 * rows * g.KH;    // >= 7 % of the filter-row applications
+}
+
+// The launch `a` as one launch per row class, in row order on the same stream; false: `a` is not split (nothing was
+// launched).  Split are f16x3 launches of the halo kernel or its pointwise mode with 128-channel tiles -- the kernels
+// whose producer walks ConvSeg::kh0 / KHfull; eligibility is asked per class launch, and a class launch that came out on
+// another kernel after all is an error, not a fallback.
+constexpr int kMaxRowClasses = 8;
+bool halo_family(ConvArgs a) {          // (launch_conv_igemm()'s order of tests, 128-channel tiles)
+    if (a.variant < 2 || a.kgroup != 0 || a.N % 128 != 0 || a.in_f32 || conv_wino_eligible(a)) return false;
+    a.halo64_tile512 = 0;
+    return conv_igemm_halo_eligible(a) || conv_igemm_halo_pw_eligible(a);
+}
+bool run_conv_row_classes(nhans_ctx* c, const ConvArgs& a, hipStream_t s) {
+    const ConvSeg& g = a.seg[0];
+    if (!c->row_split || a.prec != 1 || a.Ho_full != a.Ho || a.M % (a.Ho * a.Wo) != 0 || !halo_family(a)) return false;
+    if (a.nseg > 1 && a.seg[1].KH != 1) return false;
+    RowClass rc[kMaxRowClasses];
+    const int n = row_classes(g.H, g.KH, g.sh, g.pt, rc, kMaxRowClasses);
+    if (n < 2 || (g.H + g.sh - 1) / g.sh != a.Ho) return false;
+    if (c->row_split == 1 && !row_split_pays(g, rc, n)) return false;
+    const int B = a.M / (a.Ho * a.Wo);
+    ConvArgs q[kMaxRowClasses];
+    for (int i = 0; i < n; ++i) {
+        q[i] = a;
+        q[i].Ho = rc[i].rows; q[i].M = B * rc[i].rows * a.Wo; q[i].oh0 = rc[i].oh0; q[i].Ho_full = a.Ho;
+        q[i].fdHoWo = make_fastdiv((uint32_t)(rc[i].rows * a.Wo));
+        ConvSeg& h = q[i].seg[0];
+        h.KH = rc[i].kh; h.kh0 = rc[i].kh0; h.KHfull = g.KH; h.pt = g.pt - rc[i].kh0 - rc[i].oh0 * g.sh;
+        h.nchunks = h.KH * h.KW * h.C / 32;
+        if (a.nseg > 1) {               // the 1x1 strided `_transform` segment: its one filter row, from the class's first row on
+            ConvSeg& t = q[i].seg[1];
+            if ((rc[i].oh0 + rc[i].rows - 1) * t.sh - t.pt >= t.H || rc[i].oh0 * t.sh - t.pt < 0) return false;
+            t.pt -= rc[i].oh0 * t.sh;
+        }
+        q[i].wino_u = nullptr; q[i].wino_ws = nullptr;      // (a class has no Winograd form)
+        if (!halo_family(q[i])) return false;
+    }
+    for (int i = 0; i < n && !launch_error_pending(); ++i)
+        if (std::strncmp(run_conv(c, q[i], s), "conv_igemm_halo", 15) != 0)
+            note_refusal("row-class conv launch on a kernel that does not walk filter-row classes");
+    return true;
 }
 
 // Which convs of the stack run in their Winograd form (conv_wino.hip), for one chunk of frame windows.  NOT a restatement
@@ -148,6 +239,7 @@ float* run_stack_chunk(nhans_ctx* c, const float* logmag, const int* rb, const S
             note_refusal("stack conv whose Winograd eligibility changed between planning and launch");
             return;
         }
+        if (!w && run_conv_row_classes(c, a, s)) return;
         run_conv(c, a, s);
     };
     // frame b's 35 x 201 image = rows g0 + b - 17 ... of the log-magnitude spectrogram, zero rows outside its clip
@@ -649,6 +741,15 @@ static int debug_block_output_body(nhans_ctx* c, const float* logmag, const int6
                                 block == 8 ? 512 : c->stack[block].cout, c->up(block == 8 ? kActHead : SA(block, 1)), out, s);
     else HIP_TRY(hipMemcpyAsync(out, res, per * nframes * 4, hipMemcpyDeviceToDevice, s));
     return NHANS_OK;
+}
+
+int nhans_debug_row_classes(int H, int KH, int stride, int pt, int* out, int cap) {
+    if (H < 1 || KH < 1 || stride < 1 || pt < 0 || cap < 0 || (cap && !out)) return fail(NHANS_EINVAL, "row classes: bad argument");
+    std::vector<RowClass> rc((size_t)(H + stride - 1) / stride);
+    const int n = row_classes(H, KH, stride, pt, rc.data(), (int)rc.size());
+    if (n > cap) return fail(NHANS_EINVAL, "row classes: " + std::to_string(n) + " classes, room for " + std::to_string(cap));
+    for (int i = 0; i < n; ++i) { out[4 * i] = rc[i].oh0; out[4 * i + 1] = rc[i].rows; out[4 * i + 2] = rc[i].kh0; out[4 * i + 3] = rc[i].kh; }
+    return n;
 }
 
 int nhans_debug_block_output(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,

@@ -110,6 +110,11 @@ struct ConvSeg {
     int H, W, C;
     int KH, KW, sh, sw, pt, pl;
     int nchunks;        // KH*KW*C/32
+    // Row-class launches (host_net.hip: row_classes): this launch applies only the filter rows kh0 .. kh0 + KH - 1 of a
+    // filter of KHfull rows -- wpk is still the whole filter's array, packed (32-channel chunk, kh, kw), and pt is the
+    // class's own, pt - kh0 - oh0*sh (may be negative).  An ordinary launch has kh0 = 0, KHfull = KH.  Only the halo
+    // kernel and its pointwise mode read these.
+    int kh0, KHfull;
 };
 
 struct ConvArgs {
@@ -117,6 +122,9 @@ struct ConvArgs {
     int nseg;
     int Ho, Wo;
     int M;              // B*Ho*Wo
+    // Output view (conv_epilogue.h): the launch's Ho rows are rows oh0 .. oh0 + Ho - 1 of an output image of Ho_full rows
+    // -- position table, stored pixel and one-channel residual take row oh0 + ho.  Ordinary launch: oh0 = 0, Ho_full = Ho.
+    int oh0, Ho_full;
     int N;              // padded output channels (multiple of the N tile)
     int Nreal;          // stored channels
     int ldo;            // out row stride

@@ -45,6 +45,7 @@ SIGNATURES = {
     "nhans_take_status": (_int, [_vp, _ip, _vp]),
     "nhans_debug_launch_probe": (_int, [_size, _vp]),
     "nhans_debug_mfma_ceiling": (_int, [_dbl, _vp, _dp, _dp, _ip]),
+    "nhans_debug_row_classes": (_int, [_int, _int, _int, _int, _ip, _int]),
     "nhans_crc32c": (ctypes.c_uint32, [ctypes.c_uint32, _vp, _size]),
     # online enhancement
     "nhans_online_open": (_int, [_vp, _int, _vp, _i64p, _vp, _i64p, _int, _vp, _vpp]),
