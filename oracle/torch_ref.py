@@ -26,8 +26,11 @@ STACK = [("resblock1_1", 1), ("resblock1_2", 1), ("resblock2_1", 2), ("resblock2
 class TorchRef:
     """Weights are converted once to NCHW/OIHW tensors of `dtype`."""
 
-    def __init__(self, weights, kind="denoiser", dtype=torch.float32):
-        self.kind, self.dtype = kind, dtype
+    def __init__(self, weights, kind="denoiser", dtype=torch.float32, store=None):
+        """store (nullable callable (idx, t) -> t): what becomes of stored tensor `idx` (the HIP library's numbering, see
+        tower / mask_net) between the layer that writes it and the layers that read it -- an emulation of a storage format
+        (split_store, flushed_store below).  The network continues from its result; None: from t itself, untouched."""
+        self.kind, self.dtype, self.store = kind, dtype, store
         self.W = {}
         for k, v in weights.items():
             t = torch.from_numpy(np.ascontiguousarray(v)).to(dtype)
@@ -68,10 +71,12 @@ class TorchRef:
         return (x - m) * (g * torch.rsqrt(v + 1e-3)) + b
 
     # -- embedding tower (SN/main.py:102-124,190-216)
-    @staticmethod
-    def _tap(acts, idx, t):
+    def _tap(self, acts, idx, t):
+        if self.store is not None:
+            t = self.store(idx, t)
         if acts is not None:
             acts[idx] = t.permute(0, 2, 3, 1).contiguous()          # NHWC, as the library stores it
+        return t
 
     def tower(self, ctx, acts=None):
         """acts (nullable dict): receives the stored tensors of the HIP library in its numbering (NHANS_NUM_ACTIVATIONS),
@@ -80,11 +85,11 @@ class TorchRef:
         for b, (name, st) in enumerate(TOWER):
             s = "embedding/" + name
             p1 = torch.relu(self.bn(self.conv(x, s + "_conv1", st, "SAME", False), s + "_conv1"))
-            self._tap(acts, 2 * b, p1)
+            p1 = self._tap(acts, 2 * b, p1)
             p1 = self.conv(p1, s + "_conv2", (1, 1), "SAME", True)
             p2 = self.conv(x, s + "_transform", st, "SAME", True)
             x = torch.relu(self.bn(p1 + p2, s + "_addition"))
-            self._tap(acts, 2 * b + 1, x)
+            x = self._tap(acts, 2 * b + 1, x)
         return x.mean(dim=(2, 3))
 
     def cont_embed(self, n, scope):
@@ -109,13 +114,13 @@ class TorchRef:
                 return t + pa[:, :, None, None] + pb[:, :, None, None] + te + fe
             p1 = self.conv(x, name + "_conv1", (st, st), "SAME", False)
             p1 = torch.relu(self.bn(cond(p1, name + "_conv1"), name + "_conv1"))
-            self._tap(acts, 8 + 2 * b, p1)
+            p1 = self._tap(acts, 8 + 2 * b, p1)
             p1 = cond(self.conv(p1, name + "_conv2", (1, 1), "SAME", True), name + "_conv2")
             p2 = x if x.shape[1] == p1.shape[1] else self.conv(x, name + "_transform", (st, st), "SAME", True)
             x = torch.relu(self.bn(p1 + p2, name + "_addition"))
-            self._tap(acts, 8 + 2 * b + 1, x)
+            x = self._tap(acts, 8 + 2 * b + 1, x)
         x = torch.relu(self.bn(self.conv(x, "last_conv", (1, 1), "VALID", False), "last_conv"))
-        self._tap(acts, 24, x)
+        x = self._tap(acts, 24, x)
         x = x.permute(0, 2, 3, 1).reshape(x.shape[0], -1)       # NHWC flatten: idx = w*512 + c
         out = x @ self.W["last_dense/w"] + self.W["last_dense/b"]
         return out, mixed[:, MIX_WIN // 2, :] + out
@@ -164,3 +169,29 @@ class TorchRef:
         den = lm[:nfr] + logits
         return dict(logmag=lm, phase=ph, logits=logits, denoised=den,
                     denoised_wav=self.istft(den, ph[:nfr]), frames_done=nfr)
+
+
+# -- storage formats of the HIP library's split-f16 mode, emulated on the tensors of a (float64) run: TorchRef(store=...)
+F16_MAX, F16_MIN_NORMAL = 65504.0, 2.0 ** -14
+
+
+def _split(t, e, flush):
+    s = torch.clamp(t * 2.0 ** -e, -F16_MAX, F16_MAX)
+    hi = s.to(torch.float16)                                        # (torch's f16 keeps subnormals)
+    if flush:
+        hi = torch.where(hi.abs() < F16_MIN_NORMAL, torch.zeros_like(hi), hi)
+    lo = (s - hi.to(s.dtype)).to(torch.float16)
+    if flush:
+        lo = torch.where(lo.abs() < F16_MIN_NORMAL, torch.zeros_like(lo), lo)
+    return (hi.to(s.dtype) + lo.to(s.dtype)) * 2.0 ** e
+
+
+def split_store(E):
+    """Tensor idx as the library holds it at the exponents E[idx]: s = t * 2^-E, clamped to +-65504, hi = f16(s),
+    lo = f16(s - hi), handed on as (hi + lo) * 2^E."""
+    return lambda idx, t: _split(t, E[idx], False)
+
+
+def flushed_store(E):
+    """split_store on a path that flushes f16 subnormals: every hi or lo with a magnitude below 2^-14 is zero."""
+    return lambda idx, t: _split(t, E[idx], True)

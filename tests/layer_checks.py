@@ -102,10 +102,10 @@ class Taps:
     """acts: {index: torch tensor NHWC} for all 25 tensors; emb [3,512]; logits and denoised [21,201] -- of one dtype."""
 
 
-def cpu_taps(W, kind, dtype, lms, ctx, emb_in=None, want=("tower", "stack")):
+def cpu_taps(W, kind, dtype, lms, ctx, emb_in=None, want=("tower", "stack"), store=None):
     """All stored tensors by oracle/torch_ref.py in `dtype`.  The stack is fed emb_in ([3,512] float32; None: this run's own
-    embeddings rounded to float32) so that stack errors are not the tower's."""
-    ref = TorchRef(W, kind, dtype)
+    embeddings rounded to float32) so that stack errors are not the tower's.  store: TorchRef's storage hook."""
+    ref = TorchRef(W, kind, dtype, store=store)
     t = Taps()
     t.acts, t.emb, t.logits, t.denoised = {}, None, None, None
     with torch.no_grad():
