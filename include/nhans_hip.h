@@ -684,6 +684,62 @@ int64_t nhans_level_live_gains(nhans_live* obj, int slot, float* out_host, int64
 int nhans_level_gains(nhans_ctx* ctx, const float* den_dev, const float* mix_dev, const int64_t* offsets_host, int nclips,
                       int window_hops, double wmax, float* w_out_dev, double* sums_out_dev, void* stream);
 
+/* ---- Live sessions: interleaved multi-channel PCM in and out ------------------------------------------------------------
+ * Capture and playback interfaces hand over interleaved frames -- element k * C + c is channel c of frame k --, almost
+ * always stereo.  An object opened here is a nhans_live whose pushes take frames of channels_in channels and return frames
+ * of channels_out channels (each 1 .. NHANS_INTERLEAVED_MAX_CHANNELS), formed and stored by the two converters' own
+ * launches: no launch, buffer or copy is added, a push issues the launches of a mono object with as many slots doing the
+ * same work.  Added without moving NHANS_ABI_VERSION; a caller that may meet an older library looks the functions up by
+ * symbol.  (The names begin with nhans_interleaved_: the live prefix's set of names is closed.)
+ *
+ * NHANS_INTERLEAVED_DOWNMIX.  One slot per stream; channels_in and channels_out are independent.  Sample k of the slot's
+ * incoming stream is
+ *     x[k] = float32( (sum over c = 0 .. channels_in - 1 of double(s[k * channels_in + c])) / double(channels_in) ),
+ * the sum starting at 0.0 and adding c in ascending order -- nhans_channel_mean's arithmetic, what the reference does to a
+ * stereo file --, formed while the incoming converter stages its input, stored nowhere; the converter carries x.  Each
+ * output sample, after steps 3 and 4 of the live output arithmetic, is stored channels_out times: dst[m * channels_out + c]
+ * for every c.  The stream is bit for bit a mono float32 slot fed x.
+ *
+ * NHANS_INTERLEAVED_SPLIT.  channels_in == channels_out == C, and stream g owns the C consecutive slots g C .. g C + C - 1:
+ * slot g C + c reads s[k * C + c] and writes dst[m * C + c], bit for bit a mono slot fed channel c alone, so every channel
+ * is enhanced on its own and the stereo image survives.  Every per-slot function of a nhans_live -- restart, conditioning,
+ * capture, look-ahead, the meter -- works on those slots as on any other; a caller gives the channels of a stream the same
+ * conditioning or different ones.  Gains are NOT linked across the channels of a stream: the meter and the automatic wet
+ * factor stay per slot, so automatic compensation may move two channels differently.
+ * A push moves the C slots of a stream by the same frames with the same end flag, so they have to be in step: when a
+ * push brings a stream frames or its end and its slots differ in samples taken, ended flag or look-ahead, the push is
+ * refused with NHANS_EINVAL naming the stream and the slot that differs, and nothing changes -- after nhans_live_restart
+ * of one channel alone, until the others are restarted too.
+ *
+ * Offsets and counts of the two functions below are per STREAM and in FRAMES; everything else -- the output contract
+ * (nhans_live_emitted of the frames pushed), the arithmetic, rewind, the errors that change nothing -- is the live
+ * section's.  nhans_live_push and nhans_live_out_counts refuse an object opened here, and the two functions below refuse
+ * one opened with nhans_live_open_slots; each message names the function to call instead. */
+#define NHANS_INTERLEAVED_DOWNMIX 0
+#define NHANS_INTERLEAVED_SPLIT 1
+#define NHANS_INTERLEAVED_MAX_CHANNELS 8
+
+/* nhans_live_open_slots for `nstreams` (>= 1) streams of interleaved frames: nstreams slots (downmix) or nstreams *
+ * channels_in slots (split), all unconditioned.  Channels outside 1 .. 8, split with channels_in != channels_out, an unknown
+ * mode and everything nhans_live_open_slots refuses: NHANS_EINVAL.  Close with nhans_live_close. */
+int nhans_interleaved_live_open(nhans_ctx* ctx, int nstreams, int channels_in, int channels_out, int mode, int rate_in,
+                                int in_format, double peak, int rate_out, int out_format, double out_scale, int flags,
+                                void* stream, nhans_live** out);
+
+/* Host only: the frames a push of in_frames_host[g] frames (end_host nullable) would report per stream -- in split mode
+ * the count all slots of the stream share; a stream whose slots are out of step is refused as the push refuses it. */
+int nhans_interleaved_live_out_counts(const nhans_live* obj, const int64_t* in_frames_host, const int* end_host,
+                                      int64_t* out_frames_host);
+
+/* nhans_live_push in frames: stream g brings in_frame_offsets_host[g+1] - in_frame_offsets_host[g] (>= 0) frames that start
+ * at element in_frame_offsets_host[g] * channels_in of in_dev; the out_frames_host[g] frames that became final are
+ * written from element out_frame_offsets_host[g] * channels_out of out_dev on, and the room
+ * out_frame_offsets_host[g+1] - out_frame_offsets_host[g], in frames, must hold them.  One call, the three stages of
+ * nhans_live_push, its snapshots for a failed launch and for nhans_live_rewind; the runs of the slots of a split stream
+ * point into the same frames, one channel apart. */
+int nhans_interleaved_live_push(nhans_live* obj, const void* in_dev, const int64_t* in_frame_offsets_host, const int* end_host,
+                                void* out_dev, const int64_t* out_frame_offsets_host, int64_t* out_frames_host, void* stream);
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

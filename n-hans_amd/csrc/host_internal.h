@@ -3,7 +3,7 @@
 //   host_net.hip      conv launch sequences (tower, stack, head), STFT / iSTFT block tables, the offline entry points
 //   host_online.hip   nhans_online_*, nhans_capture_*
 //   host_rate.hip     rate-conversion stages, nhans_resample*, nhans_peak_normalise, nhans_channel_mean, nhans_resampler_*
-//   host_live.hip     nhans_live_*, nhans_lookahead_live_*, nhans_capture_live_*, nhans_level_*
+//   host_live.hip     nhans_live_*, nhans_lookahead_live_*, nhans_capture_live_*, nhans_level_*, nhans_interleaved_*
 // A unit calls down only: ctx <- net <- online <- live and ctx <- rate <- live.  (One call goes up: the built-in calibration
 // of nhans_create runs the whole offline path, enhance_clips_body.)  Only what crosses a unit boundary is declared here;
 // everything else stays in its unit's anonymous namespace.
@@ -310,6 +310,7 @@ struct RateIo {
     float wet;
     double factor;
     bool auto_wet = false;      // from_mix: each hop's factor comes from the runs' gain table (GainTab) instead of `wet`
+    bool interleaved = false;   // the PCM side is frames of several channels (Interleave): the kernel's interleaved source / sink
     size_t in_elem() const { return from_mix ? 4 : rs_elem(pcm_format); }
     size_t out_elem() const { return from_mix ? rs_elem(pcm_format) : 4; }
 };
@@ -369,8 +370,16 @@ struct GainTab {
     const int64_t* off;
 };
 
+// The PCM side of a stage (io.interleaved) as frames of `ch` channels: stream i's first sample is element base[i] of the
+// PCM buffer -- its piece's first frame, plus the channel it owns -- and it sums (incoming stage) or writes (outgoing stage)
+// `n` channels from there on in every frame.  The stage's other side stays mono, at its offsets.
+struct Interleave {
+    int ch, n;
+    const int64_t* base;
+};
+
 int stage_push(nhans_ctx* c, RateStage& g, const char* kernel, const RateIo& io, const void* in, const float* mix,
                const int64_t* inoff, const int* end, void* out, const int64_t* outoff, int64_t* counts, hipStream_t s,
-               const GainTab* gains = nullptr);
+               const GainTab* gains = nullptr, const Interleave* il = nullptr);
 
 #pragma GCC visibility pop

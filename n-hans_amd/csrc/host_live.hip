@@ -4,6 +4,9 @@
 // push runs the three stages inside ONE Call on one stream; the stages' own workspace needs (run tables, the online
 // staging) follow each other in the context's workspace, which stream order makes safe, and nothing a later stage reads
 // lives there.
+// An object opened with nhans_interleaved_live_open is the same object whose PCM sides are frames of several channels
+// (include/nhans_hip.h: nhans_interleaved_*): only where a slot's samples sit in the caller's buffers differs, which the
+// two converters' runs carry (Interleave, host_internal.h) -- the same three stages, launches and snapshots.
 #include "host_internal.h"
 
 // The level meter of a live object (nhans_level_live_enable; level.hip): per slot a double-buffered state of kLevelState
@@ -38,6 +41,12 @@ struct nhans_live {
     bool can_rewind = false;
     LevelMeter lv;
     LevelMeter::Slots undo_lv;
+    // nhans_interleaved_live_open: the pushes take frames of Ci channels and return frames of Co, G streams of K slots each
+    // -- K = 1 (downmix: the slot is the mean of the frame's channels) or K = Ci = Co (split: slot g K + c is channel c)
+    struct Frames {
+        bool on = false;
+        int Ci = 1, Co = 1, G = 0, K = 1;
+    } fr;
     double* lv_half(int k, int i) const { return lv.state + ((size_t)k * S + i) * kLevelState; }
 };
 
@@ -143,9 +152,13 @@ int live_level(nhans_live* o, const int64_t* ooff, const int* end, hipStream_t s
     return NHANS_OK;
 }
 
-int live_push_body(nhans_live* o, const void* in, const int64_t* inoff, const int* end, void* out, const int64_t* outoff,
-                   int64_t* counts, hipStream_t s) {
-    if (!inoff || !outoff || !counts) return fail(NHANS_EINVAL, "nhans_live_push: null argument");
+// One push, per slot: inoff / outoff are the slots' counts and room -- and, for a mono object, where their pieces are;
+// il_in / il_out (an interleaved object; both or neither): where they are in the caller's frames instead.
+int live_push_body(nhans_live* o, const char* fn_, const void* in, const int64_t* inoff, const int* end, void* out,
+                   const int64_t* outoff, int64_t* counts, hipStream_t s, const Interleave* il_in = nullptr,
+                   const Interleave* il_out = nullptr) {
+    const std::string fn = fn_;
+    if (!inoff || !outoff || !counts) return fail(NHANS_EINVAL, fn + ": null argument");
     nhans_ctx* c = o->c;
     const int S = o->S;
     std::vector<int64_t> moff(S + 1, 0), ooff(S + 1, 0);
@@ -153,25 +166,25 @@ int live_push_body(nhans_live* o, const void* in, const int64_t* inoff, const in
     for (int i = 0; i < S; ++i) {
         const int64_t cnt = inoff[i + 1] - inoff[i];
         const bool en = end && end[i];
-        const int rc = live_check_push(o, "nhans_live_push", i, cnt, en); if (rc) return rc;
+        const int rc = live_check_push(o, fn_, i, cnt, en); if (rc) return rc;
         const LivePlan p = live_plan(o, i, cnt, en);
         if (outoff[i + 1] - outoff[i] < p.En - p.Eo)
-            return fail(NHANS_EINVAL, "nhans_live_push: output room of slot " + std::to_string(i) + " is " +
+            return fail(NHANS_EINVAL, fn + ": output room of slot " + std::to_string(i) + " is " +
                                       std::to_string(outoff[i + 1] - outoff[i]) + " samples, " +
                                       std::to_string(p.En - p.Eo) + " needed (nhans_live_out_counts)");
         moff[i + 1] = moff[i] + p.n16;
         ooff[i + 1] = ooff[i] + p.d16;
         tin += cnt; tout += p.En - p.Eo;
     }
-    if ((tin > 0 && !in) || (tout > 0 && !out)) return fail(NHANS_EINVAL, "nhans_live_push: null buffer");
+    if ((tin > 0 && !in) || (tout > 0 && !out)) return fail(NHANS_EINVAL, fn + ": null buffer");
     int rc = live_reserve(o, (size_t)moff[S], (size_t)ooff[S]); if (rc) return rc;
 
     // ---- the three stages, the pieces [moff) and [ooff) between them: each commits its host state when its launches
     // went out, and a failure behind it puts it back (an online push undone leaves nothing for nhans_live_rewind) ----
     const RateStage::Streams was_in = o->in.save(), was_out = o->out.save();
     std::vector<int64_t> got(S, 0);
-    rc = stage_push(c, o->in, "live_in", {false, o->in_format, 0, 0.f, o->in_denom}, in, nullptr, inoff, end, o->mid, moff.data(),
-                    got.data(), s);
+    rc = stage_push(c, o->in, "live_in", {false, o->in_format, 0, 0.f, o->in_denom, false, il_in != nullptr}, in, nullptr, inoff, end,
+                    o->mid, moff.data(), got.data(), s, nullptr, il_in);
     if (rc || launch_error_pending()) return rc;          // (a launch error is reported by the entry point; no stage has committed)
     rc = online_push_body(o->on, o->mid, moff.data(), end, o->den, o->mix, ooff.data(), got.data(), s);
     if (rc || launch_error_pending()) { o->in.restore(was_in); return rc; }
@@ -184,8 +197,9 @@ int live_push_body(nhans_live* o, const void* in, const int64_t* inoff, const in
     }
     const bool auto_wet = o->lv.on && o->lv.auto_wet;
     const GainTab gains{o->lv.wtab, woff.data()};
-    rc = stage_push(c, o->out, "live_out", {true, o->out_format, 0, o->wet, o->out_scale, auto_wet}, o->den,
-                    auto_wet || o->wet != 0.f ? o->mix : nullptr, ooff.data(), end, out, outoff, counts, s, auto_wet ? &gains : nullptr);
+    rc = stage_push(c, o->out, "live_out", {true, o->out_format, 0, o->wet, o->out_scale, auto_wet, il_out != nullptr}, o->den,
+                    auto_wet || o->wet != 0.f ? o->mix : nullptr, ooff.data(), end, out, outoff, counts, s, auto_wet ? &gains : nullptr,
+                    il_out);
     if (rc || launch_error_pending()) { o->in.restore(was_in); online_undo(o->on); o->can_rewind = false; return rc; }
     o->undo_in = was_in; o->undo_out = was_out;
     if (o->lv.on) {
@@ -194,6 +208,96 @@ int live_push_body(nhans_live* o, const void* in, const int64_t* inoff, const in
         o->lv.woff = woff;
     }
     o->can_rewind = true;
+    return NHANS_OK;
+}
+
+// ---- interleaved frames (include/nhans_hip.h: nhans_interleaved_*) ----
+int frames_check_object(const nhans_live* o, const char* fn, bool want_frames, const char* other) {
+    if (o->fr.on == want_frames) return NHANS_OK;
+    return fail(NHANS_EINVAL, std::string(fn) + (want_frames ? ": the object takes mono pieces per slot (opened with nhans_live_open_slots): "
+                                                             : ": the object takes interleaved frames per stream (opened with "
+                                                               "nhans_interleaved_live_open): ") + "call " + other);
+}
+
+// What a push of cnt[g] frames (end: and the end) to every stream is per slot: the slots' counts as offsets and their end
+// flags, after the checks that need no plan -- each slot's own (live_check_push) and, for the K > 1 slots of a split
+// stream that the push moves (frames or the end), that they are in step: samples taken, ended flag and look-ahead.
+struct FramePush {
+    std::vector<int64_t> inoff;     // [S + 1]: slot i brings inoff[i + 1] - inoff[i] frames
+    std::vector<int> end;           // [S]
+};
+int frames_slots(const nhans_live* o, const char* fn_, const int64_t* cnt, const int* end, FramePush* fp) {
+    const std::string fn = fn_;
+    const int K = o->fr.K;
+    fp->inoff.assign(o->S + 1, 0);
+    fp->end.assign(o->S, 0);
+    for (int g = 0; g < o->fr.G; ++g) {
+        const bool en = end && end[g];
+        for (int k = 0; k < K; ++k) {
+            const int i = g * K + k, i0 = g * K;
+            const int rc = live_check_push(o, fn_, i, cnt[g], en); if (rc) return rc;
+            if (k > 0 && (cnt[g] > 0 || en)) {
+                const char* what = o->in.st.N[i] != o->in.st.N[i0]           ? "samples taken"
+                                   : o->in.st.ended[i] != o->in.st.ended[i0] ? "ended flag"
+                                   : o->on->la[i] != o->on->la[i0]           ? "look-ahead"
+                                   : o->out.st.N[i] != o->out.st.N[i0]       ? "samples the outgoing stage has taken"
+                                                                             : nullptr;
+                if (what)
+                    return fail(NHANS_EINVAL, fn + ": stream " + std::to_string(g) + ": slot " + std::to_string(i) + " differs from slot " +
+                                              std::to_string(i0) + " in " + what + " (the channels of a split stream move together: " +
+                                              "restart them together, set their look-ahead alike)");
+            }
+            fp->inoff[i + 1] = fp->inoff[i] + cnt[g];
+            fp->end[i] = en;
+        }
+    }
+    return NHANS_OK;
+}
+
+// frames stream g emits: those of its first slot, which its other slots share (frames_slots; a last look here)
+int frames_plan(const nhans_live* o, const char* fn, const FramePush& fp, int g, int64_t* frames) {
+    const int K = o->fr.K;
+    for (int k = 0; k < K; ++k) {
+        const int i = g * K + k;
+        const LivePlan p = live_plan(o, i, fp.inoff[i + 1] - fp.inoff[i], fp.end[i] != 0);
+        if (k == 0) *frames = p.En - p.Eo;
+        else if (p.En - p.Eo != *frames)
+            return fail(NHANS_EINVAL, std::string(fn) + ": stream " + std::to_string(g) + ": slot " + std::to_string(i) +
+                                      " differs from slot " + std::to_string(g * K) + " in the frames it would emit");
+    }
+    return NHANS_OK;
+}
+
+int frames_push_body(nhans_live* o, const void* in, const int64_t* inoff, const int* end, void* out, const int64_t* outoff,
+                     int64_t* counts, hipStream_t s) {
+    const char* fn = "nhans_interleaved_live_push";
+    int rc = frames_check_object(o, fn, true, "nhans_live_push"); if (rc) return rc;
+    if (!inoff || !outoff || !counts) return fail(NHANS_EINVAL, std::string(fn) + ": null argument");
+    const int G = o->fr.G, K = o->fr.K, S = o->S;
+    std::vector<int64_t> cnt(G);
+    for (int g = 0; g < G; ++g) cnt[g] = inoff[g + 1] - inoff[g];
+    FramePush fp;
+    rc = frames_slots(o, fn, cnt.data(), end, &fp); if (rc) return rc;
+    // per slot: its room is what it needs (the stream's room is checked here, in frames), and where its first sample is
+    std::vector<int64_t> room(S + 1, 0), base_in(S), base_out(S), got(S, 0);
+    for (int g = 0; g < G; ++g) {
+        int64_t frames = 0;
+        rc = frames_plan(o, fn, fp, g, &frames); if (rc) return rc;
+        if (outoff[g + 1] - outoff[g] < frames)
+            return fail(NHANS_EINVAL, std::string(fn) + ": output room of stream " + std::to_string(g) + " is " +
+                                      std::to_string(outoff[g + 1] - outoff[g]) + " frames, " + std::to_string(frames) +
+                                      " needed (nhans_interleaved_live_out_counts)");
+        for (int k = 0; k < K; ++k) {
+            const int i = g * K + k;
+            room[i + 1] = room[i] + frames;
+            base_in[i] = inoff[g] * o->fr.Ci + k;       // (K == 1: the frame's first channel, from which all Ci are summed)
+            base_out[i] = outoff[g] * o->fr.Co + k;
+        }
+    }
+    const Interleave il_in{o->fr.Ci, K > 1 ? 1 : o->fr.Ci, base_in.data()}, il_out{o->fr.Co, K > 1 ? 1 : o->fr.Co, base_out.data()};
+    rc = live_push_body(o, fn, in, fp.inoff.data(), fp.end.data(), out, room.data(), got.data(), s, &il_in, &il_out);
+    if (rc || launch_error_pending()) return rc;
+    for (int g = 0; g < G; ++g) counts[g] = got[g * K];
     return NHANS_OK;
 }
 
@@ -241,32 +345,68 @@ int nhans_lookahead_live_set(nhans_live* o, int slot, int lookahead) {
     return NHANS_OK;
 }
 
+namespace {
+// the checks and the object of both open functions: `count` slots (mono) or streams of `per` slots each (interleaved)
+int live_open_body(const char* fn_, const char* noun, nhans_ctx* c, int count, int per, int rate_in, int in_format, double peak,
+                   int rate_out, int out_format, double out_scale, int flags, hipStream_t s, nhans_live** out) {
+    const std::string fn = fn_;
+    if (count < 1 || count > std::numeric_limits<int>::max() / per) return fail(NHANS_EINVAL, fn + ": " + noun + " must be >= 1");
+    for (int fmt : {in_format, out_format})
+        if (fmt != kResampleInt16 && fmt != kResampleFloat32)
+            return fail(NHANS_EINVAL, fn + ": in_format and out_format must be NHANS_PCM_INT16 or NHANS_PCM_FLOAT32");
+    if (!(peak >= 0.0) || !std::isfinite(peak)) return fail(NHANS_EINVAL, fn + ": the peak must be finite and >= 0");
+    if (!(out_scale > 0.0) || !std::isfinite(out_scale)) return fail(NHANS_EINVAL, fn + ": out_scale must be finite and > 0");
+    if (flags & ~NHANS_LIVE_WET) return fail(NHANS_EINVAL, fn + ": unknown flag");
+    const ResampleFilter *fi = nullptr, *fo = nullptr;
+    int rc = live_filters(fn_, rate_in, rate_out, &fi, &fo); if (rc) return rc;
+    const int nslots = count * per;
+    nhans_live* o = new nhans_live();
+    o->c = c; o->device = c->device; o->S = nslots; o->in_format = in_format; o->out_format = out_format;
+    o->has_wet = (flags & NHANS_LIVE_WET) != 0;
+    o->in_denom = peak + 0.000001; o->out_scale = out_scale;
+    rc = o->in.alloc(c, fn_, fi, nslots);
+    if (!rc) rc = o->out.alloc(c, fn_, fo, nslots);
+    if (!rc) rc = online_open_slots_body(c, nslots, o->has_wet, s, &o->on);
+    if (rc) { live_free(o); return rc; }
+    *out = o;
+    return NHANS_OK;
+}
+}  // namespace
+
 int nhans_live_open_slots(nhans_ctx* c, int nslots, int rate_in, int in_format, double peak, int rate_out, int out_format,
                           double out_scale, int flags, void* stream, nhans_live** out) {
     if (!out) return fail(NHANS_EINVAL, "nhans_live_open_slots: null argument");
     *out = nullptr;
     Call call(c, stream);
     if (call.rc) return call.rc;
-    if (nslots < 1) return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: nslots must be >= 1"));
-    for (int fmt : {in_format, out_format})
-        if (fmt != kResampleInt16 && fmt != kResampleFloat32)
-            return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: in_format and out_format must be NHANS_PCM_INT16 or NHANS_PCM_FLOAT32"));
-    if (!(peak >= 0.0) || !std::isfinite(peak))
-        return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: the peak must be finite and >= 0"));
-    if (!(out_scale > 0.0) || !std::isfinite(out_scale))
-        return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: out_scale must be finite and > 0"));
-    if (flags & ~NHANS_LIVE_WET) return call.finish(fail(NHANS_EINVAL, "nhans_live_open_slots: unknown flag"));
-    const ResampleFilter *fi = nullptr, *fo = nullptr;
-    int rc = live_filters("nhans_live_open_slots", rate_in, rate_out, &fi, &fo); if (rc) return call.finish(rc);
-    nhans_live* o = new nhans_live();
-    o->c = c; o->device = c->device; o->S = nslots; o->in_format = in_format; o->out_format = out_format;
-    o->has_wet = (flags & NHANS_LIVE_WET) != 0;
-    o->in_denom = peak + 0.000001; o->out_scale = out_scale;
-    rc = o->in.alloc(c, "nhans_live_open_slots", fi, nslots);
-    if (!rc) rc = o->out.alloc(c, "nhans_live_open_slots", fo, nslots);
-    if (!rc) rc = online_open_slots_body(c, nslots, o->has_wet, call.s, &o->on);
-    if (rc) { live_free(o); return call.finish(rc); }
-    *out = o;
+    return call.finish(live_open_body("nhans_live_open_slots", "nslots", c, nslots, 1, rate_in, in_format, peak, rate_out, out_format,
+                                      out_scale, flags, call.s, out));
+}
+
+int nhans_interleaved_live_open(nhans_ctx* c, int nstreams, int channels_in, int channels_out, int mode, int rate_in, int in_format,
+                                double peak, int rate_out, int out_format, double out_scale, int flags, void* stream,
+                                nhans_live** out) {
+    const std::string fn = "nhans_interleaved_live_open";
+    if (!out) return fail(NHANS_EINVAL, fn + ": null argument");
+    *out = nullptr;
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    for (int ch : {channels_in, channels_out})
+        if (ch < 1 || ch > NHANS_INTERLEAVED_MAX_CHANNELS)
+            return call.finish(fail(NHANS_EINVAL, fn + ": channels_in and channels_out must be in 1 ... " +
+                                                  std::to_string(NHANS_INTERLEAVED_MAX_CHANNELS) + " (got " + std::to_string(channels_in) +
+                                                  " and " + std::to_string(channels_out) + ")"));
+    if (mode != NHANS_INTERLEAVED_DOWNMIX && mode != NHANS_INTERLEAVED_SPLIT)
+        return call.finish(fail(NHANS_EINVAL, fn + ": mode must be NHANS_INTERLEAVED_DOWNMIX or NHANS_INTERLEAVED_SPLIT"));
+    if (mode == NHANS_INTERLEAVED_SPLIT && channels_in != channels_out)
+        return call.finish(fail(NHANS_EINVAL, fn + ": NHANS_INTERLEAVED_SPLIT needs channels_in == channels_out (got " +
+                                              std::to_string(channels_in) + " and " + std::to_string(channels_out) + ")"));
+    const int K = mode == NHANS_INTERLEAVED_SPLIT ? channels_in : 1;
+    const int rc = live_open_body("nhans_interleaved_live_open", "nstreams", c, nstreams, K, rate_in, in_format, peak, rate_out,
+                                  out_format, out_scale, flags, call.s, out);
+    if (rc) return call.finish(rc);
+    (*out)->fr.on = true;
+    (*out)->fr.Ci = channels_in; (*out)->fr.Co = channels_out; (*out)->fr.G = nstreams; (*out)->fr.K = K;
     return call.finish(NHANS_OK);
 }
 
@@ -316,6 +456,7 @@ int nhans_live_set_wet(nhans_live* o, double wet) {
 
 int nhans_live_out_counts(const nhans_live* o, const int64_t* in_counts, const int* end, int64_t* counts) {
     if (!o || !in_counts || !counts) return fail(NHANS_EINVAL, "nhans_live_out_counts: null argument");
+    if (o->fr.on) return frames_check_object(o, "nhans_live_out_counts", false, "nhans_interleaved_live_out_counts");
     for (int i = 0; i < o->S; ++i) {
         const int rc = live_check_push(o, "nhans_live_out_counts", i, in_counts[i], end && end[i]); if (rc) return rc;
     }
@@ -328,8 +469,30 @@ int nhans_live_out_counts(const nhans_live* o, const int64_t* in_counts, const i
 
 int nhans_live_push(nhans_live* o, const void* in, const int64_t* inoff, const int* end, void* out, const int64_t* outoff,
                     int64_t* counts, void* stream) {
-    return object_call(o, "nhans_live_push: null object", stream,
-                       [&](hipStream_t s) { return live_push_body(o, in, inoff, end, out, outoff, counts, s); });
+    return object_call(o, "nhans_live_push: null object", stream, [&](hipStream_t s) {
+        if (o->fr.on) return frames_check_object(o, "nhans_live_push", false, "nhans_interleaved_live_push");
+        return live_push_body(o, "nhans_live_push", in, inoff, end, out, outoff, counts, s);
+    });
+}
+
+int nhans_interleaved_live_out_counts(const nhans_live* o, const int64_t* in_frames, const int* end, int64_t* out_frames) {
+    const char* fn = "nhans_interleaved_live_out_counts";
+    if (!o || !in_frames || !out_frames) return fail(NHANS_EINVAL, std::string(fn) + ": null argument");
+    int rc = frames_check_object(o, fn, true, "nhans_live_out_counts"); if (rc) return rc;
+    FramePush fp;
+    rc = frames_slots(o, fn, in_frames, end, &fp); if (rc) return rc;
+    std::vector<int64_t> frames(o->fr.G, 0);
+    for (int g = 0; g < o->fr.G; ++g) {
+        rc = frames_plan(o, fn, fp, g, &frames[g]); if (rc) return rc;
+    }
+    std::copy(frames.begin(), frames.end(), out_frames);
+    return NHANS_OK;
+}
+
+int nhans_interleaved_live_push(nhans_live* o, const void* in, const int64_t* inoff, const int* end, void* out, const int64_t* outoff,
+                                int64_t* counts, void* stream) {
+    return object_call(o, "nhans_interleaved_live_push: null object", stream,
+                       [&](hipStream_t s) { return frames_push_body(o, in, inoff, end, out, outoff, counts, s); });
 }
 
 int nhans_live_rewind(nhans_live* o) {

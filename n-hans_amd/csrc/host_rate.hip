@@ -13,15 +13,15 @@ int rs_filter(const char* fn, int rate_in, int rate_out, const ResampleFilter** 
 }
 
 int rs_launch(nhans_ctx* c, const char* name, const std::vector<ResampleRun>& runs, const float* tab, const ResampleFilter& f,
-              const RateIo& io, size_t lds, double in_bytes, int64_t out_samples, hipStream_t s) {
+              const RateIo& io, size_t lds, double in_bytes, double out_bytes, int64_t out_samples, hipStream_t s) {
     if (runs.empty()) return NHANS_OK;
     int rc = ws_reserve(c, ws_size(runs.size(), sizeof(ResampleRun))); if (rc) return rc;
     ResampleRun* runs_dev = ws_take<ResampleRun>(c, runs.size());
     rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(ResampleRun), s); if (rc) return rc;
     Prof pr(c, s, name);
-    launch_resample(name, runs_dev, (int)runs.size(), tab, f, io.from_mix, io.auto_wet, io.pcm_format, io.quantise, io.wet, io.factor, lds,
-                    s);
-    pr.done(2.0 * f.J * (double)out_samples, in_bytes + (double)io.out_elem() * out_samples + 4.0 * runs.size() * f.tab.size());
+    launch_resample(name, runs_dev, (int)runs.size(), tab, f, io.from_mix, io.auto_wet, io.interleaved, io.pcm_format, io.quantise,
+                    io.wet, io.factor, lds, s);
+    pr.done(2.0 * f.J * (double)out_samples, in_bytes + out_bytes + 4.0 * runs.size() * f.tab.size());
     return NHANS_OK;
 }
 
@@ -62,27 +62,38 @@ void rs_add_runs(std::vector<ResampleRun>& runs, size_t* lds, const ResampleFilt
 // One push through a stage, its arguments checked by the caller: the runs of every stream (stream i brings the samples
 // [inoff[i], inoff[i + 1]) of `in` -- and of `mix`, where the kernel reads the mix --), ONE launch under `kernel`, then the
 // commit.  Where the launch did not go out (a return code, or launch_error_pending()) nothing is committed.  gains
-// (io.auto_wet): the table the runs of each stream read their hops' factors from.
+// (io.auto_wet): the table the runs of each stream read their hops' factors from.  il (io.interleaved): where stream i
+// sits in the frames of the PCM side -- the counts stay those of inoff, and on that side the offsets are il's, in frames
+// of il->ch elements, the run builder's step from one run's outputs to the next being one frame per output.
 int stage_push(nhans_ctx* c, RateStage& g, const char* kernel, const RateIo& io, const void* in, const float* mix,
                const int64_t* inoff, const int* end, void* out, const int64_t* outoff, int64_t* counts, hipStream_t s,
-               const GainTab* gains) {
+               const GainTab* gains, const Interleave* il) {
     std::vector<ResampleRun> runs;
     std::vector<RateStage::Span> e(g.S);
     size_t lds = 0;
     int64_t tin = 0, tout = 0;
+    const Interleave* il_src = io.from_mix ? nullptr : il;
+    const Interleave* il_dst = io.from_mix ? il : nullptr;
+    const size_t out_step = io.out_elem() * (il_dst ? il_dst->ch : 1);
     for (int i = 0; i < g.S; ++i) {
         const int64_t cnt = inoff[i + 1] - inoff[i];
         e[i] = g.plan(i, cnt, end && end[i]);
         const size_t first = runs.size();
-        g.add_runs(runs, &lds, i, static_cast<const char*>(in) + inoff[i] * io.in_elem(), mix ? mix + inoff[i] : nullptr,
-                   out ? static_cast<char*>(out) + outoff[i] * io.out_elem() : nullptr, io.out_elem(), cnt, e[i]);
+        g.add_runs(runs, &lds, i, static_cast<const char*>(in) + (il_src ? il_src->base[i] : inoff[i]) * io.in_elem(),
+                   mix ? mix + inoff[i] : nullptr,
+                   out ? static_cast<char*>(out) + (il_dst ? il_dst->base[i] : outoff[i]) * io.out_elem() : nullptr, out_step, cnt, e[i]);
         for (size_t k = first; gains && k < runs.size(); ++k) {
             runs[k].wtab = gains->w + gains->off[i];
             runs[k].hop0 = g.st.N[i] / kHop;
         }
+        for (size_t k = first; il && k < runs.size(); ++k) {
+            if (il_src) { runs[k].src_ch = il->ch; runs[k].src_sum = il->n; }
+            else { runs[k].dst_ch = il->ch; runs[k].dst_copies = il->n; }
+        }
         tin += cnt; tout += e[i].En - e[i].Eo;
     }
-    const int rc = rs_launch(c, kernel, runs, g.tab, *g.f, io, lds, (double)tin * (io.in_elem() + (mix ? 4 : 0)), tout, s);
+    const int rc = rs_launch(c, kernel, runs, g.tab, *g.f, io, lds, (double)tin * (io.in_elem() * (il_src ? il_src->n : 1) + (mix ? 4 : 0)),
+                             (double)tout * io.out_elem() * (il_dst ? il_dst->n : 1), tout, s);
     if (rc) return rc;
     if (launch_error_pending()) return NHANS_OK;
     for (int i = 0; i < g.S; ++i) {
@@ -133,7 +144,7 @@ int resample_body(nhans_ctx* c, const void* in, int fmt, const int64_t* inoff, i
     const float* tab = nullptr;
     rc = rs_table(c, f, &tab); if (rc) return rc;
     return rs_launch(c, "resample", runs, tab, *f, {false, fmt, flags & NHANS_RESAMPLE_QUANTISE, 0.f, 0.0}, lds,
-                     (double)tin * rs_elem(fmt), tout, s);
+                     (double)tin * rs_elem(fmt), 4.0 * (double)tout, tout, s);
 }
 
 int peak_normalise_body(nhans_ctx* c, const float* in, const int64_t* off, int nclips, int flags, float* out, hipStream_t s) {

@@ -334,6 +334,12 @@ struct ResampleRun {
     // that of hop `hop0` of the stream -- sample k0 + rel takes wtab[(k0 + rel) / 160 - hop0] where the fixed mix takes wet
     const float* wtab;
     long long hop0;
+    // the interleaved PCM source and sink only (live objects that take and return frames of several channels), left zero
+    // by the run builder: src holds frames of src_ch channels and sample k0 + rel is the mean of the first src_sum of
+    // frame rel, summed in double, channel ascending (1: that channel itself); dst holds frames of dst_ch channels and
+    // output i is stored into the first dst_copies of frame i.  A slot that owns channel c of its frames has src / dst
+    // point at that channel of the first frame.
+    int src_ch, src_sum, dst_ch, dst_copies;
 };
 constexpr int kResampleRun = 1024;      // outputs per workgroup at most
 constexpr int kResampleInt16 = 0, kResampleFloat32 = 1;
@@ -342,9 +348,11 @@ size_t resample_run_lds_bytes(const ResampleFilter& f, int p0, int cnt);
 // when factor != 0 (the fixed-peak normalisation of a live stream).  from_mix true: the wet/dry mix -> PCM of pcm_format,
 // float32(double(y) * factor) before the rounding.  A run table that needs more than 64 KB of LDS is refused.
 // auto_wet (from_mix only): the wet factor of a sample is its hop's entry of the run's gain table, not `wet`.
+// interleaved: the PCM side -- the source from PCM, the sink from the mix -- is frames of several channels, laid out by the
+// runs' src_ch / src_sum or dst_ch / dst_copies.
 void launch_resample(const char* kernel, const ResampleRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
-                     bool from_mix, bool auto_wet, int pcm_format, int quantise, float wet, double factor, size_t lds_bytes,
-                     hipStream_t s);
+                     bool from_mix, bool auto_wet, bool interleaved, int pcm_format, int quantise, float wet, double factor,
+                     size_t lds_bytes, hipStream_t s);
 
 // peak + normalise: blocks of <= kNormBlock samples; block b belongs to a clip whose blocks are [pb0, pb0 + pbn)
 struct NormBlock {

@@ -11,8 +11,9 @@
 // a push only changes where an input sample is fetched from (the caller's new samples or the J carried ones), never the
 // arithmetic on it.  The body is a template over a source (PCM int16 / float32, or the wet/dry mix of a live session
 // formed while the span is staged) and a sink (float32 with the optional int16 grid and fixed peak, or scaled PCM);
-// the six pairs in use are instantiated: int16 -> float, float32 -> float, and the fixed and the automatic mix -> int16 and
-// -> float32.
+// the six mono pairs in use are instantiated: int16 -> float, float32 -> float, and the fixed and the automatic mix ->
+// int16 and -> float32 -- and, for live objects that take and return interleaved frames, the same six with the PCM side
+// read from / stored into frames of several channels (InterleavedSource, InterleavedSink).
 #include "nhans_kernels.h"
 
 #include <cmath>
@@ -130,6 +131,21 @@ struct PcmSource {
         return (float)static_cast<const T*>(r.src)[rel];
     }
 };
+// PCM frames of r.src_ch channels at src, the sample being the mean of the first r.src_sum channels of its frame as
+// channel_mean_kernel forms it: summed in double from 0.0, channel ascending, divided by double(r.src_sum), rounded to
+// float32 once.  Summing ONE channel gives that channel's sample itself (0.0 + double(s)) / 1.0 -- exact for int16 and
+// float32; -0.0f comes out as 0.0f, which no fmaf chain that starts at 0.0f can tell apart --, so a slot that owns one
+// channel of a frame and a slot that is the frame's downmix are one policy.  The span that is staged, and therefore LDS,
+// the lane -> output map and the carried samples, are those of a mono stream: after this function the stream is mono.
+template <typename T>
+struct InterleavedSource {
+    static __device__ __forceinline__ float at(const ResampleRun& r, long long rel, float) {
+        const T* f = static_cast<const T*>(r.src) + rel * r.src_ch;
+        double acc = 0.0;
+        for (int c = 0; c < r.src_sum; ++c) acc += (double)f[c];
+        return (float)(acc / (double)r.src_sum);
+    }
+};
 // d + (m - d) * w in three separately rounded float32 operations (numpy's `den + (mix - den) * factor`).  The pragma is
 // what keeps them apart: the _rn intrinsics are plain operators compiled under the translation unit's contraction mode,
 // and the compiler fuses their product into the sum -- one rounding instead of two, a last-bit difference for every
@@ -162,20 +178,36 @@ struct AutoMixSource {
 // Sink policies: what becomes of output i of the run, y = its chain.
 // float32, optionally rounded to the int16 grid, then float32(double(v) / factor) when factor != 0 (the fixed peak):
 struct FloatSink {
-    static __device__ __forceinline__ void put(void* dst, int i, float v, int quantise, double factor) {
+    static __device__ __forceinline__ void put(const ResampleRun& r, int i, float v, int quantise, double factor) {
         if (quantise) v = fminf(fmaxf(rintf(v), -32768.f), 32767.f);
         if (factor != 0.0) v = (float)((double)v / factor);
-        static_cast<float*>(dst)[i] = v;
+        static_cast<float*>(r.dst)[i] = v;
     }
 };
 // PCM: float32(double(y) * factor), then rounded and clamped for int16.  The int16 stores are plain 2-byte stores: a
 // slot's destination is only 2-byte aligned, and the 64 lanes of a wave write 128 consecutive bytes.
 template <typename T>
 struct PcmSink {
-    static __device__ __forceinline__ void put(void* dst, int i, float y, int, double factor) {
+    static __device__ __forceinline__ void put(const ResampleRun& r, int i, float y, int, double factor) {
         const float v = (float)((double)y * factor);
-        if constexpr (sizeof(T) == 2) static_cast<int16_t*>(dst)[i] = (int16_t)fminf(fmaxf(rintf(v), -32768.f), 32767.f);
-        else static_cast<float*>(dst)[i] = v;
+        if constexpr (sizeof(T) == 2) static_cast<int16_t*>(r.dst)[i] = (int16_t)fminf(fmaxf(rintf(v), -32768.f), 32767.f);
+        else static_cast<float*>(r.dst)[i] = v;
+    }
+};
+// The same value into frames of r.dst_ch channels: output i goes to the first r.dst_copies channels of frame i at dst (a
+// slot that owns one channel writes 1, a downmix played on every channel writes them all).  Still plain 2-byte stores
+// for int16: the lanes of a wave now write 2 bytes every 2 * dst_ch, and the copies of one lane are neighbours.
+template <typename T>
+struct InterleavedSink {
+    static __device__ __forceinline__ void put(const ResampleRun& r, int i, float y, int, double factor) {
+        const float v = (float)((double)y * factor);
+        const int at = i * r.dst_ch;
+        if constexpr (sizeof(T) == 2) {
+            const int16_t q = (int16_t)fminf(fmaxf(rintf(v), -32768.f), 32767.f);
+            for (int c = 0; c < r.dst_copies; ++c) static_cast<int16_t*>(r.dst)[at + c] = q;
+        } else {
+            for (int c = 0; c < r.dst_copies; ++c) static_cast<float*>(r.dst)[at + c] = v;
+        }
     }
 };
 
@@ -213,7 +245,7 @@ __global__ void __launch_bounds__(256) resample_kernel(const ResampleRun* __rest
     for (int i = tid; i < r.cnt; i += 256) {
         const int t = r.p0 + i * M;
         const int q = t / L, p = t - q * L;
-        Sink::put(r.dst, i, fir_chain(tl + p, L, xs + (J - 1) + q, J), quantise, factor);
+        Sink::put(r, i, fir_chain(tl + p, L, xs + (J - 1) + q, J), quantise, factor);
     }
     if (r.hist_out)
         for (int t = tid; t < J; t += 256) r.hist_out[t] = run_sample<Src>(r, (long long)r.n_new - J + t, J, wet);
@@ -268,15 +300,21 @@ void launch_channel_mean(const float* in, int nchan, int64_t n, float* out, hipS
 }
 
 void launch_resample(const char* kernel, const ResampleRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
-                     bool from_mix, bool auto_wet, int pcm_format, int quantise, float wet, double factor, size_t lds_bytes,
-                     hipStream_t s) {
+                     bool from_mix, bool auto_wet, bool interleaved, int pcm_format, int quantise, float wet, double factor,
+                     size_t lds_bytes, hipStream_t s) {
     if (nruns <= 0) return;
     if (lds_bytes > (size_t)64 << 10) { note_refusal(kernel); return; }
     const int tab4 = (int)(f.tab.size() / 4);
     const bool i16 = pcm_format == kResampleInt16;
-    auto* fn = !from_mix ? (i16 ? resample_kernel<PcmSource<int16_t>, FloatSink> : resample_kernel<PcmSource<float>, FloatSink>)
-               : !auto_wet ? (i16 ? resample_kernel<MixSource, PcmSink<int16_t>> : resample_kernel<MixSource, PcmSink<float>>)
-                           : (i16 ? resample_kernel<AutoMixSource, PcmSink<int16_t>> : resample_kernel<AutoMixSource, PcmSink<float>>);
+    auto* mono = !from_mix ? (i16 ? resample_kernel<PcmSource<int16_t>, FloatSink> : resample_kernel<PcmSource<float>, FloatSink>)
+                 : !auto_wet ? (i16 ? resample_kernel<MixSource, PcmSink<int16_t>> : resample_kernel<MixSource, PcmSink<float>>)
+                             : (i16 ? resample_kernel<AutoMixSource, PcmSink<int16_t>> : resample_kernel<AutoMixSource, PcmSink<float>>);
+    auto* fn = mono;
+    if (interleaved)
+        fn = !from_mix ? (i16 ? resample_kernel<InterleavedSource<int16_t>, FloatSink> : resample_kernel<InterleavedSource<float>, FloatSink>)
+             : !auto_wet ? (i16 ? resample_kernel<MixSource, InterleavedSink<int16_t>> : resample_kernel<MixSource, InterleavedSink<float>>)
+                         : (i16 ? resample_kernel<AutoMixSource, InterleavedSink<int16_t>>
+                                : resample_kernel<AutoMixSource, InterleavedSink<float>>);
     NHANS_LAUNCH(kernel, fn, dim3(nruns), dim3(256), lds_bytes, s, runs_dev, tab_dev, f.L, f.M, f.J, tab4, quantise, wet, factor);
 }
 

@@ -99,6 +99,10 @@ SIGNATURES = {
     "nhans_level_live_read": (_int, [_vp, _int, _dp, _vp]),
     "nhans_level_live_gains": (_i64, [_vp, _int, _fp, _i64, _vp]),
     "nhans_level_gains": (_int, [_vp, _vp, _vp, _i64p, _int, _int, _dbl, _vp, _vp, _vp]),
+    # live sessions on interleaved frames
+    "nhans_interleaved_live_open": (_int, [_vp, _int, _int, _int, _int, _int, _int, _dbl, _int, _int, _dbl, _int, _vp, _vpp]),
+    "nhans_interleaved_live_out_counts": (_int, [_vp, _i64p, _ip, _i64p]),
+    "nhans_interleaved_live_push": (_int, [_vp, _vp, _i64p, _ip, _vp, _i64p, _i64p, _vp]),
     "nhans_profile_json": (_int, [_vp, _str, _size]),
     "nhans_profile_reset": (_int, [_vp]),
 }
@@ -112,6 +116,8 @@ CAPTURE_A, CAPTURE_B = 0, 1
 CAPTURE_NORMALISE = 1
 ESHORT = -4
 LEVEL_MAX_WINDOW = 256
+INTERLEAVED_DOWNMIX, INTERLEAVED_SPLIT = 0, 1
+INTERLEAVED_MAX_CHANNELS = 8
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25
 ABI_VERSION = 5

@@ -66,6 +66,25 @@ def level_gains(engine, den, mix, window_hops=200, wmax=1.0, sums=False):
     return (gains, s) if sums else gains
 
 
+def downmix(frames):
+    """The sample a downmix session forms from each interleaved frame (include/nhans_hip.h, NHANS_INTERLEAVED_DOWNMIX):
+    frames [n, C] (or [n]: one channel) -> float32 [n], float32((sum_c float64(frames[k, c])) / float64(C)) with the sum
+    starting at 0.0 and adding c in ascending order -- an explicit loop: the order of numpy's own reductions is numpy's
+    choice.  One channel comes back as it is."""
+    x = np.asarray(frames)
+    if x.ndim == 1:
+        x = x[:, None]
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise ValueError("downmix: frames [n, C] with C >= 1")
+    acc = np.zeros(x.shape[0], dtype=np.float64)
+    for c in range(x.shape[1]):
+        acc = acc + x[:, c].astype(np.float64)
+    return (acc / np.float64(x.shape[1])).astype(np.float32)
+
+
+CHANNEL_MODES = {"downmix": hip.INTERLEAVED_DOWNMIX, "split": hip.INTERLEAVED_SPLIT}
+
+
 def default_out_scale(peak, out_dtype):
     """peak + 1e-6 for int16 output -- the inverse of the incoming normalisation, so that an untouched signal comes back
     on the scale it arrived on --, 1.0 for float32."""
@@ -85,7 +104,15 @@ class LiveSession(online.Slots):
     has no samples yet): the 16 kHz stage then computes the offline output of that L, Engine.enhance(..., lookahead=L).
 
     capture_contexts: the samples are what the incoming converter handed on (already divided by peak + 1e-6),
-    resample.emitted(pushed, ended, in_rate, 16000) of them so far."""
+    resample.emitted(pushed, ended, in_rate, 16000) of them so far.
+
+    channels / out_channels (1 .. 8; out_channels None: as channels) other than 1: nslots counts STREAMS of interleaved
+    frames (nhans_interleaved_*) -- push takes one [frames, channels] array per stream and returns [frames, out_channels]
+    arrays.  channel_mode "downmix": one slot per stream, fed downmix(frames), its output copied to every output
+    channel.  "split" (channels == out_channels): one slot per channel, slots_of(stream), each enhanced on its own; the
+    per-slot calls (set_context, restart, set_lookahead, capture_context, levels, ...) take those slot indices, and the
+    slots of a stream have to be restarted and given their look-ahead together.  Gains are per slot: set_auto_wet may
+    move the channels of a stream differently."""
 
     C = dict(restart="nhans_live_restart", rewind="nhans_live_rewind", out_counts="nhans_live_out_counts",
              set_context="nhans_live_set_context", set_embeddings="nhans_live_set_embeddings",
@@ -94,9 +121,16 @@ class LiveSession(online.Slots):
              close="nhans_live_close")
 
     def __init__(self, engine, nslots, in_rate, out_rate, peak, in_dtype=np.int16, out_dtype=np.int16, out_scale=None,
-                 wet=False, lookahead=online.LOOKAHEAD):
+                 wet=False, lookahead=online.LOOKAHEAD, channels=1, out_channels=None, channel_mode="downmix"):
         emitted(0, False, in_rate, out_rate)
-        self._begin(engine, nslots, False)
+        self.channels = int(channels)
+        self.out_channels = self.channels if out_channels is None else int(out_channels)
+        self.interleaved = (self.channels, self.out_channels) != (1, 1)
+        if channel_mode not in CHANNEL_MODES:
+            raise ValueError("channel_mode: 'downmix' or 'split' (got %r)" % (channel_mode,))
+        self.split = self.interleaved and channel_mode == "split"
+        self.nstreams = int(nslots)
+        self._begin(engine, self.nstreams * (self.channels if self.split else 1), False)
         self.in_rate, self.out_rate = int(in_rate), int(out_rate)
         self.in_dtype, self.out_dtype = np.dtype(in_dtype), np.dtype(out_dtype)
         self.peak = float(peak)
@@ -104,11 +138,35 @@ class LiveSession(online.Slots):
         self.has_wet = bool(wet)
         self._level_window = 0          # (the meter's window: cumulative until set_auto_wet names one)
         h = ctypes.c_void_p()
-        hip.check(self.lib.nhans_live_open_slots(engine.handle, self.S, self.in_rate, resample._format(self.in_dtype),
-                                                 self.peak, self.out_rate, resample._format(self.out_dtype), self.out_scale,
-                                                 hip.LIVE_WET if self.has_wet else 0, self.mem.stream(), ctypes.byref(h)))
+        tail = (self.in_rate, resample._format(self.in_dtype), self.peak, self.out_rate, resample._format(self.out_dtype),
+                self.out_scale, hip.LIVE_WET if self.has_wet else 0, self.mem.stream(), ctypes.byref(h))
+        if self.interleaved:
+            hip.check(self.lib.nhans_interleaved_live_open(engine.handle, self.nstreams, self.channels, self.out_channels,
+                                                           CHANNEL_MODES[channel_mode], *tail))
+        else:
+            hip.check(self.lib.nhans_live_open_slots(engine.handle, self.S, *tail))
         self.handle = h
         self._lookaheads(lookahead)
+
+    def slots_of(self, stream):
+        """The slot indices of `stream` for the per-slot calls: one slot, or in split mode one per channel, in channel
+        order."""
+        if not 0 <= int(stream) < self.nstreams:
+            raise ValueError("slots_of: stream %r out of range (0 ... %d)" % (stream, self.nstreams - 1))
+        k = self.S // self.nstreams
+        return list(range(int(stream) * k, int(stream) * k + k))
+
+    def out_counts(self, counts, end=None):
+        """What a push of counts[i] samples would emit per slot -- with interleaved frames: of counts[g] frames per
+        stream, in frames."""
+        if not self.interleaved:
+            return super().out_counts(counts, end)
+        if len(counts) != self.nstreams:
+            raise ValueError("out_counts: one count per stream (%d)" % self.nstreams)
+        out = (ctypes.c_int64 * self.nstreams)()
+        hip.check(self.lib.nhans_interleaved_live_out_counts(self.handle, hip.i64_array(counts),
+                                                             context.end_flags(end, self.nstreams), out))
+        return list(out)
 
     def set_wet(self, w):
         """The wet factor of the pushes that follow (non-zero needs wet=True at construction)."""
@@ -154,19 +212,53 @@ class LiveSession(online.Slots):
 
     # ---- pushes --------------------------------------------------------------------------------
     def _push(self, pin, ioff, end, dout, ooff, outc):
-        """One nhans_live_push of the pieces at device pointer pin into the device buffer dout."""
+        """One nhans_live_push of the pieces at device pointer pin into the device buffer dout -- with interleaved
+        frames, one nhans_interleaved_live_push: offsets and counts per stream, in frames."""
+        n = self.nstreams
+        entry = self.lib.nhans_interleaved_live_push if self.interleaved else self.lib.nhans_live_push
+
         def push():
-            got = (ctypes.c_int64 * self.S)()
-            hip.check(self.lib.nhans_live_push(self.handle, pin, hip.i64_array(ioff), context.end_flags(end, self.S),
-                                               self.mem.p(dout), hip.i64_array(ooff), got, self.mem.stream()))
+            got = (ctypes.c_int64 * n)()
+            hip.check(entry(self.handle, pin, hip.i64_array(ioff), context.end_flags(end, n), self.mem.p(dout),
+                            hip.i64_array(ooff), got, self.mem.stream()))
             return list(got)
 
-        self._push_checked(push, [ioff[i + 1] - ioff[i] for i in range(self.S)], end, outc)
+        # (the host's view is per slot: the slots of a split stream each take the stream's frames and its end)
+        k = self.S // n
+        counts = [ioff[i // k + 1] - ioff[i // k] for i in range(self.S)]
+        self._push_checked(push, counts, end if end is None or k == 1 else [end[i // k] for i in range(self.S)], outc)
+
+    def _push_frames(self, chunks, end):
+        if len(chunks) != self.nstreams:
+            raise ValueError("push: one [frames, %d] array per stream (%d)" % (self.channels, self.nstreams))
+        arrs = []
+        for c in chunks:
+            a = np.asarray(c, dtype=self.in_dtype)
+            if a.ndim == 1 and (self.channels == 1 or a.size == 0):
+                a = a.reshape(-1, self.channels)
+            if a.ndim != 2 or a.shape[1] != self.channels:
+                raise ValueError("push: one [frames, %d] array per stream" % self.channels)
+            arrs.append(a)
+        ioff = context.offsets(len(a) for a in arrs)
+        x = np.ascontiguousarray(np.concatenate(arrs), dtype=self.in_dtype).reshape(-1)
+        outc = self.out_counts([len(a) for a in arrs], end)
+        ooff = context.offsets(outc)
+        co = self.out_channels
+        din, dout = self.mem.up(x), self.mem.empty(ooff[-1] * co, self.out_dtype)
+        try:
+            self._push(self.mem.p(din), ioff, end, dout, ooff, outc)
+            out = self.mem.down(dout, ooff[-1] * co, self.out_dtype).reshape(-1, co)
+        finally:
+            self.mem.free(din, dout)
+        return [out[ooff[g]:ooff[g + 1]] for g in range(self.nstreams)]
 
     def push(self, chunks, end=None):
         """chunks: one 1-D in_dtype array per slot (may be empty); end[i]: slot i's stream ends after its chunk.  Returns
         one out_dtype array per slot: the samples that became final.  One upload of the pieces, one C call, one
-        download of the results."""
+        download of the results.  With interleaved frames: one [frames, channels] array per stream in, one
+        [frames, out_channels] array per stream out."""
+        if self.interleaved:
+            return self._push_frames(chunks, end)
         if len(chunks) != self.S:
             raise ValueError("push: one chunk per slot (%d)" % self.S)
         x, ioff = context.flat(chunks, self.in_dtype)
@@ -183,19 +275,21 @@ class LiveSession(online.Slots):
     def push_device(self, samples, counts, end=None):
         """Over Engine: samples is one contiguous device tensor of in_dtype holding the slots' pieces one after the
         other, counts[i] samples for slot i.  Returns (tensor of out_dtype on the engine's device, offsets): slot i's
-        results are tensor[offsets[i]:offsets[i + 1]].  No host copy of a sample either way."""
+        results are tensor[offsets[i]:offsets[i + 1]].  No host copy of a sample either way.
+        With interleaved frames: samples is the flat interleaved tensor, counts[g] FRAMES of `channels` elements for
+        stream g, and stream g's results are the frames tensor[offsets[g] * out_channels:offsets[g + 1] * out_channels]."""
         if not self.mem.torch:
             raise TypeError("push_device needs engine.Engine (torch device memory)")
         import torch
-        if len(counts) != self.S:
-            raise ValueError("push_device: one count per slot (%d)" % self.S)
+        if len(counts) != self.nstreams:
+            raise ValueError("push_device: one count per %s (%d)" % ("stream" if self.interleaved else "slot", self.nstreams))
         ioff = context.offsets(counts)
         if samples.dtype != getattr(torch, self.in_dtype.name) or samples.device != torch.device(self.eng.device) \
-                or not samples.is_contiguous() or samples.numel() < ioff[-1]:
+                or not samples.is_contiguous() or samples.numel() < ioff[-1] * self.channels:
             raise ValueError("push_device: a contiguous %s tensor on %s with at least %d samples"
-                             % (self.in_dtype.name, self.eng.device, ioff[-1]))
+                             % (self.in_dtype.name, self.eng.device, ioff[-1] * self.channels))
         outc = self.out_counts(counts, end)
         ooff = context.offsets(outc)
-        dout = self.mem.empty(ooff[-1], self.out_dtype)
+        dout = self.mem.empty(ooff[-1] * self.out_channels, self.out_dtype)
         self._push(hip.ptr(samples), ioff, end, dout, ooff, outc)
-        return dout[:ooff[-1]], ooff
+        return dout[:ooff[-1] * self.out_channels], ooff

@@ -39,7 +39,15 @@ and out unless --in_rate / --out_rate say otherwise), the same pushes by turns -
 "enabled" (enable_levels(), fixed factor 0.25) and "auto" (set_auto_wet(200, 1.0)) --, and launches_per_push and the
 live_level kernel time of each from a profiled pass.  On a library from before the level functions ($NHANS_LIB, for a
 same-box A/B) only "never" is there and the other figures are null.
-    python tools/online_bench.py --levels [--streams 1,16,64] [--hops 2] [--pushes 200] [--out F]"""
+    python tools/online_bench.py --levels [--streams 1,16,64] [--hops 2] [--pushes 200] [--out F]
+
+--interleaved: what interleaved frames (nhans_interleaved_*) cost a live push.  Per (S, H) one line with mode
+"interleaved": push p50 / p99 of three live.LiveSession objects of S SLOTS each, 48 kHz int16 in and out unless --in_rate /
+--out_rate say otherwise, the same pushes by turns -- "mono" (S mono slots), "downmix" (S stereo streams, one slot each,
+stereo out) and "split" (S / 2 stereo streams, two slots each; S even) --, and launches_per_push and the live_in / live_out
+kernel times of each from a profiled pass.  On a library from before the functions ($NHANS_LIB, for a same-box A/B) only
+"mono" is there and the other figures are null.
+    python tools/online_bench.py --interleaved [--streams 2,16,64] [--hops 2] [--pushes 200] [--out F]"""
 import argparse
 import json
 import os
@@ -291,6 +299,77 @@ def levels(a):
     return 0
 
 
+def interleaved(a):
+    eng = engine.Engine("denoiser", precision="f16x3")
+    ca, cb = apply.normalise(synth.silent()), apply.normalise(synth.noise_context(1))
+    rate_in, rate_out = a.in_rate or 48000, a.out_rate or 48000
+    idx = (np.arange(int(30.0 * rate_in)) * float(spec.FS) / rate_in).astype(np.int64)
+    audio = synth.mixture(1, 30.0)[np.minimum(idx, int(30.0 * spec.FS) - 1)]
+    stereo = np.ascontiguousarray(np.stack([audio, audio[::-1]], axis=1))
+    has = hasattr(hip.load(), "nhans_interleaved_live_push")
+    out = open(a.out, "a") if a.out else None
+    pct = lambda v, q: round(float(np.percentile(v, q)), 3) if len(v) else None
+    emb = eng.embed(eng.stft_features(torch.from_numpy(np.concatenate([ca, cb])).to(eng.device),
+                                      [0, len(ca), len(ca) + len(cb)], max_frames=spec.NOISE_WIN,
+                                      want_phase=False)[0].reshape(2, spec.NOISE_WIN, spec.BINS))
+    for S in [int(s) for s in a.streams.split(",")]:
+        if S % 2:
+            raise SystemExit("--interleaved: an even number of slots (a split stereo stream has two)")
+        for H in [int(h) for h in a.hops.split(",")]:
+            n = int(round(H * 0.010 * rate_in))
+            kinds = {"mono": dict(nslots=S), "downmix": dict(nslots=S, channels=2), "split": dict(nslots=S // 2, channels=2, channel_mode="split")}
+            objs = {}
+            for k in kinds if has else ("mono",):
+                kw = dict(kinds[k])
+                o = live.LiveSession(eng, kw.pop("nslots"), rate_in, rate_out, 32768, lookahead=a.lookahead, **kw)
+                for i in range(o.S):
+                    o.set_embeddings(i, emb[0], emb[1])
+                objs[k] = o
+            pos = {k: 0 for k in objs}
+
+            def push(k):
+                i = pos[k] % (len(audio) - n)
+                pos[k] += n
+                objs[k].push([audio[i:i + n]] * S if k == "mono" else [stereo[i:i + n]] * (S if k == "downmix" else S // 2))
+
+            for k in objs:
+                for _ in range(40):
+                    push(k)
+            torch.cuda.synchronize()
+            ts = {k: [] for k in objs}
+            for _ in range(a.pushes):
+                for k in objs:
+                    ts[k].append(_timed(lambda: push(k)))
+            launches, stage_ms = {}, {}
+            for k in objs:
+                eng.set_option("profile", 1)
+                eng.profile_reset()
+                for _ in range(10):
+                    push(k)
+                prof = eng.profile()
+                eng.set_option("profile", 0)
+                launches[k] = sum(v["calls"] for v in prof.values()) / 10
+                stage_ms[k] = {st: round(prof[st]["ms"] / max(prof[st]["calls"], 1), 4) if st in prof else None for st in ("live_in", "live_out")}
+            for o in objs.values():
+                o.close()
+            line = {"mode": "interleaved", "slots": S, "hops_per_push": H, "push_audio_ms": H * 10, "pushes": a.pushes,
+                    "in_rate": rate_in, "out_rate": rate_out, "lookahead": a.lookahead}
+            for k in kinds:
+                line["push_ms_p50_" + k] = pct(ts.get(k, []), 50)
+                line["push_ms_p99_" + k] = pct(ts.get(k, []), 99)
+                line["launches_per_push_" + k] = launches.get(k)
+                line["live_in_ms_" + k] = stage_ms.get(k, {}).get("live_in")
+                line["live_out_ms_" + k] = stage_ms.get(k, {}).get("live_out")
+            line.update({"lib": os.path.basename(os.environ.get("NHANS_LIB") or "tree"), "precision": "f16x3",
+                         "weights": "synthetic seed 7"})
+            print(json.dumps(line), flush=True)
+            if out:
+                out.write(json.dumps(line) + "\n")
+                out.flush()
+    eng.close()
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--churn", action="store_true", help="slots that callers join and leave (see the top of this file)")
@@ -308,7 +387,10 @@ def main():
     ap.add_argument("--capture", action="store_true", help="cost of the sample history and of a capture (see the top of this file)")
     ap.add_argument("--captures", type=int, default=20, help="--capture: timed capture_context / set_context calls")
     ap.add_argument("--levels", action="store_true", help="cost of the level meter and the automatic wet factor (see the top of this file)")
+    ap.add_argument("--interleaved", action="store_true", help="cost of interleaved stereo frames beside mono slots (see the top of this file)")
     a = ap.parse_args()
+    if a.interleaved:
+        return interleaved(a)
     if a.churn:
         return churn(a)
     if a.levels:
