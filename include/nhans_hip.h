@@ -740,6 +740,85 @@ int nhans_interleaved_live_out_counts(const nhans_live* obj, const int64_t* in_f
 int nhans_interleaved_live_push(nhans_live* obj, const void* in_dev, const int64_t* in_frame_offsets_host, const int* end_host,
                                 void* out_dev, const int64_t* out_frame_offsets_host, int64_t* out_frames_host, void* stream);
 
+/* ---- Filterbank features of log-magnitude rows, offline and live ---------------------------------------------------------
+ * Many consumers of the enhanced signal are machines -- speech, speaker and emotion recognisers -- that turn the waveform
+ * straight back into 25 ms / 10 ms log-mel frames: the framing the network already works in (400-sample periodic Hann
+ * window, hop 160, 201 bins 40 Hz apart).  The denoised log-magnitude row of frame g exists on the device the moment the
+ * stack has run; the functions below turn such rows into filterbank features there, without the iSTFT, the outgoing
+ * converter, a download and a second STFT.  Added without moving NHANS_ABI_VERSION; a caller that may meet an older
+ * library looks them up by symbol.
+ *
+ * Definition.  A filterbank is n_out bands (1 .. NHANS_FBANK_MAX_OUT), a non-negative finite matrix W[n_out, 201] given in
+ * double and stored as float32 (W32), power 1 or 2 and floor > 0 (stored as float32; it must be > 0 there).  For a row
+ * x[201] (float32, natural log: what nhans_stft_features and nhans_mask_net write)
+ *     p[k]   = exp(min(power * x[k], 88))                              float32 (expf)
+ *     mel[m] = sum of W32[m, k] * p[k],  k ascending over band m's span   ONE chain of fmaf in float32 from +0.0f
+ *     out[m] = ln(max(mel[m], floor))                                  float32 (logf)
+ * where the span of a band reaches from its first to its last non-zero float32 weight (a band without one is empty:
+ * out[m] = ln(floor)).  Over the domain of the network's rows, x in [ln 1e-5 - 20, 16], every p is a normal float32 for
+ * both powers and the clamp at 88 changes nothing; outside it the clamp keeps p finite.  A row's bits depend on the row and
+ * the filterbank only -- never on where the row sits in a call, which call computed it, or how a stream was cut into pushes.
+ * The spans of all bands together may hold NHANS_FBANK_MAX_SPAN entries (a mel bank of 128 bands has about 400): a matrix
+ * over that is refused, the message naming the cap.
+ * What the features are worth to a recogniser is a property of the trained model; nothing in this library measures it. */
+#define NHANS_FBANK_MAX_OUT 128
+#define NHANS_FBANK_MAX_SPAN 8192
+#define NHANS_FBANK_HTK 0           /* mel = 2595 log10(1 + f / 700) */
+#define NHANS_FBANK_SLANEY 1        /* mel = f / (200/3) below 1 kHz, 15 + ln(f / 1000) / (ln 6.4 / 27) from 1 kHz on */
+#define NHANS_FBANK_NORM_NONE 0
+#define NHANS_FBANK_NORM_SLANEY 1   /* band m times 2 / (p[m+2] - p[m]) */
+#define NHANS_FBANK_MIXED 1         /* attach flag: also the features of the same frames' unprocessed rows (plane 1) */
+
+typedef struct nhans_fbank nhans_fbank;
+
+/* Host only, no object.  The usual triangular matrix, in double: p[0 .. n_out + 1] equally spaced on the mel scale `scale`
+ * between f_min and f_max (0 <= f_min < f_max <= 8000 Hz), bin k at f_k = 40 k Hz,
+ *     W[m, k] = max(0, min((f_k - p[m]) / (p[m+1] - p[m]), (p[m+2] - f_k) / (p[m+2] - p[m+1])))   times the norm's factor
+ * -- the definitions librosa and torchaudio use.  Writes W to w_out_host ([n_out * 201], nullable) and returns the number
+ * of bands that are empty after float32 rounding (>= 0: narrow bands between two bins), or NHANS_EINVAL (n_out, the
+ * frequencies, an unknown scale or norm) with nothing written. */
+int nhans_fbank_design(int n_out, double f_min, double f_max, int scale, int norm, double* w_out_host);
+
+/* A filterbank on ctx's device.  The matrix is checked first, before anything touches a device: n_out outside 1 .. 128,
+ * power other than 1 or 2, a floor that is not finite and > 0 as a float32, a weight that is negative, NaN, infinite or
+ * beyond float32, or spans over NHANS_FBANK_MAX_SPAN are NHANS_EINVAL and *out is NULL.  The table is on the device when
+ * the call returns. */
+int nhans_fbank_open(nhans_ctx* ctx, const double* w_host, int n_out, int power, double floor, void* stream, nhans_fbank** out);
+void nhans_fbank_close(nhans_fbank* fb);
+
+/* Any [nrows, 201] log-magnitude rows -> [nrows, n_out] features: the denoised_out_dev of nhans_mask_net, or the logmag of
+ * nhans_stft_features for the unprocessed signal.  One launch, "fbank_rows"; nrows == 0 launches nothing.  The call uses
+ * the context the filterbank was opened on and is ordered with that context's other calls. */
+int nhans_fbank_rows(nhans_fbank* fb, const float* logmag_dev, int64_t nrows, float* out_dev, void* stream);
+
+/* Features of a live stream.  Attach COPIES fb's table into the object (one small allocation and a synchronous copy, no
+ * launch), so fb may be closed afterwards; fb == NULL detaches (flags must then be 0).  Allowed between pushes; it applies
+ * from the next push on and voids the rows of the last one.  With a filterbank attached, a push that computes frames --
+ * frames [R_old, R_new) of the "Look-ahead" contract, per slot -- issues ONE launch more, "online_fbank", behind the stack:
+ * it reads the push's denoised rows (plane 0) and, with NHANS_FBANK_MIXED, the same frames' unprocessed centre rows
+ * (plane 1) and writes a buffer of the object, which grows on demand by at least doubling.  The rows are bit for bit
+ * nhans_fbank_rows of nhans_mask_net's denoised_out_dev (option "lookahead" = the slot's L) and of nhans_stft_features'
+ * logmag for the same samples.  An object with nothing attached issues exactly the launches it issued before.
+ * Frame g is centred on sample 160 g + 200 of the slot's 16 kHz stream and its features exist 10 L + 25 ms after that
+ * sample arrived: no later than the audio, and usually a hop earlier (the even-pair rule does not apply to them). */
+int nhans_fbank_online_attach(nhans_online* obj, nhans_fbank* fb, int flags);
+
+/* Copies the rows the MOST RECENT push computed for `slot` (plane 0: denoised, 1: mixed -- NHANS_EINVAL unless attached with
+ * NHANS_FBANK_MIXED) to out_dev ([rows, n_out], room for cap_rows rows) on `stream` and returns their number;
+ * out_dev == NULL only returns the number.  *first_frame_out (nullable) is the stream frame index of the first row -- with
+ * no rows, of the next frame the slot will compute.  The number is 0 for a slot that computed nothing in the last push, and
+ * for every slot after nhans_online_rewind, an attach, a restart of that slot or a push whose launches were refused, until
+ * the next push; the redo of a rewound push brings the redone rows.  Negative on error: nothing attached, a slot or plane
+ * out of range, cap_rows too small. */
+int64_t nhans_fbank_online_read(nhans_online* obj, int slot, int plane, float* out_dev, int64_t cap_rows,
+                                int64_t* first_frame_out, void* stream);
+
+/* The same for the online stage of a live object, mono or interleaved; in split mode a channel is its slot.  The frames are
+ * those of the slot's 16 kHz stream, after the incoming converter and the fixed peak. */
+int nhans_fbank_live_attach(nhans_live* obj, nhans_fbank* fb, int flags);
+int64_t nhans_fbank_live_read(nhans_live* obj, int slot, int plane, float* out_dev, int64_t cap_rows, int64_t* first_frame_out,
+                              void* stream);
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

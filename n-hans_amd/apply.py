@@ -259,10 +259,26 @@ def _enhance_files(kind, mixedpath, ctx_a_path, ctx_b_path):
         res = _enhance_online(eng, mixedpath, ca, cb, FLAGS.online_ms, mixed if FLAGS.convert_on == "gpu" else None)
     else:
         res = eng.enhance([mixed], [ca], [cb], want_mixed=True, **_lookahead_kw())
+    if getattr(FLAGS, "fbank_out", None):
+        _write_fbank(eng, mixed, ca, cb, FLAGS.fbank_out)
     if TIMING is not None:
         TIMING.update(read_wavs_s=t1 - t0, engine_s=t2 - t1, enhance_s=time.perf_counter() - t2,
                       engine=type(eng).__name__, audio_s=len(mixed) / float(FLAGS.Fs))
     return res["denoised_wav"][0], res["mixed_wav"][0]
+
+
+def _write_fbank(eng, mixed, ca, cb, path):
+    """--fbank_out: the log-mel features of the denoised clip -- float32 [frames, n_mels], frame g centred on sample
+    160 g + 200 of the 16 kHz signal -- from the network's denoised rows on the device (Context.features: a second pass of
+    the network, no iSTFT), written with numpy.save.  The same look-ahead as the audio."""
+    from . import fbank
+    fb = fbank.Filterbank(n_mels=FLAGS.n_mels, scale=FLAGS.mel_scale)
+    try:
+        feats = eng.features([mixed], [ca], [cb], fb, **_lookahead_kw())[0]
+    finally:
+        fb.close()
+    with open(path, "wb") as f:          # (a file object: numpy.save appends no '.npy' to the name given)
+        np.save(f, np.ascontiguousarray(feats, dtype=np.float32))
 
 
 def _enhance_online(eng, mixedpath, ca, cb, piece_ms, normalised=None):
@@ -575,7 +591,18 @@ def _parse(argv, prog):
                    help='future audio every output frame may use: a multiple of 10 in 0 ... 170 (default 170, all 17 frames '
                         'of the window).  Less is what a live stream of that look-ahead would have produced -- latency '
                         '10 ms per frame + 25 ms -- at a cost in quality that depends on the trained model')
+    p.add_argument('--fbank_out', default=None, metavar='PATH.npy',
+                   help='file mode only: also write the log-mel filterbank features of the denoised signal (float32 '
+                        '[frames, n_mels], 25 ms / 10 ms frames, numpy.save) computed on the device from the network\'s '
+                        'denoised rows; the audio files are what they are without the flag')
+    p.add_argument('--n_mels', type=int, default=80, help='bands of --fbank_out, 1 ... 128 (default 80), 0 - 8000 Hz')
+    p.add_argument('--mel_scale', default='htk', choices=['htk', 'slaney'], help='mel scale of --fbank_out (default htk)')
     a = p.parse_args(argv)
+    if a.fbank_out is not None:
+        if os.path.isdir(a.input):
+            p.error('--fbank_out works on one input file; %s is a directory' % a.input)
+        if not 1 <= a.n_mels <= 128:
+            p.error('--n_mels must be in 1 ... 128; got %d' % a.n_mels)
     if not 0 <= a.lookahead_ms <= 10 * spec.LOOKAHEAD or a.lookahead_ms != 10 * int(a.lookahead_ms // 10):
         p.error('--lookahead_ms must be a multiple of 10 in 0 ... %d (one 10 ms frame of look-ahead each); got %g'
                 % (10 * spec.LOOKAHEAD, a.lookahead_ms))

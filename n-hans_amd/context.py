@@ -74,6 +74,56 @@ class Context:
         finally:
             self.set_option("lookahead", spec.LOOKAHEAD)
 
+    # ---- filterbank features of the enhanced clips (include/nhans_hip.h: nhans_fbank_*) --------
+    def features(self, mixes, ctx_a, ctx_b, fb, lookahead=spec.LOOKAHEAD, mixed=False):
+        """Lists of normalised float32 waveforms (mixtures trimmed, as enhance takes them) -> one float32 [T_i, fb.n_mels]
+        array per clip: fb (fbank.Filterbank) applied to the clip's denoised log-magnitude rows -- STFT, tower, stack and
+        filterbank on the device, no iSTFT, and only the features come back.  Frame g is centred on sample 160 g + 200.
+        lookahead as in enhance: what a live stream of that look-ahead computes for the same samples, bit for bit.
+        mixed=True: -> (denoised features, features of the unprocessed rows), two such lists.  The saturation redo of
+        enhance applies here too."""
+        return self._with_lookahead(lookahead, lambda: self._features(mixes, ctx_a, ctx_b, fb, mixed))
+
+    def _features(self, mixes, ctx_a, ctx_b, fb, mixed):
+        if not (len(mixes) == len(ctx_a) == len(ctx_b)):
+            raise ValueError("features: one (a, b) pair of conditioning recordings per clip")
+        lib, mem, n = self.lib, Mem(self), len(mixes)
+        (mf, off), (af, aoff), (bf, boff) = flat(mixes), flat(ctx_a), flat(ctx_b)
+        nfr = [int(lib.nhans_num_frames(off[i + 1] - off[i])) for i in range(n)]
+        if any(t == 0 for t in nfr):
+            raise ValueError("mixture clip %d has fewer than %d samples: no STFT frame" % (nfr.index(0), spec.WIN))
+        foff = offsets(nfr)
+        T, nm = foff[-1], fb.n_mels
+        h, s = fb.handle(self), mem.stream()
+        ins = [mem.up(x) for x in (mf, af, bf)]
+        lm, den = mem.empty(T * spec.BINS), mem.empty(T * spec.BINS)
+        ctx_lm, emb = mem.empty(2 * n * spec.NOISE_WIN * spec.BINS), mem.empty(2 * n * spec.EMB)
+        out = [mem.empty(T * nm), mem.empty(T * nm) if mixed else None]
+
+        def at(buf, floats):
+            return ctypes.c_void_p(mem.p(buf).value + 4 * floats)
+
+        def run():
+            c = hip.check
+            c(lib.nhans_stft_features(self.handle, mem.p(ins[0]), hip.i64_array(off), n, 0, mem.p(lm), None, s))
+            c(lib.nhans_stft_features(self.handle, mem.p(ins[1]), hip.i64_array(aoff), n, spec.NOISE_WIN, mem.p(ctx_lm), None, s))
+            c(lib.nhans_stft_features(self.handle, mem.p(ins[2]), hip.i64_array(boff), n, spec.NOISE_WIN,
+                                      at(ctx_lm, n * spec.NOISE_WIN * spec.BINS), None, s))
+            c(lib.nhans_embed(self.handle, mem.p(ctx_lm), 2 * n, mem.p(emb), s))
+            c(lib.nhans_mask_net(self.handle, mem.p(lm), hip.i64_array(foff), n, mem.p(emb), at(emb, n * spec.EMB), None,
+                                 mem.p(den), s))
+            c(lib.nhans_fbank_rows(h, mem.p(den), T, mem.p(out[0]), s))
+            if mixed:
+                c(lib.nhans_fbank_rows(h, mem.p(lm), T, mem.p(out[1]), s))
+
+        try:
+            redo_saturated_in_f32(self, run)          # (take_status waits for the stream)
+            res = [np.array(mem.down(o, T * nm), dtype=np.float32).reshape(T, nm) if o is not None else None for o in out]
+        finally:
+            mem.free(*ins, lm, den, ctx_lm, emb, *out)
+        split = [[r[foff[i]:foff[i + 1]] for i in range(n)] if r is not None else None for r in res]
+        return (split[0], split[1]) if mixed else split[0]
+
 
 def redo_saturated_in_f32(eng, run, undo=None):
     """run() -- the launches of one batch or push -- and its result; where they saturated the f16x3 path, run() again on

@@ -1,10 +1,12 @@
 // What the host units of libnhans_hip.so share (the C ABI itself: include/nhans_hip.h).  One unit per subsystem:
 //   host_ctx.hip      error channel, blob, context, options, calibration, workspace growth, Call, status, profiling
 //   host_net.hip      conv launch sequences (tower, stack, head), STFT / iSTFT block tables, the offline entry points
-//   host_online.hip   nhans_online_*, nhans_capture_*
+//   host_fbank.hip    filterbank design and table, nhans_fbank_design / _open / _close / _rows
+//   host_online.hip   nhans_online_*, nhans_capture_*, nhans_fbank_online_*
 //   host_rate.hip     rate-conversion stages, nhans_resample*, nhans_peak_normalise, nhans_channel_mean, nhans_resampler_*
-//   host_live.hip     nhans_live_*, nhans_lookahead_live_*, nhans_capture_live_*, nhans_level_*, nhans_interleaved_*
-// A unit calls down only: ctx <- net <- online <- live and ctx <- rate <- live.  (One call goes up: the built-in calibration
+//   host_live.hip     nhans_live_*, nhans_lookahead_live_*, nhans_capture_live_*, nhans_level_*, nhans_interleaved_*,
+//                     nhans_fbank_live_*
+// A unit calls down only: ctx <- net <- online <- live, ctx <- fbank <- online and ctx <- rate <- live.  (One call goes up: the built-in calibration
 // of nhans_create runs the whole offline path, enhance_clips_body.)  Only what crosses a unit boundary is declared here;
 // everything else stays in its unit's anonymous namespace.
 // Nothing declared here joins the library's dynamic symbols (visibility hidden) except the object types the C header
@@ -248,6 +250,37 @@ int enhance_clips_body(nhans_ctx* c, const float* mix, const int64_t* moff, int 
                        float* mixed_wav, float* logmag_out, float* phase_out, float* logits_out, float* emb_out,
                        void* stream);
 
+// ---- host_fbank.hip --------------------------------------------------------------------------------
+// A filterbank as the kernel reads it (nhans_kernels.h: the band table) with its device copy.  The host words are kept:
+// nhans_fbank_online_attach copies the table into the online object from them, so the filterbank it came from may go.
+struct FbankTable {
+    int n_out = 0, power = 2, nspan = 0;
+    float floor = 0.f;
+    std::vector<int32_t> words;     // 3 * n_out + nspan
+    int* dev = nullptr;
+};
+// a copy of `from` with a device table of its own (one hipMalloc, one synchronous copy); on failure nothing is allocated
+int fbank_table_clone(const FbankTable& from, const char* fn, FbankTable* out);
+void fbank_table_free(FbankTable* t);
+// One launch `name` over runs of rows (src, dst, nrows each; tile0 is filled in here), through runs_dev: room for nruns.
+struct FbankRows {
+    const float* src;
+    float* dst;
+    int64_t nrows;
+};
+int fbank_launch(nhans_ctx* c, const FbankTable& t, const char* name, const FbankRows* rows, int nruns, FbankRun* runs_dev,
+                 hipStream_t s);
+
+#pragma GCC visibility pop
+
+struct nhans_fbank {
+    nhans_ctx* c = nullptr;
+    int device = 0;
+    FbankTable t;
+};
+
+#pragma GCC visibility push(hidden)
+
 // ---- host_online.hip (the layout of a slot's state: there) -------------------------------------------
 constexpr int kOnRows = 2 * kCenter + kIstftHopsPerBlock - 14;  // 42 >= 17 + 24
 constexpr int kOnDenRows = kIstftHopsPerBlock + 2;              // 24
@@ -277,6 +310,18 @@ struct nhans_online {
     // -- and goes back only where a new timeline starts (restart: 0) or the ring does (enable: N).
     float* ring = nullptr;      // [S][kCaptureSamples]
     std::vector<int64_t> vlo, whi;  // whi: how far a push has written the slot's timeline (> N after a rewind; for messages)
+    // nhans_fbank_online_attach: the object's own copy of a filterbank and the feature rows of the last push -- plane 0
+    // (the denoised rows) at rows [0, F) of `rows`, plane 1 (the centre rows; `mixed` only) at [F, 2 F), slot i's at
+    // off[i] .. off[i] + cnt[i] of each plane, frames first[i] on.  cnt is all zero where there is nothing to read.
+    struct Fbank {
+        bool on = false, mixed = false;
+        FbankTable t;
+        float* rows = nullptr;
+        size_t cap = 0;             // (floats)
+        int64_t F = 0;
+        std::vector<int64_t> off, cnt, first;
+        void forget() { std::fill(cnt.begin(), cnt.end(), 0); }
+    } fb;
     float* slot(int k, int i) const { return state + ((size_t)k * S + i) * kOnSlot; }
 };
 
@@ -296,6 +341,9 @@ int capture_enable_body(nhans_online* o, const char* fn, hipStream_t s);
 int capture_context_body(nhans_online* o, const char* fn_, int n, const int* slots, const int* which, int flags,
                          hipStream_t s, int64_t* first_frame);
 int capture_embeddings_body(const nhans_online* o, const char* fn, int slot, float* ea, float* eb, hipStream_t s);
+int fbank_attach_body(nhans_online* o, const char* fn, const nhans_fbank* fb, int flags);
+int64_t fbank_read_body(nhans_online* o, const char* fn, int slot, int plane, float* out, int64_t cap_rows, int64_t* first_frame,
+                        hipStream_t s);
 
 // ---- host_rate.hip (rs_table and rs_add_runs: RateStage's inline members call them) -----------------------
 int rs_table(nhans_ctx* c, const ResampleFilter* f, const float** tab);

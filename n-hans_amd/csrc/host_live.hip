@@ -527,6 +527,21 @@ int nhans_capture_live_embeddings(const nhans_live* o, int slot, float* ea, floa
                        [&](hipStream_t s) { return capture_embeddings_body(o->on, "nhans_capture_live_embeddings", slot, ea, eb, s); });
 }
 
+// ---- filterbank features (include/nhans_hip.h: nhans_fbank_live_*): the online stage's, slot for slot ----
+int nhans_fbank_live_attach(nhans_live* o, nhans_fbank* fb, int flags) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_fbank_live_attach: null object");
+    return fbank_attach_body(o->on, "nhans_fbank_live_attach", fb, flags);
+}
+
+int64_t nhans_fbank_live_read(nhans_live* o, int slot, int plane, float* out, int64_t cap_rows, int64_t* first_frame_out, void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_fbank_live_read: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    const int64_t n = fbank_read_body(o->on, "nhans_fbank_live_read", slot, plane, out, cap_rows, first_frame_out, call.s);
+    const int rc = call.finish(n < 0 ? (int)n : NHANS_OK);
+    return rc ? rc : n;
+}
+
 // ---- level meter and automatic compensation (include/nhans_hip.h: nhans_level_*) ----
 int64_t nhans_level_hops(int64_t emitted, int ended) {
     if (emitted < 0) return fail(NHANS_EINVAL, "nhans_level_hops: negative sample count");

@@ -97,6 +97,7 @@ void online_undo(nhans_online* o) {
     o->st = o->prev;
     o->cur = 1 - o->cur;
     o->can_rewind = false;
+    o->fb.forget();
 }
 
 int online_open_slots_body(nhans_ctx* c, int S, int want_mixed, hipStream_t s, nhans_online** out) {
@@ -120,6 +121,7 @@ int online_open_slots_body(nhans_ctx* c, int S, int want_mixed, hipStream_t s, n
 void online_restart_slot(nhans_online* o, int slot) {
     o->st[slot] = OnStream();
     if (o->ring) o->vlo[slot] = o->whi[slot] = 0;
+    if (o->fb.on) o->fb.cnt[slot] = 0;
     o->can_rewind = false;
 }
 
@@ -160,6 +162,7 @@ int online_set_embeddings_body(nhans_online* o, int slot, const float* ea, const
 //   online_stft     the newly complete frames -> new log-magnitude / phase rows (the offline STFT kernel)
 //   online_assemble window source [lo, T_new) per stream, the ready frames' centre rows, synthesis staging from the state
 //   stack + head    over the ready frames of all streams at once (per-frame first-row table: WinRows::rb)
+//   online_fbank    (a filterbank attached: nhans_fbank_online_attach) the push's denoised and centre rows -> feature rows
 //   online_commit   denoised rows -> synthesis staging, and the next state slot
 //   online_istft    the offline iSTFT kernel on the synthesis staging (same pairs: the staging starts on an even frame)
 //   online_emit     the final samples -> the caller
@@ -230,6 +233,8 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
                    3 * ws_size(Y * kBins, 4) + (o->mixed ? 2 : 1) * ws_size(ooff[S], 4) + 2 * ws_size(2 * (S + 1), 8) +
                    ws_size(2 * nb_st, 4) + ws_size(2 * nb_is, 4) + ws_size(F, 4) + ws_size(nrun_cap, sizeof(OnlineCopy));
     if (F > 0) bytes += stack_ws_bytes(c, F, S, wf);
+    const bool feats = o->fb.on && F > 0;
+    if (feats) bytes += ws_size(2, sizeof(FbankRun));
     int rc = ws_reserve(c, bytes); if (rc) return rc;
     float* wav = ws_take<float>(c, soff[S]);
     float* nlm = ws_take<float>(c, NF * kBins);
@@ -250,7 +255,20 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
     OnlineCopy* runs_dev = ws_take<OnlineCopy>(c, nrun_cap);
     StackBufs sb{};
     if (F > 0) stack_take(c, F, S, wf, &sb);
-
+    FbankRun* fb_runs = feats ? ws_take<FbankRun>(c, 2) : nullptr;
+    if (feats) {
+        // (before anything goes out: a failed allocation leaves the object and the rows of the last push as they were)
+        const size_t need = (size_t)(o->fb.mixed ? 2 : 1) * F * o->fb.t.n_out;
+        if (need > o->fb.cap) {
+            const size_t want = std::max<size_t>({need, 2 * o->fb.cap, 4096});
+            float* q = nullptr;
+            const hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), want * 4);
+            if (e != hipSuccess) return fail(NHANS_ENOMEM, std::string("nhans_online_push: hipMalloc failed: ") + hipGetErrorString(e));
+            if (o->fb.rows) (void)hipFree(o->fb.rows);      // (hipFree waits for the device: no earlier read still copies from it)
+            o->fb.rows = q; o->fb.cap = want;
+            o->fb.forget();
+        }
+    }
     // ---- copy runs ----
     std::vector<OnlineCopy> runs;
     auto add = [&](const float* src, float* dst, int64_t n) {
@@ -341,6 +359,7 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
     if (runs.size() > nrun_cap) return fail(NHANS_EINVAL, "nhans_online_push: internal run bound");
 
     // ---- launches ----
+    o->fb.forget();      // (from here on the feature rows of the last push may be overwritten; set again below, with the host state)
     rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(OnlineCopy), s); if (rc) return rc;
     auto copies = [&](int k, const char* name) {
         const int n = bounds[k + 1] - bounds[k];
@@ -371,6 +390,11 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
         rc = mask_net_run(c, win, rb, ctr, F, S, o->emb, o->emb + (size_t)S * kEmb, nullptr, dnew, sb, wf, s);
         if (rc) return rc;
         if (launch_error_pending()) return NHANS_OK;      // (reported by the entry point; nothing below runs on it)
+        if (feats) {
+            // (the push's rows are compact, stream after stream, in dnew and in ctr: one run per plane whatever S is)
+            const FbankRows planes[2] = {{dnew, o->fb.rows, F}, {ctr, o->fb.rows + (size_t)F * o->fb.t.n_out, F}};
+            rc = fbank_launch(c, o->fb.t, "online_fbank", planes, o->fb.mixed ? 2 : 1, fb_runs, s); if (rc) return rc;
+        }
     }
     copies(2, "online_commit");
     if (Y > 0) {
@@ -392,7 +416,47 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
     }
     o->cur = nxt;
     o->can_rewind = true;
+    if (o->fb.on) {
+        o->fb.F = F;
+        for (int i = 0; i < S; ++i) { o->fb.off[i] = foff[i]; o->fb.cnt[i] = foff[i + 1] - foff[i]; o->fb.first[i] = pl[i].Ro; }
+    }
     return NHANS_OK;
+}
+
+// ---- filterbank features of a stream (include/nhans_hip.h: nhans_fbank_online_*) ------------------------------------------
+int fbank_attach_body(nhans_online* o, const char* fn_, const nhans_fbank* fb, int flags) {
+    const std::string fn = fn_;
+    if (flags & ~NHANS_FBANK_MIXED) return fail(NHANS_EINVAL, fn + ": unknown flag");
+    if (!fb && flags) return fail(NHANS_EINVAL, fn + ": flags must be 0 when detaching");
+    if (fb && fb->device != o->device) return fail(NHANS_EINVAL, fn + ": the filterbank lives on another device than the object");
+    const hipError_t e = hipSetDevice(o->device);
+    if (e != hipSuccess) return fail(NHANS_EHIP, fn + ": hipSetDevice: " + hipGetErrorString(e));
+    FbankTable t;
+    if (fb) { const int rc = fbank_table_clone(fb->t, fn_, &t); if (rc) return rc; }
+    fbank_table_free(&o->fb.t);
+    o->fb.t = t;
+    o->fb.on = fb != nullptr;
+    o->fb.mixed = (flags & NHANS_FBANK_MIXED) != 0;
+    o->fb.F = 0;
+    o->fb.off.assign(o->S, 0); o->fb.cnt.assign(o->S, 0); o->fb.first.assign(o->S, 0);
+    return NHANS_OK;
+}
+
+int64_t fbank_read_body(nhans_online* o, const char* fn_, int slot, int plane, float* out, int64_t cap_rows, int64_t* first_frame,
+                        hipStream_t s) {
+    const std::string fn = fn_;
+    if (!o->fb.on) return fail(NHANS_EINVAL, fn + ": no filterbank is attached (nhans_fbank_online_attach / nhans_fbank_live_attach)");
+    const int rc = slot_check(o->S, slot, fn_); if (rc) return rc;
+    if (plane != 0 && !(plane == 1 && o->fb.mixed))
+        return fail(NHANS_EINVAL, fn + ": plane " + std::to_string(plane) + (plane == 1 ? " needs an attach with NHANS_FBANK_MIXED"
+                                                                                        : " outside 0 (denoised) and 1 (mixed)"));
+    const int64_t n = o->fb.cnt[slot];
+    if (first_frame) *first_frame = n > 0 ? o->fb.first[slot] : on_ready(o->st[slot].T, o->st[slot].ended, o->la[slot]);
+    if (!out || n == 0) return n;
+    if (cap_rows < n) return fail(NHANS_EINVAL, fn + ": room for " + std::to_string(cap_rows) + " rows, " + std::to_string(n) + " needed");
+    const float* src = o->fb.rows + ((size_t)plane * o->fb.F + o->fb.off[slot]) * o->fb.t.n_out;
+    HIP_TRY(hipMemcpyAsync(out, src, (size_t)n * o->fb.t.n_out * 4, hipMemcpyDeviceToDevice, s));
+    return n;
 }
 
 // ---- conditioning captured from a slot's own stream (include/nhans_hip.h: nhans_capture_*) --------------------------------
@@ -572,7 +636,24 @@ void nhans_online_close(nhans_online* o) {
     (void)hipFree(o->emb);
     (void)hipFree(o->state);
     if (o->ring) (void)hipFree(o->ring);
+    fbank_table_free(&o->fb.t);
+    if (o->fb.rows) (void)hipFree(o->fb.rows);
     delete o;
+}
+
+int nhans_fbank_online_attach(nhans_online* o, nhans_fbank* fb, int flags) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_fbank_online_attach: null object");
+    return fbank_attach_body(o, "nhans_fbank_online_attach", fb, flags);
+}
+
+int64_t nhans_fbank_online_read(nhans_online* o, int slot, int plane, float* out, int64_t cap_rows, int64_t* first_frame_out,
+                                void* stream) {
+    if (!o) return fail(NHANS_EINVAL, "nhans_fbank_online_read: null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    const int64_t n = fbank_read_body(o, "nhans_fbank_online_read", slot, plane, out, cap_rows, first_frame_out, call.s);
+    const int rc = call.finish(n < 0 ? (int)n : NHANS_OK);
+    return rc ? rc : n;
 }
 
 int nhans_capture_plan(int64_t n_before, int64_t count, int64_t* runs_out) {

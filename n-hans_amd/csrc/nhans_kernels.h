@@ -386,4 +386,21 @@ struct LevelRun {
 constexpr int kLevelRing = 256, kLevelSums = 3 * kLevelRing, kLevelMeter = kLevelSums + 3, kLevelState = kLevelMeter + 8 + 5;
 void launch_level(const char* kernel, const LevelRun* runs_dev, int nruns, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// Filterbank features (fbank.hip; include/nhans_hip.h: nhans_fbank_*).  One run: nrows consecutive [201] log-magnitude
+// rows at src -> nrows consecutive [n_out] rows at dst; its tiles of kFbankTile rows are workgroups [tile0, tile0 +
+// ceil(nrows / kFbankTile)) of the launch, tile0 ascending from 0 over the runs (fbank_launch, host_fbank.hip, builds them).
+// The band table on the device, 32-bit words: first[n_out], count[n_out], woff[n_out], then the nspan float32 weights,
+// band m's at woff[m] .. woff[m] + count[m]; first[m] + count[m] <= 201.
+struct FbankRun {
+    const float* src;
+    float* dst;
+    long long nrows, tile0;
+};
+constexpr int kFbankTile = 16, kFbankMaxOut = 128, kFbankMaxSpan = 8192;
+constexpr float kFbankMaxExponent = 88.f;       // p = expf(min(power * x, 88)): finite whatever the row holds
+size_t fbank_lds_bytes(int n_out, int nspan);
+void launch_fbank(const char* kernel, const FbankRun* runs_dev, int nruns, long long ntiles, const int* table_dev, int n_out,
+                  int nspan, int power, float floor, hipStream_t s);
+
 }  // namespace nhans

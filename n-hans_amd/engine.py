@@ -138,6 +138,16 @@ class Engine(context.Context):
                                        len(frame_off) - 1, hip.i64_array(ooff), hip.ptr(out), self._stream()))
         return out, ooff
 
+    def fbank_rows(self, rows_t, fb):
+        """fb (fbank.Filterbank) applied to a device tensor of [n, 201] float32 log-magnitude rows -- mask_net's denoised
+        rows, or stft_features' logmag for the unprocessed signal -- -> device tensor [n, fb.n_mels]."""
+        if rows_t.dim() != 2 or rows_t.shape[1] != spec.BINS or rows_t.dtype != torch.float32:
+            raise ValueError("fbank_rows: a float32 [n, %d] tensor" % spec.BINS)
+        rows_t = rows_t.contiguous()
+        out = torch.empty((rows_t.shape[0], fb.n_mels), dtype=torch.float32, device=self.device)
+        hip.check(self.lib.nhans_fbank_rows(fb.handle(self), hip.ptr(rows_t), rows_t.shape[0], hip.ptr(out), self._stream()))
+        return out
+
     # ---- whole path -------------------------------------------------------------------------
     def enhance_device(self, mix_t, mix_off, ca_t, ca_off, cb_t, cb_off, want_mixed=False, taps=False):
         """All inputs already in HBM.  Returns dict of device tensors."""

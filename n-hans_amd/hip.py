@@ -103,6 +103,15 @@ SIGNATURES = {
     "nhans_interleaved_live_open": (_int, [_vp, _int, _int, _int, _int, _int, _int, _dbl, _int, _int, _dbl, _int, _vp, _vpp]),
     "nhans_interleaved_live_out_counts": (_int, [_vp, _i64p, _ip, _i64p]),
     "nhans_interleaved_live_push": (_int, [_vp, _vp, _i64p, _ip, _vp, _i64p, _i64p, _vp]),
+    # filterbank features
+    "nhans_fbank_design": (_int, [_int, _dbl, _dbl, _int, _int, _dp]),
+    "nhans_fbank_open": (_int, [_vp, _dp, _int, _int, _dbl, _vp, _vpp]),
+    "nhans_fbank_close": (None, [_vp]),
+    "nhans_fbank_rows": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "nhans_fbank_online_attach": (_int, [_vp, _vp, _int]),
+    "nhans_fbank_online_read": (_i64, [_vp, _int, _int, _vp, _i64, _i64p, _vp]),
+    "nhans_fbank_live_attach": (_int, [_vp, _vp, _int]),
+    "nhans_fbank_live_read": (_i64, [_vp, _int, _int, _vp, _i64, _i64p, _vp]),
     "nhans_profile_json": (_int, [_vp, _str, _size]),
     "nhans_profile_reset": (_int, [_vp]),
 }
@@ -118,6 +127,10 @@ ESHORT = -4
 LEVEL_MAX_WINDOW = 256
 INTERLEAVED_DOWNMIX, INTERLEAVED_SPLIT = 0, 1
 INTERLEAVED_MAX_CHANNELS = 8
+FBANK_MAX_OUT, FBANK_MAX_SPAN = 128, 8192
+FBANK_HTK, FBANK_SLANEY = 0, 1
+FBANK_NORM_NONE, FBANK_NORM_SLANEY = 0, 1
+FBANK_MIXED = 1
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25
 ABI_VERSION = 5

@@ -118,7 +118,7 @@ class LiveSession(online.Slots):
              set_context="nhans_live_set_context", set_embeddings="nhans_live_set_embeddings",
              set_lookahead="nhans_lookahead_live_set", capture_enable="nhans_capture_live_enable",
              capture_context="nhans_capture_live_context", capture_embeddings="nhans_capture_live_embeddings",
-             close="nhans_live_close")
+             fbank_attach="nhans_fbank_live_attach", fbank_read="nhans_fbank_live_read", close="nhans_live_close")
 
     def __init__(self, engine, nslots, in_rate, out_rate, peak, in_dtype=np.int16, out_dtype=np.int16, out_scale=None,
                  wet=False, lookahead=online.LOOKAHEAD, channels=1, out_channels=None, channel_mode="downmix"):

@@ -150,6 +150,7 @@ class Slots:
         self.ended = [False] * self.S
         self.conditioned = [conditioned] * self.S
         self._prev = None
+        self._fbank_n = 0
         self.lookahead = [LOOKAHEAD] * self.S
 
     def _c(self, what, *args):
@@ -250,6 +251,33 @@ class Slots:
             self.mem.free(rows)
         return out[:spec.EMB].copy(), out[spec.EMB:].copy()
 
+    # ---- filterbank features of the frames a push computes (include/nhans_hip.h: nhans_fbank_*) -
+    def enable_fbank(self, fb, mixed=False):
+        """From the next push on, every push also computes fb (fbank.Filterbank) of the frames it computes -- one small
+        launch more --, for features(i) to read; mixed=True: also of the same frames' unprocessed rows (plane 1).  The
+        table is copied into the object: fb may be closed.  None detaches.  The rows of the last push are voided."""
+        self._c("fbank_attach", fb.handle(self.eng) if fb is not None else None,
+                hip.FBANK_MIXED if (fb is not None and mixed) else 0)
+        self._fbank_n = fb.n_mels if fb is not None else 0
+
+    def features(self, i, plane=0):
+        """(first_frame, float32 [rows, n_mels]): the feature rows the most recent push computed for slot i -- frames
+        first_frame .. of its 16 kHz stream, frame g centred on sample 160 g + 200; ready_frames() says which frames a
+        push computes.  plane 1: the unprocessed rows (enable_fbank(mixed=True)).  No rows after rewind(), restart(i),
+        enable_fbank or for a slot the push computed nothing for; a push redone after saturation brings the redone rows."""
+        first = ctypes.c_int64(-1)
+        n = self._c("fbank_read", int(i), int(plane), None, 0, ctypes.byref(first), self.mem.stream())
+        nm = self._fbank_n
+        if n == 0:
+            return int(first.value), np.zeros((0, nm), dtype=np.float32)
+        buf = self.mem.empty(n * nm)
+        try:
+            self._c("fbank_read", int(i), int(plane), self.mem.p(buf), n, ctypes.byref(first), self.mem.stream())
+            out = np.array(self.mem.down(buf, n * nm), dtype=np.float32).reshape(n, nm)
+        finally:
+            self.mem.free(buf)
+        return int(first.value), out
+
     def _push_checked(self, push, counts, end, outc):
         """push(): one call of the push entry point, returning the counts it reported.  A push that saturates the f16x3
         path is undone and redone in f32 (context.redo_saturated_in_f32); then the host's view of the slots moves on."""
@@ -301,7 +329,7 @@ class OnlineEnhancer(Slots):
              set_context="nhans_online_set_context", set_embeddings="nhans_online_set_embeddings",
              set_lookahead="nhans_online_set_lookahead", capture_enable="nhans_capture_enable",
              capture_context="nhans_capture_context", capture_embeddings="nhans_capture_embeddings",
-             close="nhans_online_close")
+             fbank_attach="nhans_fbank_online_attach", fbank_read="nhans_fbank_online_read", close="nhans_online_close")
 
     def _begin(self, engine, S, conditioned, want_mixed):
         super()._begin(engine, S, conditioned)

@@ -229,6 +229,97 @@ def capture(a):
     return 0
 
 
+def fbank_cost(a):
+    """--fbank: push p50 / p99 of an S-stream object with nothing attached and of its twin with an 80-band HTK filterbank
+    attached (one online_fbank launch more per push that computes frames, and one features() read of slot 0), the two
+    alternating push by push; then the offline kernel alone: nhans_fbank_rows over 256 x 998 rows, --pushes calls, as bytes
+    moved (804 read + 4 n_mels written per row) per second -- by the library's own events around the launch (option
+    "profile": the kernel), and by events around the whole Python call (which also wait for the host to get there)."""
+    from nhans_amd import fbank
+    eng = engine.Engine("denoiser", precision="f16x3")
+    ca, cb = apply.normalise(synth.silent()), apply.normalise(synth.noise_context(1))
+    audio = apply.normalise(synth.mixture(1, 30.0))
+    fb = fbank.Filterbank(80)
+    out = open(a.out, "a") if a.out else None
+    pct = lambda v, q: round(float(np.percentile(v, q)), 3) if len(v) else None
+
+    def emit(line):
+        line.update({"lib": os.path.basename(os.environ.get("NHANS_LIB") or "tree"), "precision": "f16x3",
+                     "weights": "synthetic seed 7"})
+        print(json.dumps(line), flush=True)
+        if out:
+            out.write(json.dumps(line) + "\n")
+            out.flush()
+
+    for S in [int(s) for s in a.streams.split(",")]:
+        for H in [int(h) for h in a.hops.split(",")]:
+            n = H * spec.HOP
+            objs = {"detached": online.OnlineEnhancer(eng, [ca] * S, [cb] * S),
+                    "attached": online.OnlineEnhancer(eng, [ca] * S, [cb] * S),
+                    "attached_read": online.OnlineEnhancer(eng, [ca] * S, [cb] * S)}
+            objs["attached"].enable_fbank(fb)
+            objs["attached_read"].enable_fbank(fb)
+            pos = {k: 0 for k in objs}
+
+            def push(k):
+                i = pos[k] % (len(audio) - n)
+                pos[k] += n
+                objs[k].push([audio[i:i + n]] * S)
+                if k == "attached_read":
+                    objs[k].features(0)
+
+            for k in objs:
+                for _ in range(40):
+                    push(k)
+            torch.cuda.synchronize()
+            ts = {k: [] for k in objs}
+            for _ in range(a.pushes):
+                for k in objs:
+                    ts[k].append(_timed(lambda: push(k)))
+            launches = {}
+            for k in objs:
+                eng.set_option("profile", 1)
+                eng.profile_reset()
+                for _ in range(10):
+                    push(k)
+                launches[k] = sum(v["calls"] for v in eng.profile().values()) / 10
+                eng.set_option("profile", 0)
+            for o in objs.values():
+                o.close()
+            line = {"mode": "fbank", "streams": S, "hops_per_push": H, "push_audio_ms": H * 10, "pushes": a.pushes, "n_mels": 80}
+            for k in objs:
+                line["push_ms_p50_" + k] = pct(ts[k], 50)
+                line["push_ms_p99_" + k] = pct(ts[k], 99)
+                line["launches_per_push_" + k] = launches[k]
+            emit(line)
+    rows = torch.empty((256 * 998, spec.BINS), dtype=torch.float32, device=eng.device).uniform_(-31.5, 16.0)
+    for _ in range(5):
+        eng.fbank_rows(rows, fb)
+    ms = []
+    for _ in range(a.pushes):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        eng.fbank_rows(rows, fb)
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    nbytes = rows.shape[0] * 4.0 * (spec.BINS + fb.n_mels)
+    eng.set_option("profile", 1)
+    eng.profile_reset()
+    for _ in range(a.pushes):
+        eng.fbank_rows(rows, fb)
+    prof = eng.profile()["fbank_rows"]
+    eng.set_option("profile", 0)
+    kernel_ms = prof["ms"] / prof["calls"]
+    emit({"mode": "fbank_rows", "rows": rows.shape[0], "n_mels": fb.n_mels, "bytes": nbytes, "calls": len(ms),
+          "kernel_ms_mean": round(kernel_ms, 4), "kernel_gbytes_per_s": round(nbytes / (kernel_ms * 1e-3) / 1e9, 1),
+          "call_ms_p50": pct(ms, 50), "call_ms_min": round(min(ms), 4),
+          "call_gbytes_per_s_p50": round(nbytes / (pct(ms, 50) * 1e-3) / 1e9, 1)})
+    fb.close()
+    eng.close()
+    return 0
+
+
 def levels(a):
     eng = engine.Engine("denoiser", precision="f16x3")
     ca, cb = apply.normalise(synth.silent()), apply.normalise(synth.noise_context(1))
@@ -387,10 +478,13 @@ def main():
     ap.add_argument("--capture", action="store_true", help="cost of the sample history and of a capture (see the top of this file)")
     ap.add_argument("--captures", type=int, default=20, help="--capture: timed capture_context / set_context calls")
     ap.add_argument("--levels", action="store_true", help="cost of the level meter and the automatic wet factor (see the top of this file)")
+    ap.add_argument("--fbank", action="store_true", help="cost of an attached filterbank per push, and the offline kernel's bytes/s")
     ap.add_argument("--interleaved", action="store_true", help="cost of interleaved stereo frames beside mono slots (see the top of this file)")
     a = ap.parse_args()
     if a.interleaved:
         return interleaved(a)
+    if a.fbank:
+        return fbank_cost(a)
     if a.churn:
         return churn(a)
     if a.levels:
