@@ -819,6 +819,50 @@ int nhans_fbank_live_attach(nhans_live* obj, nhans_fbank* fb, int flags);
 int64_t nhans_fbank_live_read(nhans_live* obj, int slot, int plane, float* out_dev, int64_t cap_rows, int64_t* first_frame_out,
                               void* stream);
 
+/* ---- Live sessions: full-band output, the band above 8 kHz carried through ------------------------------------------------
+ * Everything a live object returns has been through the 16 kHz network path: at 44.1 or 48 kHz the output carries nothing
+ * above 8 kHz.  A full-band object adds the input's own high band, delayed to line up with the output, inside the
+ * outgoing launch.  It applies to an object with rate_in == rate_out == r, r one of 22050, 24000, 32000, 44100, 48000,
+ * 88200 or 96000, opened with NHANS_LIVE_WET, mono or interleaved.  Per slot, with
+ *   x[n]  the slot's incoming sample n as float32, as the incoming stage forms it (the PCM sample; with interleaved frames
+ *         the downmix mean or the slot's own channel),
+ *   u[n]  = float32(double(x[n]) / (peak + 1e-6)) -- the incoming stage's division --, 0 from the end of the input on,
+ *   d[k], m[k]  the final 16 kHz denoised and mixed-round-trip samples, c[k] the combined one (d + (m - d) * w with the
+ *         fixed or the hop's automatic factor; d where the factor is 0),
+ *   g     the slot's high-band gain, float32, 0 <= g <= 4,
+ * the outgoing stage converts e[k] = c[k] - g * m[k] where it converted c[k] (same filter, tap order and carried samples,
+ * which now are e), lo[n] being its output n, and stores y[n] = lo[n] + g * u[n] through the arithmetic it stored lo[n]
+ * through: float32(double(y) * out_scale), then the rounding and the clamp for int16.  Each of the two expressions is a
+ * product and a sum rounded separately in float32.  In real numbers y = R(c) + g (u - R(m)), R the conversion 16 kHz ->
+ * r: u - R(m) is the input less its own trip through 16 kHz, the complement of the two cascaded low-passes -- below
+ * 6 kHz what is left of a tone is the filters' pass-band ripple, at most 2.3e-3 of it (about -53 dB, times g), from
+ * 8.5 kHz on it is the tone.  Output sample n is aligned with input sample n.
+ *   g = 0: the output of an object that never enabled the feature, bit for bit.
+ *   wet = 1, g = 1, int16 in and out on the scale it came in on (out_scale == peak + 1e-6): the input itself, delayed.
+ *   A changed gain is piecewise: e[k] takes the gain of the push that brought 16 kHz sample k into the outgoing stage,
+ *   g * u[n] that of the push that emits n.
+ * The input samples that have no output yet are kept per slot in a double-buffered hold of H(r) float32 samples, H(r) the
+ * largest N - nhans_lookahead_live_emitted(N, 0, r, r, L) over N and L <= 17; a push of an enabled object issues one small
+ * launch more ("live_hold" in the profile) and still one "live_out".  Rewind and restart stay host-only. */
+/* H(r), in samples; NHANS_EINVAL for a rate that is not one of the seven. */
+int64_t nhans_fullband_hold_samples(int rate);
+/* Enables the full band of every slot with gain 1.0 (idempotent); the push before it cannot be rewound.  NHANS_EINVAL,
+ * with nothing changed: rate_in != rate_out; a rate <= 16000; an object opened without NHANS_LIVE_WET; a slot that has
+ * taken a sample (enable after open, or after restarting every slot that has). */
+int nhans_fullband_live_enable(nhans_live* obj, void* stream);
+/* The gain of `slot` (-1: of every slot), finite, 0 <= gain <= 4, from the next push on; the push before it cannot be
+ * rewound.  In downmix mode the high band is that of the downmix, copied to every output channel. */
+int nhans_fullband_live_set_gain(nhans_live* obj, int slot, double gain);
+/* The whole-clip twin, the kernels of ended streams: nclips clips of x at `rate` (x_format int16 or float32, clip i at
+ * x_offsets[i] .. x_offsets[i + 1]) with their d and m at 16 kHz (clip i at offsets16[i] .. offsets16[i + 1] of both) ->
+ * y as out_format, nhans_resample_out_count(n16, 16000, rate) samples per clip from out_offsets[i] on.  in_denom is the
+ * divisor of u (peak + 1e-6); wet the fixed factor, or wet_hops_dev (nullable) one factor per hop of 160 samples of each
+ * clip, ceil(n16 / 160) per clip one clip after the other -- the layout of nhans_level_gains. */
+int nhans_fullband_mix(nhans_ctx* ctx, const void* x_dev, int x_format, const int64_t* x_offsets_host, const float* den_dev,
+                       const float* mix_dev, const int64_t* offsets16_host, int nclips, int rate, double in_denom, double wet,
+                       const float* wet_hops_dev, double gain, double out_scale, int out_format, void* out_dev,
+                       const int64_t* out_offsets_host, void* stream);
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

@@ -62,6 +62,7 @@ class Flags(object):
     online_ms = None     # --online_ms: file mode through the online path (online.py) in pieces of this many ms
     convert_on = "host"  # --convert_on gpu: format / rate conversion and normalisation of the files on the device (resample.py)
     output_rate = "16000"    # --output_rate input: the output files at the input file's rate (converted back on the device)
+    highband = None      # --highband G: the input's own band above 8 kHz, times G, added to the files written at the input's rate (live.fullband_mix)
     lookahead_ms = 10 * spec.LOOKAHEAD   # --lookahead_ms: 10 ms per frame of look-ahead (include/nhans_hip.h: "lookahead"), 170 = all 17
 
 
@@ -137,11 +138,24 @@ def extend_context(samples):
     return out
 
 
-def _front_end_gpu(eng, path):
-    """--convert_on gpu: apply.normalise(read_wav_any(path)) computed on the device (resample.front_end)."""
+_highband_src = {}       # input path -> (the file's channel mean at its own rate, the divisor of its 16 kHz signal)
+
+
+def _front_end_gpu(eng, path, highband=False):
+    """--convert_on gpu: apply.normalise(read_wav_any(path)) computed on the device (resample.front_end).  highband
+    (--highband, the input file): also keeps what live.fullband_mix adds back -- the channel mean of the file at its own
+    rate, on the int16 scale, and the peak + 1e-6 the 16 kHz signal was divided by."""
     from . import resample
     rate, samples = wavread(path)
-    return resample.front_end(eng, samples, rate, FLAGS.Fs)
+    if not highband:
+        return resample.front_end(eng, samples, rate, FLAGS.Fs)
+    from . import live
+    y, peak = resample.front_end(eng, samples, rate, FLAGS.Fs, return_peak=True)
+    if not peak > 0:
+        raise ValueError("%s: --highband needs a positive peak (a silent file, or the wrapped peak of a mono int16 file "
+                         "that reaches -32768)" % path)
+    _highband_src[path] = (live.downmix(resample.decode_pcm(samples).T), peak + 0.000001)
+    return y
 
 
 def _handle_signals_gpu(kind, mixedpath, a_path, b_path):
@@ -152,7 +166,7 @@ def _handle_signals_gpu(kind, mixedpath, a_path, b_path):
             return np.zeros(spec.MIN_CTX_SAMPLES, dtype=np.float32)
         return extend_context(_front_end_gpu(eng, path))       # (repeating a recording does not change its peak)
 
-    mixed = trim_to_frames(_front_end_gpu(eng, mixedpath))
+    mixed = trim_to_frames(_front_end_gpu(eng, mixedpath, FLAGS.highband is not None))
     if len(mixed) < spec.WIN:
         raise ValueError("%s: shorter than one %d-sample STFT window" % (mixedpath, spec.WIN))
     return context(a_path), context(b_path), mixed
@@ -340,13 +354,42 @@ def _out_rate(save_to):
     return rate, lambda x: resample.resample(eng, [np.asarray(x, dtype=np.float32)], FLAGS.Fs, rate)[0]
 
 
+_job_high = {}           # save_to -> (kind, x, in_denom): --highband, what _fullband_writer adds to the files of the job
+
+
+def _note_highband(kind, mixedpath, save_to):
+    """--highband, after the input has been through the device front end: binds what it kept to the job's output."""
+    if FLAGS.highband is None:
+        return
+    from . import hip
+    rate = _job_rate.get(save_to, (FLAGS.Fs, None))[0]
+    if rate not in hip.FULLBAND_RATES:
+        raise ValueError("%s: --highband needs an input above 16 kHz (%s Hz); this file is at %d Hz"
+                         % (mixedpath, ", ".join(str(r) for r in hip.FULLBAND_RATES), rate))
+    _job_high[save_to] = (kind,) + _highband_src.pop(mixedpath)
+
+
+def _fullband_writer(save_to, rate):
+    """None without --highband; with it, full(den, mix, wet) -> the float32 signal at `rate`:
+    R(c - G mix) + G x / in_denom, c = den + (mix - den) * wet, on the device (live.fullband_mix)."""
+    job = _job_high.pop(save_to, None)
+    if job is None:
+        return None
+    from . import live
+    kind, x, in_denom = job
+    eng = get_enhancer(kind)
+    return lambda den, mix, wet: live.fullband_mix(eng, x, np.asarray(den, dtype=np.float32), np.asarray(mix, dtype=np.float32),
+                                                   rate, in_denom, wet=wet, gain=FLAGS.highband, out_dtype=np.float32)
+
+
 def write_snc_outputs(save_to, denoised_samples, mixed_samples):
     """The four files of SN/apply.py:456-472: denoised, mixed_processed (STFT->iSTFT round trip of
     the input), removed = mixed - denoised, compensated = denoised + removed * factor with the
     factor FLAGS.compensate or, under --ac, snr_est / 20.  Returns (snr_est, factor)."""
     pre = side_prefix(save_to)
     rate, conv = _out_rate(save_to)
-    wavwrite(save_to, rate, conv(denoised_samples))
+    full = _fullband_writer(save_to, rate)
+    wavwrite(save_to, rate, full(denoised_samples, mixed_samples, 0.0) if full else conv(denoised_samples))
     wavwrite(pre + 'mixed_processed.wav', rate, conv(mixed_samples))
     removed_samples = mixed_samples - denoised_samples
     wavwrite(pre + 'removed.wav', rate, conv(removed_samples))
@@ -356,7 +399,8 @@ def write_snc_outputs(save_to, denoised_samples, mixed_samples):
     print('---------------------------')
     factor = snr_est / 20 if FLAGS.ac else FLAGS.compensate
     compensated_samples = denoised_samples + removed_samples * factor
-    wavwrite(pre + 'compensated.wav', rate, conv(compensated_samples.astype(np.float32)))
+    wavwrite(pre + 'compensated.wav', rate, full(denoised_samples, mixed_samples, float(factor)) if full and np.isfinite(factor)
+             else conv(compensated_samples.astype(np.float32)))
     return snr_est, factor
 
 
@@ -366,6 +410,7 @@ def apply_snc(mixedpath, pospath, negpath, save_to):
     side files (naming: side_prefix)."""
     _note_job(spec.DENOISER, mixedpath, save_to)
     denoised_samples, mixed_samples = _enhance_files(spec.DENOISER, mixedpath, pospath, negpath)
+    _note_highband(spec.DENOISER, mixedpath, save_to)
     write_snc_outputs(save_to, denoised_samples, mixed_samples)
 
 
@@ -381,13 +426,15 @@ def apply_separator(mixedpath, cleanpath, noisepath, save_to):
     (interferer, --neg) speaker.  resnet_block order is (noise, clean), SS/main.py:205-242."""
     _note_job(spec.SEPARATOR, mixedpath, save_to)
     denoised_samples, mixed_samples = _enhance_files(spec.SEPARATOR, mixedpath, noisepath, cleanpath)
+    _note_highband(spec.SEPARATOR, mixedpath, save_to)
     write_separator_outputs(save_to, denoised_samples, mixed_samples)
 
 
 def write_separator_outputs(save_to, denoised_samples, mixed_samples):
     """SS/apply.py:391-397: the separated target and the round trip of the input."""
     rate, conv = _out_rate(save_to)
-    wavwrite(save_to, rate, conv(denoised_samples))
+    full = _fullband_writer(save_to, rate)
+    wavwrite(save_to, rate, full(denoised_samples, mixed_samples, 0.0) if full else conv(denoised_samples))
     wavwrite(side_prefix(save_to) + 'mixed_processed.wav', rate, conv(mixed_samples))
 
 
@@ -587,6 +634,10 @@ def _parse(argv, prog):
                         'the default) or gpu (the device rate converter, rates of nhans_amd.resample.RATES)')
     p.add_argument('--output_rate', default='16000', choices=['16000', 'input'],
                    help='input: write the output files at the input file\'s rate (converted back on the device)')
+    p.add_argument('--highband', type=float, default=None, metavar='G',
+                   help='file mode with --output_rate input --convert_on gpu, input above 16 kHz: the denoised and the '
+                        'compensated file also carry the input\'s own band above 8 kHz, times G (0 ... 4; 1: as it came in) '
+                        '-- the 16 kHz network path has none.  A multi-channel input gives the band of its channel mean')
     p.add_argument('--lookahead_ms', type=float, default=10.0 * spec.LOOKAHEAD,
                    help='future audio every output frame may use: a multiple of 10 in 0 ... 170 (default 170, all 17 frames '
                         'of the window).  Less is what a live stream of that look-ahead would have produced -- latency '
@@ -607,6 +658,14 @@ def _parse(argv, prog):
         p.error('--lookahead_ms must be a multiple of 10 in 0 ... %d (one 10 ms frame of look-ahead each); got %g'
                 % (10 * spec.LOOKAHEAD, a.lookahead_ms))
     a.lookahead_ms = int(a.lookahead_ms)
+    if a.highband is not None:
+        if not 0.0 <= a.highband <= 4.0:
+            p.error('--highband must be in 0 ... 4; got %g' % a.highband)
+        if os.path.isdir(a.input) or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            p.error('--highband works on one input file (directory mode and sharded runs write 16 kHz batches)')
+        if a.output_rate != 'input' or a.convert_on != 'gpu' or not a.convert:
+            p.error('--highband needs --output_rate input --convert_on gpu (and no --no-convert): the band is added at the '
+                    'input file\'s own rate, on the device')
     if a.online_ms is not None:
         if a.online_ms <= 0:
             p.error('--online_ms must be positive')

@@ -5,7 +5,7 @@
 //   host_online.hip   nhans_online_*, nhans_capture_*, nhans_fbank_online_*
 //   host_rate.hip     rate-conversion stages, nhans_resample*, nhans_peak_normalise, nhans_channel_mean, nhans_resampler_*
 //   host_live.hip     nhans_live_*, nhans_lookahead_live_*, nhans_capture_live_*, nhans_level_*, nhans_interleaved_*,
-//                     nhans_fbank_live_*
+//                     nhans_fbank_live_*, nhans_fullband_*
 // A unit calls down only: ctx <- net <- online <- live, ctx <- fbank <- online and ctx <- rate <- live.  (One call goes up: the built-in calibration
 // of nhans_create runs the whole offline path, enhance_clips_body.)  Only what crosses a unit boundary is declared here;
 // everything else stays in its unit's anonymous namespace.
@@ -359,6 +359,7 @@ struct RateIo {
     double factor;
     bool auto_wet = false;      // from_mix: each hop's factor comes from the runs' gain table (GainTab) instead of `wet`
     bool interleaved = false;   // the PCM side is frames of several channels (Interleave): the kernel's interleaved source / sink
+    bool highband = false;      // from_mix: the full-band source and sink, on what HighBandIo puts into the runs
     size_t in_elem() const { return from_mix ? 4 : rs_elem(pcm_format); }
     size_t out_elem() const { return from_mix ? rs_elem(pcm_format) : 4; }
 };
@@ -426,8 +427,29 @@ struct Interleave {
     const int64_t* base;
 };
 
+// The input's own band of a full-band live push (io.highband; ResampleRun's hb_ fields), per stream i of the outgoing
+// stage: its gain, the hold half that has its incoming samples [base[i], n_old[i]), and the push's cnt[i] new ones --
+// element pos[i] of the PCM at `in` on, laid out as the incoming stage read them (ch == 0: mono).
+struct HighBandIo {
+    const float* gain;
+    const float* const* hold;
+    const int64_t *base, *n_old, *cnt, *pos;
+    const void* in;
+    int fmt, ch, sum;
+    double denom;
+};
+// the fields of one run whose first output is output m0 of its stream
+inline void highband_run(ResampleRun& r, float gain, const float* hold, int64_t base, int64_t n_old, int64_t cnt, const void* in,
+                         int fmt, int ch, int sum, double denom, int64_t m0) {
+    r.hb_gain = gain; r.hb_hold = hold; r.hb_in = in;
+    r.hb_base = base; r.hb_n_old = n_old; r.hb_n_end = n_old + cnt; r.hb_m0 = m0;
+    r.hb_denom = denom; r.hb_fmt = fmt; r.hb_ch = ch; r.hb_sum = sum;
+}
+
 int stage_push(nhans_ctx* c, RateStage& g, const char* kernel, const RateIo& io, const void* in, const float* mix,
                const int64_t* inoff, const int* end, void* out, const int64_t* outoff, int64_t* counts, hipStream_t s,
-               const GainTab* gains = nullptr, const Interleave* il = nullptr);
+               const GainTab* gains = nullptr, const Interleave* il = nullptr, const HighBandIo* hb = nullptr);
+int rs_launch(nhans_ctx* c, const char* name, const std::vector<ResampleRun>& runs, const float* tab, const ResampleFilter& f,
+              const RateIo& io, size_t lds, double in_bytes, double out_bytes, int64_t out_samples, hipStream_t s);
 
 #pragma GCC visibility pop

@@ -7,7 +7,12 @@
 // An object opened with nhans_interleaved_live_open is the same object whose PCM sides are frames of several channels
 // (include/nhans_hip.h: nhans_interleaved_*): only where a slot's samples sit in the caller's buffers differs, which the
 // two converters' runs carry (Interleave, host_internal.h) -- the same three stages, launches and snapshots.
+// An object that has enabled its full band (include/nhans_hip.h: nhans_fullband_*) also keeps, per slot, the incoming
+// samples that have no output yet (FullBand below): one small launch more per push, and the outgoing launch adds the
+// input's own band above 8 kHz to what it stores.
 #include "host_internal.h"
+
+#include <mutex>
 
 // The level meter of a live object (nhans_level_live_enable; level.hip): per slot a double-buffered state of kLevelState
 // doubles -- a push reads half cur[i] and writes the other one, as RateStage::hist --, and the gain table of the last
@@ -25,6 +30,22 @@ struct LevelMeter {
         std::vector<char> cur;
     } st;
     std::vector<int64_t> woff;      // the last push's hops per slot, as offsets into wtab ([S + 1]; empty: none to read)
+};
+
+// The full band of a live object (nhans_fullband_live_enable; resample.hip: ResidualSource, HighbandSink, hold_kernel):
+// per slot a gain and a double-buffered hold of H float32 samples -- the slot's own incoming samples that have no output
+// yet, x as the incoming stage's source forms them.  Half cur[i] holds samples [base[i], N) of the stream, N the samples
+// the incoming stage has taken; a push that brings samples reads it and writes [E_new, N_new) into the other half, as
+// RateStage::hist, so the snapshot of a push is cur and base alone.
+struct FullBand {
+    bool on = false;
+    int64_t H = 0;
+    float* hold = nullptr;          // [2][S][H]
+    std::vector<float> gain;        // [S]
+    struct Slots {
+        std::vector<char> cur;
+        std::vector<int64_t> base;
+    } st;
 };
 
 struct nhans_live {
@@ -47,7 +68,10 @@ struct nhans_live {
         bool on = false;
         int Ci = 1, Co = 1, G = 0, K = 1;
     } fr;
+    FullBand fb;
+    FullBand::Slots undo_fb;
     double* lv_half(int k, int i) const { return lv.state + ((size_t)k * S + i) * kLevelState; }
+    float* fb_half(int k, int i) const { return fb.hold + ((size_t)k * S + i) * (size_t)fb.H; }
 };
 
 namespace {
@@ -152,6 +176,35 @@ int live_level(nhans_live* o, const int64_t* ooff, const int* end, hipStream_t s
     return NHANS_OK;
 }
 
+// The hold launch of a full-band push: one run per slot whose stream goes on after samples of this push (keep[i] >= 0:
+// the first sample its next half holds), reading half cur[i] and the caller's PCM -- slot i's from element pos[i] on --,
+// writing the other half.  Host state does not move here: *next is what fb.st becomes once the whole push has gone out.
+int live_hold(nhans_live* o, const void* in, const int64_t* pos, const Interleave* il_in, const int64_t* keep, const int64_t* n_old,
+              const int64_t* cnt, hipStream_t s, FullBand::Slots* next) {
+    nhans_ctx* c = o->c;
+    *next = o->fb.st;
+    std::vector<HoldRun> runs;
+    double samples = 0;
+    for (int i = 0; i < o->S; ++i) {
+        if (keep[i] < 0) continue;
+        const int k = o->fb.st.cur[i];
+        runs.push_back({o->fb_half(k, i), o->fb_half(1 - k, i), static_cast<const char*>(in) + pos[i] * rs_elem(o->in_format),
+                        (long long)o->fb.st.base[i], (long long)n_old[i], (long long)keep[i], (long long)(n_old[i] + cnt[i]),
+                        o->in_format, il_in ? il_in->ch : 0, il_in ? il_in->n : 0});
+        next->cur[i] = (char)(1 - k);
+        next->base[i] = keep[i];
+        samples += (double)(n_old[i] + cnt[i] - keep[i]);
+    }
+    if (runs.empty()) return NHANS_OK;
+    int rc = ws_reserve(c, ws_size(runs.size(), sizeof(HoldRun))); if (rc) return rc;
+    HoldRun* runs_dev = ws_take<HoldRun>(c, runs.size());
+    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(HoldRun), s); if (rc) return rc;
+    Prof pr(c, s, "live_hold");
+    launch_hold("live_hold", runs_dev, (int)runs.size(), s);
+    pr.done(0, 8.0 * samples);
+    return NHANS_OK;
+}
+
 // One push, per slot: inoff / outoff are the slots' counts and room -- and, for a mono object, where their pieces are;
 // il_in / il_out (an interleaved object; both or neither): where they are in the caller's frames instead.
 int live_push_body(nhans_live* o, const char* fn_, const void* in, const int64_t* inoff, const int* end, void* out,
@@ -162,12 +215,22 @@ int live_push_body(nhans_live* o, const char* fn_, const void* in, const int64_t
     nhans_ctx* c = o->c;
     const int S = o->S;
     std::vector<int64_t> moff(S + 1, 0), ooff(S + 1, 0);
+    std::vector<int64_t> keep, n_old, cnts, pos;         // (full band only)
+    if (o->fb.on) { keep.assign(S, -1); n_old = o->in.st.N; cnts.assign(S, 0); pos.assign(S, 0); }
     int64_t tin = 0, tout = 0;
     for (int i = 0; i < S; ++i) {
         const int64_t cnt = inoff[i + 1] - inoff[i];
         const bool en = end && end[i];
         const int rc = live_check_push(o, fn_, i, cnt, en); if (rc) return rc;
         const LivePlan p = live_plan(o, i, cnt, en);
+        if (o->fb.on) {
+            cnts[i] = cnt;
+            pos[i] = il_in ? il_in->base[i] : inoff[i];
+            if (cnt > 0 && !en) {        // (an ended stream emits nothing more: its hold is not read again)
+                keep[i] = std::min(p.En, n_old[i] + cnt);
+                if (n_old[i] + cnt - keep[i] > o->fb.H) return fail(NHANS_EINVAL, fn + ": internal state bound");
+            }
+        }
         if (outoff[i + 1] - outoff[i] < p.En - p.Eo)
             return fail(NHANS_EINVAL, fn + ": output room of slot " + std::to_string(i) + " is " +
                                       std::to_string(outoff[i + 1] - outoff[i]) + " samples, " +
@@ -197,11 +260,27 @@ int live_push_body(nhans_live* o, const char* fn_, const void* in, const int64_t
     }
     const bool auto_wet = o->lv.on && o->lv.auto_wet;
     const GainTab gains{o->lv.wtab, woff.data()};
-    rc = stage_push(c, o->out, "live_out", {true, o->out_format, 0, o->wet, o->out_scale, auto_wet, il_out != nullptr}, o->den,
-                    auto_wet || o->wet != 0.f ? o->mix : nullptr, ooff.data(), end, out, outoff, counts, s, auto_wet ? &gains : nullptr,
-                    il_out);
+    // (nor does an object that never enabled its full band take the ones here)
+    FullBand::Slots fb_next;
+    std::vector<const float*> halves;
+    HighBandIo hb{};
+    if (o->fb.on) {
+        rc = live_hold(o, in, pos.data(), il_in, keep.data(), n_old.data(), cnts.data(), s, &fb_next);
+        if (rc || launch_error_pending()) { o->in.restore(was_in); online_undo(o->on); o->can_rewind = false; return rc; }
+        for (int i = 0; i < S; ++i) halves.push_back(o->fb_half(o->fb.st.cur[i], i));
+        hb = {o->fb.gain.data(), halves.data(), o->fb.st.base.data(), n_old.data(), cnts.data(), pos.data(), in, o->in_format,
+              il_in ? il_in->ch : 0, il_in ? il_in->n : 0, o->in_denom};
+    }
+    rc = stage_push(c, o->out, "live_out",
+                    {true, o->out_format, 0, o->wet, o->out_scale, auto_wet, il_out != nullptr, o->fb.on}, o->den,
+                    auto_wet || o->wet != 0.f || o->fb.on ? o->mix : nullptr, ooff.data(), end, out, outoff, counts, s,
+                    auto_wet ? &gains : nullptr, il_out, o->fb.on ? &hb : nullptr);
     if (rc || launch_error_pending()) { o->in.restore(was_in); online_undo(o->on); o->can_rewind = false; return rc; }
     o->undo_in = was_in; o->undo_out = was_out;
+    if (o->fb.on) {
+        o->undo_fb = o->fb.st;
+        o->fb.st = fb_next;
+    }
     if (o->lv.on) {
         o->undo_lv = o->lv.st;
         o->lv.st = lv_next;
@@ -307,6 +386,7 @@ void live_free(nhans_live* o) {
     for (float* p : {o->mid, o->den, o->mix, o->lv.wtab})
         if (p) (void)hipFree(p);
     if (o->lv.state) (void)hipFree(o->lv.state);
+    if (o->fb.hold) (void)hipFree(o->fb.hold);
     delete o;
 }
 
@@ -417,6 +497,7 @@ int nhans_live_restart(nhans_live* o, int slot) {
     online_restart_slot(o->on, slot);
     o->in.restart(slot); o->out.restart(slot);
     if (o->lv.on) { o->lv.st.h0[slot] = 0; o->lv.woff.clear(); }     // (hop 0 reads none of the carried level state)
+    if (o->fb.on) o->fb.st.base[slot] = 0;                           // (a stream of 0 samples has none in its hold)
     o->can_rewind = false;
     return NHANS_OK;
 }
@@ -503,6 +584,7 @@ int nhans_live_rewind(nhans_live* o) {
     online_undo(o->on);
     o->out.restore(o->undo_out);
     if (o->lv.on) { o->lv.st = o->undo_lv; o->lv.woff.clear(); }
+    if (o->fb.on) o->fb.st = o->undo_fb;
     o->can_rewind = false;
     return NHANS_OK;
 }
@@ -648,6 +730,140 @@ int nhans_level_gains(nhans_ctx* c, const float* den, const float* mix, const in
     launch_level("level_gains", runs_dev, (int)runs.size(), call.s);
     pr.done(9.0 * n, 8.0 * n + 4.0 * (double)hops);
     return call.finish(NHANS_OK);
+}
+
+// ---- full-band output (include/nhans_hip.h: nhans_fullband_*) ----
+namespace {
+static bool fullband_rate(int r) {
+    for (int v : {22050, 24000, 32000, 44100, 48000, 88200, 96000})
+        if (v == r) return true;
+    return false;
+}
+
+// H(r): the most input samples a running stream has without their output.  N - emitted(N) repeats every 20 ms of input
+// (r / 50 samples bring 320 at 16 kHz, one pair of hops, and r / 50 outputs) once the first pair has come out, before
+// 0.23 s: one second of N covers it for every look-ahead.
+static int64_t fullband_hold(int rate) {
+    static std::map<int, int64_t> cache;    // (a handful of ints; lives as long as the process)
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    int64_t& H = cache[rate];
+    if (H) return H;
+    const ResampleFilter *fi = resample_filter(rate, 16000), *fo = resample_filter(16000, rate);
+    for (int L = 0; L <= kCenter; ++L)
+        for (int64_t n = 0; n <= rate; ++n) {
+            const int64_t n16 = resample_emitted(*fi, n, false);
+            H = std::max(H, n - resample_emitted(*fo, on_emitted(nhans_num_frames(n16), false, L), false));
+        }
+    return H;
+}
+}  // namespace
+
+int64_t nhans_fullband_hold_samples(int rate) {
+    if (!fullband_rate(rate))
+        return fail(NHANS_EINVAL, "nhans_fullband_hold_samples: " + std::to_string(rate) + " Hz is not a full-band rate (22050, 24000, "
+                                  "32000, 44100, 48000, 88200 or 96000 Hz)");
+    return fullband_hold(rate);
+}
+
+int nhans_fullband_live_enable(nhans_live* o, void* stream) {
+    const std::string fn = "nhans_fullband_live_enable";
+    if (!o) return fail(NHANS_EINVAL, fn + ": null object");
+    Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    if (o->fb.on) return call.finish(NHANS_OK);
+    const int rate_in = o->in.f->rate_in, rate_out = o->out.f->rate_out;
+    if (rate_in != rate_out)
+        return call.finish(fail(NHANS_EINVAL, fn + ": the rates differ (" + std::to_string(rate_in) + " Hz in, " + std::to_string(rate_out) +
+                                              " Hz out): the input's high band lines up with an output of its own rate only"));
+    if (rate_in <= 16000 || !fullband_rate(rate_in))
+        return call.finish(fail(NHANS_EINVAL, fn + ": " + std::to_string(rate_in) + " Hz has no band above the 16 kHz path's (22050 Hz and more)"));
+    if (!o->has_wet)
+        return call.finish(fail(NHANS_EINVAL, fn + ": the object was opened without NHANS_LIVE_WET (the high band is the input less "
+                                              "its mixed round trip)"));
+    for (int i = 0; i < o->S; ++i)
+        if (o->in.st.N[i] != 0 || o->in.st.ended[i] || o->on->st[i].N != 0 || o->out.st.N[i] != 0)
+            return call.finish(fail(NHANS_EINVAL, fn + ": slot " + std::to_string(i) + " has a stream under way (enable after open, or "
+                                                  "after nhans_live_restart of every slot that has taken samples)"));
+    const int64_t H = fullband_hold(rate_in);
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->fb.hold), (size_t)2 * o->S * (size_t)H * sizeof(float));
+    if (e != hipSuccess) return call.finish(fail(NHANS_ENOMEM, fn + ": hipMalloc failed: " + hipGetErrorString(e)));
+    // (nothing is cleared: a stream of 0 samples has none in its hold)
+    o->fb.H = H;
+    o->fb.gain.assign(o->S, 1.f);
+    o->fb.st.cur.assign(o->S, 0);
+    o->fb.st.base.assign(o->S, 0);
+    o->fb.on = true;
+    o->can_rewind = false;
+    return call.finish(NHANS_OK);
+}
+
+int nhans_fullband_live_set_gain(nhans_live* o, int slot, double gain) {
+    const char* fn = "nhans_fullband_live_set_gain";
+    if (!o) return fail(NHANS_EINVAL, std::string(fn) + ": null object");
+    if (!o->fb.on) return fail(NHANS_EINVAL, std::string(fn) + ": the full band is not enabled (nhans_fullband_live_enable)");
+    if (slot != -1) { const int rc = slot_check(o->S, slot, fn); if (rc) return rc; }
+    if (!std::isfinite(gain) || gain < 0.0 || gain > 4.0) return fail(NHANS_EINVAL, std::string(fn) + ": the gain must be finite, in [0, 4]");
+    for (int i = 0; i < o->S; ++i)
+        if (slot == -1 || slot == i) o->fb.gain[i] = (float)gain;
+    o->can_rewind = false;
+    return NHANS_OK;
+}
+
+int nhans_fullband_mix(nhans_ctx* c, const void* x, int x_format, const int64_t* xoff, const float* den, const float* mix,
+                       const int64_t* off, int nclips, int rate, double in_denom, double wet, const float* wet_hops, double gain,
+                       double out_scale, int out_format, void* out, const int64_t* outoff, void* stream) {
+    const std::string fn = "nhans_fullband_mix";
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    if (!xoff || !off || !outoff || nclips < 0) return call.finish(fail(NHANS_EINVAL, fn + ": null argument"));
+    for (int fmt : {x_format, out_format})
+        if (fmt != kResampleInt16 && fmt != kResampleFloat32)
+            return call.finish(fail(NHANS_EINVAL, fn + ": x_format and out_format must be NHANS_PCM_INT16 or NHANS_PCM_FLOAT32"));
+    if (!fullband_rate(rate))
+        return call.finish(fail(NHANS_EINVAL, fn + ": " + std::to_string(rate) + " Hz is not a full-band rate (22050, 24000, 32000, 44100, "
+                                              "48000, 88200 or 96000 Hz)"));
+    if (!(in_denom > 0.0) || !std::isfinite(in_denom)) return call.finish(fail(NHANS_EINVAL, fn + ": in_denom must be finite and > 0"));
+    if (!(out_scale > 0.0) || !std::isfinite(out_scale)) return call.finish(fail(NHANS_EINVAL, fn + ": out_scale must be finite and > 0"));
+    if (!std::isfinite(wet)) return call.finish(fail(NHANS_EINVAL, fn + ": the wet factor must be finite"));
+    if (!std::isfinite(gain) || gain < 0.0 || gain > 4.0) return call.finish(fail(NHANS_EINVAL, fn + ": the gain must be finite, in [0, 4]"));
+    const ResampleFilter* f = resample_filter(16000, rate);
+    const size_t elem = rs_elem(out_format);
+    int64_t t16 = 0, tx = 0, tout = 0;
+    for (int i = 0; i < nclips; ++i) {
+        const int64_t n16 = off[i + 1] - off[i], nx = xoff[i + 1] - xoff[i];
+        if (n16 < 0 || n16 > kMaxResampleClip || nx < 0)
+            return call.finish(fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(n16) + " samples at 16 kHz and " +
+                                                  std::to_string(nx) + " at its own rate (0 ... 2^31 - 1; >= 0)"));
+        const int64_t no = resample_out_count(*f, n16);
+        if (outoff[i + 1] - outoff[i] < no)
+            return call.finish(fail(NHANS_EINVAL, fn + ": output room of clip " + std::to_string(i) + " is " +
+                                                  std::to_string(outoff[i + 1] - outoff[i]) + " samples, " + std::to_string(no) +
+                                                  " needed (nhans_resample_out_count)"));
+        t16 += n16; tx += nx; tout += no;
+    }
+    if ((t16 > 0 && (!den || !mix)) || (tx > 0 && !x) || (tout > 0 && !out)) return call.finish(fail(NHANS_EINVAL, fn + ": null buffer"));
+    std::vector<ResampleRun> runs;
+    size_t lds = 0;
+    int64_t hops = 0;
+    for (int i = 0; i < nclips; ++i) {
+        const int64_t n16 = off[i + 1] - off[i];
+        const size_t first = runs.size();
+        rs_add_runs(runs, &lds, *f, den + off[i], mix + off[i], nullptr, static_cast<char*>(out) + outoff[i] * elem, elem, nullptr, 0,
+                    (int)n16, 0, resample_out_count(*f, n16));
+        for (size_t k = first; k < runs.size(); ++k) {
+            if (wet_hops) { runs[k].wtab = wet_hops + hops; runs[k].hop0 = 0; }
+            highband_run(runs[k], (float)gain, nullptr, 0, 0, xoff[i + 1] - xoff[i], static_cast<const char*>(x) + xoff[i] * rs_elem(x_format),
+                         x_format, 0, 0, in_denom, (int64_t)(k - first) * kResampleRun);
+        }
+        hops += level_hops(n16, true);
+    }
+    if (runs.empty()) return call.finish(NHANS_OK);
+    const float* tab = nullptr;
+    int rc = rs_table(c, f, &tab); if (rc) return call.finish(rc);
+    rc = rs_launch(c, "fullband_mix", runs, tab, *f, {true, out_format, 0, (float)wet, out_scale, wet_hops != nullptr, false, true}, lds,
+                   8.0 * (double)t16, (double)tout * (elem + rs_elem(x_format)), tout, call.s);
+    return call.finish(rc);
 }
 
 void nhans_live_close(nhans_live* o) {

@@ -12,6 +12,8 @@ int rs_filter(const char* fn, int rate_in, int rate_out, const ResampleFilter** 
     return NHANS_OK;
 }
 
+}  // namespace
+
 int rs_launch(nhans_ctx* c, const char* name, const std::vector<ResampleRun>& runs, const float* tab, const ResampleFilter& f,
               const RateIo& io, size_t lds, double in_bytes, double out_bytes, int64_t out_samples, hipStream_t s) {
     if (runs.empty()) return NHANS_OK;
@@ -20,12 +22,10 @@ int rs_launch(nhans_ctx* c, const char* name, const std::vector<ResampleRun>& ru
     rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(ResampleRun), s); if (rc) return rc;
     Prof pr(c, s, name);
     launch_resample(name, runs_dev, (int)runs.size(), tab, f, io.from_mix, io.auto_wet, io.interleaved, io.pcm_format, io.quantise,
-                    io.wet, io.factor, lds, s);
+                    io.wet, io.factor, lds, s, io.highband);
     pr.done(2.0 * f.J * (double)out_samples, in_bytes + out_bytes + 4.0 * runs.size() * f.tab.size());
     return NHANS_OK;
 }
-
-}  // namespace
 
 int rs_table(nhans_ctx* c, const ResampleFilter* f, const float** tab) {
     float*& t = c->rs_tab[{f->rate_in, f->rate_out}];
@@ -64,10 +64,12 @@ void rs_add_runs(std::vector<ResampleRun>& runs, size_t* lds, const ResampleFilt
 // commit.  Where the launch did not go out (a return code, or launch_error_pending()) nothing is committed.  gains
 // (io.auto_wet): the table the runs of each stream read their hops' factors from.  il (io.interleaved): where stream i
 // sits in the frames of the PCM side -- the counts stay those of inoff, and on that side the offsets are il's, in frames
-// of il->ch elements, the run builder's step from one run's outputs to the next being one frame per output.
+// of il->ch elements, the run builder's step from one run's outputs to the next being one frame per output.  hb
+// (io.highband): what the full-band sink adds to stream i's outputs, the k-th run of a stream beginning kResampleRun
+// outputs after the one before.
 int stage_push(nhans_ctx* c, RateStage& g, const char* kernel, const RateIo& io, const void* in, const float* mix,
                const int64_t* inoff, const int* end, void* out, const int64_t* outoff, int64_t* counts, hipStream_t s,
-               const GainTab* gains, const Interleave* il) {
+               const GainTab* gains, const Interleave* il, const HighBandIo* hb) {
     std::vector<ResampleRun> runs;
     std::vector<RateStage::Span> e(g.S);
     size_t lds = 0;
@@ -90,10 +92,14 @@ int stage_push(nhans_ctx* c, RateStage& g, const char* kernel, const RateIo& io,
             if (il_src) { runs[k].src_ch = il->ch; runs[k].src_sum = il->n; }
             else { runs[k].dst_ch = il->ch; runs[k].dst_copies = il->n; }
         }
+        for (size_t k = first; hb && k < runs.size(); ++k)
+            highband_run(runs[k], hb->gain[i], hb->hold[i], hb->base[i], hb->n_old[i], hb->cnt[i],
+                         static_cast<const char*>(hb->in) + hb->pos[i] * rs_elem(hb->fmt), hb->fmt, hb->ch, hb->sum, hb->denom,
+                         e[i].Eo + (int64_t)(k - first) * kResampleRun);
         tin += cnt; tout += e[i].En - e[i].Eo;
     }
     const int rc = rs_launch(c, kernel, runs, g.tab, *g.f, io, lds, (double)tin * (io.in_elem() * (il_src ? il_src->n : 1) + (mix ? 4 : 0)),
-                             (double)tout * io.out_elem() * (il_dst ? il_dst->n : 1), tout, s);
+                             (double)tout * (io.out_elem() * (il_dst ? il_dst->n : 1) + (hb ? 4 : 0)), tout, s);
     if (rc) return rc;
     if (launch_error_pending()) return NHANS_OK;
     for (int i = 0; i < g.S; ++i) {

@@ -340,6 +340,19 @@ struct ResampleRun {
     // output i is stored into the first dst_copies of frame i.  A slot that owns channel c of its frames has src / dst
     // point at that channel of the first frame.
     int src_ch, src_sum, dst_ch, dst_copies;
+    // the full-band source and sink only (include/nhans_hip.h: nhans_fullband_*), left zero by the run builder.  The
+    // source gives e = c - hb_gain * mix[rel] where the mix sources give c (mix is then never null).  Output i of the run
+    // is output hb_m0 + i = n of the stream, and the sink stores lo + hb_gain * u[n] where the plain sinks store lo:
+    // u[n] = float32(double(x[n]) / hb_denom), x[n] the stream's own incoming sample n -- hb_hold[n - hb_base] for
+    // hb_base <= n < hb_n_old (the slot's hold half), the caller's PCM at hb_in for hb_n_old <= n < hb_n_end (sample
+    // n - hb_n_old of it: hb_fmt int16 / float32 elements, hb_ch == 0 mono, else frames of hb_ch channels of which the
+    // first hb_sum are averaged as the interleaved source does) -- and u[n] = 0 from hb_n_end on.
+    const float* hb_hold;
+    const void* hb_in;
+    long long hb_base, hb_n_old, hb_n_end, hb_m0;
+    double hb_denom;
+    float hb_gain;
+    int hb_fmt, hb_ch, hb_sum;
 };
 constexpr int kResampleRun = 1024;      // outputs per workgroup at most
 constexpr int kResampleInt16 = 0, kResampleFloat32 = 1;
@@ -350,9 +363,23 @@ size_t resample_run_lds_bytes(const ResampleFilter& f, int p0, int cnt);
 // auto_wet (from_mix only): the wet factor of a sample is its hop's entry of the run's gain table, not `wet`.
 // interleaved: the PCM side -- the source from PCM, the sink from the mix -- is frames of several channels, laid out by the
 // runs' src_ch / src_sum or dst_ch / dst_copies.
+// highband (from_mix only): the full-band source and sink, on the runs' hb_ fields.
 void launch_resample(const char* kernel, const ResampleRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
                      bool from_mix, bool auto_wet, bool interleaved, int pcm_format, int quantise, float wet, double factor,
-                     size_t lds_bytes, hipStream_t s);
+                     size_t lds_bytes, hipStream_t s, bool highband = false);
+
+// The hold of a full-band live slot: samples [e_new, n_end) of the slot's incoming stream x (float32, as the incoming
+// stage's source forms them) into `out`, sample e_new first -- sample n from old[n - base] below n_old (the half the push
+// reads), from the caller's PCM at `in` from n_old on (fmt / ch / sum as ResampleRun's hb_fmt / hb_ch / hb_sum).  One
+// workgroup per run; lanes read and write consecutive samples.
+struct HoldRun {
+    const float* old;
+    float* out;
+    const void* in;
+    long long base, n_old, e_new, n_end;
+    int fmt, ch, sum;
+};
+void launch_hold(const char* kernel, const HoldRun* runs_dev, int nruns, hipStream_t s);
 
 // peak + normalise: blocks of <= kNormBlock samples; block b belongs to a clip whose blocks are [pb0, pb0 + pbn)
 struct NormBlock {

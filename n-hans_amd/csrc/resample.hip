@@ -13,7 +13,10 @@
 // formed while the span is staged) and a sink (float32 with the optional int16 grid and fixed peak, or scaled PCM);
 // the six mono pairs in use are instantiated: int16 -> float, float32 -> float, and the fixed and the automatic mix ->
 // int16 and -> float32 -- and, for live objects that take and return interleaved frames, the same six with the PCM side
-// read from / stored into frames of several channels (InterleavedSource, InterleavedSink).
+// read from / stored into frames of several channels (InterleavedSource, InterleavedSink).  A full-band live object
+// (nhans_fullband_*) runs its outgoing stage on eight more: the four mix pairs of either layout with the source
+// wrapped in ResidualSource and the sink in HighbandSink, which add the input's own band above 8 kHz inside the launch;
+// hold_kernel keeps the input samples that have no output yet.
 #include "nhans_kernels.h"
 
 #include <cmath>
@@ -123,13 +126,25 @@ __device__ __forceinline__ float fir_chain(const float* tab_p, int L, const floa
     return acc;
 }
 
+// Sample rel of PCM at src as float32 (int16 -> float32 is exact) ...
+template <typename T>
+__device__ __forceinline__ float pcm_sample(const void* src, long long rel) {
+    return (float)static_cast<const T*>(src)[rel];
+}
+// ... and of PCM frames of ch channels at src: the mean of the first `sum` channels of frame rel (InterleavedSource below)
+template <typename T>
+__device__ __forceinline__ float frame_sample(const void* src, long long rel, int ch, int sum) {
+    const T* f = static_cast<const T*>(src) + rel * ch;
+    double acc = 0.0;
+    for (int c = 0; c < sum; ++c) acc += (double)f[c];
+    return (float)(acc / (double)sum);
+}
+
 // Source policies: sample k0 + rel of the run's stream, 0 <= rel < n_new, as float32.
-// PCM at src (int16 -> float32 is exact):
+// PCM at src:
 template <typename T>
 struct PcmSource {
-    static __device__ __forceinline__ float at(const ResampleRun& r, long long rel, float) {
-        return (float)static_cast<const T*>(r.src)[rel];
-    }
+    static __device__ __forceinline__ float at(const ResampleRun& r, long long rel, float) { return pcm_sample<T>(r.src, rel); }
 };
 // PCM frames of r.src_ch channels at src, the sample being the mean of the first r.src_sum channels of its frame as
 // channel_mean_kernel forms it: summed in double from 0.0, channel ascending, divided by double(r.src_sum), rounded to
@@ -140,10 +155,7 @@ struct PcmSource {
 template <typename T>
 struct InterleavedSource {
     static __device__ __forceinline__ float at(const ResampleRun& r, long long rel, float) {
-        const T* f = static_cast<const T*>(r.src) + rel * r.src_ch;
-        double acc = 0.0;
-        for (int c = 0; c < r.src_sum; ++c) acc += (double)f[c];
-        return (float)(acc / (double)r.src_sum);
+        return frame_sample<T>(r.src, rel, r.src_ch, r.src_sum);
     }
 };
 // d + (m - d) * w in three separately rounded float32 operations (numpy's `den + (mix - den) * factor`).  The pragma is
@@ -174,6 +186,30 @@ struct AutoMixSource {
         return mix_sample(d, r.mix[rel], r.wtab[(r.k0 + rel) / kHop - r.hop0]);
     }
 };
+
+// The full-band residual e = c - g * mix of a live session (include/nhans_hip.h: nhans_fullband_*), c what Mix gives:
+// product and difference rounded separately, as mix_sample's.  mix is read whatever the wet factor is.  What the stage
+// carries from push to push (hist / hist_out) is e, with the gain of the push that staged it.
+template <typename Mix>
+struct ResidualSource {
+    static __device__ __forceinline__ float at(const ResampleRun& r, long long rel, float wet) {
+#pragma clang fp contract(off)
+        const float c = Mix::at(r, rel, wet);
+        const float p = r.hb_gain * r.mix[rel];
+        return c - p;
+    }
+};
+
+// Sample n of a stream's own incoming signal x, for base <= n < n_end: from the slot's hold half below n_old, from the
+// caller's PCM from there on, formed as the incoming stage's source forms it (fmt: int16 / float32; ch == 0: mono, else
+// frames of ch channels, the first `sum` averaged).  The one reader of both the full-band sinks and hold_kernel.
+__device__ __forceinline__ float stream_sample(const float* hold, long long base, long long n_old, const void* in, int fmt, int ch,
+                                               int sum, long long n) {
+    if (n < n_old) return n >= base && hold ? hold[n - base] : 0.f;
+    const long long rel = n - n_old;
+    if (ch == 0) return fmt == kResampleInt16 ? pcm_sample<int16_t>(in, rel) : pcm_sample<float>(in, rel);
+    return fmt == kResampleInt16 ? frame_sample<int16_t>(in, rel, ch, sum) : frame_sample<float>(in, rel, ch, sum);
+}
 
 // Sink policies: what becomes of output i of the run, y = its chain.
 // float32, optionally rounded to the int16 grid, then float32(double(v) / factor) when factor != 0 (the fixed peak):
@@ -208,6 +244,22 @@ struct InterleavedSink {
         } else {
             for (int c = 0; c < r.dst_copies; ++c) static_cast<float*>(r.dst)[at + c] = v;
         }
+    }
+};
+
+// The full-band sink: y = lo + g * u[n] for output n = hb_m0 + i of the stream, two separately rounded operations, then
+// Inner's arithmetic and store.  u[n] = float32(double(x[n]) / hb_denom) -- FloatSink's division -- and 0 from the end
+// of the stream's input on.
+template <typename Inner>
+struct HighbandSink {
+    static __device__ __forceinline__ void put(const ResampleRun& r, int i, float lo, int quantise, double factor) {
+#pragma clang fp contract(off)
+        const long long n = r.hb_m0 + i;
+        float u = 0.f;
+        if (n < r.hb_n_end)
+            u = (float)((double)stream_sample(r.hb_hold, r.hb_base, r.hb_n_old, r.hb_in, r.hb_fmt, r.hb_ch, r.hb_sum, n) / r.hb_denom);
+        const float p = r.hb_gain * u;
+        Inner::put(r, i, lo + p, quantise, factor);
     }
 };
 
@@ -249,6 +301,14 @@ __global__ void __launch_bounds__(256) resample_kernel(const ResampleRun* __rest
     }
     if (r.hist_out)
         for (int t = tid; t < J; t += 256) r.hist_out[t] = run_sample<Src>(r, (long long)r.n_new - J + t, J, wet);
+}
+
+// One workgroup per run: x[e_new .. n_end) of a full-band slot into the half its next push reads (HoldRun).
+__global__ void __launch_bounds__(256) hold_kernel(const HoldRun* __restrict__ runs) {
+    const HoldRun r = runs[blockIdx.x];
+    const long long n = r.n_end - r.e_new;
+    for (long long t = threadIdx.x; t < n; t += 256)
+        r.out[t] = stream_sample(r.old, r.base, r.n_old, r.in, r.fmt, r.ch, r.sum, r.e_new + t);
 }
 
 __device__ __forceinline__ float block_max(float m) {
@@ -301,7 +361,7 @@ void launch_channel_mean(const float* in, int nchan, int64_t n, float* out, hipS
 
 void launch_resample(const char* kernel, const ResampleRun* runs_dev, int nruns, const float* tab_dev, const ResampleFilter& f,
                      bool from_mix, bool auto_wet, bool interleaved, int pcm_format, int quantise, float wet, double factor,
-                     size_t lds_bytes, hipStream_t s) {
+                     size_t lds_bytes, hipStream_t s, bool highband) {
     if (nruns <= 0) return;
     if (lds_bytes > (size_t)64 << 10) { note_refusal(kernel); return; }
     const int tab4 = (int)(f.tab.size() / 4);
@@ -315,7 +375,24 @@ void launch_resample(const char* kernel, const ResampleRun* runs_dev, int nruns,
              : !auto_wet ? (i16 ? resample_kernel<MixSource, InterleavedSink<int16_t>> : resample_kernel<MixSource, InterleavedSink<float>>)
                          : (i16 ? resample_kernel<AutoMixSource, InterleavedSink<int16_t>>
                                 : resample_kernel<AutoMixSource, InterleavedSink<float>>);
+    if (highband && from_mix) {
+        using Fixed = ResidualSource<MixSource>;
+        using Auto = ResidualSource<AutoMixSource>;
+        if (!interleaved)
+            fn = !auto_wet ? (i16 ? resample_kernel<Fixed, HighbandSink<PcmSink<int16_t>>> : resample_kernel<Fixed, HighbandSink<PcmSink<float>>>)
+                           : (i16 ? resample_kernel<Auto, HighbandSink<PcmSink<int16_t>>> : resample_kernel<Auto, HighbandSink<PcmSink<float>>>);
+        else
+            fn = !auto_wet ? (i16 ? resample_kernel<Fixed, HighbandSink<InterleavedSink<int16_t>>>
+                                  : resample_kernel<Fixed, HighbandSink<InterleavedSink<float>>>)
+                           : (i16 ? resample_kernel<Auto, HighbandSink<InterleavedSink<int16_t>>>
+                                  : resample_kernel<Auto, HighbandSink<InterleavedSink<float>>>);
+    }
     NHANS_LAUNCH(kernel, fn, dim3(nruns), dim3(256), lds_bytes, s, runs_dev, tab_dev, f.L, f.M, f.J, tab4, quantise, wet, factor);
+}
+
+void launch_hold(const char* kernel, const HoldRun* runs_dev, int nruns, hipStream_t s) {
+    if (nruns <= 0) return;
+    NHANS_LAUNCH(kernel, hold_kernel, dim3(nruns), dim3(256), 0, s, runs_dev);
 }
 
 void launch_peak_partial(const float* x, const NormBlock* blocks_dev, int nblocks, int wrap, float* partial, hipStream_t s) {

@@ -112,6 +112,12 @@ SIGNATURES = {
     "nhans_fbank_online_read": (_i64, [_vp, _int, _int, _vp, _i64, _i64p, _vp]),
     "nhans_fbank_live_attach": (_int, [_vp, _vp, _int]),
     "nhans_fbank_live_read": (_i64, [_vp, _int, _int, _vp, _i64, _i64p, _vp]),
+    # full-band live output
+    "nhans_fullband_hold_samples": (_i64, [_int]),
+    "nhans_fullband_live_enable": (_int, [_vp, _vp]),
+    "nhans_fullband_live_set_gain": (_int, [_vp, _int, _dbl]),
+    "nhans_fullband_mix": (_int, [_vp, _vp, _int, _i64p, _vp, _vp, _i64p, _int, _int, _dbl, _dbl, _vp, _dbl, _dbl, _int, _vp,
+                                  _i64p, _vp]),
     "nhans_profile_json": (_int, [_vp, _str, _size]),
     "nhans_profile_reset": (_int, [_vp]),
 }
@@ -131,6 +137,7 @@ FBANK_MAX_OUT, FBANK_MAX_SPAN = 128, 8192
 FBANK_HTK, FBANK_SLANEY = 0, 1
 FBANK_NORM_NONE, FBANK_NORM_SLANEY = 0, 1
 FBANK_MIXED = 1
+FULLBAND_RATES = (22050, 24000, 32000, 44100, 48000, 88200, 96000)
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25
 ABI_VERSION = 5

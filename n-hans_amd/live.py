@@ -66,6 +66,49 @@ def level_gains(engine, den, mix, window_hops=200, wmax=1.0, sums=False):
     return (gains, s) if sums else gains
 
 
+def fullband_hold(rate):
+    """nhans_fullband_hold_samples: H(rate), the input samples a full-band slot keeps at most while their output is
+    still to come."""
+    return hip.check(hip.load().nhans_fullband_hold_samples(int(rate)))
+
+
+def fullband_mix(engine, x, den, mix, rate, in_denom, wet=0.0, gain=1.0, out_dtype=np.int16, out_scale=1.0, wet_hops=None):
+    """The whole-clip twin of a full-band live session (nhans_fullband_mix: the kernels of its ended streams).  x: the
+    recording at `rate` (int16 or float32; one array or a list), den / mix its final 16 kHz denoised and mixed-round-trip
+    samples, in_denom the divisor the 16 kHz path normalised by (peak + 1e-6).  Returns
+    y = R(c - gain * mix) + gain * float32(x / in_denom) per clip as out_dtype through the outgoing sink's arithmetic
+    (times out_scale, rounded and clipped for int16), c = den + (mix - den) * wet -- or, with wet_hops, one factor per
+    160-sample hop of each clip (level_gains' arrays) -- and R the conversion 16 kHz -> rate: resample.out_count(len(den),
+    16000, rate) samples, the first aligned with x[0]."""
+    single = isinstance(den, np.ndarray) and den.ndim == 1
+    xs, dens, mixes = ([x], [den], [mix]) if single else (list(x), list(den), list(mix))
+    hops = None if wet_hops is None else ([wet_hops] if single else list(wet_hops))
+    if not (len(xs) == len(dens) == len(mixes)) or any(len(d) != len(m) for d, m in zip(dens, mixes)):
+        raise ValueError("fullband_mix: x, den and mix are the same clips, den and mix sample for sample")
+    if hops is not None and [len(h) for h in hops] != [level_hops(len(d), True) for d in dens]:
+        raise ValueError("fullband_mix: wet_hops holds one factor per hop of 160 samples of each clip")
+    x_dtype = np.dtype(np.int16) if all(np.asarray(v).dtype == np.int16 for v in xs) else np.dtype(np.float32)
+    out_dtype = np.dtype(out_dtype)
+    lib, mem = hip.load(), context.Mem(engine)
+    xf, xoff = context.flat(xs, x_dtype)
+    d, off = context.flat(dens)
+    m, _ = context.flat(mixes)
+    ooff = context.offsets(hip.check(lib.nhans_resample_out_count(len(v), spec.FS, int(rate))) for v in dens)
+    bufs = [mem.up(xf), mem.up(d), mem.up(m), mem.empty(ooff[-1], out_dtype)]
+    if hops is not None:
+        bufs.append(mem.up(context.flat(hops)[0]))
+    try:
+        hip.check(lib.nhans_fullband_mix(engine.handle, mem.p(bufs[0]), resample._format(x_dtype), hip.i64_array(xoff), mem.p(bufs[1]),
+                                         mem.p(bufs[2]), hip.i64_array(off), len(dens), int(rate), float(in_denom), float(wet),
+                                         mem.p(bufs[4]) if hops is not None else None, float(gain), float(out_scale),
+                                         resample._format(out_dtype), mem.p(bufs[3]), hip.i64_array(ooff), mem.stream()))
+        y = np.array(mem.down(bufs[3], ooff[-1], out_dtype), dtype=out_dtype)
+    finally:
+        mem.free(*bufs)
+    out = [y[ooff[i]:ooff[i + 1]].copy() for i in range(len(dens))]
+    return out[0] if single else out
+
+
 def downmix(frames):
     """The sample a downmix session forms from each interleaved frame (include/nhans_hip.h, NHANS_INTERLEAVED_DOWNMIX):
     frames [n, C] (or [n]: one channel) -> float32 [n], float32((sum_c float64(frames[k, c])) / float64(C)) with the sum
@@ -171,6 +214,21 @@ class LiveSession(online.Slots):
     def set_wet(self, w):
         """The wet factor of the pushes that follow (non-zero needs wet=True at construction)."""
         hip.check(self.lib.nhans_live_set_wet(self.handle, float(w)))
+
+    # ---- full-band output (include/nhans_hip.h: nhans_fullband_*) -------------------------------
+    def enable_fullband(self):
+        """The band above 8 kHz, which the 16 kHz path cannot carry, comes from the input itself: every slot keeps the
+        input samples that have no output yet, and each output sample gets gain * (input - its own trip through 16 kHz)
+        added, aligned sample for sample (needs in_rate == out_rate > 16000, wet=True and slots that have taken no sample
+        yet; idempotent).  The gain starts at 1.0 for every slot; one small launch more per push.  With set_wet(1.0) and
+        gain 1.0 an int16 session on its default scale returns its input.  In "downmix" mode the high band is that of the
+        downmix, on every output channel; a high band per channel needs "split"."""
+        hip.check(self.lib.nhans_fullband_live_enable(self.handle, self.mem.stream()))
+
+    def set_highband(self, g, slot=None):
+        """The high-band gain, 0 .. 4, of `slot` (None: of every slot) for the pushes that follow; 0 is the output of a
+        session without the feature."""
+        hip.check(self.lib.nhans_fullband_live_set_gain(self.handle, -1 if slot is None else int(slot), float(g)))
 
     # ---- level meter and automatic compensation (include/nhans_hip.h: nhans_level_*) -----------
     def enable_levels(self):

@@ -133,11 +133,12 @@ def decode_pcm(samples):
     raise ValueError("unsupported sample format %s" % x.dtype)
 
 
-def front_end(engine, samples, rate, base=BASE):
+def front_end(engine, samples, rate, base=BASE, return_peak=False):
     """The file front end on the device: what apply.normalise(apply.read_wav_any(file)) computes on the host.  The
     channels are the clips of one ragged nhans_resample call (outputs on the int16 grid), nhans_channel_mean mixes
     them down, nhans_peak_normalise divides by the peak -- with the int16 abs wrap for a mono file, whose host array
-    would have been int16 -- and only the normalised float32 signal comes back."""
+    would have been int16 -- and only the normalised float32 signal comes back.  return_peak: -> (signal, peak), the
+    peak the signal was divided by (plus 1e-6), found here from one more download of the signal before the division."""
     geometry(rate, base)
     planes = decode_pcm(samples)
     C, n = planes.shape
@@ -151,9 +152,13 @@ def front_end(engine, samples, rate, base=BASE):
                                      hip.i64_array([c * no for c in range(C + 1)]), mem.stream()))
         if C > 1:
             hip.check(lib.nhans_channel_mean(engine.handle, mem.p(dout), C, no, mem.p(dout), mem.stream()))
+        peak = 0.0
+        if return_peak and no:
+            v = np.array(mem.down(dout, no), dtype=np.float32)
+            peak = float(np.max(np.where(v == -32768, v, np.abs(v)) if C == 1 else np.abs(v)))
         hip.check(lib.nhans_peak_normalise(engine.handle, mem.p(dout), hip.i64_array([0, no]), 1,
                                            hip.NORMALISE_WRAP_INT16 if C == 1 else 0, mem.p(dout), mem.stream()))
-        return mem.down(dout, no)
+        return (mem.down(dout, no), peak) if return_peak else mem.down(dout, no)
     finally:
         mem.free(din, dout)
 

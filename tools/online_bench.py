@@ -41,6 +41,13 @@ live_level kernel time of each from a profiled pass.  On a library from before t
 same-box A/B) only "never" is there and the other figures are null.
     python tools/online_bench.py --levels [--streams 1,16,64] [--hops 2] [--pushes 200] [--out F]
 
+--fullband: what the full band (nhans_fullband_*) costs a live push.  Per (S, H) one line with mode "fullband": push p50 /
+p99 of two S-slot live.LiveSession objects opened with the mixed round trip (48 kHz int16 in and out unless --in_rate
+says otherwise), the same pushes by turns -- "never" (no full-band call at all) and "enabled" (enable_fullband(), gain
+1) --, and launches_per_push and the live_in / live_out / live_hold kernel times of each from a profiled pass.  On a
+library from before the functions ($NHANS_LIB, for a same-box A/B) only "never" is there.
+    python tools/online_bench.py --fullband [--streams 1,16] [--hops 1,2] [--pushes 200] [--lookahead 2] [--out F]
+
 --interleaved: what interleaved frames (nhans_interleaved_*) cost a live push.  Per (S, H) one line with mode
 "interleaved": push p50 / p99 of three live.LiveSession objects of S SLOTS each, 48 kHz int16 in and out unless --in_rate /
 --out_rate say otherwise, the same pushes by turns -- "mono" (S mono slots), "downmix" (S stereo streams, one slot each,
@@ -390,6 +397,76 @@ def levels(a):
     return 0
 
 
+def fullband(a):
+    """--fullband: what the full band (nhans_fullband_*) costs a live push.  Per (S, H) one line with mode "fullband": push
+    p50 / p99 of two S-slot live.LiveSession objects (48 kHz int16 in and out, mixed round trip, wet 0.25) pushed by turns
+    -- "never" (no full-band call at all) and "enabled" (enable_fullband(), gain 1) --, launches per push, and the device
+    time of live_out and live_hold per push from a profiled pass of 10.  A library without the feature ($NHANS_LIB)
+    reports "never" alone."""
+    eng = engine.Engine("denoiser", precision="f16x3")
+    ca, cb = apply.normalise(synth.silent()), apply.normalise(synth.noise_context(1))
+    rate = a.in_rate or 48000
+    idx = (np.arange(int(30.0 * rate)) * float(spec.FS) / rate).astype(np.int64)
+    audio = synth.mixture(1, 30.0)[np.minimum(idx, int(30.0 * spec.FS) - 1)]
+    has = hasattr(hip.load(), "nhans_fullband_live_enable")
+    out = open(a.out, "a") if a.out else None
+    pct = lambda v, q: round(float(np.percentile(v, q)), 3) if len(v) else None
+    emb = eng.embed(eng.stft_features(torch.from_numpy(np.concatenate([ca, cb])).to(eng.device),
+                                      [0, len(ca), len(ca) + len(cb)], max_frames=spec.NOISE_WIN,
+                                      want_phase=False)[0].reshape(2, spec.NOISE_WIN, spec.BINS))
+    for S in [int(s) for s in a.streams.split(",")]:
+        for H in [int(h) for h in a.hops.split(",")]:
+            n = int(round(H * 0.010 * rate))
+            objs = {}
+            for k in ("never", "enabled") if has else ("never",):
+                o = live.LiveSession(eng, S, rate, rate, 32768, wet=True, lookahead=a.lookahead)
+                for i in range(S):
+                    o.set_embeddings(i, emb[0], emb[1])
+                o.set_wet(0.25)
+                if k == "enabled":
+                    o.enable_fullband()
+                objs[k] = o
+            pos = {k: 0 for k in objs}
+
+            def push(k):
+                i = pos[k] % (len(audio) - n)
+                pos[k] += n
+                objs[k].push([audio[i:i + n]] * S)
+
+            for k in objs:
+                for _ in range(40):
+                    push(k)
+            torch.cuda.synchronize()
+            ts = {k: [] for k in objs}
+            for _ in range(a.pushes):
+                for k in objs:
+                    ts[k].append(_timed(lambda: push(k)))
+            line = {"mode": "fullband", "streams": S, "hops_per_push": H, "push_audio_ms": H * 10, "pushes": a.pushes, "rate": rate,
+                    "lookahead": a.lookahead}
+            for k in objs:
+                eng.set_option("profile", 1)
+                eng.profile_reset()
+                for _ in range(10):
+                    push(k)
+                prof = eng.profile()
+                eng.set_option("profile", 0)
+                line["push_ms_p50_" + k] = pct(ts[k], 50)
+                line["push_ms_p99_" + k] = pct(ts[k], 99)
+                line["launches_per_push_" + k] = sum(v["calls"] for v in prof.values()) / 10
+                for name in ("live_in", "live_out", "live_hold"):
+                    line[name + "_ms_per_push_" + k] = round(prof[name]["ms"] / 10, 4) if name in prof else 0.0
+            for o in objs.values():
+                o.close()
+            line.update({"lib": os.path.basename(os.environ.get("NHANS_LIB") or "tree"), "precision": "f16x3",
+                         "weights": "synthetic seed 7"})
+            print(json.dumps(line), flush=True)
+            if out:
+                out.write(json.dumps(line) + "\n")
+                out.flush()
+    eng.close()
+    return 0
+
+
 def interleaved(a):
     eng = engine.Engine("denoiser", precision="f16x3")
     ca, cb = apply.normalise(synth.silent()), apply.normalise(synth.noise_context(1))
@@ -478,6 +555,7 @@ def main():
     ap.add_argument("--capture", action="store_true", help="cost of the sample history and of a capture (see the top of this file)")
     ap.add_argument("--captures", type=int, default=20, help="--capture: timed capture_context / set_context calls")
     ap.add_argument("--levels", action="store_true", help="cost of the level meter and the automatic wet factor (see the top of this file)")
+    ap.add_argument("--fullband", action="store_true", help="cost of the full band of a live session per push (see fullband())")
     ap.add_argument("--fbank", action="store_true", help="cost of an attached filterbank per push, and the offline kernel's bytes/s")
     ap.add_argument("--interleaved", action="store_true", help="cost of interleaved stereo frames beside mono slots (see the top of this file)")
     a = ap.parse_args()
@@ -487,6 +565,8 @@ def main():
         return fbank_cost(a)
     if a.churn:
         return churn(a)
+    if a.fullband:
+        return fullband(a)
     if a.levels:
         return levels(a)
     if a.capture:
