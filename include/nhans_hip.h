@@ -863,6 +863,44 @@ int nhans_fullband_mix(nhans_ctx* ctx, const void* x_dev, int x_format, const in
                        const float* wet_hops_dev, double gain, double out_scale, int out_format, void* out_dev,
                        const int64_t* out_offsets_host, void* stream);
 
+/* ---- Scoring against a clean target -----------------------------------------------------------------------------------
+ * How good an output is, computed where the output is: SI-SDR, SNR, segmental SNR of waveforms, and the reference's
+ * training loss and the log-spectral distance of log-magnitude rows, in double, without a sample leaving the device.  Added
+ * without moving NHANS_ABI_VERSION; a caller that may meet an older library looks the functions up by symbol.
+ *
+ * Waveform figures of an estimate e and a target t (float32, n = min(ne, nt) common samples; every operation in double):
+ *   See = sum e^2, Stt = sum t^2, Set = sum e t, Sdd = sum (e - t)^2
+ *   snr_db    = 10 log10(Stt / Sdd)
+ *   alpha     = Set / Stt,  r = fma(-alpha, t, e),  Srr = sum r^2  (a second pass over the samples, not the expanded form)
+ *   si_sdr_db = 10 log10(alpha alpha Stt / Srr);  e bit-equal to t: alpha == 1, Srr == 0, +inf
+ *   segsnr_db = mean over the frames f < nhans_num_frames(n) with Pt != 0 of clamp(10 log10(Pt / Pd), -10, 35), Pt and Pd the
+ *               sums of t^2 and (e - t)^2 over samples [160 f, 160 f + 400); Pd == 0 scores 35; a frame with Pt == 0 is
+ *               skipped and counted in frames_skipped
+ *   Edges follow IEEE and are not refused: Stt == 0 (n == 0 included) gives alpha = 0 and NaN for both dB figures, no
+ *   counted frame gives NaN for segsnr_db, non-finite samples propagate.
+ * Row figures of two [frames, 201] float32 log-magnitude tensors E and T (any rows of the library: the denoised rows of
+ * nhans_mask_net, or nhans_stft_features of two waveforms), d = E - T in double:
+ *   loss   = mean over frames of (sum_k d^2 imp[k]) / 201, imp = float32 linspace(2, 1, 201): the reference's training loss
+ *   lsd_db = mean over frames of sqrt((sum_k ((20 / ln 10) d)^2) / 201)
+ *   no frame: NaN for both.
+ * Every figure is a function of the clip pair alone: the order of each sum is fixed relative to the clip's first sample
+ * (n-hans_amd/csrc/score.hip states it), so a record has the same bits alone or in any batch, at any offset, on every run.
+ *
+ * Clip i of the estimates is est_dev[est_offsets_host[i] .. est_offsets_host[i + 1]), of the targets likewise with its own
+ * offsets.  out_dev receives NHANS_SCORE_FIELDS doubles per clip, frames_out_dev (nullable) one row of three doubles per
+ * frame, clip after clip, nhans_num_frames(n_i) rows for clip i: the waveform call writes column 0 (the frame's clamped
+ * value, NaN where the frame was skipped), the row call columns 1 and 2 (the frame's loss and lsd); each leaves the
+ * other's columns untouched.  NHANS_EINVAL, naming the clip, before anything is launched: nclips < 0, a NULL that is
+ * needed, an offset array that descends. */
+#define NHANS_SCORE_FIELDS 16   /* n, See, Stt, Set, Sdd, alpha, Srr, snr_db, si_sdr_db, segsnr_db,
+                                   frames_counted, frames_skipped, 0, 0, 0, 0 */
+#define NHANS_SCORE_ROW_FIELDS 8 /* frames, loss, lsd_db, 0 ... */
+int nhans_score_wave(nhans_ctx* ctx, const float* est_dev, const int64_t* est_offsets_host, const float* tgt_dev,
+                     const int64_t* tgt_offsets_host, int nclips, double* out_dev, double* frames_out_dev, void* stream);
+/* Clip i's rows are rows frame_offsets_host[i] .. frame_offsets_host[i + 1] of both tensors. */
+int nhans_score_rows(nhans_ctx* ctx, const float* est_rows_dev, const float* tgt_rows_dev, const int64_t* frame_offsets_host,
+                     int nclips, double* out_dev, double* frames_out_dev, void* stream);
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

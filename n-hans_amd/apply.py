@@ -63,6 +63,8 @@ class Flags(object):
     convert_on = "host"  # --convert_on gpu: format / rate conversion and normalisation of the files on the device (resample.py)
     output_rate = "16000"    # --output_rate input: the output files at the input file's rate (converted back on the device)
     highband = None      # --highband G: the input's own band above 8 kHz, times G, added to the files written at the input's rate (live.fullband_mix)
+    score_against = None # --score_against TARGET: score the files written against a clean target on the device (score.py)
+    score_out = None     # --score_out PATH.json: where the scores go (stdout otherwise)
     lookahead_ms = 10 * spec.LOOKAHEAD   # --lookahead_ms: 10 ms per frame of look-ahead (include/nhans_hip.h: "lookahead"), 170 = all 17
 
 
@@ -582,18 +584,21 @@ def apply_demo_separator(cleanpath, noisepath, save_to):
     wavwrite(save_to[:-15] + 'mixed_demo.wav', FLAGS.Fs, mix_rt)
 
 
-def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelname='nhans', step=0):
+def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelname='nhans', step=0, scores=False):
     """Evaluation-reader pipeline for one (speech, pos noise, neg noise) triple: SN/reader.py:310-420
     (eval branch, eval_stride 1) + SN/main.py:264-353.  Mixes at the reference's md5-derived SNRs,
     runs the network on frames from context_frames on, writes the reference's five wavs
     `<model>_<step>_<clean>_<pos>_<neg>_<snrp>_<snrn>_{mixed,denoised,target,posNoise,negNoise}.wav`
-    and returns the loss of SN/main.py:245-248 for this utterance."""
+    and returns the loss of SN/main.py:245-248 for this utterance.  scores=True: -> (that loss, scores): the device figures
+    (Engine.score_device / score_rows) of the denoised and of the mixed signal against the target -- waveforms as written,
+    row figures from the network's own denoised rows and the mixture's rows against the target's -- their improvement, and
+    under "rows" the three row arrays that were scored."""
     from . import mixing
     target, pos_sig, neg_sig, mixed, snr_pos, snr_neg = mixing.combine_signals(
         read_wav, cleanpath, noisepospath, noisenegpath, snrs=mixing.eval_snrs(cleanpath))
     eng = get_engine(spec.DENOISER)
-    den, mix_rt, extras, _, den_lm, _ = _enhance_after_context(eng, mixed, pos_sig, neg_sig,
-                                                               extra_wavs=(target, pos_sig, neg_sig))
+    den, mix_rt, extras, _, den_lm, mix_lm = _enhance_after_context(eng, mixed, pos_sig, neg_sig,
+                                                                    extra_wavs=(target, pos_sig, neg_sig))
     import torch
     tgt_lm, _ = eng.stft_features(torch.from_numpy(np.asarray(target, dtype=np.float32)).to(eng.device), [0, len(target)], 0, False)
     tgt_lm = tgt_lm[Noise_Win:].cpu().numpy()
@@ -605,7 +610,24 @@ def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelnam
                     ('negNoise', extras[2])):
         name = '{}_{}_{}_{}_{}_{}_{}_{}.wav'.format(modelname, step, base[0], base[1], base[2], snr_pos, snr_neg, kind)
         wavwrite(os.path.join(dump_dir, name), FLAGS.Fs, w)
+    if scores:
+        return loss, _utterance_scores(eng, den, mix_rt, extras[0], den_lm, mix_lm, tgt_lm)
     return loss
+
+
+def _utterance_scores(eng, den, mix_rt, target, den_lm, mix_lm, tgt_lm):
+    import torch
+    from . import score
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(eng.device)
+    tw, tr = dev(target), dev(tgt_lm)
+    out = {}
+    for name, wav, rows in (("denoised", den, den_lm), ("mixed", mix_rt, mix_lm)):
+        w = eng.score_device(dev(wav), [0, len(wav)], tw, [0, len(target)])
+        r = eng.score_rows(dev(rows), tr, [0, len(tgt_lm)])
+        out[name] = dict(score.record(w.cpu().numpy()[0]), **score.row_record(r.cpu().numpy()[0]))
+    out["improvement"] = score.improvement(out["mixed"], out["denoised"])
+    out["rows"] = {"denoised": den_lm, "mixed": mix_lm, "target": tgt_lm}
+    return out
 
 
 # ------------------------------------------------------------------------------ CLI
@@ -648,7 +670,28 @@ def _parse(argv, prog):
                         'denoised rows; the audio files are what they are without the flag')
     p.add_argument('--n_mels', type=int, default=80, help='bands of --fbank_out, 1 ... 128 (default 80), 0 - 8000 Hz')
     p.add_argument('--mel_scale', default='htk', choices=['htk', 'slaney'], help='mel scale of --fbank_out (default htk)')
+    p.add_argument('--score_against', default=None, metavar='TARGET',
+                   help='a clean target of the input -- a wav in file mode, a directory paired by file name in directory '
+                        'mode: the denoised file and the mixed round trip are scored against it on the device (SI-SDR, SNR, '
+                        'segmental SNR, the reference\'s loss, log-spectral distance) and the scores written as JSON; the '
+                        'audio files are what they are without the flag')
+    p.add_argument('--score_out', default=None, metavar='PATH.json', help='where the scores of --score_against go (default: stdout)')
     a = p.parse_args(argv)
+    if a.score_out is not None and a.score_against is None:
+        p.error('--score_out needs --score_against TARGET')
+    if a.score_against is not None:
+        if a.output_rate == 'input':
+            p.error('--score_against scores the 16 kHz files; it does not combine with --output_rate input')
+        if a.convert_on == 'gpu':
+            p.error('--score_against reads and scales the target on the host; it does not combine with --convert_on gpu')
+        if os.path.isdir(a.input) != os.path.isdir(a.score_against):
+            p.error('--score_against must be a directory when --input is one, and a file when it is a file')
+        if os.path.isdir(a.input):
+            for name in sorted(os.listdir(a.input)):
+                if name.lower().endswith('.wav') and not os.path.isfile(os.path.join(a.score_against, name)):
+                    p.error('--score_against: %s has no target of the same name in %s' % (name, a.score_against))
+        elif not os.path.isfile(a.score_against):
+            p.error('--score_against: %s is not a file' % a.score_against)
     if a.fbank_out is not None:
         if os.path.isdir(a.input):
             p.error('--fbank_out works on one input file; %s is a directory' % a.input)
@@ -712,11 +755,58 @@ def _run_cli_jobs(kind, a):
         _bind_rank_device()
         try:
             apply_batch(kind, jobs)
+            if getattr(a, "score_against", None) and int(os.environ.get("RANK", "0")) == 0:
+                _score_jobs(kind, a, jobs)
         finally:
             finish_distributed()
     else:
         for mixed, pos, neg, out in jobs:
             (apply_snc if kind == spec.DENOISER else apply_separator)(mixed, pos, neg, out)
+        if getattr(a, "score_against", None):
+            _score_jobs(kind, a, jobs)
+
+
+def scaled_target(mixedpath, targetpath):
+    """--score_against: the target read as the input is read (16 kHz on the host) and put on the scale the network saw
+    the input on -- multiplied by the INPUT's peak factor 1 / (max|input| + 1e-6), as the reference's mixing puts a target
+    on the mixture's scale -- float32."""
+    x = _reader()(mixedpath)
+    with np.errstate(over="ignore"):
+        peak = np.max(np.abs(x)) if len(x) else 0
+    return (_reader()(targetpath) / (peak + 0.000001)).astype(np.float32)
+
+
+def _score_jobs(kind, a, jobs):
+    """--score_against, after the files are written: per job the 16 kHz denoised file and the mixed round trip, as
+    written, against the scaled target over their common prefix, in ONE Context.score call; JSON to --score_out or
+    stdout: {"files": {input path: {"denoised", "mixed", "improvement"}}, "skipped": [...]} and, in directory mode, "mean"."""
+    import json
+    from . import score
+    directory = os.path.isdir(a.input)
+    done, skipped, est, tgt = [], [], [], []
+    for mixedpath, _, _, save_to in jobs:
+        mp = side_prefix(save_to) + 'mixed_processed.wav'
+        if not (os.path.exists(save_to) and os.path.exists(mp)):
+            skipped.append(mixedpath)                       # (reported where it was read: no output to score)
+            continue
+        t = scaled_target(mixedpath, os.path.join(a.score_against, os.path.basename(mixedpath)) if directory else a.score_against)
+        est += [wavread(save_to)[1], wavread(mp)[1]]
+        tgt += [t, t]
+        done.append(mixedpath)
+    recs = get_enhancer(kind).score(est, tgt) if est else []
+    files = {}
+    for i, path in enumerate(done):
+        den, mix = recs[2 * i], recs[2 * i + 1]
+        files[path] = {"denoised": den, "mixed": mix, "improvement": score.improvement(mix, den)}
+    out = {"files": files, "skipped": skipped}
+    if directory and files:
+        out["mean"] = {k: score.mean_of([f[k] for f in files.values()]) for k in ("denoised", "mixed", "improvement")}
+    text = json.dumps(out, indent=1, sort_keys=True)
+    if a.score_out:
+        with open(a.score_out, "w") as f:
+            f.write(text + "\n")
+    else:
+        print(text)
 
 
 def _bind_rank_device():

@@ -6,7 +6,7 @@ import warnings
 
 import numpy as np
 
-from . import hip, hiprt, spec
+from . import hip, hiprt, score as score_mod, spec
 
 
 class Context:
@@ -123,6 +123,54 @@ class Context:
             mem.free(*ins, lm, den, ctx_lm, emb, *out)
         split = [[r[foff[i]:foff[i + 1]] for i in range(n)] if r is not None else None for r in res]
         return (split[0], split[1]) if mixed else split[0]
+
+
+    # ---- scoring against a clean target (include/nhans_hip.h: nhans_score_*) ---------------------
+    def score(self, estimates, targets, per_frame=False):
+        """Lists of float32 waveforms, estimate i against target i over their common prefix -> one dict per clip: the
+        waveform figures (score.FIELDS: si_sdr_db, snr_db, segsnr_db, ...) and the row figures loss and lsd_db of the two
+        signals' own log-magnitude rows (nhans_stft_features) -- one upload, two STFTs and the two score calls on the
+        device, one download of the records.  per_frame=True: plus "per_frame", float64 [frames, 3]: each frame's clamped
+        segmental value (NaN where its target is silent), loss and lsd."""
+        if len(estimates) != len(targets):
+            raise ValueError("score: one target per estimate")
+        lib, mem, n = self.lib, Mem(self), len(estimates)
+        cut = [min(len(e), len(t)) for e, t in zip(estimates, targets)]
+        (ef, off), (tf, _) = flat([e[:k] for e, k in zip(estimates, cut)]), flat([t[:k] for t, k in zip(targets, cut)])
+        foff = offsets(int(lib.nhans_num_frames(k)) for k in cut)
+        F, nw, nr = foff[-1], hip.SCORE_FIELDS, hip.SCORE_ROW_FIELDS
+        s = mem.stream()
+        ins = [mem.up(ef), mem.up(tf)]
+        lm = [mem.empty(F * spec.BINS), mem.empty(F * spec.BINS)]
+        out = mem.empty(n * (nw + nr) + 3 * F, np.float64)
+
+        def at(doubles):
+            return ctypes.c_void_p(mem.p(out).value + 8 * doubles)
+
+        fr = at(n * (nw + nr)) if per_frame else None
+        try:
+            if n:
+                o = hip.i64_array(off)
+                if F:
+                    for x, rows in zip(ins, lm):
+                        hip.check(lib.nhans_stft_features(self.handle, mem.p(x), o, n, 0, mem.p(rows), None, s))
+                hip.check(lib.nhans_score_wave(self.handle, mem.p(ins[0]), o, mem.p(ins[1]), o, n, at(0), fr, s))
+                hip.check(lib.nhans_score_rows(self.handle, mem.p(lm[0]), mem.p(lm[1]), hip.i64_array(foff), n, at(n * nw), fr, s))
+            self._sync()
+            got = np.array(mem.down(out, n * (nw + nr) + 3 * F, np.float64), dtype=np.float64)
+        finally:
+            mem.free(*ins, *lm, out)
+        res = []
+        for i in range(n):
+            rec = score_mod.record(got[i * nw:(i + 1) * nw])
+            rec.update(score_mod.row_record(got[n * nw + i * nr:n * nw + (i + 1) * nr]))
+            if per_frame:
+                rec["per_frame"] = got[n * (nw + nr):].reshape(F, 3)[foff[i]:foff[i + 1]].copy()
+            res.append(rec)
+        return res
+
+    def _sync(self):
+        """Waits for the work issued on this context's stream (the null stream's copies wait by themselves)."""
 
 
 def redo_saturated_in_f32(eng, run, undo=None):

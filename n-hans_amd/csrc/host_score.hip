@@ -1,0 +1,112 @@
+// nhans_score_wave / nhans_score_rows (include/nhans_hip.h): the run tables and launches of score.hip.  What the two calls
+// refuse needs no device and is refused before the context is looked at.
+#include "host_internal.h"
+
+namespace {
+
+int score_offsets_check(const std::string& fn, const char* what, const int64_t* off, int nclips) {
+    for (int i = 0; i < nclips; ++i)
+        if (off[i + 1] < off[i])
+            return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + ": the " + what + " offsets descend (" +
+                                      std::to_string(off[i]) + " -> " + std::to_string(off[i + 1]) + ")");
+    return NHANS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nhans_score_wave(nhans_ctx* c, const float* est, const int64_t* eoff, const float* tgt, const int64_t* toff, int nclips,
+                     double* out, double* frames_out, void* stream) {
+    const std::string fn = "nhans_score_wave";
+    if (nclips < 0) return fail(NHANS_EINVAL, fn + ": negative clip count");
+    if (nclips > 0 && (!eoff || !toff || !out)) return fail(NHANS_EINVAL, fn + ": null offsets or null output with " + std::to_string(nclips) + " clips to score");
+    int rc = score_offsets_check(fn, "estimate", eoff, nclips); if (rc) return rc;
+    rc = score_offsets_check(fn, "target", toff, nclips); if (rc) return rc;
+    std::vector<ScoreRun> runs((size_t)nclips);
+    long long tiles = 0, segs = 0, frames = 0, samples = 0;
+    for (int i = 0; i < nclips; ++i) {
+        const int64_t n = std::min(eoff[i + 1] - eoff[i], toff[i + 1] - toff[i]);
+        if (n > 0 && (!est || !tgt))
+            return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(n) + " samples and a null buffer");
+        const int64_t nf = nhans_num_frames(n);
+        runs[i] = {n > 0 ? est + eoff[i] : nullptr, n > 0 ? tgt + toff[i] : nullptr, (long long)n, tiles, segs, frames, (long long)nf};
+        tiles += (n + kScoreTile - 1) / kScoreTile;
+        segs += (n + kScoreSegment - 1) / kScoreSegment;
+        frames += nf;
+        samples += n;
+    }
+    if (tiles > 0x7fffffffLL) return fail(NHANS_EINVAL, fn + ": too many samples for one call (split it)");
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    if (nclips == 0) return call.finish(NHANS_OK);
+    rc = ws_reserve(c, ws_size(runs.size(), sizeof(ScoreRun)) + ws_size((size_t)tiles * 4, 8) + ws_size((size_t)segs * 2, 8));
+    if (rc) return call.finish(rc);
+    ScoreRun* runs_dev = ws_take<ScoreRun>(c, runs.size());
+    double* part = ws_take<double>(c, (size_t)tiles * 4);
+    double* segp = ws_take<double>(c, (size_t)segs * 2);
+    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(ScoreRun), call.s); if (rc) return call.finish(rc);
+    const double n = (double)samples, T = (double)tiles, S = (double)segs, F = (double)frames, C = (double)nclips;
+    {   // per sample: a subtraction and four fused multiply-adds, and the tree
+        Prof pr(c, call.s, "score_pass1");
+        launch_score_tiles("score_pass1", 1, runs_dev, nclips, tiles, part, segp, nullptr, call.s);
+        pr.done(10.0 * n, 8.0 * n + 32.0 * T + 16.0 * S);
+    }
+    {
+        Prof pr(c, call.s, "score_finish");
+        launch_score_finish("score_finish", runs_dev, nclips, part, segp, out, frames_out, call.s);
+        pr.done(4.0 * T + 12.0 * F, 32.0 * T + 80.0 * F + (frames_out ? 8.0 * F : 0.0) + 8.0 * kScoreFields * C);
+    }
+    {
+        Prof pr(c, call.s, "score_pass2");
+        launch_score_tiles("score_pass2", 2, runs_dev, nclips, tiles, part, segp, out, call.s);
+        pr.done(5.0 * n, 8.0 * n + 8.0 * T);
+    }
+    {
+        Prof pr(c, call.s, "score_si_sdr");
+        launch_score_sisdr("score_si_sdr", runs_dev, nclips, part, out, call.s);
+        pr.done(T + 5.0 * C, 8.0 * T + 32.0 * C);
+    }
+    return call.finish(NHANS_OK);
+}
+
+int nhans_score_rows(nhans_ctx* c, const float* est, const float* tgt, const int64_t* foff, int nclips, double* out,
+                     double* frames_out, void* stream) {
+    const std::string fn = "nhans_score_rows";
+    if (nclips < 0) return fail(NHANS_EINVAL, fn + ": negative clip count");
+    if (nclips > 0 && (!foff || !out)) return fail(NHANS_EINVAL, fn + ": null offsets or null output with " + std::to_string(nclips) + " clips to score");
+    int rc = score_offsets_check(fn, "frame", foff, nclips); if (rc) return rc;
+    std::vector<ScoreRowRun> runs((size_t)nclips);
+    long long tiles = 0, frames = 0;
+    for (int i = 0; i < nclips; ++i) {
+        const int64_t nf = foff[i + 1] - foff[i];
+        if (nf > 0 && (!est || !tgt))
+            return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(nf) + " rows and a null buffer");
+        runs[i] = {nf > 0 ? est + foff[i] * kBins : nullptr, nf > 0 ? tgt + foff[i] * kBins : nullptr, (long long)nf, tiles, frames};
+        tiles += (nf + kScoreRowTile - 1) / kScoreRowTile;
+        frames += nf;
+    }
+    if (tiles > 0x7fffffffLL) return fail(NHANS_EINVAL, fn + ": too many rows for one call (split it)");
+    Call call(c, stream);
+    if (call.rc) return call.rc;
+    if (nclips == 0) return call.finish(NHANS_OK);
+    rc = ws_reserve(c, ws_size(runs.size(), sizeof(ScoreRowRun)) + ws_size((size_t)frames * 2, 8));
+    if (rc) return call.finish(rc);
+    ScoreRowRun* runs_dev = ws_take<ScoreRowRun>(c, runs.size());
+    double* vals = ws_take<double>(c, (size_t)frames * 2);
+    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(ScoreRowRun), call.s); if (rc) return call.finish(rc);
+    const double F = (double)frames, C = (double)nclips;
+    {   // per bin: a subtraction, three products and two fused multiply-adds
+        Prof pr(c, call.s, "score_rows");
+        launch_score_rows("score_rows", runs_dev, nclips, tiles, vals, frames_out, call.s);
+        pr.done(8.0 * kBins * F, (8.0 * kBins + 16.0 + (frames_out ? 16.0 : 0.0)) * F);
+    }
+    {
+        Prof pr(c, call.s, "score_rows_finish");
+        launch_score_rows_finish("score_rows_finish", runs_dev, nclips, vals, out, call.s);
+        pr.done(2.0 * F, 16.0 * F + 8.0 * kScoreRowFields * C);
+    }
+    return call.finish(NHANS_OK);
+}
+
+}  // extern "C"

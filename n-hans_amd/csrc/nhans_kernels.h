@@ -430,4 +430,34 @@ size_t fbank_lds_bytes(int n_out, int nspan);
 void launch_fbank(const char* kernel, const FbankRun* runs_dev, int nruns, long long ntiles, const int* table_dev, int n_out,
                   int nspan, int power, float floor, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// Scoring against a clean target (score.hip; include/nhans_hip.h: nhans_score_*).  One ScoreRun per clip pair, empty ones
+// included: n common samples at est / tgt; its tiles of kScoreTile samples are workgroups [tile0, tile0 + ceil(n /
+// kScoreTile)) of the two tile launches, its segments of kScoreSegment samples entries [seg0, seg0 + ceil(n /
+// kScoreSegment)) of the segment powers, its frames rows [frame0, frame0 + frames) of the per-frame output; tile0, seg0
+// and frame0 ascend from 0 over the runs.  One ScoreRowRun per pair of row tensors: frames rows of 201 at est / tgt, its
+// tiles of kScoreRowTile rows workgroups [tile0, ...) of the rows launch.  The finish launches: one workgroup per run.
+struct ScoreRun {
+    const float* est;
+    const float* tgt;
+    long long n, tile0, seg0, frame0, frames;
+};
+struct ScoreRowRun {
+    const float* est;
+    const float* tgt;
+    long long frames, tile0, frame0;
+};
+constexpr int kScoreSegment = 80, kScoreTile = 2560, kScoreRowTile = 16, kScoreFields = 16, kScoreRowFields = 8;
+// part: [tiles][4] doubles (pass 2 writes column 0 only); segs: [segments][2] = Pt, Pd; rec: [runs][kScoreFields]
+void launch_score_tiles(const char* kernel, int pass, const ScoreRun* runs_dev, int nruns, long long ntiles, double* part,
+                        double* segs, const double* rec, hipStream_t s);
+void launch_score_finish(const char* kernel, const ScoreRun* runs_dev, int nruns, const double* part, const double* segs,
+                         double* rec, double* frames_out, hipStream_t s);
+void launch_score_sisdr(const char* kernel, const ScoreRun* runs_dev, int nruns, const double* part, double* rec, hipStream_t s);
+// vals: [rows][2] = loss_f, lsd_f; rec: [runs][kScoreRowFields]
+void launch_score_rows(const char* kernel, const ScoreRowRun* runs_dev, int nruns, long long ntiles, double* vals,
+                       double* frames_out, hipStream_t s);
+void launch_score_rows_finish(const char* kernel, const ScoreRowRun* runs_dev, int nruns, const double* vals, double* rec,
+                              hipStream_t s);
+
 }  // namespace nhans

@@ -5,7 +5,7 @@ import os
 
 import torch
 
-from . import context, fold, hip, spec, weights as weights_mod
+from . import context, fold, hip, score as score_mod, spec, weights as weights_mod
 
 
 class Engine(context.Context):
@@ -147,6 +147,48 @@ class Engine(context.Context):
         out = torch.empty((rows_t.shape[0], fb.n_mels), dtype=torch.float32, device=self.device)
         hip.check(self.lib.nhans_fbank_rows(fb.handle(self), hip.ptr(rows_t), rows_t.shape[0], hip.ptr(out), self._stream()))
         return out
+
+    # ---- scoring against a clean target (include/nhans_hip.h: nhans_score_*) ----------------------
+    def score_device(self, est_t, est_off, tgt_t, tgt_off, per_frame=False):
+        """Waveform figures of clips already in HBM: estimate i = est_t[est_off[i]:est_off[i + 1]] against target i of
+        tgt_t / tgt_off, over their common prefix -> device tensor float64 [n, hip.SCORE_FIELDS] (score.FIELDS names the
+        columns); per_frame=True: -> (that, float64 [sum frames, 3] whose column 0 holds each frame's clamped segmental
+        value, NaN where the frame was skipped; columns 1 - 2 are score_rows' and stay as they were allocated: NaN)."""
+        n = len(est_off) - 1
+        if len(tgt_off) - 1 != n:
+            raise ValueError("score_device: one target per estimate")
+        for t in (est_t, tgt_t):
+            if t.dtype != torch.float32 or t.dim() != 1:
+                raise ValueError("score_device: flat float32 tensors")
+        out = torch.empty((n, hip.SCORE_FIELDS), dtype=torch.float64, device=self.device)
+        fr = None
+        if per_frame:
+            F = sum(int(self.lib.nhans_num_frames(min(est_off[i + 1] - est_off[i], tgt_off[i + 1] - tgt_off[i]))) for i in range(n))
+            fr = torch.full((F, 3), float("nan"), dtype=torch.float64, device=self.device)
+        hip.check(self.lib.nhans_score_wave(self.handle, hip.ptr(est_t.contiguous()), hip.i64_array(est_off),
+                                            hip.ptr(tgt_t.contiguous()), hip.i64_array(tgt_off), n, hip.ptr(out), hip.ptr(fr),
+                                            self._stream()))
+        return (out, fr) if per_frame else out
+
+    def score_rows(self, est_rows_t, tgt_rows_t, frame_off, per_frame=False, frames_out=None):
+        """Row figures of two float32 [rows, 201] device tensors, clip i = rows frame_off[i]:frame_off[i + 1] of both ->
+        device tensor float64 [n, hip.SCORE_ROW_FIELDS] (score.ROW_FIELDS); per_frame=True: -> (that, float64 [rows, 3] with
+        columns 1 - 2 = each frame's loss and lsd; frames_out: score_device's tensor, completed in place)."""
+        for t in (est_rows_t, tgt_rows_t):
+            if t.dim() != 2 or t.shape[1] != spec.BINS or t.dtype != torch.float32:
+                raise ValueError("score_rows: float32 [n, %d] tensors" % spec.BINS)
+        n = len(frame_off) - 1
+        out = torch.empty((n, hip.SCORE_ROW_FIELDS), dtype=torch.float64, device=self.device)
+        fr = frames_out
+        if per_frame and fr is None:
+            fr = torch.full((int(frame_off[-1]), 3), float("nan"), dtype=torch.float64, device=self.device)
+        hip.check(self.lib.nhans_score_rows(self.handle, hip.ptr(est_rows_t.contiguous()), hip.ptr(tgt_rows_t.contiguous()),
+                                            hip.i64_array(frame_off), n, hip.ptr(out), hip.ptr(fr) if per_frame else None,
+                                            self._stream()))
+        return (out, fr) if per_frame else out
+
+    def _sync(self):
+        torch.cuda.current_stream(self.device).synchronize()
 
     # ---- whole path -------------------------------------------------------------------------
     def enhance_device(self, mix_t, mix_off, ca_t, ca_off, cb_t, cb_off, want_mixed=False, taps=False):

@@ -118,6 +118,9 @@ SIGNATURES = {
     "nhans_fullband_live_set_gain": (_int, [_vp, _int, _dbl]),
     "nhans_fullband_mix": (_int, [_vp, _vp, _int, _i64p, _vp, _vp, _i64p, _int, _int, _dbl, _dbl, _vp, _dbl, _dbl, _int, _vp,
                                   _i64p, _vp]),
+    # scoring against a clean target
+    "nhans_score_wave": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _vp, _vp, _vp]),
+    "nhans_score_rows": (_int, [_vp, _vp, _vp, _i64p, _int, _vp, _vp, _vp]),
     "nhans_profile_json": (_int, [_vp, _str, _size]),
     "nhans_profile_reset": (_int, [_vp]),
 }
@@ -138,6 +141,8 @@ FBANK_HTK, FBANK_SLANEY = 0, 1
 FBANK_NORM_NONE, FBANK_NORM_SLANEY = 0, 1
 FBANK_MIXED = 1
 FULLBAND_RATES = (22050, 24000, 32000, 44100, 48000, 88200, 96000)
+SCORE_FIELDS, SCORE_ROW_FIELDS = 16, 8
+SCORE_TILE = 2560                           # samples per workgroup of score.hip (kScoreTile)
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25
 ABI_VERSION = 5
