@@ -901,6 +901,40 @@ int nhans_score_wave(nhans_ctx* ctx, const float* est_dev, const int64_t* est_of
 int nhans_score_rows(nhans_ctx* ctx, const float* est_rows_dev, const float* tgt_rows_dev, const int64_t* frame_offsets_host,
                      int nclips, double* out_dev, double* frames_out_dev, void* stream);
 
+/* Mixing at a chosen SNR on the device: the rule of the reference's demo and evaluation readers (n-hans_amd/mixing.py:
+ * domixing, domixing_separator), bit for bit, so that a corpus can be mixed, enhanced and scored without its audio
+ * leaving HBM (n-hans_amd/csrc/mix.hip).  Inputs are float32 and finite: a speech clip s of
+ * n >= 1 samples, a noise a to KEEP and a noise b to DROP of ma, mb >= 1 samples, and an SNR for each.
+ *   fit      A[i] = a[i mod ma] where ma < n, else a[i], for i < n; B likewise
+ *   power    sq[i] = float32(x[i] x[i]); S = ((0.0 + double(sq[0])) + double(sq[1])) + ..., one dependent chain of float64
+ *            additions in index order (the chain is part of the definition); P = S / double(n)
+ *   gain     f = nhans_mix_snr_factor(snr_db) = pow(10.0, -snr_db / 10.0), the C library's on the HOST;
+ *            g = sqrt((P_s / P_noise) f) in double, 1 where P_noise == 0; g32 = float32(g)
+ *   raw      raw[i] = (s[i] + g32a A[i]) + g32b B[i]: two float32 products and two float32 sums, each rounded on its own;
+ *            without a keep noise (index -1: the separator's two-way mix) raw[i] = s[i] + g32b B[i]
+ *   finish   pk = max |raw|, p = float32(pk + 1e-6f), mixture[i] = raw[i] / p;
+ *            unit = float32(float32(pk / p) + 1e-6f): the peak of the normalised mixture plus 1e-6;
+ *            target = (s + g32a A) / unit, keep = g32a A / unit, drop = g32b B / unit -- divided by about 1, not by p: the
+ *            reference's quirk.  Without a keep noise target = s / unit and keep is zeros.
+ *   record   NHANS_MIX_FIELDS doubles: P_s, P_keep, P_drop, g_keep, g_drop, pk, unit, 0 (P_keep = 0 and g_keep = 1 without
+ *            a keep noise)
+ *   An all-zero mixture gives p = 1e-6f and zeros, P_s == 0 the gain 0; non-finite samples: unspecified.
+ * Speech clip i is speech_dev[speech_offsets_host[i] .. [i + 1]), noise clip i likewise in its own buffer.  Job j mixes
+ * speech clip speech_idx_host[j] with the noises keep_idx_host[j] (-1: none; a NULL array: none for every job) and
+ * drop_idx_host[j] at snr_keep_host[j] and snr_drop_host[j] dB, so that one triple serves many SNR pairs; its outputs
+ * are elements out_offsets_host[j] .. [j + 1] of every output buffer, which must hold its n samples.  target_dev,
+ * keep_dev, drop_dev and records_dev are nullable.  A power is computed once per distinct (clip, fitted length) of a
+ * call.  NHANS_EINVAL, naming the job, before anything is launched: njobs < 0, a NULL that is needed, an index out of
+ * range, a speech or noise clip of no samples, outputs too short. */
+#define NHANS_MIX_FIELDS 8
+/* (host only; an int with an output argument like every other call of this header that can refuse) */
+int nhans_mix_snr_factor(double snr_db, double* factor_out);
+int nhans_mix(nhans_ctx* ctx, const float* speech_dev, const int64_t* speech_offsets_host, int nspeech, const float* noise_dev,
+              const int64_t* noise_offsets_host, int nnoise, const int* speech_idx_host, const int* keep_idx_host,
+              const int* drop_idx_host, const double* snr_keep_host, const double* snr_drop_host, int njobs, float* mixture_dev,
+              float* target_dev, float* keep_dev, float* drop_dev, const int64_t* out_offsets_host, double* records_dev,
+              void* stream);
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

@@ -563,28 +563,54 @@ def _enhance_after_context(eng, mix_wav, ctx_a_wav, ctx_b_wav, extra_wavs=()):
     return den_wav.cpu().numpy(), mix_rt.cpu().numpy(), extras, logits.cpu().numpy(), den.cpu().numpy(), lm_s.cpu().numpy()
 
 
-def apply_demo(speechpath, pospath, negpath, save_to):
+def _mixed_signals(mix_on, eng, cleanpath, pospath, negpath, snrs=None):
+    """mixing.combine_signals on the host (mix_on="host": the code as it always ran) or with the mixing itself on the
+    device (mix_on="gpu": Context.mix, the same bits)."""
+    from . import mixing
+    if mix_on == "host":
+        return mixing.combine_signals(read_wav, cleanpath, pospath, negpath, snrs=snrs)
+    if mix_on != "gpu":
+        raise ValueError("mix_on: 'host' or 'gpu', not %r" % (mix_on,))
+    clean, pos, neg = mixing.read_triple(read_wav, cleanpath, pospath, negpath)
+    snr_pos, snr_neg = (mixing.SNRS_DENOISER[1], mixing.SNRS_DENOISER[1]) if snrs is None else snrs
+    sig, _ = eng.mix([clean], [pos, neg], [(0, 0, 1, snr_pos, snr_neg)])
+    return (sig["target"][0], sig["keep"][0], sig["drop"][0], sig["mixture"][0], np.array(snr_pos, dtype=np.int32),
+            np.array(snr_neg, dtype=np.int32))
+
+
+def apply_demo(speechpath, pospath, negpath, save_to, mix_on="host"):
     """Denoiser demo (SN/apply.py:212-336): mix clean speech with a positive and a negative noise
     at 0 dB each, condition on the first 200 frames of the two (scaled) noises, enhance the rest.
-    Writes save_to and save_to[:-15] + 'mixed_demo.wav'."""
-    from . import mixing
-    _, pos_sig, neg_sig, mixed, _, _ = mixing.combine_signals(read_wav, speechpath, pospath, negpath)
-    den, mix_rt, _, _, _, _ = _enhance_after_context(get_engine(spec.DENOISER), mixed, pos_sig, neg_sig)
+    Writes save_to and save_to[:-15] + 'mixed_demo.wav'.  mix_on="gpu": the mixing on the device (the same files)."""
+    eng = get_engine(spec.DENOISER)
+    _, pos_sig, neg_sig, mixed, _, _ = _mixed_signals(mix_on, eng, speechpath, pospath, negpath)
+    den, mix_rt, _, _, _, _ = _enhance_after_context(eng, mixed, pos_sig, neg_sig)
     wavwrite(save_to, FLAGS.Fs, den)
     wavwrite(save_to[:-15] + 'mixed_demo.wav', FLAGS.Fs, mix_rt)
 
 
-def apply_demo_separator(cleanpath, noisepath, save_to):
+def apply_demo_separator(cleanpath, noisepath, save_to, mix_on="host"):
     """Separator demo (SS/apply.py:179-285): mix two speakers at 0 dB; contexts are the first 200
-    frames of the interferer (noise*K -> noisecontextph) and of the target (clean -> cleancontextph)."""
+    frames of the interferer (noise*K -> noisecontextph) and of the target (clean -> cleancontextph).  mix_on="gpu": the
+    mixture and the gain K from the device (Context.mix, two-way), noise*K formed on the host as before."""
     from . import mixing
-    clean, noise_k, mixed, _ = mixing.combine_signals_separator(read_wav, cleanpath, noisepath)
-    den, mix_rt, _, _, _, _ = _enhance_after_context(get_engine(spec.SEPARATOR), mixed, noise_k, clean)
+    eng = get_engine(spec.SEPARATOR)
+    if mix_on == "host":
+        clean, noise_k, mixed, _ = mixing.combine_signals_separator(read_wav, cleanpath, noisepath)
+    elif mix_on == "gpu":
+        clean = mixing._normalise(read_wav(cleanpath))
+        noise = mixing._normalise(read_wav(noisepath))
+        clean = clean[:-((len(clean) - spec.WIN) % spec.HOP)]     # sic: unconditional (mixing.combine_signals_separator)
+        sig, rec = eng.mix([clean], [noise], [(0, -1, 0, None, 0)])
+        mixed, noise_k = sig["mixture"][0], mixing._scaled(rec[0]["g_drop"], noise)
+    else:
+        raise ValueError("mix_on: 'host' or 'gpu', not %r" % (mix_on,))
+    den, mix_rt, _, _, _, _ = _enhance_after_context(eng, mixed, noise_k, clean)
     wavwrite(save_to, FLAGS.Fs, den)
     wavwrite(save_to[:-15] + 'mixed_demo.wav', FLAGS.Fs, mix_rt)
 
 
-def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelname='nhans', step=0, scores=False):
+def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelname='nhans', step=0, scores=False, mix_on="host"):
     """Evaluation-reader pipeline for one (speech, pos noise, neg noise) triple: SN/reader.py:310-420
     (eval branch, eval_stride 1) + SN/main.py:264-353.  Mixes at the reference's md5-derived SNRs,
     runs the network on frames from context_frames on, writes the reference's five wavs
@@ -592,11 +618,12 @@ def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelnam
     and returns the loss of SN/main.py:245-248 for this utterance.  scores=True: -> (that loss, scores): the device figures
     (Engine.score_device / score_rows) of the denoised and of the mixed signal against the target -- waveforms as written,
     row figures from the network's own denoised rows and the mixture's rows against the target's -- their improvement, and
-    under "rows" the three row arrays that were scored."""
+    under "rows" the three row arrays that were scored.  mix_on="gpu": the mixing on the device (the same files and loss).
+    A corpus at several SNR pairs in one pass: evaluate_corpus."""
     from . import mixing
-    target, pos_sig, neg_sig, mixed, snr_pos, snr_neg = mixing.combine_signals(
-        read_wav, cleanpath, noisepospath, noisenegpath, snrs=mixing.eval_snrs(cleanpath))
     eng = get_engine(spec.DENOISER)
+    target, pos_sig, neg_sig, mixed, snr_pos, snr_neg = _mixed_signals(
+        mix_on, eng, cleanpath, noisepospath, noisenegpath, snrs=mixing.eval_snrs(cleanpath))
     den, mix_rt, extras, _, den_lm, mix_lm = _enhance_after_context(eng, mixed, pos_sig, neg_sig,
                                                                     extra_wavs=(target, pos_sig, neg_sig))
     import torch
@@ -604,15 +631,117 @@ def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelnam
     tgt_lm = tgt_lm[Noise_Win:].cpu().numpy()
     imp = np.linspace(2, 1, spec.BINS, dtype=np.float32).reshape(1, spec.BINS)
     loss = float(np.mean(np.mean(np.square(den_lm - tgt_lm) * imp, axis=1)))
-    base = [os.path.basename(p)[:-4] for p in (cleanpath, noisepospath, noisenegpath)]
     os.makedirs(dump_dir, exist_ok=True)
     for kind, w in (('mixed', mix_rt), ('denoised', den), ('target', extras[0]), ('posNoise', extras[1]),
                     ('negNoise', extras[2])):
-        name = '{}_{}_{}_{}_{}_{}_{}_{}.wav'.format(modelname, step, base[0], base[1], base[2], snr_pos, snr_neg, kind)
-        wavwrite(os.path.join(dump_dir, name), FLAGS.Fs, w)
+        wavwrite(_eval_wav_path(dump_dir, modelname, step, (cleanpath, noisepospath, noisenegpath), snr_pos, snr_neg, kind),
+                 FLAGS.Fs, w)
     if scores:
         return loss, _utterance_scores(eng, den, mix_rt, extras[0], den_lm, mix_lm, tgt_lm)
     return loss
+
+
+def _eval_wav_path(dump_dir, modelname, step, triple, snr_pos, snr_neg, kind):
+    base = [os.path.basename(p)[:-4] for p in triple]
+    return os.path.join(dump_dir, '{}_{}_{}_{}_{}_{}_{}_{}.wav'.format(modelname, step, base[0], base[1], base[2], snr_pos, snr_neg, kind))
+
+
+def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None, per_frame=False, modelname='nhans', step=0):
+    """evaluate_utterance(scores=True) for a corpus in one pass.  triples: (cleanpath, pospath, negpath) each; snrs: the
+    (snr_pos, snr_neg) pairs applied to every triple (None: the triple's own mixing.eval_snrs).  The files are read,
+    normalised and trimmed on the host and uploaded once; the mixtures of all (triple, SNR pair) jobs (Engine.mix_device),
+    their STFTs, the tower over the 2 J context images, the stack over every job's frames from Noise_Win on, the iSTFTs
+    and the scoring run on the device over all jobs together, and only the records come back -- with dump_dir also the
+    five waveforms per job, written under evaluate_utterance's names.  lookahead as in Engine.enhance; a saturated f16x3
+    batch is redone in f32 as everywhere (context.redo_saturated_in_f32).
+    -> one dict per job, triple after triple: "triple", "snr_pos", "snr_neg", "loss" (the denoised rows' loss as the
+    device forms it: the "loss" of evaluate_utterance's scores, bit for bit), "denoised", "mixed", "improvement" (as
+    evaluate_utterance's scores) and "mix" (the job's mixing record); per_frame=True: plus "per_frame" in "denoised" and
+    "mixed", float64 [frames, 3] as Context.score's."""
+    from . import context, mixing, score
+    eng = get_engine(spec.DENOISER)
+    speech, noises, jobs, meta = [], [], [], []
+    for ti, triple in enumerate(triples):
+        clean, pos, neg = mixing.read_triple(read_wav, *triple)
+        t = int(eng.lib.nhans_num_frames(len(clean)))
+        if t <= Noise_Win:
+            raise ValueError("%s: the mixture has %d frames; more than %d are needed" % (triple[0], t, Noise_Win))
+        speech.append(clean)
+        noises += [pos, neg]
+        for snr_pos, snr_neg in ([mixing.eval_snrs(triple[0])] if snrs is None else snrs):
+            jobs.append((ti, 2 * ti, 2 * ti + 1, snr_pos, snr_neg))
+            meta.append({"triple": tuple(triple), "snr_pos": snr_pos, "snr_neg": snr_neg})
+    if not jobs:
+        return []
+    sp_t, sp_off = eng._dev(speech)
+    nz_t, nz_off = eng._dev(noises)
+    sig, off, mix_rec = eng.mix_device(sp_t, sp_off, nz_t, nz_off, jobs)
+    dump = dump_dir is not None
+    res = eng._with_lookahead(lookahead, lambda: context.redo_saturated_in_f32(
+        eng, lambda: _corpus_device(eng, sig, off, per_frame, dump)))
+    eng._sync()
+    mix_rec = mix_rec.cpu().numpy()
+    down = {k: v.cpu().numpy() for k, v in res["records"].items()}
+    frames = {k: v.cpu().numpy() for k, v in res["frames"].items()}
+    waves = {k: v.cpu().numpy() for k, v in res["waves"].items()}
+    roff, ooff = res["roff"], res["ooff"]
+    if dump:
+        os.makedirs(dump_dir, exist_ok=True)
+    out = []
+    for j, m in enumerate(meta):
+        r = dict(m)
+        for name in ("denoised", "mixed"):
+            r[name] = dict(score.record(down[name + "_wave"][j]), **score.row_record(down[name + "_rows"][j]))
+            if per_frame:
+                r[name]["per_frame"] = frames[name][roff[j]:roff[j + 1]].copy()
+        r["loss"] = r["denoised"]["loss"]
+        r["improvement"] = score.improvement(r["mixed"], r["denoised"])
+        r["mix"] = dict(zip(mixing.RECORD_FIELDS, (float(v) for v in mix_rec[j])))
+        for kind, w in waves.items():
+            wavwrite(_eval_wav_path(dump_dir, modelname, step, m["triple"], m["snr_pos"], m["snr_neg"], kind), FLAGS.Fs,
+                     w[ooff[j]:ooff[j + 1]])
+        out.append(r)
+    return out
+
+
+def _corpus_device(eng, sig, off, per_frame, dump):
+    """The launches of evaluate_corpus after the mixing, everything in HBM: job j's signals are [off[j], off[j + 1]) of
+    sig's tensors -> device records (and, for a dump, waveforms)."""
+    import torch
+    from . import context
+    J = len(off) - 1
+    nfr = [int(eng.lib.nhans_num_frames(off[j + 1] - off[j])) for j in range(J)]
+    foff = context.offsets(nfr)
+    roff = context.offsets(t - Noise_Win for t in nfr)
+
+    def rest(rows):
+        """rows [Noise_Win, t) of every job, one after the other"""
+        return torch.cat([rows[foff[j] + Noise_Win:foff[j + 1]] for j in range(J)]).contiguous()
+
+    lm, ph = eng.stft_features(sig["mixture"], off)
+    tlm, tph = eng.stft_features(sig["target"], off)
+    kl, _ = eng.stft_features(sig["keep"], off, Noise_Win, False)
+    dl, _ = eng.stft_features(sig["drop"], off, Noise_Win, False)
+    emb = eng.embed(torch.cat([kl, dl]).view(2 * J, Noise_Win, spec.BINS))
+    lm_s, ph_s, tlm_s, tph_s = rest(lm), rest(ph), rest(tlm), rest(tph)
+    _, den = eng.mask_net(lm_s, roff, emb[:J], emb[J:], want_logits=False)
+    den_wav, ooff = eng.istft(den, ph_s, roff)
+    mix_rt, _ = eng.istft(lm_s, ph_s, roff)
+    tgt_wav, _ = eng.istft(tlm_s, tph_s, roff)
+    records, frames = {}, {}
+    for name, wav, rows in (("denoised", den_wav, den), ("mixed", mix_rt, lm_s)):
+        w = eng.score_device(wav, ooff, tgt_wav, ooff, per_frame=per_frame)
+        r = eng.score_rows(rows, tlm_s, roff, per_frame=per_frame, frames_out=w[1] if per_frame else None)
+        records[name + "_wave"], records[name + "_rows"] = (w[0], r[0]) if per_frame else (w, r)
+        if per_frame:
+            frames[name] = r[1]
+    waves = {}
+    if dump:
+        waves = {"mixed": mix_rt, "denoised": den_wav, "target": tgt_wav}
+        for kind, x in (("posNoise", sig["keep"]), ("negNoise", sig["drop"])):
+            xl, xp = eng.stft_features(x, off)
+            waves[kind], _ = eng.istft(rest(xl), rest(xp), roff)
+    return {"records": records, "frames": frames, "waves": waves, "roff": roff, "ooff": ooff}
 
 
 def _utterance_scores(eng, den, mix_rt, target, den_lm, mix_lm, tgt_lm):

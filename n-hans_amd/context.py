@@ -169,6 +169,32 @@ class Context:
             res.append(rec)
         return res
 
+    # ---- mixing at a chosen SNR (include/nhans_hip.h: nhans_mix) -----------------------------------
+    def mix(self, speech, noises, jobs):
+        """Lists of float32 recordings and jobs (speech index, keep index or -1, drop index, snr_keep_db, snr_drop_db) ->
+        (dict "mixture" / "target" / "keep" / "drop" -> one float32 array per job, one record dict per job by
+        mixing.RECORD_FIELDS): mixing.domixing -- without a keep noise mixing.domixing_separator -- of every job, bit for
+        bit, computed on the device: one upload, the three launches, one download.  The indices let one triple of
+        recordings serve many SNR pairs; a power is computed once per distinct (recording, fitted length)."""
+        from . import mixing
+        lib, mem, nj = self.lib, Mem(self), len(jobs)
+        (sf, soff), (nf, noff) = flat(speech), flat(noises)
+        args, off = mix_job_arrays(jobs, soff)
+        names = ("mixture", "target", "keep", "drop")
+        ins = [mem.up(sf), mem.up(nf)]
+        outs = [mem.empty(off[-1]) for _ in names]
+        rec = mem.empty(nj * hip.MIX_FIELDS, np.float64)
+        try:
+            hip.check(lib.nhans_mix(self.handle, mem.p(ins[0]), hip.i64_array(soff), len(speech), mem.p(ins[1]), hip.i64_array(noff),
+                                    len(noises), *args, nj, *[mem.p(o) for o in outs], hip.i64_array(off), mem.p(rec), mem.stream()))
+            self._sync()
+            got = [np.array(mem.down(o, off[-1]), dtype=np.float32) for o in outs]
+            recs = np.array(mem.down(rec, nj * hip.MIX_FIELDS, np.float64), dtype=np.float64).reshape(nj, hip.MIX_FIELDS)
+        finally:
+            mem.free(*ins, *outs, rec)
+        signals = {k: [g[off[j]:off[j + 1]] for j in range(nj)] for k, g in zip(names, got)}
+        return signals, [dict(zip(mixing.RECORD_FIELDS, (float(v) for v in r))) for r in recs]
+
     def _sync(self):
         """Waits for the work issued on this context's stream (the null stream's copies wait by themselves)."""
 
@@ -274,6 +300,16 @@ def flat(arrays, dtype=np.float32):
     off = offsets(len(a) for a in arrays)
     out = np.concatenate([np.asarray(a, dtype=dtype) for a in arrays]) if len(arrays) else np.zeros(0, dtype)
     return np.ascontiguousarray(out, dtype=dtype), off
+
+
+def mix_job_arrays(jobs, speech_off):
+    """jobs (speech index, keep index or -1, drop index, snr_keep_db, snr_drop_db) -> (the five host arrays nhans_mix
+    takes, the output offsets: room for each job's speech length; an index out of range is the library's to refuse)."""
+    nj, ns = len(jobs), len(speech_off) - 1
+    si, ki, di = [(ctypes.c_int * nj)(*[int(j[k]) for j in jobs]) for k in range(3)]
+    sk, sd = [(ctypes.c_double * nj)(*[float(j[k] or 0) for j in jobs]) for k in (3, 4)]     # (None: no keep noise, no SNR)
+    off = offsets(speech_off[i + 1] - speech_off[i] if 0 <= i < ns else 0 for i in si)
+    return (si, ki, di, sk, sd), off
 
 
 def end_flags(end, n):

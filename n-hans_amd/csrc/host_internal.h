@@ -7,7 +7,8 @@
 //   host_live.hip     nhans_live_*, nhans_lookahead_live_*, nhans_capture_live_*, nhans_level_*, nhans_interleaved_*,
 //                     nhans_fbank_live_*, nhans_fullband_*
 //   host_score.hip    nhans_score_wave, nhans_score_rows
-// A unit calls down only: ctx <- net <- online <- live, ctx <- fbank <- online, ctx <- rate <- live and ctx <- score.  (One call goes up: the built-in calibration
+//   host_mix.hip      nhans_mix, nhans_mix_snr_factor
+// A unit calls down only: ctx <- net <- online <- live, ctx <- fbank <- online, ctx <- rate <- live, ctx <- score and ctx <- mix.  (One call goes up: the built-in calibration
 // of nhans_create runs the whole offline path, enhance_clips_body.)  Only what crosses a unit boundary is declared here;
 // everything else stays in its unit's anonymous namespace.
 // Nothing declared here joins the library's dynamic symbols (visibility hidden) except the object types the C header

@@ -460,4 +460,33 @@ void launch_score_rows(const char* kernel, const ScoreRowRun* runs_dev, int nrun
 void launch_score_rows_finish(const char* kernel, const ScoreRowRun* runs_dev, int nruns, const double* vals, double* rec,
                               hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// Mixing at a chosen SNR (mix.hip; include/nhans_hip.h: nhans_mix).  One MixChain per DISTINCT (clip, fitted length):
+// the mean square of the m samples at src fitted to n (sample i mod m where m < n, else sample i), one workgroup of
+// mix_power each, -> pw[its index].  One MixJob per job: n samples of speech at s, the keep noise at a (ma samples;
+// nullptr: the two-way mix) and the drop noise at b (mb), their chains' indices ps / pa / pb (pa unused without a), the
+// host's factors fa / fb = pow(10, -snr / 10), its outputs from element `out` of every output buffer on and its tiles of
+// kMixTile samples workgroups [tile0, tile0 + ceil(n / kMixTile)) of mix_combine and mix_finish (n >= 1, so tile0
+// ascends strictly).  kMixTile is also what mix_power stages at a time.
+struct MixChain {
+    const float* src;
+    long long m, n;
+};
+struct MixJob {
+    const float* s;
+    const float* a;
+    const float* b;
+    long long n, ma, mb, out, tile0;
+    double fa, fb;
+    int ps, pa, pb, pad;
+};
+constexpr int kMixTile = 2048, kMixFields = 8;
+void launch_mix_power(const char* kernel, const MixChain* chains_dev, int nchains, double* pw, hipStream_t s);
+// peaks: [tiles] floats, max |raw| of each tile; rec (nullable): [jobs][kMixFields], fields 0 - 4 written here
+void launch_mix_combine(const char* kernel, const MixJob* jobs_dev, int njobs, long long ntiles, const double* pw, float* mixture,
+                        float* peaks, double* rec, hipStream_t s);
+// mixture divided in place; target / keep / drop nullable; fields 5 - 7 of rec
+void launch_mix_finish(const char* kernel, const MixJob* jobs_dev, int njobs, long long ntiles, const double* pw, const float* peaks,
+                       float* mixture, float* target, float* keep, float* drop, double* rec, hipStream_t s);
+
 }  // namespace nhans

@@ -187,6 +187,28 @@ class Engine(context.Context):
                                             self._stream()))
         return (out, fr) if per_frame else out
 
+    # ---- mixing at a chosen SNR (include/nhans_hip.h: nhans_mix) ------------------------------------
+    def mix_device(self, speech_t, speech_off, noise_t, noise_off, jobs, want=("mixture", "target", "keep", "drop")):
+        """Mixtures of clips already in HBM.  jobs: (speech index, keep index or -1, drop index, snr_keep_db, snr_drop_db)
+        each, the indices into speech_t / speech_off and noise_t / noise_off -> (dict of flat float32 device tensors for
+        the names in `want` -- "mixture" always --, the output offsets: job j's samples are [off[j], off[j + 1]) of each,
+        float64 device tensor [jobs, hip.MIX_FIELDS] whose first columns mixing.RECORD_FIELDS names)."""
+        for t in (speech_t, noise_t):
+            if t.dtype != torch.float32 or t.dim() != 1:
+                raise ValueError("mix_device: flat float32 tensors")
+        unknown = set(want) - {"mixture", "target", "keep", "drop"}
+        if unknown:
+            raise ValueError("mix_device: no output named %s" % sorted(unknown))
+        args, off = context.mix_job_arrays(jobs, speech_off)
+        out = {k: torch.empty(max(off[-1], 1), dtype=torch.float32, device=self.device)
+               for k in ("mixture", "target", "keep", "drop") if k == "mixture" or k in want}
+        rec = torch.empty((len(jobs), hip.MIX_FIELDS), dtype=torch.float64, device=self.device)
+        hip.check(self.lib.nhans_mix(self.handle, hip.ptr(speech_t.contiguous()), hip.i64_array(speech_off), len(speech_off) - 1,
+                                     hip.ptr(noise_t.contiguous()), hip.i64_array(noise_off), len(noise_off) - 1, *args, len(jobs),
+                                     hip.ptr(out["mixture"]), hip.ptr(out.get("target")), hip.ptr(out.get("keep")),
+                                     hip.ptr(out.get("drop")), hip.i64_array(off), hip.ptr(rec), self._stream()))
+        return {k: v[:off[-1]] for k, v in out.items()}, off, rec
+
     def _sync(self):
         torch.cuda.current_stream(self.device).synchronize()
 

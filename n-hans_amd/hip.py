@@ -121,6 +121,10 @@ SIGNATURES = {
     # scoring against a clean target
     "nhans_score_wave": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _vp, _vp, _vp]),
     "nhans_score_rows": (_int, [_vp, _vp, _vp, _i64p, _int, _vp, _vp, _vp]),
+    # mixing at a chosen SNR
+    "nhans_mix_snr_factor": (_int, [_dbl, _dp]),
+    "nhans_mix": (_int, [_vp, _vp, _i64p, _int, _vp, _i64p, _int, _ip, _ip, _ip, _dp, _dp, _int, _vp, _vp, _vp, _vp, _i64p, _vp,
+                         _vp]),
     "nhans_profile_json": (_int, [_vp, _str, _size]),
     "nhans_profile_reset": (_int, [_vp]),
 }
@@ -143,6 +147,8 @@ FBANK_MIXED = 1
 FULLBAND_RATES = (22050, 24000, 32000, 44100, 48000, 88200, 96000)
 SCORE_FIELDS, SCORE_ROW_FIELDS = 16, 8
 SCORE_TILE = 2560                           # samples per workgroup of score.hip (kScoreTile)
+MIX_FIELDS = 8
+MIX_TILE = 2048                             # samples per workgroup and per staging buffer of mix.hip (kMixTile)
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25
 ABI_VERSION = 5

@@ -22,6 +22,10 @@ from . import spec
 
 SNRS_DENOISER = [-3, 0, 3, 5, 8]            # SN/apply.py:129, SN/reader.py:199
 SNRS_SEPARATOR = [-5, -3, -1, 0, 1, 3, 5]   # SS/apply.py:101
+# the first seven of the NHANS_MIX_FIELDS doubles the device writes per job (include/nhans_hip.h: nhans_mix, which computes
+# domixing / domixing_separator below bit for bit -- Context.mix): the three mean powers, the two float64 gains, the raw
+# mixture's peak and the divisor of the three other signals
+RECORD_FIELDS = ("P_s", "P_keep", "P_drop", "g_keep", "g_drop", "pk", "unit")
 
 
 def _fit_length(noise, n):
@@ -108,15 +112,22 @@ def _normalise(x):
         return (x / (np.max(np.abs(x)) + 0.000001)).astype(np.float32)
 
 
-def combine_signals(read_wav, cleanpath, noisepospath, noisenegpath, snrs=None):
-    """Denoiser demo/eval front end.  snrs=None: the demo's fixed (0, 0) dB (SN/apply.py:128-134);
-    otherwise a (snr_pos, snr_neg) pair, e.g. eval_snrs(cleanpath) for the evaluation reader.
-    Returns (target, noise_pos_signal, noise_neg_signal, mixed, snr_pos, snr_neg)."""
+def read_triple(read_wav, cleanpath, noisepospath, noisenegpath):
+    """The three recordings of a denoiser mixture as domixing takes them: each normalised, the clean one trimmed to whole
+    hops (the head of the reference's combine_signals)."""
     clean = _normalise(read_wav(cleanpath))
     pos = _normalise(read_wav(noisepospath))
     neg = _normalise(read_wav(noisenegpath))
     if (len(clean) - spec.WIN) % spec.HOP != 0:
         clean = clean[:-((len(clean) - spec.WIN) % spec.HOP)]
+    return clean, pos, neg
+
+
+def combine_signals(read_wav, cleanpath, noisepospath, noisenegpath, snrs=None):
+    """Denoiser demo/eval front end.  snrs=None: the demo's fixed (0, 0) dB (SN/apply.py:128-134);
+    otherwise a (snr_pos, snr_neg) pair, e.g. eval_snrs(cleanpath) for the evaluation reader.
+    Returns (target, noise_pos_signal, noise_neg_signal, mixed, snr_pos, snr_neg)."""
+    clean, pos, neg = read_triple(read_wav, cleanpath, noisepospath, noisenegpath)
     snr_pos, snr_neg = (SNRS_DENOISER[1], SNRS_DENOISER[1]) if snrs is None else snrs
     mixed, target, _, _, pos_sig, neg_sig = domixing(clean, pos, neg, snr_pos, snr_neg)
     return target, pos_sig, neg_sig, mixed, np.array(snr_pos, dtype=np.int32), np.array(snr_neg, dtype=np.int32)
