@@ -935,6 +935,56 @@ int nhans_mix(nhans_ctx* ctx, const float* speech_dev, const int64_t* speech_off
               float* target_dev, float* keep_dev, float* drop_dev, const int64_t* out_offsets_host, double* records_dev,
               void* stream);
 
+/* ---- STOI and extended STOI against a clean target ----------------------------------------------------------------------
+ * The intelligibility figures of Taal et al. (2011) and Jensen & Taal (2016), computed where the signals are
+ * (n-hans_amd/csrc/stoi.hip).  Added without moving NHANS_ABI_VERSION; a caller that may meet an
+ * older library looks the functions up by symbol.  x is the target and y the estimate, both float32 at 10 kHz (not the
+ * network's 16 kHz: nhans_stoi_resample below), n = min(nx, ny) common samples; every operation is in double.
+ *   window    w[i] = 0.5 (1 - cos(2 pi (i + 1) / 257)), i < 256: the 256 inner points of a 258-point symmetric Hann window
+ *             (Matlab's hanning(256))
+ *   framing   M0 = ceil((n - 256) / 128) frames for n > 256, else 0; frame m is samples [128 m, 128 m + 256).  A final frame
+ *             that would end exactly at n is not taken (the published code's rule).
+ *   silence   P_m = sum (w x_m)^2, P_max = max P_m; frame m is kept iff P_m > P_max * 1e-4 (40 dB; the product rounded
+ *             once).  The decision is taken on the target and applied to both signals; Mk frames are kept, none where
+ *             P_max == 0.
+ *   rejoining the kept windowed frames of each signal are overlap-added at hop 128 in their kept order (a signal of
+ *             128 (Mk - 1) + 256 samples) and framed again by the same rule: Mf = Mk - 1 frames (0 for Mk <= 1), each
+ *             windowed by w again, zero-padded to 512 and transformed.
+ *   bands     X[j][q] = sqrt(sum_{k in [lo_j, hi_j)} |X_q(k)|^2), 15 third-octave bands from 150 Hz, [lo, hi) =
+ *             (7,9) (9,11) (11,14) (14,17) (17,22) (22,27) (27,34) (34,43) (43,55) (55,69) (69,87) (87,109) (109,138)
+ *             (138,174) (174,219): the nearest bins of linspace(0, 10000, 513) to 150 * 2^(j/3) * 2^(-+1/6)
+ *   stoi      S = Mf - 29 segments for Mf >= 30, else 0; segment s is columns s ... s + 29.  Per band: a = |x| / (|y| + eps),
+ *             y' = min(a y, (1 + 10^(15/20)) x); x and y' are made zero-mean over the 30 columns and divided by their norm
+ *             + eps; d_s = (sum_j sum_q x^ y'^) / 15; stoi = mean_s d_s; eps = 2^-52
+ *   estoi     per segment and signal each row (band) is made zero-mean and divided by its norm + eps, then each column
+ *             likewise; e_s = (sum x~ y~) / 30; estoi = mean_s e_s
+ *   edges     S == 0 (a clip too short, or everything silent) gives NaN for both figures, the counts filled in -- IEEE, as the
+ *             scoring section above, where the published Python package returns 1e-5 with a warning.  Non-finite samples:
+ *             unspecified.
+ *   record    NHANS_STOI_FIELDS doubles: n, frames (M0), frames_kept (Mk), segments (S), stoi, estoi, 0, 0
+ * Every figure is a function of the clip pair alone: the order of each sum is fixed relative to the clip's first sample
+ * (stoi.hip states it), there are no floating-point atomics, and a record has the same bits alone or in any batch, at any
+ * offset, on every run.
+ *
+ * Clip i of the estimates is est10_dev[est_offsets_host[i] .. est_offsets_host[i + 1]), of the targets likewise with its own
+ * offsets.  out_dev receives NHANS_STOI_FIELDS doubles per clip.  segments_out_dev (nullable) receives rows of two doubles
+ * d_s, e_s, clip after clip: how many segments a clip has is known on the device only, so clip i's rows begin at row
+ * sum_{k < i} max(0, M0_k - 30) -- room for the segments of a clip without a silent frame -- and its first `segments` rows
+ * are written.  NHANS_EINVAL, naming the clip, before anything is launched: nclips < 0, a NULL that is needed, an offset
+ * array that descends.
+ *
+ * nhans_stoi_resample brings 16 kHz float32 clips to 10 kHz: the filter design, float32 taps and single fmaf chain of
+ * nhans_resample for L = 5, M = 8 (half = 80), on the same kernel -- a pair for this purpose only, not one of
+ * nhans_resample's.  Clip i gives nhans_stoi_out_count(n_i) = ceil(5 n_i / 8) samples from out_offsets_host[i] on and is
+ * refused where the room is less.  The published STOI implementations convert with another filter (Matlab's resample
+ * design): figures computed from 16 kHz signals are this library's, not theirs. */
+#define NHANS_STOI_FIELDS 8     /* n, frames, frames_kept, segments, stoi, estoi, 0, 0 */
+int64_t nhans_stoi_out_count(int64_t n16);      /* host only */
+int nhans_stoi_resample(nhans_ctx* ctx, const float* in16_dev, const int64_t* in_offsets_host, int nclips, float* out10_dev,
+                        const int64_t* out_offsets_host, void* stream);
+int nhans_stoi(nhans_ctx* ctx, const float* est10_dev, const int64_t* est_offsets_host, const float* tgt10_dev,
+               const int64_t* tgt_offsets_host, int nclips, double* out_dev, double* segments_out_dev, void* stream);
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

@@ -65,6 +65,7 @@ class Flags(object):
     highband = None      # --highband G: the input's own band above 8 kHz, times G, added to the files written at the input's rate (live.fullband_mix)
     score_against = None # --score_against TARGET: score the files written against a clean target on the device (score.py)
     score_out = None     # --score_out PATH.json: where the scores go (stdout otherwise)
+    stoi = False         # --stoi: with --score_against, also STOI and extended STOI (score.py: stoi_reference is the definition)
     lookahead_ms = 10 * spec.LOOKAHEAD   # --lookahead_ms: 10 ms per frame of look-ahead (include/nhans_hip.h: "lookahead"), 170 = all 17
 
 
@@ -610,7 +611,8 @@ def apply_demo_separator(cleanpath, noisepath, save_to, mix_on="host"):
     wavwrite(save_to[:-15] + 'mixed_demo.wav', FLAGS.Fs, mix_rt)
 
 
-def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelname='nhans', step=0, scores=False, mix_on="host"):
+def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelname='nhans', step=0, scores=False, mix_on="host",
+                       stoi=False):
     """Evaluation-reader pipeline for one (speech, pos noise, neg noise) triple: SN/reader.py:310-420
     (eval branch, eval_stride 1) + SN/main.py:264-353.  Mixes at the reference's md5-derived SNRs,
     runs the network on frames from context_frames on, writes the reference's five wavs
@@ -619,6 +621,8 @@ def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelnam
     (Engine.score_device / score_rows) of the denoised and of the mixed signal against the target -- waveforms as written,
     row figures from the network's own denoised rows and the mixture's rows against the target's -- their improvement, and
     under "rows" the three row arrays that were scored.  mix_on="gpu": the mixing on the device (the same files and loss).
+    stoi=True (with scores): the records also carry STOI and extended STOI of the same waveforms (Engine.stoi_device,
+    merged by score.merge_stoi) and the improvement stoi_i and estoi_i; the files and the loss are what they are without it.
     A corpus at several SNR pairs in one pass: evaluate_corpus."""
     from . import mixing
     eng = get_engine(spec.DENOISER)
@@ -637,7 +641,7 @@ def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelnam
         wavwrite(_eval_wav_path(dump_dir, modelname, step, (cleanpath, noisepospath, noisenegpath), snr_pos, snr_neg, kind),
                  FLAGS.Fs, w)
     if scores:
-        return loss, _utterance_scores(eng, den, mix_rt, extras[0], den_lm, mix_lm, tgt_lm)
+        return loss, _utterance_scores(eng, den, mix_rt, extras[0], den_lm, mix_lm, tgt_lm, stoi)
     return loss
 
 
@@ -646,7 +650,8 @@ def _eval_wav_path(dump_dir, modelname, step, triple, snr_pos, snr_neg, kind):
     return os.path.join(dump_dir, '{}_{}_{}_{}_{}_{}_{}_{}.wav'.format(modelname, step, base[0], base[1], base[2], snr_pos, snr_neg, kind))
 
 
-def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None, per_frame=False, modelname='nhans', step=0):
+def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None, per_frame=False, modelname='nhans', step=0,
+                    stoi=False):
     """evaluate_utterance(scores=True) for a corpus in one pass.  triples: (cleanpath, pospath, negpath) each; snrs: the
     (snr_pos, snr_neg) pairs applied to every triple (None: the triple's own mixing.eval_snrs).  The files are read,
     normalised and trimmed on the host and uploaded once; the mixtures of all (triple, SNR pair) jobs (Engine.mix_device),
@@ -657,7 +662,8 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
     -> one dict per job, triple after triple: "triple", "snr_pos", "snr_neg", "loss" (the denoised rows' loss as the
     device forms it: the "loss" of evaluate_utterance's scores, bit for bit), "denoised", "mixed", "improvement" (as
     evaluate_utterance's scores) and "mix" (the job's mixing record); per_frame=True: plus "per_frame" in "denoised" and
-    "mixed", float64 [frames, 3] as Context.score's."""
+    "mixed", float64 [frames, 3] as Context.score's.  stoi=True: STOI and extended STOI in the same pass, as
+    evaluate_utterance(scores=True, stoi=True) merges them, bit for bit; only their records come back."""
     from . import context, mixing, score
     eng = get_engine(spec.DENOISER)
     speech, noises, jobs, meta = [], [], [], []
@@ -678,7 +684,7 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
     sig, off, mix_rec = eng.mix_device(sp_t, sp_off, nz_t, nz_off, jobs)
     dump = dump_dir is not None
     res = eng._with_lookahead(lookahead, lambda: context.redo_saturated_in_f32(
-        eng, lambda: _corpus_device(eng, sig, off, per_frame, dump)))
+        eng, lambda: _corpus_device(eng, sig, off, per_frame, dump, stoi)))
     eng._sync()
     mix_rec = mix_rec.cpu().numpy()
     down = {k: v.cpu().numpy() for k, v in res["records"].items()}
@@ -692,6 +698,8 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
         r = dict(m)
         for name in ("denoised", "mixed"):
             r[name] = dict(score.record(down[name + "_wave"][j]), **score.row_record(down[name + "_rows"][j]))
+            if stoi:
+                r[name] = score.merge_stoi(r[name], score.stoi_record(down[name + "_stoi"][j]))
             if per_frame:
                 r[name]["per_frame"] = frames[name][roff[j]:roff[j + 1]].copy()
         r["loss"] = r["denoised"]["loss"]
@@ -704,7 +712,7 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
     return out
 
 
-def _corpus_device(eng, sig, off, per_frame, dump):
+def _corpus_device(eng, sig, off, per_frame, dump, stoi=False):
     """The launches of evaluate_corpus after the mixing, everything in HBM: job j's signals are [off[j], off[j + 1]) of
     sig's tensors -> device records (and, for a dump, waveforms)."""
     import torch
@@ -733,6 +741,8 @@ def _corpus_device(eng, sig, off, per_frame, dump):
         w = eng.score_device(wav, ooff, tgt_wav, ooff, per_frame=per_frame)
         r = eng.score_rows(rows, tlm_s, roff, per_frame=per_frame, frames_out=w[1] if per_frame else None)
         records[name + "_wave"], records[name + "_rows"] = (w[0], r[0]) if per_frame else (w, r)
+        if stoi:
+            records[name + "_stoi"] = eng.stoi_device(wav, ooff, tgt_wav, ooff)
         if per_frame:
             frames[name] = r[1]
     waves = {}
@@ -744,7 +754,7 @@ def _corpus_device(eng, sig, off, per_frame, dump):
     return {"records": records, "frames": frames, "waves": waves, "roff": roff, "ooff": ooff}
 
 
-def _utterance_scores(eng, den, mix_rt, target, den_lm, mix_lm, tgt_lm):
+def _utterance_scores(eng, den, mix_rt, target, den_lm, mix_lm, tgt_lm, stoi=False):
     import torch
     from . import score
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(eng.device)
@@ -754,6 +764,9 @@ def _utterance_scores(eng, den, mix_rt, target, den_lm, mix_lm, tgt_lm):
         w = eng.score_device(dev(wav), [0, len(wav)], tw, [0, len(target)])
         r = eng.score_rows(dev(rows), tr, [0, len(tgt_lm)])
         out[name] = dict(score.record(w.cpu().numpy()[0]), **score.row_record(r.cpu().numpy()[0]))
+        if stoi:
+            st = eng.stoi_device(dev(wav), [0, len(wav)], tw, [0, len(target)])
+            out[name] = score.merge_stoi(out[name], score.stoi_record(st.cpu().numpy()[0]))
     out["improvement"] = score.improvement(out["mixed"], out["denoised"])
     out["rows"] = {"denoised": den_lm, "mixed": mix_lm, "target": tgt_lm}
     return out
@@ -805,9 +818,14 @@ def _parse(argv, prog):
                         'segmental SNR, the reference\'s loss, log-spectral distance) and the scores written as JSON; the '
                         'audio files are what they are without the flag')
     p.add_argument('--score_out', default=None, metavar='PATH.json', help='where the scores of --score_against go (default: stdout)')
+    p.add_argument('--stoi', action='store_true',
+                   help='with --score_against: also STOI and extended STOI of the same files against the target, converted to '
+                        '10 kHz and computed on the device; the audio files are what they are without the flag')
     a = p.parse_args(argv)
     if a.score_out is not None and a.score_against is None:
         p.error('--score_out needs --score_against TARGET')
+    if a.stoi and a.score_against is None:
+        p.error('--stoi needs --score_against TARGET')
     if a.score_against is not None:
         if a.output_rate == 'input':
             p.error('--score_against scores the 16 kHz files; it does not combine with --output_rate input')
@@ -922,7 +940,7 @@ def _score_jobs(kind, a, jobs):
         est += [wavread(save_to)[1], wavread(mp)[1]]
         tgt += [t, t]
         done.append(mixedpath)
-    recs = get_enhancer(kind).score(est, tgt) if est else []
+    recs = get_enhancer(kind).score(est, tgt, stoi=getattr(a, "stoi", False)) if est else []
     files = {}
     for i, path in enumerate(done):
         den, mix = recs[2 * i], recs[2 * i + 1]

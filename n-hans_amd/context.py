@@ -126,14 +126,19 @@ class Context:
 
 
     # ---- scoring against a clean target (include/nhans_hip.h: nhans_score_*) ---------------------
-    def score(self, estimates, targets, per_frame=False):
+    def score(self, estimates, targets, per_frame=False, stoi=False):
         """Lists of float32 waveforms, estimate i against target i over their common prefix -> one dict per clip: the
         waveform figures (score.FIELDS: si_sdr_db, snr_db, segsnr_db, ...) and the row figures loss and lsd_db of the two
         signals' own log-magnitude rows (nhans_stft_features) -- one upload, two STFTs and the two score calls on the
         device, one download of the records.  per_frame=True: plus "per_frame", float64 [frames, 3]: each frame's clamped
-        segmental value (NaN where its target is silent), loss and lsd."""
+        segmental value (NaN where its target is silent), loss and lsd.  stoi=True: plus the figures of Context.stoi of
+        the same pairs (16 kHz signals), merged into each record -- a name the record already has (n, frames: there the
+        16 kHz samples and the STFT rows) is prefixed: stoi_n, stoi_frames."""
         if len(estimates) != len(targets):
             raise ValueError("score: one target per estimate")
+        if stoi:
+            return [score_mod.merge_stoi(r, t)
+                    for r, t in zip(self.score(estimates, targets, per_frame=per_frame), self.stoi(estimates, targets))]
         lib, mem, n = self.lib, Mem(self), len(estimates)
         cut = [min(len(e), len(t)) for e, t in zip(estimates, targets)]
         (ef, off), (tf, _) = flat([e[:k] for e, k in zip(estimates, cut)]), flat([t[:k] for t, k in zip(targets, cut)])
@@ -166,6 +171,55 @@ class Context:
             rec.update(score_mod.row_record(got[n * nw + i * nr:n * nw + (i + 1) * nr]))
             if per_frame:
                 rec["per_frame"] = got[n * (nw + nr):].reshape(F, 3)[foff[i]:foff[i + 1]].copy()
+            res.append(rec)
+        return res
+
+    # ---- STOI and extended STOI against a clean target (include/nhans_hip.h: nhans_stoi) ----------
+    def stoi(self, estimates, targets, rate=16000, per_segment=False):
+        """Lists of float32 waveforms at `rate` (16000: the network's, converted to 10 kHz on the device by
+        nhans_stoi_resample; 10000: scored as they are), estimate i against target i -> one dict per clip by
+        score.STOI_FIELDS: n (common samples at 10 kHz), frames, frames_kept, segments, stoi, estoi -- NaN for both figures
+        where there is no segment.  One upload, the conversion, the score and one download of the records.
+        per_segment=True: plus "per_segment", float64 [segments, 2] = each segment's d_s and e_s."""
+        if len(estimates) != len(targets):
+            raise ValueError("stoi: one target per estimate")
+        if rate not in (16000, score_mod.STOI_RATE):
+            raise ValueError("stoi: signals at 16000 or %d Hz, not %r" % (score_mod.STOI_RATE, rate))
+        lib, mem, n = self.lib, Mem(self), len(estimates)
+        (ef, eoff), (tf, toff) = flat(estimates), flat(targets)
+        s = mem.stream()
+        bufs = [mem.up(ef), mem.up(tf)]
+        offs = [eoff, toff]
+        try:
+            if rate == 16000 and n:
+                for k in (0, 1):
+                    o10 = offsets(score_mod.stoi_out_count(offs[k][i + 1] - offs[k][i]) for i in range(n))
+                    conv = mem.empty(o10[-1])
+                    bufs.append(conv)
+                    hip.check(lib.nhans_stoi_resample(self.handle, mem.p(bufs[k]), hip.i64_array(offs[k]), n, mem.p(conv),
+                                                      hip.i64_array(o10), s))
+                    offs[k] = o10
+                src = bufs[2:]
+            else:
+                src = bufs[:2]
+            cnt = [min(offs[0][i + 1] - offs[0][i], offs[1][i + 1] - offs[1][i]) for i in range(n)]
+            soff = offsets(max(score_mod.stoi_num_frames(k) - score_mod.STOI_SEGMENT, 0) for k in cnt)
+            nf, ns = hip.STOI_FIELDS, soff[-1] if per_segment else 0
+            out = mem.empty(n * nf + 2 * ns, np.float64)
+            bufs.append(out)
+            if n:
+                seg = ctypes.c_void_p(mem.p(out).value + 8 * n * nf) if per_segment else None
+                hip.check(lib.nhans_stoi(self.handle, mem.p(src[0]), hip.i64_array(offs[0]), mem.p(src[1]), hip.i64_array(offs[1]), n,
+                                         mem.p(out), seg, s))
+            self._sync()
+            got = np.array(mem.down(out, n * nf + 2 * ns, np.float64), dtype=np.float64)
+        finally:
+            mem.free(*bufs)
+        res = []
+        for i in range(n):
+            rec = score_mod.stoi_record(got[i * nf:(i + 1) * nf])
+            if per_segment:
+                rec["per_segment"] = got[n * nf:].reshape(ns, 2)[soff[i]:soff[i] + rec["segments"]].copy()
             res.append(rec)
         return res
 

@@ -8,7 +8,8 @@
 //                     nhans_fbank_live_*, nhans_fullband_*
 //   host_score.hip    nhans_score_wave, nhans_score_rows
 //   host_mix.hip      nhans_mix, nhans_mix_snr_factor
-// A unit calls down only: ctx <- net <- online <- live, ctx <- fbank <- online, ctx <- rate <- live, ctx <- score and ctx <- mix.  (One call goes up: the built-in calibration
+//   host_stoi.hip     nhans_stoi, nhans_stoi_resample, nhans_stoi_out_count
+// A unit calls down only: ctx <- net <- online <- live, ctx <- fbank <- online, ctx <- rate <- live, ctx <- score, ctx <- mix and ctx <- rate <- stoi.  (One call goes up: the built-in calibration
 // of nhans_create runs the whole offline path, enhance_clips_body.)  Only what crosses a unit boundary is declared here;
 // everything else stays in its unit's anonymous namespace.
 // Nothing declared here joins the library's dynamic symbols (visibility hidden) except the object types the C header

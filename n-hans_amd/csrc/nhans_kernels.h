@@ -312,6 +312,8 @@ struct ResampleFilter {
 };
 // nullptr for a pair that is not supported; the design of a pair is computed once per process (thread-safe)
 const ResampleFilter* resample_filter(int rate_in, int rate_out);
+// 16000 -> 10000 Hz (L = 5, M = 8, half = 80): the same design, for nhans_stoi_resample only -- not a pair of the public list
+const ResampleFilter* resample_filter_stoi();
 int64_t resample_out_count(const ResampleFilter& f, int64_t n);                 // ceil(n L / M)
 int64_t resample_emitted(const ResampleFilter& f, int64_t n, bool ended);      // the streaming output contract
 
@@ -488,5 +490,37 @@ void launch_mix_combine(const char* kernel, const MixJob* jobs_dev, int njobs, l
 // mixture divided in place; target / keep / drop nullable; fields 5 - 7 of rec
 void launch_mix_finish(const char* kernel, const MixJob* jobs_dev, int njobs, long long ntiles, const double* pw, const float* peaks,
                        float* mixture, float* target, float* keep, float* drop, double* rec, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// STOI and extended STOI against a clean target (stoi.hip; include/nhans_hip.h: nhans_stoi).  One StoiRun per clip pair,
+// empty ones included: n common samples at est / tgt (10 kHz) and `frames` = M0 frames of 256 at hop 128.  What a clip
+// owns in the call's scratch is sized by n alone, since how many frames are silent is known on the device only: entries
+// [frame0, frame0 + M0) of the frame powers and of the kept-frame list, rows [band0, band0 + max(M0 - 1, 0)) of the two
+// band tensors, rows [seg0, seg0 + max(M0 - 30, 0)) of the segment figures; and workgroups [ptile0, ...) of the power
+// launch (kStoiPowerTile frames each), [btile0, ...) of the band launch (kStoiBandTile analysis frames each) and
+// [stile0, ...) of the segment launch (kStoiSegTile segments each).  All of them ascend from 0 over the runs.  A
+// workgroup past what the clip really kept finds that in nkept[run] and leaves.
+struct StoiRun {
+    const float* est;
+    const float* tgt;
+    long long n, frames, frame0, band0, seg0, ptile0, btile0, stile0;
+};
+constexpr int kStoiFields = 8, kStoiFrame = 256, kStoiHop = 128, kStoiFft = 512, kStoiBands = 15, kStoiSegment = 30;
+constexpr int kStoiPowerTile = 4, kStoiBandTile = 2, kStoiSegTile = 16;
+constexpr int kStoiTable = kStoiFrame + 2 * kStoiFft;      // doubles: the window, then cos and -sin of 2 pi t / 512
+inline long long stoi_frames(long long n) { return n > kStoiFrame ? (n - kStoiFrame + kStoiHop - 1) / kStoiHop : 0; }
+void stoi_table(double* tab);                               // (host) the kStoiTable doubles
+void launch_stoi_power(const char* kernel, const StoiRun* runs_dev, int nruns, long long ntiles, const double* tab, double* power,
+                       hipStream_t s);
+void launch_stoi_keep(const char* kernel, const StoiRun* runs_dev, int nruns, const double* power, int* kept, long long* nkept,
+                      hipStream_t s);
+// bands: [2][rows][15] doubles, the target's then the estimate's (the second half begins at row `rows`)
+void launch_stoi_bands(const char* kernel, const StoiRun* runs_dev, int nruns, long long ntiles, const double* tab, const int* kept,
+                       const long long* nkept, double* bands, long long rows, hipStream_t s);
+// segs: [rows][2] = d_s, e_s; segs_out: the caller's copy, nullable
+void launch_stoi_segments(const char* kernel, const StoiRun* runs_dev, int nruns, long long ntiles, const long long* nkept,
+                          const double* bands, long long rows, double* segs, double* segs_out, hipStream_t s);
+void launch_stoi_finish(const char* kernel, const StoiRun* runs_dev, int nruns, const long long* nkept, const double* segs,
+                        double* rec, hipStream_t s);
 
 }  // namespace nhans

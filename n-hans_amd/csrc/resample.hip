@@ -90,8 +90,10 @@ ResampleFilter* design(int rate_in, int rate_out) {
 
 }  // namespace
 
-const ResampleFilter* resample_filter(int rate_in, int rate_out) {
-    if ((rate_in != 16000 && rate_out != 16000) || !rate_supported(rate_in) || !rate_supported(rate_out)) return nullptr;
+namespace {
+
+// the design of a pair, computed once per process
+const ResampleFilter* filter_of(int rate_in, int rate_out) {
     static std::mutex mu;
     static std::map<std::pair<int, int>, ResampleFilter*> cache;    // (lives as long as the process)
     std::lock_guard<std::mutex> lock(mu);
@@ -99,6 +101,15 @@ const ResampleFilter* resample_filter(int rate_in, int rate_out) {
     if (!f) f = design(rate_in, rate_out);
     return f;
 }
+
+}  // namespace
+
+const ResampleFilter* resample_filter(int rate_in, int rate_out) {
+    if ((rate_in != 16000 && rate_out != 16000) || !rate_supported(rate_in) || !rate_supported(rate_out)) return nullptr;
+    return filter_of(rate_in, rate_out);
+}
+
+const ResampleFilter* resample_filter_stoi() { return filter_of(16000, 10000); }
 
 int64_t resample_out_count(const ResampleFilter& f, int64_t n) { return (n * f.L + f.M - 1) / f.M; }
 

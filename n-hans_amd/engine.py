@@ -187,6 +187,40 @@ class Engine(context.Context):
                                             self._stream()))
         return (out, fr) if per_frame else out
 
+    # ---- STOI and extended STOI against a clean target (include/nhans_hip.h: nhans_stoi) -----------
+    def stoi_device(self, est_t, est_off, tgt_t, tgt_off, rate=16000, per_segment=False):
+        """STOI figures of clips already in HBM: estimate i = est_t[est_off[i]:est_off[i + 1]] against target i of tgt_t /
+        tgt_off, float32 at `rate` (16000: converted to 10 kHz by nhans_stoi_resample first; 10000: as they are) -> device
+        tensor float64 [n, hip.STOI_FIELDS] (score.STOI_FIELDS names the columns); per_segment=True: -> (that, float64
+        [rows, 2] = d_s, e_s, the row offsets: clip i's rows begin at offsets[i] and its first `segments` are written, the
+        rest stay NaN)."""
+        n = len(est_off) - 1
+        if len(tgt_off) - 1 != n:
+            raise ValueError("stoi_device: one target per estimate")
+        if rate not in (16000, score_mod.STOI_RATE):
+            raise ValueError("stoi_device: signals at 16000 or %d Hz, not %r" % (score_mod.STOI_RATE, rate))
+        for t in (est_t, tgt_t):
+            if t.dtype != torch.float32 or t.dim() != 1:
+                raise ValueError("stoi_device: flat float32 tensors")
+        sig = [(est_t.contiguous(), [int(v) for v in est_off]), (tgt_t.contiguous(), [int(v) for v in tgt_off])]
+        if rate == 16000:
+            for k, (x, off) in enumerate(sig):
+                o10 = context.offsets(score_mod.stoi_out_count(off[i + 1] - off[i]) for i in range(n))
+                y = torch.empty(max(o10[-1], 1), dtype=torch.float32, device=self.device)
+                hip.check(self.lib.nhans_stoi_resample(self.handle, hip.ptr(x), hip.i64_array(off), n, hip.ptr(y), hip.i64_array(o10),
+                                                       self._stream()))
+                sig[k] = (y, o10)
+        (e, eo), (t, to) = sig
+        out = torch.empty((n, hip.STOI_FIELDS), dtype=torch.float64, device=self.device)
+        seg, soff = None, None
+        if per_segment:
+            soff = context.offsets(max(score_mod.stoi_num_frames(min(eo[i + 1] - eo[i], to[i + 1] - to[i])) - score_mod.STOI_SEGMENT, 0)
+                                   for i in range(n))
+            seg = torch.full((max(soff[-1], 1), 2), float("nan"), dtype=torch.float64, device=self.device)
+        hip.check(self.lib.nhans_stoi(self.handle, hip.ptr(e), hip.i64_array(eo), hip.ptr(t), hip.i64_array(to), n, hip.ptr(out),
+                                      hip.ptr(seg), self._stream()))
+        return (out, seg[:soff[-1]], soff) if per_segment else out
+
     # ---- mixing at a chosen SNR (include/nhans_hip.h: nhans_mix) ------------------------------------
     def mix_device(self, speech_t, speech_off, noise_t, noise_off, jobs, want=("mixture", "target", "keep", "drop")):
         """Mixtures of clips already in HBM.  jobs: (speech index, keep index or -1, drop index, snr_keep_db, snr_drop_db)

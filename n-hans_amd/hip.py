@@ -125,6 +125,10 @@ SIGNATURES = {
     "nhans_mix_snr_factor": (_int, [_dbl, _dp]),
     "nhans_mix": (_int, [_vp, _vp, _i64p, _int, _vp, _i64p, _int, _ip, _ip, _ip, _dp, _dp, _int, _vp, _vp, _vp, _vp, _i64p, _vp,
                          _vp]),
+    # STOI and extended STOI against a clean target
+    "nhans_stoi_out_count": (_i64, [_i64]),
+    "nhans_stoi_resample": (_int, [_vp, _vp, _i64p, _int, _vp, _i64p, _vp]),
+    "nhans_stoi": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _vp, _vp, _vp]),
     "nhans_profile_json": (_int, [_vp, _str, _size]),
     "nhans_profile_reset": (_int, [_vp]),
 }
@@ -148,6 +152,7 @@ FULLBAND_RATES = (22050, 24000, 32000, 44100, 48000, 88200, 96000)
 SCORE_FIELDS, SCORE_ROW_FIELDS = 16, 8
 SCORE_TILE = 2560                           # samples per workgroup of score.hip (kScoreTile)
 MIX_FIELDS = 8
+STOI_FIELDS = 8
 MIX_TILE = 2048                             # samples per workgroup and per staging buffer of mix.hip (kMixTile)
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25

@@ -4,7 +4,9 @@ the log-spectral distance of log-magnitude rows (include/nhans_hip.h: nhans_scor
 The device computes the figures (score.hip) -- Context.score / Engine.score_device / Engine.score_rows; this module
 holds their names, the improvement of one record over another, and the float64 numpy DEFINITION the tests and the
 documents measure the device against: `reference` and `reference_rows` form every sum with math.fsum, which is exact, so
-the only roundings in them are the ones the definition names.  No torch here: the command line imports this."""
+the only roundings in them are the ones the definition names.  STOI and extended STOI (stoi.hip: Context.stoi /
+Engine.stoi_device) have theirs in `stoi_reference`, built from the steps below it.  No torch
+here: the command line imports this."""
 import math
 
 import numpy as np
@@ -18,7 +20,15 @@ FIGURES = ("si_sdr_db", "snr_db", "segsnr_db", "loss", "lsd_db")
 SEG_LO, SEG_HI = -10.0, 35.0
 LSD_SCALE = 20.0 / math.log(10.0)
 IMP = np.linspace(2, 1, spec.BINS, dtype=np.float32)        # the reference's loss weights (SN/main.py:245-248)
-_INTS = ("n", "frames", "frames_counted", "frames_skipped")
+STOI_FIELDS = ("n", "frames", "frames_kept", "segments", "stoi", "estoi")     # the first six of NHANS_STOI_FIELDS doubles
+# third-octave bands from 150 Hz as bins [lo, hi) of the 512-point transform at 10 kHz (stoi_band_table re-derives them)
+STOI_BANDS = ((7, 9), (9, 11), (11, 14), (14, 17), (17, 22), (22, 27), (27, 34), (34, 43), (43, 55), (55, 69), (69, 87),
+              (87, 109), (109, 138), (138, 174), (174, 219))
+STOI_RATE, STOI_FRAME, STOI_HOP, STOI_FFT, STOI_SEGMENT = 10000, 256, 128, 512, 30
+STOI_EPS = 2.0 ** -52
+STOI_CLIP = 1.0 + 10.0 ** (15.0 / 20.0)
+STOI_RANGE = 1e-4                                           # 40 dB
+_INTS = ("n", "frames", "frames_counted", "frames_skipped", "frames_kept", "segments", "stoi_n", "stoi_frames")
 
 
 def record(values):
@@ -31,10 +41,23 @@ def row_record(values):
     return {k: (int(values[i]) if k in _INTS else float(values[i])) for i, k in enumerate(ROW_FIELDS)}
 
 
+def stoi_record(values):
+    """NHANS_STOI_FIELDS doubles of one clip -> dict by name."""
+    return {k: (int(values[i]) if k in _INTS else float(values[i])) for i, k in enumerate(STOI_FIELDS)}
+
+
+def merge_stoi(rec, stoi_rec):
+    """A score record with the STOI figures of the same pair merged in; a name the record already has (n, frames: there
+    the 16 kHz samples and the STFT rows) is prefixed: stoi_n, stoi_frames."""
+    return dict(rec, **{("stoi_" + k if k in rec else k): v for k, v in stoi_rec.items()})
+
+
 def improvement(before, after):
     """What `after` gains over `before`, both scored against the same target: the dB differences and the ratio of the
-    losses (below one is better)."""
+    losses (below one is better); where both carry STOI figures, their differences stoi_i and estoi_i too."""
     out = {k[:-3] + "_i": after[k] - before[k] for k in ("si_sdr_db", "snr_db", "segsnr_db") if k in after and k in before}
+    if "stoi" in after and "stoi" in before:
+        out.update(stoi_i=after["stoi"] - before["stoi"], estoi_i=after["estoi"] - before["estoi"])
     if "loss" in after and "loss" in before:
         with np.errstate(divide="ignore", invalid="ignore"):
             out["loss_ratio"] = float(np.float64(after["loss"]) / np.float64(before["loss"]))
@@ -172,4 +195,101 @@ def reference_all(e, t):
     out = reference(e, t)
     rows = reference_rows(features64(e[:n]).astype(np.float32), features64(t[:n]).astype(np.float32))
     out.update(loss=rows["loss"], lsd_db=rows["lsd_db"], frames=rows["frames"])
+    return out
+
+
+# ---- STOI and extended STOI: the float64 definition (include/nhans_hip.h) ----------------------------
+def stoi_out_count(n16):
+    """samples at 10 kHz of n16 samples at 16 kHz: ceil(5 n / 8) (nhans_stoi_out_count)"""
+    return -((-5 * int(n16)) // 8)
+
+
+def stoi_band_table(rate=STOI_RATE, nfft=STOI_FFT, nbands=len(STOI_BANDS), first=150.0):
+    """The bands from their formula: the bins of linspace(0, rate, nfft + 1) nearest to first * 2^(j/3) * 2^(-+1/6)."""
+    f = np.linspace(0, rate, nfft + 1)[:nfft // 2 + 1]
+    cf = first * 2.0 ** (np.arange(nbands) / 3.0)
+    lo, hi = cf * 2.0 ** (-1.0 / 6.0), cf * 2.0 ** (1.0 / 6.0)
+    return tuple((int(np.argmin(np.square(f - a))), int(np.argmin(np.square(f - b)))) for a, b in zip(lo, hi))
+
+
+def stoi_window():
+    """hanning(256): the 256 inner points of a 258-point symmetric Hann window"""
+    return 0.5 * (1.0 - np.cos(2.0 * np.pi * (np.arange(STOI_FRAME) + 1.0) / (STOI_FRAME + 1.0)))
+
+
+def stoi_num_frames(n):
+    return -((STOI_FRAME - int(n)) // STOI_HOP) if n > STOI_FRAME else 0
+
+
+def stoi_frames(x, w):
+    """-> float64 [M0, 256]: the frames of x at hop 128, each times w (a final frame that would end at len(x) is not taken)"""
+    x = np.asarray(x, dtype=np.float64)
+    M = stoi_num_frames(len(x))
+    idx = STOI_HOP * np.arange(M)[:, None] + np.arange(STOI_FRAME)[None, :]
+    return x[idx] * w[None, :] if M else np.zeros((0, STOI_FRAME))
+
+
+def stoi_keep(frames):
+    """windowed frames -> (bool [M0]: P_m > P_max * 1e-4, the powers P_m)"""
+    p = np.array([_fsum(f * f) for f in frames], dtype=np.float64)
+    return (p > p.max() * STOI_RANGE if len(p) else np.zeros(0, bool)), p
+
+
+def stoi_rejoin(frames):
+    """kept windowed frames [Mk, 256] -> their overlap-add at hop 128, 128 (Mk - 1) + 256 samples (none for Mk == 0)"""
+    out = np.zeros(STOI_HOP * (len(frames) - 1) + STOI_FRAME if len(frames) else 0)
+    for k, f in enumerate(frames):
+        out[STOI_HOP * k:STOI_HOP * k + STOI_FRAME] += f
+    return out
+
+
+def stoi_bands_of(frames, bands=STOI_BANDS):
+    """windowed analysis frames [Mf, 256] -> float64 [Mf, 15]: sqrt of each band's summed |rfft(frame, 512)|^2"""
+    X = np.fft.rfft(frames, n=STOI_FFT, axis=1) if len(frames) else np.zeros((0, STOI_FFT // 2 + 1), complex)
+    p = X.real * X.real + X.imag * X.imag
+    return np.array([[math.sqrt(_fsum(row[lo:hi])) for lo, hi in bands] for row in p], dtype=np.float64).reshape(len(frames), len(bands))
+
+
+def _unit(v):
+    """v (1-D) made zero-mean and divided by its norm + eps"""
+    c = v - _fsum(v) / len(v)
+    return c / (math.sqrt(_fsum(c * c)) + STOI_EPS)
+
+
+def stoi_segment(X, Y, clip=STOI_CLIP):
+    """[30, 15] band values of the target and of the estimate -> d_s"""
+    terms = []
+    for j in range(X.shape[1]):
+        x, y = X[:, j], Y[:, j]
+        a = math.sqrt(_fsum(x * x)) / (math.sqrt(_fsum(y * y)) + STOI_EPS)
+        terms.append(_unit(x) * _unit(np.minimum(a * y, clip * x)))
+    return _fsum(np.concatenate(terms)) / X.shape[1]
+
+
+def estoi_segment(X, Y):
+    """[30, 15] band values of the target and of the estimate -> e_s: rows (bands) normalised, then columns"""
+    def both(A):
+        R = np.stack([_unit(A[:, j]) for j in range(A.shape[1])], axis=1)
+        return np.stack([_unit(R[q]) for q in range(A.shape[0])], axis=0)
+    return _fsum((both(X) * both(Y)).ravel()) / X.shape[0]
+
+
+def stoi_reference(e10, t10, per_segment=False):
+    """STOI and extended STOI of estimate e10 against target t10 (float32 values at 10 kHz; scored over the common prefix)
+    as the header defines them -> dict by STOI_FIELDS (per_segment=True: plus "per_segment", float64 [segments, 2] = d_s,
+    e_s)."""
+    n = min(len(e10), len(t10))
+    e, t = np.asarray(e10[:n], dtype=np.float32).astype(np.float64), np.asarray(t10[:n], dtype=np.float32).astype(np.float64)
+    w = stoi_window()
+    ft, fe = stoi_frames(t, w), stoi_frames(e, w)
+    keep, _ = stoi_keep(ft)
+    X = stoi_bands_of(stoi_frames(stoi_rejoin(ft[keep]), w))
+    Y = stoi_bands_of(stoi_frames(stoi_rejoin(fe[keep]), w))
+    S = max(len(X) - STOI_SEGMENT + 1, 0)
+    per = np.array([[stoi_segment(X[s:s + STOI_SEGMENT], Y[s:s + STOI_SEGMENT]),
+                     estoi_segment(X[s:s + STOI_SEGMENT], Y[s:s + STOI_SEGMENT])] for s in range(S)], dtype=np.float64).reshape(S, 2)
+    out = {"n": n, "frames": len(ft), "frames_kept": int(keep.sum()), "segments": S,
+           "stoi": _fsum(per[:, 0]) / S if S else float("nan"), "estoi": _fsum(per[:, 1]) / S if S else float("nan")}
+    if per_segment:
+        out["per_segment"] = per
     return out

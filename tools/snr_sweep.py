@@ -6,7 +6,9 @@ over the mixture, per (snr_pos, snr_neg, look-ahead).  The recordings are read a
 ON THE SYNTHETIC WEIGHTS THESE NUMBERS SAY NOTHING ABOUT QUALITY: a seeded random network denoises nothing.  The tool is
 for whoever has the trained bundle -- point NHANS_MODEL_DIR at it and pass --weights checkpoint; with the synthetic
 weights it shows that the plumbing runs.
-    python tools/snr_sweep.py DIR [--snrs -3,0,3,5,8] [--lookaheads 17,8,2] [--weights synthetic] [--json out.json]
+    python tools/snr_sweep.py DIR [--snrs -3,0,3,5,8] [--lookaheads 17,8,2] [--weights synthetic] [--json out.json] [--stoi]
+  --stoi adds the columns stoi_i and estoi_i: STOI and extended STOI in the same pass (NaN for a job whose output is too
+  short for one 30-frame segment: 4,097 samples at 10 kHz).
   DIR holds <name>_speech.wav, <name>_pos.wav and <name>_neg.wav per triple (16 kHz int16; the speech longer than 200
   frames = 32,240 samples).  No DIR: three synthetic triples written to a temporary directory."""
 import argparse
@@ -23,6 +25,7 @@ import nhans_amd  # noqa: E402,F401
 from nhans_amd import apply, engine, spec, synth  # noqa: E402
 
 FIGURES = ("si_sdr_i", "snr_i", "segsnr_i", "loss_ratio")
+STOI_FIGURES = ("stoi_i", "estoi_i")
 
 
 def find_triples(directory):
@@ -42,22 +45,22 @@ def synthetic_triples(directory):
     return find_triples(directory)
 
 
-def table(rows):
+def table(rows, figures=FIGURES):
     """rows: dicts with snr_pos, snr_neg, lookahead and the means -> the printed table"""
-    head = "%8s %8s %5s %6s" % ("snr_pos", "snr_neg", "L", "jobs") + "".join("%12s" % f for f in FIGURES)
+    head = "%8s %8s %5s %6s" % ("snr_pos", "snr_neg", "L", "jobs") + "".join("%12s" % f for f in figures)
     lines = [head]
     for r in rows:
-        lines.append("%8g %8g %5d %6d" % (r["snr_pos"], r["snr_neg"], r["lookahead"], r["jobs"]) + "".join("%12.4f" % r[f] for f in FIGURES))
+        lines.append("%8g %8g %5d %6d" % (r["snr_pos"], r["snr_neg"], r["lookahead"], r["jobs"]) + "".join("%12.4f" % r[f] for f in figures))
     return "\n".join(lines)
 
 
-def summarise(results, lookahead):
+def summarise(results, lookahead, figures=FIGURES):
     """evaluate_corpus's records -> one row per SNR pair: the plain means of the improvements"""
     groups = {}
     for r in results:
         groups.setdefault((r["snr_pos"], r["snr_neg"]), []).append(r["improvement"])
     return [dict({"snr_pos": p, "snr_neg": n, "lookahead": lookahead, "jobs": len(g)},
-                 **{f: float(np.mean([x[f] for x in g])) for f in FIGURES}) for (p, n), g in sorted(groups.items())]
+                 **{f: float(np.mean([x[f] for x in g])) for f in figures}) for (p, n), g in sorted(groups.items())]
 
 
 def main(argv=None):
@@ -67,7 +70,9 @@ def main(argv=None):
     ap.add_argument("--lookaheads", default=str(spec.LOOKAHEAD))
     ap.add_argument("--weights", default="synthetic", choices=["synthetic", "checkpoint"])
     ap.add_argument("--json", default=None, help="also write the rows as JSON")
+    ap.add_argument("--stoi", action="store_true", help="also the mean improvements of STOI and extended STOI: stoi_i, estoi_i")
     a = ap.parse_args(argv)
+    figures = FIGURES + (STOI_FIGURES if a.stoi else ())
     grid = [float(v) if "." in v else int(v) for v in a.snrs.split(",")]
     las = [int(v) for v in a.lookaheads.split(",")]
     for L in las:
@@ -87,9 +92,9 @@ def main(argv=None):
         pairs = [(p, n) for p in grid for n in grid]
         rows = []
         for L in las:
-            rows += summarise(apply.evaluate_corpus(triples, snrs=pairs, lookahead=L), L)
+            rows += summarise(apply.evaluate_corpus(triples, snrs=pairs, lookahead=L, stoi=a.stoi), L, figures)
         print("%d triples x %d SNR pairs x %d look-aheads, weights: %s" % (len(triples), len(pairs), len(las), a.weights))
-        print(table(rows))
+        print(table(rows, figures))
         if a.json:
             with open(a.json, "w") as f:
                 json.dump({"triples": len(triples), "weights": a.weights, "rows": rows}, f, indent=1)
