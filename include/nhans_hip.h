@@ -16,7 +16,10 @@
  * on success or a negative NHANS_E* code, with a message in nhans_last_error() (thread-local).
  * `*_dev` pointers are device (HBM) addresses owned by the caller; `*_host` pointers are host
  * arrays.  `stream` is a hipStream_t (0 = default stream); all work is enqueued on it and the
- * functions do not synchronise.  The library owns only its context: folded weights and a
+ * functions do not synchronise.  Caller-owned memory: a call writes the counted elements of each clip's room -- the
+ * elements its section documents -- and nothing else of the caller's memory, whatever the alignment of the pointers and
+ * however much larger a room is than its count, and it reads no element outside the ranges its offsets name
+ * (tests/test_gpu_memory_contract.py holds every entry point to this).  The library owns only its context: folded weights and a
  * workspace that grows on demand.  One context per (device, model); a context is not
  * thread-safe, distinct contexts are independent (also on different devices of one process).
  * Consecutive calls on one context share its workspace: the library orders them itself -- a call
