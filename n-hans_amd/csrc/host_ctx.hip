@@ -99,8 +99,8 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
-int ws_reserve(nhans_ctx* c, size_t bytes) {
-    if (bytes <= c->ws_bytes) { c->ws_top = 0; return NHANS_OK; }
+static int ws_reserve(nhans_ctx* c, size_t bytes) {
+    if (bytes <= c->ws_bytes) return NHANS_OK;
     if (c->ws) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->ws)); c->ws = nullptr; c->ws_bytes = 0; }
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->ws), bytes);
     if (e != hipSuccess) {
@@ -109,7 +109,13 @@ int ws_reserve(nhans_ctx* c, size_t bytes) {
         return fail(NHANS_ENOMEM, buf);
     }
     c->ws_bytes = bytes;
-    c->ws_top = 0;
+    return NHANS_OK;
+}
+
+int ws_commit(nhans_ctx* c, const WsPlan& p) {
+    if (!p.ok()) return fail(NHANS_EINVAL, "workspace plan: more than " + std::to_string(WsPlan::kCap) + " buffers");
+    const int rc = ws_reserve(c, p.bytes()); if (rc) return rc;
+    p.place(c->ws);         // (only now: the reserve may have freed what the workspace was)
     return NHANS_OK;
 }
 
@@ -168,7 +174,7 @@ int Call::finish(int body_rc) {
     return body_rc ? body_rc : lrc;
 }
 
-// ---- argument checks the streaming objects share ----------------------------------------------------
+// ---- argument checks several units share (slot_check, push_check: the streaming objects) -------------
 int slot_check(int S, int slot, const char* fn) {
     if (slot < 0 || slot >= S)
         return fail(NHANS_EINVAL, std::string(fn) + ": slot " + std::to_string(slot) + " outside [0, " + std::to_string(S) + ")");
@@ -186,6 +192,14 @@ int push_check(const char* fn, const char* noun, int i, int64_t cnt, bool en, bo
     if (uncond && (cnt > 0 || en))
         return fail(NHANS_EINVAL, std::string(fn) + ": slot " + std::to_string(i) + " has no conditioning yet (" + uncond + ")");
     if (cnt > max_cnt) return fail(NHANS_EINVAL, std::string(fn) + ": push too large for one call (split it)");
+    return NHANS_OK;
+}
+
+int offsets_check(const std::string& fn, const char* what, const int64_t* off, int nclips) {
+    for (int i = 0; i < nclips; ++i)
+        if (off[i + 1] < off[i])
+            return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + ": the " + what + " offsets descend (" +
+                                      std::to_string(off[i]) + " -> " + std::to_string(off[i + 1]) + ")");
     return NHANS_OK;
 }
 

@@ -165,8 +165,10 @@ int nhans_fbank_rows(nhans_fbank* fb, const float* logmag, int64_t nrows, float*
         if (nrows < 0) return fail(NHANS_EINVAL, "nhans_fbank_rows: negative row count");
         if (nrows == 0) return (int)NHANS_OK;
         if (!logmag || !out) return fail(NHANS_EINVAL, "nhans_fbank_rows: null buffer");
-        int rc = ws_reserve(fb->c, ws_size(1, sizeof(FbankRun))); if (rc) return rc;
-        FbankRun* runs_dev = ws_take<FbankRun>(fb->c, 1);
+        WsPlan p;
+        FbankRun* runs_dev;     // (fbank_launch fills and copies the one run)
+        p.add(&runs_dev, 1);
+        const int rc = ws_commit(fb->c, p); if (rc) return rc;
         const FbankRows rows{logmag, out, nrows};
         return fbank_launch(fb->c, fb->t, "fbank_rows", &rows, 1, runs_dev, s);
     });

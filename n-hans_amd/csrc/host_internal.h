@@ -1,5 +1,7 @@
 // What the host units of libnhans_hip.so share (the C ABI itself: include/nhans_hip.h).  One unit per subsystem:
-//   host_ctx.hip      error channel, blob, context, options, calibration, workspace growth, Call, status, profiling
+//   ws_plan.h         WsPlan: a call's device scratch, each buffer declared once (knows neither HIP nor the context)
+//   host_ctx.hip      error channel, blob, context, options, calibration, workspace growth and ws_commit, Call, status,
+//                     profiling, the argument checks several units share
 //   host_net.hip      conv launch sequences (tower, stack, head), STFT / iSTFT block tables, the offline entry points
 //   host_fbank.hip    filterbank design and table, nhans_fbank_design / _open / _close / _rows
 //   host_online.hip   nhans_online_*, nhans_capture_*, nhans_fbank_online_*
@@ -17,6 +19,7 @@
 #pragma once
 #include "../../include/nhans_hip.h"
 #include "nhans_kernels.h"
+#include "ws_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -77,7 +80,7 @@ struct nhans_ctx {
     std::vector<int> cond_off;      // column offset of conv j (= 2*block + {0,1})
     // workspace
     char* ws = nullptr;
-    size_t ws_bytes = 0, ws_top = 0;
+    size_t ws_bytes = 0;
     // split-K scratch of the conv kernel (small launches only)
     // Allocated LAZILY, sized by the launches that actually split (run_conv: conv_splitk_scratch_bytes) and grown up to
     // 96 tiles x 32 groups x 128 KB = 384 MB, all the split-K rule of conv_igemm_dma.hip admits (round-5 advisor: 384 MB
@@ -151,18 +154,21 @@ struct nhans_ctx {
 
 #pragma GCC visibility push(hidden)
 
-int ws_reserve(nhans_ctx* c, size_t bytes);
+// A call's scratch: declare every buffer in a WsPlan (ws_plan.h), then commit -- the workspace grows to the plan's bytes
+// if it has to (synchronise, free, allocate) and every declared pointer is placed in it, from offset 0.  One call may
+// commit several plans in sequence: each takes the workspace from offset 0 again, and stream order makes that safe.
+int ws_commit(nhans_ctx* c, const WsPlan& p);
 // Host -> device copy of a small table through the pinned ring, so the caller's (pageable, soon
 // destroyed) buffer is never the source of an in-flight asynchronous copy.
 int h2d(nhans_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t s);
 
-template <typename T> T* ws_take(nhans_ctx* c, size_t count) {
-    size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-    T* p = reinterpret_cast<T*>(c->ws + c->ws_top);
-    c->ws_top += bytes;
-    return p;
+// The plan of a call whose only scratch is one host table: room for it, and its copy on s.
+template <typename T> int ws_upload(nhans_ctx* c, const std::vector<T>& v, hipStream_t s, T** dev) {
+    WsPlan p;
+    p.add(dev, v.size());
+    const int rc = ws_commit(c, p); if (rc) return rc;
+    return h2d(c, *dev, v.data(), v.size() * sizeof(T), s);
 }
-inline size_t ws_size(size_t count, size_t elem) { return (count * elem + 255) & ~(size_t)255; }
 
 // RAII-less profiling bracket around one launch
 struct Prof {
@@ -225,6 +231,8 @@ int object_call(Obj* o, const char* null_msg, void* stream, Body body) {
 int slot_check(int S, int slot, const char* fn);
 constexpr int64_t kMaxResampleClip = ((int64_t)1 << 31) - 1, kNoPushCap = std::numeric_limits<int64_t>::max();
 int push_check(const char* fn, const char* noun, int i, int64_t cnt, bool en, bool ended, const char* uncond, int64_t max_cnt);
+// the nclips + 1 offsets `off` (`what`: which ones, for the message) do not descend
+int offsets_check(const std::string& fn, const char* what, const int64_t* off, int nclips);
 
 // ---- host_net.hip ---------------------------------------------------------------------------------
 struct StackBufs {
@@ -232,9 +240,11 @@ struct StackBufs {
     float* X; float* A; float* Y;
     float* T;       // f32 output of a block's 1x1 `_transform` conv when its conv2 runs in Winograd form
 };
-size_t stack_ws_bytes(const nhans_ctx* c, int64_t total, int nclips, int64_t wf);
-void stack_take(nhans_ctx* c, int64_t total, int nclips, int64_t wf, StackBufs* sb);
-size_t tower_buf_floats(const nhans_ctx* c);
+void stack_plan(WsPlan& p, const nhans_ctx* c, int64_t total, int nclips, int64_t wf, StackBufs* sb);
+struct TowerBufs {
+    float *X, *A, *Y;       // the embedding tower's three ping-pong buffers, contexts_per_chunk images each
+};
+void tower_plan(WsPlan& p, const nhans_ctx* c, TowerBufs* tb);
 size_t stft_blocks(const int64_t* soff, int nclips, int maxf);
 size_t istft_blocks(const int64_t* foff, int nclips);
 int stft_impl(nhans_ctx* c, const float* wav, const int64_t* soff, int nclips, int maxf, float* logmag,
@@ -243,8 +253,7 @@ int stft_impl(nhans_ctx* c, const float* wav, const int64_t* soff, int nclips, i
 int istft_impl(nhans_ctx* c, const float* logmag, const float* phase, const int64_t* foff, int nclips,
                const int64_t* ooff, float* wav_out, int64_t* dev_tables, int* dev_blocks, hipStream_t s,
                const char* prof_name = "istft_ola");
-int embed_impl(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, float* X, float* Ab, float* Y,
-               hipStream_t s);
+int embed_impl(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, const TowerBufs& tb, hipStream_t s);
 int mask_net_run(nhans_ctx* c, const float* win_src, const int* rb, const float* centre, int64_t total, int nclips,
                  const float* ea, const float* eb, float* logits, float* denoised, const StackBufs& sb, int64_t wf,
                  hipStream_t s);

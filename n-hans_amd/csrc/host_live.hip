@@ -167,9 +167,8 @@ int live_level(nhans_live* o, const int64_t* ooff, const int* end, hipStream_t s
         next->cur[i] = (char)(1 - k);
     }
     if (runs.empty()) return NHANS_OK;
-    int rc = ws_reserve(c, ws_size(runs.size(), sizeof(LevelRun))); if (rc) return rc;
-    LevelRun* runs_dev = ws_take<LevelRun>(c, runs.size());
-    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(LevelRun), s); if (rc) return rc;
+    LevelRun* runs_dev;
+    const int rc = ws_upload(c, runs, s, &runs_dev); if (rc) return rc;
     Prof pr(c, s, "live_level");
     launch_level("live_level", runs_dev, (int)runs.size(), s);
     pr.done(9.0 * (double)(ooff[S] - ooff[0]), 8.0 * (double)(ooff[S] - ooff[0]) + (double)runs.size() * 2 * kLevelState * 8);
@@ -196,9 +195,8 @@ int live_hold(nhans_live* o, const void* in, const int64_t* pos, const Interleav
         samples += (double)(n_old[i] + cnt[i] - keep[i]);
     }
     if (runs.empty()) return NHANS_OK;
-    int rc = ws_reserve(c, ws_size(runs.size(), sizeof(HoldRun))); if (rc) return rc;
-    HoldRun* runs_dev = ws_take<HoldRun>(c, runs.size());
-    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(HoldRun), s); if (rc) return rc;
+    HoldRun* runs_dev;
+    const int rc = ws_upload(c, runs, s, &runs_dev); if (rc) return rc;
     Prof pr(c, s, "live_hold");
     launch_hold("live_hold", runs_dev, (int)runs.size(), s);
     pr.done(0, 8.0 * samples);
@@ -722,9 +720,8 @@ int nhans_level_gains(nhans_ctx* c, const float* den, const float* mix, const in
         hops += nh;
     }
     if (runs.empty()) return call.finish(NHANS_OK);
-    rc = ws_reserve(c, ws_size(runs.size(), sizeof(LevelRun))); if (rc) return call.finish(rc);
-    LevelRun* runs_dev = ws_take<LevelRun>(c, runs.size());
-    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(LevelRun), call.s); if (rc) return call.finish(rc);
+    LevelRun* runs_dev;
+    rc = ws_upload(c, runs, call.s, &runs_dev); if (rc) return call.finish(rc);
     const double n = (double)(off[nclips] - off[0]);
     Prof pr(c, call.s, "level_gains");
     launch_level("level_gains", runs_dev, (int)runs.size(), call.s);

@@ -58,13 +58,13 @@ int nhans_mix(nhans_ctx* c, const float* speech, const int64_t* soff, int nspeec
     Call call(c, stream);
     if (call.rc) return call.rc;
     if (njobs == 0) return call.finish(NHANS_OK);
-    int rc = ws_reserve(c, ws_size(chains.size(), sizeof(MixChain)) + ws_size(jobs.size(), sizeof(MixJob)) + ws_size(chains.size(), 8) +
-                               ws_size((size_t)tiles, 4));
-    if (rc) return call.finish(rc);
-    MixChain* chains_dev = ws_take<MixChain>(c, chains.size());
-    MixJob* jobs_dev = ws_take<MixJob>(c, jobs.size());
-    double* pw = ws_take<double>(c, chains.size());
-    float* peaks = ws_take<float>(c, (size_t)tiles);
+    WsPlan p;
+    MixChain* chains_dev; MixJob* jobs_dev; double* pw; float* peaks;
+    p.add(&chains_dev, chains.size());
+    p.add(&jobs_dev, jobs.size());
+    p.add(&pw, chains.size());
+    p.add(&peaks, (size_t)tiles);
+    int rc = ws_commit(c, p); if (rc) return call.finish(rc);
     rc = h2d(c, chains_dev, chains.data(), chains.size() * sizeof(MixChain), call.s); if (rc) return call.finish(rc);
     rc = h2d(c, jobs_dev, jobs.data(), jobs.size() * sizeof(MixJob), call.s); if (rc) return call.finish(rc);
     const double n = (double)samples, T = (double)tiles, J = (double)njobs;

@@ -390,13 +390,12 @@ struct HostTables {
 }  // namespace
 
 // ---- embedding tower for `n` context images already in HBM ----------------------------------
-int embed_impl(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, float* X, float* Ab, float* Y,
-               hipStream_t s) {
+int embed_impl(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, const TowerBufs& tb, hipStream_t s) {
     const auto& T = c->tower;
     for (int i0 = 0; i0 < n; i0 += c->contexts_per_chunk) {
         const int nc = std::min(c->contexts_per_chunk, n - i0);
         const float* img = ctx_lm + (size_t)i0 * kCtxFrames * kBins;
-        float *x = X, *a1 = Ab, *y = Y;
+        float *x = tb.X, *a1 = tb.A, *y = tb.Y;
         for (int b = 0; b < 4; ++b) {
             const BlockGeo& g = T[b];
             const std::string p = "t" + std::to_string(b);
@@ -453,27 +452,25 @@ int embed_impl(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, float* 
     return NHANS_OK;
 }
 
-size_t tower_buf_floats(const nhans_ctx* c) {
+static size_t tower_buf_floats(const nhans_ctx* c) {
     size_t m = 0;
     for (const auto& g : c->tower) m = std::max(m, (size_t)g.hout * g.wout * g.cout);
     return m * (size_t)c->contexts_per_chunk;
 }
 
-// ---- conditioned stack + head ---------------------------------------------------------------
-size_t stack_ws_bytes(const nhans_ctx* c, int64_t total, int nclips, int64_t wf) {
-    size_t b = 3 * ws_size(total, 4) + ws_size(nclips + 1, 8) + ws_size((size_t)nclips * c->cond_cols, 4);
-    b += 3 * ws_size(stack_buf_floats(c, wf), 4);
-    b += ws_size(transform_buf_floats(c, wf), 4);
-    return b;
+void tower_plan(WsPlan& p, const nhans_ctx* c, TowerBufs* tb) {
+    const size_t nb = tower_buf_floats(c);
+    p.add(&tb->X, nb); p.add(&tb->A, nb); p.add(&tb->Y, nb);
 }
 
-void stack_take(nhans_ctx* c, int64_t total, int nclips, int64_t wf, StackBufs* sb) {
-    sb->f_clip = ws_take<int>(c, total); sb->f_t = ws_take<int>(c, total); sb->f_T = ws_take<int>(c, total);
-    sb->foff_dev = ws_take<int64_t>(c, nclips + 1);
-    sb->cb_all = ws_take<float>(c, (size_t)nclips * c->cond_cols);
+// ---- conditioned stack + head ---------------------------------------------------------------
+void stack_plan(WsPlan& p, const nhans_ctx* c, int64_t total, int nclips, int64_t wf, StackBufs* sb) {
+    p.add(&sb->f_clip, total); p.add(&sb->f_t, total); p.add(&sb->f_T, total);
+    p.add(&sb->foff_dev, nclips + 1);
+    p.add(&sb->cb_all, (size_t)nclips * c->cond_cols);
     const size_t nb = stack_buf_floats(c, wf);
-    sb->X = ws_take<float>(c, nb); sb->A = ws_take<float>(c, nb); sb->Y = ws_take<float>(c, nb);
-    sb->T = ws_take<float>(c, transform_buf_floats(c, wf));
+    p.add(&sb->X, nb); p.add(&sb->A, nb); p.add(&sb->Y, nb);
+    p.add(&sb->T, transform_buf_floats(c, wf));
 }
 
 // The stack + head over `total` frame windows whose per-frame tables (sb.f_clip, f_t, f_T) are in place.  win_src / rb:
@@ -606,34 +603,31 @@ int enhance_clips_body(nhans_ctx* c, const float* mix, const int64_t* moff, int 
     const size_t nb_mix = stft_blocks(moff, nclips, 0), nb_ca = stft_blocks(caoff, nclips, kCtxFrames),
                  nb_cb = stft_blocks(cboff, nclips, kCtxFrames), nb_is = istft_blocks(foff.data(), nclips);
     const size_t nblk = std::max(std::max(nb_mix, nb_ca), std::max(nb_cb, nb_is));
-    size_t bytes = 4 * ws_size((size_t)total * kBins, 4) + ws_size((size_t)2 * nclips * kCtxFrames * kBins, 4) +
-                   ws_size((size_t)2 * nclips * kEmb, 4) + 4 * ws_size(2 * (nclips + 1), 8) + 4 * ws_size(2 * nblk, 4);
-    bytes += std::max(stack_ws_bytes(c, total, nclips, wf), 3 * ws_size(tower_buf_floats(c), 4));
-    rc = ws_reserve(c, bytes); if (rc) return rc;
-    float* lm = ws_take<float>(c, (size_t)total * kBins);
-    float* ph = ws_take<float>(c, (size_t)total * kBins);
-    float* den = ws_take<float>(c, (size_t)total * kBins);
-    float* lg = ws_take<float>(c, (size_t)total * kBins);
-    float* ctxlm = ws_take<float>(c, (size_t)2 * nclips * kCtxFrames * kBins);
-    float* emb = ws_take<float>(c, (size_t)2 * nclips * kEmb);
+    WsPlan p;
+    float *lm, *ph, *den, *lg, *ctxlm, *emb;
     int64_t* tabs[4]; int* blks[4];
-    for (int i = 0; i < 4; ++i) { tabs[i] = ws_take<int64_t>(c, 2 * (nclips + 1)); blks[i] = ws_take<int>(c, 2 * nblk); }
-    const size_t mark = c->ws_top;
+    TowerBufs tb; StackBufs sb;
+    p.add(&lm, (size_t)total * kBins);
+    p.add(&ph, (size_t)total * kBins);
+    p.add(&den, (size_t)total * kBins);
+    p.add(&lg, (size_t)total * kBins);
+    p.add(&ctxlm, (size_t)2 * nclips * kCtxFrames * kBins);
+    p.add(&emb, (size_t)2 * nclips * kEmb);
+    for (int i = 0; i < 4; ++i) { p.add(&tabs[i], 2 * (nclips + 1)); p.add(&blks[i], 2 * nblk); }
+    // (the tower is done with its buffers before the stack's first launch, on the same stream: the two share their place)
+    const size_t shared = p.mark();
+    tower_plan(p, c, &tb);
+    p.rewind(shared);
+    stack_plan(p, c, total, nclips, wf, &sb);
+    rc = ws_commit(c, p); if (rc) return rc;
 
     rc = stft_impl(c, mix, moff, nclips, 0, lm, ph, tabs[0], blks[0], nullptr, s); if (rc) return rc;
     rc = stft_impl(c, ca, caoff, nclips, kCtxFrames, ctxlm, nullptr, tabs[1], blks[1], nullptr, s); if (rc) return rc;
     rc = stft_impl(c, cbw, cboff, nclips, kCtxFrames, ctxlm + (size_t)nclips * kCtxFrames * kBins, nullptr, tabs[2],
                    blks[2], nullptr, s);
     if (rc) return rc;
-    {
-        const size_t nb = tower_buf_floats(c);
-        float* X = ws_take<float>(c, nb); float* A = ws_take<float>(c, nb); float* Y = ws_take<float>(c, nb);
-        rc = embed_impl(c, ctxlm, 2 * nclips, emb, X, A, Y, s); if (rc) return rc;
-    }
+    rc = embed_impl(c, ctxlm, 2 * nclips, emb, tb, s); if (rc) return rc;
     if (total > 0) {
-        c->ws_top = mark;
-        StackBufs sb;
-        stack_take(c, total, nclips, wf, &sb);
         rc = mask_net_impl(c, lm, foff.data(), nclips, emb, emb + (size_t)nclips * kEmb, lg, den, sb, wf, s);
         if (rc) return rc;
         rc = istft_impl(c, den, ph, foff.data(), nclips, moff, den_wav, tabs[3], blks[3], s); if (rc) return rc;
@@ -655,12 +649,17 @@ extern "C" {
 size_t nhans_workspace_bytes(nhans_ctx* c, int64_t total_frames, int nclips) {
     if (!c) return 0;
     const int64_t wf = std::min<int64_t>(c->frames_per_chunk, std::max<int64_t>(total_frames, 1));
-    size_t b = stack_ws_bytes(c, total_frames, nclips, wf);
-    b = std::max(b, 3 * ws_size(tower_buf_floats(c), 4));
-    b += 4 * ws_size((size_t)total_frames * kBins, 4);                       // logmag, phase, denoised, logits
-    b += ws_size((size_t)2 * nclips * kCtxFrames * kBins, 4) + ws_size((size_t)2 * nclips * kEmb, 4);
-    b += 1 << 20;
-    return b;
+    // an uncommitted plan, for its size alone: enhance_clips_body's without its small tables -- the rows and the
+    // conditioning, then tower and stack in one place
+    WsPlan p; StackBufs sb; TowerBufs tb; float* f;
+    for (int i = 0; i < 4; ++i) p.add(&f, (size_t)total_frames * kBins);    // logmag, phase, denoised, logits
+    p.add(&f, (size_t)2 * nclips * kCtxFrames * kBins);
+    p.add(&f, (size_t)2 * nclips * kEmb);
+    const size_t shared = p.mark();
+    tower_plan(p, c, &tb);
+    p.rewind(shared);
+    stack_plan(p, c, total_frames, nclips, wf, &sb);
+    return p.bytes() + (1 << 20);
 }
 
 static int stft_features_body(nhans_ctx* c, const float* wav, const int64_t* soff, int nclips, int maxf,
@@ -669,9 +668,10 @@ static int stft_features_body(nhans_ctx* c, const float* wav, const int64_t* sof
     if (!wav || !soff || !logmag || nclips < 0) return fail(NHANS_EINVAL, "null argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t nb = stft_blocks(soff, nclips, maxf);
-    rc = ws_reserve(c, ws_size(2 * (nclips + 1), 8) + ws_size(2 * nb, 4)); if (rc) return rc;
-    int64_t* tabs = ws_take<int64_t>(c, 2 * (nclips + 1));
-    int* blocks = ws_take<int>(c, 2 * nb);
+    WsPlan p;
+    int64_t* tabs; int* blocks;
+    p.add(&tabs, 2 * (nclips + 1)); p.add(&blocks, 2 * nb);
+    rc = ws_commit(c, p); if (rc) return rc;
     return stft_impl(c, wav, soff, nclips, maxf, logmag, phase, tabs, blocks, nullptr, s);
 }
 
@@ -686,10 +686,10 @@ static int embed_body(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, 
     int rc = NHANS_OK;
     if (!ctx_lm || !emb_out || n < 0) return fail(NHANS_EINVAL, "null argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t nb = tower_buf_floats(c);
-    rc = ws_reserve(c, 3 * ws_size(nb, 4)); if (rc) return rc;
-    float* X = ws_take<float>(c, nb); float* A = ws_take<float>(c, nb); float* Y = ws_take<float>(c, nb);
-    return embed_impl(c, ctx_lm, n, emb_out, X, A, Y, s);
+    WsPlan p; TowerBufs tb;
+    tower_plan(p, c, &tb);
+    rc = ws_commit(c, p); if (rc) return rc;
+    return embed_impl(c, ctx_lm, n, emb_out, tb, s);
 }
 
 int nhans_embed(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, void* stream) {
@@ -706,9 +706,9 @@ static int mask_net_body(nhans_ctx* c, const float* logmag, const int64_t* foff,
     const int64_t total = foff[nclips];
     if (total <= 0) return NHANS_OK;
     const int64_t wf = std::min<int64_t>(c->frames_per_chunk, total);
-    rc = ws_reserve(c, stack_ws_bytes(c, total, nclips, wf)); if (rc) return rc;
-    StackBufs sb;
-    stack_take(c, total, nclips, wf, &sb);
+    WsPlan p; StackBufs sb;
+    stack_plan(p, c, total, nclips, wf, &sb);
+    rc = ws_commit(c, p); if (rc) return rc;
     return mask_net_impl(c, logmag, foff, nclips, ea, eb, logits, denoised, sb, wf, s);
 }
 
@@ -726,9 +726,9 @@ static int debug_block_output_body(nhans_ctx* c, const float* logmag, const int6
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t total = foff[nclips];
     if (frame0 < 0 || frame0 + nframes > total) return fail(NHANS_EINVAL, "frame range outside batch");
-    rc = ws_reserve(c, stack_ws_bytes(c, total, nclips, nframes)); if (rc) return rc;
-    StackBufs sb;
-    stack_take(c, total, nclips, nframes, &sb);
+    WsPlan p; StackBufs sb;
+    stack_plan(p, c, total, nclips, nframes, &sb);
+    rc = ws_commit(c, p); if (rc) return rc;
     rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc;
     launch_frame_index(sb.foff_dev, nclips, total, c->lookahead, sb.f_clip, sb.f_t, sb.f_T, s);
     launch_cond(ea, eb, nclips, c->A("cond.w"), c->A("cond.base"), c->cond_cols, sb.cb_all, s);
@@ -772,9 +772,9 @@ static int debug_activation_body(nhans_ctx* c, const float* logmag, const int64_
     const int64_t total = foff[nclips];
     if (frame0 < 0 || frame0 + nframes > total) return fail(NHANS_EINVAL, "frame range outside batch");
     const int64_t wf = std::min<int64_t>(c->frames_per_chunk, nframes);
-    rc = ws_reserve(c, stack_ws_bytes(c, total, nclips, wf)); if (rc) return rc;
-    StackBufs sb;
-    stack_take(c, total, nclips, wf, &sb);
+    WsPlan p; StackBufs sb;
+    stack_plan(p, c, total, nclips, wf, &sb);
+    rc = ws_commit(c, p); if (rc) return rc;
     rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc;
     launch_frame_index(sb.foff_dev, nclips, total, c->lookahead, sb.f_clip, sb.f_t, sb.f_T, s);
     launch_cond(ea, eb, nclips, c->A("cond.w"), c->A("cond.base"), c->cond_cols, sb.cb_all, s);
@@ -803,12 +803,12 @@ static int debug_tower_activation_body(nhans_ctx* c, const float* ctx_lm, int n,
     if (index < 0 || index >= SA(0, 0))
         return fail(NHANS_EINVAL, "activation index outside the tower's 0 .. 7 (stack tensors: nhans_debug_activation)");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t nb = tower_buf_floats(c);
-    rc = ws_reserve(c, 3 * ws_size(nb, 4) + ws_size((size_t)n * kEmb, 4)); if (rc) return rc;
-    float* X = ws_take<float>(c, nb); float* A = ws_take<float>(c, nb); float* Y = ws_take<float>(c, nb);
-    float* emb = ws_take<float>(c, (size_t)n * kEmb);
+    WsPlan p; TowerBufs tb; float* emb;
+    tower_plan(p, c, &tb);
+    p.add(&emb, (size_t)n * kEmb);
+    rc = ws_commit(c, p); if (rc) return rc;
     c->cap_idx = index; c->cap_out = out;
-    rc = embed_impl(c, ctx_lm, n, emb, X, A, Y, s);
+    rc = embed_impl(c, ctx_lm, n, emb, tb, s);
     c->cap_idx = -1; c->cap_out = nullptr;
     return rc;
 }
@@ -825,9 +825,10 @@ static int istft_body(nhans_ctx* c, const float* logmag, const float* phase, con
     if (!logmag || !phase || !foff || !ooff || !wav_out) return fail(NHANS_EINVAL, "null argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t nb = istft_blocks(foff, nclips);
-    rc = ws_reserve(c, ws_size(2 * (nclips + 1), 8) + ws_size(2 * nb, 4)); if (rc) return rc;
-    int64_t* tabs = ws_take<int64_t>(c, 2 * (nclips + 1));
-    int* blocks = ws_take<int>(c, 2 * nb);
+    WsPlan p;
+    int64_t* tabs; int* blocks;
+    p.add(&tabs, 2 * (nclips + 1)); p.add(&blocks, 2 * nb);
+    rc = ws_commit(c, p); if (rc) return rc;
     return istft_impl(c, logmag, phase, foff, nclips, ooff, wav_out, tabs, blocks, s);
 }
 

@@ -48,20 +48,20 @@ int online_open_body(nhans_ctx* c, int S, const float* ca, const int64_t* caoff,
     if (S < 1) return fail(NHANS_EINVAL, "nhans_online_open: nstreams must be >= 1");
     if (!ca || !caoff || !cbw || !cboff) return fail(NHANS_EINVAL, "null argument");
     const size_t nb = std::max(stft_blocks(caoff, S, kCtxFrames), stft_blocks(cboff, S, kCtxFrames));
-    const size_t tb = tower_buf_floats(c);
-    int rc = ws_reserve(c, ws_size((size_t)2 * S * kCtxFrames * kBins, 4) + 2 * ws_size(2 * (S + 1), 8) +
-                               2 * ws_size(2 * nb, 4) + 3 * ws_size(tb, 4));
-    if (rc) return rc;
-    float* ctxlm = ws_take<float>(c, (size_t)2 * S * kCtxFrames * kBins);
+    WsPlan p;
+    float* ctxlm;
     int64_t* tabs[2]; int* blks[2];
-    for (int i = 0; i < 2; ++i) { tabs[i] = ws_take<int64_t>(c, 2 * (S + 1)); blks[i] = ws_take<int>(c, 2 * nb); }
-    float* X = ws_take<float>(c, tb); float* A = ws_take<float>(c, tb); float* Y = ws_take<float>(c, tb);
+    TowerBufs tb;
+    p.add(&ctxlm, (size_t)2 * S * kCtxFrames * kBins);
+    for (int i = 0; i < 2; ++i) { p.add(&tabs[i], 2 * (S + 1)); p.add(&blks[i], 2 * nb); }
+    tower_plan(p, c, &tb);
+    int rc = ws_commit(c, p); if (rc) return rc;
     rc = stft_impl(c, ca, caoff, S, kCtxFrames, ctxlm, nullptr, tabs[0], blks[0], nullptr, s); if (rc) return rc;
     rc = stft_impl(c, cbw, cboff, S, kCtxFrames, ctxlm + (size_t)S * kCtxFrames * kBins, nullptr, tabs[1], blks[1], nullptr, s);
     if (rc) return rc;
     nhans_online* o = nullptr;
     rc = online_alloc(c, S, want_mixed, true, "nhans_online_open", &o); if (rc) return rc;
-    rc = embed_impl(c, ctxlm, 2 * S, o->emb, X, A, Y, s);
+    rc = embed_impl(c, ctxlm, 2 * S, o->emb, tb, s);
     if (rc) { (void)hipFree(o->emb); (void)hipFree(o->state); delete o; return rc; }
     *out = o;
     return NHANS_OK;
@@ -133,20 +133,20 @@ int online_set_context_body(nhans_online* o, int slot, const float* ca, int64_t 
     if (na < 0 || nb_ < 0) return fail(NHANS_EINVAL, "nhans_online_set_context: negative sample count");
     const int64_t aoff[2] = {0, na}, boff[2] = {0, nb_};
     const size_t nb = std::max(stft_blocks(aoff, 1, kCtxFrames), stft_blocks(boff, 1, kCtxFrames));
-    const size_t tb = tower_buf_floats(c);
-    rc = ws_reserve(c, ws_size((size_t)2 * kCtxFrames * kBins, 4) + ws_size(2 * kEmb, 4) + 2 * ws_size(4, 8) +
-                           2 * ws_size(2 * nb, 4) + 3 * ws_size(tb, 4));
-    if (rc) return rc;
-    float* ctxlm = ws_take<float>(c, (size_t)2 * kCtxFrames * kBins);
-    float* rows = ws_take<float>(c, 2 * kEmb);
+    WsPlan p;
+    float *ctxlm, *rows;
     int64_t* tabs[2]; int* blks[2];
-    for (int i = 0; i < 2; ++i) { tabs[i] = ws_take<int64_t>(c, 4); blks[i] = ws_take<int>(c, 2 * nb); }
-    float* X = ws_take<float>(c, tb); float* A = ws_take<float>(c, tb); float* Y = ws_take<float>(c, tb);
+    TowerBufs tb;
+    p.add(&ctxlm, (size_t)2 * kCtxFrames * kBins);
+    p.add(&rows, 2 * kEmb);
+    for (int i = 0; i < 2; ++i) { p.add(&tabs[i], 4); p.add(&blks[i], 2 * nb); }
+    tower_plan(p, c, &tb);
+    rc = ws_commit(c, p); if (rc) return rc;
     rc = stft_impl(c, ca, aoff, 1, kCtxFrames, ctxlm, nullptr, tabs[0], blks[0], nullptr, s); if (rc) return rc;
     rc = stft_impl(c, cbw, boff, 1, kCtxFrames, ctxlm + (size_t)kCtxFrames * kBins, nullptr, tabs[1], blks[1], nullptr, s);
     if (rc) return rc;
     // (the tower writes workspace rows, not the object's: a failure leaves the slot's conditioning as it was)
-    rc = embed_impl(c, ctxlm, 2, rows, X, A, Y, s); if (rc) return rc;
+    rc = embed_impl(c, ctxlm, 2, rows, tb, s); if (rc) return rc;
     if (launch_error_pending()) return NHANS_OK;          // (reported by the entry point; the slot keeps its rows)
     return online_set_rows(o, slot, rows, rows + kEmb, s, first_frame);
 }
@@ -229,33 +229,31 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
     // sample history two more into its ring, of kCaptureSamples floats together)
     const size_t nrun_cap = (size_t)S * 32 + (size_t)(soff[S] + (WR + F + 4 * Y) * kBins + 2 * tot_out) / kOnlineCopyMax + 64 +
                             (o->ring ? (size_t)S * (2 + kCaptureSamples / kOnlineCopyMax + 1) : 0);
-    size_t bytes = ws_size(soff[S], 4) + 2 * ws_size(NF * kBins, 4) + ws_size(WR * kBins, 4) + 2 * ws_size(F * kBins, 4) +
-                   3 * ws_size(Y * kBins, 4) + (o->mixed ? 2 : 1) * ws_size(ooff[S], 4) + 2 * ws_size(2 * (S + 1), 8) +
-                   ws_size(2 * nb_st, 4) + ws_size(2 * nb_is, 4) + ws_size(F, 4) + ws_size(nrun_cap, sizeof(OnlineCopy));
-    if (F > 0) bytes += stack_ws_bytes(c, F, S, wf);
     const bool feats = o->fb.on && F > 0;
-    if (feats) bytes += ws_size(2, sizeof(FbankRun));
-    int rc = ws_reserve(c, bytes); if (rc) return rc;
-    float* wav = ws_take<float>(c, soff[S]);
-    float* nlm = ws_take<float>(c, NF * kBins);
-    float* nph = ws_take<float>(c, NF * kBins);
-    float* win = ws_take<float>(c, WR * kBins);
-    float* ctr = ws_take<float>(c, F * kBins);
-    float* dnew = ws_take<float>(c, F * kBins);
-    float* yden = ws_take<float>(c, Y * kBins);
-    float* yph = ws_take<float>(c, Y * kBins);
-    float* ylm = ws_take<float>(c, Y * kBins);
-    float* tden = ws_take<float>(c, ooff[S]);
-    float* tmix = o->mixed ? ws_take<float>(c, ooff[S]) : nullptr;
-    int64_t* tab_st = ws_take<int64_t>(c, 2 * (S + 1));
-    int64_t* tab_is = ws_take<int64_t>(c, 2 * (S + 1));
-    int* blk_st = ws_take<int>(c, 2 * nb_st);
-    int* blk_is = ws_take<int>(c, 2 * nb_is);
-    int* rb = ws_take<int>(c, F);
-    OnlineCopy* runs_dev = ws_take<OnlineCopy>(c, nrun_cap);
-    StackBufs sb{};
-    if (F > 0) stack_take(c, F, S, wf, &sb);
-    FbankRun* fb_runs = feats ? ws_take<FbankRun>(c, 2) : nullptr;
+    WsPlan ws;
+    float *wav, *nlm, *nph, *win, *ctr, *dnew, *yden, *yph, *ylm, *tden, *tmix = nullptr;
+    int64_t *tab_st, *tab_is; int *blk_st, *blk_is, *rb;
+    OnlineCopy* runs_dev; StackBufs sb{}; FbankRun* fb_runs = nullptr;
+    ws.add(&wav, soff[S]);
+    ws.add(&nlm, NF * kBins);
+    ws.add(&nph, NF * kBins);
+    ws.add(&win, WR * kBins);
+    ws.add(&ctr, F * kBins);
+    ws.add(&dnew, F * kBins);
+    ws.add(&yden, Y * kBins);
+    ws.add(&yph, Y * kBins);
+    ws.add(&ylm, Y * kBins);
+    ws.add(&tden, ooff[S]);
+    if (o->mixed) ws.add(&tmix, ooff[S]);
+    ws.add(&tab_st, 2 * (S + 1));
+    ws.add(&tab_is, 2 * (S + 1));
+    ws.add(&blk_st, 2 * nb_st);
+    ws.add(&blk_is, 2 * nb_is);
+    ws.add(&rb, F);
+    ws.add(&runs_dev, nrun_cap);
+    if (F > 0) stack_plan(ws, c, F, S, wf, &sb);
+    if (feats) ws.add(&fb_runs, 2);
+    int rc = ws_commit(c, ws); if (rc) return rc;
     if (feats) {
         // (before anything goes out: a failed allocation leaves the object and the rows of the last push as they were)
         const size_t need = (size_t)(o->fb.mixed ? 2 : 1) * F * o->fb.t.n_out;
@@ -516,18 +514,19 @@ int capture_context_body(nhans_online* o, const char* fn_, int n, const int* slo
     std::vector<int64_t> soff(n + 1);
     for (int k = 0; k <= n; ++k) soff[k] = (int64_t)k * kCaptureSamples;
     const size_t nb = stft_blocks(soff.data(), n, kCtxFrames);
-    const size_t tb = tower_buf_floats(c);
-    int rc = ws_reserve(c, ws_size((size_t)n * kCaptureSamples, 4) + ws_size((size_t)n * kCtxFrames * kBins, 4) +
-                               ws_size((size_t)n * kEmb, 4) + ws_size(2 * (n + 1), 8) + ws_size(2 * nb, 4) +
-                               ws_size(n, sizeof(CaptureEntry)) + 3 * ws_size(tb, 4));
-    if (rc) return rc;
-    float* clips = ws_take<float>(c, (size_t)n * kCaptureSamples);
-    float* ctxlm = ws_take<float>(c, (size_t)n * kCtxFrames * kBins);
-    float* rows = ws_take<float>(c, (size_t)n * kEmb);
-    int64_t* tabs = ws_take<int64_t>(c, 2 * (n + 1));
-    int* blks = ws_take<int>(c, 2 * nb);
-    CaptureEntry* ent_dev = ws_take<CaptureEntry>(c, n);
-    float* X = ws_take<float>(c, tb); float* A = ws_take<float>(c, tb); float* Y = ws_take<float>(c, tb);
+    WsPlan p;
+    float *clips, *ctxlm, *rows;
+    int64_t* tabs; int* blks;
+    CaptureEntry* ent_dev;
+    TowerBufs tb;
+    p.add(&clips, (size_t)n * kCaptureSamples);
+    p.add(&ctxlm, (size_t)n * kCtxFrames * kBins);
+    p.add(&rows, (size_t)n * kEmb);
+    p.add(&tabs, 2 * (n + 1));
+    p.add(&blks, 2 * nb);
+    p.add(&ent_dev, n);
+    tower_plan(p, c, &tb);
+    int rc = ws_commit(c, p); if (rc) return rc;
     std::vector<CaptureEntry> ent(n);
     for (int k = 0; k < n; ++k)
         ent[k] = {o->ring + (size_t)slots[k] * kCaptureSamples, clips + (size_t)k * kCaptureSamples,
@@ -540,7 +539,7 @@ int capture_context_body(nhans_online* o, const char* fn_, int n, const int* slo
     }
     rc = stft_impl(c, clips, soff.data(), n, kCtxFrames, ctxlm, nullptr, tabs, blks, nullptr, s); if (rc) return rc;
     // (the tower writes workspace rows, not the object's: a failure leaves every slot's conditioning as it was)
-    rc = embed_impl(c, ctxlm, n, rows, X, A, Y, s); if (rc) return rc;
+    rc = embed_impl(c, ctxlm, n, rows, tb, s); if (rc) return rc;
     if (launch_error_pending()) return NHANS_OK;          // (reported by the entry point; the slots keep their rows)
     for (int k = 0; k < n; ++k)
         HIP_TRY(hipMemcpyAsync(o->emb + ((size_t)which[k] * o->S + slots[k]) * kEmb, rows + (size_t)k * kEmb, kEmb * 4,

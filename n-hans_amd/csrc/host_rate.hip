@@ -17,9 +17,8 @@ int rs_filter(const char* fn, int rate_in, int rate_out, const ResampleFilter** 
 int rs_launch(nhans_ctx* c, const char* name, const std::vector<ResampleRun>& runs, const float* tab, const ResampleFilter& f,
               const RateIo& io, size_t lds, double in_bytes, double out_bytes, int64_t out_samples, hipStream_t s) {
     if (runs.empty()) return NHANS_OK;
-    int rc = ws_reserve(c, ws_size(runs.size(), sizeof(ResampleRun))); if (rc) return rc;
-    ResampleRun* runs_dev = ws_take<ResampleRun>(c, runs.size());
-    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(ResampleRun), s); if (rc) return rc;
+    ResampleRun* runs_dev;
+    const int rc = ws_upload(c, runs, s, &runs_dev); if (rc) return rc;
     Prof pr(c, s, name);
     launch_resample(name, runs_dev, (int)runs.size(), tab, f, io.from_mix, io.auto_wet, io.interleaved, io.pcm_format, io.quantise,
                     io.wet, io.factor, lds, s, io.highband);
@@ -168,9 +167,11 @@ int peak_normalise_body(nhans_ctx* c, const float* in, const int64_t* off, int n
     }
     if (blocks.empty()) return NHANS_OK;
     if (!in || !out) return fail(NHANS_EINVAL, "nhans_peak_normalise: null buffer");
-    int rc = ws_reserve(c, ws_size(blocks.size(), sizeof(NormBlock)) + ws_size(blocks.size(), 4)); if (rc) return rc;
-    NormBlock* bd = ws_take<NormBlock>(c, blocks.size());
-    float* partial = ws_take<float>(c, blocks.size());
+    WsPlan p;
+    NormBlock* bd; float* partial;
+    p.add(&bd, blocks.size());
+    p.add(&partial, blocks.size());
+    int rc = ws_commit(c, p); if (rc) return rc;
     rc = h2d(c, bd, blocks.data(), blocks.size() * sizeof(NormBlock), s); if (rc) return rc;
     const double n = (double)(off[nclips] - off[0]);
     { Prof pr(c, s, "peak_partial"); launch_peak_partial(in, bd, (int)blocks.size(), flags & NHANS_NORMALISE_WRAP_INT16, partial, s); pr.done(0, 4.0 * n); }

@@ -2,18 +2,6 @@
 // refuse needs no device and is refused before the context is looked at.
 #include "host_internal.h"
 
-namespace {
-
-int score_offsets_check(const std::string& fn, const char* what, const int64_t* off, int nclips) {
-    for (int i = 0; i < nclips; ++i)
-        if (off[i + 1] < off[i])
-            return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + ": the " + what + " offsets descend (" +
-                                      std::to_string(off[i]) + " -> " + std::to_string(off[i + 1]) + ")");
-    return NHANS_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int nhans_score_wave(nhans_ctx* c, const float* est, const int64_t* eoff, const float* tgt, const int64_t* toff, int nclips,
@@ -21,8 +9,8 @@ int nhans_score_wave(nhans_ctx* c, const float* est, const int64_t* eoff, const 
     const std::string fn = "nhans_score_wave";
     if (nclips < 0) return fail(NHANS_EINVAL, fn + ": negative clip count");
     if (nclips > 0 && (!eoff || !toff || !out)) return fail(NHANS_EINVAL, fn + ": null offsets or null output with " + std::to_string(nclips) + " clips to score");
-    int rc = score_offsets_check(fn, "estimate", eoff, nclips); if (rc) return rc;
-    rc = score_offsets_check(fn, "target", toff, nclips); if (rc) return rc;
+    int rc = offsets_check(fn, "estimate", eoff, nclips); if (rc) return rc;
+    rc = offsets_check(fn, "target", toff, nclips); if (rc) return rc;
     std::vector<ScoreRun> runs((size_t)nclips);
     long long tiles = 0, segs = 0, frames = 0, samples = 0;
     for (int i = 0; i < nclips; ++i) {
@@ -40,11 +28,12 @@ int nhans_score_wave(nhans_ctx* c, const float* est, const int64_t* eoff, const 
     Call call(c, stream);
     if (call.rc) return call.rc;
     if (nclips == 0) return call.finish(NHANS_OK);
-    rc = ws_reserve(c, ws_size(runs.size(), sizeof(ScoreRun)) + ws_size((size_t)tiles * 4, 8) + ws_size((size_t)segs * 2, 8));
-    if (rc) return call.finish(rc);
-    ScoreRun* runs_dev = ws_take<ScoreRun>(c, runs.size());
-    double* part = ws_take<double>(c, (size_t)tiles * 4);
-    double* segp = ws_take<double>(c, (size_t)segs * 2);
+    WsPlan p;
+    ScoreRun* runs_dev; double *part, *segp;
+    p.add(&runs_dev, runs.size());
+    p.add(&part, (size_t)tiles * 4);
+    p.add(&segp, (size_t)segs * 2);
+    rc = ws_commit(c, p); if (rc) return call.finish(rc);
     rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(ScoreRun), call.s); if (rc) return call.finish(rc);
     const double n = (double)samples, T = (double)tiles, S = (double)segs, F = (double)frames, C = (double)nclips;
     {   // per sample: a subtraction and four fused multiply-adds, and the tree
@@ -75,7 +64,7 @@ int nhans_score_rows(nhans_ctx* c, const float* est, const float* tgt, const int
     const std::string fn = "nhans_score_rows";
     if (nclips < 0) return fail(NHANS_EINVAL, fn + ": negative clip count");
     if (nclips > 0 && (!foff || !out)) return fail(NHANS_EINVAL, fn + ": null offsets or null output with " + std::to_string(nclips) + " clips to score");
-    int rc = score_offsets_check(fn, "frame", foff, nclips); if (rc) return rc;
+    int rc = offsets_check(fn, "frame", foff, nclips); if (rc) return rc;
     std::vector<ScoreRowRun> runs((size_t)nclips);
     long long tiles = 0, frames = 0;
     for (int i = 0; i < nclips; ++i) {
@@ -90,10 +79,11 @@ int nhans_score_rows(nhans_ctx* c, const float* est, const float* tgt, const int
     Call call(c, stream);
     if (call.rc) return call.rc;
     if (nclips == 0) return call.finish(NHANS_OK);
-    rc = ws_reserve(c, ws_size(runs.size(), sizeof(ScoreRowRun)) + ws_size((size_t)frames * 2, 8));
-    if (rc) return call.finish(rc);
-    ScoreRowRun* runs_dev = ws_take<ScoreRowRun>(c, runs.size());
-    double* vals = ws_take<double>(c, (size_t)frames * 2);
+    WsPlan p;
+    ScoreRowRun* runs_dev; double* vals;
+    p.add(&runs_dev, runs.size());
+    p.add(&vals, (size_t)frames * 2);
+    rc = ws_commit(c, p); if (rc) return call.finish(rc);
     rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(ScoreRowRun), call.s); if (rc) return call.finish(rc);
     const double F = (double)frames, C = (double)nclips;
     {   // per bin: a subtraction, three products and two fused multiply-adds

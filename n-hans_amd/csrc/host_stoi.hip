@@ -5,14 +5,6 @@
 
 namespace {
 
-int stoi_offsets_check(const std::string& fn, const char* what, const int64_t* off, int nclips) {
-    for (int i = 0; i < nclips; ++i)
-        if (off[i + 1] < off[i])
-            return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + ": the " + what + " offsets descend (" +
-                                      std::to_string(off[i]) + " -> " + std::to_string(off[i + 1]) + ")");
-    return NHANS_OK;
-}
-
 int stoi_resample_body(nhans_ctx* c, const float* in, const int64_t* inoff, int nclips, float* out, const int64_t* outoff,
                        const ResampleFilter& f, hipStream_t s) {
     std::vector<ResampleRun> runs;
@@ -45,8 +37,8 @@ int nhans_stoi_resample(nhans_ctx* c, const float* in, const int64_t* inoff, int
     const std::string fn = "nhans_stoi_resample";
     if (nclips < 0) return fail(NHANS_EINVAL, fn + ": negative clip count");
     if (nclips > 0 && (!inoff || !outoff)) return fail(NHANS_EINVAL, fn + ": null offsets with " + std::to_string(nclips) + " clips to convert");
-    int rc = stoi_offsets_check(fn, "input", inoff, nclips); if (rc) return rc;
-    rc = stoi_offsets_check(fn, "output", outoff, nclips); if (rc) return rc;
+    int rc = offsets_check(fn, "input", inoff, nclips); if (rc) return rc;
+    rc = offsets_check(fn, "output", outoff, nclips); if (rc) return rc;
     const ResampleFilter& f = *resample_filter_stoi();
     for (int i = 0; i < nclips; ++i) {
         const int64_t n = inoff[i + 1] - inoff[i];
@@ -69,8 +61,8 @@ int nhans_stoi(nhans_ctx* c, const float* est, const int64_t* eoff, const float*
     const std::string fn = "nhans_stoi";
     if (nclips < 0) return fail(NHANS_EINVAL, fn + ": negative clip count");
     if (nclips > 0 && (!eoff || !toff || !out)) return fail(NHANS_EINVAL, fn + ": null offsets or null output with " + std::to_string(nclips) + " clips to score");
-    int rc = stoi_offsets_check(fn, "estimate", eoff, nclips); if (rc) return rc;
-    rc = stoi_offsets_check(fn, "target", toff, nclips); if (rc) return rc;
+    int rc = offsets_check(fn, "estimate", eoff, nclips); if (rc) return rc;
+    rc = offsets_check(fn, "target", toff, nclips); if (rc) return rc;
     std::vector<StoiRun> runs((size_t)nclips);
     long long frames = 0, rows = 0, segs = 0, pt = 0, bt = 0, st = 0;
     for (int i = 0; i < nclips; ++i) {
@@ -90,17 +82,16 @@ int nhans_stoi(nhans_ctx* c, const float* est, const int64_t* eoff, const float*
     Call call(c, stream);
     if (call.rc) return call.rc;
     if (nclips == 0) return call.finish(NHANS_OK);
-    rc = ws_reserve(c, ws_size(runs.size(), sizeof(StoiRun)) + ws_size(kStoiTable, 8) + ws_size((size_t)frames, 8) +
-                           ws_size((size_t)frames, 4) + ws_size(runs.size(), 8) + ws_size((size_t)rows * 2 * kStoiBands, 8) +
-                           ws_size((size_t)segs * 2, 8));
-    if (rc) return call.finish(rc);
-    StoiRun* runs_dev = ws_take<StoiRun>(c, runs.size());
-    double* tab = ws_take<double>(c, kStoiTable);
-    double* power = ws_take<double>(c, (size_t)frames);
-    int* kept = ws_take<int>(c, (size_t)frames);
-    long long* nkept = ws_take<long long>(c, runs.size());
-    double* bands = ws_take<double>(c, (size_t)rows * 2 * kStoiBands);
-    double* segv = ws_take<double>(c, (size_t)segs * 2);
+    WsPlan p;
+    StoiRun* runs_dev; double *tab, *power, *bands, *segv; int* kept; long long* nkept;
+    p.add(&runs_dev, runs.size());
+    p.add(&tab, kStoiTable);
+    p.add(&power, (size_t)frames);
+    p.add(&kept, (size_t)frames);
+    p.add(&nkept, runs.size());
+    p.add(&bands, (size_t)rows * 2 * kStoiBands);
+    p.add(&segv, (size_t)segs * 2);
+    rc = ws_commit(c, p); if (rc) return call.finish(rc);
     rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(StoiRun), call.s); if (rc) return call.finish(rc);
     std::vector<double> table(kStoiTable);
     stoi_table(table.data());
