@@ -276,6 +276,14 @@ int nhans_debug_mfma_ceiling(double seconds, void* stream, double* sustained_tfl
  * `cap`: NHANS_EINVAL. */
 int nhans_debug_row_classes(int H, int KH, int stride, int pt, int* out, int cap);
 
+/* Host helper (no device involved): the batch nhans_create calibrates the activation exponents on (see "calibrate") -- two
+ * mixtures of lengths_out[0] samples each, written one after the other to mix_out, and their two pairs of context
+ * recordings of lengths_out[1] samples each, clip 0's then clip 1's, in ctx_a_out and ctx_b_out.  The built-in
+ * calibration is a "calibrate" bracket at precision 0 round nhans_enhance_clips of exactly these arrays (the same
+ * function fills them), so a caller can repeat it and compare.  The three arrays all null: only the lengths are
+ * written.  lengths_out null, or some arrays null and some not: NHANS_EINVAL. */
+int nhans_debug_builtin_batch(float* mix_out, float* ctx_a_out, float* ctx_b_out, int64_t* lengths_out);
+
 /* Host helper (no device involved): CRC-32C (Castagnoli) of a host buffer continued from `crc`
  * (0 to start).  TensorFlow checkpoint bundles store crc32c::Mask() of it per tensor; tfbundle.py
  * verifies the 116 MB data shard with it (BundleEntryProto field 6 of the reference's shipped trained_model .index files). */

@@ -211,13 +211,13 @@ const char* nhans_last_error(void) { return g_err.c_str(); }
 
 int64_t nhans_num_frames(int64_t n) { return n < kWin ? 0 : 1 + (n - kWin) / kHop; }
 
-// Activation exponents of a fresh context: one pass of the whole path at precision 0 over a built-in batch of two clips
-// -- a two-second mixture of a gliding harmonic voice with syllabic amplitude modulation and noise, conditioned once on
-// two noise recordings and once on (silence, noise): an all-zero recording is the reference's default `--pos` and
-// drives the tower with the constant silence floor -- with every tensor's maximum recorded.  Deterministic (LCG).
-static int calibrate_builtin(nhans_ctx* c) {
-    const int64_t n_mix = kWin + (int64_t)kHop * 197, n_ctx = kWin + (int64_t)kHop * (kCtxFrames - 1);
-    std::vector<float> mix(2 * n_mix), ca(2 * n_ctx), cb(2 * n_ctx);
+// The batch of the built-in calibration: two clips -- a two-second mixture of a gliding harmonic voice with syllabic
+// amplitude modulation and noise, conditioned once on two noise recordings and once on (silence, noise): an all-zero
+// recording is the reference's default `--pos` and drives the tower with the constant silence floor.  Deterministic (LCG).
+// mix [2 * n_mix], ca / cb [2 * n_ctx], clip after clip.  calibrate_builtin() and nhans_debug_builtin_batch share it.
+constexpr int64_t kBuiltinMix = kWin + (int64_t)kHop * 197, kBuiltinCtx = kWin + (int64_t)kHop * (kCtxFrames - 1);
+static void builtin_batch(float* mix, float* ca, float* cb) {
+    const int64_t n_mix = kBuiltinMix, n_ctx = kBuiltinCtx;
     uint32_t lcg = 0x2545F491u;
     auto noise = [&]() { lcg = lcg * 1664525u + 1013904223u; return (float)(int32_t)lcg * (1.0f / 2147483648.0f); };
     double ph = 0.0;
@@ -238,6 +238,14 @@ static int calibrate_builtin(nhans_ctx* c) {
         ca[n_ctx + i] = 0.f;                  // clip 1: silence / white noise
         cb[n_ctx + i] = 0.25f * noise();
     }
+}
+
+// Activation exponents of a fresh context: one pass of the whole path at precision 0 over the built-in batch with every
+// tensor's maximum recorded -- a "calibrate" bracket round nhans_enhance_clips of that batch.
+static int calibrate_builtin(nhans_ctx* c) {
+    const int64_t n_mix = kBuiltinMix, n_ctx = kBuiltinCtx;
+    std::vector<float> mix(2 * n_mix), ca(2 * n_ctx), cb(2 * n_ctx);
+    builtin_batch(mix.data(), ca.data(), cb.data());
     const int64_t moff[3] = {0, n_mix, 2 * n_mix}, coff[3] = {0, n_ctx, 2 * n_ctx};
     float* dev = nullptr;
     const size_t words = (size_t)4 * n_mix + (size_t)4 * n_ctx;
@@ -496,6 +504,16 @@ int nhans_debug_launch_probe(size_t dynamic_lds_bytes, void* stream) {
     NHANS_LAUNCH("launch_probe", launch_probe_kernel, dim3(1), dim3(64), dynamic_lds_bytes, static_cast<hipStream_t>(stream),
                  static_cast<int*>(nullptr));
     return launch_status();
+}
+
+int nhans_debug_builtin_batch(float* mix_out, float* ctx_a_out, float* ctx_b_out, int64_t* lengths_out) {
+    if (!lengths_out) return fail(NHANS_EINVAL, "built-in batch: null lengths");
+    if ((mix_out || ctx_a_out || ctx_b_out) && !(mix_out && ctx_a_out && ctx_b_out))
+        return fail(NHANS_EINVAL, "built-in batch: all three arrays or none");
+    lengths_out[0] = kBuiltinMix;
+    lengths_out[1] = kBuiltinCtx;
+    if (mix_out) builtin_batch(mix_out, ctx_a_out, ctx_b_out);
+    return NHANS_OK;
 }
 
 uint32_t nhans_crc32c(uint32_t crc, const void* data, size_t n) {

@@ -46,6 +46,7 @@ SIGNATURES = {
     "nhans_debug_launch_probe": (_int, [_size, _vp]),
     "nhans_debug_mfma_ceiling": (_int, [_dbl, _vp, _dp, _dp, _ip]),
     "nhans_debug_row_classes": (_int, [_int, _int, _int, _int, _ip, _int]),
+    "nhans_debug_builtin_batch": (_int, [_fp, _fp, _fp, _i64p]),
     "nhans_crc32c": (ctypes.c_uint32, [ctypes.c_uint32, _vp, _size]),
     # online enhancement
     "nhans_online_open": (_int, [_vp, _int, _vp, _i64p, _vp, _i64p, _int, _vp, _vpp]),
@@ -218,6 +219,19 @@ def mfma_ceiling(seconds, stream=None):
     sus, first, n = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int(0)
     check(load().nhans_debug_mfma_ceiling(float(seconds), stream, ctypes.byref(sus), ctypes.byref(first), ctypes.byref(n)))
     return {"sustained_tflops": sus.value, "first_launch_tflops": first.value, "launches": n.value}
+
+
+def builtin_batch():
+    """-> (mixtures, ctx_a, ctx_b): two float32 numpy arrays each -- the batch nhans_create calibrates the activation
+    exponents on (nhans_debug_builtin_batch, host only)."""
+    import numpy as np
+    lib = load()
+    n = (ctypes.c_int64 * 2)()
+    check(lib.nhans_debug_builtin_batch(None, None, None, n))
+    mix, ca, cb = np.zeros(2 * n[0], np.float32), np.zeros(2 * n[1], np.float32), np.zeros(2 * n[1], np.float32)
+    as_fp = lambda a: a.ctypes.data_as(_fp)
+    check(lib.nhans_debug_builtin_batch(as_fp(mix), as_fp(ca), as_fp(cb), n))
+    return tuple([a[:len(a) // 2], a[len(a) // 2:]] for a in (mix, ca, cb))
 
 
 def profile_dict(handle):

@@ -48,6 +48,8 @@ WEIGHTS = {
     "heavy": R.heavy,
     "trained_bn": R.trained_bn,
 }
+# weight sets reference() knows besides those the layer tests run over
+OTHER_WEIGHTS = {"one_channel_loud": R.one_channel_loud}
 
 # ---- the bar -----------------------------------------------------------------------------------------------------
 CAP = 2e-5
@@ -137,7 +139,7 @@ def reference(kind, recipe):
     """(f64 taps, f32 taps, features) of one model and weight set; the last one asked for is kept (0.9 GB)."""
     if _last_reference[0] != (kind, recipe):
         _last_reference[:] = [None, None]
-        W = WEIGHTS[recipe](kind)
+        W = (WEIGHTS.get(recipe) or OTHER_WEIGHTS[recipe])(kind)
         lms, ctx = features()
         t64 = cpu_taps(W, kind, torch.float64, lms, ctx)
         emb_in = t64.emb.to(torch.float32).numpy()

@@ -17,6 +17,11 @@ depends on the weight DISTRIBUTION.  These recipes span what a trained or a fres
               0.01 for conv / dense weights, sigma = 0 for `*_dense3`, `*_emb` and `last_dense`, zero biases, BatchNorm
               at its TF defaults (gamma 1, beta 0, pop_mean 0, pop_variance 1): `out` is exactly 0 and `denoised` is
               exactly the centre frame of the window.
+
+Beside them, for the calibration tests (tests/calibration_checks.py) and not among RECIPES:
+
+  one_channel_loud  `synthetic7` with one output channel of each of the 25 stored tensors 2^5 times louder and its readers
+              compensated: the maximum of every tensor sits in channel 0, 31, 32 or C - 1 in turn.
 """
 import zlib
 
@@ -109,6 +114,70 @@ def tf_init(kind, s=51):
         else:
             raise KeyError(name)
         W[name] = a.astype(np.float32)
+    return W
+
+
+LOUD_LOG2 = 5
+
+
+def loud_scopes():
+    """BatchNorm scope behind each of the 25 convs that write a stored tensor, in the library's numbering
+    (NHANS_NUM_ACTIVATIONS), with the tensor's channel count."""
+    out = []
+    for i, g in enumerate(spec.tower_geometry() + spec.main_geometry()):
+        p = ("embedding/" if i < 4 else "") + g["name"]
+        out += [(p + "_conv1", g["cout"]), (p + "_addition", g["cout"])]
+    return out + [("last_conv", 512)]
+
+
+def loud_channel(j, C):
+    """The loud channel of tensor j: the ends of the split layout's 32-channel hi / lo blocks, in turn."""
+    return (0, 31, 32, C - 1)[j % 4]
+
+
+def loud_readers(kind, j, W):
+    """Weights that read tensor j, as (name, axis of the tensor's channel, its stride in that axis): conv2 of the block for a
+    conv1 tensor; for a block output the next block's conv1 and `_transform`, for the tower's last the conditioning
+    projections of every stack conv (the embedding is its mean), for the stack's last `last_conv`, then `last_dense` (NHWC
+    flatten: row w * 512 + c).  The identity shortcut of the next block has no weight: blocks 1, 3, 5 and 7 of the stack."""
+    blocks = ["embedding/" + g["name"] for g in spec.tower_geometry()] + [g["name"] for g in spec.main_geometry()]
+    if j == 24:
+        return [("last_dense/w", 0, 512)]
+    p = blocks[j // 2]
+    if j % 2 == 0:
+        return [(p + "_conv2/w", 2, 1)]
+    if j == 7:
+        return [(k, 0, 1) for k in W if k.endswith("_emb/w") and not k.startswith("embedding/")]
+    if j == 23:
+        return [("last_conv/w", 2, 1)]
+    q = blocks[j // 2 + 1]
+    return [(q + "_conv1/w", 2, 1)] + ([(q + "_transform/w", 2, 1)] if q + "_transform/w" in W else [])
+
+
+def one_channel_loud(kind, s=7, log2=LOUD_LOG2):
+    """`synthetic7` with one output channel of every stored tensor 2^log2 times louder -- gamma and beta of the BatchNorm
+    behind the conv times a power of two: exact in every format, and ReLU commutes with it --, channel loud_channel(j, C),
+    and that input channel of every weight that reads the tensor (loud_readers) divided by the same power of two: every
+    other figure of the network stays what it is in `synthetic7`, exactly, but for what an identity shortcut carries of a
+    loud channel into the next block.  The maximum of each tensor then sits in a known channel
+    (tests/test_calibration_checks_host.py asserts it in float64): a maximum kernel that skips part of a channel block
+    cannot find it.  Not one of RECIPES: it exists for the calibration tests (tests/calibration_checks.py), the oracle
+    comparison of tests/test_gpu_recipes.py has its weight sets."""
+    W = dict(weights.synthetic_weights(kind, s))
+    for j, (scope, C) in enumerate(loud_scopes()):
+        c = loud_channel(j, C)
+        for leaf in ("gamma", "beta"):
+            a = W[scope + "/" + leaf].copy()
+            assert a.reshape(-1).size == C, (scope, a.shape, C)
+            a.reshape(-1)[c] *= np.float32(2.0 ** log2)
+            W[scope + "/" + leaf] = a
+        for name, axis, stride in loud_readers(kind, j, W):
+            a = W[name].copy()
+            assert a.shape[axis] == (C if stride == 1 else 26 * C) and stride in (1, C), (name, a.shape, C)
+            idx = [slice(None)] * a.ndim
+            idx[axis] = slice(c, None, stride) if stride > 1 else slice(c, c + 1)
+            a[tuple(idx)] *= np.float32(2.0 ** -log2)
+            W[name] = a
     return W
 
 
