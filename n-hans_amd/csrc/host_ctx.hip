@@ -20,32 +20,6 @@ struct BlobEntry {
     uint64_t nfloats;
 };
 
-std::vector<BlockGeo> tower_geometry() {       // SN/main.py:194-198
-    const int kh[4] = {8, 8, 4, 4}, kw[4] = {4, 4, 4, 4}, sh[4] = {3, 3, 1, 1}, sw[4] = {2, 2, 1, 2};
-    const int co[4] = {64, 128, 256, 512};
-    std::vector<BlockGeo> v;
-    int h = kCtxFrames, w = kBins, c = 1;
-    for (int i = 0; i < 4; ++i) {
-        BlockGeo g{kh[i], kw[i], sh[i], sw[i], c, co[i], h, w, (h + sh[i] - 1) / sh[i], (w + sw[i] - 1) / sw[i]};
-        v.push_back(g);
-        h = g.hout; w = g.wout; c = g.cout;
-    }
-    return v;
-}
-
-std::vector<BlockGeo> main_geometry() {        // SN/main.py:221-229
-    const int k[8] = {4, 4, 4, 4, 3, 3, 3, 3}, s[8] = {1, 1, 2, 1, 2, 1, 2, 1};
-    const int co[8] = {64, 64, 128, 128, 256, 256, 512, 512};
-    std::vector<BlockGeo> v;
-    int h = kMixWin, w = kBins, c = 1;
-    for (int i = 0; i < 8; ++i) {
-        BlockGeo g{k[i], k[i], s[i], s[i], c, co[i], h, w, (h + s[i] - 1) / s[i], (w + s[i] - 1) / s[i]};
-        v.push_back(g);
-        h = g.hout; w = g.wout; c = g.cout;
-    }
-    return v;
-}
-
 constexpr int kActTargetLog2 = 8;
 
 // Two tensors that feed ONE accumulator (a channel-changing block's conv2 reads its conv1 output and, through the
@@ -298,8 +272,8 @@ int nhans_create_ex(int model_kind, const void* blob, size_t nbytes, int device_
     nhans_ctx* c = new nhans_ctx();
     c->kind = model_kind;
     c->device = device_id;
-    c->tower = tower_geometry();
-    c->stack = main_geometry();
+    c->tower = tower_geometry(kCtxFrames, kBins);
+    c->stack = main_geometry(kMixWin, kBins);
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->blob_dev), nbytes);
     if (e != hipSuccess) { delete c; return fail(NHANS_ENOMEM, "hipMalloc for weights failed"); }
     c->blob_bytes = nbytes;
@@ -316,61 +290,33 @@ int nhans_create_ex(int model_kind, const void* blob, size_t nbytes, int device_
     if (e == hipSuccess) e = hipMemset(c->amax_dev, 0, kNumAct * sizeof(unsigned));
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->tail_ev, hipEventDisableTiming);
     if (e != hipSuccess) { nhans_destroy(c); return fail(NHANS_EHIP, "status word / ordering event creation failed"); }
+    // the blob's directory, for this function alone: every array the launch sequences will dereference is declared in
+    // net_weights.h, looked up here once and kept as a pointer in c->net -- or the blob is refused
+    std::map<std::string, std::pair<const float*, size_t>> arr;
     const BlobEntry* ent = reinterpret_cast<const BlobEntry*>(static_cast<const char*>(blob) + sizeof(BlobHeader));
     for (uint32_t i = 0; i < h->n_entries; ++i) {
         if (ent[i].offset % 16 || ent[i].offset + ent[i].nfloats * 4 > nbytes) {
             nhans_destroy(c); return fail(NHANS_EINVAL, "blob entry out of range");
         }
         std::string name(ent[i].name, strnlen(ent[i].name, sizeof ent[i].name));
-        c->arr[name] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(c->blob_dev) + ent[i].offset);
-        c->arr_n[name] = ent[i].nfloats;
+        arr[name] = {reinterpret_cast<const float*>(reinterpret_cast<const char*>(c->blob_dev) + ent[i].offset), ent[i].nfloats};
     }
     // conditioning columns: conv order m0.c1, m0.c2, m1.c1, ...
     int off = 0;
     for (int b = 0; b < 8; ++b) for (int j = 0; j < 2; ++j) { c->cond_off.push_back(off); off += c->stack[b].cout; }
     c->cond_cols = off;
-    // every array the launch sequences will dereference must be present with the right size
-    std::vector<std::pair<std::string, size_t>> need = {
-        {"tw400", 800}, {"window", 400}, {"wsyn", 400}, {"zero", 16384},
-        {"cond.w", (size_t)2 * kEmb * off}, {"cond.base", (size_t)off},
-        {"head.conv.wpk", (size_t)5 * 512 * 512}, {"head.conv.cb", 512},
-        {"head.dense.wpk", (size_t)26 * 512 * 256}, {"head.dense.cb", 256}, {"head.dense.idw", 256}};
-    for (int b = 0; b < 4; ++b) {
-        const BlockGeo& g = c->tower[b];
-        const std::string p = "t" + std::to_string(b);
-        const size_t k2 = (size_t)g.kh * g.kw * g.cout * g.cout;
-        if (b == 0) { need.push_back({p + ".c1.w", (size_t)g.kh * g.kw * 64}); need.push_back({p + ".c2.idw", (size_t)g.cout}); }
-        else { need.push_back({p + ".c1.wpk", (size_t)g.kh * g.kw * g.cin * g.cout}); need.push_back({p + ".c2.wpk_t", (size_t)g.cin * g.cout}); }
-        need.push_back({p + ".c1.cb", (size_t)g.cout});
-        need.push_back({p + ".c2.wpk", k2});
-        need.push_back({p + ".c2.cb", (size_t)g.cout});
-    }
-    for (int b = 0; b < 8; ++b) {
-        const BlockGeo& g = c->stack[b];
-        const std::string p = "m" + std::to_string(b);
-        if (b == 0) need.push_back({p + ".c1.w", (size_t)g.kh * g.kw * 64});
-        else need.push_back({p + ".c1.wpk", (size_t)g.kh * g.kw * g.cin * g.cout});
-        need.push_back({p + ".c2.wpk", (size_t)g.kh * g.kw * g.cout * g.cout});
-        if (b > 0 && g.cin != g.cout) need.push_back({p + ".c2.wpk_t", (size_t)g.cin * g.cout});
-        need.push_back({p + ".c2.idw", (size_t)g.cout});
-        for (const char* cv : {".c1", ".c2"}) {
-            need.push_back({p + cv + ".tf", (size_t)g.hout * g.wout * g.cout});
-        }
-    }
-    for (const auto& kv : need) {
-        auto it = c->arr_n.find(kv.first);
-        if (it == c->arr_n.end() || it->second != kv.second) {
-            std::string msg = "folded blob: array '" + kv.first + "' missing or wrong size (want " +
-                              std::to_string(kv.second) + ")";
-            nhans_destroy(c);
-            return fail(NHANS_EINVAL, msg);
-        }
-    }
+    const std::string bad = resolve_net_weights(c->tower, c->stack, [&](const std::string& name, const float** p, size_t* n) {
+        const auto it = arr.find(name);
+        if (it == arr.end()) return false;
+        *p = it->second.first; *n = it->second.second;
+        return true;
+    }, &c->net);
+    if (!bad.empty()) { nhans_destroy(c); return fail(NHANS_EINVAL, bad); }
     if (act_exp) {
         // (exponents a previous context calibrated for this very blob -- the caller's cache vouches for that: no pass)
         std::copy(act_exp, act_exp + kNumAct, c->act_exp);
         tie_exponents(c);
-    } else if (c->A("head.dense.wpk_h")) {
+    } else if (c->net.has_split) {
         const int rc = calibrate_builtin(c);
         if (rc) { nhans_destroy(c); return rc; }
     }
@@ -450,7 +396,7 @@ int nhans_set_option(nhans_ctx* c, const char* key, int64_t value) {
     }
     else if (k == "precision") {
         if (value != 0 && value != 1) return fail(NHANS_EINVAL, "precision must be 0 (f32) or 1 (f16x3)");
-        if (value == 1 && !c->A("head.dense.wpk_h"))
+        if (value == 1 && !c->net.has_split)
             return fail(NHANS_EINVAL, "the folded blob carries no split-f16 weights");
         c->prec = (int)value;
     }

@@ -1,7 +1,9 @@
 // What the host units of libnhans_hip.so share (the C ABI itself: include/nhans_hip.h).  One unit per subsystem:
 //   ws_plan.h         WsPlan: a call's device scratch, each buffer declared once (knows neither HIP nor the context)
-//   host_ctx.hip      error channel, blob, context, options, calibration, workspace growth and ws_commit, Call, status,
-//                     profiling, the argument checks several units share
+//   net_weights.h     NetWeights: the blob's arrays, each declared once with its size and class and resolved into one field
+//                     (knows neither HIP nor the context); BlockGeo and the two geometries
+//   host_ctx.hip      error channel, blob (nhans_create_ex checks it: resolve_net_weights), context, options, calibration,
+//                     workspace growth and ws_commit, Call, status, profiling, the argument checks several units share
 //   host_net.hip      conv launch sequences (tower, stack, head), STFT / iSTFT block tables, the offline entry points
 //   host_fbank.hip    filterbank design and table, nhans_fbank_design / _open / _close / _rows
 //   host_online.hip   nhans_online_*, nhans_capture_*, nhans_fbank_online_*
@@ -20,6 +22,7 @@
 #include "../../include/nhans_hip.h"
 #include "nhans_kernels.h"
 #include "ws_plan.h"
+#include "net_weights.h"
 
 #include <algorithm>
 #include <cmath>
@@ -45,10 +48,6 @@ int fail(int code, const std::string& msg);       // sets nhans_last_error() (th
             return fail(NHANS_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
     } while (0)
 
-struct BlockGeo {
-    int kh, kw, sh, sw, cin, cout, hin, win, hout, wout;
-};
-
 constexpr int kNumAct = NHANS_NUM_ACTIVATIONS;
 constexpr int TA(int b, int j) { return 2 * b + j; }            // tower block b, conv j+1
 constexpr int SA(int b, int j) { return 8 + 2 * b + j; }        // stack block b, conv j+1
@@ -73,8 +72,7 @@ struct nhans_ctx {
     StackPlan last_plan;
     float* blob_dev = nullptr;
     size_t blob_bytes = 0;
-    std::map<std::string, const float*> arr;
-    std::map<std::string, size_t> arr_n;
+    NetWeights net;         // the blob's arrays on the device (net_weights.h), resolved and checked by nhans_create_ex
     std::vector<BlockGeo> tower, stack;
     int cond_cols = 0;
     std::vector<int> cond_off;      // column offset of conv j (= 2*block + {0,1})
@@ -142,14 +140,6 @@ struct nhans_ctx {
     hipEvent_t tail_ev = nullptr;
     hipStream_t last_stream = nullptr;
     bool have_tail = false;
-
-    const float* A(const std::string& n) const {
-        auto it = arr.find(n);
-        return it == arr.end() ? nullptr : it->second;
-    }
-    // packed conv weights / per-channel unscale vector of the active precision
-    const float* WP(const std::string& n) const { return A(prec ? n + "_h" : n); }
-    const float* WS(const std::string& conv) const { return prec ? A(conv + ".ws") : nullptr; }
 };
 
 #pragma GCC visibility push(hidden)
@@ -223,6 +213,14 @@ template <typename Obj, typename Body>
 int object_call(Obj* o, const char* null_msg, void* stream, Body body) {
     if (!o) return fail(NHANS_EINVAL, null_msg);
     Call call(o->c, stream);
+    if (call.rc) return call.rc;
+    return call.finish(body(call.s));
+}
+
+// The bracket for an entry point of the context itself: body(stream) inside the Call.
+template <typename Body>
+int ctx_call(nhans_ctx* c, void* stream, Body body) {
+    Call call(c, stream);
     if (call.rc) return call.rc;
     return call.finish(body(call.s));
 }

@@ -11,7 +11,7 @@ void same_pad(int n, int k, int s, int* out, int* before) {
 }
 
 void fill_epilogue_defaults(nhans_ctx* c, ConvArgs& a) {
-    a.zero = c->A("zero");
+    a.zero = c->net.zero;
     a.sat = c->status_dev;
     a.img_clip = nullptr; a.tf = nullptr; a.tt = nullptr; a.ff = nullptr; a.id_mode = 0; a.id = nullptr; a.id_ld = 0;
     a.idw = nullptr; a.idH = a.idW = 0; a.idsh = a.idsw = 1; a.relu = 1; a.aux = nullptr; a.aux_ld = 0;
@@ -44,6 +44,70 @@ void set_out_geometry(ConvArgs& a, int B, int Ho, int Wo, int N, int Nreal, int 
     a.oh0 = 0; a.Ho_full = Ho;
     a.fdHoWo = make_fastdiv((uint32_t)(Ho * Wo));
     a.fdWo = make_fastdiv((uint32_t)Wo);
+}
+
+// ---- the launches of one residual block:  x -> conv1 -> a1 -> conv2 (+ shortcut from x) -> out,  n images ---------------
+// Written once for the embedding tower and the conditioned stack.  `w` holds what the block has (net_weights.h): a field
+// the tower has no array for -- position tables, Winograd packs -- is null there.  `act` is the exponent index of a1; x
+// is tensor act - 1 and out is tensor act + 1 (host_internal.h: TA, SA).  What only the stack has -- conditioning rows
+// and clip map, the sliding-window source, the layouts and saturation limits of its StackPlan -- it sets on the result.
+const float* unscale(const nhans_ctx* c, const ConvWeights& w) { return c->prec ? w.ws : nullptr; }
+
+// conv1 of a block whose input is a one-channel image
+DirectArgs first_conv_args(nhans_ctx* c, const ConvWeights& w, const BlockGeo& g, const float* x, float* a1, int n, int act) {
+    DirectArgs d{};
+    d.src = x; d.w = w.w; d.H = g.hin; d.W = g.win; d.KH = g.kh; d.KW = g.kw; d.sh = g.sh; d.sw = g.sw;
+    int o; same_pad(g.hin, g.kh, g.sh, &o, &d.pt); same_pad(g.win, g.kw, g.sw, &o, &d.pl);
+    d.Ho = g.hout; d.Wo = g.wout; d.M = n * g.hout * g.wout; d.out = a1;
+    d.cb = w.cb; d.cb_stride = 0; d.img_clip = nullptr; d.tf = w.tf; d.tt = w.tt; d.ff = w.ff;
+    d.relu = 1; d.fdHoWo = make_fastdiv(g.hout * g.wout); d.fdWo = make_fastdiv(g.wout);
+    d.out_split = c->prec; d.sat = c->prec ? c->status_dev : nullptr; d.out_scale = c->down(act); d.sat_limit = kSatLimitF16;
+    return d;
+}
+void run_first_conv(nhans_ctx* c, const DirectArgs& d, hipStream_t s) {
+    Prof pr(c, s, "direct_conv64");
+    launch_direct_conv64(d, s);
+    pr.done(2.0 * d.M * d.KH * d.KW * 64, 0);
+}
+
+// what conv1 and conv2 share: the k x k segment over `src` (tensor in_act) and the epilogue terms of the conv's own arrays
+ConvArgs block_conv_args(nhans_ctx* c, const ConvWeights& w, const BlockGeo& g, const float* src, int H, int W, int C, int sh,
+                         int sw, int in_act) {
+    ConvArgs a{};
+    fill_epilogue_defaults(c, a);
+    a.nseg = 1;
+    a.seg[0] = make_seg(src, w.wpk[c->prec], H, W, C, g.kh, g.kw, sh, sw, true);
+    a.cb = w.cb; a.tf = w.tf; a.tt = w.tt; a.ff = w.ff; a.idw = w.idw;
+    a.ws = unscale(c, w);
+    a.wino_u = w.wino_u; a.wino_ws = w.wino_ws;
+    a.in_scale = c->up(in_act); a.out_scale = c->down(in_act + 1);
+    return a;
+}
+
+ConvArgs conv1_args(nhans_ctx* c, const ConvWeights& w, const BlockGeo& g, const float* x, float* a1, int n, int act) {
+    ConvArgs a = block_conv_args(c, w, g, x, g.hin, g.win, g.cin, g.sh, g.sw, act - 1);
+    set_out_geometry(a, n, g.hout, g.wout, g.cout, g.cout, g.cout, a1);
+    return a;
+}
+
+// conv2 with the block's shortcut: the one-channel image x itself; x as an identity residual; or, in a block that changes
+// its channel count, the 1x1 strided `_transform` conv of x -- as extra K columns of this launch, or, where the caller
+// runs it on its own (stack, Winograd form), its f32 output `apart` as a residual with weight one
+ConvArgs conv2_args(nhans_ctx* c, const ConvWeights& w, const BlockGeo& g, const float* a1, const float* x, const float* apart,
+                    float* out, int n, int act) {
+    ConvArgs a = block_conv_args(c, w, g, a1, g.hout, g.wout, g.cout, 1, 1, act);
+    if (g.cin == 1) {
+        a.id_mode = 2; a.id = x; a.idH = g.hin; a.idW = g.win; a.idsh = g.sh; a.idsw = g.sw;
+    } else if (g.cin == g.cout) {
+        a.id_mode = 1; a.id = x; a.id_ld = g.cout; a.id_split = c->prec; a.id_scale = c->up(act - 1);
+    } else if (apart) {
+        a.id_mode = 1; a.id = apart; a.id_ld = g.cout; a.id_split = 0; a.idw = c->net.ones;
+    } else {                            // (x and a1 share one exponent: tie_exponents())
+        a.nseg = 2;
+        a.seg[1] = make_seg(x, w.wpk_t[c->prec], g.hin, g.win, g.cin, 1, 1, g.sh, g.sw, false);
+    }
+    set_out_geometry(a, n, g.hout, g.wout, g.cout, g.cout, g.cout, out);
+    return a;
 }
 
 // -> the name of the kernel variant that ran
@@ -255,82 +319,59 @@ float* run_stack_chunk(nhans_ctx* c, const float* logmag, const int* rb, const S
     // readers, and the debug entry point (upto = block + 1) must see the tensors the production call writes
     for (int b = 0; b < 8 && (b < upto || !go); ++b) {
         const BlockGeo& g = c->stack[b];
-        const std::string p = "m" + std::to_string(b);
+        const BlockWeights& w = c->net.stack[b];
+        const int act = SA(b, 0);
         const float* cb1 = sb.cb_all + c->cond_off[2 * b];
         const float* cb2 = sb.cb_all + c->cond_off[2 * b + 1];
+        const float* in = b ? x : lm_chunk;     // (block 0: the window image itself)
         if (b == 0) {
-            DirectArgs d{};
-            d.src = lm_chunk; d.win = win; d.w = c->A(p + ".c1.w"); d.H = g.hin; d.W = g.win; d.KH = g.kh; d.KW = g.kw;
-            d.sh = 1; d.sw = 1;
-            int o; same_pad(g.hin, g.kh, 1, &o, &d.pt); same_pad(g.win, g.kw, 1, &o, &d.pl);
-            d.Ho = g.hout; d.Wo = g.wout; d.M = n * g.hout * g.wout; d.out = a1;
-            d.cb = cb1; d.cb_stride = c->cond_cols; d.img_clip = clipmap;
-            d.tf = c->A(p + ".c1.tf"); d.tt = c->A(p + ".c1.tt"); d.ff = c->A(p + ".c1.ff");
-            if (!d.tt || !d.ff) d.tt = d.ff = nullptr;
-            d.relu = 1; d.out_split = c->prec && !stored_f32(c, plan, 0, 0); d.sat = c->prec ? c->status_dev : nullptr;
-            d.out_scale = c->down(SA(0, 0)); d.sat_limit = sat_limit_for(plan, 0, 2);
-            d.fdHoWo = make_fastdiv(g.hout * g.wout); d.fdWo = make_fastdiv(g.wout);
-            if (go && !dead()) {
-                Prof pr(c, s, "direct_conv64");
-                launch_direct_conv64(d, s);
-                pr.done(2.0 * d.M * g.kh * g.kw * 64, 0);
-            }
+            DirectArgs d = first_conv_args(c, w.c1, g, in, a1, n, act);
+            d.win = win; d.cb = cb1; d.cb_stride = c->cond_cols; d.img_clip = clipmap;
+            d.out_split = c->prec && !stored_f32(c, plan, 0, 0); d.sat_limit = sat_limit_for(plan, 0, 2);
+            if (go && !dead()) run_first_conv(c, d, s);
         } else {
-            ConvArgs a{};
-            fill_epilogue_defaults(c, a);
-            a.nseg = 1;
-            a.seg[0] = make_seg(x, c->WP(p + ".c1.wpk"), g.hin, g.win, g.cin, g.kh, g.kw, g.sh, g.sw, true);
-            set_out_geometry(a, n, g.hout, g.wout, g.cout, g.cout, g.cout, a1);
+            ConvArgs a = conv1_args(c, w.c1, g, in, a1, n, act);
             a.cb = cb1; a.cb_stride = c->cond_cols; a.img_clip = clipmap;
-            a.tf = c->A(p + ".c1.tf"); a.tt = c->A(p + ".c1.tt"); a.ff = c->A(p + ".c1.ff");
-            a.ws = c->WS(p + ".c1");
-            a.wino_u = c->A(p + ".c1.wino"); a.wino_ws = c->A(p + ".c1.wino.ws");
-            a.in_scale = c->up(SA(b - 1, 1)); a.out_scale = c->down(SA(b, 0));
             a.sat_limit = sat_limit_for(plan, b, 2);
             a.in_f32 = stored_f32(c, plan, b - 1, 1); a.out_split = c->prec && !stored_f32(c, plan, b, 0);
             conv(b, 1, a);
         }
-        if (go) tap(c, SA(b, 0), a1, (size_t)n * g.hout * g.wout * g.cout, g.cout, s, stored_f32(c, plan, b, 0));
-        ConvArgs a{};
-        fill_epilogue_defaults(c, a);
-        a.nseg = 1;
-        a.seg[0] = make_seg(a1, c->WP(p + ".c2.wpk"), g.hout, g.wout, g.cout, g.kh, g.kw, 1, 1, true);
-        a.cb = cb2; a.cb_stride = c->cond_cols; a.img_clip = clipmap;
-        a.tf = c->A(p + ".c2.tf"); a.tt = c->A(p + ".c2.tt"); a.ff = c->A(p + ".c2.ff");
-        a.idw = c->A(p + ".c2.idw");
-        a.ws = c->WS(p + ".c2");
-        a.wino_u = c->A(p + ".c2.wino"); a.wino_ws = c->A(p + ".c2.wino.ws");
-        a.in_scale = c->up(SA(b, 0)); a.out_scale = c->down(SA(b, 1));
-        a.sat_limit = sat_limit_for(plan, b + 1, 1);
-        a.in_f32 = stored_f32(c, plan, b, 0); a.out_split = c->prec && !stored_f32(c, plan, b, 1);
+        if (go) tap(c, act, a1, (size_t)n * g.hout * g.wout * g.cout, g.cout, s, stored_f32(c, plan, b, 0));
+        auto conv2 = [&](const float* apart, float* to) {
+            ConvArgs a = conv2_args(c, w.c2, g, a1, in, apart, to, n, act);
+            a.cb = cb2; a.cb_stride = c->cond_cols; a.img_clip = clipmap;
+            a.sat_limit = sat_limit_for(plan, b + 1, 1);
+            a.in_f32 = stored_f32(c, plan, b, 0); a.out_split = c->prec && !stored_f32(c, plan, b, 1);
+            return a;
+        };
+        ConvArgs a;
         float* out;
         if (b == 0) {                       // 1 -> 64 transform on the window image itself
-            a.id_mode = 2; a.id = lm_chunk; a.id_win = win; a.idH = g.hin; a.idW = g.win; a.idsh = 1; a.idsw = 1;
             out = x;
+            a = conv2(nullptr, out);
+            a.id_win = win;
         } else if (g.cin == g.cout) {       // identity shortcut, written in place over the block input
-            a.id_mode = 1; a.id = x; a.id_ld = g.cout; a.id_split = c->prec && !stored_f32(c, plan, b - 1, 1);
-            a.id_scale = c->up(SA(b - 1, 1));
             // (in place only if input and output share a layout: a thread's output bytes are its residual bytes then)
             out = stored_f32(c, plan, b - 1, 1) == stored_f32(c, plan, b, 1) ? x : y;
+            a = conv2(nullptr, out);
+            a.id_split = c->prec && !stored_f32(c, plan, b - 1, 1);
         } else {
             // Channel-changing block.  If its conv2 -- as a one-segment conv with an f32 residual tensor -- has a
             // Winograd form, the 1x1 strided `_transform` conv (which cannot ride in the K loop of the transformed
             // domain; 3 % of the block's MACs) runs first on its own into an f32 tensor that conv2's epilogue then adds
             // like a residual (the bias of both is in conv2's bias row).  Otherwise it is extra K columns of conv2.
-            ConvArgs w = a;
-            w.id_mode = 1; w.id = sb.T; w.id_ld = g.cout; w.id_split = 0;
-            w.idw = c->A("head.dense.idw");     // ones
-            set_out_geometry(w, n, g.hout, g.wout, g.cout, g.cout, g.cout, y);
-            if (go ? plan.wino[b][2] : wino_form(w)) {
+            out = y;
+            a = conv2(sb.T, out);
+            if (go ? plan.wino[b][2] : wino_form(a)) {
                 ConvArgs t{};
                 fill_epilogue_defaults(c, t);
                 t.nseg = 1;
-                t.seg[0] = make_seg(x, c->WP(p + ".c2.wpk_t"), g.hin, g.win, g.cin, 1, 1, g.sh, g.sw, false);
+                t.seg[0] = make_seg(x, w.c2.wpk_t[c->prec], g.hin, g.win, g.cin, 1, 1, g.sh, g.sw, false);
                 set_out_geometry(t, n, g.hout, g.wout, g.cout, g.cout, g.cout, sb.T);
-                t.cb = c->A("zero"); t.cb_stride = 0;
-                t.ws = c->WS(p + ".c2");            // (conv2 and the transform share one column scale: fold.py emit())
+                t.cb = c->net.zero; t.cb_stride = 0;
+                t.ws = unscale(c, w.c2);            // (conv2 and the transform share one column scale: fold.py emit())
                 t.relu = 0; t.out_split = 0;
-                t.in_scale = c->up(SA(b - 1, 1));   // (f32 output: no exponent)
+                t.in_scale = c->up(act - 1);        // (f32 output: no exponent)
                 if (go && !dead()) {
                     if (c->stream_1x1 && conv_1x1_stream_eligible(t)) {       // 1.75 GB in, 3.5 GB out, 16 KFLOP per output pixel: a stream
                         Prof pr(c, s, "conv_1x1_stream");
@@ -341,16 +382,12 @@ float* run_stack_chunk(nhans_ctx* c, const float* logmag, const int* rb, const S
                         run_conv(c, t, s);
                     }
                 }
-                a = w;
-            } else {                        // (x and a1 share one exponent)
-                a.nseg = 2;
-                a.seg[1] = make_seg(x, c->WP(p + ".c2.wpk_t"), g.hin, g.win, g.cin, 1, 1, g.sh, g.sw, false);
+            } else {
+                a = conv2(nullptr, out);
             }
-            out = y;
         }
-        set_out_geometry(a, n, g.hout, g.wout, g.cout, g.cout, g.cout, out);
         conv(b, 2, a);
-        if (go) tap(c, SA(b, 1), out, (size_t)n * g.hout * g.wout * g.cout, g.cout, s, stored_f32(c, plan, b, 1));
+        if (go) tap(c, act + 1, out, (size_t)n * g.hout * g.wout * g.cout, g.cout, s, stored_f32(c, plan, b, 1));
         if (out == y) std::swap(x, y);
     }
     result = x;
@@ -359,10 +396,10 @@ float* run_stack_chunk(nhans_ctx* c, const float* logmag, const int* rb, const S
         ConvArgs a{};
         fill_epilogue_defaults(c, a);
         a.nseg = 1;
-        a.seg[0] = make_seg(x, c->WP("head.conv.wpk"), g.hout, g.wout, g.cout, g.hout, 1, 1, 1, false);
+        a.seg[0] = make_seg(x, c->net.head_conv.wpk[c->prec], g.hout, g.wout, g.cout, g.hout, 1, 1, 1, false);
         set_out_geometry(a, n, 1, g.wout, 512, 512, 512, a1);
-        a.cb = c->A("head.conv.cb");
-        a.ws = c->WS("head.conv");
+        a.cb = c->net.head_conv.cb;
+        a.ws = unscale(c, c->net.head_conv);
         a.in_scale = c->up(SA(7, 1)); a.out_scale = c->down(kActHead);
         run_conv(c, a, s);
         tap(c, kActHead, a1, (size_t)n * g.wout * 512, 512, s);
@@ -372,20 +409,6 @@ float* run_stack_chunk(nhans_ctx* c, const float* logmag, const int* rb, const S
     c->last_plan = plan;
     return result;
 }
-
-int mask_net_impl(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
-                  const float* eb, float* logits, float* denoised, const StackBufs& sb, int64_t wf,
-                  hipStream_t s) {
-    const int64_t total = foff[nclips];
-    { int rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc; }
-    launch_frame_index(sb.foff_dev, nclips, total, c->lookahead, sb.f_clip, sb.f_t, sb.f_T, s);
-    return mask_net_run(c, logmag, nullptr, logmag, total, nclips, ea, eb, logits, denoised, sb, wf, s);
-}
-
-struct HostTables {
-    std::vector<int64_t> soff, foff, ooff;
-    std::vector<int> bclip, bpos;
-};
 
 }  // namespace
 
@@ -398,50 +421,20 @@ int embed_impl(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, const T
         float *x = tb.X, *a1 = tb.A, *y = tb.Y;
         for (int b = 0; b < 4; ++b) {
             const BlockGeo& g = T[b];
-            const std::string p = "t" + std::to_string(b);
+            const BlockWeights& w = c->net.tower[b];
+            const int act = TA(b, 0);
+            const float* in = b ? x : img;
             if (b == 0) {
-                DirectArgs d{};
-                d.src = img; d.w = c->A(p + ".c1.w"); d.H = g.hin; d.W = g.win; d.KH = g.kh; d.KW = g.kw;
-                d.sh = g.sh; d.sw = g.sw;
-                int o; same_pad(g.hin, g.kh, g.sh, &o, &d.pt); same_pad(g.win, g.kw, g.sw, &o, &d.pl);
-                d.Ho = g.hout; d.Wo = g.wout; d.M = nc * g.hout * g.wout; d.out = a1;
-                d.cb = c->A(p + ".c1.cb"); d.cb_stride = 0; d.img_clip = nullptr; d.tf = nullptr; d.tt = nullptr; d.ff = nullptr;
-                d.relu = 1; d.fdHoWo = make_fastdiv(g.hout * g.wout); d.fdWo = make_fastdiv(g.wout);
-                d.out_split = c->prec; d.sat = c->prec ? c->status_dev : nullptr; d.out_scale = c->down(TA(0, 0)); d.sat_limit = kSatLimitF16;
-                Prof pr(c, s, "direct_conv64");
-                launch_direct_conv64(d, s);
-                pr.done(2.0 * d.M * g.kh * g.kw * 64, 0);
+                run_first_conv(c, first_conv_args(c, w.c1, g, in, a1, nc, act), s);
             } else {
-                ConvArgs a{};
-                fill_epilogue_defaults(c, a);
-                a.nseg = 1;
-                a.seg[0] = make_seg(x, c->WP(p + ".c1.wpk"), g.hin, g.win, g.cin, g.kh, g.kw, g.sh, g.sw, true);
-                set_out_geometry(a, nc, g.hout, g.wout, g.cout, g.cout, g.cout, a1);
-                a.cb = c->A(p + ".c1.cb");
-                a.ws = c->WS(p + ".c1");
-                a.in_scale = c->up(TA(b - 1, 1)); a.out_scale = c->down(TA(b, 0));
+                ConvArgs a = conv1_args(c, w.c1, g, in, a1, nc, act);
                 a.kgroup = -1;                  // a handful of context images: grouped sum, split-K when small
                 run_conv(c, a, s);
             }
-            tap(c, TA(b, 0), a1, (size_t)nc * g.hout * g.wout * g.cout, g.cout, s);
-            ConvArgs a{};
-            fill_epilogue_defaults(c, a);
-            a.nseg = 1;
-            a.seg[0] = make_seg(a1, c->WP(p + ".c2.wpk"), g.hout, g.wout, g.cout, g.kh, g.kw, 1, 1, true);
-            if (b == 0) {
-                a.id_mode = 2; a.id = img; a.idH = g.hin; a.idW = g.win; a.idsh = g.sh; a.idsw = g.sw;
-                a.idw = c->A(p + ".c2.idw");
-            } else {
-                a.nseg = 2;
-                a.seg[1] = make_seg(x, c->WP(p + ".c2.wpk_t"), g.hin, g.win, g.cin, 1, 1, g.sh, g.sw, false);
-            }
-            set_out_geometry(a, nc, g.hout, g.wout, g.cout, g.cout, g.cout, y);
-            a.cb = c->A(p + ".c2.cb");
-            a.ws = c->WS(p + ".c2");
+            tap(c, act, a1, (size_t)nc * g.hout * g.wout * g.cout, g.cout, s);
             // (the `_transform` segment reads x, whose exponent tie_exponents() keeps equal to a1's: one accumulator)
-            a.in_scale = c->up(TA(b, 0)); a.out_scale = c->down(TA(b, 1));
-            run_conv(c, a, s);                  // (stride 1: halo kernel; measured faster than split-K here)
-            tap(c, TA(b, 1), y, (size_t)nc * g.hout * g.wout * g.cout, g.cout, s);
+            run_conv(c, conv2_args(c, w.c2, g, a1, in, nullptr, y, nc, act), s);     // (stride 1: halo kernel; measured faster than split-K here)
+            tap(c, act + 1, y, (size_t)nc * g.hout * g.wout * g.cout, g.cout, s);
             std::swap(x, y);
         }
         const BlockGeo& g = T[3];
@@ -473,17 +466,38 @@ void stack_plan(WsPlan& p, const nhans_ctx* c, int64_t total, int nclips, int64_
     p.add(&sb->T, transform_buf_floats(c, wf));
 }
 
-// The stack + head over `total` frame windows whose per-frame tables (sb.f_clip, f_t, f_T) are in place.  win_src / rb:
-// the window source (rb nullable, see run_stack_chunk); centre [total, 201]: the frames' own rows, the head's identity
-// term (mixed_central, SN/main.py:242) -- offline that is win_src itself.
-int mask_net_run(nhans_ctx* c, const float* win_src, const int* rb, const float* centre, int64_t total, int nclips,
-                 const float* ea, const float* eb, float* logits, float* denoised, const StackBufs& sb, int64_t wf,
-                 hipStream_t s) {
-    {
-        Prof pr(c, s, "cond_proj");
-        launch_cond(ea, eb, nclips, c->A("cond.w"), c->A("cond.base"), c->cond_cols, sb.cb_all, s);
-        pr.done(2.0 * nclips * 2 * kEmb * c->cond_cols, 0);
+// The conditioning rows of `nclips` clips (production: under the profiling bracket `cond_proj`; the debug captures are not
+// profiled).
+static void cond_rows(nhans_ctx* c, const float* ea, const float* eb, int nclips, const StackBufs& sb, bool production, hipStream_t s) {
+    if (!production) { launch_cond(ea, eb, nclips, c->net.cond_w, c->net.cond_base, c->cond_cols, sb.cb_all, s); return; }
+    Prof pr(c, s, "cond_proj");
+    launch_cond(ea, eb, nclips, c->net.cond_w, c->net.cond_base, c->cond_cols, sb.cb_all, s);
+    pr.done(2.0 * nclips * 2 * kEmb * c->cond_cols, 0);
+}
+
+// What a run of the stack over a batch of clips (frame offsets foff) starts with: the stack's buffers for passes of wf
+// frame windows placed -- commit: as the call's only scratch; otherwise the caller's own committed plan holds sb already
+// --, the frame offsets on the device, the per-frame tables and the conditioning rows.
+static int stack_begin(nhans_ctx* c, bool commit, const int64_t* foff, int nclips, int64_t wf, const float* ea, const float* eb,
+                       bool production, StackBufs* sb, hipStream_t s) {
+    const int64_t total = foff[nclips];
+    int rc = NHANS_OK;
+    if (commit) {
+        WsPlan p;
+        stack_plan(p, c, total, nclips, wf, sb);
+        rc = ws_commit(c, p); if (rc) return rc;
     }
+    rc = h2d(c, sb->foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc;
+    launch_frame_index(sb->foff_dev, nclips, total, c->lookahead, sb->f_clip, sb->f_t, sb->f_T, s);
+    cond_rows(c, ea, eb, nclips, *sb, production, s);
+    return NHANS_OK;
+}
+
+// The stack + head over `total` frame windows whose per-frame tables (sb.f_clip, f_t, f_T) and conditioning rows are in
+// place.  win_src / rb: the window source (rb nullable, see run_stack_chunk); centre [total, 201]: the frames' own rows, the
+// head's identity term (mixed_central, SN/main.py:242) -- offline that is win_src itself.
+static int stack_and_head(nhans_ctx* c, const float* win_src, const int* rb, const float* centre, int64_t total, float* logits,
+                          float* denoised, const StackBufs& sb, int64_t wf, hipStream_t s) {
     const BlockGeo& g = c->stack[7];
     for (int64_t g0 = 0; g0 < total; g0 += wf) {
         const int n = (int)std::min<int64_t>(wf, total - g0);
@@ -493,19 +507,34 @@ int mask_net_run(nhans_ctx* c, const float* win_src, const int* rb, const float*
         ConvArgs a{};
         fill_epilogue_defaults(c, a);
         a.nseg = 1;
-        a.seg[0] = make_seg(hc, c->WP("head.dense.wpk"), 1, 1, g.wout * 512, 1, 1, 1, 1, false);
+        a.seg[0] = make_seg(hc, c->net.head_dense.wpk[c->prec], 1, 1, g.wout * 512, 1, 1, 1, 1, false);
         set_out_geometry(a, n, 1, 1, 256, kBins, kBins, denoised + g0 * kBins);
-        a.cb = c->A("head.dense.cb");
-        a.ws = c->WS("head.dense");
+        a.cb = c->net.head_dense.cb;
+        a.ws = unscale(c, c->net.head_dense);
         a.out_split = 0;
         a.relu = 0;
         a.in_scale = c->up(kActHead);
-        a.id_mode = 1; a.id = centre + g0 * kBins; a.id_ld = kBins; a.idw = c->A("head.dense.idw");
+        a.id_mode = 1; a.id = centre + g0 * kBins; a.id_ld = kBins; a.idw = c->net.ones;
         if (logits) { a.aux = logits + g0 * kBins; a.aux_ld = kBins; }
         a.kgroup = -1;                          // K = 13312 over a few hundred frames: grouped sum, split-K when small
         run_conv(c, a, s);
     }
     return NHANS_OK;
+}
+
+// (online enhancement: the per-frame tables come from the object's streams, host_online.hip)
+int mask_net_run(nhans_ctx* c, const float* win_src, const int* rb, const float* centre, int64_t total, int nclips,
+                 const float* ea, const float* eb, float* logits, float* denoised, const StackBufs& sb, int64_t wf,
+                 hipStream_t s) {
+    cond_rows(c, ea, eb, nclips, sb, true, s);
+    return stack_and_head(c, win_src, rb, centre, total, logits, denoised, sb, wf, s);
+}
+
+// the offline mask net over a batch of clips (commit: see stack_begin)
+static int mask_net_impl(nhans_ctx* c, bool commit, const float* logmag, const int64_t* foff, int nclips, const float* ea,
+                         const float* eb, float* logits, float* denoised, StackBufs* sb, int64_t wf, hipStream_t s) {
+    const int rc = stack_begin(c, commit, foff, nclips, wf, ea, eb, true, sb, s); if (rc) return rc;
+    return stack_and_head(c, logmag, nullptr, logmag, foff[nclips], logits, denoised, *sb, wf, s);
 }
 
 // ---- STFT / iSTFT host-side block tables ----------------------------------------------------
@@ -533,7 +562,7 @@ int stft_impl(nhans_ctx* c, const float* wav, const int64_t* soff, int nclips, i
     rc = h2d(c, dev_blocks + nb, bf0.data(), (size_t)nb * 4, s); if (rc) return rc;
     ClipTable t{dev_tables, dev_tables + (nclips + 1), nullptr};
     Prof pr(c, s, prof_name ? prof_name : phase ? "stft_features" : "stft_context_features");   // (contexts: log-magnitude only, 200 frames per clip)
-    launch_stft(wav, t, dev_blocks, dev_blocks + nb, nb, c->A("tw400"), c->A("window"), logmag, phase, s);
+    launch_stft(wav, t, dev_blocks, dev_blocks + nb, nb, c->net.tw400, c->net.window, logmag, phase, s);
     pr.done(0, (double)foff[nclips] * (kHop * 4 + (phase ? 2 : 1) * kBins * 4));
     if (foff_out) *foff_out = foff;
     return NHANS_OK;
@@ -567,7 +596,7 @@ int istft_impl(nhans_ctx* c, const float* logmag, const float* phase, const int6
     rc = h2d(c, dev_blocks + nb, bh0.data(), (size_t)nb * 4, s); if (rc) return rc;
     ClipTable t{nullptr, dev_tables, dev_tables + (nclips + 1)};
     Prof pr(c, s, prof_name);
-    launch_istft(logmag, phase, t, dev_blocks, dev_blocks + nb, nb, c->A("tw400"), c->A("wsyn"), wav_out, s);
+    launch_istft(logmag, phase, t, dev_blocks, dev_blocks + nb, nb, c->net.tw400, c->net.wsyn, wav_out, s);
     pr.done(0, (double)foff[nclips] * (kHop * 4 + 2 * kBins * 4));
     return NHANS_OK;
 }
@@ -628,7 +657,7 @@ int enhance_clips_body(nhans_ctx* c, const float* mix, const int64_t* moff, int 
     if (rc) return rc;
     rc = embed_impl(c, ctxlm, 2 * nclips, emb, tb, s); if (rc) return rc;
     if (total > 0) {
-        rc = mask_net_impl(c, lm, foff.data(), nclips, emb, emb + (size_t)nclips * kEmb, lg, den, sb, wf, s);
+        rc = mask_net_impl(c, false, lm, foff.data(), nclips, emb, emb + (size_t)nclips * kEmb, lg, den, &sb, wf, s);
         if (rc) return rc;
         rc = istft_impl(c, den, ph, foff.data(), nclips, moff, den_wav, tabs[3], blks[3], s); if (rc) return rc;
         if (mixed_wav) {
@@ -662,85 +691,38 @@ size_t nhans_workspace_bytes(nhans_ctx* c, int64_t total_frames, int nclips) {
     return p.bytes() + (1 << 20);
 }
 
-static int stft_features_body(nhans_ctx* c, const float* wav, const int64_t* soff, int nclips, int maxf,
-                        float* logmag, float* phase, void* stream) {
-    int rc = NHANS_OK;
-    if (!wav || !soff || !logmag || nclips < 0) return fail(NHANS_EINVAL, "null argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t nb = stft_blocks(soff, nclips, maxf);
-    WsPlan p;
-    int64_t* tabs; int* blocks;
-    p.add(&tabs, 2 * (nclips + 1)); p.add(&blocks, 2 * nb);
-    rc = ws_commit(c, p); if (rc) return rc;
-    return stft_impl(c, wav, soff, nclips, maxf, logmag, phase, tabs, blocks, nullptr, s);
-}
-
 int nhans_stft_features(nhans_ctx* c, const float* wav, const int64_t* soff, int nclips, int maxf,
                         float* logmag, float* phase, void* stream) {
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(stft_features_body(c, wav, soff, nclips, maxf, logmag, phase, stream));
-}
-
-static int embed_body(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, void* stream) {
-    int rc = NHANS_OK;
-    if (!ctx_lm || !emb_out || n < 0) return fail(NHANS_EINVAL, "null argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    WsPlan p; TowerBufs tb;
-    tower_plan(p, c, &tb);
-    rc = ws_commit(c, p); if (rc) return rc;
-    return embed_impl(c, ctx_lm, n, emb_out, tb, s);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (!wav || !soff || !logmag || nclips < 0) return fail(NHANS_EINVAL, "null argument");
+        const size_t nb = stft_blocks(soff, nclips, maxf);
+        WsPlan p;
+        int64_t* tabs; int* blocks;
+        p.add(&tabs, 2 * (nclips + 1)); p.add(&blocks, 2 * nb);
+        const int rc = ws_commit(c, p); if (rc) return rc;
+        return stft_impl(c, wav, soff, nclips, maxf, logmag, phase, tabs, blocks, nullptr, s);
+    });
 }
 
 int nhans_embed(nhans_ctx* c, const float* ctx_lm, int n, float* emb_out, void* stream) {
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(embed_body(c, ctx_lm, n, emb_out, stream));
-}
-
-static int mask_net_body(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
-                   const float* eb, float* logits, float* denoised, void* stream) {
-    int rc = NHANS_OK;
-    if (!logmag || !foff || !ea || !eb || !denoised || nclips < 1) return fail(NHANS_EINVAL, "null argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t total = foff[nclips];
-    if (total <= 0) return NHANS_OK;
-    const int64_t wf = std::min<int64_t>(c->frames_per_chunk, total);
-    WsPlan p; StackBufs sb;
-    stack_plan(p, c, total, nclips, wf, &sb);
-    rc = ws_commit(c, p); if (rc) return rc;
-    return mask_net_impl(c, logmag, foff, nclips, ea, eb, logits, denoised, sb, wf, s);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (!ctx_lm || !emb_out || n < 0) return fail(NHANS_EINVAL, "null argument");
+        WsPlan p; TowerBufs tb;
+        tower_plan(p, c, &tb);
+        const int rc = ws_commit(c, p); if (rc) return rc;
+        return embed_impl(c, ctx_lm, n, emb_out, tb, s);
+    });
 }
 
 int nhans_mask_net(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
                    const float* eb, float* logits, float* denoised, void* stream) {
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(mask_net_body(c, logmag, foff, nclips, ea, eb, logits, denoised, stream));
-}
-
-static int debug_block_output_body(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
-                             const float* eb, int64_t frame0, int nframes, int block, float* out, void* stream) {
-    int rc = NHANS_OK;
-    if (!logmag || !foff || !ea || !eb || !out || block < 0 || block > 8) return fail(NHANS_EINVAL, "bad argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t total = foff[nclips];
-    if (frame0 < 0 || frame0 + nframes > total) return fail(NHANS_EINVAL, "frame range outside batch");
-    WsPlan p; StackBufs sb;
-    stack_plan(p, c, total, nclips, nframes, &sb);
-    rc = ws_commit(c, p); if (rc) return rc;
-    rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc;
-    launch_frame_index(sb.foff_dev, nclips, total, c->lookahead, sb.f_clip, sb.f_t, sb.f_T, s);
-    launch_cond(ea, eb, nclips, c->A("cond.w"), c->A("cond.base"), c->cond_cols, sb.cb_all, s);
-    const float* res = run_stack_chunk(c, logmag, nullptr, sb, frame0, nframes, block + 1, s);
-    size_t per;
-    if (block == 8) per = (size_t)26 * 512;
-    else per = (size_t)c->stack[block].hout * c->stack[block].wout * c->stack[block].cout;
-    if (c->prec && block < 8 && stored_f32(c, c->last_plan, block, 1)) launch_scale_copy(res, per * nframes, c->up(SA(block, 1)), out, s);
-    else if (c->prec) launch_unsplit(res, (int64_t)nframes * (int64_t)(per / (block == 8 ? 512 : c->stack[block].cout)),
-                                block == 8 ? 512 : c->stack[block].cout, c->up(block == 8 ? kActHead : SA(block, 1)), out, s);
-    else HIP_TRY(hipMemcpyAsync(out, res, per * nframes * 4, hipMemcpyDeviceToDevice, s));
-    return NHANS_OK;
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (!logmag || !foff || !ea || !eb || !denoised || nclips < 1) return fail(NHANS_EINVAL, "null argument");
+        const int64_t total = foff[nclips];
+        if (total <= 0) return NHANS_OK;
+        StackBufs sb;
+        return mask_net_impl(c, true, logmag, foff, nclips, ea, eb, logits, denoised, &sb, std::min<int64_t>(c->frames_per_chunk, total), s);
+    });
 }
 
 int nhans_debug_row_classes(int H, int KH, int stride, int pt, int* out, int cap) {
@@ -754,98 +736,85 @@ int nhans_debug_row_classes(int H, int KH, int stride, int pt, int* out, int cap
 
 int nhans_debug_block_output(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
                              const float* eb, int64_t frame0, int nframes, int block, float* out, void* stream) {
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(debug_block_output_body(c, logmag, foff, nclips, ea, eb, frame0, nframes, block, out, stream));
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (!logmag || !foff || !ea || !eb || !out || block < 0 || block > 8) return fail(NHANS_EINVAL, "bad argument");
+        if (frame0 < 0 || frame0 + nframes > foff[nclips]) return fail(NHANS_EINVAL, "frame range outside batch");
+        StackBufs sb;
+        const int rc = stack_begin(c, true, foff, nclips, nframes, ea, eb, false, &sb, s); if (rc) return rc;
+        const float* res = run_stack_chunk(c, logmag, nullptr, sb, frame0, nframes, block + 1, s);
+        size_t per;
+        if (block == 8) per = (size_t)26 * 512;
+        else per = (size_t)c->stack[block].hout * c->stack[block].wout * c->stack[block].cout;
+        if (c->prec && block < 8 && stored_f32(c, c->last_plan, block, 1)) launch_scale_copy(res, per * nframes, c->up(SA(block, 1)), out, s);
+        else if (c->prec) launch_unsplit(res, (int64_t)nframes * (int64_t)(per / (block == 8 ? 512 : c->stack[block].cout)),
+                                    block == 8 ? 512 : c->stack[block].cout, c->up(block == 8 ? kActHead : SA(block, 1)), out, s);
+        else HIP_TRY(hipMemcpyAsync(out, res, per * nframes * 4, hipMemcpyDeviceToDevice, s));
+        return NHANS_OK;
+    });
 }
 
 // Any stored tensor of the stack + head (index 8 .. 24) for frames [frame0, frame0 + nframes): the production launch
 // sequence -- one plan for the whole stack, frames_per_chunk frame windows per pass counted from frame0 -- up to the block
 // that writes it; the tap() point of that tensor converts every chunk's finished buffer.
-static int debug_activation_body(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
-                                 const float* eb, int64_t frame0, int nframes, int index, float* out, void* stream) {
-    int rc = NHANS_OK;
-    if (!logmag || !foff || !ea || !eb || !out || nclips < 1 || nframes < 1) return fail(NHANS_EINVAL, "bad argument");
-    if (index < SA(0, 0) || index >= kNumAct)
-        return fail(NHANS_EINVAL, "activation index outside the stack's 8 .. " + std::to_string(kNumAct - 1) + " (tower tensors: nhans_debug_tower_activation)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t total = foff[nclips];
-    if (frame0 < 0 || frame0 + nframes > total) return fail(NHANS_EINVAL, "frame range outside batch");
-    const int64_t wf = std::min<int64_t>(c->frames_per_chunk, nframes);
-    WsPlan p; StackBufs sb;
-    stack_plan(p, c, total, nclips, wf, &sb);
-    rc = ws_commit(c, p); if (rc) return rc;
-    rc = h2d(c, sb.foff_dev, foff, (nclips + 1) * sizeof(int64_t), s); if (rc) return rc;
-    launch_frame_index(sb.foff_dev, nclips, total, c->lookahead, sb.f_clip, sb.f_t, sb.f_T, s);
-    launch_cond(ea, eb, nclips, c->A("cond.w"), c->A("cond.base"), c->cond_cols, sb.cb_all, s);
-    const int upto = index == kActHead ? 9 : (index - SA(0, 0)) / 2 + 1;
-    c->cap_idx = index; c->cap_out = out;
-    for (int64_t g0 = frame0; g0 < frame0 + nframes; g0 += wf) {
-        run_stack_chunk(c, logmag, nullptr, sb, g0, (int)std::min<int64_t>(wf, frame0 + nframes - g0), upto, s);
-        if (launch_error_pending()) break;
-    }
-    c->cap_idx = -1; c->cap_out = nullptr;
-    return NHANS_OK;
-}
-
 int nhans_debug_activation(nhans_ctx* c, const float* logmag, const int64_t* foff, int nclips, const float* ea,
                            const float* eb, int64_t frame0, int nframes, int index, float* out, void* stream) {
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(debug_activation_body(c, logmag, foff, nclips, ea, eb, frame0, nframes, index, out, stream));
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (!logmag || !foff || !ea || !eb || !out || nclips < 1 || nframes < 1) return fail(NHANS_EINVAL, "bad argument");
+        if (index < SA(0, 0) || index >= kNumAct)
+            return fail(NHANS_EINVAL, "activation index outside the stack's 8 .. " + std::to_string(kNumAct - 1) + " (tower tensors: nhans_debug_tower_activation)");
+        if (frame0 < 0 || frame0 + nframes > foff[nclips]) return fail(NHANS_EINVAL, "frame range outside batch");
+        const int64_t wf = std::min<int64_t>(c->frames_per_chunk, nframes);
+        StackBufs sb;
+        const int rc = stack_begin(c, true, foff, nclips, wf, ea, eb, false, &sb, s); if (rc) return rc;
+        const int upto = index == kActHead ? 9 : (index - SA(0, 0)) / 2 + 1;
+        c->cap_idx = index; c->cap_out = out;
+        for (int64_t g0 = frame0; g0 < frame0 + nframes; g0 += wf) {
+            run_stack_chunk(c, logmag, nullptr, sb, g0, (int)std::min<int64_t>(wf, frame0 + nframes - g0), upto, s);
+            if (launch_error_pending()) break;
+        }
+        c->cap_idx = -1; c->cap_out = nullptr;
+        return NHANS_OK;
+    });
 }
 
 // Any stored tensor of the embedding tower (index 0 .. 7) for n context images: nhans_embed's own launches (chunks of
 // contexts_per_chunk images, the pooled embeddings go to the workspace) with the tap() point of that tensor copying out.
-static int debug_tower_activation_body(nhans_ctx* c, const float* ctx_lm, int n, int index, float* out, void* stream) {
-    int rc = NHANS_OK;
-    if (!ctx_lm || !out || n < 1) return fail(NHANS_EINVAL, "bad argument");
-    if (index < 0 || index >= SA(0, 0))
-        return fail(NHANS_EINVAL, "activation index outside the tower's 0 .. 7 (stack tensors: nhans_debug_activation)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    WsPlan p; TowerBufs tb; float* emb;
-    tower_plan(p, c, &tb);
-    p.add(&emb, (size_t)n * kEmb);
-    rc = ws_commit(c, p); if (rc) return rc;
-    c->cap_idx = index; c->cap_out = out;
-    rc = embed_impl(c, ctx_lm, n, emb, tb, s);
-    c->cap_idx = -1; c->cap_out = nullptr;
-    return rc;
-}
-
 int nhans_debug_tower_activation(nhans_ctx* c, const float* ctx_lm, int n, int index, float* out, void* stream) {
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(debug_tower_activation_body(c, ctx_lm, n, index, out, stream));
-}
-
-static int istft_body(nhans_ctx* c, const float* logmag, const float* phase, const int64_t* foff, int nclips,
-                const int64_t* ooff, float* wav_out, void* stream) {
-    int rc = NHANS_OK;
-    if (!logmag || !phase || !foff || !ooff || !wav_out) return fail(NHANS_EINVAL, "null argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t nb = istft_blocks(foff, nclips);
-    WsPlan p;
-    int64_t* tabs; int* blocks;
-    p.add(&tabs, 2 * (nclips + 1)); p.add(&blocks, 2 * nb);
-    rc = ws_commit(c, p); if (rc) return rc;
-    return istft_impl(c, logmag, phase, foff, nclips, ooff, wav_out, tabs, blocks, s);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (!ctx_lm || !out || n < 1) return fail(NHANS_EINVAL, "bad argument");
+        if (index < 0 || index >= SA(0, 0))
+            return fail(NHANS_EINVAL, "activation index outside the tower's 0 .. 7 (stack tensors: nhans_debug_activation)");
+        WsPlan p; TowerBufs tb; float* emb;
+        tower_plan(p, c, &tb);
+        p.add(&emb, (size_t)n * kEmb);
+        int rc = ws_commit(c, p); if (rc) return rc;
+        c->cap_idx = index; c->cap_out = out;
+        rc = embed_impl(c, ctx_lm, n, emb, tb, s);
+        c->cap_idx = -1; c->cap_out = nullptr;
+        return rc;
+    });
 }
 
 int nhans_istft(nhans_ctx* c, const float* logmag, const float* phase, const int64_t* foff, int nclips,
                 const int64_t* ooff, float* wav_out, void* stream) {
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(istft_body(c, logmag, phase, foff, nclips, ooff, wav_out, stream));
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (!logmag || !phase || !foff || !ooff || !wav_out) return fail(NHANS_EINVAL, "null argument");
+        const size_t nb = istft_blocks(foff, nclips);
+        WsPlan p;
+        int64_t* tabs; int* blocks;
+        p.add(&tabs, 2 * (nclips + 1)); p.add(&blocks, 2 * nb);
+        const int rc = ws_commit(c, p); if (rc) return rc;
+        return istft_impl(c, logmag, phase, foff, nclips, ooff, wav_out, tabs, blocks, s);
+    });
 }
 
 int nhans_enhance_clips(nhans_ctx* c, const float* mix, const int64_t* moff, int nclips, const float* ca,
                         const int64_t* caoff, const float* cbw, const int64_t* cboff, float* den_wav,
                         float* mixed_wav, float* logmag_out, float* phase_out, float* logits_out, float* emb_out,
                         void* stream) {
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(enhance_clips_body(c, mix, moff, nclips, ca, caoff, cbw, cboff, den_wav, mixed_wav, logmag_out, phase_out, logits_out, emb_out, stream));
+    return ctx_call(c, stream, [&](hipStream_t) -> int {
+        return enhance_clips_body(c, mix, moff, nclips, ca, caoff, cbw, cboff, den_wav, mixed_wav, logmag_out, phase_out, logits_out, emb_out, stream);
+    });
 }
 
 }  // extern "C"

@@ -217,7 +217,7 @@ def _pad(v, npad):
 
 
 def fold_arrays(W, kind, split_f16=True):
-    """-> dict name -> float32 1-D array (see csrc/host_ctx.hip and csrc/host_net.hip for the consumer).  With split_f16 the
+    """-> dict name -> float32 1-D array (csrc/net_weights.h declares every one of them with its size for the consumer, csrc/host_net.hip).  With split_f16 the
     blob also carries every packed conv weight in split-f16 form (`*_h`) and the per-channel
     unscale vectors (`<conv>.ws`) for the f16x3 mode."""
     out = {}

@@ -208,6 +208,60 @@ def test_blob_without_the_tables_two_terms_still_runs(lib_built, weights_denoise
     assert not any(n.startswith("conv_wino") for n in names)
 
 
+@pytest.mark.parametrize("missing", ["m3.c1.wpk_h", "t2.c2.ws"])
+def test_split_blob_without_one_of_its_split_arrays_is_refused(eng, weights_denoiser, monkeypatch, missing):
+    """A blob that carries split-f16 weights (`head.dense.wpk_h`) must carry every `*_h` pack and `<conv>.ws` a precision-1
+    launch dereferences (csrc/net_weights.h).  One without `m3.c1.wpk_h` used to create a context and accept precision 1.
+    The refusal comes from nhans_create itself: no context, so no entry point can have launched anything -- and the profile
+    of a context alive beside it stays empty."""
+    from nhans_amd import fold
+    full = fold.fold_arrays
+
+    def without_one(W, kind, split_f16=True):
+        arrays = full(W, kind, split_f16)
+        assert missing in arrays
+        return {k: v for k, v in arrays.items() if k != missing}
+
+    monkeypatch.setattr(fold, "fold_arrays", without_one)
+    eng.set_option("profile", 1)
+    eng.profile_reset()
+    try:
+        with pytest.raises(hip.NhansError) as err:
+            engine.Engine("denoiser", weights_denoiser, precision="f16x3")
+        assert err.value.code == -1 and "'%s' missing or wrong size" % missing in str(err.value)
+        assert ("'%s'" % missing).encode() in eng.lib.nhans_last_error()
+        blob = bytearray(fold.fold_weights(weights_denoiser, "denoiser"))
+        handle = ctypes.c_void_p(None)
+        rc = eng.lib.nhans_create(hip.KIND_CODE["denoiser"], (ctypes.c_char * len(blob)).from_buffer(blob), len(blob), 0,
+                                  ctypes.byref(handle))
+        assert rc == -1 and not handle.value
+        assert eng.profile() == {}
+    finally:
+        eng.set_option("profile", 0)
+
+
+def test_blob_without_split_weights_runs_f32_and_refuses_f16x3(lib_built, weights_denoiser, monkeypatch):
+    """An f32-only blob (fold_arrays(..., split_f16=False)): none of the split arrays is asked for, precision 0 computes what
+    the full blob computes at precision 0, precision 1 is refused."""
+    from nhans_amd import fold
+    mix = apply.trim_to_frames(apply.normalise(synth.mixture(5, 0.3)))
+    ca, cb = apply.normalise(synth.silent()), apply.normalise(synth.noise_context(5))
+    e = engine.Engine("denoiser", weights_denoiser, precision="f32")
+    ref = e.enhance([mix], [ca], [cb], want_mixed=False, taps=True)
+    e.close()
+    full = fold.fold_arrays
+    monkeypatch.setattr(fold, "fold_arrays", lambda W, kind, split_f16=True: full(W, kind, False))
+    e = engine.Engine("denoiser", weights_denoiser, precision="f32")
+    try:
+        got = e.enhance([mix], [ca], [cb], want_mixed=False, taps=True)
+        with pytest.raises(hip.NhansError, match="the folded blob carries no split-f16 weights"):
+            e.set_precision("f16x3")
+        assert e.precision == "f32"
+    finally:
+        e.close()
+    assert np.array_equal(got["logits"], ref["logits"]) and np.array_equal(got["denoised_wav"][0], ref["denoised_wav"][0])
+
+
 def test_blob_of_an_older_packing_version_is_refused(lib_built, weights_denoiser):
     """Advisor finding (round 3): the K order of the packed weights changed while the blob said version 1, so a blob
     folded by an older tree loaded and computed wrong results.  The version now follows the packing conventions
