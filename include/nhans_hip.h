@@ -161,6 +161,9 @@ void nhans_destroy(nhans_ctx* ctx);
  *          "split_k" (1, default: the launches too small to fill the chip -- the head's dense layer, the embedding tower
  *           at a few clips -- run one workgroup per (tile, K group) through a scratch buffer; 0: every workgroup walks
  *           its K groups itself.  The groups and the order of the additions depend on the layer only: identical bits),
+ *          "bss_group_bytes" (2147483648, default: the bytes of workspace the Gram factors of one group of nhans_bss_eval's
+ *           clips may take together; a group holds at least one clip.  A debug value: the grouping changes no bit of any
+ *           record, a small value only forces more groups),
  * (A `make DEV=1` build adds "debug_cycles_ptr" and the NHANS_ABLATE environment switch used by tools/; the default build has no developer hooks and reads no environment.)
  * Besides the workspace a context holds split-K scratch for the few launches that are too small to fill the chip (the
  * head's dense layer, the embedding tower at a few clips): allocated on the first such launch, sized by what the launches
@@ -995,6 +998,49 @@ int nhans_stoi_resample(nhans_ctx* ctx, const float* in16_dev, const int64_t* in
                         const int64_t* out_offsets_host, void* stream);
 int nhans_stoi(nhans_ctx* ctx, const float* est10_dev, const int64_t* est_offsets_host, const float* tgt10_dev,
                const int64_t* tgt_offsets_host, int nclips, double* out_dev, double* segments_out_dev, void* stream);
+
+/* ---- BSS Eval: SDR, SIR and SAR against target and interferer ---------------------------------------------------------------
+ * The decomposition of Vincent, Gribonval and Fevotte (2006; bss_eval_sources of the published toolboxes) of one estimate
+ * with fixed roles, computed where the signals are (n-hans_amd/csrc/bsseval.hip).  Added without
+ * moving NHANS_ABI_VERSION; a caller that may meet an older library looks the function up by symbol.  Inputs are float32:
+ * an estimate e and J = 1 or 2 sources, s_0 the target and s_1 the interferer, every signal cut to the n samples all of
+ * them have, and a filter length L, 1 <= L <= 512.  Every signal is zero outside [0, n), t runs over [0, n + L - 1), and
+ * every operation is in double.
+ *   correlations  r_jk[d] = sum_t s_j[t] s_k[t + d] for |d| < L;  q_k[b] = sum_t e[t + b] s_k[t] for 0 <= b < L.  A product of
+ *                 two float32 values is exact in double; the sums are formed directly, in a fixed order (bsseval.hip).
+ *   Gram system   G[(j,a),(k,b)] = r_jk[a - b], J L x J L, symmetric, block Toeplitz;  D[(k,b)] = q_k[b].
+ *   solves        G C = D by Cholesky (lower factor, no pivoting) and two triangular solves; the leading L x L block of G
+ *                 with D[:L] likewise gives C0 (its factor is the leading block of G's factor: one factorisation serves both).
+ *                 A pivot that is not finite or is <= J L 2^-52 G_kk (G_kk the diagonal element of G in the pivot's row)
+ *                 makes the clip SINGULAR: the six energies and the three figures are NaN, the flag field is 1, n, J and L
+ *                 are filled in, and the filters, where asked for, are NaN.  An all-zero source is singular, and so is a
+ *                 clip of no samples.  Nothing is refused for it.
+ *   projections   P[t] = sum_k sum_b C[k,b] s_k[t - b];  s_target[t] = sum_b C0[b] s_0[t - b];  e_interf = P - s_target;
+ *                 e_artif = e - P.
+ *   energies      each one fixed-order sum of squares over t: E_e = |e|^2, E_tgt = |s_target|^2, E_int = |e_interf|^2,
+ *                 E_art = |e_artif|^2, E_dist = |e - s_target|^2, E_ti = |s_target + e_interf|^2
+ *   figures       sdr_db = 10 log10(E_tgt / E_dist), sir_db = 10 log10(E_tgt / E_int), sar_db = 10 log10(E_ti / E_art), by
+ *                 IEEE.  With J = 1 e_interf is identically zero: sir_db = +inf and sar_db has the value of sdr_db.
+ *                 Non-finite samples: unspecified.
+ *   record        NHANS_BSS_FIELDS doubles: n, J, L, E_e, E_tgt, E_int, E_art, E_dist, E_ti, sdr_db, sir_db, sar_db, singular,
+ *                 0, 0, 0
+ * The decomposition does not change when a source is scaled or filtered by up to L taps.  The published toolboxes form
+ * the correlations by FFT and fall back to least squares on a singular Gram matrix; figures agree with theirs to rounding
+ * at best, not bit for bit.  Every figure is a function of the clip tuple and L alone: it has the same bits alone or in
+ * any batch, at any offset, on every run; no floating-point atomics, no reduction whose shape depends on the batch.
+ *
+ * Clip i of the estimates is est_dev[est_offsets_host[i] .. est_offsets_host[i + 1]); src_dev is a HOST array of nsrc device
+ * pointers and src_offsets_host a host array of nsrc offset arrays: clip i of source j is src_dev[j][src_offsets_host[j][i]
+ * .. [i + 1]).  out_dev receives NHANS_BSS_FIELDS doubles per clip.  filters_out_dev (nullable) receives per clip C -- J L
+ * doubles, source 0's taps first -- and then C0 -- L doubles.  The factor of G takes (J L)^2 doubles of the workspace per
+ * clip, 8 MiB at J = 2 and L = 512: the clips of a call are worked in groups whose factors together stay within 2 GiB
+ * (256 clips at full size; option "bss_group_bytes"), and the grouping changes no bit of any record.  NHANS_EINVAL, naming
+ * the clip, before anything is launched: nclips < 0, nsrc not 1 or 2, filt_len outside 1 ... 512, a NULL that is needed,
+ * an offset array that descends, a clip of more than 2^31 - 1 samples. */
+#define NHANS_BSS_FIELDS 16     /* n, J, L, E_e, E_tgt, E_int, E_art, E_dist, E_ti, sdr_db, sir_db, sar_db, singular, 0, 0, 0 */
+int nhans_bss_eval(nhans_ctx* ctx, const float* est_dev, const int64_t* est_offsets_host, const float* const* src_dev,
+                   const int64_t* const* src_offsets_host, int nsrc, int nclips, int filt_len, double* out_dev,
+                   double* filters_out_dev, void* stream);
 
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the

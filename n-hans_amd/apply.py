@@ -65,6 +65,8 @@ class Flags(object):
     highband = None      # --highband G: the input's own band above 8 kHz, times G, added to the files written at the input's rate (live.fullband_mix)
     score_against = None # --score_against TARGET: score the files written against a clean target on the device (score.py)
     score_out = None     # --score_out PATH.json: where the scores go (stdout otherwise)
+    bss = False          # --bss: with --score_against and --interferer, also SDR, SIR and SAR (score.py: bss_reference is the definition)
+    interferer = None    # --interferer FILE: the signal that was to be removed, for --bss
     stoi = False         # --stoi: with --score_against, also STOI and extended STOI (score.py: stoi_reference is the definition)
     lookahead_ms = 10 * spec.LOOKAHEAD   # --lookahead_ms: 10 ms per frame of look-ahead (include/nhans_hip.h: "lookahead"), 170 = all 17
 
@@ -612,7 +614,7 @@ def apply_demo_separator(cleanpath, noisepath, save_to, mix_on="host"):
 
 
 def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelname='nhans', step=0, scores=False, mix_on="host",
-                       stoi=False):
+                       stoi=False, bss=False):
     """Evaluation-reader pipeline for one (speech, pos noise, neg noise) triple: SN/reader.py:310-420
     (eval branch, eval_stride 1) + SN/main.py:264-353.  Mixes at the reference's md5-derived SNRs,
     runs the network on frames from context_frames on, writes the reference's five wavs
@@ -623,6 +625,9 @@ def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelnam
     under "rows" the three row arrays that were scored.  mix_on="gpu": the mixing on the device (the same files and loss).
     stoi=True (with scores): the records also carry STOI and extended STOI of the same waveforms (Engine.stoi_device,
     merged by score.merge_stoi) and the improvement stoi_i and estoi_i; the files and the loss are what they are without it.
+    bss=True (with scores): the records also carry SDR, SIR and SAR (Engine.bss_eval_device, merged by score.merge_bss) of
+    the same waveforms against the mixing's own target and negative noise -- as mixed, from the first scored sample on --
+    and the improvement sdr_i, sir_i and sar_i; the files and the loss are what they are without it.
     A corpus at several SNR pairs in one pass: evaluate_corpus."""
     from . import mixing
     eng = get_engine(spec.DENOISER)
@@ -641,7 +646,9 @@ def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelnam
         wavwrite(_eval_wav_path(dump_dir, modelname, step, (cleanpath, noisepospath, noisenegpath), snr_pos, snr_neg, kind),
                  FLAGS.Fs, w)
     if scores:
-        return loss, _utterance_scores(eng, den, mix_rt, extras[0], den_lm, mix_lm, tgt_lm, stoi)
+        first = Noise_Win * spec.HOP                    # the sample the scored waveforms begin at
+        return loss, _utterance_scores(eng, den, mix_rt, extras[0], den_lm, mix_lm, tgt_lm, stoi,
+                                       (target[first:], neg_sig[first:]) if bss else None)
     return loss
 
 
@@ -651,7 +658,7 @@ def _eval_wav_path(dump_dir, modelname, step, triple, snr_pos, snr_neg, kind):
 
 
 def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None, per_frame=False, modelname='nhans', step=0,
-                    stoi=False):
+                    stoi=False, bss=False):
     """evaluate_utterance(scores=True) for a corpus in one pass.  triples: (cleanpath, pospath, negpath) each; snrs: the
     (snr_pos, snr_neg) pairs applied to every triple (None: the triple's own mixing.eval_snrs).  The files are read,
     normalised and trimmed on the host and uploaded once; the mixtures of all (triple, SNR pair) jobs (Engine.mix_device),
@@ -663,7 +670,8 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
     device forms it: the "loss" of evaluate_utterance's scores, bit for bit), "denoised", "mixed", "improvement" (as
     evaluate_utterance's scores) and "mix" (the job's mixing record); per_frame=True: plus "per_frame" in "denoised" and
     "mixed", float64 [frames, 3] as Context.score's.  stoi=True: STOI and extended STOI in the same pass, as
-    evaluate_utterance(scores=True, stoi=True) merges them, bit for bit; only their records come back."""
+    evaluate_utterance(scores=True, stoi=True) merges them, bit for bit; only their records come back.  bss=True: SDR, SIR
+    and SAR against each job's own target and negative noise, which the mixing left in HBM, likewise."""
     from . import context, mixing, score
     eng = get_engine(spec.DENOISER)
     speech, noises, jobs, meta = [], [], [], []
@@ -684,7 +692,7 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
     sig, off, mix_rec = eng.mix_device(sp_t, sp_off, nz_t, nz_off, jobs)
     dump = dump_dir is not None
     res = eng._with_lookahead(lookahead, lambda: context.redo_saturated_in_f32(
-        eng, lambda: _corpus_device(eng, sig, off, per_frame, dump, stoi)))
+        eng, lambda: _corpus_device(eng, sig, off, per_frame, dump, stoi, bss)))
     eng._sync()
     mix_rec = mix_rec.cpu().numpy()
     down = {k: v.cpu().numpy() for k, v in res["records"].items()}
@@ -700,6 +708,8 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
             r[name] = dict(score.record(down[name + "_wave"][j]), **score.row_record(down[name + "_rows"][j]))
             if stoi:
                 r[name] = score.merge_stoi(r[name], score.stoi_record(down[name + "_stoi"][j]))
+            if bss:
+                r[name] = score.merge_bss(r[name], score.bss_record(down[name + "_bss"][j]))
             if per_frame:
                 r[name]["per_frame"] = frames[name][roff[j]:roff[j + 1]].copy()
         r["loss"] = r["denoised"]["loss"]
@@ -712,7 +722,7 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
     return out
 
 
-def _corpus_device(eng, sig, off, per_frame, dump, stoi=False):
+def _corpus_device(eng, sig, off, per_frame, dump, stoi=False, bss=False):
     """The launches of evaluate_corpus after the mixing, everything in HBM: job j's signals are [off[j], off[j + 1]) of
     sig's tensors -> device records (and, for a dump, waveforms)."""
     import torch
@@ -737,12 +747,17 @@ def _corpus_device(eng, sig, off, per_frame, dump, stoi=False):
     mix_rt, _ = eng.istft(lm_s, ph_s, roff)
     tgt_wav, _ = eng.istft(tlm_s, tph_s, roff)
     records, frames = {}, {}
+    # the sources of BSS Eval: job j's target and drop signals as mixed, from the first scored sample on (a clip is cut to
+    # the samples the estimate has, so a source's range may run on into the next job's)
+    soff = [o + Noise_Win * spec.HOP for o in off[:-1]] + [off[-1]]
     for name, wav, rows in (("denoised", den_wav, den), ("mixed", mix_rt, lm_s)):
         w = eng.score_device(wav, ooff, tgt_wav, ooff, per_frame=per_frame)
         r = eng.score_rows(rows, tlm_s, roff, per_frame=per_frame, frames_out=w[1] if per_frame else None)
         records[name + "_wave"], records[name + "_rows"] = (w[0], r[0]) if per_frame else (w, r)
         if stoi:
             records[name + "_stoi"] = eng.stoi_device(wav, ooff, tgt_wav, ooff)
+        if bss:
+            records[name + "_bss"] = eng.bss_eval_device(wav, ooff, [(sig["target"], soff), (sig["drop"], soff)])
         if per_frame:
             frames[name] = r[1]
     waves = {}
@@ -754,7 +769,7 @@ def _corpus_device(eng, sig, off, per_frame, dump, stoi=False):
     return {"records": records, "frames": frames, "waves": waves, "roff": roff, "ooff": ooff}
 
 
-def _utterance_scores(eng, den, mix_rt, target, den_lm, mix_lm, tgt_lm, stoi=False):
+def _utterance_scores(eng, den, mix_rt, target, den_lm, mix_lm, tgt_lm, stoi=False, bss_sources=None):
     import torch
     from . import score
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(eng.device)
@@ -767,6 +782,9 @@ def _utterance_scores(eng, den, mix_rt, target, den_lm, mix_lm, tgt_lm, stoi=Fal
         if stoi:
             st = eng.stoi_device(dev(wav), [0, len(wav)], tw, [0, len(target)])
             out[name] = score.merge_stoi(out[name], score.stoi_record(st.cpu().numpy()[0]))
+        if bss_sources is not None:
+            b = eng.bss_eval_device(dev(wav), [0, len(wav)], [(dev(x), [0, len(x)]) for x in bss_sources])
+            out[name] = score.merge_bss(out[name], score.bss_record(b.cpu().numpy()[0]))
     out["improvement"] = score.improvement(out["mixed"], out["denoised"])
     out["rows"] = {"denoised": den_lm, "mixed": mix_lm, "target": tgt_lm}
     return out
@@ -821,7 +839,19 @@ def _parse(argv, prog):
     p.add_argument('--stoi', action='store_true',
                    help='with --score_against: also STOI and extended STOI of the same files against the target, converted to '
                         '10 kHz and computed on the device; the audio files are what they are without the flag')
+    p.add_argument('--bss', action='store_true',
+                   help='with --score_against and --interferer: also SDR, SIR and SAR (BSS Eval, filters of 512 taps) of the same '
+                        'files against the target and the interferer, computed on the device; the audio files are what they '
+                        'are without the flag')
+    p.add_argument('--interferer', default=None, metavar='FILE',
+                   help='for --bss: the signal that was to be removed -- the noise, or the other speaker; a wav in file mode, a '
+                        'directory paired by file name in directory mode.  It needs no peak scaling: the decomposition does not '
+                        'change when a source is scaled, or filtered by up to 512 taps')
     a = p.parse_args(argv)
+    if a.bss != (a.interferer is not None):
+        p.error('--bss and --interferer FILE go together')
+    if a.bss and a.score_against is None:
+        p.error('--bss needs --score_against TARGET')
     if a.score_out is not None and a.score_against is None:
         p.error('--score_out needs --score_against TARGET')
     if a.stoi and a.score_against is None:
@@ -839,6 +869,15 @@ def _parse(argv, prog):
                     p.error('--score_against: %s has no target of the same name in %s' % (name, a.score_against))
         elif not os.path.isfile(a.score_against):
             p.error('--score_against: %s is not a file' % a.score_against)
+        if a.bss:
+            if os.path.isdir(a.input) != os.path.isdir(a.interferer):
+                p.error('--interferer must be a directory when --input is one, and a file when it is a file')
+            if os.path.isdir(a.input):
+                for name in sorted(os.listdir(a.input)):
+                    if name.lower().endswith('.wav') and not os.path.isfile(os.path.join(a.interferer, name)):
+                        p.error('--interferer: %s has no interferer of the same name in %s' % (name, a.interferer))
+            elif not os.path.isfile(a.interferer):
+                p.error('--interferer: %s is not a file' % a.interferer)
     if a.fbank_out is not None:
         if os.path.isdir(a.input):
             p.error('--fbank_out works on one input file; %s is a directory' % a.input)
@@ -930,7 +969,8 @@ def _score_jobs(kind, a, jobs):
     import json
     from . import score
     directory = os.path.isdir(a.input)
-    done, skipped, est, tgt = [], [], [], []
+    done, skipped, est, tgt, interf = [], [], [], [], []
+    bss = getattr(a, "bss", False)
     for mixedpath, _, _, save_to in jobs:
         mp = side_prefix(save_to) + 'mixed_processed.wav'
         if not (os.path.exists(save_to) and os.path.exists(mp)):
@@ -939,8 +979,11 @@ def _score_jobs(kind, a, jobs):
         t = scaled_target(mixedpath, os.path.join(a.score_against, os.path.basename(mixedpath)) if directory else a.score_against)
         est += [wavread(save_to)[1], wavread(mp)[1]]
         tgt += [t, t]
+        if bss:
+            x = _reader()(os.path.join(a.interferer, os.path.basename(mixedpath)) if directory else a.interferer).astype(np.float32)
+            interf += [x, x]
         done.append(mixedpath)
-    recs = get_enhancer(kind).score(est, tgt, stoi=getattr(a, "stoi", False)) if est else []
+    recs = get_enhancer(kind).score(est, tgt, stoi=getattr(a, "stoi", False), bss=interf if bss else None) if est else []
     files = {}
     for i, path in enumerate(done):
         den, mix = recs[2 * i], recs[2 * i + 1]

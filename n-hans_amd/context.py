@@ -126,16 +126,22 @@ class Context:
 
 
     # ---- scoring against a clean target (include/nhans_hip.h: nhans_score_*) ---------------------
-    def score(self, estimates, targets, per_frame=False, stoi=False):
+    def score(self, estimates, targets, per_frame=False, stoi=False, bss=None):
         """Lists of float32 waveforms, estimate i against target i over their common prefix -> one dict per clip: the
         waveform figures (score.FIELDS: si_sdr_db, snr_db, segsnr_db, ...) and the row figures loss and lsd_db of the two
         signals' own log-magnitude rows (nhans_stft_features) -- one upload, two STFTs and the two score calls on the
         device, one download of the records.  per_frame=True: plus "per_frame", float64 [frames, 3]: each frame's clamped
         segmental value (NaN where its target is silent), loss and lsd.  stoi=True: plus the figures of Context.stoi of
         the same pairs (16 kHz signals), merged into each record -- a name the record already has (n, frames: there the
-        16 kHz samples and the STFT rows) is prefixed: stoi_n, stoi_frames."""
+        16 kHz samples and the STFT rows) is prefixed: stoi_n, stoi_frames.  bss: a list of interferers (or True: the
+        target alone) -- plus the figures of Context.bss_eval of the same estimates (sdr_db, sir_db, sar_db, ...), merged
+        into each record; its n is bss_n."""
         if len(estimates) != len(targets):
             raise ValueError("score: one target per estimate")
+        if bss is not None and bss is not False:
+            return [score_mod.merge_bss(r, b)
+                    for r, b in zip(self.score(estimates, targets, per_frame=per_frame, stoi=stoi),
+                                    self.bss_eval(estimates, targets, None if bss is True else bss))]
         if stoi:
             return [score_mod.merge_stoi(r, t)
                     for r, t in zip(self.score(estimates, targets, per_frame=per_frame), self.stoi(estimates, targets))]
@@ -220,6 +226,38 @@ class Context:
             rec = score_mod.stoi_record(got[i * nf:(i + 1) * nf])
             if per_segment:
                 rec["per_segment"] = got[n * nf:].reshape(ns, 2)[soff[i]:soff[i] + rec["segments"]].copy()
+            res.append(rec)
+        return res
+
+    # ---- BSS Eval against target and interferer (include/nhans_hip.h: nhans_bss_eval) -------------
+    def bss_eval(self, estimates, targets, interferers=None, filt_len=score_mod.BSS_MAX_FILTER, filters=False):
+        """Lists of float32 waveforms, estimate i against target i and (interferers given) interferer i over the samples
+        all of them have -> one dict per clip by score.BSS_FIELDS: sdr_db, sir_db, sar_db, the six energies, n, J, L and
+        singular (1: the Gram matrix failed the pivot rule -- an all-zero source, say -- and every figure is NaN).  One
+        upload, one call, one download.  filters=True: plus "C", float64 [J, filt_len], and "C0", float64 [filt_len]."""
+        src = [targets] if interferers is None else [targets, interferers]
+        if any(len(s) != len(estimates) for s in src):
+            raise ValueError("bss_eval: one target%s per estimate" % ("" if interferers is None else " and one interferer"))
+        lib, mem, n, J, L = self.lib, Mem(self), len(estimates), len(src), int(filt_len)
+        flats = [flat(x) for x in [estimates] + src]
+        base = offsets(len(f) for f, _ in flats)
+        buf = mem.up(np.ascontiguousarray(np.concatenate([f for f, _ in flats])))
+        nf, per = hip.BSS_FIELDS, (J + 1) * L if filters else 0
+        out = mem.empty(n * (nf + per), np.float64)
+        try:
+            at = lambda k: ctypes.c_void_p(mem.p(buf).value + 4 * base[k])
+            hip.check(bss_call(lib, self.handle, at(0), flats[0][1], [at(1 + j) for j in range(J)], [flats[1 + j][1] for j in range(J)],
+                               n, L, mem.p(out), ctypes.c_void_p(mem.p(out).value + 8 * n * nf) if filters else None, mem.stream()))
+            self._sync()
+            got = np.array(mem.down(out, n * (nf + per), np.float64), dtype=np.float64)
+        finally:
+            mem.free(buf, out)
+        res = []
+        for i in range(n):
+            rec = score_mod.bss_record(got[i * nf:(i + 1) * nf])
+            if filters:
+                f = got[n * nf + i * per:n * nf + (i + 1) * per]
+                rec.update(C=f[:J * L].reshape(J, L).copy(), C0=f[J * L:].copy())
             res.append(rec)
         return res
 
@@ -364,6 +402,16 @@ def mix_job_arrays(jobs, speech_off):
     sk, sd = [(ctypes.c_double * nj)(*[float(j[k] or 0) for j in jobs]) for k in (3, 4)]     # (None: no keep noise, no SNR)
     off = offsets(speech_off[i + 1] - speech_off[i] if 0 <= i < ns else 0 for i in si)
     return (si, ki, di, sk, sd), off
+
+
+def bss_call(lib, handle, est_p, est_off, src_ps, src_offs, n, filt_len, out_p, filters_p, stream):
+    """nhans_bss_eval with its two host tables built from J device pointers and J offset lists -> the call's return code"""
+    J = len(src_ps)
+    ptrs = (ctypes.c_void_p * J)(*[p.value if isinstance(p, ctypes.c_void_p) else p for p in src_ps])
+    offs = [hip.i64_array(o) for o in src_offs]
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    tab = (i64p * J)(*[ctypes.cast(o, i64p) for o in offs])
+    return lib.nhans_bss_eval(handle, est_p, hip.i64_array(est_off), ptrs, tab, J, n, int(filt_len), out_p, filters_p, stream)
 
 
 def end_flags(end, n):

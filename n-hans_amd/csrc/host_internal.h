@@ -13,7 +13,8 @@
 //   host_score.hip    nhans_score_wave, nhans_score_rows
 //   host_mix.hip      nhans_mix, nhans_mix_snr_factor
 //   host_stoi.hip     nhans_stoi, nhans_stoi_resample, nhans_stoi_out_count
-// A unit calls down only: ctx <- net <- online <- live, ctx <- fbank <- online, ctx <- rate <- live, ctx <- score, ctx <- mix and ctx <- rate <- stoi.  (One call goes up: the built-in calibration
+//   host_bsseval.hip  nhans_bss_eval
+// A unit calls down only: ctx <- net <- online <- live, ctx <- fbank <- online, ctx <- rate <- live, ctx <- score, ctx <- mix, ctx <- rate <- stoi and ctx <- bsseval.  (One call goes up: the built-in calibration
 // of nhans_create runs the whole offline path, enhance_clips_body.)  Only what crosses a unit boundary is declared here;
 // everything else stays in its unit's anonymous namespace.
 // Nothing declared here joins the library's dynamic symbols (visibility hidden) except the object types the C header
@@ -101,6 +102,7 @@ struct nhans_ctx {
     // still fits the kernels' 32-bit element offsets; the three ping-pong buffers are then 20 GB of the 288.
     int64_t frames_per_chunk = 3776;
     int contexts_per_chunk = 64;
+    size_t bss_group_bytes = (size_t)2 << 30;   // option bss_group_bytes: the factor storage one group of nhans_bss_eval's clips may take (host_bsseval.hip; same bits)
     int lookahead = kCenter;    // option lookahead: frame t of a clip sees the clip end at min(len, t + lookahead + 1) (offline calls)
     // pinned staging ring for the small host tables (offsets, block lists) copied per call
     char* pin = nullptr;

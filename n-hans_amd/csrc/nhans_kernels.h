@@ -523,4 +523,33 @@ void launch_stoi_segments(const char* kernel, const StoiRun* runs_dev, int nruns
 void launch_stoi_finish(const char* kernel, const StoiRun* runs_dev, int nruns, const long long* nkept, const double* segs,
                         double* rec, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// BSS Eval: SDR, SIR and SAR against target and interferer (bsseval.hip; include/nhans_hip.h: nhans_bss_eval).  One BssRun
+// per clip of a group, empty ones included: n common samples at est / s0 / s1 (s1: nullptr with one source), workgroups
+// [ctile0, ctile0 + ctiles) of the correlation launch (kBssCorrTile samples each; their partial sums are rows of the same
+// numbers) and [ptile0, ptile0 + ptiles) of the projection launch (kBssProjTile samples of [0, n + L - 1) each; their
+// partial energies likewise).  Both ascend from 0 over the runs.  L and J = 1 | 2 are the call's; NI = 6 sums of L lags
+// with two sources (r00, r10, r01, r11, q0, q1), 2 with one (r00, q0); M = J L.
+struct BssRun {
+    const float* est;
+    const float* s0;
+    const float* s1;
+    long long n, ctile0, ctiles, ptile0, ptiles;
+};
+constexpr int kBssFields = 16, kBssMaxL = 512, kBssCorrTile = 2048, kBssProjTile = 1024, kBssPanel = 16;
+// part: [tiles][NI][L]
+void launch_bss_corr(const char* kernel, const BssRun* runs_dev, int nruns, long long ntiles, int L, int J, double* part, hipStream_t s);
+// lag: [clips][NI][L]
+void launch_bss_reduce(const char* kernel, const BssRun* runs_dev, int nruns, int L, int J, const double* part, double* lag, hipStream_t s);
+// G: [clips][M][M], column-major, the lower triangle written
+void launch_bss_gram(const char* kernel, int nruns, int L, int J, const double* lag, double* G, hipStream_t s);
+// G -> its factor in place; sol and filt (the caller's copy, nullable): [clips][M + L] = C, then C0; flag: [clips], 1 = singular
+void launch_bss_chol(const char* kernel, int nruns, int L, int J, const double* lag, double* G, double* sol, double* filt, int* flag,
+                     hipStream_t s);
+// epart: [tiles][6] = the tile's part of E_e, E_tgt, E_int, E_art, E_dist, E_ti
+void launch_bss_project(const char* kernel, const BssRun* runs_dev, int nruns, long long ntiles, int L, int J, const double* sol,
+                        const int* flag, double* epart, hipStream_t s);
+void launch_bss_finish(const char* kernel, const BssRun* runs_dev, int nruns, int L, int J, const int* flag, const double* epart, double* rec,
+                       hipStream_t s);
+
 }  // namespace nhans

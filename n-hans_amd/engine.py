@@ -187,6 +187,25 @@ class Engine(context.Context):
                                             self._stream()))
         return (out, fr) if per_frame else out
 
+    # ---- BSS Eval against target and interferer (include/nhans_hip.h: nhans_bss_eval) ---------------
+    def bss_eval_device(self, est_t, est_off, sources, filt_len=score_mod.BSS_MAX_FILTER, filters=False):
+        """SDR, SIR and SAR of clips already in HBM: estimate i = est_t[est_off[i]:est_off[i + 1]] against sources = [(tensor,
+        offsets)] (the target) or [(target tensor, offsets), (interferer tensor, offsets)], flat float32, over the samples all
+        of them have -> device tensor float64 [n, hip.BSS_FIELDS] (score.BSS_FIELDS names the columns); filters=True: -> (that,
+        float64 [n, (J + 1) filt_len]: C, source 0's taps first, then C0)."""
+        n, J, L = len(est_off) - 1, len(sources), int(filt_len)
+        if J not in (1, 2) or any(len(off) - 1 != n for _, off in sources):
+            raise ValueError("bss_eval_device: one or two sources, one clip of each per estimate")
+        for t in [est_t] + [t for t, _ in sources]:
+            if t.dtype != torch.float32 or t.dim() != 1:
+                raise ValueError("bss_eval_device: flat float32 tensors")
+        ten = [est_t.contiguous()] + [t.contiguous() for t, _ in sources]
+        out = torch.empty((n, hip.BSS_FIELDS), dtype=torch.float64, device=self.device)
+        filt = torch.empty((n, (J + 1) * L), dtype=torch.float64, device=self.device) if filters else None
+        hip.check(context.bss_call(self.lib, self.handle, hip.ptr(ten[0]), [int(v) for v in est_off], [hip.ptr(t) for t in ten[1:]],
+                                   [[int(v) for v in off] for _, off in sources], n, L, hip.ptr(out), hip.ptr(filt), self._stream()))
+        return (out, filt) if filters else out
+
     # ---- STOI and extended STOI against a clean target (include/nhans_hip.h: nhans_stoi) -----------
     def stoi_device(self, est_t, est_off, tgt_t, tgt_off, rate=16000, per_segment=False):
         """STOI figures of clips already in HBM: estimate i = est_t[est_off[i]:est_off[i + 1]] against target i of tgt_t /

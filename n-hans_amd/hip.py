@@ -130,6 +130,8 @@ SIGNATURES = {
     "nhans_stoi_out_count": (_i64, [_i64]),
     "nhans_stoi_resample": (_int, [_vp, _vp, _i64p, _int, _vp, _i64p, _vp]),
     "nhans_stoi": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _vp, _vp, _vp]),
+    # BSS Eval against target and interferer (the two tables are host arrays: of device pointers, of host offset arrays)
+    "nhans_bss_eval": (_int, [_vp, _vp, _i64p, _vpp, ctypes.POINTER(_i64p), _int, _int, _int, _vp, _vp, _vp]),
     "nhans_profile_json": (_int, [_vp, _str, _size]),
     "nhans_profile_reset": (_int, [_vp]),
 }
@@ -154,6 +156,9 @@ SCORE_FIELDS, SCORE_ROW_FIELDS = 16, 8
 SCORE_TILE = 2560                           # samples per workgroup of score.hip (kScoreTile)
 MIX_FIELDS = 8
 STOI_FIELDS = 8
+BSS_FIELDS = 16
+BSS_MAX_FILTER = 512
+BSS_CORR_TILE = 2048                        # samples per workgroup of bsseval.hip's correlation launch (kBssCorrTile)
 MIX_TILE = 2048                             # samples per workgroup and per staging buffer of mix.hip (kMixTile)
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25

@@ -5,8 +5,9 @@ The device computes the figures (score.hip) -- Context.score / Engine.score_devi
 holds their names, the improvement of one record over another, and the float64 numpy DEFINITION the tests and the
 documents measure the device against: `reference` and `reference_rows` form every sum with math.fsum, which is exact, so
 the only roundings in them are the ones the definition names.  STOI and extended STOI (stoi.hip: Context.stoi /
-Engine.stoi_device) have theirs in `stoi_reference`, built from the steps below it.  No torch
-here: the command line imports this."""
+Engine.stoi_device) have theirs in `stoi_reference`, built from the steps below it, and BSS
+Eval's SDR, SIR and SAR (bsseval.hip: Context.bss_eval / Engine.bss_eval_device) in
+`bss_reference`.  No torch here: the command line imports this."""
 import math
 
 import numpy as np
@@ -28,7 +29,12 @@ STOI_RATE, STOI_FRAME, STOI_HOP, STOI_FFT, STOI_SEGMENT = 10000, 256, 128, 512, 
 STOI_EPS = 2.0 ** -52
 STOI_CLIP = 1.0 + 10.0 ** (15.0 / 20.0)
 STOI_RANGE = 1e-4                                           # 40 dB
-_INTS = ("n", "frames", "frames_counted", "frames_skipped", "frames_kept", "segments", "stoi_n", "stoi_frames")
+BSS_FIELDS = ("n", "J", "L", "E_e", "E_tgt", "E_int", "E_art", "E_dist", "E_ti", "sdr_db", "sir_db", "sar_db",
+              "singular")                                   # the first thirteen of NHANS_BSS_FIELDS doubles
+BSS_ENERGIES, BSS_FIGURES = BSS_FIELDS[3:9], BSS_FIELDS[9:12]
+BSS_MAX_FILTER = 512
+_INTS = ("n", "frames", "frames_counted", "frames_skipped", "frames_kept", "segments", "stoi_n", "stoi_frames", "J", "L", "singular",
+         "bss_n")
 
 
 def record(values):
@@ -52,12 +58,27 @@ def merge_stoi(rec, stoi_rec):
     return dict(rec, **{("stoi_" + k if k in rec else k): v for k, v in stoi_rec.items()})
 
 
+def bss_record(values):
+    """NHANS_BSS_FIELDS doubles of one clip -> dict by name."""
+    return {k: (int(values[i]) if k in _INTS else float(values[i])) for i, k in enumerate(BSS_FIELDS)}
+
+
+def merge_bss(rec, bss_rec):
+    """A score record with the BSS Eval figures of the same estimate merged in; a name the record already has (n) is
+    prefixed: bss_n."""
+    return dict(rec, **{("bss_" + k if k in rec else k): v for k, v in bss_rec.items()})
+
+
 def improvement(before, after):
     """What `after` gains over `before`, both scored against the same target: the dB differences and the ratio of the
-    losses (below one is better); where both carry STOI figures, their differences stoi_i and estoi_i too."""
+    losses (below one is better); where both carry STOI figures, their differences stoi_i and estoi_i too; where both
+    carry BSS Eval figures, sdr_i, sir_i and sar_i."""
     out = {k[:-3] + "_i": after[k] - before[k] for k in ("si_sdr_db", "snr_db", "segsnr_db") if k in after and k in before}
     if "stoi" in after and "stoi" in before:
         out.update(stoi_i=after["stoi"] - before["stoi"], estoi_i=after["estoi"] - before["estoi"])
+    if all(k in after and k in before for k in BSS_FIGURES):
+        with np.errstate(invalid="ignore"):
+            out.update({k[:-3] + "_i": float(np.float64(after[k]) - np.float64(before[k])) for k in BSS_FIGURES})
     if "loss" in after and "loss" in before:
         with np.errstate(divide="ignore", invalid="ignore"):
             out["loss_ratio"] = float(np.float64(after["loss"]) / np.float64(before["loss"]))
@@ -292,4 +313,103 @@ def stoi_reference(e10, t10, per_segment=False):
            "stoi": _fsum(per[:, 0]) / S if S else float("nan"), "estoi": _fsum(per[:, 1]) / S if S else float("nan")}
     if per_segment:
         out["per_segment"] = per
+    return out
+
+
+# ---- BSS Eval: the float64 definition (include/nhans_hip.h: nhans_bss_eval) --------------------------
+def _lag_sum(a, b, d):
+    """sum_t a[t] b[t + d], exactly rounded (the products of float32 values are exact in double)"""
+    n = len(a)
+    if d >= 0:
+        return _fsum((a[:n - d] * b[d:]).tolist()) if d < n else 0.0
+    return _fsum((a[-d:] * b[:n + d]).tolist()) if -d < n else 0.0
+
+
+def bss_correlations(e, sources, L):
+    """float64 arrays of float32 values, all n long -> (r, q): r[j][k] = float64 [2 L - 1], r_jk[d] at index d + L - 1;
+    q[k] = float64 [L]"""
+    J = len(sources)
+    r = [[None] * J for _ in range(J)]
+    for j in range(J):
+        pos = np.array([_lag_sum(sources[j], sources[j], d) for d in range(L)])
+        r[j][j] = np.concatenate([pos[:0:-1], pos])
+        for k in range(j + 1, J):
+            r[j][k] = np.array([_lag_sum(sources[j], sources[k], d) for d in range(-(L - 1), L)])
+            r[k][j] = r[j][k][::-1].copy()
+    q = [np.array([_lag_sum(s, e, b) for b in range(L)]) for s in sources]
+    return r, q
+
+
+def bss_gram(r, q, L):
+    """-> (G [J L, J L], D [J L]): G[(j,a),(k,b)] = r_jk[a - b], D[(k,b)] = q_k[b]"""
+    J = len(q)
+    idx = np.arange(L)[:, None] - np.arange(L)[None, :] + (L - 1)
+    G = np.block([[r[j][k][idx] for k in range(J)] for j in range(J)])
+    return G, np.concatenate(q)
+
+
+def bss_pivot_margin(G, R):
+    """The least ratio of a pivot R_kk^2 of the lower factor R to the singular threshold J L 2^-52 G_kk (0 where a pivot is
+    not finite or G_kk is 0)."""
+    with np.errstate(all="ignore"):
+        piv, thr = np.diag(R) ** 2, len(G) * 2.0 ** -52 * np.diag(G)
+        m = np.where(np.isfinite(piv) & (thr > 0), piv / thr, 0.0)
+    return float(m.min()) if len(m) else 0.0
+
+
+def bss_solve(G, D, L):
+    """-> (C, C0, pivot margin), or None where the clip is singular by the header's pivot rule"""
+    from scipy.linalg import cho_factor, cho_solve
+    try:
+        with np.errstate(all="ignore"):
+            R = np.tril(cho_factor(G, lower=True, check_finite=False)[0])
+    except (np.linalg.LinAlgError, ValueError):
+        return None
+    margin = bss_pivot_margin(G, R)
+    if not margin > 1.0:
+        return None
+    return cho_solve((R, True), D, check_finite=False), cho_solve((R[:L, :L], True), D[:L], check_finite=False), margin
+
+
+def bss_project(C, C0, sources, L):
+    """-> (P, s_target), float64 [n + L - 1]"""
+    P = np.zeros(len(sources[0]) + L - 1)
+    for k, s in enumerate(sources):
+        P = P + np.convolve(C[k * L:(k + 1) * L], s)
+    return P, np.convolve(C0, sources[0])
+
+
+def bss_figures(e, P, st, L):
+    """the energies and figures of the record from the projections"""
+    ep = np.concatenate([e, np.zeros(L - 1)])
+    ei, ea = P - st, ep - P
+    sq = lambda v: _fsum((v * v).tolist())
+    out = {"E_e": sq(ep), "E_tgt": sq(st), "E_int": sq(ei), "E_art": sq(ea), "E_dist": sq(ep - st), "E_ti": sq(st + ei)}
+    out.update(sdr_db=_db(_div(out["E_tgt"], out["E_dist"])), sir_db=_db(_div(out["E_tgt"], out["E_int"])),
+               sar_db=_db(_div(out["E_ti"], out["E_art"])))
+    return out
+
+
+def bss_reference(e, sources, filt_len=BSS_MAX_FILTER, filters=False):
+    """SDR, SIR and SAR of estimate e against sources = [target] or [target, interferer] (float32 values; every signal cut
+    to the common length) with filters of filt_len taps, as the header defines them -> dict by BSS_FIELDS (filters=True:
+    plus "C", float64 [J, L], "C0", float64 [L], "G", "D" and "pivot_margin": the least ratio of a pivot to the singular
+    threshold).  The correlations are exactly rounded (math.fsum), the solve is scipy's Cholesky, the projections
+    np.convolve.  A singular clip (a clip of no samples is one): NaN for every energy and figure, singular = 1."""
+    L, J = int(filt_len), len(sources)
+    if J not in (1, 2) or not 1 <= L <= BSS_MAX_FILTER:
+        raise ValueError("bss_reference: one or two sources and a filter of 1 ... %d taps" % BSS_MAX_FILTER)
+    n = min([len(e)] + [len(s) for s in sources])
+    e = np.asarray(e[:n], dtype=np.float32).astype(np.float64)
+    src = [np.asarray(s[:n], dtype=np.float32).astype(np.float64) for s in sources]
+    out = dict({"n": n, "J": J, "L": L}, **{k: float("nan") for k in BSS_ENERGIES + BSS_FIGURES})
+    out["singular"] = 1
+    G, D = bss_gram(*bss_correlations(e, src, L), L)
+    sol = bss_solve(G, D, L) if n else None
+    if sol is not None:
+        C, C0, margin = sol
+        P, st = bss_project(C, C0, src, L)
+        out.update(bss_figures(e, P, st, L), singular=0)
+    if filters:
+        out.update(G=G, D=D, C=C.reshape(J, L) if sol else None, C0=C0 if sol else None, pivot_margin=margin if sol else 0.0)
     return out
