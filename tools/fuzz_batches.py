@@ -1,6 +1,6 @@
 """Randomised batch / chunk / knob invariance screen on the GPU: random ragged batches (1..8 clips of 1..998 frames),
 random frames_per_chunk and contexts_per_chunk, arithmetic mode and conv_variant, and a random setting of every knob that is bit-identical
-by contract (epilogue_wide, consumer_interleave), both models -- every clip's
+by contract (epilogue_wide, consumer_interleave, row_split 0 / 1 / 2), both models -- every clip's
 logits and waveform must equal, bit for bit, the same clip run alone with the default knobs (same arithmetic mode
 and conv_variant), and be finite.  Exercises the tile-boundary handling of every conv kernel at many M that no
 fixed test hits.
@@ -21,8 +21,8 @@ def main():
     iters = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
     bad = 0
-    knobs = ("epilogue_wide", "consumer_interleave")     # bit-identical by contract
-    defaults = {"epilogue_wide": 1, "consumer_interleave": 1}
+    knobs = ("epilogue_wide", "consumer_interleave", "row_split")     # bit-identical by contract
+    defaults = {"epilogue_wide": 1, "consumer_interleave": 1, "row_split": 1}
     for kind in ("denoiser", "separator"):
         eng = engine.Engine(kind, precision="f16x3")
         variants = [-1, -1, 0, 1, 2]
@@ -57,7 +57,7 @@ def main():
             wino = int(rng.random() < 0.7)               # Winograd form of the 4x4 stack convs (another summation: part of the key)
             refs = [reference(prec, variant, wino, i) for i in ids]
             fpc = int(rng.choice([1, 7, 33, 100, 257, 1024, 3776]))
-            cfg = {k: int(rng.integers(0, 3 if k == "consumer_interleave" else 2)) for k in knobs}
+            cfg = {k: int(rng.integers(0, 2 if k == "epilogue_wide" else 3)) for k in knobs}
             cfg["contexts_per_chunk"] = int(rng.choice([1, 3, 5, 64]))      # tower passes with a remainder chunk
             eng.set_precision(prec)
             eng.set_option("conv_variant", variant)
