@@ -1042,6 +1042,56 @@ int nhans_bss_eval(nhans_ctx* ctx, const float* est_dev, const int64_t* est_offs
                    const int64_t* const* src_offsets_host, int nsrc, int nclips, int filt_len, double* out_dev,
                    double* filters_out_dev, void* stream);
 
+/* ---- Delay estimation: scoring signals that are not aligned -----------------------------------------------------------------
+ * Every scoring call above pairs sample u of the estimate with sample u of the target.  Where the target comes from outside
+ * -- another microphone, a loop-back capture, another front end with a delay of its own -- the pair is aligned first, where
+ * the signals are (n-hans_amd/csrc/align.hip).  Added without moving NHANS_ABI_VERSION; a caller that
+ * may meet an older library looks the functions up by symbol.  Inputs per clip are an estimate e of ne samples and a target
+ * t of nt samples, both float32 and finite, and one max_lag = D per call, 0 <= D <= 16000 (one second at 16 kHz).  Every
+ * operation is in double.
+ *   correlation   for -D <= d <= D:  c[d] = sum_u e[u + d] t[u] over u in [max(0, -d), min(nt, ne - d)); an empty range gives
+ *                 +0.0.  d > 0 means the estimate is LATE: e[u + d] lines up with t[u].  A product of two float32 values is
+ *                 exact in double; the sum is formed directly, in a fixed order (align.hip states it).
+ *   delay         the d with the largest c[d].  The comparison is signed: an estimate of inverted polarity is not searched
+ *                 for (its largest c[d] is wherever the signals happen to agree best in sign).  Of equal values the one
+ *                 with the smaller |d| wins, and of -d and +d the non-negative one.  All-zero input therefore gives 0.
+ *   confidence    rho = c[delay] / sqrt(See Stt), See = sum e^2 and Stt = sum t^2 over the WHOLE clips, each a fixed-order sum
+ *                 (the product rounded once, then the root, then the quotient).  IEEE applies: 0 / 0 is NaN, and nothing is
+ *                 refused for it.
+ *   common count  n_common = max(0, min(ne - max(delay, 0), nt - max(-delay, 0))): the samples the cut pair has.
+ *   record        NHANS_ALIGN_FIELDS doubles: ne, nt, D, delay, c_peak, rho, n_common, 0
+ * Whole samples only: no sub-sample delay, no polarity search, no clock drift (one delay per clip).  c[d] is a function of
+ * the clip pair and of d alone: it has the same bits for every D >= |d|, alone or in any batch, at any offset of either
+ * buffer, beside any neighbours, on every run -- no floating-point atomics, no reduction whose shape depends on the batch or
+ * on D: the sample tiles are anchored at the target's u = 0 and a clip's tile parts are added in ascending order.  Only
+ * samples inside a clip are ever fetched.  Non-finite samples: unspecified.
+ *
+ * Clip i of the estimates is est_dev[est_offsets_host[i] .. est_offsets_host[i + 1]), of the targets likewise with its own
+ * offsets.  out_dev receives NHANS_ALIGN_FIELDS doubles per clip.  corr_out_dev (nullable) receives the 2 max_lag + 1 values
+ * c[-D] ... c[D] per clip, lag -D first.  The workspace holds nclips (2 max_lag + 1) doubles when corr_out_dev is NULL and
+ * otherwise only a table of the clips.  NHANS_EINVAL, naming the clip, before anything is launched and with nothing written:
+ * nclips < 0, max_lag outside 0 ... 16000, a NULL that is needed, an offset array that descends, a clip of more than
+ * 2^31 - 1 samples.
+ *
+ * nhans_align_common(ne, nt, delay) is n_common (host only).
+ *
+ * nhans_align_cut writes, for clip i with d = delay_host[i], e[max(d, 0) .. + n_common) to est_out_dev and t[max(-d, 0) ..
+ * + n_common) to tgt_out_dev, both from element out_offsets_host[i] on: one launch for the whole call.  The cut pairs are
+ * what the scoring calls above take, with out_offsets_host for both signals.  Either signal may be left out: est_dev and
+ * est_out_dev both NULL, or tgt_dev and tgt_out_dev both NULL -- the offsets of a signal left out still say how long it is.
+ * A further signal that is sample-aligned with the target (the interferer of nhans_bss_eval) is cut by a second call
+ * with that signal in the target's place, the same delays and no estimate.  NHANS_EINVAL, naming the clip, before anything is
+ * launched and with nothing written: nclips < 0, a NULL that is needed (one of a pair alone included), an offset array that
+ * descends, a delay d > ne or -d > nt (more than the clip it shortens), an output room shorter than n_common. */
+#define NHANS_ALIGN_FIELDS 8    /* ne, nt, D, delay, c_peak, rho, n_common, 0 */
+#define NHANS_ALIGN_MAX_LAG 16000
+int nhans_align(nhans_ctx* ctx, const float* est_dev, const int64_t* est_offsets_host, const float* tgt_dev,
+                const int64_t* tgt_offsets_host, int nclips, int max_lag, double* out_dev, double* corr_out_dev, void* stream);
+int64_t nhans_align_common(int64_t ne, int64_t nt, int64_t delay);      /* host only */
+int nhans_align_cut(nhans_ctx* ctx, const float* est_dev, const int64_t* est_offsets_host, const float* tgt_dev,
+                    const int64_t* tgt_offsets_host, int nclips, const int64_t* delay_host, float* est_out_dev, float* tgt_out_dev,
+                    const int64_t* out_offsets_host, void* stream);
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

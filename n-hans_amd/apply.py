@@ -67,6 +67,7 @@ class Flags(object):
     score_out = None     # --score_out PATH.json: where the scores go (stdout otherwise)
     bss = False          # --bss: with --score_against and --interferer, also SDR, SIR and SAR (score.py: bss_reference is the definition)
     interferer = None    # --interferer FILE: the signal that was to be removed, for --bss
+    align_ms = None      # --align_ms MS: with --score_against, the delay of the denoised file against the target is estimated within MS and taken out
     stoi = False         # --stoi: with --score_against, also STOI and extended STOI (score.py: stoi_reference is the definition)
     lookahead_ms = 10 * spec.LOOKAHEAD   # --lookahead_ms: 10 ms per frame of look-ahead (include/nhans_hip.h: "lookahead"), 170 = all 17
 
@@ -847,7 +848,18 @@ def _parse(argv, prog):
                    help='for --bss: the signal that was to be removed -- the noise, or the other speaker; a wav in file mode, a '
                         'directory paired by file name in directory mode.  It needs no peak scaling: the decomposition does not '
                         'change when a source is scaled, or filtered by up to 512 taps')
+    p.add_argument('--align_ms', type=float, default=None, metavar='MS',
+                   help='with --score_against, for a target that is not sample-aligned with the input: the delay of the '
+                        'denoised file against the target is estimated on the device within MS milliseconds either way '
+                        '(0 < MS <= 1000; whole samples, positive: the files are late) and taken out of the denoised file, '
+                        'the mixed round trip and the target (and the --interferer) before they are scored; the scores '
+                        'gain delay_samples and align_rho per file; the audio files are what they are without the flag')
     a = p.parse_args(argv)
+    if a.align_ms is not None:
+        if a.score_against is None:
+            p.error('--align_ms needs --score_against TARGET')
+        if not 0.0 < a.align_ms <= 1000.0:
+            p.error('--align_ms must be in 0 < MS <= 1000; got %g' % a.align_ms)
     if a.bss != (a.interferer is not None):
         p.error('--bss and --interferer FILE go together')
     if a.bss and a.score_against is None:
@@ -965,7 +977,10 @@ def scaled_target(mixedpath, targetpath):
 def _score_jobs(kind, a, jobs):
     """--score_against, after the files are written: per job the 16 kHz denoised file and the mixed round trip, as
     written, against the scaled target over their common prefix, in ONE Context.score call; JSON to --score_out or
-    stdout: {"files": {input path: {"denoised", "mixed", "improvement"}}, "skipped": [...]} and, in directory mode, "mean"."""
+    stdout: {"files": {input path: {"denoised", "mixed", "improvement"}}, "skipped": [...]} and, in directory mode, "mean".
+    --align_ms: one Context.align call first, each denoised file against its target within round(16 MS) samples; a file's
+    delay is taken out of both of its signals alike -- the two are sample-aligned by construction -- and out of the
+    interferer as out of the target, and the file's entry gains "delay_samples" and "align_rho"."""
     import json
     from . import score
     directory = os.path.isdir(a.input)
@@ -983,11 +998,17 @@ def _score_jobs(kind, a, jobs):
             x = _reader()(os.path.join(a.interferer, os.path.basename(mixedpath)) if directory else a.interferer).astype(np.float32)
             interf += [x, x]
         done.append(mixedpath)
-    recs = get_enhancer(kind).score(est, tgt, stoi=getattr(a, "stoi", False), bss=interf if bss else None) if est else []
+    align_ms, found = getattr(a, "align_ms", None), None
+    if align_ms is not None and est:
+        found = get_enhancer(kind).align(est[0::2], tgt[0::2], max_lag=int(round(16 * align_ms)))
+    recs = get_enhancer(kind).score(est, tgt, stoi=getattr(a, "stoi", False), bss=interf if bss else None,
+                                    delays=[r["delay"] for r in found for _ in (0, 1)] if found else None) if est else []
     files = {}
     for i, path in enumerate(done):
         den, mix = recs[2 * i], recs[2 * i + 1]
         files[path] = {"denoised": den, "mixed": mix, "improvement": score.improvement(mix, den)}
+        if found:
+            files[path].update(delay_samples=found[i]["delay"], align_rho=found[i]["rho"])
     out = {"files": files, "skipped": skipped}
     if directory and files:
         out["mean"] = {k: score.mean_of([f[k] for f in files.values()]) for k in ("denoised", "mixed", "improvement")}

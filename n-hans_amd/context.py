@@ -126,7 +126,7 @@ class Context:
 
 
     # ---- scoring against a clean target (include/nhans_hip.h: nhans_score_*) ---------------------
-    def score(self, estimates, targets, per_frame=False, stoi=False, bss=None):
+    def score(self, estimates, targets, per_frame=False, stoi=False, bss=None, align=None, delays=None):
         """Lists of float32 waveforms, estimate i against target i over their common prefix -> one dict per clip: the
         waveform figures (score.FIELDS: si_sdr_db, snr_db, segsnr_db, ...) and the row figures loss and lsd_db of the two
         signals' own log-magnitude rows (nhans_stft_features) -- one upload, two STFTs and the two score calls on the
@@ -135,9 +135,18 @@ class Context:
         the same pairs (16 kHz signals), merged into each record -- a name the record already has (n, frames: there the
         16 kHz samples and the STFT rows) is prefixed: stoi_n, stoi_frames.  bss: a list of interferers (or True: the
         target alone) -- plus the figures of Context.bss_eval of the same estimates (sdr_db, sir_db, sar_db, ...), merged
-        into each record; its n is bss_n."""
+        into each record; its n is bss_n.
+        Signals that are not aligned: align=D estimates one delay per pair within D samples either way (Context.align),
+        delays=[...] applies given integers (positive: the estimate is late); each pair is cut to its common part
+        (score.align_cut; an interferer as its target) and scored as above, and each record gains "delay" and, where the
+        delay was estimated, "align_rho"."""
         if len(estimates) != len(targets):
             raise ValueError("score: one target per estimate")
+        if align is not None or delays is not None:
+            extra = bss if bss is not None and bss is not False and bss is not True else None
+            es, ts, xs, tags = self._aligned("score", estimates, targets, extra, align, delays)
+            recs = self.score(es, ts, per_frame=per_frame, stoi=stoi, bss=xs if extra is not None else bss)
+            return [dict(r, **tag) for r, tag in zip(recs, tags)]
         if bss is not None and bss is not False:
             return [score_mod.merge_bss(r, b)
                     for r, b in zip(self.score(estimates, targets, per_frame=per_frame, stoi=stoi),
@@ -180,15 +189,68 @@ class Context:
             res.append(rec)
         return res
 
+    # ---- delay estimation (include/nhans_hip.h: nhans_align) ---------------------------------------
+    def align(self, estimates, targets, max_lag=8000, corr=False):
+        """Lists of float32 waveforms, estimate i against target i -> one dict per clip by score.ALIGN_FIELDS: delay (the lag
+        within max_lag samples either way at which the cross-correlation is largest; positive: the estimate is late,
+        e[u + delay] lines up with t[u]), rho (that value over the root of the two energies), c_peak, n_common, ne, nt, D.
+        One upload, one call, one download.  corr=True: plus "corr", float64 [2 max_lag + 1], lag -max_lag first."""
+        if len(estimates) != len(targets):
+            raise ValueError("align: one target per estimate")
+        lib, mem, n, D = self.lib, Mem(self), len(estimates), int(max_lag)
+        (ef, eoff), (tf, toff) = flat(estimates), flat(targets)
+        buf = mem.up(np.ascontiguousarray(np.concatenate([ef, tf])))
+        nf, per = hip.ALIGN_FIELDS, (2 * D + 1 if corr else 0)
+        out = mem.empty(n * (nf + per), np.float64)
+        try:
+            hip.check(lib.nhans_align(self.handle, mem.p(buf), hip.i64_array(eoff), ctypes.c_void_p(mem.p(buf).value + 4 * len(ef)),
+                                      hip.i64_array(toff), n, D, mem.p(out),
+                                      ctypes.c_void_p(mem.p(out).value + 8 * n * nf) if corr else None, mem.stream()))
+            self._sync()
+            got = np.array(mem.down(out, n * (nf + per), np.float64), dtype=np.float64)
+        finally:
+            mem.free(buf, out)
+        res = []
+        for i in range(n):
+            rec = score_mod.align_record(got[i * nf:(i + 1) * nf])
+            if corr:
+                rec["corr"] = got[n * nf + i * per:n * nf + (i + 1) * per].copy()
+            res.append(rec)
+        return res
+
+    def _aligned(self, who, estimates, targets, others, align, delays):
+        """The pairs with their delays taken out -> (estimates, targets, others, what each record gains): align=D
+        estimates the delays (Context.align), delays=[...] are given; `others` (None, or one further signal per pair that
+        is sample-aligned with its target) are cut as the targets are."""
+        if align is not None and delays is not None:
+            raise ValueError("%s: align= estimates the delays and delays= gives them: not both" % who)
+        if others is not None and len(others) != len(estimates):
+            raise ValueError("%s: one interferer per estimate" % who)
+        if align is not None:
+            recs = self.align(estimates, targets, max_lag=align)
+            tags = [{"delay": r["delay"], "align_rho": r["rho"]} for r in recs]
+        else:
+            if len(delays) != len(estimates):
+                raise ValueError("%s: one delay per estimate" % who)
+            tags = [{"delay": int(d)} for d in delays]
+        pairs = [score_mod.align_cut(e, t, tag["delay"]) for e, t, tag in zip(estimates, targets, tags)]
+        xs = None if others is None else [score_mod.align_cut(e, x, tag["delay"])[1] for e, x, tag in zip(estimates, others, tags)]
+        return [p[0] for p in pairs], [p[1] for p in pairs], xs, tags
+
     # ---- STOI and extended STOI against a clean target (include/nhans_hip.h: nhans_stoi) ----------
-    def stoi(self, estimates, targets, rate=16000, per_segment=False):
+    def stoi(self, estimates, targets, rate=16000, per_segment=False, delays=None):
         """Lists of float32 waveforms at `rate` (16000: the network's, converted to 10 kHz on the device by
         nhans_stoi_resample; 10000: scored as they are), estimate i against target i -> one dict per clip by
         score.STOI_FIELDS: n (common samples at 10 kHz), frames, frames_kept, segments, stoi, estoi -- NaN for both figures
         where there is no segment.  One upload, the conversion, the score and one download of the records.
-        per_segment=True: plus "per_segment", float64 [segments, 2] = each segment's d_s and e_s."""
+        per_segment=True: plus "per_segment", float64 [segments, 2] = each segment's d_s and e_s.  delays=[...]: each pair
+        is first cut to its common part with the estimate's delay (samples at `rate`, positive: late) taken out, and each
+        record gains "delay"."""
         if len(estimates) != len(targets):
             raise ValueError("stoi: one target per estimate")
+        if delays is not None:
+            es, ts, _, tags = self._aligned("stoi", estimates, targets, None, None, delays)
+            return [dict(r, **tag) for r, tag in zip(self.stoi(es, ts, rate=rate, per_segment=per_segment), tags)]
         if rate not in (16000, score_mod.STOI_RATE):
             raise ValueError("stoi: signals at 16000 or %d Hz, not %r" % (score_mod.STOI_RATE, rate))
         lib, mem, n = self.lib, Mem(self), len(estimates)
@@ -230,14 +292,19 @@ class Context:
         return res
 
     # ---- BSS Eval against target and interferer (include/nhans_hip.h: nhans_bss_eval) -------------
-    def bss_eval(self, estimates, targets, interferers=None, filt_len=score_mod.BSS_MAX_FILTER, filters=False):
+    def bss_eval(self, estimates, targets, interferers=None, filt_len=score_mod.BSS_MAX_FILTER, filters=False, delays=None):
         """Lists of float32 waveforms, estimate i against target i and (interferers given) interferer i over the samples
         all of them have -> one dict per clip by score.BSS_FIELDS: sdr_db, sir_db, sar_db, the six energies, n, J, L and
         singular (1: the Gram matrix failed the pivot rule -- an all-zero source, say -- and every figure is NaN).  One
-        upload, one call, one download.  filters=True: plus "C", float64 [J, filt_len], and "C0", float64 [filt_len]."""
+        upload, one call, one download.  filters=True: plus "C", float64 [J, filt_len], and "C0", float64 [filt_len].
+        delays=[...]: each tuple is first cut to its common part with the estimate's delay (positive: late) taken out --
+        the interferer as its target -- and each record gains "delay"."""
         src = [targets] if interferers is None else [targets, interferers]
         if any(len(s) != len(estimates) for s in src):
             raise ValueError("bss_eval: one target%s per estimate" % ("" if interferers is None else " and one interferer"))
+        if delays is not None:
+            es, ts, xs, tags = self._aligned("bss_eval", estimates, targets, interferers, None, delays)
+            return [dict(r, **tag) for r, tag in zip(self.bss_eval(es, ts, xs, filt_len=filt_len, filters=filters), tags)]
         lib, mem, n, J, L = self.lib, Mem(self), len(estimates), len(src), int(filt_len)
         flats = [flat(x) for x in [estimates] + src]
         base = offsets(len(f) for f, _ in flats)

@@ -552,4 +552,27 @@ void launch_bss_project(const char* kernel, const BssRun* runs_dev, int nruns, l
 void launch_bss_finish(const char* kernel, const BssRun* runs_dev, int nruns, int L, int J, const int* flag, const double* epart, double* rec,
                        hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// Delay estimation (align.hip; include/nhans_hip.h: nhans_align, nhans_align_cut).  One AlignRun per clip pair, empty ones
+// included: ne samples at est, nt at tgt (a pointer is nullptr where its count is 0).  D = max_lag is the call's; a clip's
+// lag vector is 2 D + 1 doubles, lag -D first.  align_corr: one workgroup per (clip, block of kAlignLagBlock lags), sample
+// tiles of kAlignTile anchored at the target's first sample.  One AlignCopy per non-empty piece of the ragged copy: n > 0
+// samples from src to dst, workgroups [tile0, tile0 + ceil(n / kAlignCutTile)), tile0 ascending strictly from 0.
+struct AlignRun {
+    const float* est;
+    const float* tgt;
+    long long ne, nt;
+};
+struct AlignCopy {
+    const float* src;
+    float* dst;
+    long long n, tile0;
+};
+constexpr int kAlignFields = 8, kAlignMaxLag = 16000, kAlignTile = 2048, kAlignLagBlock = 2048, kAlignCutTile = 4096;
+// corr: [clips][2 D + 1]
+void launch_align_corr(const char* kernel, const AlignRun* runs_dev, int nruns, int D, double* corr, hipStream_t s);
+// rec: [clips][kAlignFields]
+void launch_align_pick(const char* kernel, const AlignRun* runs_dev, int nruns, int D, const double* corr, double* rec, hipStream_t s);
+void launch_align_cut(const char* kernel, const AlignCopy* jobs_dev, int njobs, long long ntiles, hipStream_t s);
+
 }  // namespace nhans

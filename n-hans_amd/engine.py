@@ -187,6 +187,46 @@ class Engine(context.Context):
                                             self._stream()))
         return (out, fr) if per_frame else out
 
+    # ---- delay estimation (include/nhans_hip.h: nhans_align, nhans_align_cut) ------------------------
+    def align_device(self, est_t, est_off, tgt_t, tgt_off, max_lag=8000, corr=False):
+        """Delays of clips already in HBM: estimate i = est_t[est_off[i]:est_off[i + 1]] against target i of tgt_t / tgt_off,
+        flat float32, within max_lag samples either way -> device tensor float64 [n, hip.ALIGN_FIELDS] (score.ALIGN_FIELDS
+        names the columns; delay > 0: the estimate is late); corr=True: -> (that, float64 [n, 2 max_lag + 1]: the
+        cross-correlation, lag -max_lag first)."""
+        n, D = len(est_off) - 1, int(max_lag)
+        if len(tgt_off) - 1 != n:
+            raise ValueError("align_device: one target per estimate")
+        for t in (est_t, tgt_t):
+            if t.dtype != torch.float32 or t.dim() != 1:
+                raise ValueError("align_device: flat float32 tensors")
+        if not 0 <= D <= hip.ALIGN_MAX_LAG:
+            raise ValueError("align_device: max_lag 0 ... %d, not %r" % (hip.ALIGN_MAX_LAG, max_lag))
+        out = torch.empty((n, hip.ALIGN_FIELDS), dtype=torch.float64, device=self.device)
+        c = torch.empty((n, 2 * D + 1), dtype=torch.float64, device=self.device) if corr else None
+        hip.check(self.lib.nhans_align(self.handle, hip.ptr(est_t.contiguous()), hip.i64_array(est_off), hip.ptr(tgt_t.contiguous()),
+                                       hip.i64_array(tgt_off), n, D, hip.ptr(out), hip.ptr(c), self._stream()))
+        return (out, c) if corr else out
+
+    def align_cut_device(self, est_t, est_off, tgt_t, tgt_off, delays):
+        """The pairs of align_device with their delays (host integers: column 3 of its records) taken out, in one launch ->
+        (estimates, targets, offsets): two flat float32 device tensors in which pair i is [offsets[i], offsets[i + 1]), its
+        n_common samples, for the scoring calls.  est_t or tgt_t may be None (its offsets still say how long its clips
+        are): that signal is not cut and comes back as None -- a further signal that is sample-aligned with the target
+        is cut by passing it as tgt_t with est_t=None."""
+        n = len(est_off) - 1
+        if len(tgt_off) - 1 != n or len(delays) != n:
+            raise ValueError("align_cut_device: one target and one delay per estimate")
+        for t in (est_t, tgt_t):
+            if t is not None and (t.dtype != torch.float32 or t.dim() != 1):
+                raise ValueError("align_cut_device: flat float32 tensors")
+        d = [int(v) for v in delays]
+        off = context.offsets(int(self.lib.nhans_align_common(est_off[i + 1] - est_off[i], tgt_off[i + 1] - tgt_off[i], d[i])) for i in range(n))
+        ins = [None if t is None else t.contiguous() for t in (est_t, tgt_t)]
+        outs = [None if t is None else torch.empty(max(off[-1], 1), dtype=torch.float32, device=self.device) for t in ins]
+        hip.check(self.lib.nhans_align_cut(self.handle, hip.ptr(ins[0]), hip.i64_array(est_off), hip.ptr(ins[1]), hip.i64_array(tgt_off), n,
+                                           hip.i64_array(d), hip.ptr(outs[0]), hip.ptr(outs[1]), hip.i64_array(off), self._stream()))
+        return tuple(None if o is None else o[:off[-1]] for o in outs) + (off,)
+
     # ---- BSS Eval against target and interferer (include/nhans_hip.h: nhans_bss_eval) ---------------
     def bss_eval_device(self, est_t, est_off, sources, filt_len=score_mod.BSS_MAX_FILTER, filters=False):
         """SDR, SIR and SAR of clips already in HBM: estimate i = est_t[est_off[i]:est_off[i + 1]] against sources = [(tensor,

@@ -132,6 +132,10 @@ SIGNATURES = {
     "nhans_stoi": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _vp, _vp, _vp]),
     # BSS Eval against target and interferer (the two tables are host arrays: of device pointers, of host offset arrays)
     "nhans_bss_eval": (_int, [_vp, _vp, _i64p, _vpp, ctypes.POINTER(_i64p), _int, _int, _int, _vp, _vp, _vp]),
+    # delay estimation and the cut to the common part
+    "nhans_align": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _int, _vp, _vp, _vp]),
+    "nhans_align_common": (_i64, [_i64, _i64, _i64]),
+    "nhans_align_cut": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _i64p, _vp, _vp, _i64p, _vp]),
     "nhans_profile_json": (_int, [_vp, _str, _size]),
     "nhans_profile_reset": (_int, [_vp]),
 }
@@ -159,6 +163,9 @@ STOI_FIELDS = 8
 BSS_FIELDS = 16
 BSS_MAX_FILTER = 512
 BSS_CORR_TILE = 2048                        # samples per workgroup of bsseval.hip's correlation launch (kBssCorrTile)
+ALIGN_FIELDS = 8
+ALIGN_MAX_LAG = 16000
+ALIGN_TILE, ALIGN_LAG_BLOCK = 2048, 2048    # samples per tile and lags per workgroup of align.hip (kAlignTile, kAlignLagBlock)
 MIX_TILE = 2048                             # samples per workgroup and per staging buffer of mix.hip (kMixTile)
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25

@@ -7,7 +7,8 @@ documents measure the device against: `reference` and `reference_rows` form ever
 the only roundings in them are the ones the definition names.  STOI and extended STOI (stoi.hip: Context.stoi /
 Engine.stoi_device) have theirs in `stoi_reference`, built from the steps below it, and BSS
 Eval's SDR, SIR and SAR (bsseval.hip: Context.bss_eval / Engine.bss_eval_device) in
-`bss_reference`.  No torch here: the command line imports this."""
+`bss_reference`.  Delay estimation for signals that are not aligned (align.hip: Context.align, Context.score(align=...);
+DESIGN.md section 1.13) has its definition in `align_reference`.  No torch here: the command line imports this."""
 import math
 
 import numpy as np
@@ -33,8 +34,10 @@ BSS_FIELDS = ("n", "J", "L", "E_e", "E_tgt", "E_int", "E_art", "E_dist", "E_ti",
               "singular")                                   # the first thirteen of NHANS_BSS_FIELDS doubles
 BSS_ENERGIES, BSS_FIGURES = BSS_FIELDS[3:9], BSS_FIELDS[9:12]
 BSS_MAX_FILTER = 512
+ALIGN_FIELDS = ("ne", "nt", "D", "delay", "c_peak", "rho", "n_common")        # the first seven of NHANS_ALIGN_FIELDS doubles
+ALIGN_MAX_LAG = 16000
 _INTS = ("n", "frames", "frames_counted", "frames_skipped", "frames_kept", "segments", "stoi_n", "stoi_frames", "J", "L", "singular",
-         "bss_n")
+         "bss_n", "ne", "nt", "D", "delay", "n_common")
 
 
 def record(values):
@@ -67,6 +70,11 @@ def merge_bss(rec, bss_rec):
     """A score record with the BSS Eval figures of the same estimate merged in; a name the record already has (n) is
     prefixed: bss_n."""
     return dict(rec, **{("bss_" + k if k in rec else k): v for k, v in bss_rec.items()})
+
+
+def align_record(values):
+    """NHANS_ALIGN_FIELDS doubles of one clip -> dict by name."""
+    return {k: (int(values[i]) if k in _INTS else float(values[i])) for i, k in enumerate(ALIGN_FIELDS)}
 
 
 def improvement(before, after):
@@ -413,3 +421,59 @@ def bss_reference(e, sources, filt_len=BSS_MAX_FILTER, filters=False):
     if filters:
         out.update(G=G, D=D, C=C.reshape(J, L) if sol else None, C0=C0 if sol else None, pivot_margin=margin if sol else 0.0)
     return out
+
+
+# ---- delay estimation: the float64 definition (include/nhans_hip.h: nhans_align) -----------------------
+def align_common(ne, nt, delay):
+    """The samples a pair of ne and nt samples has in common once the estimate is taken to be `delay` samples late."""
+    return max(0, min(ne - max(delay, 0), nt - max(-delay, 0)))
+
+
+def align_lag_sum(e, t, d):
+    """c[d] = sum_u e[u + d] t[u] over u in [max(0, -d), min(nt, ne - d)), exactly rounded (float64 arrays of float32
+    values: the products are exact); an empty range gives +0.0"""
+    lo, hi = max(0, -d), min(len(t), len(e) - d)
+    return _fsum((e[lo + d:hi + d] * t[lo:hi]).tolist()) if hi > lo else 0.0
+
+
+def align_pick(c, max_lag):
+    """The lag of the largest of c[-D] ... c[D] (lag -D first): of equal values the smaller |d|, of -d and +d the
+    non-negative one."""
+    D = int(max_lag)
+    best = 0
+    for d in sorted(range(-D, D + 1), key=lambda d: (abs(d), -d)):      # 0, +1, -1, +2, -2, ...: the first of equals stays
+        if c[d + D] > c[best + D]:
+            best = d
+    return best
+
+
+def align_reference(e, t, max_lag, corr=False):
+    """The delay of estimate e against target t (float32 values) within max_lag samples either way, as the header defines
+    it -> dict by ALIGN_FIELDS: delay > 0 means the estimate is late, e[u + delay] lines up with t[u].  Every sum is exactly
+    rounded (math.fsum of the exact products).  corr=True: plus "corr", float64 [2 max_lag + 1], lag -max_lag first."""
+    D = int(max_lag)
+    if not 0 <= D <= ALIGN_MAX_LAG:
+        raise ValueError("align_reference: max_lag 0 ... %d" % ALIGN_MAX_LAG)
+    e = np.asarray(e, dtype=np.float32).astype(np.float64)
+    t = np.asarray(t, dtype=np.float32).astype(np.float64)
+    c = np.array([align_lag_sum(e, t, d) for d in range(-D, D + 1)])
+    delay = align_pick(c, D)
+    See, Stt = _fsum((e * e).tolist()), _fsum((t * t).tolist())
+    with np.errstate(all="ignore"):
+        rho = float(np.float64(c[delay + D]) / np.sqrt(np.float64(See) * np.float64(Stt)))
+    out = {"ne": len(e), "nt": len(t), "D": D, "delay": delay, "c_peak": float(c[delay + D]), "rho": rho,
+           "n_common": align_common(len(e), len(t), delay)}
+    if corr:
+        out["corr"] = c
+    return out
+
+
+def align_cut(e, t, delay):
+    """-> (e[max(delay, 0):][:n], t[max(-delay, 0):][:n]), n the common count: the pair with the estimate's delay taken out.
+    A delay of more than the clip it shortens is an error, as the library has it."""
+    d = int(delay)
+    if d > len(e) or -d > len(t):
+        raise ValueError("align_cut: delay %d is more than the %d samples of the %s it shortens"
+                         % (d, len(e) if d > 0 else len(t), "estimate" if d > 0 else "target"))
+    n = align_common(len(e), len(t), d)
+    return e[max(d, 0):max(d, 0) + n], t[max(-d, 0):max(-d, 0) + n]
