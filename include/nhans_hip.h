@@ -1092,6 +1092,82 @@ int nhans_align_cut(nhans_ctx* ctx, const float* est_dev, const int64_t* est_off
                     const int64_t* tgt_offsets_host, int nclips, const int64_t* delay_host, float* est_out_dev, float* tgt_out_dev,
                     const int64_t* out_offsets_host, void* stream);
 
+/* ---- LLR, cepstral distance and frequency-weighted segmental SNR against a clean target --------------------------------------
+ * How much an enhancement distorted the speech itself: three figures of the objective-measure set of Hu & Loizou (2008;
+ * Quackenbush et al. 1988), computed where the signals are (n-hans_amd/csrc/quality.hip).  Added
+ * without moving NHANS_ABI_VERSION; a caller that may meet an older library looks the functions up by symbol.  e is the
+ * estimate and t the target, both float32 at 16 kHz, scored over the common prefix n = min(ne, nt) and converted to double
+ * once.  Every operation below is in double and is one IEEE operation rounded to nearest: x * y, x + y, x - y, x / y,
+ * fma(x, y, z) = x y + z rounded once, sqrt.  Nothing is left to contraction.  "chain over i" means acc = +0.0, then one
+ * operation per i, ascending.
+ *   framing   N = 480, hop 120; M = 0 for n < 480, else (n - 480) / 120 + 1 (integer division); frame f is samples
+ *             [120 f, 120 f + 480).  w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / 481), computed on the host in double
+ *             (nhans_quality_tables returns the very table).  xw[i] = x[120 f + i] * w[i].
+ *   LPC       order P = 16, per frame and signal.  r[k], k = 0 ... 16: the chain over i = 0 ... 479 - k of
+ *             acc = fma(xw[i], xw[i + k], acc).  Levinson-Durbin: E = r[0], a[0] = 1; for m = 1 ... 16:
+ *                 acc = r[m]; for j = 1 ... m - 1 ascending: acc = fma(a[j], r[m - j], acc);   k_m = -(acc / E);
+ *                 for j = 1 ... m - 1: a'[j] = fma(k_m, a[m - j], a[j]);   then a[j] = a'[j], a[m] = k_m;
+ *                 E = E * fma(-k_m, k_m, 1)          (this is E_m)
+ *   LLR       q(a) = the chain over i = 0 ... 16 of acc = fma(a[i], row_i, acc), row_i the chain over j = 0 ... 16 of
+ *             acc = fma(r_t[|i - j|], a[j], acc): always on the TARGET's autocorrelation.  num = q(a_e), den = q(a_t),
+ *             llr_f = min(max(ln(num / den), 0), 2).
+ *   CD        c[m], m = 1 ... 16: s = the chain over k = 1 ... m - 1 of acc = fma(((double)k / (double)m) * c[k], a[m - k], acc);
+ *             c[m] = (-a[m]) - s.  dc2 = the chain over m = 1 ... 16 of acc = fma(d, d, acc), d = c_t[m] - c_e[m].
+ *             cd_f = min(max((10 / ln 10) * sqrt(2 * dc2), 0), 10), 10 / ln 10 = 4.342944819032518.
+ *   skipped   a frame has no LLR and no CD (its values are NaN; it is counted out of frames_lpc) where r_t[0] == 0 or
+ *             r_e[0] == 0, an E_m of either recursion is not a positive finite number (the recursion stops there), or den
+ *             or num is not a positive finite number.
+ *   fwSegSNR  each windowed frame is zero-padded to 512 and transformed by the radix-8 transform of
+ *             n-hans_amd/csrc/stoi_fft.h (one transform per signal: an all-zero frame has an all-zero spectrum, exactly);
+ *             |X_k| of the target's and |Y_k| of the estimate's, k = 0 ... 256, |u| = sqrt(fma(u_i, u_i, u_r * u_r)).  Band matrix W:
+ *             [K][257], K <= 32, non-negative; the default has K = 25 triangles on the HTK mel scale between 0 and 8000 Hz
+ *             over the bin frequencies 31.25 k (the construction of nhans_fbank_design on 257 bins; nhans_quality_tables
+ *             returns it).  X_j = the chain over k = 0 ... 256 of acc = fma(W[j][k], |X_k|, acc); Y_j likewise.
+ *             s_j = 35 where X_j == Y_j, else min(max(10 * log10((X_j * X_j) / ((X_j - Y_j) * (X_j - Y_j))), -10), 35);
+ *             g_j = pow(X_j, 0.2); G = the chain over j of acc = acc + g_j, D = the chain over j of acc = fma(g_j, 35 - s_j, acc);
+ *             fw_f = 35 - D / G: the weighted mean sum_j g_j s_j / sum_j g_j, formed from the bands' deficits so that equal
+ *             signals give 35 exactly.  A frame with G == 0 is skipped (NaN; counted out of frames_fw).
+ *   figures   llr, cd_db, fwsegsnr_db: the chain acc = acc + v_f over the kept frames, f ascending, divided by their count.
+ *             llr_95, cd_95_db: the mean of the q = (19 Mk + 10) / 20 (integer division) smallest of the Mk kept values --
+ *             the published practice of dropping the worst 5 % of the frames.  The q-th smallest value v is found exactly
+ *             (a radix select on the bit patterns, which order as the non-negative values do; no sort); the figure is
+ *             (b + (double)(q - nb) * v) / (double)q, b the chain acc = acc + v_f over the nb kept frames with v_f < v, f
+ *             ascending.  No kept frame: NaN, the counts filled in (the convention of nhans_stoi).  ln, log10 and pow are
+ *             the device library's (a few units in the last place); non-finite samples: unspecified.
+ *   record    NHANS_QUALITY_FIELDS doubles: n, frames (M), frames_lpc, frames_fw, llr, llr_95, cd_db, cd_95_db,
+ *             fwsegsnr_db, then zeros.  Lower is better for LLR and CD, higher for fwSegSNR.
+ * The band table is this library's own.  The published MATLAB code of the measure set uses a fixed table of 25 critical
+ * bands with Gaussian-shaped filters and a 1,024-point transform; it was not at hand, and nothing here claims equal
+ * figures with it.  Not computed: weighted spectral slope, Itakura-Saito, PESQ and the composites CSIG / CBAK / COVL (they
+ * need PESQ); other sample rates; live sessions.
+ * Every figure is a function of the clip pair (and W) alone: no floating-point atomics, no reduction whose shape depends
+ * on the batch; a record and every per-frame value have the same bits alone or in any batch, at any offset, on every run.
+ * Only samples inside a clip are fetched.
+ *
+ * Clip i of the estimates is est_dev[est_offsets_host[i] .. est_offsets_host[i + 1]), of the targets likewise with its own
+ * offsets.  bands_host (nullable: the default matrix) is a HOST array of nbands * 257 doubles, nbands ignored where it is
+ * NULL.  out_dev receives NHANS_QUALITY_FIELDS doubles per clip.  frames_out_dev (nullable) receives rows of three doubles
+ * llr_f, cd_f, fw_f, clip after clip: clip i's M_i rows begin at row sum_{k < i} M_k; NaN where the frame was skipped.  The
+ * workspace holds three doubles a frame when frames_out_dev is NULL.  NHANS_EINVAL, naming the clip, before anything is
+ * launched and with nothing written: nclips < 0, nbands outside 1 ... 32 or a weight that is negative or not finite, a
+ * NULL that is needed, an offset array that descends, a clip of more than 2^31 - 1 samples.
+ *
+ * nhans_quality_lpc (for tests and diagnosis) runs the LPC launch alone and writes NHANS_QUALITY_LPC_FIELDS doubles per
+ * frame, rows as above: r_t[0 .. 16], r_e[0 .. 16], a_t[0 .. 16], a_e[0 .. 16], num, den, dc2, 0.  Where a recursion stopped
+ * its a[1 .. 16] are NaN, and so is what is computed from them.
+ * nhans_quality_tables (host only) copies the 480 doubles of w and the 25 * 257 of the default W; either may be NULL. */
+#define NHANS_QUALITY_FIELDS 16 /* n, frames, frames_lpc, frames_fw, llr, llr_95, cd_db, cd_95_db, fwsegsnr_db, 0 ... */
+#define NHANS_QUALITY_LPC_FIELDS 72
+#define NHANS_QUALITY_BINS 257
+#define NHANS_QUALITY_BANDS 25
+#define NHANS_QUALITY_MAX_BANDS 32
+int nhans_quality(nhans_ctx* ctx, const float* est_dev, const int64_t* est_offsets_host, const float* tgt_dev,
+                  const int64_t* tgt_offsets_host, int nclips, const double* bands_host, int nbands, double* out_dev,
+                  double* frames_out_dev, void* stream);
+int nhans_quality_lpc(nhans_ctx* ctx, const float* est_dev, const int64_t* est_offsets_host, const float* tgt_dev,
+                      const int64_t* tgt_offsets_host, int nclips, double* lpc_out_dev, void* stream);
+int nhans_quality_tables(double* window_out, double* bands_out);        /* host only */
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

@@ -68,6 +68,7 @@ class Flags(object):
     bss = False          # --bss: with --score_against and --interferer, also SDR, SIR and SAR (score.py: bss_reference is the definition)
     interferer = None    # --interferer FILE: the signal that was to be removed, for --bss
     align_ms = None      # --align_ms MS: with --score_against, the delay of the denoised file against the target is estimated within MS and taken out
+    quality = False      # --quality: with --score_against, also LLR, cepstral distance and fwSegSNR (score.py: quality_reference is the definition)
     stoi = False         # --stoi: with --score_against, also STOI and extended STOI (score.py: stoi_reference is the definition)
     lookahead_ms = 10 * spec.LOOKAHEAD   # --lookahead_ms: 10 ms per frame of look-ahead (include/nhans_hip.h: "lookahead"), 170 = all 17
 
@@ -615,7 +616,7 @@ def apply_demo_separator(cleanpath, noisepath, save_to, mix_on="host"):
 
 
 def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelname='nhans', step=0, scores=False, mix_on="host",
-                       stoi=False, bss=False):
+                       stoi=False, bss=False, quality=False):
     """Evaluation-reader pipeline for one (speech, pos noise, neg noise) triple: SN/reader.py:310-420
     (eval branch, eval_stride 1) + SN/main.py:264-353.  Mixes at the reference's md5-derived SNRs,
     runs the network on frames from context_frames on, writes the reference's five wavs
@@ -629,6 +630,9 @@ def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelnam
     bss=True (with scores): the records also carry SDR, SIR and SAR (Engine.bss_eval_device, merged by score.merge_bss) of
     the same waveforms against the mixing's own target and negative noise -- as mixed, from the first scored sample on --
     and the improvement sdr_i, sir_i and sar_i; the files and the loss are what they are without it.
+    quality=True (with scores): the records also carry LLR, cepstral distance and fwSegSNR of the same waveforms
+    (Engine.quality_device, merged by score.merge_quality) and the improvement llr_i, llr_95_i, cd_i, cd_95_i (lower is
+    better: an improvement is negative) and fwsegsnr_i; the files and the loss are what they are without it.
     A corpus at several SNR pairs in one pass: evaluate_corpus."""
     from . import mixing
     eng = get_engine(spec.DENOISER)
@@ -649,7 +653,7 @@ def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelnam
     if scores:
         first = Noise_Win * spec.HOP                    # the sample the scored waveforms begin at
         return loss, _utterance_scores(eng, den, mix_rt, extras[0], den_lm, mix_lm, tgt_lm, stoi,
-                                       (target[first:], neg_sig[first:]) if bss else None)
+                                       (target[first:], neg_sig[first:]) if bss else None, quality)
     return loss
 
 
@@ -659,7 +663,7 @@ def _eval_wav_path(dump_dir, modelname, step, triple, snr_pos, snr_neg, kind):
 
 
 def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None, per_frame=False, modelname='nhans', step=0,
-                    stoi=False, bss=False):
+                    stoi=False, bss=False, quality=False):
     """evaluate_utterance(scores=True) for a corpus in one pass.  triples: (cleanpath, pospath, negpath) each; snrs: the
     (snr_pos, snr_neg) pairs applied to every triple (None: the triple's own mixing.eval_snrs).  The files are read,
     normalised and trimmed on the host and uploaded once; the mixtures of all (triple, SNR pair) jobs (Engine.mix_device),
@@ -672,7 +676,9 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
     evaluate_utterance's scores) and "mix" (the job's mixing record); per_frame=True: plus "per_frame" in "denoised" and
     "mixed", float64 [frames, 3] as Context.score's.  stoi=True: STOI and extended STOI in the same pass, as
     evaluate_utterance(scores=True, stoi=True) merges them, bit for bit; only their records come back.  bss=True: SDR, SIR
-    and SAR against each job's own target and negative noise, which the mixing left in HBM, likewise."""
+    and SAR against each job's own target and negative noise, which the mixing left in HBM, likewise.  quality=True: LLR,
+    cepstral distance and fwSegSNR in the same pass, as evaluate_utterance(scores=True, quality=True) merges them, bit for
+    bit."""
     from . import context, mixing, score
     eng = get_engine(spec.DENOISER)
     speech, noises, jobs, meta = [], [], [], []
@@ -693,7 +699,7 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
     sig, off, mix_rec = eng.mix_device(sp_t, sp_off, nz_t, nz_off, jobs)
     dump = dump_dir is not None
     res = eng._with_lookahead(lookahead, lambda: context.redo_saturated_in_f32(
-        eng, lambda: _corpus_device(eng, sig, off, per_frame, dump, stoi, bss)))
+        eng, lambda: _corpus_device(eng, sig, off, per_frame, dump, stoi, bss, quality)))
     eng._sync()
     mix_rec = mix_rec.cpu().numpy()
     down = {k: v.cpu().numpy() for k, v in res["records"].items()}
@@ -711,6 +717,8 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
                 r[name] = score.merge_stoi(r[name], score.stoi_record(down[name + "_stoi"][j]))
             if bss:
                 r[name] = score.merge_bss(r[name], score.bss_record(down[name + "_bss"][j]))
+            if quality:
+                r[name] = score.merge_quality(r[name], score.quality_record(down[name + "_quality"][j]))
             if per_frame:
                 r[name]["per_frame"] = frames[name][roff[j]:roff[j + 1]].copy()
         r["loss"] = r["denoised"]["loss"]
@@ -723,7 +731,7 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
     return out
 
 
-def _corpus_device(eng, sig, off, per_frame, dump, stoi=False, bss=False):
+def _corpus_device(eng, sig, off, per_frame, dump, stoi=False, bss=False, quality=False):
     """The launches of evaluate_corpus after the mixing, everything in HBM: job j's signals are [off[j], off[j + 1]) of
     sig's tensors -> device records (and, for a dump, waveforms)."""
     import torch
@@ -759,6 +767,8 @@ def _corpus_device(eng, sig, off, per_frame, dump, stoi=False, bss=False):
             records[name + "_stoi"] = eng.stoi_device(wav, ooff, tgt_wav, ooff)
         if bss:
             records[name + "_bss"] = eng.bss_eval_device(wav, ooff, [(sig["target"], soff), (sig["drop"], soff)])
+        if quality:
+            records[name + "_quality"] = eng.quality_device(wav, ooff, tgt_wav, ooff)
         if per_frame:
             frames[name] = r[1]
     waves = {}
@@ -770,7 +780,7 @@ def _corpus_device(eng, sig, off, per_frame, dump, stoi=False, bss=False):
     return {"records": records, "frames": frames, "waves": waves, "roff": roff, "ooff": ooff}
 
 
-def _utterance_scores(eng, den, mix_rt, target, den_lm, mix_lm, tgt_lm, stoi=False, bss_sources=None):
+def _utterance_scores(eng, den, mix_rt, target, den_lm, mix_lm, tgt_lm, stoi=False, bss_sources=None, quality=False):
     import torch
     from . import score
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(eng.device)
@@ -786,6 +796,9 @@ def _utterance_scores(eng, den, mix_rt, target, den_lm, mix_lm, tgt_lm, stoi=Fal
         if bss_sources is not None:
             b = eng.bss_eval_device(dev(wav), [0, len(wav)], [(dev(x), [0, len(x)]) for x in bss_sources])
             out[name] = score.merge_bss(out[name], score.bss_record(b.cpu().numpy()[0]))
+        if quality:
+            qr = eng.quality_device(dev(wav), [0, len(wav)], tw, [0, len(target)])
+            out[name] = score.merge_quality(out[name], score.quality_record(qr.cpu().numpy()[0]))
     out["improvement"] = score.improvement(out["mixed"], out["denoised"])
     out["rows"] = {"denoised": den_lm, "mixed": mix_lm, "target": tgt_lm}
     return out
@@ -840,6 +853,10 @@ def _parse(argv, prog):
     p.add_argument('--stoi', action='store_true',
                    help='with --score_against: also STOI and extended STOI of the same files against the target, converted to '
                         '10 kHz and computed on the device; the audio files are what they are without the flag')
+    p.add_argument('--quality', action='store_true',
+                   help='with --score_against: also the log-likelihood ratio and the cepstral distance of the LPC models (lower '
+                        'is better) and the frequency-weighted segmental SNR of the same files against the target, computed on '
+                        'the device; the audio files are what they are without the flag')
     p.add_argument('--bss', action='store_true',
                    help='with --score_against and --interferer: also SDR, SIR and SAR (BSS Eval, filters of 512 taps) of the same '
                         'files against the target and the interferer, computed on the device; the audio files are what they '
@@ -868,6 +885,8 @@ def _parse(argv, prog):
         p.error('--score_out needs --score_against TARGET')
     if a.stoi and a.score_against is None:
         p.error('--stoi needs --score_against TARGET')
+    if a.quality and a.score_against is None:
+        p.error('--quality needs --score_against TARGET')
     if a.score_against is not None:
         if a.output_rate == 'input':
             p.error('--score_against scores the 16 kHz files; it does not combine with --output_rate input')
@@ -1002,6 +1021,7 @@ def _score_jobs(kind, a, jobs):
     if align_ms is not None and est:
         found = get_enhancer(kind).align(est[0::2], tgt[0::2], max_lag=int(round(16 * align_ms)))
     recs = get_enhancer(kind).score(est, tgt, stoi=getattr(a, "stoi", False), bss=interf if bss else None,
+                                    quality=getattr(a, "quality", False),
                                     delays=[r["delay"] for r in found for _ in (0, 1)] if found else None) if est else []
     files = {}
     for i, path in enumerate(done):

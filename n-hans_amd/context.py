@@ -126,7 +126,7 @@ class Context:
 
 
     # ---- scoring against a clean target (include/nhans_hip.h: nhans_score_*) ---------------------
-    def score(self, estimates, targets, per_frame=False, stoi=False, bss=None, align=None, delays=None):
+    def score(self, estimates, targets, per_frame=False, stoi=False, bss=None, align=None, delays=None, quality=False):
         """Lists of float32 waveforms, estimate i against target i over their common prefix -> one dict per clip: the
         waveform figures (score.FIELDS: si_sdr_db, snr_db, segsnr_db, ...) and the row figures loss and lsd_db of the two
         signals' own log-magnitude rows (nhans_stft_features) -- one upload, two STFTs and the two score calls on the
@@ -135,7 +135,9 @@ class Context:
         the same pairs (16 kHz signals), merged into each record -- a name the record already has (n, frames: there the
         16 kHz samples and the STFT rows) is prefixed: stoi_n, stoi_frames.  bss: a list of interferers (or True: the
         target alone) -- plus the figures of Context.bss_eval of the same estimates (sdr_db, sir_db, sar_db, ...), merged
-        into each record; its n is bss_n.
+        into each record; its n is bss_n.  quality=True: plus the figures of Context.quality of the same pairs (llr, llr_95,
+        cd_db, cd_95_db, fwsegsnr_db, frames_lpc, frames_fw), merged into each record; its n and frames are quality_n and
+        quality_frames.
         Signals that are not aligned: align=D estimates one delay per pair within D samples either way (Context.align),
         delays=[...] applies given integers (positive: the estimate is late); each pair is cut to its common part
         (score.align_cut; an interferer as its target) and scored as above, and each record gains "delay" and, where the
@@ -145,8 +147,12 @@ class Context:
         if align is not None or delays is not None:
             extra = bss if bss is not None and bss is not False and bss is not True else None
             es, ts, xs, tags = self._aligned("score", estimates, targets, extra, align, delays)
-            recs = self.score(es, ts, per_frame=per_frame, stoi=stoi, bss=xs if extra is not None else bss)
+            recs = self.score(es, ts, per_frame=per_frame, stoi=stoi, bss=xs if extra is not None else bss, quality=quality)
             return [dict(r, **tag) for r, tag in zip(recs, tags)]
+        if quality:
+            return [score_mod.merge_quality(r, qr)
+                    for r, qr in zip(self.score(estimates, targets, per_frame=per_frame, stoi=stoi, bss=bss),
+                                     self.quality(estimates, targets))]
         if bss is not None and bss is not False:
             return [score_mod.merge_bss(r, b)
                     for r, b in zip(self.score(estimates, targets, per_frame=per_frame, stoi=stoi),
@@ -291,6 +297,62 @@ class Context:
             res.append(rec)
         return res
 
+    # ---- LLR, cepstral distance and fwSegSNR against a clean target (include/nhans_hip.h: nhans_quality) ----
+    def quality(self, estimates, targets, per_frame=False, bands=None, delays=None):
+        """Lists of float32 waveforms at 16 kHz, estimate i against target i over their common prefix -> one dict per clip by
+        score.QUALITY_FIELDS: n, frames, frames_lpc, frames_fw, llr, llr_95, cd_db, cd_95_db (lower is better for these
+        four) and fwsegsnr_db -- NaN where no frame was kept.  One upload, one call, one download.  per_frame=True: plus
+        "per_frame", float64 [frames, 3] = each frame's llr_f, cd_f and fw_f, NaN where it was skipped.  bands: a
+        non-negative [K <= 32, 257] matrix in place of score.quality_band_matrix().  delays=[...]: each pair is first cut
+        to its common part with the estimate's delay (positive: late) taken out, and each record gains "delay"."""
+        if len(estimates) != len(targets):
+            raise ValueError("quality: one target per estimate")
+        if delays is not None:
+            es, ts, _, tags = self._aligned("quality", estimates, targets, None, None, delays)
+            return [dict(r, **tag) for r, tag in zip(self.quality(es, ts, per_frame=per_frame, bands=bands), tags)]
+        lib, mem, n = self.lib, Mem(self), len(estimates)
+        W, K = quality_bands_arg(bands)
+        (ef, eoff), (tf, toff) = flat(estimates), flat(targets)
+        foff = offsets(score_mod.quality_num_frames(min(eoff[i + 1] - eoff[i], toff[i + 1] - toff[i])) for i in range(n))
+        buf = mem.up(np.ascontiguousarray(np.concatenate([ef, tf])))
+        nf, per = hip.QUALITY_FIELDS, (3 * foff[-1] if per_frame else 0)
+        out = mem.empty(n * nf + per, np.float64)
+        try:
+            hip.check(lib.nhans_quality(self.handle, mem.p(buf), hip.i64_array(eoff), ctypes.c_void_p(mem.p(buf).value + 4 * len(ef)),
+                                        hip.i64_array(toff), n, W, K, mem.p(out),
+                                        ctypes.c_void_p(mem.p(out).value + 8 * n * nf) if per_frame else None, mem.stream()))
+            self._sync()
+            got = np.array(mem.down(out, n * nf + per, np.float64), dtype=np.float64)
+        finally:
+            mem.free(buf, out)
+        res = []
+        for i in range(n):
+            rec = score_mod.quality_record(got[i * nf:(i + 1) * nf])
+            if per_frame:
+                rec["per_frame"] = got[n * nf:].reshape(-1, 3)[foff[i]:foff[i + 1]].copy()
+            res.append(rec)
+        return res
+
+    def quality_lpc(self, estimates, targets):
+        """The per-frame LPC quantities of nhans_quality (nhans_quality_lpc; for tests and diagnosis) -> one float64
+        [frames, hip.QUALITY_LPC_FIELDS] array per clip: r_t[17], r_e[17], a_t[17], a_e[17], num, den, dc2, 0."""
+        if len(estimates) != len(targets):
+            raise ValueError("quality_lpc: one target per estimate")
+        lib, mem, n = self.lib, Mem(self), len(estimates)
+        (ef, eoff), (tf, toff) = flat(estimates), flat(targets)
+        foff = offsets(score_mod.quality_num_frames(min(eoff[i + 1] - eoff[i], toff[i + 1] - toff[i])) for i in range(n))
+        buf = mem.up(np.ascontiguousarray(np.concatenate([ef, tf])))
+        nl = hip.QUALITY_LPC_FIELDS
+        out = mem.empty(nl * foff[-1], np.float64)
+        try:
+            hip.check(lib.nhans_quality_lpc(self.handle, mem.p(buf), hip.i64_array(eoff), ctypes.c_void_p(mem.p(buf).value + 4 * len(ef)),
+                                            hip.i64_array(toff), n, mem.p(out), mem.stream()))
+            self._sync()
+            got = np.array(mem.down(out, nl * foff[-1], np.float64), dtype=np.float64).reshape(-1, nl)
+        finally:
+            mem.free(buf, out)
+        return [got[foff[i]:foff[i + 1]].copy() for i in range(n)]
+
     # ---- BSS Eval against target and interferer (include/nhans_hip.h: nhans_bss_eval) -------------
     def bss_eval(self, estimates, targets, interferers=None, filt_len=score_mod.BSS_MAX_FILTER, filters=False, delays=None):
         """Lists of float32 waveforms, estimate i against target i and (interferers given) interferer i over the samples
@@ -356,6 +418,16 @@ class Context:
 
     def _sync(self):
         """Waits for the work issued on this context's stream (the null stream's copies wait by themselves)."""
+
+
+def quality_bands_arg(bands):
+    """bands (None, or a [K <= 32, 257] matrix) -> (the host pointer nhans_quality takes, K)"""
+    if bands is None:
+        return None, 0
+    W = np.ascontiguousarray(bands, dtype=np.float64)
+    if W.ndim != 2 or W.shape[1] != hip.QUALITY_BINS:
+        raise ValueError("quality: bands is a [K, %d] matrix" % hip.QUALITY_BINS)
+    return W.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(W.shape[0])
 
 
 def redo_saturated_in_f32(eng, run, undo=None):

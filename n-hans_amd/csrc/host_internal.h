@@ -15,7 +15,8 @@
 //   host_stoi.hip     nhans_stoi, nhans_stoi_resample, nhans_stoi_out_count
 //   host_bsseval.hip  nhans_bss_eval
 //   host_align.hip    nhans_align, nhans_align_common, nhans_align_cut
-// A unit calls down only: ctx <- net <- online <- live, ctx <- fbank <- online, ctx <- rate <- live, ctx <- score, ctx <- mix, ctx <- rate <- stoi, ctx <- bsseval and ctx <- align.  (One call goes up: the built-in calibration
+//   host_quality.hip  nhans_quality, nhans_quality_lpc, nhans_quality_tables
+// A unit calls down only: ctx <- net <- online <- live, ctx <- fbank <- online, ctx <- rate <- live, ctx <- score, ctx <- mix, ctx <- rate <- stoi, ctx <- bsseval, ctx <- align and ctx <- quality.  (One call goes up: the built-in calibration
 // of nhans_create runs the whole offline path, enhance_clips_body.)  Only what crosses a unit boundary is declared here;
 // everything else stays in its unit's anonymous namespace.
 // Nothing declared here joins the library's dynamic symbols (visibility hidden) except the object types the C header

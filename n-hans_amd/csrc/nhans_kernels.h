@@ -575,4 +575,33 @@ void launch_align_corr(const char* kernel, const AlignRun* runs_dev, int nruns, 
 void launch_align_pick(const char* kernel, const AlignRun* runs_dev, int nruns, int D, const double* corr, double* rec, hipStream_t s);
 void launch_align_cut(const char* kernel, const AlignCopy* jobs_dev, int njobs, long long ntiles, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// LLR, cepstral distance and frequency-weighted segmental SNR against a clean target (quality.hip; include/nhans_hip.h:
+// nhans_quality).  One QualityRun per clip pair, empty ones included: n common samples at est / tgt (16 kHz) and `frames`
+// = M frames of 480 at hop 120.  A clip owns rows [frame0, frame0 + M) of the per-frame values and workgroups
+// [ltile0, ...) of the LPC launch (kQualityLpcTile frames each) and [btile0, ...) of the band launch (kQualityBandTile
+// frames each); all of them ascend from 0 over the runs.
+struct QualityRun {
+    const float* est;
+    const float* tgt;
+    long long n, frames, frame0, ltile0, btile0;
+};
+constexpr int kQualityFields = 16, kQualityFrame = 480, kQualityHop = 120, kQualityOrder = 16, kQualityFft = 512, kQualityBins = 257;
+constexpr int kQualityBands = 25, kQualityMaxBands = 32, kQualityLpcTile = 7, kQualityBandTile = 2;
+constexpr int kQualityLpcFields = 72;       // a frame's row of nhans_quality_lpc: r_t[17], r_e[17], a_t[17], a_e[17], num, den, dc2, 0
+constexpr int kQualityTable = kQualityFrame + 2 * kQualityFft;      // doubles: the window, then cos and -sin of 2 pi t / 512
+constexpr double kQualityLlrMax = 2.0, kQualityCdMax = 10.0, kQualityCdScale = 4.342944819032518 /* 10 / ln 10 */;
+constexpr double kQualitySnrMin = -10.0, kQualitySnrMax = 35.0, kQualityGamma = 0.2;
+inline long long quality_frames(long long n) { return n >= kQualityFrame ? (n - kQualityFrame) / kQualityHop + 1 : 0; }
+void quality_table(double* tab);                            // (host) the kQualityTable doubles
+void quality_default_bands(double* w);                      // (host) [kQualityBands][kQualityBins]
+// vals: [frames][3] = llr_f, cd_f (this launch), fw_f (the band launch); lpc_out (nullable): [frames][kQualityLpcFields]
+void launch_quality_lpc(const char* kernel, const QualityRun* runs_dev, int nruns, long long ntiles, const double* tab, double* vals,
+                        double* lpc_out, hipStream_t s);
+// bands: [nbands][kQualityBins]; span: [nbands][2] = the bins [first, last + 1) of each row's non-zero weights (0, 0: none)
+void launch_quality_bands(const char* kernel, const QualityRun* runs_dev, int nruns, long long ntiles, const double* tab,
+                          const double* bands, const int* span, int nbands, double* vals, hipStream_t s);
+// rec: [clips][kQualityFields]
+void launch_quality_finish(const char* kernel, const QualityRun* runs_dev, int nruns, const double* vals, double* rec, hipStream_t s);
+
 }  // namespace nhans

@@ -280,6 +280,29 @@ class Engine(context.Context):
                                       hip.ptr(seg), self._stream()))
         return (out, seg[:soff[-1]], soff) if per_segment else out
 
+    # ---- LLR, cepstral distance and fwSegSNR against a clean target (include/nhans_hip.h: nhans_quality) ----
+    def quality_device(self, est_t, est_off, tgt_t, tgt_off, per_frame=False, bands=None):
+        """The quality figures of clips already in HBM: estimate i = est_t[est_off[i]:est_off[i + 1]] against target i of
+        tgt_t / tgt_off, float32 at 16 kHz -> device tensor float64 [n, hip.QUALITY_FIELDS] (score.QUALITY_FIELDS names the
+        columns); per_frame=True: -> (that, float64 [frames, 3] = llr_f, cd_f, fw_f, the row offsets: clip i's rows are
+        [offsets[i], offsets[i + 1]))."""
+        n = len(est_off) - 1
+        if len(tgt_off) - 1 != n:
+            raise ValueError("quality_device: one target per estimate")
+        for t in (est_t, tgt_t):
+            if t.dtype != torch.float32 or t.dim() != 1:
+                raise ValueError("quality_device: flat float32 tensors")
+        W, K = context.quality_bands_arg(bands)
+        eo, to = [int(v) for v in est_off], [int(v) for v in tgt_off]
+        out = torch.empty((n, hip.QUALITY_FIELDS), dtype=torch.float64, device=self.device)
+        fr, foff = None, None
+        if per_frame:
+            foff = context.offsets(score_mod.quality_num_frames(min(eo[i + 1] - eo[i], to[i + 1] - to[i])) for i in range(n))
+            fr = torch.empty((max(foff[-1], 1), 3), dtype=torch.float64, device=self.device)
+        hip.check(self.lib.nhans_quality(self.handle, hip.ptr(est_t.contiguous()), hip.i64_array(eo), hip.ptr(tgt_t.contiguous()),
+                                         hip.i64_array(to), n, W, K, hip.ptr(out), hip.ptr(fr), self._stream()))
+        return (out, fr[:foff[-1]], foff) if per_frame else out
+
     # ---- mixing at a chosen SNR (include/nhans_hip.h: nhans_mix) ------------------------------------
     def mix_device(self, speech_t, speech_off, noise_t, noise_off, jobs, want=("mixture", "target", "keep", "drop")):
         """Mixtures of clips already in HBM.  jobs: (speech index, keep index or -1, drop index, snr_keep_db, snr_drop_db)

@@ -136,6 +136,10 @@ SIGNATURES = {
     "nhans_align": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _int, _vp, _vp, _vp]),
     "nhans_align_common": (_i64, [_i64, _i64, _i64]),
     "nhans_align_cut": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _i64p, _vp, _vp, _i64p, _vp]),
+    # LLR, cepstral distance and frequency-weighted segmental SNR against a clean target (the band matrix is a host array)
+    "nhans_quality": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _dp, _int, _vp, _vp, _vp]),
+    "nhans_quality_lpc": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _vp, _vp]),
+    "nhans_quality_tables": (_int, [_dp, _dp]),
     "nhans_profile_json": (_int, [_vp, _str, _size]),
     "nhans_profile_reset": (_int, [_vp]),
 }
@@ -166,6 +170,10 @@ BSS_CORR_TILE = 2048                        # samples per workgroup of bsseval.h
 ALIGN_FIELDS = 8
 ALIGN_MAX_LAG = 16000
 ALIGN_TILE, ALIGN_LAG_BLOCK = 2048, 2048    # samples per tile and lags per workgroup of align.hip (kAlignTile, kAlignLagBlock)
+QUALITY_FIELDS, QUALITY_LPC_FIELDS = 16, 72
+QUALITY_FRAME, QUALITY_HOP, QUALITY_ORDER, QUALITY_FFT, QUALITY_BINS = 480, 120, 16, 512, 257
+QUALITY_BANDS, QUALITY_MAX_BANDS = 25, 32
+QUALITY_LPC_TILE, QUALITY_BAND_TILE = 7, 2  # frames per workgroup of quality.hip's LPC and band launches (kQualityLpcTile, kQualityBandTile)
 MIX_TILE = 2048                             # samples per workgroup and per staging buffer of mix.hip (kMixTile)
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25

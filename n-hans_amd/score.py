@@ -8,7 +8,9 @@ the only roundings in them are the ones the definition names.  STOI and extended
 Engine.stoi_device) have theirs in `stoi_reference`, built from the steps below it, and BSS
 Eval's SDR, SIR and SAR (bsseval.hip: Context.bss_eval / Engine.bss_eval_device) in
 `bss_reference`.  Delay estimation for signals that are not aligned (align.hip: Context.align, Context.score(align=...);
-DESIGN.md section 1.13) has its definition in `align_reference`.  No torch here: the command line imports this."""
+DESIGN.md section 1.13) has its definition in `align_reference`.  LLR, cepstral distance and frequency-weighted
+segmental SNR (quality.hip: Context.quality / Engine.quality_device) have theirs in
+`quality_reference`.  No torch here: the command line imports this."""
 import math
 
 import numpy as np
@@ -36,8 +38,15 @@ BSS_ENERGIES, BSS_FIGURES = BSS_FIELDS[3:9], BSS_FIELDS[9:12]
 BSS_MAX_FILTER = 512
 ALIGN_FIELDS = ("ne", "nt", "D", "delay", "c_peak", "rho", "n_common")        # the first seven of NHANS_ALIGN_FIELDS doubles
 ALIGN_MAX_LAG = 16000
+QUALITY_FIELDS = ("n", "frames", "frames_lpc", "frames_fw", "llr", "llr_95", "cd_db", "cd_95_db",
+                  "fwsegsnr_db")                            # the first nine of NHANS_QUALITY_FIELDS doubles
+QUALITY_FIGURES = QUALITY_FIELDS[4:]
+QUALITY_FRAME, QUALITY_HOP, QUALITY_ORDER, QUALITY_FFT, QUALITY_BINS = 480, 120, 16, 512, 257
+QUALITY_BANDS, QUALITY_MAX_BANDS = 25, 32
+QUALITY_LLR_MAX, QUALITY_CD_MAX, QUALITY_CD_SCALE = 2.0, 10.0, 4.342944819032518      # 10 / ln 10
+QUALITY_SNR_MIN, QUALITY_SNR_MAX, QUALITY_GAMMA = -10.0, 35.0, 0.2
 _INTS = ("n", "frames", "frames_counted", "frames_skipped", "frames_kept", "segments", "stoi_n", "stoi_frames", "J", "L", "singular",
-         "bss_n", "ne", "nt", "D", "delay", "n_common")
+         "bss_n", "ne", "nt", "D", "delay", "n_common", "frames_lpc", "frames_fw", "quality_n", "quality_frames")
 
 
 def record(values):
@@ -77,16 +86,32 @@ def align_record(values):
     return {k: (int(values[i]) if k in _INTS else float(values[i])) for i, k in enumerate(ALIGN_FIELDS)}
 
 
+def quality_record(values):
+    """NHANS_QUALITY_FIELDS doubles of one clip -> dict by name."""
+    return {k: (int(values[i]) if k in _INTS else float(values[i])) for i, k in enumerate(QUALITY_FIELDS)}
+
+
+def merge_quality(rec, quality_rec):
+    """A score record with the LLR, cepstral-distance and fwSegSNR figures of the same pair merged in; a name the record
+    already has (n, frames: there the STFT rows) is prefixed: quality_n, quality_frames."""
+    return dict(rec, **{("quality_" + k if k in rec else k): v for k, v in quality_rec.items()})
+
+
 def improvement(before, after):
     """What `after` gains over `before`, both scored against the same target: the dB differences and the ratio of the
     losses (below one is better); where both carry STOI figures, their differences stoi_i and estoi_i too; where both
-    carry BSS Eval figures, sdr_i, sir_i and sar_i."""
+    carry BSS Eval figures, sdr_i, sir_i and sar_i; where both carry the quality figures, the plain differences llr_i,
+    llr_95_i, cd_i, cd_95_i (LOWER is better for these four: an improvement is negative) and fwsegsnr_i."""
     out = {k[:-3] + "_i": after[k] - before[k] for k in ("si_sdr_db", "snr_db", "segsnr_db") if k in after and k in before}
     if "stoi" in after and "stoi" in before:
         out.update(stoi_i=after["stoi"] - before["stoi"], estoi_i=after["estoi"] - before["estoi"])
     if all(k in after and k in before for k in BSS_FIGURES):
         with np.errstate(invalid="ignore"):
             out.update({k[:-3] + "_i": float(np.float64(after[k]) - np.float64(before[k])) for k in BSS_FIGURES})
+    if all(k in after and k in before for k in QUALITY_FIGURES):
+        with np.errstate(invalid="ignore"):
+            out.update({(k[:-3] if k.endswith("_db") else k) + "_i": float(np.float64(after[k]) - np.float64(before[k]))
+                        for k in QUALITY_FIGURES})
     if "loss" in after and "loss" in before:
         with np.errstate(divide="ignore", invalid="ignore"):
             out["loss_ratio"] = float(np.float64(after["loss"]) / np.float64(before["loss"]))
@@ -477,3 +502,174 @@ def align_cut(e, t, delay):
                          % (d, len(e) if d > 0 else len(t), "estimate" if d > 0 else "target"))
     n = align_common(len(e), len(t), d)
     return e[max(d, 0):max(d, 0) + n], t[max(-d, 0):max(-d, 0) + n]
+
+
+# ---- LLR, cepstral distance, fwSegSNR: the float64 definition (include/nhans_hip.h: nhans_quality) -------
+_quality_tables = None
+
+
+def _quality_host_tables():
+    """(w [480], W [25, 257]): the very tables the library uploads (nhans_quality_tables, host only)."""
+    global _quality_tables
+    if _quality_tables is None:
+        import ctypes
+        from . import hip
+        w, W = np.zeros(QUALITY_FRAME), np.zeros((QUALITY_BANDS, QUALITY_BINS))
+        dp = ctypes.POINTER(ctypes.c_double)
+        hip.check(hip.load().nhans_quality_tables(w.ctypes.data_as(dp), W.ctypes.data_as(dp)))
+        _quality_tables = (w, W)
+    return _quality_tables
+
+
+def quality_window():
+    """w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / 481), i < 480: the table the device reads, bit for bit."""
+    return _quality_host_tables()[0].copy()
+
+
+def quality_band_matrix():
+    """The default band matrix, float64 [25, 257]: triangles on the HTK mel scale between 0 and 8000 Hz over the bin
+    frequencies 31.25 k -- fbank.design's construction on 257 bins, built by the library on the host."""
+    return _quality_host_tables()[1].copy()
+
+
+def quality_num_frames(n):
+    return (int(n) - QUALITY_FRAME) // QUALITY_HOP + 1 if n >= QUALITY_FRAME else 0
+
+
+def quality_frames(x, w):
+    """the windowed frames of x (float64), [M, 480]: frame f is x[120 f : 120 f + 480] * w"""
+    M = quality_num_frames(len(x))
+    idx = QUALITY_HOP * np.arange(M)[:, None] + np.arange(QUALITY_FRAME)[None, :]
+    return x[idx] * w[None, :] if M else np.zeros((0, QUALITY_FRAME))
+
+
+def quality_autocorr(xw):
+    """r[0 .. 16] of one windowed frame, every sum exactly rounded"""
+    N = len(xw)
+    return np.array([_fsum((xw[:N - k] * xw[k:]).tolist()) for k in range(QUALITY_ORDER + 1)])
+
+
+def _pos_finite(v):
+    return v > 0.0 and math.isfinite(v)
+
+
+def quality_levinson(r):
+    """Levinson-Durbin on r[0 .. 16] -> (a [17] with a[0] = 1, [E_1 .. E_16], ok): ok is False where r[0] == 0 or an E_m is
+    not a positive finite number (the recursion stops there)."""
+    P = QUALITY_ORDER
+    a = np.zeros(P + 1)
+    a[0] = 1.0
+    E, errs = float(r[0]), []
+    if r[0] == 0.0:
+        return a, errs, False
+    for m in range(1, P + 1):
+        k = -_fsum([r[m]] + [a[j] * r[m - j] for j in range(1, m)]) / E
+        a[1:m] = a[1:m] + k * a[1:m][::-1]
+        a[m] = k
+        E = E * (1.0 - k * k)
+        errs.append(E)
+        if not _pos_finite(E):
+            return a, errs, False
+    return a, errs, True
+
+
+def quality_toeplitz(r):
+    i = np.arange(len(r))
+    return np.asarray(r)[np.abs(i[:, None] - i[None, :])]
+
+
+def quality_form(a, r):
+    """a' R a with R[i][j] = r[|i - j|]"""
+    return _fsum((a[:, None] * quality_toeplitz(r) * a[None, :]).ravel().tolist())
+
+
+def quality_cepstrum(a):
+    """c[0 .. 16] (c[0] = 0) of the all-pole model 1 / A(z): c[m] = -a[m] - sum_{k < m} (k / m) c[k] a[m - k]"""
+    P = QUALITY_ORDER
+    c = np.zeros(P + 1)
+    for m in range(1, P + 1):
+        c[m] = -a[m] - _fsum([(k / m) * c[k] * a[m - k] for k in range(1, m)])
+    return c
+
+
+def quality_lpc_frame(tw, ew):
+    """One frame pair (windowed, float64) -> dict: r_t, r_e, a_t, a_e, num, den, dc2, llr, cd (NaN where skipped), ok."""
+    rt, re_ = quality_autocorr(tw), quality_autocorr(ew)
+    at, _, okt = quality_levinson(rt)
+    ae, _, oke = quality_levinson(re_)
+    out = {"r_t": rt, "r_e": re_, "a_t": at, "a_e": ae, "num": float("nan"), "den": float("nan"), "dc2": float("nan"),
+           "llr": float("nan"), "cd": float("nan"), "ok": False}
+    if not (okt and oke):
+        return out
+    num, den = quality_form(ae, rt), quality_form(at, rt)
+    d = quality_cepstrum(at) - quality_cepstrum(ae)
+    out.update(num=num, den=den, dc2=_fsum((d[1:] * d[1:]).tolist()))
+    if not (_pos_finite(num) and _pos_finite(den)):
+        return out
+    llr = min(max(math.log(num / den), 0.0), QUALITY_LLR_MAX)
+    cd = min(max(QUALITY_CD_SCALE * math.sqrt(2.0 * out["dc2"]), 0.0), QUALITY_CD_MAX)
+    out.update(llr=llr + 0.0, cd=cd + 0.0, ok=True)
+    return out
+
+
+def quality_band_sums(fw_frames, W):
+    """|rfft(frames, 512)| @ W' with exactly rounded sums -> [M, K]"""
+    X = np.abs(np.fft.rfft(fw_frames, n=QUALITY_FFT, axis=1)) if len(fw_frames) else np.zeros((0, QUALITY_BINS))
+    return np.array([[_fsum((w * x).tolist()) for w in W] for x in X], dtype=np.float64).reshape(len(X), len(W))
+
+
+def quality_fw_frame(X, Y):
+    """The frequency-weighted segmental SNR of one frame from its band sums X (target) and Y (estimate): 35 less the
+    weighted mean of the bands' deficits 35 - s_j; NaN where the weights sum to zero."""
+    s = []
+    for x, y in zip(X, Y):
+        if x == y:
+            s.append(QUALITY_SNR_MAX)
+        else:
+            s.append(min(max(_db(_div(x * x, (x - y) * (x - y))), QUALITY_SNR_MIN), QUALITY_SNR_MAX))
+    g = [float(x) ** QUALITY_GAMMA for x in X]
+    G = _fsum(g)
+    return QUALITY_SNR_MAX - _fsum([a * (QUALITY_SNR_MAX - b) for a, b in zip(g, s)]) / G if G != 0.0 else float("nan")
+
+
+def quality_trimmed_mean(values):
+    """The mean of the q = (19 Mk + 10) // 20 smallest of the Mk values (NaN for none)."""
+    v = sorted(values)
+    q = (19 * len(v) + 10) // 20
+    return _fsum(v[:q]) / q if q else float("nan")
+
+
+def quality_summary(n, per):
+    """The record of a clip of n common samples from its per-frame values [frames, 3] (NaN: skipped) -> dict by
+    QUALITY_FIELDS."""
+    llr, cd, fw = ([float(v) for v in per[:, k] if v == v] for k in range(3))
+    mean = lambda v: _fsum(v) / len(v) if v else float("nan")
+    return {"n": int(n), "frames": len(per), "frames_lpc": len(llr), "frames_fw": len(fw), "llr": mean(llr),
+            "llr_95": quality_trimmed_mean(llr), "cd_db": mean(cd), "cd_95_db": quality_trimmed_mean(cd), "fwsegsnr_db": mean(fw)}
+
+
+def quality_reference(e, t, per_frame=False, bands=None, details=False):
+    """LLR, cepstral distance and frequency-weighted segmental SNR of estimate e against target t (float32 values at 16 kHz;
+    scored over the common prefix) as the header defines them -> dict by QUALITY_FIELDS.  per_frame=True: plus "per_frame",
+    float64 [frames, 3] = llr_f, cd_f, fw_f, NaN where the frame was skipped.  bands: a non-negative [K <= 32, 257] matrix
+    (None: quality_band_matrix()).  details=True: plus "lpc", one quality_lpc_frame dict per frame, and "band_sums",
+    (X, Y) float64 [frames, K]."""
+    n = min(len(e), len(t))
+    e = np.asarray(e[:n], dtype=np.float32).astype(np.float64)
+    t = np.asarray(t[:n], dtype=np.float32).astype(np.float64)
+    W = quality_band_matrix() if bands is None else np.asarray(bands, dtype=np.float64)
+    if W.ndim != 2 or W.shape[1] != QUALITY_BINS or not 1 <= W.shape[0] <= QUALITY_MAX_BANDS or not (W >= 0).all() \
+            or not np.isfinite(W).all():
+        raise ValueError("quality_reference: bands is a non-negative finite [K <= %d, %d] matrix" % (QUALITY_MAX_BANDS, QUALITY_BINS))
+    w = quality_window()
+    ft, fe = quality_frames(t, w), quality_frames(e, w)
+    M = len(ft)
+    lpc = [quality_lpc_frame(ft[f], fe[f]) for f in range(M)]
+    X, Y = quality_band_sums(ft, W), quality_band_sums(fe, W)
+    per = np.array([[lpc[f]["llr"], lpc[f]["cd"], quality_fw_frame(X[f], Y[f])] for f in range(M)], dtype=np.float64).reshape(M, 3)
+    out = quality_summary(n, per)
+    if per_frame:
+        out["per_frame"] = per
+    if details:
+        out.update(lpc=lpc, band_sums=(X, Y))
+    return out

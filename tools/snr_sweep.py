@@ -6,11 +6,13 @@ over the mixture, per (snr_pos, snr_neg, look-ahead).  The recordings are read a
 ON THE SYNTHETIC WEIGHTS THESE NUMBERS SAY NOTHING ABOUT QUALITY: a seeded random network denoises nothing.  The tool is
 for whoever has the trained bundle -- point NHANS_MODEL_DIR at it and pass --weights checkpoint; with the synthetic
 weights it shows that the plumbing runs.
-    python tools/snr_sweep.py DIR [--snrs -3,0,3,5,8] [--lookaheads 17,8,2] [--weights synthetic] [--json out.json] [--stoi] [--bss]
+    python tools/snr_sweep.py DIR [--snrs -3,0,3,5,8] [--lookaheads 17,8,2] [--weights synthetic] [--json out.json] [--stoi] [--bss] [--quality]
   --stoi adds the columns stoi_i and estoi_i: STOI and extended STOI in the same pass (NaN for a job whose output is too
   short for one 30-frame segment: 4,097 samples at 10 kHz).
   --bss adds the columns sdr_i, sir_i and sar_i: BSS Eval against each job's own target and negative noise, in the same
   pass (filters of 512 taps).
+  --quality adds the columns llr_i, cd_i and fwsegsnr_i: the log-likelihood ratio and the cepstral distance of the LPC
+  models (LOWER is better: an improvement is negative) and the frequency-weighted segmental SNR, in the same pass.
   DIR holds <name>_speech.wav, <name>_pos.wav and <name>_neg.wav per triple (16 kHz int16; the speech longer than 200
   frames = 32,240 samples).  No DIR: three synthetic triples written to a temporary directory."""
 import argparse
@@ -29,6 +31,7 @@ from nhans_amd import apply, engine, spec, synth  # noqa: E402
 FIGURES = ("si_sdr_i", "snr_i", "segsnr_i", "loss_ratio")
 STOI_FIGURES = ("stoi_i", "estoi_i")
 BSS_FIGURES = ("sdr_i", "sir_i", "sar_i")
+QUALITY_FIGURES = ("llr_i", "cd_i", "fwsegsnr_i")
 
 
 def find_triples(directory):
@@ -75,8 +78,10 @@ def main(argv=None):
     ap.add_argument("--json", default=None, help="also write the rows as JSON")
     ap.add_argument("--stoi", action="store_true", help="also the mean improvements of STOI and extended STOI: stoi_i, estoi_i")
     ap.add_argument("--bss", action="store_true", help="also the mean improvements of BSS Eval's SDR, SIR and SAR: sdr_i, sir_i, sar_i")
+    ap.add_argument("--quality", action="store_true",
+                    help="also the mean changes of LLR and cepstral distance (lower is better) and of fwSegSNR: llr_i, cd_i, fwsegsnr_i")
     a = ap.parse_args(argv)
-    figures = FIGURES + (STOI_FIGURES if a.stoi else ()) + (BSS_FIGURES if a.bss else ())
+    figures = FIGURES + (STOI_FIGURES if a.stoi else ()) + (BSS_FIGURES if a.bss else ()) + (QUALITY_FIGURES if a.quality else ())
     grid = [float(v) if "." in v else int(v) for v in a.snrs.split(",")]
     las = [int(v) for v in a.lookaheads.split(",")]
     for L in las:
@@ -96,7 +101,7 @@ def main(argv=None):
         pairs = [(p, n) for p in grid for n in grid]
         rows = []
         for L in las:
-            rows += summarise(apply.evaluate_corpus(triples, snrs=pairs, lookahead=L, stoi=a.stoi, bss=a.bss), L, figures)
+            rows += summarise(apply.evaluate_corpus(triples, snrs=pairs, lookahead=L, stoi=a.stoi, bss=a.bss, quality=a.quality), L, figures)
         print("%d triples x %d SNR pairs x %d look-aheads, weights: %s" % (len(triples), len(pairs), len(las), a.weights))
         print(table(rows, figures))
         if a.json:
