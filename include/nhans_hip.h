@@ -1118,7 +1118,7 @@ int nhans_align_cut(nhans_ctx* ctx, const float* est_dev, const int64_t* est_off
  *             r_e[0] == 0, an E_m of either recursion is not a positive finite number (the recursion stops there), or den
  *             or num is not a positive finite number.
  *   fwSegSNR  each windowed frame is zero-padded to 512 and transformed by the radix-8 transform of
- *             n-hans_amd/csrc/stoi_fft.h (one transform per signal: an all-zero frame has an all-zero spectrum, exactly);
+ *             n-hans_amd/csrc/fft512.h (one transform per signal: an all-zero frame has an all-zero spectrum, exactly);
  *             |X_k| of the target's and |Y_k| of the estimate's, k = 0 ... 256, |u| = sqrt(fma(u_i, u_i, u_r * u_r)).  Band matrix W:
  *             [K][257], K <= 32, non-negative; the default has K = 25 triangles on the HTK mel scale between 0 and 8000 Hz
  *             over the bin frequencies 31.25 k (the construction of nhans_fbank_design on 257 bins; nhans_quality_tables

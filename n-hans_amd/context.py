@@ -203,19 +203,11 @@ class Context:
         One upload, one call, one download.  corr=True: plus "corr", float64 [2 max_lag + 1], lag -max_lag first."""
         if len(estimates) != len(targets):
             raise ValueError("align: one target per estimate")
-        lib, mem, n, D = self.lib, Mem(self), len(estimates), int(max_lag)
+        n, D = len(estimates), int(max_lag)
         (ef, eoff), (tf, toff) = flat(estimates), flat(targets)
-        buf = mem.up(np.ascontiguousarray(np.concatenate([ef, tf])))
         nf, per = hip.ALIGN_FIELDS, (2 * D + 1 if corr else 0)
-        out = mem.empty(n * (nf + per), np.float64)
-        try:
-            hip.check(lib.nhans_align(self.handle, mem.p(buf), hip.i64_array(eoff), ctypes.c_void_p(mem.p(buf).value + 4 * len(ef)),
-                                      hip.i64_array(toff), n, D, mem.p(out),
-                                      ctypes.c_void_p(mem.p(out).value + 8 * n * nf) if corr else None, mem.stream()))
-            self._sync()
-            got = np.array(mem.down(out, n * (nf + per), np.float64), dtype=np.float64)
-        finally:
-            mem.free(buf, out)
+        got = self._records_call([ef, tf], n * nf, n * per if corr else None, lambda at, out, extra, s: self.lib.nhans_align(
+            self.handle, at(0), hip.i64_array(eoff), at(1), hip.i64_array(toff), n, D, out, extra, s))
         res = []
         for i in range(n):
             rec = score_mod.align_record(got[i * nf:(i + 1) * nf])
@@ -310,21 +302,12 @@ class Context:
         if delays is not None:
             es, ts, _, tags = self._aligned("quality", estimates, targets, None, None, delays)
             return [dict(r, **tag) for r, tag in zip(self.quality(es, ts, per_frame=per_frame, bands=bands), tags)]
-        lib, mem, n = self.lib, Mem(self), len(estimates)
+        n, nf = len(estimates), hip.QUALITY_FIELDS
         W, K = quality_bands_arg(bands)
         (ef, eoff), (tf, toff) = flat(estimates), flat(targets)
         foff = offsets(score_mod.quality_num_frames(min(eoff[i + 1] - eoff[i], toff[i + 1] - toff[i])) for i in range(n))
-        buf = mem.up(np.ascontiguousarray(np.concatenate([ef, tf])))
-        nf, per = hip.QUALITY_FIELDS, (3 * foff[-1] if per_frame else 0)
-        out = mem.empty(n * nf + per, np.float64)
-        try:
-            hip.check(lib.nhans_quality(self.handle, mem.p(buf), hip.i64_array(eoff), ctypes.c_void_p(mem.p(buf).value + 4 * len(ef)),
-                                        hip.i64_array(toff), n, W, K, mem.p(out),
-                                        ctypes.c_void_p(mem.p(out).value + 8 * n * nf) if per_frame else None, mem.stream()))
-            self._sync()
-            got = np.array(mem.down(out, n * nf + per, np.float64), dtype=np.float64)
-        finally:
-            mem.free(buf, out)
+        got = self._records_call([ef, tf], n * nf, 3 * foff[-1] if per_frame else None, lambda at, out, extra, s: self.lib.nhans_quality(
+            self.handle, at(0), hip.i64_array(eoff), at(1), hip.i64_array(toff), n, W, K, out, extra, s))
         res = []
         for i in range(n):
             rec = score_mod.quality_record(got[i * nf:(i + 1) * nf])
@@ -338,19 +321,11 @@ class Context:
         [frames, hip.QUALITY_LPC_FIELDS] array per clip: r_t[17], r_e[17], a_t[17], a_e[17], num, den, dc2, 0."""
         if len(estimates) != len(targets):
             raise ValueError("quality_lpc: one target per estimate")
-        lib, mem, n = self.lib, Mem(self), len(estimates)
+        n, nl = len(estimates), hip.QUALITY_LPC_FIELDS
         (ef, eoff), (tf, toff) = flat(estimates), flat(targets)
         foff = offsets(score_mod.quality_num_frames(min(eoff[i + 1] - eoff[i], toff[i + 1] - toff[i])) for i in range(n))
-        buf = mem.up(np.ascontiguousarray(np.concatenate([ef, tf])))
-        nl = hip.QUALITY_LPC_FIELDS
-        out = mem.empty(nl * foff[-1], np.float64)
-        try:
-            hip.check(lib.nhans_quality_lpc(self.handle, mem.p(buf), hip.i64_array(eoff), ctypes.c_void_p(mem.p(buf).value + 4 * len(ef)),
-                                            hip.i64_array(toff), n, mem.p(out), mem.stream()))
-            self._sync()
-            got = np.array(mem.down(out, nl * foff[-1], np.float64), dtype=np.float64).reshape(-1, nl)
-        finally:
-            mem.free(buf, out)
+        got = self._records_call([ef, tf], nl * foff[-1], None, lambda at, out, extra, s: self.lib.nhans_quality_lpc(
+            self.handle, at(0), hip.i64_array(eoff), at(1), hip.i64_array(toff), n, out, s)).reshape(-1, nl)
         return [got[foff[i]:foff[i + 1]].copy() for i in range(n)]
 
     # ---- BSS Eval against target and interferer (include/nhans_hip.h: nhans_bss_eval) -------------
@@ -367,20 +342,11 @@ class Context:
         if delays is not None:
             es, ts, xs, tags = self._aligned("bss_eval", estimates, targets, interferers, None, delays)
             return [dict(r, **tag) for r, tag in zip(self.bss_eval(es, ts, xs, filt_len=filt_len, filters=filters), tags)]
-        lib, mem, n, J, L = self.lib, Mem(self), len(estimates), len(src), int(filt_len)
+        n, J, L = len(estimates), len(src), int(filt_len)
         flats = [flat(x) for x in [estimates] + src]
-        base = offsets(len(f) for f, _ in flats)
-        buf = mem.up(np.ascontiguousarray(np.concatenate([f for f, _ in flats])))
         nf, per = hip.BSS_FIELDS, (J + 1) * L if filters else 0
-        out = mem.empty(n * (nf + per), np.float64)
-        try:
-            at = lambda k: ctypes.c_void_p(mem.p(buf).value + 4 * base[k])
-            hip.check(bss_call(lib, self.handle, at(0), flats[0][1], [at(1 + j) for j in range(J)], [flats[1 + j][1] for j in range(J)],
-                               n, L, mem.p(out), ctypes.c_void_p(mem.p(out).value + 8 * n * nf) if filters else None, mem.stream()))
-            self._sync()
-            got = np.array(mem.down(out, n * (nf + per), np.float64), dtype=np.float64)
-        finally:
-            mem.free(buf, out)
+        got = self._records_call([f for f, _ in flats], n * nf, n * per if filters else None, lambda at, out, extra, s: bss_call(
+            self.lib, self.handle, at(0), flats[0][1], [at(1 + j) for j in range(J)], [flats[1 + j][1] for j in range(J)], n, L, out, extra, s))
         res = []
         for i in range(n):
             rec = score_mod.bss_record(got[i * nf:(i + 1) * nf])
@@ -415,6 +381,24 @@ class Context:
             mem.free(*ins, *outs, rec)
         signals = {k: [g[off[j]:off[j + 1]] for j in range(nj)] for k, g in zip(names, got)}
         return signals, [dict(zip(mixing.RECORD_FIELDS, (float(v) for v in r))) for r in recs]
+
+    def _records_call(self, signals, nrec, nextra, call):
+        """What the calls that return records share: the flat float32 `signals` uploaded as one buffer, one float64 output
+        of nrec doubles of records and nextra of the optional output after them (None: not asked for), call(at, out, extra,
+        stream) -> status -- at(k): where signal k begins on the device, out: the records, extra: the optional output or
+        None --, the wait, and all nrec + nextra doubles downloaded; both buffers are freed whatever happened."""
+        mem, nall = Mem(self), nrec + (nextra or 0)
+        base = offsets(len(x) for x in signals)
+        buf = mem.up(np.ascontiguousarray(np.concatenate(signals)))
+        out = mem.empty(nall, np.float64)
+        try:
+            at = lambda k: ctypes.c_void_p(mem.p(buf).value + 4 * base[k])
+            extra = None if nextra is None else ctypes.c_void_p(mem.p(out).value + 8 * nrec)
+            hip.check(call(at, mem.p(out), extra, mem.stream()))
+            self._sync()
+            return np.array(mem.down(out, nall, np.float64), dtype=np.float64)
+        finally:
+            mem.free(buf, out)
 
     def _sync(self):
         """Waits for the work issued on this context's stream (the null stream's copies wait by themselves)."""

@@ -20,7 +20,7 @@
 //     does not show.
 // No floating-point atomics, and no reduction whose shape depends on the batch or on D.  Samples are fetched with single
 // 4-byte loads, and only samples inside a clip are ever fetched.
-#include "nhans_kernels.h"
+#include "score_common.h"
 
 #include <cmath>
 
@@ -164,19 +164,10 @@ __global__ void __launch_bounds__(256) align_pick_kernel(const AlignRun* __restr
     }
 }
 
-__device__ __forceinline__ int align_find_copy(const AlignCopy* __restrict__ jobs, int njobs, long long b) {
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].tile0 <= b) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 // One workgroup: kAlignCutTile samples of one piece.
 __global__ void __launch_bounds__(256) align_cut_kernel(const AlignCopy* __restrict__ jobs, int njobs) {
     const long long b = blockIdx.x;
-    const AlignCopy job = jobs[align_find_copy(jobs, njobs, b)];
+    const AlignCopy job = jobs[find_run<AlignCopy, &AlignCopy::tile0>(jobs, njobs, b)];
     const long long i0 = (b - job.tile0) * kAlignCutTile;
     const int n = (int)(job.n - i0 < kAlignCutTile ? job.n - i0 : kAlignCutTile);
     for (int i = threadIdx.x; i < n; i += 256) job.dst[i0 + i] = job.src[i0 + i];
@@ -199,8 +190,7 @@ void launch_align_pick(const char* kernel, const AlignRun* runs_dev, int nruns, 
 }
 
 void launch_align_cut(const char* kernel, const AlignCopy* jobs_dev, int njobs, long long ntiles, hipStream_t s) {
-    if (njobs <= 0 || ntiles <= 0) return;
-    if (ntiles > 0x7fffffffLL) { note_refusal(kernel); return; }
+    if (!tiles_ok(kernel, njobs, ntiles)) return;
     NHANS_LAUNCH(kernel, align_cut_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, jobs_dev, njobs);
 }
 

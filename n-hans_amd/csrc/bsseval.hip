@@ -29,7 +29,7 @@
 //     tree 128, ..., 1 through LDS; a clip's energy adds its tiles' one after the other, ascending.
 // No floating-point atomics, and no reduction whose shape depends on the batch.  Samples are fetched with single 4-byte
 // loads, and only samples [0, n) of a clip are ever fetched.
-#include "nhans_kernels.h"
+#include "score_common.h"
 
 #include <cmath>
 
@@ -40,18 +40,6 @@ namespace {
 constexpr int kBssMaxM = 2 * kBssMaxL;
 constexpr int kBssCorrWin = kBssCorrTile + kBssMaxL - 1, kBssProjWin = kBssProjTile + kBssMaxL - 1;
 
-template <long long BssRun::*T0>
-__device__ __forceinline__ int bss_find_run(const BssRun* __restrict__ runs, int nruns, long long b) {
-    int lo = 0, hi = nruns - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (runs[mid].*T0 <= b) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ double bss_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
 // One workgroup: one tile of one clip, all three signals staged as doubles with the L - 1 samples after the tile; thread l
 // owns the lags l and l + 256.  The products' left factors s_0[t], s_1[t] are one address for the whole wavefront, the right
 // factors consecutive doubles: no bank conflict.  LDS: 3 x 2,559 doubles = 61,416 bytes, two workgroups per CU.
@@ -59,7 +47,7 @@ __global__ void __launch_bounds__(256) bss_corr_kernel(const BssRun* __restrict_
     __shared__ double sig[3][kBssCorrWin];
     const int tid = threadIdx.x;
     const long long b = blockIdx.x;
-    const BssRun run = runs[bss_find_run<&BssRun::ctile0>(runs, nruns, b)];
+    const BssRun run = runs[find_run<BssRun, &BssRun::ctile0>(runs, nruns, b)];
     const long long t0 = (b - run.ctile0) * kBssCorrTile;
     const int W = kBssCorrTile + L - 1;
     for (int i = tid; i < W; i += 256) {
@@ -127,11 +115,6 @@ __global__ void __launch_bounds__(256) bss_gram_kernel(int L, int J, const doubl
     }
 }
 
-__device__ __forceinline__ double bss_wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = __dadd_rn(v, __shfl_down(v, off));
-    return v;       // (lane 0 holds the sum)
-}
-
 // this thread's part of column k of the factor below the diagonal -- rows k + 1 + l + 256 j < m, j < 4 -- and the diagonal
 __device__ __forceinline__ void bss_column(const double* __restrict__ A, int M, int m, int k, double (&c)[4], double& d) {
     const double* __restrict__ col = A + (size_t)k * M;
@@ -157,7 +140,7 @@ __device__ __forceinline__ void bss_back(const double* __restrict__ A, int M, in
             const int i = k + 1 + tid + 256 * j;
             if (i < m) a = __fma_rn(cur[j], v[i], a);
         }
-        a = bss_wave_sum(a);
+        a = wave_sum(a);
         if ((tid & 63) == 0) red[tid >> 6] = a;
         __syncthreads();
         if (tid == 0) {
@@ -206,7 +189,7 @@ __global__ void __launch_bounds__(256) bss_chol_kernel(int L, int J, const doubl
             const double piv = pan[p * LD + p];
             if (!(fabs(piv) <= 1.79769313486231570e308) || piv <= __dmul_rn(thr, k0 + p < L ? g00 : g11)) {
                 // singular (the same value in every thread: the whole workgroup leaves)
-                const double nan = bss_nan();
+                const double nan = quiet_nan();
                 for (int i = tid; i < M + L; i += 256) { out[i] = nan; if (fout) fout[i] = nan; }
                 if (tid == 0) flag[clip] = 1;
                 return;
@@ -311,7 +294,7 @@ __global__ void __launch_bounds__(256) bss_project_kernel(const BssRun* __restri
     __shared__ double red[6][256];
     const int tid = threadIdx.x, M = J * L;
     const long long b = blockIdx.x;
-    const int ri = bss_find_run<&BssRun::ptile0>(runs, nruns, b);
+    const int ri = find_run<BssRun, &BssRun::ptile0>(runs, nruns, b);
     if (flag[ri]) return;       // (the whole workgroup)
     const BssRun run = runs[ri];
     const long long t0 = (b - run.ptile0) * kBssProjTile, T = run.n + L - 1;
@@ -372,7 +355,7 @@ __global__ void __launch_bounds__(64) bss_finish_kernel(const BssRun* __restrict
     const bool bad = flag[blockIdx.x] != 0;
     if (tid < 6) {
         double a = 0.0;
-        if (bad) a = bss_nan();
+        if (bad) a = quiet_nan();
         else for (long long k = 0; k < run.ptiles; ++k) a = __dadd_rn(a, epart[(size_t)(run.ptile0 + k) * 6 + tid]);
         E[tid] = a;
     }
@@ -381,16 +364,16 @@ __global__ void __launch_bounds__(64) bss_finish_kernel(const BssRun* __restrict
     if (tid < 6) o[3 + tid] = E[tid];
     if (tid == 6) { o[0] = (double)run.n; o[1] = (double)J; o[2] = (double)L; o[12] = bad ? 1.0 : 0.0; o[13] = 0.0; o[14] = 0.0; o[15] = 0.0; }
     // E: 0 E_e, 1 E_tgt, 2 E_int, 3 E_art, 4 E_dist, 5 E_ti
-    if (tid == 7) o[9] = bad ? bss_nan() : bss_db(E[1], E[4]);
-    if (tid == 8) o[10] = bad ? bss_nan() : bss_db(E[1], E[2]);
-    if (tid == 9) o[11] = bad ? bss_nan() : bss_db(E[5], E[3]);
+    if (tid == 7) o[9] = bad ? quiet_nan() : bss_db(E[1], E[4]);
+    if (tid == 8) o[10] = bad ? quiet_nan() : bss_db(E[1], E[2]);
+    if (tid == 9) o[11] = bad ? quiet_nan() : bss_db(E[5], E[3]);
 }
 
 }  // namespace
 
 void launch_bss_corr(const char* kernel, const BssRun* runs_dev, int nruns, long long ntiles, int L, int J, double* part, hipStream_t s) {
-    if (nruns <= 0 || ntiles <= 0) return;
-    if (ntiles > 0x7fffffffLL || L < 1 || L > kBssMaxL || J < 1 || J > 2) { note_refusal(kernel); return; }
+    if (!tiles_ok(kernel, nruns, ntiles)) return;
+    if (L < 1 || L > kBssMaxL || J < 1 || J > 2) { note_refusal(kernel); return; }
     NHANS_LAUNCH(kernel, bss_corr_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, runs_dev, nruns, L, J, part);
 }
 
@@ -416,8 +399,8 @@ void launch_bss_chol(const char* kernel, int nruns, int L, int J, const double* 
 
 void launch_bss_project(const char* kernel, const BssRun* runs_dev, int nruns, long long ntiles, int L, int J, const double* sol,
                         const int* flag, double* epart, hipStream_t s) {
-    if (nruns <= 0 || ntiles <= 0) return;
-    if (ntiles > 0x7fffffffLL || L < 1 || L > kBssMaxL || J < 1 || J > 2) { note_refusal(kernel); return; }
+    if (!tiles_ok(kernel, nruns, ntiles)) return;
+    if (L < 1 || L > kBssMaxL || J < 1 || J > 2) { note_refusal(kernel); return; }
     NHANS_LAUNCH(kernel, bss_project_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, runs_dev, nruns, L, J, sol, flag, epart);
 }
 

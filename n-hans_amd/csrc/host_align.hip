@@ -26,23 +26,18 @@ int64_t nhans_align_common(int64_t ne, int64_t nt, int64_t delay) { return align
 int nhans_align(nhans_ctx* c, const float* est, const int64_t* eoff, const float* tgt, const int64_t* toff, int nclips, int max_lag,
                 double* out, double* corr_out, void* stream) {
     const std::string fn = "nhans_align";
-    if (nclips < 0) return fail(NHANS_EINVAL, fn + ": negative clip count");
-    if (max_lag < 0 || max_lag > kAlignMaxLag)
+    if (nclips >= 0 && (max_lag < 0 || max_lag > kAlignMaxLag))      // (a negative count is refused first, below)
         return fail(NHANS_EINVAL, fn + ": max_lag " + std::to_string(max_lag) + " (0 ... " + std::to_string(kAlignMaxLag) + ")");
-    if (nclips > 0 && (!eoff || !toff || !out))
-        return fail(NHANS_EINVAL, fn + ": null offsets or null output with " + std::to_string(nclips) + " clips to align");
-    int rc = offsets_check(fn, "estimate", eoff, nclips); if (rc) return rc;
-    rc = offsets_check(fn, "target", toff, nclips); if (rc) return rc;
     const int D = max_lag;
-    std::vector<AlignRun> runs((size_t)nclips);
-    for (int i = 0; i < nclips; ++i) {
-        const int64_t ne = eoff[i + 1] - eoff[i], nt = toff[i + 1] - toff[i];
+    std::vector<AlignRun> runs;
+    int rc = pair_clips(fn, "align", est, eoff, tgt, toff, nclips, out, [&](int i, const float* e, const float* t, int64_t ne, int64_t nt) {
         if (ne > kMaxResampleClip || nt > kMaxResampleClip)
             return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(std::max(ne, nt)) + " samples (0 ... 2^31 - 1)");
-        if ((ne > 0 && !est) || (nt > 0 && !tgt))
-            return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(ne > 0 && !est ? ne : nt) + " samples and a null buffer");
-        runs[i] = {ne > 0 ? est + eoff[i] : nullptr, nt > 0 ? tgt + toff[i] : nullptr, (long long)ne, (long long)nt};
-    }
+        if ((ne > 0 && !e) || (nt > 0 && !t)) return null_clip(fn, i, ne > 0 && !e ? ne : nt);
+        runs.push_back({ne > 0 ? e : nullptr, nt > 0 ? t : nullptr, (long long)ne, (long long)nt});
+        return NHANS_OK;
+    });
+    if (rc) return rc;
     Call call(c, stream);
     if (call.rc) return call.rc;
     if (nclips == 0) return call.finish(NHANS_OK);

@@ -31,8 +31,7 @@ int nhans_bss_eval(nhans_ctx* c, const float* est, const int64_t* eoff, const fl
         for (int j = 0; j < J; ++j) n = std::min(n, soff[j][i + 1] - soff[j][i]);
         if (n > kMaxResampleClip)
             return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(n) + " samples (0 ... 2^31 - 1)");
-        if (n > 0 && (!est || !src[0] || (J == 2 && !src[1])))
-            return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(n) + " samples and a null buffer");
+        if (n > 0 && (!est || !src[0] || (J == 2 && !src[1]))) return null_clip(fn, i, n);
         const long long T = n + L - 1;
         runs[i] = {n > 0 ? est + eoff[i] : nullptr, n > 0 ? src[0] + soff[0][i] : nullptr, n > 0 && J == 2 ? src[1] + soff[1][i] : nullptr,
                    (long long)n, 0, (n + kBssCorrTile - 1) / kBssCorrTile, 0, (T + kBssProjTile - 1) / kBssProjTile};

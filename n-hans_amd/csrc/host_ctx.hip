@@ -177,6 +177,24 @@ int offsets_check(const std::string& fn, const char* what, const int64_t* off, i
     return NHANS_OK;
 }
 
+int null_clip(const std::string& fn, int i, int64_t n) {
+    return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(n) + " samples and a null buffer");
+}
+
+int pair_clips(const std::string& fn, const char* verb, const float* est, const int64_t* eoff, const float* tgt, const int64_t* toff,
+               int nclips, const void* out, const PairBody& body) {
+    if (nclips < 0) return fail(NHANS_EINVAL, fn + ": negative clip count");
+    if (nclips > 0 && (!eoff || !toff || !out))
+        return fail(NHANS_EINVAL, fn + ": null offsets or null output with " + std::to_string(nclips) + " clips to " + verb);
+    int rc = offsets_check(fn, "estimate", eoff, nclips); if (rc) return rc;
+    rc = offsets_check(fn, "target", toff, nclips); if (rc) return rc;
+    for (int i = 0; i < nclips; ++i) {
+        rc = body(i, est ? est + eoff[i] : nullptr, tgt ? tgt + toff[i] : nullptr, eoff[i + 1] - eoff[i], toff[i + 1] - toff[i]);
+        if (rc) return rc;
+    }
+    return NHANS_OK;
+}
+
 // ================================================================================================
 extern "C" {
 

@@ -32,6 +32,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <map>
 #include <string>
@@ -235,6 +236,14 @@ constexpr int64_t kMaxResampleClip = ((int64_t)1 << 31) - 1, kNoPushCap = std::n
 int push_check(const char* fn, const char* noun, int i, int64_t cnt, bool en, bool ended, const char* uncond, int64_t max_cnt);
 // the nclips + 1 offsets `off` (`what`: which ones, for the message) do not descend
 int offsets_check(const std::string& fn, const char* what, const int64_t* off, int nclips);
+// What the calls on (est, eoff, tgt, toff, nclips, out) refuse before they look at a clip -- a negative count, null
+// offsets or output (`verb`: what the call does to clips, for the message), descending offsets --, then body(i, e, t, ne,
+// nt) for clip after clip: its first samples in the two buffers (nullptr where the buffer is) and its two lengths.  The
+// body keeps its call's own caps and its run-table line; the first status that is not NHANS_OK ends the walk.
+using PairBody = std::function<int(int i, const float* e, const float* t, int64_t ne, int64_t nt)>;
+int pair_clips(const std::string& fn, const char* verb, const float* est, const int64_t* eoff, const float* tgt, const int64_t* toff,
+               int nclips, const void* out, const PairBody& body);
+int null_clip(const std::string& fn, int i, int64_t n);        // the refusal of clip i: n samples and a null buffer
 
 // ---- host_net.hip ---------------------------------------------------------------------------------
 struct StackBufs {

@@ -9,25 +9,20 @@ namespace {
 // the checks the two calls share and the run table; *frames, *lt, *bt: the totals
 int quality_runs(const std::string& fn, const float* est, const int64_t* eoff, const float* tgt, const int64_t* toff, int nclips,
                  const void* out, std::vector<QualityRun>* runs, long long* frames, long long* lt, long long* bt) {
-    if (nclips < 0) return fail(NHANS_EINVAL, fn + ": negative clip count");
-    if (nclips > 0 && (!eoff || !toff || !out))
-        return fail(NHANS_EINVAL, fn + ": null offsets or null output with " + std::to_string(nclips) + " clips to score");
-    int rc = offsets_check(fn, "estimate", eoff, nclips); if (rc) return rc;
-    rc = offsets_check(fn, "target", toff, nclips); if (rc) return rc;
-    runs->resize((size_t)nclips);
     *frames = *lt = *bt = 0;
-    for (int i = 0; i < nclips; ++i) {
-        const int64_t n = std::min(eoff[i + 1] - eoff[i], toff[i + 1] - toff[i]);
-        if (n > 0 && (!est || !tgt))
-            return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(n) + " samples and a null buffer");
+    const int rc = pair_clips(fn, "score", est, eoff, tgt, toff, nclips, out, [&](int i, const float* e, const float* t, int64_t ne, int64_t nt) {
+        const int64_t n = std::min(ne, nt);
+        if (n > 0 && (!e || !t)) return null_clip(fn, i, n);
         if (n > kMaxResampleClip)
             return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(n) + " samples (0 ... 2^31 - 1)");
         const long long m = quality_frames(n);
-        (*runs)[i] = {n > 0 ? est + eoff[i] : nullptr, n > 0 ? tgt + toff[i] : nullptr, (long long)n, m, *frames, *lt, *bt};
+        runs->push_back({n > 0 ? e : nullptr, n > 0 ? t : nullptr, (long long)n, m, *frames, *lt, *bt});
         *frames += m;
         *lt += (m + kQualityLpcTile - 1) / kQualityLpcTile;
         *bt += (m + kQualityBandTile - 1) / kQualityBandTile;
-    }
+        return NHANS_OK;
+    });
+    if (rc) return rc;
     if (*lt > 0x7fffffffLL || *bt > 0x7fffffffLL) return fail(NHANS_EINVAL, fn + ": too many samples for one call (split it)");
     return NHANS_OK;
 }

@@ -7,23 +7,20 @@ extern "C" {
 int nhans_score_wave(nhans_ctx* c, const float* est, const int64_t* eoff, const float* tgt, const int64_t* toff, int nclips,
                      double* out, double* frames_out, void* stream) {
     const std::string fn = "nhans_score_wave";
-    if (nclips < 0) return fail(NHANS_EINVAL, fn + ": negative clip count");
-    if (nclips > 0 && (!eoff || !toff || !out)) return fail(NHANS_EINVAL, fn + ": null offsets or null output with " + std::to_string(nclips) + " clips to score");
-    int rc = offsets_check(fn, "estimate", eoff, nclips); if (rc) return rc;
-    rc = offsets_check(fn, "target", toff, nclips); if (rc) return rc;
-    std::vector<ScoreRun> runs((size_t)nclips);
+    std::vector<ScoreRun> runs;
     long long tiles = 0, segs = 0, frames = 0, samples = 0;
-    for (int i = 0; i < nclips; ++i) {
-        const int64_t n = std::min(eoff[i + 1] - eoff[i], toff[i + 1] - toff[i]);
-        if (n > 0 && (!est || !tgt))
-            return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(n) + " samples and a null buffer");
+    int rc = pair_clips(fn, "score", est, eoff, tgt, toff, nclips, out, [&](int i, const float* e, const float* t, int64_t ne, int64_t nt) {
+        const int64_t n = std::min(ne, nt);
+        if (n > 0 && (!e || !t)) return null_clip(fn, i, n);
         const int64_t nf = nhans_num_frames(n);
-        runs[i] = {n > 0 ? est + eoff[i] : nullptr, n > 0 ? tgt + toff[i] : nullptr, (long long)n, tiles, segs, frames, (long long)nf};
+        runs.push_back({n > 0 ? e : nullptr, n > 0 ? t : nullptr, (long long)n, tiles, segs, frames, (long long)nf});
         tiles += (n + kScoreTile - 1) / kScoreTile;
         segs += (n + kScoreSegment - 1) / kScoreSegment;
         frames += nf;
         samples += n;
-    }
+        return NHANS_OK;
+    });
+    if (rc) return rc;
     if (tiles > 0x7fffffffLL) return fail(NHANS_EINVAL, fn + ": too many samples for one call (split it)");
     Call call(c, stream);
     if (call.rc) return call.rc;

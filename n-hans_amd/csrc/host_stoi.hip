@@ -48,8 +48,7 @@ int nhans_stoi_resample(nhans_ctx* c, const float* in, const int64_t* inoff, int
         if (outoff[i + 1] - outoff[i] < no)
             return fail(NHANS_EINVAL, fn + ": output room of clip " + std::to_string(i) + " is " + std::to_string(outoff[i + 1] - outoff[i]) +
                                       " samples, " + std::to_string(no) + " needed (nhans_stoi_out_count)");
-        if (n > 0 && (!in || !out))
-            return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(n) + " samples and a null buffer");
+        if (n > 0 && (!in || !out)) return null_clip(fn, i, n);
     }
     Call call(c, stream);
     if (call.rc) return call.rc;
@@ -59,25 +58,22 @@ int nhans_stoi_resample(nhans_ctx* c, const float* in, const int64_t* inoff, int
 int nhans_stoi(nhans_ctx* c, const float* est, const int64_t* eoff, const float* tgt, const int64_t* toff, int nclips, double* out,
                double* segments_out, void* stream) {
     const std::string fn = "nhans_stoi";
-    if (nclips < 0) return fail(NHANS_EINVAL, fn + ": negative clip count");
-    if (nclips > 0 && (!eoff || !toff || !out)) return fail(NHANS_EINVAL, fn + ": null offsets or null output with " + std::to_string(nclips) + " clips to score");
-    int rc = offsets_check(fn, "estimate", eoff, nclips); if (rc) return rc;
-    rc = offsets_check(fn, "target", toff, nclips); if (rc) return rc;
-    std::vector<StoiRun> runs((size_t)nclips);
+    std::vector<StoiRun> runs;
     long long frames = 0, rows = 0, segs = 0, pt = 0, bt = 0, st = 0;
-    for (int i = 0; i < nclips; ++i) {
-        const int64_t n = std::min(eoff[i + 1] - eoff[i], toff[i + 1] - toff[i]);
-        if (n > 0 && (!est || !tgt))
-            return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(n) + " samples and a null buffer");
+    int rc = pair_clips(fn, "score", est, eoff, tgt, toff, nclips, out, [&](int i, const float* e, const float* t, int64_t ne, int64_t nt) {
+        const int64_t n = std::min(ne, nt);
+        if (n > 0 && (!e || !t)) return null_clip(fn, i, n);
         const long long m0 = stoi_frames(n);
         if (m0 > 0x7fffffffLL) return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has too many samples for one call (split it)");
         const long long nb = std::max(m0 - 1, 0LL), ns = std::max(m0 - kStoiSegment, 0LL);
-        runs[i] = {n > 0 ? est + eoff[i] : nullptr, n > 0 ? tgt + toff[i] : nullptr, (long long)n, m0, frames, rows, segs, pt, bt, st};
+        runs.push_back({n > 0 ? e : nullptr, n > 0 ? t : nullptr, (long long)n, m0, frames, rows, segs, pt, bt, st});
         frames += m0; rows += nb; segs += ns;
         pt += (m0 + kStoiPowerTile - 1) / kStoiPowerTile;
         bt += (nb + kStoiBandTile - 1) / kStoiBandTile;
         st += (ns + kStoiSegTile - 1) / kStoiSegTile;
-    }
+        return NHANS_OK;
+    });
+    if (rc) return rc;
     if (pt > 0x7fffffffLL) return fail(NHANS_EINVAL, fn + ": too many samples for one call (split it)");
     Call call(c, stream);
     if (call.rc) return call.rc;

@@ -10,16 +10,11 @@
 // compensation, SN/apply.py write_snc_outputs:
 //     g = (Sd / Sr) / 20,   w_h = float32(min(max(g, 0), wmax)),   0 where Sr == 0 or g is NaN,
 // every sum formed in ascending hop order, whether a term comes from the carried state or from this push.
-#include "nhans_kernels.h"
+#include "score_common.h"
 
 namespace nhans {
 
 namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = __dadd_rn(v, __shfl_down(v, off));
-    return v;       // (lane 0 holds the sum)
-}
 
 // The powers of one hop of cnt <= 160 samples at d / m, by one whole wavefront; the result is lane 0's.
 __device__ __forceinline__ void hop_powers(const float* __restrict__ d, const float* __restrict__ m, int cnt, int lane,

@@ -22,7 +22,7 @@
 // mix_finish.  No atomics.  Samples move through LDS: 16-byte loads and stores where the tile's address allows them,
 // single ones for the head and tail (and for a noise that wraps), so an odd offset changes how a sample is fetched and
 // nothing about what is computed.
-#include "nhans_kernels.h"
+#include "score_common.h"
 
 namespace nhans {
 
@@ -108,16 +108,6 @@ __global__ void __launch_bounds__(256) mix_power_kernel(const MixChain* __restri
     if (tid == 0) pw[blockIdx.x] = S / (double)c.n;
 }
 
-// the job a workgroup's tile belongs to: the last one whose tile0 is <= b
-__device__ __forceinline__ int find_job(const MixJob* __restrict__ jobs, int njobs, long long b) {
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].tile0 <= b) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ double snr_gain(double p_speech, double p_noise, double f) {
     return p_noise == 0.0 ? 1.0 : sqrt(__dmul_rn(p_speech / p_noise, f));
 }
@@ -165,7 +155,7 @@ __global__ void __launch_bounds__(256) mix_combine_kernel(const MixJob* __restri
     __shared__ float ss[kMixTile], sa[kMixTile], sb[kMixTile], wmax[4];
     const int tid = threadIdx.x;
     const long long b = blockIdx.x;
-    const int ji = find_job(jobs, njobs, b);
+    const int ji = find_run<MixJob, &MixJob::tile0>(jobs, njobs, b);
     const MixJob job = jobs[ji];
     const long long s0 = (b - job.tile0) * kMixTile, left = job.n - s0;
     const int cnt = (int)(left < kMixTile ? left : kMixTile);
@@ -197,7 +187,7 @@ __global__ void __launch_bounds__(256) mix_finish_kernel(const MixJob* __restric
     __shared__ float ss[kMixTile], sa[kMixTile], sb[kMixTile], so[kMixTile], wmax[4];
     const int tid = threadIdx.x;
     const long long b = blockIdx.x;
-    const int ji = find_job(jobs, njobs, b);
+    const int ji = find_run<MixJob, &MixJob::tile0>(jobs, njobs, b);
     const MixJob job = jobs[ji];
     const long long s0 = (b - job.tile0) * kMixTile, left = job.n - s0;
     const int cnt = (int)(left < kMixTile ? left : kMixTile);
@@ -247,15 +237,13 @@ void launch_mix_power(const char* kernel, const MixChain* chains_dev, int nchain
 
 void launch_mix_combine(const char* kernel, const MixJob* jobs_dev, int njobs, long long ntiles, const double* pw, float* mixture,
                         float* peaks, double* rec, hipStream_t s) {
-    if (njobs <= 0 || ntiles <= 0) return;
-    if (ntiles > 0x7fffffffLL) { note_refusal(kernel); return; }
+    if (!tiles_ok(kernel, njobs, ntiles)) return;
     NHANS_LAUNCH(kernel, mix_combine_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, jobs_dev, njobs, pw, mixture, peaks, rec);
 }
 
 void launch_mix_finish(const char* kernel, const MixJob* jobs_dev, int njobs, long long ntiles, const double* pw, const float* peaks,
                        float* mixture, float* target, float* keep, float* drop, double* rec, hipStream_t s) {
-    if (njobs <= 0 || ntiles <= 0) return;
-    if (ntiles > 0x7fffffffLL) { note_refusal(kernel); return; }
+    if (!tiles_ok(kernel, njobs, ntiles)) return;
     NHANS_LAUNCH(kernel, mix_finish_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, jobs_dev, njobs, pw, peaks, mixture, target, keep,
                  drop, rec);
 }

@@ -8,7 +8,7 @@
 //                      ascending of the two windowed samples, each windowed by one __dmul_rn as it is read.  Then one lane
 //                      per (frame, signal) runs the Levinson-Durbin recursion and the cepstrum recursion, one lane per
 //                      (frame, den | num) a quadratic form, one lane per frame the distance and the two clamped values.
-//   2. quality_bands   a wavefront per (frame, signal): the 512-point transform (stoi_fft.h) of the windowed frame, |X_k| for
+//   2. quality_bands   a wavefront per (frame, signal): the 512-point transform (fft512.h) of the windowed frame, |X_k| for
 //                      k <= 256, then one lane per band the band sum over k ascending, one lane per band s_j and g_j,
 //                      lane 0 the weighted mean over j ascending.  Two transforms a frame, not one of x_w + i y_w
 //                      separated by symmetry: the separated spectrum of an all-zero target is zero only up to the
@@ -29,8 +29,8 @@
 // No floating-point atomics and no reduction whose shape depends on the batch: a record and every per-frame value have the
 // same bits alone or in any batch, at any offset, on every run.  Samples are fetched with single 4-byte loads and only
 // inside [0, n) of a clip.
-#include "nhans_kernels.h"
-#include "stoi_fft.h"
+#include "score_common.h"
+#include "fft512.h"
 
 #include <algorithm>
 #include <cmath>
@@ -46,20 +46,7 @@ static_assert(kEstAt % 32 == 17, "the estimate's span sits 17 (mod 32) doubles a
 static_assert(kQualityLpcTile * 2 * QP1 <= 256, "one thread per autocorrelation chain");
 static_assert(kQualityFft == 512 && kQualityBandTile == 2 && kQualityMaxBands <= 64, "the band launch's shape");
 
-__device__ __forceinline__ double q_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 __device__ __forceinline__ bool q_pos_finite(double v) { return v > 0.0 && v < __longlong_as_double(0x7ff0000000000000LL); }
-
-// the run a workgroup belongs to: the last one whose first workgroup (member T0, ascending) is <= b; clips without a
-// workgroup share the T0 of the clip after them and are never the last
-template <long long QualityRun::*T0>
-__device__ __forceinline__ int find_run(const QualityRun* __restrict__ runs, int nruns, long long b) {
-    int lo = 0, hi = nruns - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (runs[mid].*T0 <= b) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 __global__ void __launch_bounds__(256) quality_lpc_kernel(const QualityRun* __restrict__ runs, int nruns, const double* __restrict__ tab,
                                                           double* __restrict__ vals, double* __restrict__ lpc_out) {
@@ -73,7 +60,7 @@ __global__ void __launch_bounds__(256) quality_lpc_kernel(const QualityRun* __re
     __shared__ int ok[kQualityLpcTile][2];
     const int tid = threadIdx.x;
     const long long b = blockIdx.x;
-    const QualityRun run = runs[find_run<&QualityRun::ltile0>(runs, nruns, b)];
+    const QualityRun run = runs[find_run<QualityRun, &QualityRun::ltile0>(runs, nruns, b)];
     const long long f0 = (b - run.ltile0) * kQualityLpcTile;
     const int nf = (int)(run.frames - f0 < kQualityLpcTile ? run.frames - f0 : kQualityLpcTile);     // >= 1
     const int span = QN + (nf - 1) * QH;                    // f0 * 120 + span <= n
@@ -123,7 +110,7 @@ __global__ void __launch_bounds__(256) quality_lpc_kernel(const QualityRun* __re
                 cc[m] = __dsub_rn(-aa[m], s);
             }
         } else {
-            for (int m = 1; m <= QP; ++m) { aa[m] = q_nan(); cc[m] = q_nan(); }
+            for (int m = 1; m <= QP; ++m) { aa[m] = quiet_nan(); cc[m] = quiet_nan(); }
         }
         ok[f][sg] = good ? 1 : 0;
     }
@@ -151,7 +138,7 @@ __global__ void __launch_bounds__(256) quality_lpc_kernel(const QualityRun* __re
             const double t = __dsub_rn(cep[f][0][m], cep[f][1][m]);
             dc2 = __fma_rn(t, t, dc2);
         }
-        double llr = q_nan(), cd = q_nan();
+        double llr = quiet_nan(), cd = quiet_nan();
         if (good) {
             llr = __dadd_rn(fmin(fmax(log(__ddiv_rn(num, den)), 0.0), kQualityLlrMax), 0.0);
             cd = __dadd_rn(fmin(fmax(__dmul_rn(kQualityCdScale, __dsqrt_rn(__dmul_rn(2.0, dc2))), 0.0), kQualityCdMax), 0.0);
@@ -171,25 +158,22 @@ __global__ void __launch_bounds__(256) quality_lpc_kernel(const QualityRun* __re
 }
 
 // One workgroup: kQualityBandTile frames of one clip, a wavefront per (frame, signal): waves 0 and 1 the target and the
-// estimate of the first, waves 2 and 3 of the second.  A wavefront without a frame runs the same barriers on zeros.
+// estimate of the first, waves 2 and 3 of the second.  A wavefront without a frame runs the transform on zeros: its
+// barriers are the workgroup's.
 __global__ void __launch_bounds__(256) quality_bands_kernel(const QualityRun* __restrict__ runs, int nruns, const double* __restrict__ tab,
                                                             const double* __restrict__ W, const int* __restrict__ span, int K,
                                                             double* __restrict__ vals) {
     __shared__ double tw[2 * kQualityFft];                  // cos, then -sin
-    __shared__ double buf[2 * kQualityBandTile][2][kStoiFftBuf];
+    __shared__ double buf[2 * kQualityBandTile][2][kFft512Buf];
     __shared__ double mag[2 * kQualityBandTile][kQualityBins + 1];
     __shared__ double bs[kQualityBandTile][2][kQualityMaxBands];     // X_j and Y_j, then (the same lane, in place) g_j and 35 - s_j
     const int tid = threadIdx.x, j = tid & 63, wave = tid >> 6, fr = wave >> 1, sg = wave & 1;
     const long long b = blockIdx.x;
-    const QualityRun run = runs[find_run<&QualityRun::btile0>(runs, nruns, b)];
+    const QualityRun run = runs[find_run<QualityRun, &QualityRun::btile0>(runs, nruns, b)];
     const long long f = (b - run.btile0) * kQualityBandTile + fr;
     const bool active = f < run.frames;
     for (int t = tid; t < 2 * kQualityFft; t += 256) tw[t] = tab[QN + t];
-    const double* tc = tw;
-    const double* ts = tw + kQualityFft;
-    double* re = buf[wave][0];
-    double* im = buf[wave][1];
-    StoiC v[8];
+    Fft512C v[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) v[q] = {0.0, 0.0};
     if (active) {
@@ -200,17 +184,7 @@ __global__ void __launch_bounds__(256) quality_bands_kernel(const QualityRun* __
             if (i < QN) v[q].r = __dmul_rn((double)x[i], tab[i]);
         }
     }
-    stoi_fft_butterfly<1>(j, tc, ts, v);
-    stoi_fft_store<1>(j, v, re, im);
-    __syncthreads();
-    stoi_fft_load(j, re, im, v);
-    __syncthreads();
-    stoi_fft_butterfly<8>(j, tc, ts, v);
-    stoi_fft_store<8>(j, v, re, im);
-    __syncthreads();
-    stoi_fft_load(j, re, im, v);
-    __syncthreads();
-    stoi_fft_butterfly<64>(j, tc, ts, v);
+    fft512_wave(j, tw, tw + kQualityFft, v, buf[wave][0], buf[wave][1]);
     // thread j holds bins j + 64 q; the bands read bins 0 ... 256
 #pragma unroll
     for (int q = 0; q < 4; ++q) mag[wave][j + 64 * q] = __dsqrt_rn(__fma_rn(v[q].i, v[q].i, __dmul_rn(v[q].r, v[q].r)));
@@ -245,7 +219,7 @@ __global__ void __launch_bounds__(256) quality_bands_kernel(const QualityRun* __
             S = __fma_rn(bs[fr][0][q], bs[fr][1][q], S);
         }
         // 35 less the weighted mean of the deficits: equal signals give 35 exactly
-        vals[(size_t)(run.frame0 + f) * 3 + 2] = G == 0.0 ? q_nan() : __dsub_rn(kQualitySnrMax, __ddiv_rn(S, G));
+        vals[(size_t)(run.frame0 + f) * 3 + 2] = G == 0.0 ? quiet_nan() : __dsub_rn(kQualitySnrMax, __ddiv_rn(S, G));
     }
 }
 
@@ -309,7 +283,7 @@ __global__ void __launch_bounds__(256) quality_finish_kernel(const QualityRun* _
     }
     double* o = rec + (size_t)blockIdx.x * kQualityFields;
     if (tid < 2) {
-        double m = q_nan(), m95 = q_nan();
+        double m = quiet_nan(), m95 = quiet_nan();
         if (Mk > 0) {
             const double t = thr[tid];
             double a = 0.0;
@@ -324,7 +298,7 @@ __global__ void __launch_bounds__(256) quality_finish_kernel(const QualityRun* _
     }
     if (tid == 2) {
         o[0] = (double)run.n; o[1] = (double)M; o[2] = (double)Mk; o[3] = (double)kept[2];
-        o[8] = kept[2] > 0 ? __ddiv_rn(sum[2], (double)kept[2]) : q_nan();
+        o[8] = kept[2] > 0 ? __ddiv_rn(sum[2], (double)kept[2]) : quiet_nan();
         for (int i = 9; i < kQualityFields; ++i) o[i] = 0.0;
     }
 }
@@ -337,11 +311,7 @@ double q_mel_to_hz(double m) { return 700.0 * (std::pow(10.0, m / 2595.0) - 1.0)
 void quality_table(double* tab) {
     const double pi = 3.14159265358979323846;
     for (int i = 0; i < kQualityFrame; ++i) tab[i] = 0.5 - 0.5 * std::cos(2.0 * pi * (double)(i + 1) / (double)(kQualityFrame + 1));
-    for (int t = 0; t < kQualityFft; ++t) {
-        const double a = 2.0 * pi * (double)t / (double)kQualityFft;
-        tab[kQualityFrame + t] = std::cos(a);
-        tab[kQualityFrame + kQualityFft + t] = -std::sin(a);
-    }
+    fft512_twiddles(tab + kQualityFrame);
 }
 
 // kQualityBands triangles on the HTK mel scale between 0 and 8000 Hz over the bins 31.25 k: the construction of
@@ -361,15 +331,14 @@ void quality_default_bands(double* w) {
 
 void launch_quality_lpc(const char* kernel, const QualityRun* runs_dev, int nruns, long long ntiles, const double* tab, double* vals,
                         double* lpc_out, hipStream_t s) {
-    if (nruns <= 0 || ntiles <= 0) return;
-    if (ntiles > 0x7fffffffLL) { note_refusal(kernel); return; }
+    if (!tiles_ok(kernel, nruns, ntiles)) return;
     NHANS_LAUNCH(kernel, quality_lpc_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, runs_dev, nruns, tab, vals, lpc_out);
 }
 
 void launch_quality_bands(const char* kernel, const QualityRun* runs_dev, int nruns, long long ntiles, const double* tab,
                           const double* bands, const int* span, int nbands, double* vals, hipStream_t s) {
-    if (nruns <= 0 || ntiles <= 0) return;
-    if (ntiles > 0x7fffffffLL || nbands < 1 || nbands > kQualityMaxBands) { note_refusal(kernel); return; }
+    if (!tiles_ok(kernel, nruns, ntiles)) return;
+    if (nbands < 1 || nbands > kQualityMaxBands) { note_refusal(kernel); return; }
     NHANS_LAUNCH(kernel, quality_bands_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, runs_dev, nruns, tab, bands, span, nbands, vals);
 }
 

@@ -33,7 +33,7 @@
 // No floating-point atomics, and no reduction whose shape depends on the batch.  The samples of a tile come in through
 // LDS: 16-byte loads where the tile's address allows them and single loads for the head and tail where it does not, so
 // an odd offset changes how a sample is fetched and nothing about where it is added.
-#include "nhans_kernels.h"
+#include "score_common.h"
 
 namespace nhans {
 
@@ -45,11 +45,6 @@ constexpr int kSeg = kScoreSegment, kSegsPerTile = kScoreTile / kScoreSegment;  
 __device__ __forceinline__ double group_sum(double v) {
     for (int off = 8; off > 0; off >>= 1) v = __dadd_rn(v, __shfl_down(v, off, 16));
     return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = __dadd_rn(v, __shfl_down(v, off));
-    return v;       // (lane 0 holds the sum)
 }
 
 // cnt <= kScoreTile samples at src -> dst (LDS), by the whole workgroup
@@ -68,17 +63,6 @@ __device__ __forceinline__ void stage_tile(const float* __restrict__ src, int cn
     if (tid < cnt - done) dst[done + tid] = src[done + tid];
 }
 
-// the run a workgroup's tile belongs to: the last one whose tile0 is <= b (tile0 ascending; clips without a sample share
-// the tile0 of the clip after them and are never the last)
-__device__ __forceinline__ int find_run(const ScoreRun* __restrict__ runs, int nruns, long long b) {
-    int lo = 0, hi = nruns - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (runs[mid].tile0 <= b) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 // PASS 1: See, Stt, Set, Sdd of a tile -> part[tile][4], and Pt, Pd of its segments -> segs[segment][2].
 // PASS 2: Srr of a tile -> part[tile][0], alpha read from the clip's record.
 template <int PASS>
@@ -88,7 +72,7 @@ __global__ void __launch_bounds__(256) score_tiles_kernel(const ScoreRun* __rest
     __shared__ double sums[4][kSegsPerTile];
     const int tid = threadIdx.x;
     const long long b = blockIdx.x;
-    const int ri = find_run(runs, nruns, b);
+    const int ri = find_run<ScoreRun, &ScoreRun::tile0>(runs, nruns, b);
     const ScoreRun run = runs[ri];
     const long long s0 = (b - run.tile0) * kScoreTile;
     const long long left = run.n - s0;
@@ -181,7 +165,7 @@ __global__ void __launch_bounds__(256) score_finish_kernel(const ScoreRun* __res
             for (int j = 1; j < 5; ++j) { pt = __dadd_rn(pt, p[2 * j]); pd = __dadd_rn(pd, p[2 * j + 1]); }
             double v;
             bool skip = false;
-            if (pt == 0.0) { skip = true; v = __longlong_as_double(0x7ff8000000000000LL); }
+            if (pt == 0.0) { skip = true; v = quiet_nan(); }
             else if (pd == 0.0) v = 35.0;
             else {
                 v = ten_log10(pt / pd);
@@ -206,7 +190,7 @@ __global__ void __launch_bounds__(256) score_finish_kernel(const ScoreRun* __res
         __syncthreads();
     }
     if (tid == 0) {
-        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+        const double nan = quiet_nan();
         const long long counted = run.frames - skipped;
         const double See = tot[0], Stt = tot[1], Set = tot[2], Sdd = tot[3];
         double* o = rec + (size_t)blockIdx.x * kScoreFields;
@@ -248,12 +232,8 @@ __global__ void __launch_bounds__(256) score_rows_kernel(const ScoreRowRun* __re
                                                          double* __restrict__ frames_out) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long b = blockIdx.x;
-    int lo = 0, hi = nruns - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (runs[mid].tile0 <= b) lo = mid; else hi = mid - 1;
-    }
-    const ScoreRowRun run = runs[lo];
+    const int ri = find_run<ScoreRowRun, &ScoreRowRun::tile0>(runs, nruns, b);
+    const ScoreRowRun run = runs[ri];
     const long long row0 = (b - run.tile0) * kScoreRowTile;
     const long long left = run.frames - row0;
     const int nr = (int)(left < kScoreRowTile ? left : kScoreRowTile);
@@ -304,7 +284,7 @@ __global__ void __launch_bounds__(256) score_rows_finish_kernel(const ScoreRowRu
         __syncthreads();
     }
     double* o = rec + (size_t)blockIdx.x * kScoreRowFields;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const double nan = quiet_nan();
     if (tid < 2) o[1 + tid] = run.frames > 0 ? a / (double)run.frames : nan;
     if (tid == 2) o[0] = (double)run.frames;
     if (tid >= 3 && tid < kScoreRowFields) o[tid] = 0.0;
@@ -314,8 +294,7 @@ __global__ void __launch_bounds__(256) score_rows_finish_kernel(const ScoreRowRu
 
 void launch_score_tiles(const char* kernel, int pass, const ScoreRun* runs_dev, int nruns, long long ntiles, double* part,
                         double* segs, const double* rec, hipStream_t s) {
-    if (nruns <= 0 || ntiles <= 0) return;
-    if (ntiles > 0x7fffffffLL) { note_refusal(kernel); return; }
+    if (!tiles_ok(kernel, nruns, ntiles)) return;
     if (pass == 1)
         NHANS_LAUNCH(kernel, score_tiles_kernel<1>, dim3((unsigned)ntiles), dim3(256), 0, s, runs_dev, nruns, part, segs, rec);
     else
@@ -335,8 +314,7 @@ void launch_score_sisdr(const char* kernel, const ScoreRun* runs_dev, int nruns,
 
 void launch_score_rows(const char* kernel, const ScoreRowRun* runs_dev, int nruns, long long ntiles, double* vals,
                        double* frames_out, hipStream_t s) {
-    if (nruns <= 0 || ntiles <= 0) return;
-    if (ntiles > 0x7fffffffLL) { note_refusal(kernel); return; }
+    if (!tiles_ok(kernel, nruns, ntiles)) return;
     NHANS_LAUNCH(kernel, score_rows_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, runs_dev, nruns, vals, frames_out);
 }
 

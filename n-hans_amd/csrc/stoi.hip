@@ -8,7 +8,7 @@
 //   3. stoi_bands     per analysis frame q < Mk - 1 and signal: the 256 samples [128 q, 128 q + 256) of the kept windowed
 //                     frames overlap-added at hop 128 -- kept frame q plus kept frame q - 1 (first half) or q + 1 (second
 //                     half); the joined signal is never stored --, windowed again, zero-padded to 512 and transformed
-//                     (stoi_fft.h), then B[j][q] = sqrt(sum_{k in band j} |X_q(k)|^2) for the 15 third-octave bands.
+//                     (fft512.h), then B[j][q] = sqrt(sum_{k in band j} |X_q(k)|^2) for the 15 third-octave bands.
 //   4. stoi_segments  per segment s < Mk - 30 (columns s ... s + 29 of both band tensors): d_s and e_s.
 //   5. stoi_finish    per clip: stoi = (sum_s d_s) / S, estoi likewise; NaN where S == 0.
 //
@@ -25,8 +25,8 @@
 //     divide once.
 // No floating-point atomics, and no reduction whose shape depends on the batch.  Samples are fetched with single 4-byte
 // loads, so an odd offset changes nothing.
-#include "nhans_kernels.h"
-#include "stoi_fft.h"
+#include "score_common.h"
+#include "fft512.h"
 
 #include <cmath>
 
@@ -41,27 +41,10 @@ constexpr double kStoiRange = 1e-4;                         // 40 dB
 // third-octave bands from 150 Hz as bins [lo, hi) of the 512-point transform at 10 kHz: band j is [kBandEdge[j], kBandEdge[j + 1])
 __constant__ int kBandEdge[kStoiBands + 1] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219};
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = __dadd_rn(v, __shfl_down(v, off));
-    return v;       // (lane 0 holds the sum)
-}
-
 // the sum over the 16 lanes of a segment's group, in every one of them
 __device__ __forceinline__ double group_all(double v) {
     for (int off = 8; off > 0; off >>= 1) v = __dadd_rn(v, __shfl_xor(v, off, 16));
     return v;
-}
-
-// the run a workgroup belongs to: the last one whose first workgroup (member T0, ascending) is <= b; clips without a
-// workgroup share the T0 of the clip after them and are never the last
-template <long long StoiRun::*T0>
-__device__ __forceinline__ int find_run(const StoiRun* __restrict__ runs, int nruns, long long b) {
-    int lo = 0, hi = nruns - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (runs[mid].*T0 <= b) lo = mid; else hi = mid - 1;
-    }
-    return lo;
 }
 
 // One wavefront per frame of the target.
@@ -69,7 +52,7 @@ __global__ void __launch_bounds__(256) stoi_power_kernel(const StoiRun* __restri
                                                          double* __restrict__ power) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long b = blockIdx.x;
-    const StoiRun run = runs[find_run<&StoiRun::ptile0>(runs, nruns, b)];
+    const StoiRun run = runs[find_run<StoiRun, &StoiRun::ptile0>(runs, nruns, b)];
     const long long m = (b - run.ptile0) * kStoiPowerTile + wave;
     if (m >= run.frames) return;
     const float* __restrict__ x = run.tgt + m * kStoiHop;
@@ -132,24 +115,22 @@ __device__ __forceinline__ double analysis_sample(const float* __restrict__ x, c
 }
 
 // One workgroup: kStoiBandTile analysis frames of one clip, a wavefront per (frame, signal): waves 0 and 1 the target and
-// the estimate of the first, waves 2 and 3 of the second.  A wavefront without a frame runs the same barriers on zeros.
+// the estimate of the first, waves 2 and 3 of the second.  A wavefront without a frame runs the transform on zeros: its
+// barriers are the workgroup's.
 __global__ void __launch_bounds__(256) stoi_bands_kernel(const StoiRun* __restrict__ runs, int nruns, const double* __restrict__ tab,
                                                          const int* __restrict__ kept, const long long* __restrict__ nkept,
                                                          double* __restrict__ bands, long long rows) {
     __shared__ double tw[2 * kStoiFft];                     // cos, then -sin
-    __shared__ double buf[4][2][kStoiFftBuf];
+    __shared__ double buf[4][2][kFft512Buf];
     const int tid = threadIdx.x, j = tid & 63, wave = tid >> 6, sig = wave & 1;
     const long long b = blockIdx.x;
-    const int ri = find_run<&StoiRun::btile0>(runs, nruns, b);
+    const int ri = find_run<StoiRun, &StoiRun::btile0>(runs, nruns, b);
     const StoiRun run = runs[ri];
     const long long q = (b - run.btile0) * kStoiBandTile + (wave >> 1);
     const bool active = q < nkept[ri] - 1;
     for (int t = tid; t < 2 * kStoiFft; t += 256) tw[t] = tab[kStoiFrame + t];
-    const double* tc = tw;
-    const double* ts = tw + kStoiFft;
     double* re = buf[wave][0];
-    double* im = buf[wave][1];
-    StoiC v[8];
+    Fft512C v[8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) v[r] = {0.0, 0.0};
     if (active) {
@@ -158,17 +139,7 @@ __global__ void __launch_bounds__(256) stoi_bands_kernel(const StoiRun* __restri
 #pragma unroll
         for (int r = 0; r < kStoiFrame / 64; ++r) v[r].r = analysis_sample(x, kp, q, j + 64 * r, tab);
     }
-    stoi_fft_butterfly<1>(j, tc, ts, v);
-    stoi_fft_store<1>(j, v, re, im);
-    __syncthreads();
-    stoi_fft_load(j, re, im, v);
-    __syncthreads();
-    stoi_fft_butterfly<8>(j, tc, ts, v);
-    stoi_fft_store<8>(j, v, re, im);
-    __syncthreads();
-    stoi_fft_load(j, re, im, v);
-    __syncthreads();
-    stoi_fft_butterfly<64>(j, tc, ts, v);
+    fft512_wave(j, tw, tw + kStoiFft, v, re, buf[wave][1]);
     // thread j holds bins j + 64 r; the bands end at bin 218
 #pragma unroll
     for (int r = 0; r < 4; ++r) re[j + 64 * r] = __fma_rn(v[r].i, v[r].i, __dmul_rn(v[r].r, v[r].r));
@@ -187,7 +158,7 @@ __global__ void __launch_bounds__(256) stoi_segments_kernel(const StoiRun* __res
     constexpr int N = kStoiSegment;
     const int tid = threadIdx.x, g = tid >> 4, l = tid & 15;
     const long long b = blockIdx.x;
-    const int ri = find_run<&StoiRun::stile0>(runs, nruns, b);
+    const int ri = find_run<StoiRun, &StoiRun::stile0>(runs, nruns, b);
     const StoiRun run = runs[ri];
     const long long s = (b - run.stile0) * kStoiSegTile + g;
     if (s >= nkept[ri] - N) return;             // (the whole group: no barrier in this kernel)
@@ -265,7 +236,7 @@ __global__ void __launch_bounds__(256) stoi_finish_kernel(const StoiRun* __restr
         __syncthreads();
     }
     double* o = rec + (size_t)blockIdx.x * kStoiFields;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const double nan = quiet_nan();
     if (tid < 2) o[4 + tid] = S > 0 ? a / (double)S : nan;
     if (tid == 2) { o[0] = (double)run.n; o[1] = (double)run.frames; o[2] = (double)mk; o[3] = (double)S; o[6] = 0.0; o[7] = 0.0; }
 }
@@ -275,17 +246,12 @@ __global__ void __launch_bounds__(256) stoi_finish_kernel(const StoiRun* __restr
 void stoi_table(double* tab) {
     const double pi = 3.14159265358979323846;
     for (int i = 0; i < kStoiFrame; ++i) tab[i] = 0.5 * (1.0 - std::cos(2.0 * pi * (double)(i + 1) / (double)(kStoiFrame + 1)));
-    for (int t = 0; t < kStoiFft; ++t) {
-        const double a = 2.0 * pi * (double)t / (double)kStoiFft;
-        tab[kStoiFrame + t] = std::cos(a);
-        tab[kStoiFrame + kStoiFft + t] = -std::sin(a);
-    }
+    fft512_twiddles(tab + kStoiFrame);
 }
 
 void launch_stoi_power(const char* kernel, const StoiRun* runs_dev, int nruns, long long ntiles, const double* tab, double* power,
                        hipStream_t s) {
-    if (nruns <= 0 || ntiles <= 0) return;
-    if (ntiles > 0x7fffffffLL) { note_refusal(kernel); return; }
+    if (!tiles_ok(kernel, nruns, ntiles)) return;
     NHANS_LAUNCH(kernel, stoi_power_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, runs_dev, nruns, tab, power);
 }
 
@@ -297,15 +263,13 @@ void launch_stoi_keep(const char* kernel, const StoiRun* runs_dev, int nruns, co
 
 void launch_stoi_bands(const char* kernel, const StoiRun* runs_dev, int nruns, long long ntiles, const double* tab, const int* kept,
                        const long long* nkept, double* bands, long long rows, hipStream_t s) {
-    if (nruns <= 0 || ntiles <= 0) return;
-    if (ntiles > 0x7fffffffLL) { note_refusal(kernel); return; }
+    if (!tiles_ok(kernel, nruns, ntiles)) return;
     NHANS_LAUNCH(kernel, stoi_bands_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, runs_dev, nruns, tab, kept, nkept, bands, rows);
 }
 
 void launch_stoi_segments(const char* kernel, const StoiRun* runs_dev, int nruns, long long ntiles, const long long* nkept,
                           const double* bands, long long rows, double* segs, double* segs_out, hipStream_t s) {
-    if (nruns <= 0 || ntiles <= 0) return;
-    if (ntiles > 0x7fffffffLL) { note_refusal(kernel); return; }
+    if (!tiles_ok(kernel, nruns, ntiles)) return;
     NHANS_LAUNCH(kernel, stoi_segments_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, runs_dev, nruns, nkept, bands, rows, segs,
                  segs_out);
 }

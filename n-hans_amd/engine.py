@@ -8,6 +8,17 @@ import torch
 from . import context, fold, hip, score as score_mod, spec, weights as weights_mod
 
 
+def _pair_check(who, est_t, est_off, tgt_t, tgt_off):
+    """What the *_device methods (`who`) on estimate / target pairs ask of their arguments -> the number of pairs."""
+    n = len(est_off) - 1
+    if len(tgt_off) - 1 != n:
+        raise ValueError("%s: one target per estimate" % who)
+    for t in (est_t, tgt_t):
+        if t.dtype != torch.float32 or t.dim() != 1:
+            raise ValueError("%s: flat float32 tensors" % who)
+    return n
+
+
 class Engine(context.Context):
     """kind: 'denoiser' | 'separator'.  weights: checkpoint dict (name -> float32 array) or None for
     the seeded synthetic weights.  Conditioning order everywhere is (a, b) = resnet_block argument
@@ -154,12 +165,7 @@ class Engine(context.Context):
         tgt_t / tgt_off, over their common prefix -> device tensor float64 [n, hip.SCORE_FIELDS] (score.FIELDS names the
         columns); per_frame=True: -> (that, float64 [sum frames, 3] whose column 0 holds each frame's clamped segmental
         value, NaN where the frame was skipped; columns 1 - 2 are score_rows' and stay as they were allocated: NaN)."""
-        n = len(est_off) - 1
-        if len(tgt_off) - 1 != n:
-            raise ValueError("score_device: one target per estimate")
-        for t in (est_t, tgt_t):
-            if t.dtype != torch.float32 or t.dim() != 1:
-                raise ValueError("score_device: flat float32 tensors")
+        n = _pair_check("score_device", est_t, est_off, tgt_t, tgt_off)
         out = torch.empty((n, hip.SCORE_FIELDS), dtype=torch.float64, device=self.device)
         fr = None
         if per_frame:
@@ -193,12 +199,7 @@ class Engine(context.Context):
         flat float32, within max_lag samples either way -> device tensor float64 [n, hip.ALIGN_FIELDS] (score.ALIGN_FIELDS
         names the columns; delay > 0: the estimate is late); corr=True: -> (that, float64 [n, 2 max_lag + 1]: the
         cross-correlation, lag -max_lag first)."""
-        n, D = len(est_off) - 1, int(max_lag)
-        if len(tgt_off) - 1 != n:
-            raise ValueError("align_device: one target per estimate")
-        for t in (est_t, tgt_t):
-            if t.dtype != torch.float32 or t.dim() != 1:
-                raise ValueError("align_device: flat float32 tensors")
+        n, D = _pair_check("align_device", est_t, est_off, tgt_t, tgt_off), int(max_lag)
         if not 0 <= D <= hip.ALIGN_MAX_LAG:
             raise ValueError("align_device: max_lag 0 ... %d, not %r" % (hip.ALIGN_MAX_LAG, max_lag))
         out = torch.empty((n, hip.ALIGN_FIELDS), dtype=torch.float64, device=self.device)
@@ -253,14 +254,9 @@ class Engine(context.Context):
         tensor float64 [n, hip.STOI_FIELDS] (score.STOI_FIELDS names the columns); per_segment=True: -> (that, float64
         [rows, 2] = d_s, e_s, the row offsets: clip i's rows begin at offsets[i] and its first `segments` are written, the
         rest stay NaN)."""
-        n = len(est_off) - 1
-        if len(tgt_off) - 1 != n:
-            raise ValueError("stoi_device: one target per estimate")
+        n = _pair_check("stoi_device", est_t, est_off, tgt_t, tgt_off)
         if rate not in (16000, score_mod.STOI_RATE):
             raise ValueError("stoi_device: signals at 16000 or %d Hz, not %r" % (score_mod.STOI_RATE, rate))
-        for t in (est_t, tgt_t):
-            if t.dtype != torch.float32 or t.dim() != 1:
-                raise ValueError("stoi_device: flat float32 tensors")
         sig = [(est_t.contiguous(), [int(v) for v in est_off]), (tgt_t.contiguous(), [int(v) for v in tgt_off])]
         if rate == 16000:
             for k, (x, off) in enumerate(sig):
@@ -286,12 +282,7 @@ class Engine(context.Context):
         tgt_t / tgt_off, float32 at 16 kHz -> device tensor float64 [n, hip.QUALITY_FIELDS] (score.QUALITY_FIELDS names the
         columns); per_frame=True: -> (that, float64 [frames, 3] = llr_f, cd_f, fw_f, the row offsets: clip i's rows are
         [offsets[i], offsets[i + 1]))."""
-        n = len(est_off) - 1
-        if len(tgt_off) - 1 != n:
-            raise ValueError("quality_device: one target per estimate")
-        for t in (est_t, tgt_t):
-            if t.dtype != torch.float32 or t.dim() != 1:
-                raise ValueError("quality_device: flat float32 tensors")
+        n = _pair_check("quality_device", est_t, est_off, tgt_t, tgt_off)
         W, K = context.quality_bands_arg(bands)
         eo, to = [int(v) for v in est_off], [int(v) for v in tgt_off]
         out = torch.empty((n, hip.QUALITY_FIELDS), dtype=torch.float64, device=self.device)

@@ -11,6 +11,7 @@ Eval's SDR, SIR and SAR (bsseval.hip: Context.bss_eval / Engine.bss_eval_device;
 DESIGN.md section 1.13) has its definition in `align_reference`.  LLR, cepstral distance and frequency-weighted
 segmental SNR (quality.hip: Context.quality / Engine.quality_device) have theirs in
 `quality_reference`.  No torch here: the command line imports this."""
+import functools
 import math
 
 import numpy as np
@@ -49,52 +50,28 @@ _INTS = ("n", "frames", "frames_counted", "frames_skipped", "frames_kept", "segm
          "bss_n", "ne", "nt", "D", "delay", "n_common", "frames_lpc", "frames_fw", "quality_n", "quality_frames")
 
 
-def record(values):
-    """NHANS_SCORE_FIELDS doubles of one clip -> dict by name."""
-    return {k: (int(values[i]) if k in _INTS else float(values[i])) for i, k in enumerate(FIELDS)}
+def record(values, fields=FIELDS):
+    """The doubles of one clip's record (NHANS_SCORE_FIELDS of them; NHANS_<FAMILY>_FIELDS with that family's names as
+    `fields`) -> dict by name."""
+    return {k: (int(values[i]) if k in _INTS else float(values[i])) for i, k in enumerate(fields)}
 
 
-def row_record(values):
-    """NHANS_SCORE_ROW_FIELDS doubles of one clip -> dict by name."""
-    return {k: (int(values[i]) if k in _INTS else float(values[i])) for i, k in enumerate(ROW_FIELDS)}
+row_record = functools.partial(record, fields=ROW_FIELDS)
+stoi_record = functools.partial(record, fields=STOI_FIELDS)
+bss_record = functools.partial(record, fields=BSS_FIELDS)
+align_record = functools.partial(record, fields=ALIGN_FIELDS)
+quality_record = functools.partial(record, fields=QUALITY_FIELDS)
 
 
-def stoi_record(values):
-    """NHANS_STOI_FIELDS doubles of one clip -> dict by name."""
-    return {k: (int(values[i]) if k in _INTS else float(values[i])) for i, k in enumerate(STOI_FIELDS)}
+def merge(rec, other, prefix):
+    """A score record with another family's figures of the same pair merged in; a name the record already has (n, frames:
+    there the 16 kHz samples and the STFT rows) takes the prefix: stoi_n, stoi_frames, bss_n, quality_n, quality_frames."""
+    return dict(rec, **{(prefix + k if k in rec else k): v for k, v in other.items()})
 
 
-def merge_stoi(rec, stoi_rec):
-    """A score record with the STOI figures of the same pair merged in; a name the record already has (n, frames: there
-    the 16 kHz samples and the STFT rows) is prefixed: stoi_n, stoi_frames."""
-    return dict(rec, **{("stoi_" + k if k in rec else k): v for k, v in stoi_rec.items()})
-
-
-def bss_record(values):
-    """NHANS_BSS_FIELDS doubles of one clip -> dict by name."""
-    return {k: (int(values[i]) if k in _INTS else float(values[i])) for i, k in enumerate(BSS_FIELDS)}
-
-
-def merge_bss(rec, bss_rec):
-    """A score record with the BSS Eval figures of the same estimate merged in; a name the record already has (n) is
-    prefixed: bss_n."""
-    return dict(rec, **{("bss_" + k if k in rec else k): v for k, v in bss_rec.items()})
-
-
-def align_record(values):
-    """NHANS_ALIGN_FIELDS doubles of one clip -> dict by name."""
-    return {k: (int(values[i]) if k in _INTS else float(values[i])) for i, k in enumerate(ALIGN_FIELDS)}
-
-
-def quality_record(values):
-    """NHANS_QUALITY_FIELDS doubles of one clip -> dict by name."""
-    return {k: (int(values[i]) if k in _INTS else float(values[i])) for i, k in enumerate(QUALITY_FIELDS)}
-
-
-def merge_quality(rec, quality_rec):
-    """A score record with the LLR, cepstral-distance and fwSegSNR figures of the same pair merged in; a name the record
-    already has (n, frames: there the STFT rows) is prefixed: quality_n, quality_frames."""
-    return dict(rec, **{("quality_" + k if k in rec else k): v for k, v in quality_rec.items()})
+merge_stoi = functools.partial(merge, prefix="stoi_")
+merge_bss = functools.partial(merge, prefix="bss_")
+merge_quality = functools.partial(merge, prefix="quality_")
 
 
 def improvement(before, after):
