@@ -1168,6 +1168,99 @@ int nhans_quality_lpc(nhans_ctx* ctx, const float* est_dev, const int64_t* est_o
                       const int64_t* tgt_offsets_host, int nclips, double* lpc_out_dev, void* stream);
 int nhans_quality_tables(double* window_out, double* bands_out);        /* host only */
 
+/* ---- Drift-aware alignment: the delay tracked over a clip and warped out ----------------------------------------------------
+ * nhans_align estimates one whole-sample delay per clip.  Where estimate and target were sampled by two clocks -- a far
+ * microphone, a loop-back capture through a sound card -- the delay is neither an integer nor constant: converters differ by
+ * tens to a few hundred ppm, and 100 ppm move a 10 s clip by 16 samples.  These calls track the delay over the clip, fit a
+ * line to it and resample the estimate onto the target's clock (n-hans_amd/csrc/drift.hip).  Added
+ * without moving NHANS_ABI_VERSION; a caller that may meet an older library looks the functions up by symbol.
+ *   model      target sample u lines up with position p(u) = a + u + b u of the estimate: a is the delay at u = 0 in samples,
+ *              real-valued (a > 0: the estimate is late, the convention of nhans_align), b the drift (b > 0: the estimate's
+ *              clock runs fast), |b| <= 2^-10 (977 ppm), |a| <= 2^31.  All arithmetic is in double, one IEEE operation rounded
+ *              to nearest each (nothing is contracted); "chain" means acc = +0.0, then acc = fma(x, y, acc) per index,
+ *              ascending.  Inputs are float32 at any rate.  A sample outside a clip is a zero and is never fetched.
+ *   table      T = 16, Q = 512.  G[q][k] = sinc(x) kaiser(x / T; beta = 10), x = k - q / Q, for q = 0 ... Q and k = -T + 1 ... T:
+ *              sinc(x) = sin(pi x) / (pi x), kaiser(r; beta) = I0(beta sqrt(1 - r^2)) / I0(beta), designed on the host in double;
+ *              row 0 is set to the exact unit impulse.  D[q][k] = G[q + 1][k] - G[q][k], q < Q, rounded once.  The
+ *              interpolator is flat within 2e-5 up to 0.39 of the sample rate (6.3 kHz at 16 kHz), where its transition
+ *              band begins: content above that is attenuated and images.  nhans_drift_table (host only) copies the
+ *              (Q + 1) 2T doubles of G and the Q 2T of D, tap k at column k + T - 1; either pointer may be NULL.
+ *   segments   blocks of B = 4096 target samples at hop H = 2048: a clip of nt samples has J = 0 for nt < B, else
+ *              (nt - B) / H + 1 (integer division) -- nhans_drift_segments (host only); samples after the last full block are
+ *              not used.  Each call takes a centre line (ca, cb) per clip and one search radius R, 1 <= R <= 1024.  Segment
+ *              j's centre lag is z_j = floor(fma(cb, j H + (B - 1) / 2, ca) + 0.5), computed on the host.
+ *   lag vector c_j[d] = sum_i e[j H + i + d] t[j H + i] over i = 0 ... B - 1, for d in [z_j - R - T, z_j + R + T]: two tiles of
+ *              2048 samples anchored at the block's first sample, each one chain (the products are exact), the second
+ *              tile's part added to the first's.  c_j[d] is a function of the pair, of j and of d alone.
+ *   integer    d* = the d of [z_j - R, z_j + R] with the largest c_j[d]; of equal values the one with the smaller |d - z_j|,
+ *   peak       and of z_j - r and z_j + r the latter (the order of nhans_align, taken relative to z_j).
+ *   fine peak  v_k = the lag vector interpolated at d* + k / 32, k = -32 ... 32: with w = floor(k / 32) and r = k - 32 w, the chain
+ *              over the taps i = -T + 1 ... T of fma(c_j[d* + w + i], G[16 r][i], acc); a lag outside the vector (only d* + 17 at
+ *              k = 32 can be; its weight is exactly 0) is passed over.  The best k: the larger value, then the smaller |k|,
+ *              then the larger k.  For |k| < 32, den = (v_{k-1} - 2 v_k) + v_{k+1}; where den < 0 the parabola's offset is
+ *              delta = ((v_{k-1} - v_{k+1}) / (2 den)) / 32, clamped to -1/64 ... 1/64; otherwise and for |k| = 32, delta = 0.
+ *              tau_j = (d* + k / 32) + delta.
+ *   abscissa   E_t = sum t[j H + i]^2 and N = sum i t[j H + i]^2 over the block, each in a fixed order (drift.hip states it);
+ *              u_j = j H + N / E_t: the block's energy centroid, not its centre -- the delay a block measures is the delay
+ *              where its energy is.
+ *   confidence E_e = sum e[j H + i + d*]^2 over the block; rho_j = v_k / sqrt(E_e E_t) (the product rounded once, the root, the
+ *              quotient).  IEEE applies: a silent block gives NaN for u_j and rho_j, and nothing is refused for it.
+ *   flags      1: the peak is at the edge of the search, d* = z_j - R, d* = z_j + R, k = -32 or k = 32;  2: E_t == 0 or E_e == 0.
+ *   record     NHANS_DRIFT_FIELDS doubles per segment: u_j, tau_j, rho_j, E_t, v_k, d*, flags, z_j.
+ *   line fit   nhans_drift_fit (host only), from the records of one clip, rho_min (0.3 is the Python default) and trim (1.0):
+ *              the valid segments have flags == 0 and rho >= rho_min.  Weighted least squares of tau on u with weights
+ *              w = E_t, every sum over the segments ascending from +0.0, every product rounded by itself:
+ *              W = sum w, mu = (sum w u) / W, mt = (sum w tau) / W, Suu = sum (w du) du, Sut = sum (w du) dt with du = u - mu and
+ *              dt = tau - mt; b = Sut / Suu, a = mt - b mu.  One trimming pass: the segments with |tau - (a + b u)| > trim are
+ *              dropped and, if any was, the rest is fitted again.  rms_residual = sqrt((sum (w r) r) / W) over the segments
+ *              used, r the residual to the final line.  out: NHANS_DRIFT_FIT_FIELDS doubles a, b, n_valid, n_used,
+ *              rms_residual, fit_ok.  fit_ok = 0 where fewer than 3 segments were used, where W or Suu is not positive (then
+ *              a, b and the residual are NaN) or where |b| > 2^-10.
+ *   warp       for clip i with (a, b) and a target of nt samples, the output covers the maximal range [u_lo, u_hi) of [0, nt)
+ *              with 0 <= p(u) <= ne - 1 -- nhans_drift_range (host only), computed with the device's own expression of p;
+ *              an empty range is 0, 0.  p = fma(b, u, a) + u (two roundings), m = floor(p), f = (p - m) Q (exact),
+ *              q = min(floor(f), Q - 1), lambda = f - q, g_k = fma(lambda, D[q][k], G[q][k]), and
+ *              y[u] = (float) the chain over k = -T + 1 ... T of fma(e[m + k], g_k, acc).  With a an integer and b = 0 the output
+ *              is e[a + u] bit for bit (row 0 is the unit impulse; a sample -0.0 comes out as +0.0).  The aligned target is
+ *              t[u_lo .. u_hi), and a further signal that is sample-aligned with the target is cut likewise: nhans_align_cut
+ *              with no estimate, estimate lengths u_hi - u_lo and delay -u_lo.
+ * Out of scope: a drift that is not linear over the clip (a clock that wanders, a dropped buffer), a polarity search, and
+ * live sessions.  Every record and every output sample has the same bits alone or in any batch, at any offset of either
+ * buffer, beside any neighbours, for every R that reaches the same lags, on every run: no floating-point atomics, no
+ * reduction whose shape depends on the batch.  Only samples inside a clip are fetched.  Non-finite samples: unspecified.
+ *
+ * nhans_drift_track: clip i of the estimates is est_dev[est_offsets_host[i] .. est_offsets_host[i + 1]), of the targets
+ * likewise with its own offsets; centre_a_host and centre_b_host hold one line per clip.  out_dev receives
+ * NHANS_DRIFT_FIELDS doubles per segment, clip after clip: clip i's J_i records begin at record sum_{k < i} J_k.
+ * corr_out_dev (nullable) receives the 2 (R + T) + 1 values of every segment's lag vector, lag z_j - R - T first, in the same
+ * order.  The workspace holds a table of the segments only.  NHANS_EINVAL, naming the clip, before anything is launched
+ * and with nothing written: nclips < 0, radius outside 1 ... 1024, a NULL that is needed, an offset array that descends, a
+ * clip of more than 2^31 - 1 samples, a line that is not finite, |cb| > 2^-10, |ca| > 2^31 or a centre whose lags
+ * z_j - R - T ... z_j + R + T leave the int32 range.
+ *
+ * nhans_drift_warp: the estimates as above; tgt_offsets_host says how long the targets are (their samples are not
+ * read); a_host and b_host hold one line per clip.  Clip i's u_hi - u_lo samples are written from out_dev[out_offsets_host[i]]
+ * on: one launch for the whole call.  NHANS_EINVAL, naming the clip, before anything is launched and with nothing written:
+ * nclips < 0, a NULL that is needed, an offset array that descends, a clip of more than 2^31 - 1 samples, a line that is
+ * not finite, |b| > 2^-10, |a| > 2^31, an output room shorter than the range. */
+#define NHANS_DRIFT_FIELDS 8    /* u, tau, rho, E_t, v_peak, d_int, flags, z */
+#define NHANS_DRIFT_FIT_FIELDS 6 /* a, b, n_valid, n_used, rms_residual, fit_ok */
+#define NHANS_DRIFT_TAPS 16
+#define NHANS_DRIFT_PHASES 512
+#define NHANS_DRIFT_BLOCK 4096
+#define NHANS_DRIFT_HOP 2048
+#define NHANS_DRIFT_MAX_RADIUS 1024
+int nhans_drift_table(double* g_out, double* d_out);                    /* host only */
+int64_t nhans_drift_segments(int64_t nt);                               /* host only */
+int nhans_drift_range(int64_t ne, int64_t nt, double a, double b, int64_t* u_lo_out, int64_t* u_hi_out);    /* host only */
+int nhans_drift_fit(const double* records_host, int nsegments, double rho_min, double trim, double* out_host);  /* host only */
+int nhans_drift_track(nhans_ctx* ctx, const float* est_dev, const int64_t* est_offsets_host, const float* tgt_dev,
+                      const int64_t* tgt_offsets_host, int nclips, const double* centre_a_host, const double* centre_b_host,
+                      int radius, double* out_dev, double* corr_out_dev, void* stream);
+int nhans_drift_warp(nhans_ctx* ctx, const float* est_dev, const int64_t* est_offsets_host, const int64_t* tgt_offsets_host,
+                     int nclips, const double* a_host, const double* b_host, float* out_dev, const int64_t* out_offsets_host,
+                     void* stream);
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

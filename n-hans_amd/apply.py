@@ -68,6 +68,7 @@ class Flags(object):
     bss = False          # --bss: with --score_against and --interferer, also SDR, SIR and SAR (score.py: bss_reference is the definition)
     interferer = None    # --interferer FILE: the signal that was to be removed, for --bss
     align_ms = None      # --align_ms MS: with --score_against, the delay of the denoised file against the target is estimated within MS and taken out
+    align_drift = False  # --align_drift: with --align_ms, a line is fitted to the delay over the file and warped out (Context.align_drift)
     quality = False      # --quality: with --score_against, also LLR, cepstral distance and fwSegSNR (score.py: quality_reference is the definition)
     stoi = False         # --stoi: with --score_against, also STOI and extended STOI (score.py: stoi_reference is the definition)
     lookahead_ms = 10 * spec.LOOKAHEAD   # --lookahead_ms: 10 ms per frame of look-ahead (include/nhans_hip.h: "lookahead"), 170 = all 17
@@ -871,7 +872,16 @@ def _parse(argv, prog):
                         '(0 < MS <= 1000; whole samples, positive: the files are late) and taken out of the denoised file, '
                         'the mixed round trip and the target (and the --interferer) before they are scored; the scores '
                         'gain delay_samples and align_rho per file; the audio files are what they are without the flag')
+    p.add_argument('--align_drift', action='store_true',
+                   help='with --align_ms, for a target recorded on another clock: the delay of the denoised file against '
+                        'the target is tracked over the file around the one --align_ms finds, a line delay + drift fitted '
+                        'to it, and the denoised file and the mixed round trip resampled onto the target\'s clock on the '
+                        'device before they are scored (the target and the --interferer are cut to the same range); the '
+                        'scores gain delay_samples (real), drift_ppm and drift_ok per file; the audio files are what they '
+                        'are without the flag')
     a = p.parse_args(argv)
+    if a.align_drift and a.align_ms is None:
+        p.error('--align_drift needs --align_ms MS')
     if a.align_ms is not None:
         if a.score_against is None:
             p.error('--align_ms needs --score_against TARGET')
@@ -999,7 +1009,10 @@ def _score_jobs(kind, a, jobs):
     stdout: {"files": {input path: {"denoised", "mixed", "improvement"}}, "skipped": [...]} and, in directory mode, "mean".
     --align_ms: one Context.align call first, each denoised file against its target within round(16 MS) samples; a file's
     delay is taken out of both of its signals alike -- the two are sample-aligned by construction -- and out of the
-    interferer as out of the target, and the file's entry gains "delay_samples" and "align_rho"."""
+    interferer as out of the target, and the file's entry gains "delay_samples" and "align_rho".
+    --align_drift: one Context.align_drift call instead, the line of each denoised file against its target; a file's line is
+    warped out of both of its signals alike and the target and the interferer are cut to the warp's range; the file's
+    entry gains "delay_samples" (real), "drift_ppm", "drift_ok" and "align_rho"."""
     import json
     from . import score
     directory = os.path.isdir(a.input)
@@ -1018,7 +1031,12 @@ def _score_jobs(kind, a, jobs):
             interf += [x, x]
         done.append(mixedpath)
     align_ms, found = getattr(a, "align_ms", None), None
-    if align_ms is not None and est:
+    lines = None
+    if align_ms is not None and est and getattr(a, "align_drift", False):
+        eng = get_enhancer(kind)
+        lines = eng.align_drift(est[0::2], tgt[0::2], max_lag=int(round(16 * align_ms)))
+        est, tgt, interf = eng._drift_pairs(est, tgt, interf if bss else None, [l for l in lines for _ in (0, 1)])
+    elif align_ms is not None and est:
         found = get_enhancer(kind).align(est[0::2], tgt[0::2], max_lag=int(round(16 * align_ms)))
     recs = get_enhancer(kind).score(est, tgt, stoi=getattr(a, "stoi", False), bss=interf if bss else None,
                                     quality=getattr(a, "quality", False),
@@ -1029,6 +1047,10 @@ def _score_jobs(kind, a, jobs):
         files[path] = {"denoised": den, "mixed": mix, "improvement": score.improvement(mix, den)}
         if found:
             files[path].update(delay_samples=found[i]["delay"], align_rho=found[i]["rho"])
+        if lines:
+            l = lines[i]
+            files[path].update(delay_samples=l["delay"] if l["fit_ok"] else l["delay_int"], drift_ppm=l["drift_ppm"],
+                               drift_ok=l["fit_ok"], align_rho=l["rho"])
     out = {"files": files, "skipped": skipped}
     if directory and files:
         out["mean"] = {k: score.mean_of([f[k] for f in files.values()]) for k in ("denoised", "mixed", "improvement")}

@@ -126,7 +126,7 @@ class Context:
 
 
     # ---- scoring against a clean target (include/nhans_hip.h: nhans_score_*) ---------------------
-    def score(self, estimates, targets, per_frame=False, stoi=False, bss=None, align=None, delays=None, quality=False):
+    def score(self, estimates, targets, per_frame=False, stoi=False, bss=None, align=None, delays=None, quality=False, drift=False):
         """Lists of float32 waveforms, estimate i against target i over their common prefix -> one dict per clip: the
         waveform figures (score.FIELDS: si_sdr_db, snr_db, segsnr_db, ...) and the row figures loss and lsd_db of the two
         signals' own log-magnitude rows (nhans_stft_features) -- one upload, two STFTs and the two score calls on the
@@ -141,9 +141,24 @@ class Context:
         Signals that are not aligned: align=D estimates one delay per pair within D samples either way (Context.align),
         delays=[...] applies given integers (positive: the estimate is late); each pair is cut to its common part
         (score.align_cut; an interferer as its target) and scored as above, and each record gains "delay" and, where the
-        delay was estimated, "align_rho"."""
+        delay was estimated, "align_rho".
+        Signals sampled by two clocks: align=D with drift=True fits a line to the delay over the clip (Context.align_drift)
+        and resamples the estimate onto the target's clock (Context.drift_warp; the target and an interferer are cut to
+        the warp's range); each record gains "delay" (real, at the target's first sample), "drift_ppm", "drift_ok" and
+        "align_rho".  A pair without a good fit (drift_ok 0) is cut by its whole-sample delay, exactly as without drift."""
         if len(estimates) != len(targets):
             raise ValueError("score: one target per estimate")
+        if drift:
+            if align is None:
+                raise ValueError("score: drift=True tracks the delay around the one align=D estimates: give align=")
+            extra = bss if bss is not None and bss is not False and bss is not True else None
+            if extra is not None and len(extra) != len(estimates):
+                raise ValueError("score: one interferer per estimate")
+            lines = self.align_drift(estimates, targets, max_lag=align)
+            es, ts, xs = self._drift_pairs(estimates, targets, extra, lines)
+            recs = self.score(es, ts, per_frame=per_frame, stoi=stoi, bss=xs if extra is not None else bss, quality=quality)
+            return [dict(r, delay=l["delay"] if l["fit_ok"] else l["delay_int"], drift_ppm=l["drift_ppm"], drift_ok=l["fit_ok"],
+                         align_rho=l["rho"]) for r, l in zip(recs, lines)]
         if align is not None or delays is not None:
             extra = bss if bss is not None and bss is not False and bss is not True else None
             es, ts, xs, tags = self._aligned("score", estimates, targets, extra, align, delays)
@@ -234,6 +249,110 @@ class Context:
         pairs = [score_mod.align_cut(e, t, tag["delay"]) for e, t, tag in zip(estimates, targets, tags)]
         xs = None if others is None else [score_mod.align_cut(e, x, tag["delay"])[1] for e, x, tag in zip(estimates, others, tags)]
         return [p[0] for p in pairs], [p[1] for p in pairs], xs, tags
+
+    # ---- drift-aware alignment (include/nhans_hip.h: nhans_drift_*) --------------------------------
+    def drift_track(self, estimates, targets, centres, radius=64, corr=False):
+        """Lists of float32 waveforms, estimate i against target i, tracked in blocks of 4,096 target samples at hop 2,048
+        around the centre lines centres[i] = (ca, cb) within `radius` lags -> per clip a list of one dict per segment by
+        score.DRIFT_FIELDS: u (the block's energy centroid), tau (the delay there), rho, E_t, v_peak, d_int, flags, z.  One
+        upload, one launch, one download.  corr=True: each segment plus "corr", float64 [2 (radius + 16) + 1], lag
+        z - radius - 16 first."""
+        if len(estimates) != len(targets) or len(centres) != len(estimates):
+            raise ValueError("drift_track: one target and one centre line per estimate")
+        n, R = len(estimates), int(radius)
+        (ef, eoff), (tf, toff) = flat(estimates), flat(targets)
+        soff = offsets(score_mod.drift_segments(len(t)) for t in targets)
+        S, nf, per = soff[-1], hip.DRIFT_FIELDS, 2 * (R + hip.DRIFT_TAPS) + 1
+        ca, cb = hip.dbl_array(c[0] for c in centres), hip.dbl_array(c[1] for c in centres)
+        got = self._records_call([ef, tf], S * nf, S * per if corr else None, lambda at, out, extra, s: self.lib.nhans_drift_track(
+            self.handle, at(0), hip.i64_array(eoff), at(1), hip.i64_array(toff), n, ca, cb, R, out, extra, s))
+        res = []
+        for i in range(n):
+            segs = []
+            for k in range(soff[i], soff[i + 1]):
+                rec = score_mod.drift_segment_record(got[k * nf:(k + 1) * nf])
+                if corr:
+                    rec["corr"] = got[S * nf + k * per:S * nf + (k + 1) * per].copy()
+                segs.append(rec)
+            res.append(segs)
+        return res
+
+    def drift_warp(self, estimates, target_lengths, lines):
+        """Lists of float32 waveforms, the lengths of their targets and one line (a, b) each -> per clip (y, u_lo, u_hi): the
+        estimate resampled onto the target's clock, y[u - u_lo] = the estimate at a + u + b u for the u of [u_lo, u_hi) --
+        the largest range of the target whose positions lie inside the estimate (hip.drift_range).  The aligned target
+        is target[u_lo:u_hi].  One upload, one launch, one download."""
+        if len(target_lengths) != len(estimates) or len(lines) != len(estimates):
+            raise ValueError("drift_warp: one target length and one line per estimate")
+        lib, mem, n = self.lib, Mem(self), len(estimates)
+        ef, eoff = flat(estimates)
+        toff = offsets(target_lengths)
+        rng = [hip.drift_range(eoff[i + 1] - eoff[i], toff[i + 1] - toff[i], lines[i][0], lines[i][1]) for i in range(n)]
+        ooff = offsets(hi - lo for lo, hi in rng)
+        buf, out = mem.up(ef), mem.empty(ooff[-1])
+        try:
+            hip.check(lib.nhans_drift_warp(self.handle, mem.p(buf), hip.i64_array(eoff), hip.i64_array(toff), n,
+                                           hip.dbl_array(l[0] for l in lines), hip.dbl_array(l[1] for l in lines), mem.p(out),
+                                           hip.i64_array(ooff), mem.stream()))
+            self._sync()
+            got = np.array(mem.down(out, ooff[-1]), dtype=np.float32)
+        finally:
+            mem.free(buf, out)
+        return [(got[ooff[i]:ooff[i + 1]], rng[i][0], rng[i][1]) for i in range(n)]
+
+    def drift_fit(self, segments, rho_min=score_mod.DRIFT_RHO_MIN, trim=score_mod.DRIFT_TRIM):
+        """The line through one clip's segments (drift_track's dicts): nhans_drift_fit -> dict by score.DRIFT_FIT_FIELDS."""
+        return hip.drift_fit([[s[k] for k in score_mod.DRIFT_FIELDS] for s in segments], rho_min, trim)
+
+    def align_drift(self, estimates, targets, max_lag=8000, track_lag=64):
+        """Lists of float32 waveforms, estimate i against target i -> one dict per pair: the line p(u) = delay + u + drift u of
+        the estimate's positions over the target's samples u.  Context.align gives the whole-sample delay d0 within max_lag;
+        the delay is tracked over the clip around (d0, 0) within track_lag lags and a line fitted (drift_track, drift_fit);
+        where that fit is good the clip is tracked again around the fitted line within 8 lags -- which recovers the outer
+        segments of a long clip, whose delay has left the first window -- and fitted again.  Keys: delay (real, samples at
+        u = 0; positive: the estimate is late), drift (b) and drift_ppm (10^6 b; positive: the estimate's clock runs fast),
+        fit_ok, segments, segments_used, rms_residual, rho (of the whole-sample record), delay_int (d0).  Where fit_ok is 0
+        -- a clip of fewer than three blocks, too few segments that correlate, a slope beyond 2^-10 -- delay is d0 and drift 0.
+        segments_used and rms_residual are those of the last fit made, whether it was good or not: where the first fit was
+        good and the second was not, they describe the second, failed one, and the result is still (d0, 0)."""
+        coarse = self.align(estimates, targets, max_lag=max_lag)
+        n = len(coarse)
+        fits = [self.drift_fit(s) for s in self.drift_track(estimates, targets, [(float(r["delay"]), 0.0) for r in coarse], radius=track_lag)]
+        again = [i for i in range(n) if fits[i]["fit_ok"]]
+        if again:
+            segs = self.drift_track([estimates[i] for i in again], [targets[i] for i in again],
+                                    [(fits[i]["a"], fits[i]["b"]) for i in again], radius=8)
+            for i, s in zip(again, segs):
+                fits[i] = self.drift_fit(s)
+        res = []
+        for r, f in zip(coarse, fits):
+            ok = bool(f["fit_ok"])
+            a, b = (f["a"], f["b"]) if ok else (float(r["delay"]), 0.0)
+            res.append({"delay": a, "drift": b, "drift_ppm": 1e6 * b, "fit_ok": int(ok), "segments": score_mod.drift_segments(r["nt"]),
+                        "segments_used": f["n_used"], "rms_residual": f["rms_residual"], "rho": r["rho"], "delay_int": r["delay"]})
+        return res
+
+    def _drift_pairs(self, estimates, targets, others, lines):
+        """The pairs with their lines (align_drift's dicts) taken out -> (estimates, targets, others): a pair whose fit is good
+        is warped onto the target's clock (drift_warp) and its target -- and the further signal of `others` that is
+        sample-aligned with it -- cut to the warp's range; any other pair is cut by its whole-sample delay (score.align_cut)."""
+        ok = [i for i, l in enumerate(lines) if l["fit_ok"]]
+        warped = dict(zip(ok, self.drift_warp([estimates[i] for i in ok], [len(targets[i]) for i in ok],
+                                              [(lines[i]["delay"], lines[i]["drift"]) for i in ok]))) if ok else {}
+        es, ts, xs = [], [], (None if others is None else [])
+        for i, (e, t) in enumerate(zip(estimates, targets)):
+            if i in warped:
+                y, lo, hi = warped[i]
+                cut = lambda x: x[lo:hi]
+            else:
+                d = lines[i]["delay_int"]
+                y = score_mod.align_cut(e, t, d)[0]
+                cut = lambda x, d=d: score_mod.align_cut(e, x, d)[1]
+            es.append(y)
+            ts.append(cut(t))
+            if others is not None:
+                xs.append(cut(others[i]))
+        return es, ts, xs
 
     # ---- STOI and extended STOI against a clean target (include/nhans_hip.h: nhans_stoi) ----------
     def stoi(self, estimates, targets, rate=16000, per_segment=False, delays=None):

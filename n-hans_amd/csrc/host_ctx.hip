@@ -353,6 +353,7 @@ void nhans_destroy(nhans_ctx* c) {
     if (c->status_dev) (void)hipFree(c->status_dev);
     if (c->amax_dev) (void)hipFree(c->amax_dev);
     for (auto& kv : c->rs_tab) (void)hipFree(kv.second);
+    if (c->drift_tab) (void)hipFree(c->drift_tab);
     if (c->ws) (void)hipFree(c->ws);
     if (c->kscratch) (void)hipFree(c->kscratch);
     if (c->kcounter) (void)hipFree(c->kcounter);

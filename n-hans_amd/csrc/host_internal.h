@@ -16,7 +16,8 @@
 //   host_bsseval.hip  nhans_bss_eval
 //   host_align.hip    nhans_align, nhans_align_common, nhans_align_cut
 //   host_quality.hip  nhans_quality, nhans_quality_lpc, nhans_quality_tables
-// A unit calls down only: ctx <- net <- online <- live, ctx <- fbank <- online, ctx <- rate <- live, ctx <- score, ctx <- mix, ctx <- rate <- stoi, ctx <- bsseval, ctx <- align and ctx <- quality.  (One call goes up: the built-in calibration
+//   host_drift.hip    nhans_drift_table, nhans_drift_segments, nhans_drift_range, nhans_drift_fit, nhans_drift_track, nhans_drift_warp
+// A unit calls down only: ctx <- net <- online <- live, ctx <- fbank <- online, ctx <- rate <- live, ctx <- score, ctx <- mix, ctx <- rate <- stoi, ctx <- bsseval, ctx <- align, ctx <- quality and ctx <- drift.  (One call goes up: the built-in calibration
 // of nhans_create runs the whole offline path, enhance_clips_body.)  Only what crosses a unit boundary is declared here;
 // everything else stays in its unit's anonymous namespace.
 // Nothing declared here joins the library's dynamic symbols (visibility hidden) except the object types the C header
@@ -126,6 +127,7 @@ struct nhans_ctx {
     long long* dbg = nullptr;   // NHANS_DEV builds: per-workgroup cycle stamps of the last conv launch
     int* status_dev = nullptr;  // sticky NHANS_STATUS_* bits set by kernels (nhans_take_status)
     std::map<std::pair<int, int>, float*> rs_tab;   // device copies of the rate converter's phase tables, by (rate_in, rate_out)
+    double* drift_tab = nullptr;    // device copy of the drift interpolation table, G then D (host_drift.hip: designed at its first use)
     // Activation exponents: a split-f16 tensor is stored as x * 2^-e with one e per tensor of the network, chosen from
     // the largest |x| a calibration pass saw so that the stored maximum is <= 2^kActTargetLog2 -- 2^8 below the f16
     // limit (and the 1-D Winograd transform's worst-case gain of ~20 still fits).  Tensors: tower block b conv1/conv2

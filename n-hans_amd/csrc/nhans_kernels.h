@@ -604,4 +604,44 @@ void launch_quality_bands(const char* kernel, const QualityRun* runs_dev, int nr
 // rec: [clips][kQualityFields]
 void launch_quality_finish(const char* kernel, const QualityRun* runs_dev, int nruns, const double* vals, double* rec, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// Drift-aware alignment (drift.hip; include/nhans_hip.h: nhans_drift_track, nhans_drift_warp).  Target sample u lines up
+// with position p(u) = a + u + b u of the estimate.  The interpolation table: G [kDriftQ + 1][2 kDriftT] then D [kDriftQ][2
+// kDriftT] doubles, tap k = -kDriftT + 1 ... kDriftT at column k + kDriftT - 1.  One DriftSeg per tracked segment, in the
+// order of the records: the block of kDriftBlock target samples at tgt (target sample u0 of its clip), the whole estimate
+// (ne samples at est, nullptr where ne is 0) and the centre lag z; its lag vector is 2 (R + kDriftT) + 1 doubles, lag
+// z - R - kDriftT first.  One DriftWarp per clip with a non-empty range: outputs [u_lo, u_lo + n) to dst, workgroups [tile0,
+// tile0 + ceil(n / kDriftWarpTile)), tile0 ascending strictly from 0.
+struct DriftSeg {
+    const float* est;
+    const float* tgt;
+    long long ne, u0;
+    int z, pad;
+};
+struct DriftWarp {
+    const float* est;
+    float* dst;
+    long long ne, u_lo, n, tile0;
+    double a, b;
+};
+constexpr int kDriftFields = 8, kDriftFitFields = 6, kDriftT = 16, kDriftQ = 512, kDriftBlock = 4096, kDriftHop = 2048, kDriftMaxR = 1024;
+constexpr int kDriftTile = 2048;            // samples per fma chain of a lag sum (the tile of align.hip)
+constexpr int kDriftFine = 32;              // fine positions per sample of the peak search
+constexpr int kDriftWarpTile = 1024;        // outputs per workgroup of the warp
+constexpr int kDriftTableG = (kDriftQ + 1) * 2 * kDriftT, kDriftTableD = kDriftQ * 2 * kDriftT;
+constexpr double kDriftMaxSlope = 0.0009765625;     // 2^-10
+constexpr double kDriftMaxDelay = 2147483648.0;     // |a| <= 2^31: p(u) stays strictly increasing in u, rounding included
+inline long long drift_segments(long long nt) { return nt >= kDriftBlock ? (nt - kDriftBlock) / kDriftHop + 1 : 0; }
+// p(u), the one expression of the device and of nhans_drift_range: fma(b, u, a) rounded, then + u rounded
+__host__ __device__ inline double drift_pos(double a, double b, double u) {
+#pragma clang fp contract(off)
+    const double f = __builtin_fma(b, u, a);
+    return f + u;
+}
+void drift_table(double* g, double* d);                      // (host) kDriftTableG and kDriftTableD doubles
+// tab: G then D on the device; rec: [segments][kDriftFields]; corr (nullable): [segments][2 (R + kDriftT) + 1]
+void launch_drift_track(const char* kernel, const DriftSeg* segs_dev, int nsegs, int R, const double* tab, double* rec, double* corr,
+                        hipStream_t s);
+void launch_drift_warp(const char* kernel, const DriftWarp* jobs_dev, int njobs, long long ntiles, const double* tab, hipStream_t s);
+
 }  // namespace nhans

@@ -228,6 +228,45 @@ class Engine(context.Context):
                                            hip.i64_array(d), hip.ptr(outs[0]), hip.ptr(outs[1]), hip.i64_array(off), self._stream()))
         return tuple(None if o is None else o[:off[-1]] for o in outs) + (off,)
 
+    # ---- drift-aware alignment (include/nhans_hip.h: nhans_drift_track, nhans_drift_warp) -------------
+    def drift_track_device(self, est_t, est_off, tgt_t, tgt_off, centres, radius=64, corr=False):
+        """The delay of clips already in HBM tracked over each clip: estimate i = est_t[est_off[i]:est_off[i + 1]] against
+        target i of tgt_t / tgt_off, flat float32, around the centre lines centres[i] = (ca, cb) within `radius` lags ->
+        (device tensor float64 [segments, hip.DRIFT_FIELDS] -- score.DRIFT_FIELDS names the columns --, the segment
+        offsets: clip i's rows are [offsets[i], offsets[i + 1])); corr=True: -> (those two, float64 [segments, 2 (radius +
+        16) + 1]: each segment's lag vector, lag z - radius - 16 first)."""
+        n, R = _pair_check("drift_track_device", est_t, est_off, tgt_t, tgt_off), int(radius)
+        if len(centres) != n:
+            raise ValueError("drift_track_device: one centre line per estimate")
+        if not 1 <= R <= hip.DRIFT_MAX_RADIUS:
+            raise ValueError("drift_track_device: radius 1 ... %d, not %r" % (hip.DRIFT_MAX_RADIUS, radius))
+        soff = context.offsets(score_mod.drift_segments(tgt_off[i + 1] - tgt_off[i]) for i in range(n))
+        S = max(soff[-1], 1)                 # (a tensor of no rows has no pointer, and the call refuses a null output)
+        out = torch.empty((S, hip.DRIFT_FIELDS), dtype=torch.float64, device=self.device)
+        c = torch.empty((S, 2 * (R + hip.DRIFT_TAPS) + 1), dtype=torch.float64, device=self.device) if corr else None
+        hip.check(self.lib.nhans_drift_track(self.handle, hip.ptr(est_t.contiguous()), hip.i64_array(est_off), hip.ptr(tgt_t.contiguous()),
+                                             hip.i64_array(tgt_off), n, hip.dbl_array(l[0] for l in centres),
+                                             hip.dbl_array(l[1] for l in centres), R, hip.ptr(out), hip.ptr(c), self._stream()))
+        return (out[:soff[-1]], soff, c[:soff[-1]]) if corr else (out[:soff[-1]], soff)
+
+    def drift_warp_device(self, est_t, est_off, tgt_off, lines):
+        """The estimates of drift_track_device resampled onto their targets' clocks, lines[i] = (a, b), in one launch ->
+        (flat float32 device tensor, offsets, ranges): clip i's samples are [offsets[i], offsets[i + 1]) and stand for the
+        target samples ranges[i] = (u_lo, u_hi) (hip.drift_range); tgt_off only says how long the targets are.  The aligned
+        targets are the slices [u_lo, u_hi) -- align_cut_device with est_t=None, estimate lengths u_hi - u_lo and delays -u_lo."""
+        n = len(est_off) - 1
+        if len(tgt_off) - 1 != n or len(lines) != n:
+            raise ValueError("drift_warp_device: one target and one line per estimate")
+        if est_t.dtype != torch.float32 or est_t.dim() != 1:
+            raise ValueError("drift_warp_device: a flat float32 tensor")
+        rng = [hip.drift_range(est_off[i + 1] - est_off[i], tgt_off[i + 1] - tgt_off[i], lines[i][0], lines[i][1]) for i in range(n)]
+        off = context.offsets(hi - lo for lo, hi in rng)
+        out = torch.empty(max(off[-1], 1), dtype=torch.float32, device=self.device)
+        hip.check(self.lib.nhans_drift_warp(self.handle, hip.ptr(est_t.contiguous()), hip.i64_array(est_off), hip.i64_array(tgt_off), n,
+                                            hip.dbl_array(l[0] for l in lines), hip.dbl_array(l[1] for l in lines), hip.ptr(out),
+                                            hip.i64_array(off), self._stream()))
+        return out[:off[-1]], off, rng
+
     # ---- BSS Eval against target and interferer (include/nhans_hip.h: nhans_bss_eval) ---------------
     def bss_eval_device(self, est_t, est_off, sources, filt_len=score_mod.BSS_MAX_FILTER, filters=False):
         """SDR, SIR and SAR of clips already in HBM: estimate i = est_t[est_off[i]:est_off[i + 1]] against sources = [(tensor,

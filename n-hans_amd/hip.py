@@ -140,6 +140,13 @@ SIGNATURES = {
     "nhans_quality": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _dp, _int, _vp, _vp, _vp]),
     "nhans_quality_lpc": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _vp, _vp]),
     "nhans_quality_tables": (_int, [_dp, _dp]),
+    # drift-aware alignment: the delay tracked over a clip, the line fit and the warp (the lines are host arrays)
+    "nhans_drift_table": (_int, [_dp, _dp]),
+    "nhans_drift_segments": (_i64, [_i64]),
+    "nhans_drift_range": (_int, [_i64, _i64, _dbl, _dbl, _i64p, _i64p]),
+    "nhans_drift_fit": (_int, [_dp, _int, _dbl, _dbl, _dp]),
+    "nhans_drift_track": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _dp, _dp, _int, _vp, _vp, _vp]),
+    "nhans_drift_warp": (_int, [_vp, _vp, _i64p, _i64p, _int, _dp, _dp, _vp, _i64p, _vp]),
     "nhans_profile_json": (_int, [_vp, _str, _size]),
     "nhans_profile_reset": (_int, [_vp]),
 }
@@ -170,6 +177,9 @@ BSS_CORR_TILE = 2048                        # samples per workgroup of bsseval.h
 ALIGN_FIELDS = 8
 ALIGN_MAX_LAG = 16000
 ALIGN_TILE, ALIGN_LAG_BLOCK = 2048, 2048    # samples per tile and lags per workgroup of align.hip (kAlignTile, kAlignLagBlock)
+DRIFT_FIELDS, DRIFT_FIT_FIELDS = 8, 6
+DRIFT_TAPS, DRIFT_PHASES, DRIFT_BLOCK, DRIFT_HOP, DRIFT_MAX_RADIUS = 16, 512, 4096, 2048, 1024
+DRIFT_TILE, DRIFT_FINE, DRIFT_WARP_TILE = 2048, 32, 1024    # samples per fma chain, fine positions per sample, outputs per workgroup of drift.hip
 QUALITY_FIELDS, QUALITY_LPC_FIELDS = 16, 72
 QUALITY_FRAME, QUALITY_HOP, QUALITY_ORDER, QUALITY_FFT, QUALITY_BINS = 480, 120, 16, 512, 257
 QUALITY_BANDS, QUALITY_MAX_BANDS = 25, 32
@@ -223,6 +233,28 @@ def check(rc):
 def i64_array(values):
     arr = (ctypes.c_int64 * len(values))(*[int(v) for v in values])
     return arr
+
+
+def dbl_array(values):
+    values = [float(v) for v in values]
+    return (ctypes.c_double * len(values))(*values)
+
+
+def drift_range(ne, nt, a, b):
+    """-> (u_lo, u_hi): the target samples a warp by the line (a, b) covers (nhans_drift_range, host only)"""
+    lo, hi = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(load().nhans_drift_range(int(ne), int(nt), float(a), float(b), ctypes.byref(lo), ctypes.byref(hi)))
+    return lo.value, hi.value
+
+
+def drift_fit(rows, rho_min, trim):
+    """rows of NHANS_DRIFT_FIELDS doubles, one clip's segments -> dict by score.DRIFT_FIT_FIELDS (nhans_drift_fit, host only)"""
+    import numpy as np
+    from . import score
+    flat = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, DRIFT_FIELDS)
+    out = (ctypes.c_double * DRIFT_FIT_FIELDS)()
+    check(load().nhans_drift_fit(flat.ctypes.data_as(_dp), len(flat), float(rho_min), float(trim), out))
+    return score.drift_fit_record(list(out))
 
 
 def ptr(t):

@@ -10,7 +10,9 @@ Eval's SDR, SIR and SAR (bsseval.hip: Context.bss_eval / Engine.bss_eval_device;
 `bss_reference`.  Delay estimation for signals that are not aligned (align.hip: Context.align, Context.score(align=...);
 DESIGN.md section 1.13) has its definition in `align_reference`.  LLR, cepstral distance and frequency-weighted
 segmental SNR (quality.hip: Context.quality / Engine.quality_device) have theirs in
-`quality_reference`.  No torch here: the command line imports this."""
+`quality_reference`.  Drift-aware alignment for signals recorded on two clocks (drift.hip: Context.align_drift,
+Context.score(align=..., drift=True)) has its definition in `drift_reference`, `drift_fit` and
+`drift_warp_reference`.  No torch here: the command line imports this."""
 import functools
 import math
 
@@ -479,6 +481,337 @@ def align_cut(e, t, delay):
                          % (d, len(e) if d > 0 else len(t), "estimate" if d > 0 else "target"))
     n = align_common(len(e), len(t), d)
     return e[max(d, 0):max(d, 0) + n], t[max(-d, 0):max(-d, 0) + n]
+
+
+# ---- drift-aware alignment: the float64 definition (include/nhans_hip.h: nhans_drift_*) -----------------
+# Target sample u lines up with position p(u) = a + u + b u of the estimate (a > 0: the estimate is late; b > 0: its clock
+# runs fast).  Every operation is one IEEE double operation rounded to nearest; `_fma` is the fused multiply-add.
+#   table      T = 16, Q = 512: G[q][k] = sinc(x) kaiser(x / T; beta = 10), x = k - q / Q, q = 0 ... Q, k = -T + 1 ... T (column
+#              k + T - 1); row 0 the exact unit impulse; D[q] = G[q + 1] - G[q]  (drift_table; drift_library_table: the library's)
+#   segments   blocks of B = 4096 target samples at hop H = 2048, J = (nt - B) // H + 1 of them (0 for nt < B); segment j's
+#              centre lag z_j = floor(fma(cb, j H + (B - 1) / 2, ca) + 0.5)  (drift_centres)
+#   lag vector c_j[d] = sum_i e[j H + i + d] t[j H + i], d in [z_j - R - T, z_j + R + T]; exactly rounded here (math.fsum of the exact
+#              products), a fixed order of its own on the device
+#   integer    d* in [z_j - R, z_j + R]: the largest c_j[d], then the smaller |d - z_j|, then the larger d
+#   fine peak  v_k at d* + k / 32, k = -32 ... 32: w = floor(k / 32), r = k - 32 w, the chain acc = fma(c_j[d* + w + i], G[16 r][i], acc)
+#              over i = -T + 1 ... T from +0.0 (a lag outside the vector is passed over); the best k: larger value, smaller |k|,
+#              larger k; for |k| < 32: den = (v_{k-1} - 2 v_k) + v_{k+1}, delta = ((v_{k-1} - v_{k+1}) / (2 den)) / 32 clamped to
+#              +-1/64 where den < 0, else 0; tau_j = (d* + k / 32) + delta
+#   abscissa   u_j = j H + (sum_i i t_i^2) / E_t, E_t = sum_i t_i^2 over the block (exactly rounded sums here)
+#   confidence rho_j = v_k / sqrt(E_e E_t), E_e = sum_i e[j H + i + d*]^2
+#   flags      1: d* = z_j -+ R or k = -+32;  2: E_t == 0 or E_e == 0
+#   fit        drift_fit: weighted least squares of tau on u, weights E_t, over the segments with flags == 0 and rho >= rho_min;
+#              one trimming pass at `trim` samples; every sum ascending, every product rounded by itself -- nhans_drift_fit
+#              restated operation by operation
+#   warp       drift_warp_reference: y[u] = float32(chain over k of fma(e[m + k], g_k, acc)), p = fma(b, u, a) + u, m = floor(p),
+#              f = (p - m) Q, q = min(floor(f), Q - 1), g_k = fma(f - q, D[q][k], G[q][k]), over [u_lo, u_hi) = drift_range
+DRIFT_FIELDS = ("u", "tau", "rho", "E_t", "v_peak", "d_int", "flags", "z")     # the NHANS_DRIFT_FIELDS doubles of a segment
+DRIFT_FIT_FIELDS = ("a", "b", "n_valid", "n_used", "rms_residual", "fit_ok")   # the NHANS_DRIFT_FIT_FIELDS doubles of a fit
+DRIFT_T, DRIFT_Q, DRIFT_BLOCK, DRIFT_HOP, DRIFT_MAX_RADIUS, DRIFT_FINE = 16, 512, 4096, 2048, 1024, 32
+DRIFT_MAX_SLOPE, DRIFT_MAX_DELAY = 2.0 ** -10, 2.0 ** 31
+DRIFT_RHO_MIN, DRIFT_TRIM = 0.3, 1.0
+DRIFT_EDGE, DRIFT_SILENT = 1, 2
+
+
+def _two_sum(x, y):
+    s = x + y
+    v = s - x
+    return s, (x - (s - v)) + (y - v)
+
+
+def _fma(a, b, c):
+    """fma(a, b, c) = a b + c rounded once, elementwise on float64 arrays (Boldo & Melquiond 2008: the product split exactly
+    by Dekker, two error-free sums, the two errors added with rounding to odd, one last rounded sum).  Exact while nothing
+    overflows or falls below 2^-969; a lane that is not finite gets a b + c."""
+    a, b, c = np.broadcast_arrays(np.asarray(a, np.float64), np.asarray(b, np.float64), np.asarray(c, np.float64))
+    with np.errstate(all="ignore"):
+        uh = a * b
+        sa, sb = 134217729.0 * a, 134217729.0 * b
+        ah, bh = sa - (sa - a), sb - (sb - b)
+        al, bl = a - ah, b - bh
+        ul = al * bl - (((uh - ah * bh) - al * bh) - ah * bl)
+        th, tl = _two_sum(c, ul)
+        vh, vl = _two_sum(uh, th)
+        s, err = _two_sum(tl, vl)
+        even = (s.view(np.int64) & 1) == 0
+        up = np.nextafter(s, np.where(err > 0, np.inf, -np.inf))
+        z = np.where((err != 0) & even, up, s)
+        r = vh + z
+        return np.where(np.isfinite(r) & np.isfinite(uh), r, a * b + c)
+
+
+def _bessel_i0(x):
+    """the power series sum_k ((x / 2)^k / k!)^2 of the library's design, elementwise"""
+    q = 0.25 * np.asarray(x, np.float64) ** 2
+    term, total = np.ones_like(q), np.ones_like(q)
+    for k in range(1, 200):
+        term = term * (q / (float(k) * float(k)))
+        total = total + term
+        if np.all(term < total * 1e-18):
+            break
+    return total
+
+
+@functools.lru_cache(maxsize=None)
+def drift_table():
+    """-> (G float64 [Q + 1, 2 T], D float64 [Q, 2 T]): the numpy design of the interpolation table"""
+    T, Q = DRIFT_T, DRIFT_Q
+    k = np.arange(-T + 1, T + 1, dtype=np.float64)[None, :]
+    x = k - np.arange(Q + 1, dtype=np.float64)[:, None] / Q
+    G = np.sinc(x) * (_bessel_i0(10.0 * np.sqrt(np.maximum(0.0, 1.0 - (x / T) ** 2))) / _bessel_i0(10.0))
+    G[0] = 0.0
+    G[0, T - 1] = 1.0
+    G.setflags(write=False)
+    D = G[1:] - G[:-1]
+    D.setflags(write=False)
+    return G, D
+
+
+_drift_library_table = None
+
+
+def drift_library_table():
+    """-> (G, D): the very table the library uploads (nhans_drift_table, host only)"""
+    global _drift_library_table
+    if _drift_library_table is None:
+        import ctypes
+        from . import hip
+        T2, Q = 2 * DRIFT_T, DRIFT_Q
+        G, D = np.zeros((Q + 1, T2)), np.zeros((Q, T2))
+        dp = ctypes.POINTER(ctypes.c_double)
+        hip.check(hip.load().nhans_drift_table(G.ctypes.data_as(dp), D.ctypes.data_as(dp)))
+        _drift_library_table = (G, D)
+    return _drift_library_table
+
+
+def drift_segments(nt):
+    return (int(nt) - DRIFT_BLOCK) // DRIFT_HOP + 1 if nt >= DRIFT_BLOCK else 0
+
+
+def drift_centres(ca, cb, J):
+    """-> the J centre lags z_j of the line (ca, cb), Python ints"""
+    x = np.arange(J, dtype=np.float64) * DRIFT_HOP + 0.5 * (DRIFT_BLOCK - 1)
+    return [int(v) for v in np.floor(_fma(float(cb), x, float(ca)) + 0.5)]
+
+
+def drift_pos(a, b, u):
+    """p(u) = fma(b, u, a) + u, elementwise"""
+    u = np.asarray(u, np.float64)
+    return _fma(float(b), u, float(a)) + u
+
+
+def _drift_line_check(who, a, b):
+    if not (math.isfinite(a) and math.isfinite(b)):
+        raise ValueError("%s: the line (%r, %r) is not finite" % (who, a, b))
+    if abs(b) > DRIFT_MAX_SLOPE:
+        raise ValueError("%s: drift %r is outside -2^-10 ... 2^-10" % (who, b))
+    if abs(a) > DRIFT_MAX_DELAY:
+        raise ValueError("%s: delay %r leaves the int32 range" % (who, a))
+
+
+def drift_range(ne, nt, a, b):
+    """-> (u_lo, u_hi): the maximal range of [0, nt) with 0 <= p(u) <= ne - 1, by bisection (p is strictly increasing);
+    (0, 0) where it is empty"""
+    _drift_line_check("drift_range", a, b)
+    if ne <= 0 or nt <= 0:
+        return 0, 0
+
+    def first(pred):
+        lo, hi = 0, int(nt)
+        while lo < hi:
+            mid = (lo + hi) // 2
+            if pred(float(drift_pos(a, b, float(mid)))):
+                hi = mid
+            else:
+                lo = mid + 1
+        return lo
+
+    u_lo, u_hi = first(lambda p: p >= 0.0), first(lambda p: p > float(ne - 1))
+    return (u_lo, u_hi) if u_hi > u_lo else (0, 0)
+
+
+def drift_before(v, d, bv, bd):
+    """(v, d) before (bv, bd): the larger value, then the smaller |d|, then the larger d"""
+    if v != bv:
+        return v > bv
+    return abs(d) < abs(bd) if abs(d) != abs(bd) else d > bd
+
+
+def drift_fine(c, lm, G):
+    """The 65 fine values around the lag at index lm of the lag vector c (float64), each one fma chain over the taps ->
+    float64 [65]"""
+    T, F = DRIFT_T, DRIFT_FINE
+    k = np.arange(-F, F + 1)
+    w = k // F
+    rows = G[(DRIFT_Q // F) * (k - F * w)]                   # [65, 2 T]
+    acc = np.zeros(len(k))
+    for j in range(2 * T):
+        l = lm + w + j - (T - 1)
+        ok = (l >= 0) & (l < len(c))
+        acc = np.where(ok, _fma(c[np.clip(l, 0, len(c) - 1)], rows[:, j], acc), acc)
+    return acc
+
+
+def drift_peak(c, R, z, Et, Ee_of, u0, N, G):
+    """What a segment's record is made of, from its lag vector c (lag z - R - T first), its energy Et and first moment N, and
+    Ee_of(d*) -> the estimate's energy paired at d*: the record as the device forms it, operation by operation."""
+    T, F = DRIFT_T, DRIFT_FINE
+    best, bv = None, None
+    for r in range(-R, R + 1):
+        v = float(c[r + R + T])
+        if best is None or drift_before(v, r, bv, best):
+            best, bv = r, v
+    fine = drift_fine(np.asarray(c, np.float64), best + R + T, G)
+    fk, fv = None, None
+    for i in range(2 * F + 1):
+        if fk is None or drift_before(float(fine[i]), i - F, fv, fk):
+            fk, fv = i - F, float(fine[i])
+    delta = 0.0
+    if -F < fk < F:
+        vm, vp = float(fine[fk + F - 1]), float(fine[fk + F + 1])
+        den = (vm - 2.0 * fv) + vp
+        if den < 0.0:
+            delta = min(max(((vm - vp) / (2.0 * den)) / F, -0.5 / F), 0.5 / F)
+    dstar = z + best
+    Ee = Ee_of(dstar)
+    flags = (DRIFT_EDGE if abs(best) == R or abs(fk) == F else 0) | (DRIFT_SILENT if Et == 0.0 or Ee == 0.0 else 0)
+    with np.errstate(all="ignore"):
+        u = float(np.float64(u0) + np.float64(N) / np.float64(Et))
+        rho = float(np.float64(fv) / np.sqrt(np.float64(Ee) * np.float64(Et)))
+    return {"u": u, "tau": (dstar + fk / F) + delta, "rho": rho, "E_t": float(Et), "v_peak": fv, "d_int": dstar, "flags": flags,
+            "z": z, "k": fk, "E_e": float(Ee), "delta": delta, "fine": fine}
+
+
+def drift_lag_sum(e, tb, x0):
+    """sum_i e[x0 + i] tb[i] over the block tb, samples of e outside the clip being zeros: exactly rounded"""
+    lo, hi = max(0, -x0), min(len(tb), len(e) - x0)
+    return _fsum((e[x0 + lo:x0 + hi] * tb[lo:hi]).tolist()) if hi > lo else 0.0
+
+
+def _drift_moment(tb):
+    """(sum t^2, sum i t^2) of a block, both exactly rounded: a square of a float32 value has 48 bits and is split into two
+    halves whose products with i are exact"""
+    sq = tb * tb
+    hi = sq.astype(np.float32).astype(np.float64)
+    i = np.arange(len(tb), dtype=np.float64)
+    return _fsum(sq.tolist()), _fsum((i * hi).tolist() + (i * (sq - hi)).tolist())
+
+
+def drift_reference(e, t, ca=0.0, cb=0.0, radius=64, corr=False, table=None):
+    """The segments of estimate e against target t (float32 values) tracked around the centre line (ca, cb) within `radius`
+    lags, as the header defines them -> one dict per segment by DRIFT_FIELDS (plus k, E_e, delta and the fine values, for
+    the tests).  Every sum over samples is exactly rounded.  corr=True: plus "corr", the lag vector float64 [2 (R + T) + 1].
+    table: (G, D), by default the numpy design."""
+    R, T, B, H = int(radius), DRIFT_T, DRIFT_BLOCK, DRIFT_HOP
+    if not 1 <= R <= DRIFT_MAX_RADIUS:
+        raise ValueError("drift_reference: radius 1 ... %d" % DRIFT_MAX_RADIUS)
+    _drift_line_check("drift_reference", ca, cb)
+    G = (table or drift_table())[0]
+    e = np.asarray(e, dtype=np.float32).astype(np.float64)
+    t = np.asarray(t, dtype=np.float32).astype(np.float64)
+    out = []
+    for j, z in enumerate(drift_centres(ca, cb, drift_segments(len(t)))):
+        tb = t[j * H:j * H + B]
+        c = np.array([drift_lag_sum(e, tb, j * H + d) for d in range(z - R - T, z + R + T + 1)])
+        Et, N = _drift_moment(tb)
+
+        def Ee_of(d, j=j):
+            lo, hi = max(0, j * H + d), min(len(e), j * H + d + B)
+            return _fsum((e[lo:hi] ** 2).tolist()) if hi > lo else 0.0
+
+        rec = drift_peak(c, R, z, Et, Ee_of, j * H, N, G)
+        if corr:
+            rec["corr"] = c
+        out.append(rec)
+    return out
+
+
+def drift_fit(records, rho_min=DRIFT_RHO_MIN, trim=DRIFT_TRIM):
+    """nhans_drift_fit restated: records (dicts by DRIFT_FIELDS, or rows of NHANS_DRIFT_FIELDS doubles) of one clip -> dict
+    by DRIFT_FIT_FIELDS.  Plain Python floats: every operation below is one rounded double operation, in the library's order."""
+    rows = [[float(r[k]) for k in DRIFT_FIELDS] if isinstance(r, dict) else [float(v) for v in r] for r in records]
+    use = [r for r in rows if r[6] == 0.0 and r[2] >= rho_min]
+    n_valid = len(use)
+    nan = float("nan")
+
+    def fit(use):
+        W = su = st = 0.0
+        for r in use:
+            W = W + r[3]
+            su = su + r[3] * r[0]
+            st = st + r[3] * r[1]
+        if not W > 0.0:
+            return None
+        mu, mt = su / W, st / W
+        Suu = Sut = 0.0
+        for r in use:
+            du, dt = r[0] - mu, r[1] - mt
+            wdu = r[3] * du
+            Suu = Suu + wdu * du
+            Sut = Sut + wdu * dt
+        if not Suu > 0.0:
+            return None
+        b = Sut / Suu
+        return mt - b * mu, b
+
+    res = lambda r, f: r[1] - (f[0] + f[1] * r[0])
+    f = fit(use)
+    if f is not None:
+        kept = [r for r in use if abs(res(r, f)) <= trim]
+        if len(kept) != len(use):
+            use = kept
+            f = fit(use)
+    rms = nan
+    if f is not None:
+        W = S = 0.0
+        for r in use:
+            e = res(r, f)
+            W = W + r[3]
+            S = S + (r[3] * e) * e
+        rms = math.sqrt(S / W)
+    a, b = f if f is not None else (nan, nan)
+    ok = f is not None and len(use) >= 3 and abs(b) <= DRIFT_MAX_SLOPE
+    return {"a": a, "b": b, "n_valid": n_valid, "n_used": len(use), "rms_residual": rms, "fit_ok": int(ok)}
+
+
+def drift_fit_record(values):
+    """the NHANS_DRIFT_FIT_FIELDS doubles of nhans_drift_fit -> dict by DRIFT_FIT_FIELDS"""
+    return {k: (int(values[i]) if k in ("n_valid", "n_used", "fit_ok") else float(values[i])) for i, k in enumerate(DRIFT_FIT_FIELDS)}
+
+
+def drift_segment_record(values):
+    """the NHANS_DRIFT_FIELDS doubles of one segment -> dict by DRIFT_FIELDS"""
+    return {k: (int(values[i]) if k in ("d_int", "flags", "z") else float(values[i])) for i, k in enumerate(DRIFT_FIELDS)}
+
+
+def drift_warp_reference(e, nt, a, b, table=None):
+    """The estimate e (float32 values) resampled at p(u) = a + u + b u for the u of drift_range(len(e), nt, a, b) -> (float32
+    [u_hi - u_lo], u_lo, u_hi): the chain of the header, operation by operation -- with the library's own table
+    (table=drift_library_table()) what the device gives bit for bit.  table: (G, D), by default the numpy design."""
+    T, Q = DRIFT_T, DRIFT_Q
+    G, D = table or drift_table()
+    e = np.asarray(e, dtype=np.float32).astype(np.float64)
+    u_lo, u_hi = drift_range(len(e), int(nt), a, b)
+    if u_hi == u_lo:
+        return np.zeros(0, np.float32), 0, 0
+    p = drift_pos(a, b, np.arange(u_lo, u_hi, dtype=np.float64))
+    fl = np.floor(p)
+    m = fl.astype(np.int64)
+    f = (p - fl) * Q
+    q = np.minimum(f.astype(np.int64), Q - 1)
+    lam = f - q
+    acc = np.zeros(len(p))
+    for j in range(2 * T):
+        x = m + j - (T - 1)
+        ok = (x >= 0) & (x < len(e))
+        ev = np.where(ok, e[np.clip(x, 0, len(e) - 1)], 0.0)
+        acc = _fma(ev, _fma(lam, D[q, j], G[q, j]), acc)
+    return acc.astype(np.float32), u_lo, u_hi
+
+
+def drift_cut(t, u_lo, u_hi):
+    """the target (or a signal that is sample-aligned with it) over the range of a warp"""
+    return t[u_lo:u_hi]
 
 
 # ---- LLR, cepstral distance, fwSegSNR: the float64 definition (include/nhans_hip.h: nhans_quality) -------
