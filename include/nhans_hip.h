@@ -164,6 +164,8 @@ void nhans_destroy(nhans_ctx* ctx);
  *          "bss_group_bytes" (2147483648, default: the bytes of workspace the Gram factors of one group of nhans_bss_eval's
  *           clips may take together; a group holds at least one clip.  A debug value: the grouping changes no bit of any
  *           record, a small value only forces more groups),
+ *          "phase_iters" (0, default, ... 256: Griffin-Lim iterations of nhans_enhance_clips on the denoised rows before
+ *           their iSTFT -- "Phase refinement" below; online and live objects ignore it),
  * (A `make DEV=1` build adds "debug_cycles_ptr" and the NHANS_ABLATE environment switch used by tools/; the default build has no developer hooks and reads no environment.)
  * Besides the workspace a context holds split-K scratch for the few launches that are too small to fill the chip (the
  * head's dense layer, the embedding tower at a few clips): allocated on the first such launch, sized by what the launches
@@ -1260,6 +1262,64 @@ int nhans_drift_track(nhans_ctx* ctx, const float* est_dev, const int64_t* est_o
 int nhans_drift_warp(nhans_ctx* ctx, const float* est_dev, const int64_t* est_offsets_host, const int64_t* tgt_offsets_host,
                      int nclips, const double* a_host, const double* b_host, float* out_dev, const int64_t* out_offsets_host,
                      void* stream);
+
+/* ---- Phase refinement: Griffin-Lim iterations after the mask ---------------------------------------------------------
+ * The enhanced waveform has always been rebuilt from the network's log-magnitudes and the MIXTURE's phase.  These calls
+ * move that phase towards one that is consistent with the magnitudes, on the device, without a waveform reaching HBM
+ * between the inverse and the forward transform (n-hans_amd/csrc/phase.hip; the same definition
+ * in float64: n-hans_amd/phase.py).  Added without moving NHANS_ABI_VERSION; a caller that may meet an older library
+ * looks the functions up by symbol.
+ *
+ * A clip has T >= 1 frames of 201 bins; lm are its log-magnitude rows, A = exp(lm) with nhans_istft's exp, rounded to
+ * float32.  The state t is complex float32 [T, 201], stored as (re, im) pairs.
+ *   u(z)       z / |z|, and 1 + 0j where |z| is zero or below the smallest normal float32 (1.18e-38) -- the convention
+ *              atan2(0, 0) = 0 of nhans_stft_features.  On the device: z times a power of two that brings it into range
+ *              (2^64 below 2^-40, 2^-68 above 2^40), m = re^2 + im^2, r = the hardware reciprocal square root of m
+ *              refined once (r (1.5 - 0.5 m r^2)), u = (re r, im r).  Non-finite z: unspecified.
+ *   P(lm, t)   c = A u(t) (c = 0 for frames outside the clip).  x = inverse 400-point transform, synthesis window and
+ *              overlap-add of c exactly as nhans_istft defines them: the imaginary parts of bins 0 and 200 are dropped,
+ *              two frames share one complex transform, every sample is the sum over its <= 3 frames in ascending order.
+ *              d = analysis window and forward real-input transform of the frames of x exactly as nhans_stft_features
+ *              defines them before its log and angle.  d is complex float32 [T, 201].
+ *   iteration  t_0 = cos ph + i sin ph from the input phases (nhans_istft's sine and cosine).  d_n = P(lm, t_n), then
+ *              t_{n+1} = fma(alpha, d_n - d_{n-1}, d_n) per component with d_{-1} := d_0 (so t_1 = d_0).
+ *   result     after N iterations phase_out = angle(t_N) with nhans_stft_features' atan2.  N = 0 copies the input phases
+ *              bit for bit.  The final waveform is nhans_istft(lm, phase_out).
+ *   inc[n]     sum (|d_n| - A)^2 / sum A^2 over the clip, n = 0 ... N - 1: the relative inconsistency.  |d| is the float32
+ *              square root of re^2 + im^2, the difference is taken in float32, squares and sums are double.  The order is
+ *              fixed: a frame's 201 terms with bins ascending (fma chain), then over the frames of the clip lane l of 64
+ *              sums frames l, l + 64, ... ascending and the 64 sums go through the tree 32, ..., 1 of the scoring kernels.
+ *              NaN where sum A^2 is zero.
+ * There is no log, atan2, sine or cosine inside an iteration: exp(lm) is taken once per call into a plane of its own
+ * and only the last state is turned into angles.  The clip edges are not perfect-reconstruction regions of the window
+ * pair, so P is not idempotent there and inc need not fall monotonically.
+ * Every output has the same bits for a clip alone or in any batch, at any position, on every run.  Inputs are only read;
+ * nothing is written outside the outputs.  The workspace holds the A plane, two state planes (three with momentum) and the
+ * frame partials: 20 (28) bytes per bin.
+ *
+ * nhans_phase_project: one projection.  t_dev and d_out_dev are complex rows [F, 201] (F = frame_offsets_host[nclips]);
+ *   inc_out_dev (nullable) receives one double per clip.
+ * nhans_phase_refine: N = iters iterations (0 <= iters <= 256) with momentum alpha (0 <= alpha < 1; 0 is plain
+ *   Griffin-Lim and the recommended value: 0.99 lowers inc faster and loses SI-SDR after about 8 iterations).
+ *   phase_out_dev [F, 201] may be phase_in_dev itself.  inc_out_dev (nullable) receives double [nclips][iters].
+ * NHANS_EINVAL before anything is launched and with nothing written: a NULL that is needed, nclips < 0, iters or alpha
+ * outside their range, offsets that descend, a clip without a frame or with more than 5,000,000 (the message names it).
+ *
+ * Option "phase_iters" (default 0, 0 ... 256) and nhans_phase_set_alpha (default 0.0): with N > 0 nhans_enhance_clips
+ * refines the denoised rows from the mixture's phase between the mask net and the iSTFT of denoised_wav_dev -- bit for
+ * bit nhans_istft over nhans_phase_refine of the denoised rows and the phase_out_dev tap.  The mixed_wav round trip and
+ * all taps stay as they are (phase_out_dev is the MIXTURE's phase).  With N = 0 the call issues exactly the launches it
+ * always has.  Online and live objects ignore the option: every iteration reaches two frames further into the future
+ * (frame f of d_n depends on frames f - 2 ... f + 2 of t_n), so N iterations would add 2 N frames = 20 N ms of latency
+ * to a stream whose whole look-ahead is 17 frames.
+ * What the iterations are worth on a trained model's rows is unmeasured here (no trained weights ship with the library);
+ * on the clean target's own magnitudes with the mixture's phase they gain 1.4 - 3.7 dB SI-SDR (README). */
+#define NHANS_PHASE_MAX_ITERS 256
+int nhans_phase_set_alpha(nhans_ctx* ctx, double alpha);
+int nhans_phase_project(nhans_ctx* ctx, const float* logmag_dev, const float* t_dev, const int64_t* frame_offsets_host, int nclips,
+                        float* d_out_dev, double* inc_out_dev, void* stream);
+int nhans_phase_refine(nhans_ctx* ctx, const float* logmag_dev, const float* phase_in_dev, const int64_t* frame_offsets_host,
+                       int nclips, int iters, double alpha, float* phase_out_dev, double* inc_out_dev, void* stream);
 
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the

@@ -71,6 +71,8 @@ class Flags(object):
     align_drift = False  # --align_drift: with --align_ms, a line is fitted to the delay over the file and warped out (Context.align_drift)
     quality = False      # --quality: with --score_against, also LLR, cepstral distance and fwSegSNR (score.py: quality_reference is the definition)
     stoi = False         # --stoi: with --score_against, also STOI and extended STOI (score.py: stoi_reference is the definition)
+    phase_iters = 0      # --phase_iters N: Griffin-Lim iterations on the denoised rows before their iSTFT (include/nhans_hip.h: "phase_iters")
+    phase_alpha = 0.0    # --phase_alpha A: their momentum, 0 <= A < 1
     lookahead_ms = 10 * spec.LOOKAHEAD   # --lookahead_ms: 10 ms per frame of look-ahead (include/nhans_hip.h: "lookahead"), 170 = all 17
 
 
@@ -265,6 +267,12 @@ def _lookahead_kw():
     return {} if L == spec.LOOKAHEAD else {"lookahead": L}
 
 
+def _phase_kw():
+    """{} without --phase_iters, for the same reason."""
+    n = int(getattr(FLAGS, "phase_iters", 0) or 0)
+    return {"phase_iters": n, "phase_alpha": float(getattr(FLAGS, "phase_alpha", 0.0))} if n else {}
+
+
 def _enhance_files(kind, mixedpath, ctx_a_path, ctx_b_path):
     """-> (denoised_samples, mixed_processed_samples) float32 for one file triple; ctx order is
     resnet_block argument order."""
@@ -280,7 +288,7 @@ def _enhance_files(kind, mixedpath, ctx_a_path, ctx_b_path):
     if getattr(FLAGS, "online_ms", None):
         res = _enhance_online(eng, mixedpath, ca, cb, FLAGS.online_ms, mixed if FLAGS.convert_on == "gpu" else None)
     else:
-        res = eng.enhance([mixed], [ca], [cb], want_mixed=True, **_lookahead_kw())
+        res = eng.enhance([mixed], [ca], [cb], want_mixed=True, **_lookahead_kw(), **_phase_kw())
     if getattr(FLAGS, "fbank_out", None):
         _write_fbank(eng, mixed, ca, cb, FLAGS.fbank_out)
     if TIMING is not None:
@@ -462,7 +470,7 @@ def _enhance_in_calls(eng, mixes, ca, cb):
         while j < len(mixes) and (j == i or tot + len(mixes[j]) <= MAX_CALL_SAMPLES):
             tot += len(mixes[j])
             j += 1
-        res = eng.enhance(mixes[i:j], ca[i:j], cb[i:j], want_mixed=True, **_lookahead_kw())
+        res = eng.enhance(mixes[i:j], ca[i:j], cb[i:j], want_mixed=True, **_lookahead_kw(), **_phase_kw())
         outs.extend(zip(res["denoised_wav"], res["mixed_wav"]))
         i = j
     return outs
@@ -533,13 +541,14 @@ def finish_distributed():
 
 
 # ------------------------------------------------------------------------------ demo / eval mode
-def _enhance_after_context(eng, mix_wav, ctx_a_wav, ctx_b_wav, extra_wavs=()):
+def _enhance_after_context(eng, mix_wav, ctx_a_wav, ctx_b_wav, extra_wavs=(), phase_iters=0, phase_alpha=0.0):
     """Shared by apply_demo and the evaluation reader (SN/apply.py:247-266, SN/reader.py:398-409):
     the first Noise_Win frames of the two conditioning signals are the contexts, and the network
     runs on the mixture's frames FROM Noise_Win ON, windowed as a clip of its own (zero rows before
     frame Noise_Win, not the preceding frames).  Uses the stage-level C ABI.  Returns
     (denoised_samples, mixed_samples, [iSTFT of each extra signal's frames from Noise_Win on],
-    logits, denoised_logmag)."""
+    logits, denoised_logmag).  phase_iters > 0: the denoised samples from phases refined on the denoised rows
+    (Engine.phase_refine_rows, from the mixture's); everything else as without."""
     import torch
     dev = eng.device
     wavs = [mix_wav] + list(extra_wavs)
@@ -558,7 +567,7 @@ def _enhance_after_context(eng, mix_wav, ctx_a_wav, ctx_b_wav, extra_wavs=()):
     lm_s, ph_s = lm[Noise_Win:t].contiguous(), ph[Noise_Win:t].contiguous()
     n = t - Noise_Win
     logits, den = eng.mask_net(lm_s, [0, n], emb[0:1], emb[1:2])
-    den_wav, _ = eng.istft(den, ph_s, [0, n])
+    den_wav, _ = eng.istft(den, eng.phase_refine_rows(den, ph_s, [0, n], phase_iters, phase_alpha) if phase_iters else ph_s, [0, n])
     mix_rt, _ = eng.istft(lm_s, ph_s, [0, n])
     extras, f0 = [], t
     for k in nfr[1:]:
@@ -617,7 +626,7 @@ def apply_demo_separator(cleanpath, noisepath, save_to, mix_on="host"):
 
 
 def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelname='nhans', step=0, scores=False, mix_on="host",
-                       stoi=False, bss=False, quality=False):
+                       stoi=False, bss=False, quality=False, phase_iters=0, phase_alpha=0.0):
     """Evaluation-reader pipeline for one (speech, pos noise, neg noise) triple: SN/reader.py:310-420
     (eval branch, eval_stride 1) + SN/main.py:264-353.  Mixes at the reference's md5-derived SNRs,
     runs the network on frames from context_frames on, writes the reference's five wavs
@@ -634,13 +643,17 @@ def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelnam
     quality=True (with scores): the records also carry LLR, cepstral distance and fwSegSNR of the same waveforms
     (Engine.quality_device, merged by score.merge_quality) and the improvement llr_i, llr_95_i, cd_i, cd_95_i (lower is
     better: an improvement is negative) and fwsegsnr_i; the files and the loss are what they are without it.
+    phase_iters > 0: the denoised waveform -- the file and every waveform figure of it -- from phases refined by that many
+    Griffin-Lim iterations of momentum phase_alpha (Engine.phase_refine_rows); the loss, the row figures and the other four
+    files are what they are without it.
     A corpus at several SNR pairs in one pass: evaluate_corpus."""
     from . import mixing
     eng = get_engine(spec.DENOISER)
     target, pos_sig, neg_sig, mixed, snr_pos, snr_neg = _mixed_signals(
         mix_on, eng, cleanpath, noisepospath, noisenegpath, snrs=mixing.eval_snrs(cleanpath))
     den, mix_rt, extras, _, den_lm, mix_lm = _enhance_after_context(eng, mixed, pos_sig, neg_sig,
-                                                                    extra_wavs=(target, pos_sig, neg_sig))
+                                                                    extra_wavs=(target, pos_sig, neg_sig),
+                                                                    phase_iters=phase_iters, phase_alpha=phase_alpha)
     import torch
     tgt_lm, _ = eng.stft_features(torch.from_numpy(np.asarray(target, dtype=np.float32)).to(eng.device), [0, len(target)], 0, False)
     tgt_lm = tgt_lm[Noise_Win:].cpu().numpy()
@@ -658,13 +671,41 @@ def evaluate_utterance(cleanpath, noisepospath, noisenegpath, dump_dir, modelnam
     return loss
 
 
+def phase_ceiling(engine, mixed, target, iters=(0, 8, 32), alpha=0.0):
+    """What a perfect mask could reach with and without phase refinement: the clean target's own magnitudes with the
+    mixture's phase, refined by each count of `iters` Griffin-Lim iterations on the device (Engine.phase_refine_rows) and
+    scored against the target (Engine.score_device).  mixed, target: float32 waveforms of one length, trimmed to whole
+    frames -> one record per count: score.FIELDS of the rebuilt waveform against the target, plus "iters" and "inc" (the
+    inconsistency of every iteration, float64 [iters]).  The trained model's own rows are not the target's: what the
+    iterations gain there is a different figure."""
+    import torch
+    from . import score
+    mixed, target = (np.ascontiguousarray(x, dtype=np.float32) for x in (mixed, target))
+    if len(mixed) != len(target):
+        raise ValueError("phase_ceiling: mixture and target of one length")
+    n = len(target)
+    both = torch.from_numpy(np.concatenate([target, mixed])).to(engine.device)
+    lm, ph = engine.stft_features(both, [0, n, 2 * n])
+    t = lm.shape[0] // 2
+    if t == 0:
+        raise ValueError("phase_ceiling: fewer than %d samples: no STFT frame" % spec.WIN)
+    tlm, mph = lm[:t].contiguous(), ph[t:].contiguous()
+    out = []
+    for k in iters:
+        rph, inc = engine.phase_refine_rows(tlm, mph, [0, t], int(k), alpha, inc=True)
+        wav, ooff = engine.istft(tlm, rph, [0, t])
+        rec = score.record(engine.score_device(wav, ooff, both[:n].contiguous(), [0, n])[0].cpu().numpy())
+        out.append(dict(rec, iters=int(k), inc=inc[0].cpu().numpy()))
+    return out
+
+
 def _eval_wav_path(dump_dir, modelname, step, triple, snr_pos, snr_neg, kind):
     base = [os.path.basename(p)[:-4] for p in triple]
     return os.path.join(dump_dir, '{}_{}_{}_{}_{}_{}_{}_{}.wav'.format(modelname, step, base[0], base[1], base[2], snr_pos, snr_neg, kind))
 
 
 def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None, per_frame=False, modelname='nhans', step=0,
-                    stoi=False, bss=False, quality=False):
+                    stoi=False, bss=False, quality=False, phase_iters=0, phase_alpha=0.0):
     """evaluate_utterance(scores=True) for a corpus in one pass.  triples: (cleanpath, pospath, negpath) each; snrs: the
     (snr_pos, snr_neg) pairs applied to every triple (None: the triple's own mixing.eval_snrs).  The files are read,
     normalised and trimmed on the host and uploaded once; the mixtures of all (triple, SNR pair) jobs (Engine.mix_device),
@@ -679,7 +720,7 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
     evaluate_utterance(scores=True, stoi=True) merges them, bit for bit; only their records come back.  bss=True: SDR, SIR
     and SAR against each job's own target and negative noise, which the mixing left in HBM, likewise.  quality=True: LLR,
     cepstral distance and fwSegSNR in the same pass, as evaluate_utterance(scores=True, quality=True) merges them, bit for
-    bit."""
+    bit.  phase_iters, phase_alpha: as evaluate_utterance's, the refinement of all jobs in the same pass."""
     from . import context, mixing, score
     eng = get_engine(spec.DENOISER)
     speech, noises, jobs, meta = [], [], [], []
@@ -700,7 +741,7 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
     sig, off, mix_rec = eng.mix_device(sp_t, sp_off, nz_t, nz_off, jobs)
     dump = dump_dir is not None
     res = eng._with_lookahead(lookahead, lambda: context.redo_saturated_in_f32(
-        eng, lambda: _corpus_device(eng, sig, off, per_frame, dump, stoi, bss, quality)))
+        eng, lambda: _corpus_device(eng, sig, off, per_frame, dump, stoi, bss, quality, (int(phase_iters), float(phase_alpha)))))
     eng._sync()
     mix_rec = mix_rec.cpu().numpy()
     down = {k: v.cpu().numpy() for k, v in res["records"].items()}
@@ -732,7 +773,7 @@ def evaluate_corpus(triples, snrs=None, lookahead=spec.LOOKAHEAD, dump_dir=None,
     return out
 
 
-def _corpus_device(eng, sig, off, per_frame, dump, stoi=False, bss=False, quality=False):
+def _corpus_device(eng, sig, off, per_frame, dump, stoi=False, bss=False, quality=False, refine=(0, 0.0)):
     """The launches of evaluate_corpus after the mixing, everything in HBM: job j's signals are [off[j], off[j + 1]) of
     sig's tensors -> device records (and, for a dump, waveforms)."""
     import torch
@@ -753,7 +794,7 @@ def _corpus_device(eng, sig, off, per_frame, dump, stoi=False, bss=False, qualit
     emb = eng.embed(torch.cat([kl, dl]).view(2 * J, Noise_Win, spec.BINS))
     lm_s, ph_s, tlm_s, tph_s = rest(lm), rest(ph), rest(tlm), rest(tph)
     _, den = eng.mask_net(lm_s, roff, emb[:J], emb[J:], want_logits=False)
-    den_wav, ooff = eng.istft(den, ph_s, roff)
+    den_wav, ooff = eng.istft(den, eng.phase_refine_rows(den, ph_s, roff, *refine) if refine[0] else ph_s, roff)
     mix_rt, _ = eng.istft(lm_s, ph_s, roff)
     tgt_wav, _ = eng.istft(tlm_s, tph_s, roff)
     records, frames = {}, {}
@@ -839,6 +880,10 @@ def _parse(argv, prog):
                    help='future audio every output frame may use: a multiple of 10 in 0 ... 170 (default 170, all 17 frames '
                         'of the window).  Less is what a live stream of that look-ahead would have produced -- latency '
                         '10 ms per frame + 25 ms -- at a cost in quality that depends on the trained model')
+    p.add_argument('--phase_iters', type=int, default=0, metavar='N',
+                   help='Griffin-Lim iterations on the denoised rows, from the mixture\'s phase, before the denoised file is rebuilt '
+                        '(0 ... 256; default 0: the mixture\'s phase as it is; offline only)')
+    p.add_argument('--phase_alpha', type=float, default=0.0, metavar='A', help='momentum of --phase_iters, 0 <= A < 1 (default 0)')
     p.add_argument('--fbank_out', default=None, metavar='PATH.npy',
                    help='file mode only: also write the log-mel filterbank features of the denoised signal (float32 '
                         '[frames, n_mels], 25 ms / 10 ms frames, numpy.save) computed on the device from the network\'s '
@@ -936,6 +981,12 @@ def _parse(argv, prog):
         if a.output_rate != 'input' or a.convert_on != 'gpu' or not a.convert:
             p.error('--highband needs --output_rate input --convert_on gpu (and no --no-convert): the band is added at the '
                     'input file\'s own rate, on the device')
+    if not 0 <= a.phase_iters <= 256:
+        p.error('--phase_iters must be in 0 ... 256; got %d' % a.phase_iters)
+    if not 0.0 <= a.phase_alpha < 1.0:
+        p.error('--phase_alpha must be in [0, 1); got %g' % a.phase_alpha)
+    if a.phase_iters and a.online_ms is not None:
+        p.error('--phase_iters does not go with --online_ms: every iteration reaches two frames further into the future')
     if a.online_ms is not None:
         if a.online_ms <= 0:
             p.error('--online_ms must be positive')

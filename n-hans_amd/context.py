@@ -74,6 +74,21 @@ class Context:
         finally:
             self.set_option("lookahead", spec.LOOKAHEAD)
 
+    def _with_phase(self, iters, alpha, run):
+        """run() with the option "phase_iters" at `iters` Griffin-Lim iterations of momentum `alpha` (include/nhans_hip.h:
+        nhans_phase_*) and back at none afterwards, whatever run() did."""
+        if not iters:
+            return run()
+        if not 0 < int(iters) <= hip.PHASE_MAX_ITERS:
+            raise ValueError("phase_iters 0 ... %d, not %r" % (hip.PHASE_MAX_ITERS, iters))
+        hip.check(self.lib.nhans_phase_set_alpha(self.handle, float(alpha)))
+        self.set_option("phase_iters", int(iters))
+        try:
+            return run()
+        finally:
+            self.set_option("phase_iters", 0)
+            hip.check(self.lib.nhans_phase_set_alpha(self.handle, 0.0))
+
     # ---- filterbank features of the enhanced clips (include/nhans_hip.h: nhans_fbank_*) --------
     def features(self, mixes, ctx_a, ctx_b, fb, lookahead=spec.LOOKAHEAD, mixed=False):
         """Lists of normalised float32 waveforms (mixtures trimmed, as enhance takes them) -> one float32 [T_i, fb.n_mels]

@@ -382,6 +382,10 @@ int nhans_set_option(nhans_ctx* c, const char* key, int64_t value) {
         if (value < 1) return fail(NHANS_EINVAL, "bss_group_bytes < 1");
         c->bss_group_bytes = (size_t)value;
     }
+    else if (k == "phase_iters") {
+        if (value < 0 || value > kPhaseMaxIters) return fail(NHANS_EINVAL, "phase_iters must be in [0, " + std::to_string(kPhaseMaxIters) + "]");
+        c->phase_iters = (int)value;
+    }
     else if (k == "profile") c->profile = value != 0;
     else if (k == "debug_cycles_ptr") {
         if (!kDev) return fail(NHANS_EINVAL, "debug_cycles_ptr exists only in a NHANS_DEV build (make DEV=1)");

@@ -17,7 +17,8 @@
 //   host_align.hip    nhans_align, nhans_align_common, nhans_align_cut
 //   host_quality.hip  nhans_quality, nhans_quality_lpc, nhans_quality_tables
 //   host_drift.hip    nhans_drift_table, nhans_drift_segments, nhans_drift_range, nhans_drift_fit, nhans_drift_track, nhans_drift_warp
-// A unit calls down only: ctx <- net <- online <- live, ctx <- fbank <- online, ctx <- rate <- live, ctx <- score, ctx <- mix, ctx <- rate <- stoi, ctx <- bsseval, ctx <- align, ctx <- quality and ctx <- drift.  (One call goes up: the built-in calibration
+//   host_phase.hip    nhans_phase_project, nhans_phase_refine, nhans_phase_set_alpha; the refinement inside nhans_enhance_clips
+// A unit calls down only: ctx <- net <- online <- live, ctx <- fbank <- online, ctx <- rate <- live, ctx <- score, ctx <- mix, ctx <- rate <- stoi, ctx <- bsseval, ctx <- align, ctx <- quality, ctx <- drift and ctx <- phase <- net.  (One call goes up: the built-in calibration
 // of nhans_create runs the whole offline path, enhance_clips_body.)  Only what crosses a unit boundary is declared here;
 // everything else stays in its unit's anonymous namespace.
 // Nothing declared here joins the library's dynamic symbols (visibility hidden) except the object types the C header
@@ -108,6 +109,8 @@ struct nhans_ctx {
     int contexts_per_chunk = 64;
     size_t bss_group_bytes = (size_t)2 << 30;   // option bss_group_bytes: the factor storage one group of nhans_bss_eval's clips may take (host_bsseval.hip; same bits)
     int lookahead = kCenter;    // option lookahead: frame t of a clip sees the clip end at min(len, t + lookahead + 1) (offline calls)
+    int phase_iters = 0;        // option phase_iters: Griffin-Lim iterations of nhans_enhance_clips between mask net and iSTFT (0: none)
+    double phase_alpha = 0.0;   // nhans_phase_set_alpha: their momentum
     // pinned staging ring for the small host tables (offsets, block lists) copied per call
     char* pin = nullptr;
     size_t pin_bytes = (size_t)16 << 20, pin_top = 0;
@@ -246,6 +249,21 @@ using PairBody = std::function<int(int i, const float* e, const float* t, int64_
 int pair_clips(const std::string& fn, const char* verb, const float* est, const int64_t* eoff, const float* tgt, const int64_t* toff,
                int nclips, const void* out, const PairBody& body);
 int null_clip(const std::string& fn, int i, int64_t n);        // the refusal of clip i: n samples and a null buffer
+
+// ---- host_phase.hip -------------------------------------------------------------------------------
+// The scratch of a refinement of `total` frames in nclips clips, declared once: the A plane, two state planes, the d
+// plane (momentum only), the frame partials, the tables.  phase_refine_run issues the launches of iters >= 1 iterations
+// from phase_in to phase_out (may be the same rows); inc_out (nullable): [nclips][iters] doubles.
+struct PhaseBufs {
+    float *A, *t[2], *d;
+    double *num, *den;
+    int64_t* foff_dev;
+    int* blocks;
+    size_t nblocks;
+};
+void phase_plan(WsPlan& p, const int64_t* foff, int nclips, bool momentum, PhaseBufs* pb);
+int phase_refine_run(nhans_ctx* c, const float* logmag, const float* phase_in, const int64_t* foff, int nclips, int iters, double alpha,
+                     float* phase_out, double* inc_out, const PhaseBufs& pb, hipStream_t s);
 
 // ---- host_net.hip ---------------------------------------------------------------------------------
 struct StackBufs {

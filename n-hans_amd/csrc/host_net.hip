@@ -648,6 +648,15 @@ int enhance_clips_body(nhans_ctx* c, const float* mix, const int64_t* moff, int 
     tower_plan(p, c, &tb);
     p.rewind(shared);
     stack_plan(p, c, total, nclips, wf, &sb);
+    // option phase_iters: the refinement's planes share that place too (the stack is done with its buffers by then), and its
+    // result is a plane of its own -- the phase_out_dev tap and the mixed_wav round trip keep the mixture's phase
+    const bool refine = c->phase_iters > 0 && total > 0;
+    PhaseBufs pb; float* ph_ref = nullptr;
+    if (refine) {
+        p.rewind(shared);
+        p.add(&ph_ref, (size_t)total * kBins);
+        phase_plan(p, foff.data(), nclips, c->phase_alpha != 0.0, &pb);
+    }
     rc = ws_commit(c, p); if (rc) return rc;
 
     rc = stft_impl(c, mix, moff, nclips, 0, lm, ph, tabs[0], blks[0], nullptr, s); if (rc) return rc;
@@ -659,7 +668,11 @@ int enhance_clips_body(nhans_ctx* c, const float* mix, const int64_t* moff, int 
     if (total > 0) {
         rc = mask_net_impl(c, false, lm, foff.data(), nclips, emb, emb + (size_t)nclips * kEmb, lg, den, &sb, wf, s);
         if (rc) return rc;
-        rc = istft_impl(c, den, ph, foff.data(), nclips, moff, den_wav, tabs[3], blks[3], s); if (rc) return rc;
+        if (refine) {
+            rc = phase_refine_run(c, den, ph, foff.data(), nclips, c->phase_iters, c->phase_alpha, ph_ref, nullptr, pb, s);
+            if (rc) return rc;
+        }
+        rc = istft_impl(c, den, refine ? ph_ref : ph, foff.data(), nclips, moff, den_wav, tabs[3], blks[3], s); if (rc) return rc;
         if (mixed_wav) {
             // tabs/blks[3] are reused: same stream, so the first launch has consumed them in order
             rc = istft_impl(c, lm, ph, foff.data(), nclips, moff, mixed_wav, tabs[3], blks[3], s); if (rc) return rc;

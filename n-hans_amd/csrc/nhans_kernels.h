@@ -302,6 +302,27 @@ constexpr int64_t kMaxFramesPerClip = 5000000;   // 13.9 h: the STFT / iSTFT ker
 constexpr int kIstftHopsPerBlock = 22;    // output hops per block; needs 24 frames
 
 // ---------------------------------------------------------------------------------------------
+// Phase refinement (phase.hip; include/nhans_hip.h: nhans_phase_*).  Complex planes are [frames, 201] pairs of float32
+// (re, im).  One projection launch: d = P(A, t) per clip of frame_off_dev, workgroups walking the (clip, first frame) runs
+// of kPhaseRun frames in block_clip / block_f0 -- 24 inverse transforms (the run and two halo frames either side), the
+// span's overlap-add in LDS, kPhaseRun forward transforms.  d_prev (nullable): t_out = d + alpha (d - d_prev), else
+// t_out = d; d_out may be d_prev itself (an element is read and written by one lane); d_out, t_out and num (nullable) are
+// written for the frames of the clip only.  num[frame] = sum_k (|d| - A)^2 in double, bins ascending.
+constexpr int kPhaseRun = 20;
+constexpr int kPhaseMaxIters = 256;
+void launch_phase_project(const float* A, const float* t_in, const int64_t* frame_off_dev, const int* block_clip, const int* block_f0,
+                          int nblocks, const float* tw400, const float* window, const float* wsyn, const float* d_prev, float alpha,
+                          float* d_out, float* t_out, double* num, hipStream_t s);
+// A = exp(logmag) and den[frame] = sum_k A^2 (double, bins ascending); phase (nullable, with t0): t0 = cos + i sin
+void launch_phase_prepare(const float* logmag, const float* phase, int64_t nframes, float* A, float* t0, double* den, hipStream_t s);
+// phase_out = angle(t), n elements
+void launch_phase_angle(const float* t, int64_t n, float* phase_out, hipStream_t s);
+// inc_out[clip * stride + col] = sum num / sum den over the clip's frames: lane l of 64 sums frames l, l + 64, ... ascending,
+// the 64 sums by wave_sum (score_common.h)
+void launch_phase_inc(const double* num, const double* den, const int64_t* frame_off_dev, int nclips, double* inc_out, int stride, int col,
+                      hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // Sample-rate conversion and the file front end (resample.hip; include/nhans_hip.h: nhans_resample*)
 // The filter of scipy.signal.resample_poly(x, L, M), designed on the host in double.  tab = the taps rounded to float32,
 // phase-minor: tab[j * L + p] = h[p + j * L] (0 beyond the last tap), padded to a multiple of 4 floats.

@@ -21,73 +21,11 @@
 //   registers before the current run is transformed; the windowed frames land in an LDS buffer that aliases the
 //   (wavefront-private) transform areas; overlap-add is in gather form (each output sample summed from its <= 3
 //   frames in ascending order, four samples per lane: no atomics, bitwise deterministic).
-// log/atan2/exp/sincos run on the hardware transcendental units (below).
-#include "nhans_kernels.h"
-#include "fft400.h"
+// log/atan2/exp/sincos run on the hardware transcendental units (stft_common.h: that math, the
+// access forms and the transpose geometry, shared with phase.hip).
+#include "stft_common.h"
 
 namespace nhans {
-
-constexpr int kFpw = 3;                 // iSTFT: transforms per wavefront
-constexpr int kTRow = 21;               // padded transpose row (complex values)
-constexpr int kTFrame = 20 * kTRow;     // 420 complex per frame
-// ---- feature math on the hardware transcendental units.  Both kernels are VALU-bound once their loads
-// are pipelined (PMC: 490 VALU wave-instructions per frame, two thirds of them libm's atan2f / logf /
-// sincosf / expf with their full-range reductions); the ranges here are narrow and float32-level accuracy
-// is all the path can use (phase 1.7e-7 rad, magnitudes ~2e-7 relative).
-__device__ __forceinline__ float fast_atan2(float y, float x) {
-    const float ax = fabsf(x), ay = fabsf(y);
-    const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    // v_rcp_f32 takes no denormal input: it answers inf, and mn * inf is inf or NaN.  A bin whose larger component is below
-    // the smallest normal number (a magnitude under 1.7e-38 beside the 1e-5 floor) counts as zero magnitude on the axis of
-    // that component: 0, +-pi/2 or +-pi.  Normal inputs take the same instructions as before, bit for bit.
-    const float r = mx >= 1.17549435e-38f ? mn * __builtin_amdgcn_rcpf(mx) : 0.f;     // atan2(0, 0) = 0 like libm
-    const float t = r * r;
-    // minimax fit of atan(r)/r in r^2 on [0, 1]: 1.7e-7 rad in float32 arithmetic
-    float p = -0.004733146633952856f;
-    p = fmaf(p, t, 0.024376805871725082f);
-    p = fmaf(p, t, -0.0596301406621933f);
-    p = fmaf(p, t, 0.09921535104513168f);
-    p = fmaf(p, t, -0.140206977725029f);
-    p = fmaf(p, t, 0.1996956467628479f);
-    p = fmaf(p, t, -0.3333193361759186f);
-    p = fmaf(p, t, 0.9999998807907104f);
-    float a = p * r;
-    a = ay > ax ? 1.57079632679489662f - a : a;
-    a = x < 0.f ? 3.14159265358979324f - a : a;
-    return copysignf(a, y);
-}
-__device__ __forceinline__ float fast_log(float v) {           // v >= 1e-5: v_log_f32 is log2, 1 ulp
-    return __builtin_amdgcn_logf(v) * 0.69314718055994531f;
-}
-__device__ __forceinline__ float fast_exp(float x) {           // |x| < 60; the product x*log2(e) carried as hi + lo
-    const float hi = x * 1.44269504088896341f;
-    const float lo = fmaf(x, 1.44269504088896341f, -hi) + x * 1.925963033500e-8f;
-    return __builtin_amdgcn_exp2f(hi) * fmaf(lo, 0.69314718055994531f, 1.0f);
-}
-__device__ __forceinline__ void fast_sincos(float a, float* sn, float* cs) {   // |a| <= pi: v_sin/v_cos take revolutions
-    const float rev = a * 0.15915494309189535f;
-    *sn = __builtin_amdgcn_sinf(rev);
-    *cs = __builtin_amdgcn_cosf(rev);
-}
-
-
-// Global access as (wave-uniform 64-bit base) + (32-bit BYTE offset per lane): the form the scalar-base global
-// instructions take directly; element indexing would make the compiler widen every offset to 64 bits first.
-__device__ __forceinline__ float ldg32(const float* base, unsigned byte_off) {
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-__device__ __forceinline__ void stg32(float* base, unsigned byte_off, float v) {
-    *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_off) = v;
-}
-
-// A wavefront's transpose / spectrum area is private to it: its lanes exchange data through it with no
-// workgroup barrier, only "my LDS traffic has completed" (lanes of a wave run in lockstep).
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // The ANALYSIS transform is one real frame per transform, but a REAL one: pass 1 computes rows k1 = 0..10 of the
 // 20 x 20 decomposition from real columns (fft400.h: rdft20_half -- the conjugate-symmetric half, with the k1 = 3
@@ -98,9 +36,6 @@ __device__ __forceinline__ void wave_lds_sync() {
 // built and taken out: it leaks float32 rounding of the louder frame into the quieter one, log(|X| + 1e-5)
 // amplifies that at silent bins -- 1.25e-4 instead of 7e-5 on the separator's context embeddings, past the 1e-4
 // bar.  The inverse transform below does pack two frames: there the leak is 1e-7 of a waveform sample.)
-constexpr int kRows = 11;                    // rows k1 = 0..10 of the transposed intermediate
-constexpr int kTReal = kRows * kTRow;        // 231 complex per frame
-
 __global__ void __launch_bounds__(256) stft_features_kernel(
     const float* __restrict__ wav, ClipTable tab, const int* __restrict__ block_clip,
     const int* __restrict__ block_f0, int nblocks, const cplx* __restrict__ tw400g, const float* __restrict__ windowg,

@@ -13,7 +13,7 @@
 #include <cstddef>
 
 struct WsPlan {
-    static constexpr int kCap = 40;     // the largest plan, a live push with the stack inside it, declares 27
+    static constexpr int kCap = 40;     // the largest plan, nhans_enhance_clips with its phase refinement, declares 35 (a live push: 27)
     static constexpr size_t round_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
     template <typename T> void add(T** slot, size_t count) {

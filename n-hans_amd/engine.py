@@ -149,6 +149,38 @@ class Engine(context.Context):
                                        len(frame_off) - 1, hip.i64_array(ooff), hip.ptr(out), self._stream()))
         return out, ooff
 
+    # ---- phase refinement (include/nhans_hip.h: nhans_phase_*) ----------------------------------------
+    def _phase_rows_check(self, who, frame_off, real, cplx=()):
+        for t in real:
+            if t.dim() != 2 or t.shape != (int(frame_off[-1]), spec.BINS) or t.dtype != torch.float32:
+                raise ValueError("%s: float32 [%d, %d] rows" % (who, frame_off[-1], spec.BINS))
+        for t in cplx:
+            if t.shape != (int(frame_off[-1]), spec.BINS) or t.dtype != torch.complex64:
+                raise ValueError("%s: a complex64 [%d, %d] state" % (who, frame_off[-1], spec.BINS))
+
+    def phase_project_rows(self, logmag, t, frame_off, inc=False):
+        """One projection d = P(logmag, t) of device tensors: logmag float32 [F, 201], t complex64 [F, 201], clip i = rows
+        frame_off[i]:frame_off[i + 1] -> d complex64 [F, 201]; inc=True: -> (d, float64 [n]: each clip's inconsistency)."""
+        self._phase_rows_check("phase_project_rows", frame_off, (logmag,), (t,))
+        n = len(frame_off) - 1
+        d = torch.empty_like(t)
+        ic = torch.empty(max(n, 1), dtype=torch.float64, device=self.device) if inc else None
+        hip.check(self.lib.nhans_phase_project(self.handle, hip.ptr(logmag.contiguous()), hip.ptr(torch.view_as_real(t.contiguous())),
+                                               hip.i64_array(frame_off), n, hip.ptr(torch.view_as_real(d)), hip.ptr(ic), self._stream()))
+        return (d, ic[:n]) if inc else d
+
+    def phase_refine_rows(self, logmag, phase, frame_off, iters, alpha=0.0, inc=False):
+        """iters Griffin-Lim iterations of momentum alpha on device tensors: logmag and phase float32 [F, 201], clip i = rows
+        frame_off[i]:frame_off[i + 1] -> the refined phases, float32 [F, 201] (iters = 0: the input's bits); inc=True: ->
+        (that, float64 [n, iters]: inc[n] of every clip).  The waveform is istft(logmag, refined phases, frame_off)."""
+        self._phase_rows_check("phase_refine_rows", frame_off, (logmag, phase))
+        n, N = len(frame_off) - 1, int(iters)
+        out = torch.empty_like(phase)
+        ic = torch.empty((max(n, 1), max(N, 1)), dtype=torch.float64, device=self.device) if inc else None
+        hip.check(self.lib.nhans_phase_refine(self.handle, hip.ptr(logmag.contiguous()), hip.ptr(phase.contiguous()),
+                                              hip.i64_array(frame_off), n, N, float(alpha), hip.ptr(out), hip.ptr(ic), self._stream()))
+        return (out, ic[:n, :N].contiguous() if N else ic[:n, :0]) if inc else out
+
     def fbank_rows(self, rows_t, fb):
         """fb (fbank.Filterbank) applied to a device tensor of [n, 201] float32 log-magnitude rows -- mask_net's denoised
         rows, or stft_features' logmag for the unprocessed signal -- -> device tensor [n, fb.n_mels]."""
@@ -380,11 +412,15 @@ class Engine(context.Context):
             hip.ptr(res.get("emb")), self._stream()))
         return res
 
-    def enhance(self, mixes, ctx_a, ctx_b, want_mixed=True, taps=False, lookahead=spec.LOOKAHEAD):
+    def enhance(self, mixes, ctx_a, ctx_b, want_mixed=True, taps=False, lookahead=spec.LOOKAHEAD, phase_iters=0, phase_alpha=0.0):
         """Lists of normalised float32 waveforms (mixtures trimmed) -> per-clip numpy results.  lookahead: L frames,
         0 .. 17 (include/nhans_hip.h, option "lookahead": frame g sees its clip end at g + L + 1) -- what a live stream
-        of that look-ahead emits for the same samples; the saturation redo runs with the same L."""
-        return self._with_lookahead(lookahead, lambda: self._enhance(mixes, ctx_a, ctx_b, want_mixed, taps))
+        of that look-ahead emits for the same samples; the saturation redo runs with the same L.  phase_iters: Griffin-Lim
+        iterations (momentum phase_alpha) on the denoised rows, from the mixture's phase, before their iSTFT (option
+        "phase_iters"; 0: the mixture's phase as it is); the mixed round trip and the taps stay as they are, and the redo
+        runs the iterations too."""
+        return self._with_phase(phase_iters, phase_alpha, lambda: self._with_lookahead(
+            lookahead, lambda: self._enhance(mixes, ctx_a, ctx_b, want_mixed, taps)))
 
     def _enhance(self, mixes, ctx_a, ctx_b, want_mixed, taps):
         mix_t, mix_off = self._dev(mixes)

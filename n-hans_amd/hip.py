@@ -147,6 +147,10 @@ SIGNATURES = {
     "nhans_drift_fit": (_int, [_dp, _int, _dbl, _dbl, _dp]),
     "nhans_drift_track": (_int, [_vp, _vp, _i64p, _vp, _i64p, _int, _dp, _dp, _int, _vp, _vp, _vp]),
     "nhans_drift_warp": (_int, [_vp, _vp, _i64p, _i64p, _int, _dp, _dp, _vp, _i64p, _vp]),
+    # phase refinement: Griffin-Lim iterations after the mask
+    "nhans_phase_set_alpha": (_int, [_vp, _dbl]),
+    "nhans_phase_project": (_int, [_vp, _vp, _vp, _i64p, _int, _vp, _vp, _vp]),
+    "nhans_phase_refine": (_int, [_vp, _vp, _vp, _i64p, _int, _int, _dbl, _vp, _vp, _vp]),
     "nhans_profile_json": (_int, [_vp, _str, _size]),
     "nhans_profile_reset": (_int, [_vp]),
 }
@@ -184,6 +188,8 @@ QUALITY_FIELDS, QUALITY_LPC_FIELDS = 16, 72
 QUALITY_FRAME, QUALITY_HOP, QUALITY_ORDER, QUALITY_FFT, QUALITY_BINS = 480, 120, 16, 512, 257
 QUALITY_BANDS, QUALITY_MAX_BANDS = 25, 32
 QUALITY_LPC_TILE, QUALITY_BAND_TILE = 7, 2  # frames per workgroup of quality.hip's LPC and band launches (kQualityLpcTile, kQualityBandTile)
+PHASE_MAX_ITERS = 256
+PHASE_RUN = 20                              # frames per run of phase.hip's projection (kPhaseRun)
 MIX_TILE = 2048                             # samples per workgroup and per staging buffer of mix.hip (kMixTile)
 STATUS_SATURATED = 1
 NUM_ACTIVATIONS = 25

@@ -32,11 +32,13 @@ class LiteEngine(context.Context):
         self.handle = handle
         self.set_precision(precision)
 
-    def enhance(self, mixes, ctx_a, ctx_b, want_mixed=True, lookahead=spec.LOOKAHEAD):
+    def enhance(self, mixes, ctx_a, ctx_b, want_mixed=True, lookahead=spec.LOOKAHEAD, phase_iters=0, phase_alpha=0.0):
         """Lists of normalised float32 waveforms (mixtures trimmed) -> {"denoised_wav": [...], "mixed_wav": [...]}; the same
-        saturation fallback as engine.Engine.enhance (the batch redone on the exact-f32 matrix path, exponents raised) and
-        the same lookahead (L frames, 0 .. 17; the redo runs with the same L)."""
-        return self._with_lookahead(lookahead, lambda: self._enhance(mixes, ctx_a, ctx_b, want_mixed))
+        saturation fallback as engine.Engine.enhance (the batch redone on the exact-f32 matrix path, exponents raised),
+        the same lookahead (L frames, 0 .. 17; the redo runs with the same L) and the same phase refinement (phase_iters
+        Griffin-Lim iterations of momentum phase_alpha on the denoised rows; the redo runs them too)."""
+        return self._with_phase(phase_iters, phase_alpha, lambda: self._with_lookahead(
+            lookahead, lambda: self._enhance(mixes, ctx_a, ctx_b, want_mixed)))
 
     def _enhance(self, mixes, ctx_a, ctx_b, want_mixed):
         (mf, off), (af, aoff), (bf, boff) = context.flat(mixes), context.flat(ctx_a), context.flat(ctx_b)

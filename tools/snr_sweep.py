@@ -6,7 +6,7 @@ over the mixture, per (snr_pos, snr_neg, look-ahead).  The recordings are read a
 ON THE SYNTHETIC WEIGHTS THESE NUMBERS SAY NOTHING ABOUT QUALITY: a seeded random network denoises nothing.  The tool is
 for whoever has the trained bundle -- point NHANS_MODEL_DIR at it and pass --weights checkpoint; with the synthetic
 weights it shows that the plumbing runs.
-    python tools/snr_sweep.py DIR [--snrs -3,0,3,5,8] [--lookaheads 17,8,2] [--weights synthetic] [--json out.json] [--stoi] [--bss] [--quality]
+    python tools/snr_sweep.py DIR [--snrs -3,0,3,5,8] [--lookaheads 17,8,2] [--weights synthetic] [--json out.json] [--stoi] [--bss] [--quality] [--phase_iters N]
   --stoi adds the columns stoi_i and estoi_i: STOI and extended STOI in the same pass (NaN for a job whose output is too
   short for one 30-frame segment: 4,097 samples at 10 kHz).
   --bss adds the columns sdr_i, sir_i and sar_i: BSS Eval against each job's own target and negative noise, in the same
@@ -76,6 +76,7 @@ def main(argv=None):
     ap.add_argument("--lookaheads", default=str(spec.LOOKAHEAD))
     ap.add_argument("--weights", default="synthetic", choices=["synthetic", "checkpoint"])
     ap.add_argument("--json", default=None, help="also write the rows as JSON")
+    ap.add_argument("--phase_iters", type=int, default=0, help="Griffin-Lim iterations on the denoised rows before their iSTFT (default 0)")
     ap.add_argument("--stoi", action="store_true", help="also the mean improvements of STOI and extended STOI: stoi_i, estoi_i")
     ap.add_argument("--bss", action="store_true", help="also the mean improvements of BSS Eval's SDR, SIR and SAR: sdr_i, sir_i, sar_i")
     ap.add_argument("--quality", action="store_true",
@@ -101,7 +102,7 @@ def main(argv=None):
         pairs = [(p, n) for p in grid for n in grid]
         rows = []
         for L in las:
-            rows += summarise(apply.evaluate_corpus(triples, snrs=pairs, lookahead=L, stoi=a.stoi, bss=a.bss, quality=a.quality), L, figures)
+            rows += summarise(apply.evaluate_corpus(triples, snrs=pairs, lookahead=L, stoi=a.stoi, bss=a.bss, quality=a.quality, phase_iters=a.phase_iters), L, figures)
         print("%d triples x %d SNR pairs x %d look-aheads, weights: %s" % (len(triples), len(pairs), len(las), a.weights))
         print(table(rows, figures))
         if a.json:
