@@ -38,38 +38,38 @@ int nhans_align(nhans_ctx* c, const float* est, const int64_t* eoff, const float
         return NHANS_OK;
     });
     if (rc) return rc;
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    if (nclips == 0) return call.finish(NHANS_OK);
-    const size_t nlags = (size_t)2 * D + 1;
-    WsPlan p;
-    AlignRun* runs_dev; double* corr;
-    p.add(&runs_dev, runs.size());
-    p.add(&corr, corr_out ? 0 : runs.size() * nlags);
-    rc = ws_commit(c, p); if (rc) return call.finish(rc);
-    if (corr_out) corr = corr_out;
-    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(AlignRun), call.s); if (rc) return call.finish(rc);
-    const double C = (double)nclips, NL = (double)nlags;
-    double flops = 0.0, samples = 0.0, staged = 0.0;
-    if (c->profile) {
-        const double nblk = (double)((nlags + kAlignLagBlock - 1) / kAlignLagBlock);
-        for (const AlignRun& r : runs) {
-            flops += align_flops(r.ne, r.nt, D);
-            samples += (double)(r.ne + r.nt);
-            staged += nblk * (double)((r.nt + kAlignTile - 1) / kAlignTile) * (2.0 * kAlignTile + kAlignLagBlock);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (nclips == 0) return NHANS_OK;
+        const size_t nlags = (size_t)2 * D + 1;
+        WsPlan p;
+        AlignRun* runs_dev; double* corr;
+        p.add(&runs_dev, runs.size());
+        p.add(&corr, corr_out ? 0 : runs.size() * nlags);
+        rc = ws_commit(c, p); if (rc) return rc;
+        if (corr_out) corr = corr_out;
+        rc = h2d(c, runs_dev, runs, s); if (rc) return rc;
+        const double C = (double)nclips, NL = (double)nlags;
+        double flops = 0.0, samples = 0.0, staged = 0.0;
+        if (c->profile) {
+            const double nblk = (double)((nlags + kAlignLagBlock - 1) / kAlignLagBlock);
+            for (const AlignRun& r : runs) {
+                flops += align_flops(r.ne, r.nt, D);
+                samples += (double)(r.ne + r.nt);
+                staged += nblk * (double)((r.nt + kAlignTile - 1) / kAlignTile) * (2.0 * kAlignTile + kAlignLagBlock);
+            }
         }
-    }
-    {   // per lag and common sample: one fused multiply-add; a workgroup fetches a tile of t and the span of e it meets
-        Prof pr(c, call.s, "align_corr");
-        launch_align_corr("align_corr", runs_dev, nclips, D, corr, call.s);
-        pr.done(flops, 4.0 * staged + 8.0 * C * NL);
-    }
-    {
-        Prof pr(c, call.s, "align_pick");
-        launch_align_pick("align_pick", runs_dev, nclips, D, corr, out, call.s);
-        pr.done(2.0 * samples + C * NL, 4.0 * samples + 8.0 * C * NL + 8.0 * kAlignFields * C);
-    }
-    return call.finish(NHANS_OK);
+        {   // per lag and common sample: one fused multiply-add; a workgroup fetches a tile of t and the span of e it meets
+            Prof pr(c, s, "align_corr");
+            launch_align_corr("align_corr", runs_dev, nclips, D, corr, s);
+            pr.done(flops, 4.0 * staged + 8.0 * C * NL);
+        }
+        {
+            Prof pr(c, s, "align_pick");
+            launch_align_pick("align_pick", runs_dev, nclips, D, corr, out, s);
+            pr.done(2.0 * samples + C * NL, 4.0 * samples + 8.0 * C * NL + 8.0 * kAlignFields * C);
+        }
+        return NHANS_OK;
+    });
 }
 
 int nhans_align_cut(nhans_ctx* c, const float* est, const int64_t* eoff, const float* tgt, const int64_t* toff, int nclips,
@@ -106,17 +106,17 @@ int nhans_align_cut(nhans_ctx* c, const float* est, const int64_t* eoff, const f
         }
     }
     if (tiles > 0x7fffffffLL) return fail(NHANS_EINVAL, fn + ": too many samples for one call (split it)");
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    if (jobs.empty()) return call.finish(NHANS_OK);
-    AlignCopy* jobs_dev;
-    rc = ws_upload(c, jobs, call.s, &jobs_dev); if (rc) return call.finish(rc);
-    {
-        Prof pr(c, call.s, "align_cut");
-        launch_align_cut("align_cut", jobs_dev, (int)jobs.size(), tiles, call.s);
-        pr.done(0.0, 8.0 * total);
-    }
-    return call.finish(NHANS_OK);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (jobs.empty()) return NHANS_OK;
+        AlignCopy* jobs_dev;
+        rc = ws_upload(c, jobs, s, &jobs_dev); if (rc) return rc;
+        {
+            Prof pr(c, s, "align_cut");
+            launch_align_cut("align_cut", jobs_dev, (int)jobs.size(), tiles, s);
+            pr.done(0.0, 8.0 * total);
+        }
+        return NHANS_OK;
+    });
 }
 
 }  // extern "C"

@@ -173,20 +173,20 @@ int nhans_drift_track(nhans_ctx* c, const float* est, const int64_t* eoff, const
     });
     if (rc) return rc;
     if (segs.size() > 0x7fffffffu) return fail(NHANS_EINVAL, fn + ": too many segments for one call (split it)");
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    if (segs.empty()) return call.finish(NHANS_OK);
-    const double* tab;
-    rc = drift_tab_dev(c, &tab); if (rc) return call.finish(rc);
-    DriftSeg* segs_dev;
-    rc = ws_upload(c, segs, call.s, &segs_dev); if (rc) return call.finish(rc);
-    {   // per segment and lag 4,096 fused multiply-adds; a workgroup fetches its block of t and the span of e it meets
-        const double S = (double)segs.size(), NL = 2.0 * (R + kDriftT) + 1.0;
-        Prof pr(c, call.s, "drift_track");
-        launch_drift_track("drift_track", segs_dev, (int)segs.size(), R, tab, out, corr_out, call.s);
-        pr.done(2.0 * S * NL * kDriftBlock, S * (4.0 * (2.0 * kDriftBlock + NL) + 8.0 * kDriftFields + (corr_out ? 8.0 * NL : 0.0)));
-    }
-    return call.finish(NHANS_OK);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (segs.empty()) return NHANS_OK;
+        const double* tab;
+        rc = drift_tab_dev(c, &tab); if (rc) return rc;
+        DriftSeg* segs_dev;
+        rc = ws_upload(c, segs, s, &segs_dev); if (rc) return rc;
+        {   // per segment and lag 4,096 fused multiply-adds; a workgroup fetches its block of t and the span of e it meets
+            const double S = (double)segs.size(), NL = 2.0 * (R + kDriftT) + 1.0;
+            Prof pr(c, s, "drift_track");
+            launch_drift_track("drift_track", segs_dev, (int)segs.size(), R, tab, out, corr_out, s);
+            pr.done(2.0 * S * NL * kDriftBlock, S * (4.0 * (2.0 * kDriftBlock + NL) + 8.0 * kDriftFields + (corr_out ? 8.0 * NL : 0.0)));
+        }
+        return NHANS_OK;
+    });
 }
 
 int nhans_drift_warp(nhans_ctx* c, const float* est, const int64_t* eoff, const int64_t* toff, int nclips, const double* a,
@@ -218,19 +218,19 @@ int nhans_drift_warp(nhans_ctx* c, const float* est, const int64_t* eoff, const 
         total += (double)(hi - lo);
     }
     if (tiles > 0x7fffffffLL) return fail(NHANS_EINVAL, fn + ": too many samples for one call (split it)");
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    if (jobs.empty()) return call.finish(NHANS_OK);
-    const double* tab;
-    rc = drift_tab_dev(c, &tab); if (rc) return call.finish(rc);
-    DriftWarp* jobs_dev;
-    rc = ws_upload(c, jobs, call.s, &jobs_dev); if (rc) return call.finish(rc);
-    {   // per output 32 taps, two fused multiply-adds each (the coefficient, the sum); it reads about as many samples as it writes
-        Prof pr(c, call.s, "drift_warp");
-        launch_drift_warp("drift_warp", jobs_dev, (int)jobs.size(), tiles, tab, call.s);
-        pr.done(8.0 * kDriftT * total, 8.0 * total + 8.0 * (kDriftTableG + kDriftTableD));
-    }
-    return call.finish(NHANS_OK);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (jobs.empty()) return NHANS_OK;
+        const double* tab;
+        rc = drift_tab_dev(c, &tab); if (rc) return rc;
+        DriftWarp* jobs_dev;
+        rc = ws_upload(c, jobs, s, &jobs_dev); if (rc) return rc;
+        {   // per output 32 taps, two fused multiply-adds each (the coefficient, the sum); it reads about as many samples as it writes
+            Prof pr(c, s, "drift_warp");
+            launch_drift_warp("drift_warp", jobs_dev, (int)jobs.size(), tiles, tab, s);
+            pr.done(8.0 * kDriftT * total, 8.0 * total + 8.0 * (kDriftTableG + kDriftTableD));
+        }
+        return NHANS_OK;
+    });
 }
 
 }  // extern "C"

@@ -99,7 +99,7 @@ int fbank_launch(nhans_ctx* c, const FbankTable& t, const char* name, const Fban
     }
     if (runs.empty()) return NHANS_OK;
     if (tiles > 0x7fffffffLL) return fail(NHANS_EINVAL, std::string(name) + ": too many rows for one launch (split the call)");
-    const int rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(FbankRun), s); if (rc) return rc;
+    const int rc = h2d(c, runs_dev, runs, s); if (rc) return rc;
     Prof pr(c, s, name);
     launch_fbank(name, runs_dev, (int)runs.size(), tiles, t.dev, t.n_out, t.nspan, t.power, t.floor, s);
     pr.done((double)total * (2.0 * t.nspan + kBins + t.n_out), (double)total * 4.0 * (kBins + t.n_out));
@@ -143,14 +143,14 @@ int nhans_fbank_open(nhans_ctx* c, const double* w, int n_out, int power, double
     // (the matrix first: what it refuses needs no device)
     FbankTable host;
     int rc = table_build("nhans_fbank_open", w, n_out, power, floor, &host); if (rc) return rc;
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    nhans_fbank* fb = new nhans_fbank();
-    fb->c = c; fb->device = c->device;
-    rc = fbank_table_clone(host, "nhans_fbank_open", &fb->t);
-    if (rc) { delete fb; return call.finish(rc); }
-    *out = fb;
-    return call.finish(NHANS_OK);
+    return ctx_call(c, stream, [&](hipStream_t) -> int {
+        nhans_fbank* fb = new nhans_fbank();
+        fb->c = c; fb->device = c->device;
+        rc = fbank_table_clone(host, "nhans_fbank_open", &fb->t);
+        if (rc) { delete fb; return rc; }
+        *out = fb;
+        return NHANS_OK;
+    });
 }
 
 void nhans_fbank_close(nhans_fbank* fb) {

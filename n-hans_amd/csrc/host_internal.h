@@ -161,13 +161,17 @@ int ws_commit(nhans_ctx* c, const WsPlan& p);
 // Host -> device copy of a small table through the pinned ring, so the caller's (pageable, soon
 // destroyed) buffer is never the source of an in-flight asynchronous copy.
 int h2d(nhans_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t s);
+// a whole host table to the device array of its element type
+template <typename T> int h2d(nhans_ctx* c, T* dst, const std::vector<T>& v, hipStream_t s) {
+    return h2d(c, dst, v.data(), v.size() * sizeof(T), s);
+}
 
 // The plan of a call whose only scratch is one host table: room for it, and its copy on s.
 template <typename T> int ws_upload(nhans_ctx* c, const std::vector<T>& v, hipStream_t s, T** dev) {
     WsPlan p;
     p.add(dev, v.size());
     const int rc = ws_commit(c, p); if (rc) return rc;
-    return h2d(c, *dev, v.data(), v.size() * sizeof(T), s);
+    return h2d(c, *dev, v, s);
 }
 
 // RAII-less profiling bracket around one launch
@@ -206,33 +210,49 @@ int check_ctx(nhans_ctx* c);
 // A launch the runtime rejected anywhere in the sequence just issued -> NHANS_EHIP.
 int launch_status();
 
-// Bracket of one hot-path entry point: selects the device, orders the call behind the previous
+// Bracket of one stream-taking entry point: selects the device, orders the call behind the previous
 // call on this context when that one ran on another stream (they share workspace, pinned tables
 // and split-K tickets), and on the way out collects launch failures and marks the new tail.
-struct Call {
+// Nothing of it is public: bracket_call below is the only code that can open or close one, and the entry points
+// reach it through ctx_call, object_call and object_count_call -- a body cannot return past the way out.
+class Call {
     nhans_ctx* c;
     hipStream_t s;
     int rc;
     Call(nhans_ctx* c_, void* stream);
     int finish(int body_rc);
+    template <typename Body> friend int64_t bracket_call(nhans_ctx* c, void* stream, Body body);
 };
 
-// The same bracket for an entry point of an object that holds its context (nhans_online, nhans_resampler, nhans_live):
-// the null check with the entry point's own message first, then body(stream) inside the Call.
-template <typename Obj, typename Body>
-int object_call(Obj* o, const char* null_msg, void* stream, Body body) {
-    if (!o) return fail(NHANS_EINVAL, null_msg);
-    Call call(o->c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(body(call.s));
-}
-
-// The bracket for an entry point of the context itself: body(stream) inside the Call.
+// body(stream) inside the Call.  What the body returns is a status (negative: every code but NHANS_OK is) or a count
+// (>= 0; NHANS_OK is the count 0), and so is what comes back: the first of the Call's own refusal, the body's status and
+// a failed launch -- else the body's count.
 template <typename Body>
-int ctx_call(nhans_ctx* c, void* stream, Body body) {
+int64_t bracket_call(nhans_ctx* c, void* stream, Body body) {
     Call call(c, stream);
     if (call.rc) return call.rc;
-    return call.finish(body(call.s));
+    const int64_t n = body(call.s);
+    const int rc = call.finish(n < 0 ? (int)n : NHANS_OK);
+    return rc ? rc : n;
+}
+
+// The bracket for an entry point of the context itself; its body returns a status.
+template <typename Body>
+int ctx_call(nhans_ctx* c, void* stream, Body body) {
+    return (int)bracket_call(c, stream, body);
+}
+
+// The bracket for an entry point of an object that holds its context (nhans_online, nhans_resampler, nhans_live,
+// nhans_fbank): the null check with the entry point's own message first.  object_count_call: the body returns an
+// int64_t, a count or a negative status.
+template <typename Obj, typename Body>
+int64_t object_count_call(Obj* o, const char* null_msg, void* stream, Body body) {
+    if (!o) return fail(NHANS_EINVAL, null_msg);
+    return bracket_call(o->c, stream, body);
+}
+template <typename Obj, typename Body>
+int object_call(Obj* o, const char* null_msg, void* stream, Body body) {
+    return (int)object_count_call(o, null_msg, stream, body);
 }
 
 // argument checks the streaming objects share
@@ -291,7 +311,7 @@ int mask_net_run(nhans_ctx* c, const float* win_src, const int* rb, const float*
 int enhance_clips_body(nhans_ctx* c, const float* mix, const int64_t* moff, int nclips, const float* ca,
                        const int64_t* caoff, const float* cbw, const int64_t* cboff, float* den_wav,
                        float* mixed_wav, float* logmag_out, float* phase_out, float* logits_out, float* emb_out,
-                       void* stream);
+                       hipStream_t s);
 
 // ---- host_fbank.hip --------------------------------------------------------------------------------
 // A filterbank as the kernel reads it (nhans_kernels.h: the band table) with its device copy.  The host words are kept:

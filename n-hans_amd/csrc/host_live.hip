@@ -249,12 +249,14 @@ int live_push_body(nhans_live* o, const char* fn_, const void* in, const int64_t
     if (rc || launch_error_pending()) return rc;          // (a launch error is reported by the entry point; no stage has committed)
     rc = online_push_body(o->on, o->mid, moff.data(), end, o->den, o->mix, ooff.data(), got.data(), s);
     if (rc || launch_error_pending()) { o->in.restore(was_in); return rc; }
+    // a failure from here on: both stages that have committed go back
+    auto unwind = [&](int status) { o->in.restore(was_in); online_undo(o->on); o->can_rewind = false; return status; };
     // (an object that never enabled its meter takes none of the branches below: launch for launch the push it was)
     std::vector<int64_t> woff;
     LevelMeter::Slots lv_next;
     if (o->lv.on) {
         rc = live_level(o, ooff.data(), end, s, &woff, &lv_next);
-        if (rc || launch_error_pending()) { o->in.restore(was_in); online_undo(o->on); o->can_rewind = false; return rc; }
+        if (rc || launch_error_pending()) return unwind(rc);
     }
     const bool auto_wet = o->lv.on && o->lv.auto_wet;
     const GainTab gains{o->lv.wtab, woff.data()};
@@ -264,7 +266,7 @@ int live_push_body(nhans_live* o, const char* fn_, const void* in, const int64_t
     HighBandIo hb{};
     if (o->fb.on) {
         rc = live_hold(o, in, pos.data(), il_in, keep.data(), n_old.data(), cnts.data(), s, &fb_next);
-        if (rc || launch_error_pending()) { o->in.restore(was_in); online_undo(o->on); o->can_rewind = false; return rc; }
+        if (rc || launch_error_pending()) return unwind(rc);
         for (int i = 0; i < S; ++i) halves.push_back(o->fb_half(o->fb.st.cur[i], i));
         hb = {o->fb.gain.data(), halves.data(), o->fb.st.base.data(), n_old.data(), cnts.data(), pos.data(), in, o->in_format,
               il_in ? il_in->ch : 0, il_in ? il_in->n : 0, o->in_denom};
@@ -273,7 +275,7 @@ int live_push_body(nhans_live* o, const char* fn_, const void* in, const int64_t
                     {true, o->out_format, 0, o->wet, o->out_scale, auto_wet, il_out != nullptr, o->fb.on}, o->den,
                     auto_wet || o->wet != 0.f || o->fb.on ? o->mix : nullptr, ooff.data(), end, out, outoff, counts, s,
                     auto_wet ? &gains : nullptr, il_out, o->fb.on ? &hb : nullptr);
-    if (rc || launch_error_pending()) { o->in.restore(was_in); online_undo(o->on); o->can_rewind = false; return rc; }
+    if (rc || launch_error_pending()) return unwind(rc);
     o->undo_in = was_in; o->undo_out = was_out;
     if (o->fb.on) {
         o->undo_fb = o->fb.st;
@@ -455,10 +457,10 @@ int nhans_live_open_slots(nhans_ctx* c, int nslots, int rate_in, int in_format, 
                           double out_scale, int flags, void* stream, nhans_live** out) {
     if (!out) return fail(NHANS_EINVAL, "nhans_live_open_slots: null argument");
     *out = nullptr;
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(live_open_body("nhans_live_open_slots", "nslots", c, nslots, 1, rate_in, in_format, peak, rate_out, out_format,
-                                      out_scale, flags, call.s, out));
+    return ctx_call(c, stream, [&](hipStream_t s) {
+        return live_open_body("nhans_live_open_slots", "nslots", c, nslots, 1, rate_in, in_format, peak, rate_out, out_format, out_scale,
+                              flags, s, out);
+    });
 }
 
 int nhans_interleaved_live_open(nhans_ctx* c, int nstreams, int channels_in, int channels_out, int mode, int rate_in, int in_format,
@@ -467,25 +469,25 @@ int nhans_interleaved_live_open(nhans_ctx* c, int nstreams, int channels_in, int
     const std::string fn = "nhans_interleaved_live_open";
     if (!out) return fail(NHANS_EINVAL, fn + ": null argument");
     *out = nullptr;
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    for (int ch : {channels_in, channels_out})
-        if (ch < 1 || ch > NHANS_INTERLEAVED_MAX_CHANNELS)
-            return call.finish(fail(NHANS_EINVAL, fn + ": channels_in and channels_out must be in 1 ... " +
-                                                  std::to_string(NHANS_INTERLEAVED_MAX_CHANNELS) + " (got " + std::to_string(channels_in) +
-                                                  " and " + std::to_string(channels_out) + ")"));
-    if (mode != NHANS_INTERLEAVED_DOWNMIX && mode != NHANS_INTERLEAVED_SPLIT)
-        return call.finish(fail(NHANS_EINVAL, fn + ": mode must be NHANS_INTERLEAVED_DOWNMIX or NHANS_INTERLEAVED_SPLIT"));
-    if (mode == NHANS_INTERLEAVED_SPLIT && channels_in != channels_out)
-        return call.finish(fail(NHANS_EINVAL, fn + ": NHANS_INTERLEAVED_SPLIT needs channels_in == channels_out (got " +
-                                              std::to_string(channels_in) + " and " + std::to_string(channels_out) + ")"));
-    const int K = mode == NHANS_INTERLEAVED_SPLIT ? channels_in : 1;
-    const int rc = live_open_body("nhans_interleaved_live_open", "nstreams", c, nstreams, K, rate_in, in_format, peak, rate_out,
-                                  out_format, out_scale, flags, call.s, out);
-    if (rc) return call.finish(rc);
-    (*out)->fr.on = true;
-    (*out)->fr.Ci = channels_in; (*out)->fr.Co = channels_out; (*out)->fr.G = nstreams; (*out)->fr.K = K;
-    return call.finish(NHANS_OK);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        for (int ch : {channels_in, channels_out})
+            if (ch < 1 || ch > NHANS_INTERLEAVED_MAX_CHANNELS)
+                return fail(NHANS_EINVAL, fn + ": channels_in and channels_out must be in 1 ... " +
+                                          std::to_string(NHANS_INTERLEAVED_MAX_CHANNELS) + " (got " + std::to_string(channels_in) +
+                                          " and " + std::to_string(channels_out) + ")");
+        if (mode != NHANS_INTERLEAVED_DOWNMIX && mode != NHANS_INTERLEAVED_SPLIT)
+            return fail(NHANS_EINVAL, fn + ": mode must be NHANS_INTERLEAVED_DOWNMIX or NHANS_INTERLEAVED_SPLIT");
+        if (mode == NHANS_INTERLEAVED_SPLIT && channels_in != channels_out)
+            return fail(NHANS_EINVAL, fn + ": NHANS_INTERLEAVED_SPLIT needs channels_in == channels_out (got " +
+                                      std::to_string(channels_in) + " and " + std::to_string(channels_out) + ")");
+        const int K = mode == NHANS_INTERLEAVED_SPLIT ? channels_in : 1;
+        const int rc = live_open_body("nhans_interleaved_live_open", "nstreams", c, nstreams, K, rate_in, in_format, peak, rate_out,
+                                      out_format, out_scale, flags, s, out);
+        if (rc) return rc;
+        (*out)->fr.on = true;
+        (*out)->fr.Ci = channels_in; (*out)->fr.Co = channels_out; (*out)->fr.G = nstreams; (*out)->fr.K = K;
+        return NHANS_OK;
+    });
 }
 
 int nhans_live_restart(nhans_live* o, int slot) {
@@ -502,26 +504,24 @@ int nhans_live_restart(nhans_live* o, int slot) {
 
 int nhans_live_set_context(nhans_live* o, int slot, const float* ca, int64_t na, const float* cbw, int64_t nb, void* stream,
                            int64_t* first_frame_out) {
-    if (!o) return fail(NHANS_EINVAL, "nhans_live_set_context: null object");
-    Call call(o->c, stream);
-    if (call.rc) return call.rc;
-    int rc = slot_check(o->S, slot, "nhans_live_set_context"); if (rc) return call.finish(rc);
-    if (!ca || !cbw) return call.finish(fail(NHANS_EINVAL, "nhans_live_set_context: null argument"));
-    if (na < 0 || nb < 0) return call.finish(fail(NHANS_EINVAL, "nhans_live_set_context: negative sample count"));
-    rc = online_set_context_body(o->on, slot, ca, na, cbw, nb, call.s, first_frame_out);
-    if (!rc && !launch_error_pending()) o->can_rewind = false;
-    return call.finish(rc);
+    return object_call(o, "nhans_live_set_context: null object", stream, [&](hipStream_t s) -> int {
+        int rc = slot_check(o->S, slot, "nhans_live_set_context"); if (rc) return rc;
+        if (!ca || !cbw) return fail(NHANS_EINVAL, "nhans_live_set_context: null argument");
+        if (na < 0 || nb < 0) return fail(NHANS_EINVAL, "nhans_live_set_context: negative sample count");
+        rc = online_set_context_body(o->on, slot, ca, na, cbw, nb, s, first_frame_out);
+        if (!rc && !launch_error_pending()) o->can_rewind = false;
+        return rc;
+    });
 }
 
 int nhans_live_set_embeddings(nhans_live* o, int slot, const float* ea, const float* eb, void* stream, int64_t* first_frame_out) {
-    if (!o) return fail(NHANS_EINVAL, "nhans_live_set_embeddings: null object");
-    Call call(o->c, stream);
-    if (call.rc) return call.rc;
-    int rc = slot_check(o->S, slot, "nhans_live_set_embeddings"); if (rc) return call.finish(rc);
-    if (!ea || !eb) return call.finish(fail(NHANS_EINVAL, "nhans_live_set_embeddings: null argument"));
-    rc = online_set_embeddings_body(o->on, slot, ea, eb, call.s, first_frame_out);
-    if (!rc) o->can_rewind = false;
-    return call.finish(rc);
+    return object_call(o, "nhans_live_set_embeddings: null object", stream, [&](hipStream_t s) -> int {
+        int rc = slot_check(o->S, slot, "nhans_live_set_embeddings"); if (rc) return rc;
+        if (!ea || !eb) return fail(NHANS_EINVAL, "nhans_live_set_embeddings: null argument");
+        rc = online_set_embeddings_body(o->on, slot, ea, eb, s, first_frame_out);
+        if (!rc) o->can_rewind = false;
+        return rc;
+    });
 }
 
 int nhans_live_set_wet(nhans_live* o, double wet) {
@@ -594,12 +594,11 @@ int nhans_capture_live_enable(nhans_live* o, void* stream) {
 
 int nhans_capture_live_context(nhans_live* o, int n, const int* slots, const int* which, int flags, void* stream,
                                int64_t* first_frame_out) {
-    if (!o) return fail(NHANS_EINVAL, "nhans_capture_live_context: null object");
-    Call call(o->c, stream);
-    if (call.rc) return call.rc;
-    const int rc = capture_context_body(o->on, "nhans_capture_live_context", n, slots, which, flags, call.s, first_frame_out);
-    if (!rc && !launch_error_pending()) o->can_rewind = false;
-    return call.finish(rc);
+    return object_call(o, "nhans_capture_live_context: null object", stream, [&](hipStream_t s) {
+        const int rc = capture_context_body(o->on, "nhans_capture_live_context", n, slots, which, flags, s, first_frame_out);
+        if (!rc && !launch_error_pending()) o->can_rewind = false;
+        return rc;
+    });
 }
 
 int nhans_capture_live_embeddings(const nhans_live* o, int slot, float* ea, float* eb, void* stream) {
@@ -614,12 +613,9 @@ int nhans_fbank_live_attach(nhans_live* o, nhans_fbank* fb, int flags) {
 }
 
 int64_t nhans_fbank_live_read(nhans_live* o, int slot, int plane, float* out, int64_t cap_rows, int64_t* first_frame_out, void* stream) {
-    if (!o) return fail(NHANS_EINVAL, "nhans_fbank_live_read: null object");
-    Call call(o->c, stream);
-    if (call.rc) return call.rc;
-    const int64_t n = fbank_read_body(o->on, "nhans_fbank_live_read", slot, plane, out, cap_rows, first_frame_out, call.s);
-    const int rc = call.finish(n < 0 ? (int)n : NHANS_OK);
-    return rc ? rc : n;
+    return object_count_call(o, "nhans_fbank_live_read: null object", stream, [&](hipStream_t s) {
+        return fbank_read_body(o->on, "nhans_fbank_live_read", slot, plane, out, cap_rows, first_frame_out, s);
+    });
 }
 
 // ---- level meter and automatic compensation (include/nhans_hip.h: nhans_level_*) ----
@@ -629,23 +625,22 @@ int64_t nhans_level_hops(int64_t emitted, int ended) {
 }
 
 int nhans_level_live_enable(nhans_live* o, void* stream) {
-    if (!o) return fail(NHANS_EINVAL, "nhans_level_live_enable: null object");
-    Call call(o->c, stream);
-    if (call.rc) return call.rc;
-    if (!o->has_wet)
-        return call.finish(fail(NHANS_EINVAL, "nhans_level_live_enable: the object was opened without NHANS_LIVE_WET "
-                                              "(the meter reads the mixed round trip)"));
-    if (o->lv.on) return call.finish(NHANS_OK);
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->lv.state), (size_t)2 * o->S * kLevelState * sizeof(double));
-    if (e != hipSuccess)
-        return call.finish(fail(NHANS_ENOMEM, std::string("nhans_level_live_enable: hipMalloc failed: ") + hipGetErrorString(e)));
-    // (nothing is cleared: a slot's first hop h0 reads none of the state)
-    o->lv.st.h0.resize(o->S);
-    for (int i = 0; i < o->S; ++i) o->lv.st.h0[i] = level_hops(o->out.st.N[i], o->out.st.ended[i]);
-    o->lv.st.cur.assign(o->S, 0);
-    o->lv.on = true;
-    o->can_rewind = false;
-    return call.finish(NHANS_OK);
+    return object_call(o, "nhans_level_live_enable: null object", stream, [&](hipStream_t) -> int {
+        if (!o->has_wet)
+            return fail(NHANS_EINVAL, "nhans_level_live_enable: the object was opened without NHANS_LIVE_WET "
+                                      "(the meter reads the mixed round trip)");
+        if (o->lv.on) return NHANS_OK;
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->lv.state), (size_t)2 * o->S * kLevelState * sizeof(double));
+        if (e != hipSuccess)
+            return fail(NHANS_ENOMEM, std::string("nhans_level_live_enable: hipMalloc failed: ") + hipGetErrorString(e));
+        // (nothing is cleared: a slot's first hop h0 reads none of the state)
+        o->lv.st.h0.resize(o->S);
+        for (int i = 0; i < o->S; ++i) o->lv.st.h0[i] = level_hops(o->out.st.N[i], o->out.st.ended[i]);
+        o->lv.st.cur.assign(o->S, 0);
+        o->lv.on = true;
+        o->can_rewind = false;
+        return NHANS_OK;
+    });
 }
 
 namespace {
@@ -669,64 +664,61 @@ int nhans_level_live_auto(nhans_live* o, int window_hops, double wmax) {
 }
 
 int nhans_level_live_read(nhans_live* o, int slot, double* out, void* stream) {
-    if (!o) return fail(NHANS_EINVAL, "nhans_level_live_read: null object");
-    Call call(o->c, stream);
-    if (call.rc) return call.rc;
-    int rc = slot_check(o->S, slot, "nhans_level_live_read"); if (rc) return call.finish(rc);
-    if (!out) return call.finish(fail(NHANS_EINVAL, "nhans_level_live_read: null argument"));
-    if (!o->lv.on) return call.finish(fail(NHANS_EINVAL, "nhans_level_live_read: the meter is not enabled (nhans_level_live_enable)"));
-    if (level_hops(o->out.st.N[slot], o->out.st.ended[slot]) <= o->lv.st.h0[slot])
-        return call.finish(fail(NHANS_ESHORT, "nhans_level_live_read: slot " + std::to_string(slot) + " has no final hop yet"));
-    hipError_t e = hipMemcpyAsync(out, o->lv_half(o->lv.st.cur[slot], slot) + kLevelMeter, 8 * sizeof(double), hipMemcpyDeviceToHost, call.s);
-    if (e == hipSuccess) e = hipStreamSynchronize(call.s);
-    if (e != hipSuccess) return call.finish(fail(NHANS_EHIP, std::string("nhans_level_live_read: ") + hipGetErrorString(e)));
-    return call.finish(NHANS_OK);
+    return object_call(o, "nhans_level_live_read: null object", stream, [&](hipStream_t s) -> int {
+        int rc = slot_check(o->S, slot, "nhans_level_live_read"); if (rc) return rc;
+        if (!out) return fail(NHANS_EINVAL, "nhans_level_live_read: null argument");
+        if (!o->lv.on) return fail(NHANS_EINVAL, "nhans_level_live_read: the meter is not enabled (nhans_level_live_enable)");
+        if (level_hops(o->out.st.N[slot], o->out.st.ended[slot]) <= o->lv.st.h0[slot])
+            return fail(NHANS_ESHORT, "nhans_level_live_read: slot " + std::to_string(slot) + " has no final hop yet");
+        hipError_t e = hipMemcpyAsync(out, o->lv_half(o->lv.st.cur[slot], slot) + kLevelMeter, 8 * sizeof(double), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return fail(NHANS_EHIP, std::string("nhans_level_live_read: ") + hipGetErrorString(e));
+        return NHANS_OK;
+    });
 }
 
 int64_t nhans_level_live_gains(nhans_live* o, int slot, float* out, int64_t cap, void* stream) {
-    if (!o) return fail(NHANS_EINVAL, "nhans_level_live_gains: null object");
-    Call call(o->c, stream);
-    if (call.rc) return call.rc;
-    int rc = slot_check(o->S, slot, "nhans_level_live_gains"); if (rc) return call.finish(rc);
-    if (!o->lv.on) return call.finish(fail(NHANS_EINVAL, "nhans_level_live_gains: the meter is not enabled (nhans_level_live_enable)"));
-    const int64_t n = o->lv.woff.empty() ? 0 : o->lv.woff[slot + 1] - o->lv.woff[slot];
-    if (!out || n == 0) { rc = call.finish(NHANS_OK); return rc ? rc : n; }
-    if (cap < n)
-        return call.finish(fail(NHANS_EINVAL, "nhans_level_live_gains: room for " + std::to_string(cap) + " gains, " +
-                                              std::to_string(n) + " needed"));
-    hipError_t e = hipMemcpyAsync(out, o->lv.wtab + o->lv.woff[slot], (size_t)n * sizeof(float), hipMemcpyDeviceToHost, call.s);
-    if (e == hipSuccess) e = hipStreamSynchronize(call.s);
-    if (e != hipSuccess) return call.finish(fail(NHANS_EHIP, std::string("nhans_level_live_gains: ") + hipGetErrorString(e)));
-    rc = call.finish(NHANS_OK);
-    return rc ? rc : n;
+    return object_count_call(o, "nhans_level_live_gains: null object", stream, [&](hipStream_t s) -> int64_t {
+        const int rc = slot_check(o->S, slot, "nhans_level_live_gains"); if (rc) return rc;
+        if (!o->lv.on) return fail(NHANS_EINVAL, "nhans_level_live_gains: the meter is not enabled (nhans_level_live_enable)");
+        const int64_t n = o->lv.woff.empty() ? 0 : o->lv.woff[slot + 1] - o->lv.woff[slot];
+        if (!out || n == 0) return n;
+        if (cap < n)
+            return fail(NHANS_EINVAL, "nhans_level_live_gains: room for " + std::to_string(cap) + " gains, " +
+                                      std::to_string(n) + " needed");
+        hipError_t e = hipMemcpyAsync(out, o->lv.wtab + o->lv.woff[slot], (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return fail(NHANS_EHIP, std::string("nhans_level_live_gains: ") + hipGetErrorString(e));
+        return n;
+    });
 }
 
 int nhans_level_gains(nhans_ctx* c, const float* den, const float* mix, const int64_t* off, int nclips, int window_hops,
                       double wmax, float* w_out, double* sums_out, void* stream) {
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    if (!off || nclips < 0) return call.finish(fail(NHANS_EINVAL, "nhans_level_gains: null argument"));
-    int rc = level_check("nhans_level_gains", window_hops, 0, wmax); if (rc) return call.finish(rc);
-    std::vector<LevelRun> runs;
-    int64_t hops = 0;
-    for (int i = 0; i < nclips; ++i) {
-        const int64_t n = off[i + 1] - off[i];
-        if (n < 0) return call.finish(fail(NHANS_EINVAL, "nhans_level_gains: clip " + std::to_string(i) + " has a negative sample count"));
-        const int64_t nh = level_hops(n, true);
-        if (nh > 0 && (!den || !mix || !w_out)) return call.finish(fail(NHANS_EINVAL, "nhans_level_gains: null buffer"));
-        if (nh > 0)
-            runs.push_back({den + off[i], mix + off[i], nullptr, nullptr, sums_out ? sums_out + 8 * (size_t)i : nullptr, w_out + hops,
-                            (long long)n, 0, (long long)nh, 0, window_hops, wmax});
-        hops += nh;
-    }
-    if (runs.empty()) return call.finish(NHANS_OK);
-    LevelRun* runs_dev;
-    rc = ws_upload(c, runs, call.s, &runs_dev); if (rc) return call.finish(rc);
-    const double n = (double)(off[nclips] - off[0]);
-    Prof pr(c, call.s, "level_gains");
-    launch_level("level_gains", runs_dev, (int)runs.size(), call.s);
-    pr.done(9.0 * n, 8.0 * n + 4.0 * (double)hops);
-    return call.finish(NHANS_OK);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (!off || nclips < 0) return fail(NHANS_EINVAL, "nhans_level_gains: null argument");
+        int rc = level_check("nhans_level_gains", window_hops, 0, wmax); if (rc) return rc;
+        std::vector<LevelRun> runs;
+        int64_t hops = 0;
+        for (int i = 0; i < nclips; ++i) {
+            const int64_t n = off[i + 1] - off[i];
+            if (n < 0) return fail(NHANS_EINVAL, "nhans_level_gains: clip " + std::to_string(i) + " has a negative sample count");
+            const int64_t nh = level_hops(n, true);
+            if (nh > 0 && (!den || !mix || !w_out)) return fail(NHANS_EINVAL, "nhans_level_gains: null buffer");
+            if (nh > 0)
+                runs.push_back({den + off[i], mix + off[i], nullptr, nullptr, sums_out ? sums_out + 8 * (size_t)i : nullptr, w_out + hops,
+                                (long long)n, 0, (long long)nh, 0, window_hops, wmax});
+            hops += nh;
+        }
+        if (runs.empty()) return NHANS_OK;
+        LevelRun* runs_dev;
+        rc = ws_upload(c, runs, s, &runs_dev); if (rc) return rc;
+        const double n = (double)(off[nclips] - off[0]);
+        Prof pr(c, s, "level_gains");
+        launch_level("level_gains", runs_dev, (int)runs.size(), s);
+        pr.done(9.0 * n, 8.0 * n + 4.0 * (double)hops);
+        return NHANS_OK;
+    });
 }
 
 // ---- full-band output (include/nhans_hip.h: nhans_fullband_*) ----
@@ -765,34 +757,33 @@ int64_t nhans_fullband_hold_samples(int rate) {
 
 int nhans_fullband_live_enable(nhans_live* o, void* stream) {
     const std::string fn = "nhans_fullband_live_enable";
-    if (!o) return fail(NHANS_EINVAL, fn + ": null object");
-    Call call(o->c, stream);
-    if (call.rc) return call.rc;
-    if (o->fb.on) return call.finish(NHANS_OK);
-    const int rate_in = o->in.f->rate_in, rate_out = o->out.f->rate_out;
-    if (rate_in != rate_out)
-        return call.finish(fail(NHANS_EINVAL, fn + ": the rates differ (" + std::to_string(rate_in) + " Hz in, " + std::to_string(rate_out) +
-                                              " Hz out): the input's high band lines up with an output of its own rate only"));
-    if (rate_in <= 16000 || !fullband_rate(rate_in))
-        return call.finish(fail(NHANS_EINVAL, fn + ": " + std::to_string(rate_in) + " Hz has no band above the 16 kHz path's (22050 Hz and more)"));
-    if (!o->has_wet)
-        return call.finish(fail(NHANS_EINVAL, fn + ": the object was opened without NHANS_LIVE_WET (the high band is the input less "
-                                              "its mixed round trip)"));
-    for (int i = 0; i < o->S; ++i)
-        if (o->in.st.N[i] != 0 || o->in.st.ended[i] || o->on->st[i].N != 0 || o->out.st.N[i] != 0)
-            return call.finish(fail(NHANS_EINVAL, fn + ": slot " + std::to_string(i) + " has a stream under way (enable after open, or "
-                                                  "after nhans_live_restart of every slot that has taken samples)"));
-    const int64_t H = fullband_hold(rate_in);
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->fb.hold), (size_t)2 * o->S * (size_t)H * sizeof(float));
-    if (e != hipSuccess) return call.finish(fail(NHANS_ENOMEM, fn + ": hipMalloc failed: " + hipGetErrorString(e)));
-    // (nothing is cleared: a stream of 0 samples has none in its hold)
-    o->fb.H = H;
-    o->fb.gain.assign(o->S, 1.f);
-    o->fb.st.cur.assign(o->S, 0);
-    o->fb.st.base.assign(o->S, 0);
-    o->fb.on = true;
-    o->can_rewind = false;
-    return call.finish(NHANS_OK);
+    return object_call(o, "nhans_fullband_live_enable: null object", stream, [&](hipStream_t) -> int {
+        if (o->fb.on) return NHANS_OK;
+        const int rate_in = o->in.f->rate_in, rate_out = o->out.f->rate_out;
+        if (rate_in != rate_out)
+            return fail(NHANS_EINVAL, fn + ": the rates differ (" + std::to_string(rate_in) + " Hz in, " + std::to_string(rate_out) +
+                                      " Hz out): the input's high band lines up with an output of its own rate only");
+        if (rate_in <= 16000 || !fullband_rate(rate_in))
+            return fail(NHANS_EINVAL, fn + ": " + std::to_string(rate_in) + " Hz has no band above the 16 kHz path's (22050 Hz and more)");
+        if (!o->has_wet)
+            return fail(NHANS_EINVAL, fn + ": the object was opened without NHANS_LIVE_WET (the high band is the input less "
+                                      "its mixed round trip)");
+        for (int i = 0; i < o->S; ++i)
+            if (o->in.st.N[i] != 0 || o->in.st.ended[i] || o->on->st[i].N != 0 || o->out.st.N[i] != 0)
+                return fail(NHANS_EINVAL, fn + ": slot " + std::to_string(i) + " has a stream under way (enable after open, or "
+                                          "after nhans_live_restart of every slot that has taken samples)");
+        const int64_t H = fullband_hold(rate_in);
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->fb.hold), (size_t)2 * o->S * (size_t)H * sizeof(float));
+        if (e != hipSuccess) return fail(NHANS_ENOMEM, fn + ": hipMalloc failed: " + hipGetErrorString(e));
+        // (nothing is cleared: a stream of 0 samples has none in its hold)
+        o->fb.H = H;
+        o->fb.gain.assign(o->S, 1.f);
+        o->fb.st.cur.assign(o->S, 0);
+        o->fb.st.base.assign(o->S, 0);
+        o->fb.on = true;
+        o->can_rewind = false;
+        return NHANS_OK;
+    });
 }
 
 int nhans_fullband_live_set_gain(nhans_live* o, int slot, double gain) {
@@ -811,56 +802,55 @@ int nhans_fullband_mix(nhans_ctx* c, const void* x, int x_format, const int64_t*
                        const int64_t* off, int nclips, int rate, double in_denom, double wet, const float* wet_hops, double gain,
                        double out_scale, int out_format, void* out, const int64_t* outoff, void* stream) {
     const std::string fn = "nhans_fullband_mix";
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    if (!xoff || !off || !outoff || nclips < 0) return call.finish(fail(NHANS_EINVAL, fn + ": null argument"));
-    for (int fmt : {x_format, out_format})
-        if (fmt != kResampleInt16 && fmt != kResampleFloat32)
-            return call.finish(fail(NHANS_EINVAL, fn + ": x_format and out_format must be NHANS_PCM_INT16 or NHANS_PCM_FLOAT32"));
-    if (!fullband_rate(rate))
-        return call.finish(fail(NHANS_EINVAL, fn + ": " + std::to_string(rate) + " Hz is not a full-band rate (22050, 24000, 32000, 44100, "
-                                              "48000, 88200 or 96000 Hz)"));
-    if (!(in_denom > 0.0) || !std::isfinite(in_denom)) return call.finish(fail(NHANS_EINVAL, fn + ": in_denom must be finite and > 0"));
-    if (!(out_scale > 0.0) || !std::isfinite(out_scale)) return call.finish(fail(NHANS_EINVAL, fn + ": out_scale must be finite and > 0"));
-    if (!std::isfinite(wet)) return call.finish(fail(NHANS_EINVAL, fn + ": the wet factor must be finite"));
-    if (!std::isfinite(gain) || gain < 0.0 || gain > 4.0) return call.finish(fail(NHANS_EINVAL, fn + ": the gain must be finite, in [0, 4]"));
-    const ResampleFilter* f = resample_filter(16000, rate);
-    const size_t elem = rs_elem(out_format);
-    int64_t t16 = 0, tx = 0, tout = 0;
-    for (int i = 0; i < nclips; ++i) {
-        const int64_t n16 = off[i + 1] - off[i], nx = xoff[i + 1] - xoff[i];
-        if (n16 < 0 || n16 > kMaxResampleClip || nx < 0)
-            return call.finish(fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(n16) + " samples at 16 kHz and " +
-                                                  std::to_string(nx) + " at its own rate (0 ... 2^31 - 1; >= 0)"));
-        const int64_t no = resample_out_count(*f, n16);
-        if (outoff[i + 1] - outoff[i] < no)
-            return call.finish(fail(NHANS_EINVAL, fn + ": output room of clip " + std::to_string(i) + " is " +
-                                                  std::to_string(outoff[i + 1] - outoff[i]) + " samples, " + std::to_string(no) +
-                                                  " needed (nhans_resample_out_count)"));
-        t16 += n16; tx += nx; tout += no;
-    }
-    if ((t16 > 0 && (!den || !mix)) || (tx > 0 && !x) || (tout > 0 && !out)) return call.finish(fail(NHANS_EINVAL, fn + ": null buffer"));
-    std::vector<ResampleRun> runs;
-    size_t lds = 0;
-    int64_t hops = 0;
-    for (int i = 0; i < nclips; ++i) {
-        const int64_t n16 = off[i + 1] - off[i];
-        const size_t first = runs.size();
-        rs_add_runs(runs, &lds, *f, den + off[i], mix + off[i], nullptr, static_cast<char*>(out) + outoff[i] * elem, elem, nullptr, 0,
-                    (int)n16, 0, resample_out_count(*f, n16));
-        for (size_t k = first; k < runs.size(); ++k) {
-            if (wet_hops) { runs[k].wtab = wet_hops + hops; runs[k].hop0 = 0; }
-            highband_run(runs[k], (float)gain, nullptr, 0, 0, xoff[i + 1] - xoff[i], static_cast<const char*>(x) + xoff[i] * rs_elem(x_format),
-                         x_format, 0, 0, in_denom, (int64_t)(k - first) * kResampleRun);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (!xoff || !off || !outoff || nclips < 0) return fail(NHANS_EINVAL, fn + ": null argument");
+        for (int fmt : {x_format, out_format})
+            if (fmt != kResampleInt16 && fmt != kResampleFloat32)
+                return fail(NHANS_EINVAL, fn + ": x_format and out_format must be NHANS_PCM_INT16 or NHANS_PCM_FLOAT32");
+        if (!fullband_rate(rate))
+            return fail(NHANS_EINVAL, fn + ": " + std::to_string(rate) + " Hz is not a full-band rate (22050, 24000, 32000, 44100, "
+                                      "48000, 88200 or 96000 Hz)");
+        if (!(in_denom > 0.0) || !std::isfinite(in_denom)) return fail(NHANS_EINVAL, fn + ": in_denom must be finite and > 0");
+        if (!(out_scale > 0.0) || !std::isfinite(out_scale)) return fail(NHANS_EINVAL, fn + ": out_scale must be finite and > 0");
+        if (!std::isfinite(wet)) return fail(NHANS_EINVAL, fn + ": the wet factor must be finite");
+        if (!std::isfinite(gain) || gain < 0.0 || gain > 4.0) return fail(NHANS_EINVAL, fn + ": the gain must be finite, in [0, 4]");
+        const ResampleFilter* f = resample_filter(16000, rate);
+        const size_t elem = rs_elem(out_format);
+        int64_t t16 = 0, tx = 0, tout = 0;
+        for (int i = 0; i < nclips; ++i) {
+            const int64_t n16 = off[i + 1] - off[i], nx = xoff[i + 1] - xoff[i];
+            if (n16 < 0 || n16 > kMaxResampleClip || nx < 0)
+                return fail(NHANS_EINVAL, fn + ": clip " + std::to_string(i) + " has " + std::to_string(n16) + " samples at 16 kHz and " +
+                                          std::to_string(nx) + " at its own rate (0 ... 2^31 - 1; >= 0)");
+            const int64_t no = resample_out_count(*f, n16);
+            if (outoff[i + 1] - outoff[i] < no)
+                return fail(NHANS_EINVAL, fn + ": output room of clip " + std::to_string(i) + " is " +
+                                          std::to_string(outoff[i + 1] - outoff[i]) + " samples, " + std::to_string(no) +
+                                          " needed (nhans_resample_out_count)");
+            t16 += n16; tx += nx; tout += no;
         }
-        hops += level_hops(n16, true);
-    }
-    if (runs.empty()) return call.finish(NHANS_OK);
-    const float* tab = nullptr;
-    int rc = rs_table(c, f, &tab); if (rc) return call.finish(rc);
-    rc = rs_launch(c, "fullband_mix", runs, tab, *f, {true, out_format, 0, (float)wet, out_scale, wet_hops != nullptr, false, true}, lds,
-                   8.0 * (double)t16, (double)tout * (elem + rs_elem(x_format)), tout, call.s);
-    return call.finish(rc);
+        if ((t16 > 0 && (!den || !mix)) || (tx > 0 && !x) || (tout > 0 && !out)) return fail(NHANS_EINVAL, fn + ": null buffer");
+        std::vector<ResampleRun> runs;
+        size_t lds = 0;
+        int64_t hops = 0;
+        for (int i = 0; i < nclips; ++i) {
+            const int64_t n16 = off[i + 1] - off[i];
+            const size_t first = runs.size();
+            rs_add_runs(runs, &lds, *f, den + off[i], mix + off[i], nullptr, static_cast<char*>(out) + outoff[i] * elem, elem, nullptr, 0,
+                        (int)n16, 0, resample_out_count(*f, n16));
+            for (size_t k = first; k < runs.size(); ++k) {
+                if (wet_hops) { runs[k].wtab = wet_hops + hops; runs[k].hop0 = 0; }
+                highband_run(runs[k], (float)gain, nullptr, 0, 0, xoff[i + 1] - xoff[i], static_cast<const char*>(x) + xoff[i] * rs_elem(x_format),
+                             x_format, 0, 0, in_denom, (int64_t)(k - first) * kResampleRun);
+            }
+            hops += level_hops(n16, true);
+        }
+        if (runs.empty()) return NHANS_OK;
+        const float* tab = nullptr;
+        const int rc = rs_table(c, f, &tab); if (rc) return rc;
+        return rs_launch(c, "fullband_mix", runs, tab, *f, {true, out_format, 0, (float)wet, out_scale, wet_hops != nullptr, false, true}, lds,
+                         8.0 * (double)t16, (double)tout * (elem + rs_elem(x_format)), tout, s);
+    });
 }
 
 void nhans_live_close(nhans_live* o) {

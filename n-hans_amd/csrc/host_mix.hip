@@ -55,36 +55,36 @@ int nhans_mix(nhans_ctx* c, const float* speech, const int64_t* soff, int nspeec
     }
     if (tiles > 0x7fffffffLL) return fail(NHANS_EINVAL, fn + ": too many samples for one call (split it)");
     for (const MixChain& ch : chains) chained += ch.n;
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    if (njobs == 0) return call.finish(NHANS_OK);
-    WsPlan p;
-    MixChain* chains_dev; MixJob* jobs_dev; double* pw; float* peaks;
-    p.add(&chains_dev, chains.size());
-    p.add(&jobs_dev, jobs.size());
-    p.add(&pw, chains.size());
-    p.add(&peaks, (size_t)tiles);
-    int rc = ws_commit(c, p); if (rc) return call.finish(rc);
-    rc = h2d(c, chains_dev, chains.data(), chains.size() * sizeof(MixChain), call.s); if (rc) return call.finish(rc);
-    rc = h2d(c, jobs_dev, jobs.data(), jobs.size() * sizeof(MixJob), call.s); if (rc) return call.finish(rc);
-    const double n = (double)samples, T = (double)tiles, J = (double)njobs;
-    const int outs = 1 + (target ? 1 : 0) + (keep ? 1 : 0) + (drop ? 1 : 0);
-    {   // per fitted sample: a product and one addition of the chain
-        Prof pr(c, call.s, "mix_power");
-        launch_mix_power("mix_power", chains_dev, (int)chains.size(), pw, call.s);
-        pr.done(2.0 * (double)chained, 4.0 * (double)chained + 8.0 * (double)chains.size());
-    }
-    {   // per sample: two products and two sums
-        Prof pr(c, call.s, "mix_combine");
-        launch_mix_combine("mix_combine", jobs_dev, njobs, tiles, pw, mixture, peaks, records, call.s);
-        pr.done(4.0 * n, 16.0 * n + 4.0 * T + (records ? 40.0 * J : 0.0));
-    }
-    {   // per sample and output: at most a product, a sum and a division
-        Prof pr(c, call.s, "mix_finish");
-        launch_mix_finish("mix_finish", jobs_dev, njobs, tiles, pw, peaks, mixture, target, keep, drop, records, call.s);
-        pr.done(3.0 * outs * n, (16.0 + 4.0 * outs) * n + (records ? 24.0 * J : 0.0));
-    }
-    return call.finish(NHANS_OK);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (njobs == 0) return NHANS_OK;
+        WsPlan p;
+        MixChain* chains_dev; MixJob* jobs_dev; double* pw; float* peaks;
+        p.add(&chains_dev, chains.size());
+        p.add(&jobs_dev, jobs.size());
+        p.add(&pw, chains.size());
+        p.add(&peaks, (size_t)tiles);
+        int rc = ws_commit(c, p); if (rc) return rc;
+        rc = h2d(c, chains_dev, chains, s); if (rc) return rc;
+        rc = h2d(c, jobs_dev, jobs, s); if (rc) return rc;
+        const double n = (double)samples, T = (double)tiles, J = (double)njobs;
+        const int outs = 1 + (target ? 1 : 0) + (keep ? 1 : 0) + (drop ? 1 : 0);
+        {   // per fitted sample: a product and one addition of the chain
+            Prof pr(c, s, "mix_power");
+            launch_mix_power("mix_power", chains_dev, (int)chains.size(), pw, s);
+            pr.done(2.0 * (double)chained, 4.0 * (double)chained + 8.0 * (double)chains.size());
+        }
+        {   // per sample: two products and two sums
+            Prof pr(c, s, "mix_combine");
+            launch_mix_combine("mix_combine", jobs_dev, njobs, tiles, pw, mixture, peaks, records, s);
+            pr.done(4.0 * n, 16.0 * n + 4.0 * T + (records ? 40.0 * J : 0.0));
+        }
+        {   // per sample and output: at most a product, a sum and a division
+            Prof pr(c, s, "mix_finish");
+            launch_mix_finish("mix_finish", jobs_dev, njobs, tiles, pw, peaks, mixture, target, keep, drop, records, s);
+            pr.done(3.0 * outs * n, (16.0 + 4.0 * outs) * n + (records ? 24.0 * J : 0.0));
+        }
+        return NHANS_OK;
+    });
 }
 
 }  // extern "C"

@@ -557,9 +557,9 @@ int stft_impl(nhans_ctx* c, const float* wav, const int64_t* soff, int nclips, i
     }
     const int nb = (int)bclip.size();
     int rc = h2d(c, dev_tables, soff, (nclips + 1) * 8, s); if (rc) return rc;
-    rc = h2d(c, dev_tables + (nclips + 1), foff.data(), (nclips + 1) * 8, s); if (rc) return rc;
-    rc = h2d(c, dev_blocks, bclip.data(), (size_t)nb * 4, s); if (rc) return rc;
-    rc = h2d(c, dev_blocks + nb, bf0.data(), (size_t)nb * 4, s); if (rc) return rc;
+    rc = h2d(c, dev_tables + (nclips + 1), foff, s); if (rc) return rc;
+    rc = h2d(c, dev_blocks, bclip, s); if (rc) return rc;
+    rc = h2d(c, dev_blocks + nb, bf0, s); if (rc) return rc;
     ClipTable t{dev_tables, dev_tables + (nclips + 1), nullptr};
     Prof pr(c, s, prof_name ? prof_name : phase ? "stft_features" : "stft_context_features");   // (contexts: log-magnitude only, 200 frames per clip)
     launch_stft(wav, t, dev_blocks, dev_blocks + nb, nb, c->net.tw400, c->net.window, logmag, phase, s);
@@ -592,8 +592,8 @@ int istft_impl(nhans_ctx* c, const float* logmag, const float* phase, const int6
     const int nb = (int)bclip.size();
     int rc = h2d(c, dev_tables, foff, (nclips + 1) * 8, s); if (rc) return rc;
     rc = h2d(c, dev_tables + (nclips + 1), ooff, (nclips + 1) * 8, s); if (rc) return rc;
-    rc = h2d(c, dev_blocks, bclip.data(), (size_t)nb * 4, s); if (rc) return rc;
-    rc = h2d(c, dev_blocks + nb, bh0.data(), (size_t)nb * 4, s); if (rc) return rc;
+    rc = h2d(c, dev_blocks, bclip, s); if (rc) return rc;
+    rc = h2d(c, dev_blocks + nb, bh0, s); if (rc) return rc;
     ClipTable t{nullptr, dev_tables, dev_tables + (nclips + 1)};
     Prof pr(c, s, prof_name);
     launch_istft(logmag, phase, t, dev_blocks, dev_blocks + nb, nb, c->net.tw400, c->net.wsyn, wav_out, s);
@@ -614,11 +614,10 @@ size_t istft_blocks(const int64_t* foff, int nclips) {
 int enhance_clips_body(nhans_ctx* c, const float* mix, const int64_t* moff, int nclips, const float* ca,
                         const int64_t* caoff, const float* cbw, const int64_t* cboff, float* den_wav,
                         float* mixed_wav, float* logmag_out, float* phase_out, float* logits_out, float* emb_out,
-                        void* stream) {
+                        hipStream_t s) {
     int rc = NHANS_OK;
     if (!mix || !moff || !ca || !caoff || !cbw || !cboff || !den_wav || nclips < 1)
         return fail(NHANS_EINVAL, "null argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
     std::vector<int64_t> foff(nclips + 1, 0);
     for (int i = 0; i < nclips; ++i) {
         const int64_t n = moff[i + 1] - moff[i];
@@ -825,8 +824,8 @@ int nhans_enhance_clips(nhans_ctx* c, const float* mix, const int64_t* moff, int
                         const int64_t* caoff, const float* cbw, const int64_t* cboff, float* den_wav,
                         float* mixed_wav, float* logmag_out, float* phase_out, float* logits_out, float* emb_out,
                         void* stream) {
-    return ctx_call(c, stream, [&](hipStream_t) -> int {
-        return enhance_clips_body(c, mix, moff, nclips, ca, caoff, cbw, cboff, den_wav, mixed_wav, logmag_out, phase_out, logits_out, emb_out, stream);
+    return ctx_call(c, stream, [&](hipStream_t s) {
+        return enhance_clips_body(c, mix, moff, nclips, ca, caoff, cbw, cboff, den_wav, mixed_wav, logmag_out, phase_out, logits_out, emb_out, s);
     });
 }
 

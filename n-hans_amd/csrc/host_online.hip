@@ -358,7 +358,7 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
 
     // ---- launches ----
     o->fb.forget();      // (from here on the feature rows of the last push may be overwritten; set again below, with the host state)
-    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(OnlineCopy), s); if (rc) return rc;
+    rc = h2d(c, runs_dev, runs, s); if (rc) return rc;
     auto copies = [&](int k, const char* name) {
         const int n = bounds[k + 1] - bounds[k];
         if (n <= 0) return;
@@ -381,10 +381,10 @@ int online_push_body(nhans_online* o, const float* in, const int64_t* inoff, con
     }
     copies(1, "online_assemble");
     if (F > 0) {
-        rc = h2d(c, sb.f_clip, h_clip.data(), F * 4, s); if (rc) return rc;
-        rc = h2d(c, sb.f_t, h_t.data(), F * 4, s); if (rc) return rc;
-        rc = h2d(c, sb.f_T, h_T.data(), F * 4, s); if (rc) return rc;
-        rc = h2d(c, rb, h_rb.data(), F * 4, s); if (rc) return rc;
+        rc = h2d(c, sb.f_clip, h_clip, s); if (rc) return rc;
+        rc = h2d(c, sb.f_t, h_t, s); if (rc) return rc;
+        rc = h2d(c, sb.f_T, h_T, s); if (rc) return rc;
+        rc = h2d(c, rb, h_rb, s); if (rc) return rc;
         rc = mask_net_run(c, win, rb, ctr, F, S, o->emb, o->emb + (size_t)S * kEmb, nullptr, dnew, sb, wf, s);
         if (rc) return rc;
         if (launch_error_pending()) return NHANS_OK;      // (reported by the entry point; nothing below runs on it)
@@ -531,7 +531,7 @@ int capture_context_body(nhans_online* o, const char* fn_, int n, const int* slo
     for (int k = 0; k < n; ++k)
         ent[k] = {o->ring + (size_t)slots[k] * kCaptureSamples, clips + (size_t)k * kCaptureSamples,
                   (int)(o->st[slots[k]].N % kCaptureSamples), flags & NHANS_CAPTURE_NORMALISE};
-    rc = h2d(c, ent_dev, ent.data(), (size_t)n * sizeof(CaptureEntry), s); if (rc) return rc;
+    rc = h2d(c, ent_dev, ent, s); if (rc) return rc;
     {
         Prof pr(c, s, "capture_clip_kernel");
         launch_capture_clip(ent_dev, n, s);
@@ -562,15 +562,11 @@ extern "C" {
 
 int nhans_online_open(nhans_ctx* c, int nstreams, const float* ca, const int64_t* caoff, const float* cbw,
                       const int64_t* cboff, int want_mixed, void* stream, nhans_online** out) {
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(online_open_body(c, nstreams, ca, caoff, cbw, cboff, want_mixed, call.s, out));
+    return ctx_call(c, stream, [&](hipStream_t s) { return online_open_body(c, nstreams, ca, caoff, cbw, cboff, want_mixed, s, out); });
 }
 
 int nhans_online_open_slots(nhans_ctx* c, int nslots, int want_mixed, void* stream, nhans_online** out) {
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(online_open_slots_body(c, nslots, want_mixed, call.s, out));
+    return ctx_call(c, stream, [&](hipStream_t s) { return online_open_slots_body(c, nslots, want_mixed, s, out); });
 }
 
 int nhans_online_restart(nhans_online* o, int slot) {
@@ -647,12 +643,9 @@ int nhans_fbank_online_attach(nhans_online* o, nhans_fbank* fb, int flags) {
 
 int64_t nhans_fbank_online_read(nhans_online* o, int slot, int plane, float* out, int64_t cap_rows, int64_t* first_frame_out,
                                 void* stream) {
-    if (!o) return fail(NHANS_EINVAL, "nhans_fbank_online_read: null object");
-    Call call(o->c, stream);
-    if (call.rc) return call.rc;
-    const int64_t n = fbank_read_body(o, "nhans_fbank_online_read", slot, plane, out, cap_rows, first_frame_out, call.s);
-    const int rc = call.finish(n < 0 ? (int)n : NHANS_OK);
-    return rc ? rc : n;
+    return object_count_call(o, "nhans_fbank_online_read: null object", stream, [&](hipStream_t s) {
+        return fbank_read_body(o, "nhans_fbank_online_read", slot, plane, out, cap_rows, first_frame_out, s);
+    });
 }
 
 int nhans_capture_plan(int64_t n_before, int64_t count, int64_t* runs_out) {

@@ -29,8 +29,8 @@ int tables_upload(nhans_ctx* c, const int64_t* foff, int nclips, const PhaseBufs
     for (int i = 0; i < nclips; ++i)
         for (int64_t f0 = 0; f0 < foff[i + 1] - foff[i]; f0 += kPhaseRun) { bclip.push_back(i); bf0.push_back((int)f0); }
     int rc = h2d(c, pb.foff_dev, foff, (size_t)(nclips + 1) * 8, s); if (rc) return rc;
-    rc = h2d(c, pb.blocks, bclip.data(), bclip.size() * 4, s); if (rc) return rc;
-    return h2d(c, pb.blocks + pb.nblocks, bf0.data(), bf0.size() * 4, s);
+    rc = h2d(c, pb.blocks, bclip, s); if (rc) return rc;
+    return h2d(c, pb.blocks + pb.nblocks, bf0, s);
 }
 
 // one projection launch and, where asked, the clips' inconsistency into column col of inc_out [nclips][stride]

@@ -60,57 +60,57 @@ int nhans_quality(nhans_ctx* c, const float* est, const int64_t* eoff, const flo
     std::vector<QualityRun> runs;
     long long frames = 0, lt = 0, bt = 0;
     int rc = quality_runs(fn, est, eoff, tgt, toff, nclips, out, &runs, &frames, &lt, &bt); if (rc) return rc;
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    if (nclips == 0) return call.finish(NHANS_OK);
-    const int K = bands ? nbands : kQualityBands;
-    WsPlan p;
-    QualityRun* runs_dev; double *tab, *W, *vals; int* span_dev;
-    p.add(&runs_dev, runs.size());
-    p.add(&tab, kQualityTable);
-    p.add(&W, (size_t)K * kQualityBins);
-    p.add(&span_dev, (size_t)2 * K);
-    p.add(&vals, frames_out ? 0 : (size_t)frames * 3);
-    rc = ws_commit(c, p); if (rc) return call.finish(rc);
-    if (frames_out) vals = frames_out;
-    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(QualityRun), call.s); if (rc) return call.finish(rc);
-    std::vector<double> table(kQualityTable), wdef;
-    quality_table(table.data());
-    rc = h2d(c, tab, table.data(), table.size() * sizeof(double), call.s); if (rc) return call.finish(rc);
-    if (!bands) {
-        wdef.resize((size_t)kQualityBands * kQualityBins);
-        quality_default_bands(wdef.data());
-    }
-    const double* wsrc = bands ? bands : wdef.data();
-    rc = h2d(c, W, wsrc, (size_t)K * kQualityBins * sizeof(double), call.s); if (rc) return call.finish(rc);
-    // a row's chain runs from its first non-zero weight to its last: the zero weights outside add exact zeros
-    std::vector<int> span((size_t)2 * K, 0);
-    double terms = 0.0;
-    for (int j = 0; j < K; ++j) {
-        int lo = kQualityBins, hi = 0;
-        for (int k = 0; k < kQualityBins; ++k)
-            if (wsrc[(size_t)j * kQualityBins + k] != 0.0) { lo = std::min(lo, k); hi = k + 1; }
-        if (hi > 0) { span[2 * j] = lo; span[2 * j + 1] = hi; terms += hi - lo; }
-    }
-    rc = h2d(c, span_dev, span.data(), span.size() * sizeof(int), call.s); if (rc) return call.finish(rc);
-    const double F = (double)frames, C = (double)nclips;
-    {   // a workgroup stages its tile's span of both signals once: 120 new samples a frame and signal, 480 at a tile's head
-        Prof pr(c, call.s, "quality_lpc");
-        launch_quality_lpc("quality_lpc", runs_dev, nclips, lt, tab, vals, nullptr, call.s);
-        pr.done(lpc_flops(F), 2.0 * 4.0 * (kQualityHop * F + 360.0 * (double)lt) + 16.0 * F);
-    }
-    {   // per frame and signal: 480 products, 5 N log2 N of the transform, 4 a bin for the magnitude, 2 per band term worked
-        Prof pr(c, call.s, "quality_bands");
-        launch_quality_bands("quality_bands", runs_dev, nclips, bt, tab, W, span_dev, K, vals, call.s);
-        pr.done(2.0 * F * (kQualityFrame + 5.0 * kQualityFft * 9.0 + 4.0 * kQualityBins + 2.0 * terms),
-                F * (2.0 * 4.0 * kQualityFrame + 8.0));
-    }
-    {   // per frame: three means, two selects of eight passes, two trimmed sums
-        Prof pr(c, call.s, "quality_finish");
-        launch_quality_finish("quality_finish", runs_dev, nclips, vals, out, call.s);
-        pr.done(5.0 * F, 8.0 * F * (3.0 + 16.0 + 2.0) + 8.0 * kQualityFields * C);
-    }
-    return call.finish(NHANS_OK);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (nclips == 0) return NHANS_OK;
+        const int K = bands ? nbands : kQualityBands;
+        WsPlan p;
+        QualityRun* runs_dev; double *tab, *W, *vals; int* span_dev;
+        p.add(&runs_dev, runs.size());
+        p.add(&tab, kQualityTable);
+        p.add(&W, (size_t)K * kQualityBins);
+        p.add(&span_dev, (size_t)2 * K);
+        p.add(&vals, frames_out ? 0 : (size_t)frames * 3);
+        rc = ws_commit(c, p); if (rc) return rc;
+        if (frames_out) vals = frames_out;
+        rc = h2d(c, runs_dev, runs, s); if (rc) return rc;
+        std::vector<double> table(kQualityTable), wdef;
+        quality_table(table.data());
+        rc = h2d(c, tab, table, s); if (rc) return rc;
+        if (!bands) {
+            wdef.resize((size_t)kQualityBands * kQualityBins);
+            quality_default_bands(wdef.data());
+        }
+        const double* wsrc = bands ? bands : wdef.data();
+        rc = h2d(c, W, wsrc, (size_t)K * kQualityBins * sizeof(double), s); if (rc) return rc;
+        // a row's chain runs from its first non-zero weight to its last: the zero weights outside add exact zeros
+        std::vector<int> span((size_t)2 * K, 0);
+        double terms = 0.0;
+        for (int j = 0; j < K; ++j) {
+            int lo = kQualityBins, hi = 0;
+            for (int k = 0; k < kQualityBins; ++k)
+                if (wsrc[(size_t)j * kQualityBins + k] != 0.0) { lo = std::min(lo, k); hi = k + 1; }
+            if (hi > 0) { span[2 * j] = lo; span[2 * j + 1] = hi; terms += hi - lo; }
+        }
+        rc = h2d(c, span_dev, span, s); if (rc) return rc;
+        const double F = (double)frames, C = (double)nclips;
+        {   // a workgroup stages its tile's span of both signals once: 120 new samples a frame and signal, 480 at a tile's head
+            Prof pr(c, s, "quality_lpc");
+            launch_quality_lpc("quality_lpc", runs_dev, nclips, lt, tab, vals, nullptr, s);
+            pr.done(lpc_flops(F), 2.0 * 4.0 * (kQualityHop * F + 360.0 * (double)lt) + 16.0 * F);
+        }
+        {   // per frame and signal: 480 products, 5 N log2 N of the transform, 4 a bin for the magnitude, 2 per band term worked
+            Prof pr(c, s, "quality_bands");
+            launch_quality_bands("quality_bands", runs_dev, nclips, bt, tab, W, span_dev, K, vals, s);
+            pr.done(2.0 * F * (kQualityFrame + 5.0 * kQualityFft * 9.0 + 4.0 * kQualityBins + 2.0 * terms),
+                    F * (2.0 * 4.0 * kQualityFrame + 8.0));
+        }
+        {   // per frame: three means, two selects of eight passes, two trimmed sums
+            Prof pr(c, s, "quality_finish");
+            launch_quality_finish("quality_finish", runs_dev, nclips, vals, out, s);
+            pr.done(5.0 * F, 8.0 * F * (3.0 + 16.0 + 2.0) + 8.0 * kQualityFields * C);
+        }
+        return NHANS_OK;
+    });
 }
 
 int nhans_quality_lpc(nhans_ctx* c, const float* est, const int64_t* eoff, const float* tgt, const int64_t* toff, int nclips,
@@ -119,25 +119,25 @@ int nhans_quality_lpc(nhans_ctx* c, const float* est, const int64_t* eoff, const
     std::vector<QualityRun> runs;
     long long frames = 0, lt = 0, bt = 0;
     int rc = quality_runs(fn, est, eoff, tgt, toff, nclips, lpc_out, &runs, &frames, &lt, &bt); if (rc) return rc;
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    if (nclips == 0) return call.finish(NHANS_OK);
-    WsPlan p;
-    QualityRun* runs_dev; double *tab, *vals;
-    p.add(&runs_dev, runs.size());
-    p.add(&tab, kQualityTable);
-    p.add(&vals, (size_t)frames * 3);
-    rc = ws_commit(c, p); if (rc) return call.finish(rc);
-    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(QualityRun), call.s); if (rc) return call.finish(rc);
-    std::vector<double> table(kQualityTable);
-    quality_table(table.data());
-    rc = h2d(c, tab, table.data(), table.size() * sizeof(double), call.s); if (rc) return call.finish(rc);
-    {
-        Prof pr(c, call.s, "quality_lpc");
-        launch_quality_lpc("quality_lpc", runs_dev, nclips, lt, tab, vals, lpc_out, call.s);
-        pr.done(lpc_flops((double)frames), 2.0 * 4.0 * (kQualityHop * (double)frames + 360.0 * (double)lt) + 8.0 * (2.0 + kQualityLpcFields) * (double)frames);
-    }
-    return call.finish(NHANS_OK);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (nclips == 0) return NHANS_OK;
+        WsPlan p;
+        QualityRun* runs_dev; double *tab, *vals;
+        p.add(&runs_dev, runs.size());
+        p.add(&tab, kQualityTable);
+        p.add(&vals, (size_t)frames * 3);
+        rc = ws_commit(c, p); if (rc) return rc;
+        rc = h2d(c, runs_dev, runs, s); if (rc) return rc;
+        std::vector<double> table(kQualityTable);
+        quality_table(table.data());
+        rc = h2d(c, tab, table, s); if (rc) return rc;
+        {
+            Prof pr(c, s, "quality_lpc");
+            launch_quality_lpc("quality_lpc", runs_dev, nclips, lt, tab, vals, lpc_out, s);
+            pr.done(lpc_flops((double)frames), 2.0 * 4.0 * (kQualityHop * (double)frames + 360.0 * (double)lt) + 8.0 * (2.0 + kQualityLpcFields) * (double)frames);
+        }
+        return NHANS_OK;
+    });
 }
 
 }  // extern "C"

@@ -172,7 +172,7 @@ int peak_normalise_body(nhans_ctx* c, const float* in, const int64_t* off, int n
     p.add(&bd, blocks.size());
     p.add(&partial, blocks.size());
     int rc = ws_commit(c, p); if (rc) return rc;
-    rc = h2d(c, bd, blocks.data(), blocks.size() * sizeof(NormBlock), s); if (rc) return rc;
+    rc = h2d(c, bd, blocks, s); if (rc) return rc;
     const double n = (double)(off[nclips] - off[0]);
     { Prof pr(c, s, "peak_partial"); launch_peak_partial(in, bd, (int)blocks.size(), flags & NHANS_NORMALISE_WRAP_INT16, partial, s); pr.done(0, 4.0 * n); }
     if (launch_error_pending()) return NHANS_OK;
@@ -235,26 +235,23 @@ int nhans_resample_taps(int rate_in, int rate_out, double* out, int cap) {
 
 int nhans_resample(nhans_ctx* c, const void* in, int in_format, const int64_t* inoff, int nclips, int rate_in, int rate_out,
                    int flags, float* out, const int64_t* outoff, void* stream) {
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(resample_body(c, in, in_format, inoff, nclips, rate_in, rate_out, flags, out, outoff, call.s));
+    return ctx_call(c, stream,
+                    [&](hipStream_t s) { return resample_body(c, in, in_format, inoff, nclips, rate_in, rate_out, flags, out, outoff, s); });
 }
 
 int nhans_peak_normalise(nhans_ctx* c, const float* in, const int64_t* off, int nclips, int flags, float* out, void* stream) {
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(peak_normalise_body(c, in, off, nclips, flags, out, call.s));
+    return ctx_call(c, stream, [&](hipStream_t s) { return peak_normalise_body(c, in, off, nclips, flags, out, s); });
 }
 
 int nhans_channel_mean(nhans_ctx* c, const float* in, int nchan, int64_t n, float* out, void* stream) {
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    if (nchan < 1 || n < 0 || n >= ((int64_t)1 << 39)) return call.finish(fail(NHANS_EINVAL, "nhans_channel_mean: nchannels must be >= 1 and 0 <= nsamples < 2^39"));
-    if (n > 0 && (!in || !out)) return call.finish(fail(NHANS_EINVAL, "nhans_channel_mean: null buffer"));
-    Prof pr(c, call.s, "channel_mean");
-    launch_channel_mean(in, nchan, n, out, call.s);
-    pr.done(0, 4.0 * (double)n * (nchan + 1));
-    return call.finish(NHANS_OK);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (nchan < 1 || n < 0 || n >= ((int64_t)1 << 39)) return fail(NHANS_EINVAL, "nhans_channel_mean: nchannels must be >= 1 and 0 <= nsamples < 2^39");
+        if (n > 0 && (!in || !out)) return fail(NHANS_EINVAL, "nhans_channel_mean: null buffer");
+        Prof pr(c, s, "channel_mean");
+        launch_channel_mean(in, nchan, n, out, s);
+        pr.done(0, 4.0 * (double)n * (nchan + 1));
+        return NHANS_OK;
+    });
 }
 
 int nhans_resampler_open(nhans_ctx* c, int nstreams, int rate_in, int rate_out, int in_format, int flags, nhans_resampler** out) {

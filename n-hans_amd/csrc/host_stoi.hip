@@ -50,9 +50,7 @@ int nhans_stoi_resample(nhans_ctx* c, const float* in, const int64_t* inoff, int
                                       " samples, " + std::to_string(no) + " needed (nhans_stoi_out_count)");
         if (n > 0 && (!in || !out)) return null_clip(fn, i, n);
     }
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    return call.finish(stoi_resample_body(c, in, inoff, nclips, out, outoff, f, call.s));
+    return ctx_call(c, stream, [&](hipStream_t s) { return stoi_resample_body(c, in, inoff, nclips, out, outoff, f, s); });
 }
 
 int nhans_stoi(nhans_ctx* c, const float* est, const int64_t* eoff, const float* tgt, const int64_t* toff, int nclips, double* out,
@@ -75,50 +73,50 @@ int nhans_stoi(nhans_ctx* c, const float* est, const int64_t* eoff, const float*
     });
     if (rc) return rc;
     if (pt > 0x7fffffffLL) return fail(NHANS_EINVAL, fn + ": too many samples for one call (split it)");
-    Call call(c, stream);
-    if (call.rc) return call.rc;
-    if (nclips == 0) return call.finish(NHANS_OK);
-    WsPlan p;
-    StoiRun* runs_dev; double *tab, *power, *bands, *segv; int* kept; long long* nkept;
-    p.add(&runs_dev, runs.size());
-    p.add(&tab, kStoiTable);
-    p.add(&power, (size_t)frames);
-    p.add(&kept, (size_t)frames);
-    p.add(&nkept, runs.size());
-    p.add(&bands, (size_t)rows * 2 * kStoiBands);
-    p.add(&segv, (size_t)segs * 2);
-    rc = ws_commit(c, p); if (rc) return call.finish(rc);
-    rc = h2d(c, runs_dev, runs.data(), runs.size() * sizeof(StoiRun), call.s); if (rc) return call.finish(rc);
-    std::vector<double> table(kStoiTable);
-    stoi_table(table.data());
-    rc = h2d(c, tab, table.data(), table.size() * sizeof(double), call.s); if (rc) return call.finish(rc);
-    const double F = (double)frames, R = (double)rows, S = (double)segs, C = (double)nclips;
-    {   // per sample of a frame: a product and a fused multiply-add
-        Prof pr(c, call.s, "stoi_power");
-        launch_stoi_power("stoi_power", runs_dev, nclips, pt, tab, power, call.s);
-        pr.done(3.0 * kStoiFrame * F, 4.0 * kStoiFrame * F + 8.0 * F);
-    }
-    {
-        Prof pr(c, call.s, "stoi_keep");
-        launch_stoi_keep("stoi_keep", runs_dev, nclips, power, kept, nkept, call.s);
-        pr.done(F, 16.0 * F + 4.0 * F + 8.0 * C);
-    }
-    {   // per frame and signal: 4 operations a sample, 5 N log2 N of the transform, 3 a bin; what is silent is not computed
-        Prof pr(c, call.s, "stoi_bands");
-        launch_stoi_bands("stoi_bands", runs_dev, nclips, bt, tab, kept, nkept, bands, rows, call.s);
-        pr.done(2.0 * R * (4.0 * kStoiFrame + 5.0 * kStoiFft * 9.0 + 3.0 * 212.0), 2.0 * R * (8.0 * kStoiFrame + 8.0 * kStoiBands));
-    }
-    {   // per segment: about 30 operations a value of either tensor
-        Prof pr(c, call.s, "stoi_segments");
-        launch_stoi_segments("stoi_segments", runs_dev, nclips, st, nkept, bands, rows, segv, segments_out, call.s);
-        pr.done(S * 2.0 * kStoiBands * kStoiSegment * 30.0, S * (2.0 * 8.0 * kStoiBands * kStoiSegment + 16.0 + (segments_out ? 16.0 : 0.0)));
-    }
-    {
-        Prof pr(c, call.s, "stoi_finish");
-        launch_stoi_finish("stoi_finish", runs_dev, nclips, nkept, segv, out, call.s);
-        pr.done(2.0 * S, 16.0 * S + 8.0 * kStoiFields * C);
-    }
-    return call.finish(NHANS_OK);
+    return ctx_call(c, stream, [&](hipStream_t s) -> int {
+        if (nclips == 0) return NHANS_OK;
+        WsPlan p;
+        StoiRun* runs_dev; double *tab, *power, *bands, *segv; int* kept; long long* nkept;
+        p.add(&runs_dev, runs.size());
+        p.add(&tab, kStoiTable);
+        p.add(&power, (size_t)frames);
+        p.add(&kept, (size_t)frames);
+        p.add(&nkept, runs.size());
+        p.add(&bands, (size_t)rows * 2 * kStoiBands);
+        p.add(&segv, (size_t)segs * 2);
+        rc = ws_commit(c, p); if (rc) return rc;
+        rc = h2d(c, runs_dev, runs, s); if (rc) return rc;
+        std::vector<double> table(kStoiTable);
+        stoi_table(table.data());
+        rc = h2d(c, tab, table, s); if (rc) return rc;
+        const double F = (double)frames, R = (double)rows, S = (double)segs, C = (double)nclips;
+        {   // per sample of a frame: a product and a fused multiply-add
+            Prof pr(c, s, "stoi_power");
+            launch_stoi_power("stoi_power", runs_dev, nclips, pt, tab, power, s);
+            pr.done(3.0 * kStoiFrame * F, 4.0 * kStoiFrame * F + 8.0 * F);
+        }
+        {
+            Prof pr(c, s, "stoi_keep");
+            launch_stoi_keep("stoi_keep", runs_dev, nclips, power, kept, nkept, s);
+            pr.done(F, 16.0 * F + 4.0 * F + 8.0 * C);
+        }
+        {   // per frame and signal: 4 operations a sample, 5 N log2 N of the transform, 3 a bin; what is silent is not computed
+            Prof pr(c, s, "stoi_bands");
+            launch_stoi_bands("stoi_bands", runs_dev, nclips, bt, tab, kept, nkept, bands, rows, s);
+            pr.done(2.0 * R * (4.0 * kStoiFrame + 5.0 * kStoiFft * 9.0 + 3.0 * 212.0), 2.0 * R * (8.0 * kStoiFrame + 8.0 * kStoiBands));
+        }
+        {   // per segment: about 30 operations a value of either tensor
+            Prof pr(c, s, "stoi_segments");
+            launch_stoi_segments("stoi_segments", runs_dev, nclips, st, nkept, bands, rows, segv, segments_out, s);
+            pr.done(S * 2.0 * kStoiBands * kStoiSegment * 30.0, S * (2.0 * 8.0 * kStoiBands * kStoiSegment + 16.0 + (segments_out ? 16.0 : 0.0)));
+        }
+        {
+            Prof pr(c, s, "stoi_finish");
+            launch_stoi_finish("stoi_finish", runs_dev, nclips, nkept, segv, out, s);
+            pr.done(2.0 * S, 16.0 * S + 8.0 * kStoiFields * C);
+        }
+        return NHANS_OK;
+    });
 }
 
 }  // extern "C"

@@ -49,6 +49,39 @@ def test_consecutive_calls_on_different_streams_are_ordered(eng):
     assert eng.take_status() == 0
 
 
+def test_scoring_calls_on_alternating_streams_are_ordered_through_a_refused_call(eng):
+    """The same ordering for the scoring family, which shares the one workspace too: quality on stream A, align on stream B,
+    a call refused inside the bracket (nhans_channel_mean with no channel), the wave score on stream A again, no host
+    synchronisation in between -- every set of records equals, bit for bit, that of the call run alone.  Two pairs of
+    2,561 and 5,121 samples: a score tile's edge, and two tiles."""
+    rng = np.random.RandomState(620)
+    tgt = [rng.standard_normal(n).astype(np.float32) * 0.1 for n in (2561, 5121)]
+    est = [np.roll(t, 5 + 12 * i) + rng.standard_normal(t.size).astype(np.float32) * 0.02 for i, t in enumerate(tgt)]
+    (e, eo), (t, to) = eng._dev(est), eng._dev(tgt)
+    calls = [lambda: eng.quality_device(e, eo, t, to), lambda: eng.align_device(e, eo, t, to, max_lag=64),
+             lambda: eng.score_device(e, eo, t, to)]
+    solo = []
+    for call in calls:
+        solo.append(call().cpu().numpy())           # (the download synchronises)
+        torch.cuda.synchronize()
+    assert all(np.isfinite(s[:, 0]).all() for s in solo) and list(solo[1][:, 3]) == [5.0, 17.0]
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    for _ in range(3):
+        with torch.cuda.stream(sa):
+            q = calls[0]()
+        with torch.cuda.stream(sb):
+            a = calls[1]()
+        with torch.cuda.stream(sa):
+            rc = eng.lib.nhans_channel_mean(eng.handle, hip.ptr(e), 0, 16, hip.ptr(e), eng._stream())
+            msg = eng.lib.nhans_last_error()
+            s = calls[2]()
+        torch.cuda.synchronize()
+        assert rc == -1 and msg == b"nhans_channel_mean: nchannels must be >= 1 and 0 <= nsamples < 2^39"     # NHANS_EINVAL
+        for got, want in zip((q, a, s), solo):
+            assert np.array_equal(got.cpu().numpy().view(np.uint64), want.view(np.uint64))
+    assert eng.take_status() == 0
+
+
 def test_argument_errors_come_back_as_codes_with_a_message(eng):
     lib = eng.lib
     z = ctypes.c_void_p(None)

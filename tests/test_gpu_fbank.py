@@ -380,6 +380,9 @@ def test_live_sessions_mono_and_split(eng):
             sess.set_context(0, *_ctx(911 + c))
             sess.enable_fbank(fb)
             mono.append(_live_rows(sess, [([xs[c][a:b]], [b == n]) for a, b in cuts], [0])[0])
+            with pytest.raises(hip.NhansError) as err:      # (a read returns its rows' count, or the status: one slot)
+                sess.features(1)
+            assert err.value.code == -1 and "nhans_fbank_live_read: slot 1 outside [0, 1)" in str(err.value)
         finally:
             sess.close()
     for c in range(2):

@@ -603,6 +603,18 @@ def test_refusals_leave_the_object_usable(eng):
         assert lib.nhans_level_live_read(sess.handle, 1, out, eng._stream()) == -1
         assert b"nhans_level_live_read" in lib.nhans_last_error()
         assert lib.nhans_level_live_read(sess.handle, 0, None, eng._stream()) == -1
+        assert lib.nhans_level_live_gains(sess.handle, 1, None, 0, eng._stream()) == -1
+        assert b"nhans_level_live_gains: slot 1 outside" in lib.nhans_last_error()
+
+    def short_room():
+        """Room for one gain fewer than the last push made final: the status, not a count."""
+        n = lib.nhans_level_live_gains(sess.handle, 0, None, 0, eng._stream())
+        if n > 0:
+            room = (ctypes.c_float * n)()
+            assert lib.nhans_level_live_gains(sess.handle, 0, room, n - 1, eng._stream()) == -1
+            assert lib.nhans_last_error() == b"nhans_level_live_gains: room for %d gains, %d needed" % (n - 1, n)
+            assert lib.nhans_level_live_gains(sess.handle, 0, room, n, eng._stream()) == n
+        return n > 0
 
     try:
         bad()
@@ -611,7 +623,7 @@ def test_refusals_leave_the_object_usable(eng):
         with pytest.raises(hip.NhansError) as err:
             sess.levels(0)
         assert err.value.code == hip.ESHORT
-        outs, pos = [], 0
+        outs, pos, short = [], 0, 0
         cuts = _cuts("primes", len(x), rate_in)
         for k, n in enumerate(cuts):
             if k % 3 == 0:
@@ -619,6 +631,8 @@ def test_refusals_leave_the_object_usable(eng):
             got, = sess.push([x[pos:pos + n]], [k == len(cuts) - 1])
             outs.append(got)
             pos += n
+            short += short_room()
+        assert short > 0
         assert sess.levels(0)["hops"] == len(want) * 16000 // rate_out // HOP + 1
     finally:
         sess.close()
