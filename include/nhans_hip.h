@@ -1321,6 +1321,79 @@ int nhans_phase_project(nhans_ctx* ctx, const float* logmag_dev, const float* t_
 int nhans_phase_refine(nhans_ctx* ctx, const float* logmag_dev, const float* phase_in_dev, const int64_t* frame_offsets_host,
                        int nclips, int iters, double alpha, float* phase_out_dev, double* inc_out_dev, void* stream);
 
+/* ---- Mask-driven MVDR beamforming of multi-channel clips ---------------------------------------------------------------
+ * A multi-channel clip has always been reduced to the mean of its channels (nhans_channel_mean) before anything else.
+ * These calls use what an array carries, the phase differences between its microphones: a mask (the network's, or any)
+ * picks out the spatial covariance of speech and of noise, and a distortionless linear filter (MVDR, Souden's form) is put
+ * on the channels.  n-hans_amd/csrc/mvdr.hip; the same definition in float64:
+ * n-hans_amd/mvdr.py.  Added without moving NHANS_ABI_VERSION; a caller that may meet an older library looks the functions
+ * up by symbol.
+ *
+ * A clip has C channels, 1 <= C <= 8, of n samples each and T = nhans_num_frames(n) >= 1 frames.  C is one value per call.
+ *   planes     clip i is C planes of n_i samples one after the other: channel c begins at planes + C off[i] + c n_i, with
+ *              off = sample_offsets_host counted in samples PER CHANNEL (the offsets the mono calls take for one channel).
+ *   X          the spectra, complex float32 stored as (re, im), in the planes' layout: the T_i rows of 201 bins of
+ *              channel c of clip i begin at row C foff[i] + c T_i, foff[i] = sum_{j<i} T_j -- the rows nhans_stft_features
+ *              gives for the planes taken as nclips * C clips.  X_c[t, k] is what nhans_stft_features holds before its log
+ *              and angle: logmag_out_dev and phase_out_dev of nhans_mvdr_spectra (nullable, [C F, 201] in X's layout, F =
+ *              foff[nclips]) are the analysis kernel's log and atan2 of the very registers X is stored from, and equal
+ *              nhans_stft_features' rows of the channel-clips bit for bit.
+ *   mask       float32 rows [F, 201] at foff.  m = min(max(v, 0), 1), where max(NaN, 0) = 0: a NaN counts as 0 (the bin of
+ *              that frame is all noise).  With NHANS_MVDR_LOGGAIN the rows are a log-gain g -- what nhans_mask_net writes
+ *              to logits_out_dev -- and v = 1 for g > 0, else exp(g) with nhans_istft's exp; a NaN g counts as m = 0.
+ *   Phi        per clip and bin, in double, x = (X_0 ... X_{C-1})[t, k]:  Phi_s = sum_t m x x^H,  Phi_n = sum_t (1 - m) x x^H
+ *              with 1 - m formed in double.  Entry (i, j) of a frame is p = x_i conj(x_j), each part one rounding (the two
+ *              products of float32 values are exact in double), then fma(m, p, sum) and fma(1 - m, p, sum).  The diagonal's
+ *              imaginary part is 0.  The sum runs over the frames in ASCENDING order, one chain per entry: the kernel
+ *              splits a bin's entries, not its frames, over the waves of a workgroup, so an entry has one owner and no
+ *              partial sums are combined.  Every value is a function of the clip alone.
+ *              cov_out_dev (nullable): complex double [nclips][2][C][C][201] -- Phi_s then Phi_n, entry (i, j), bin last.
+ *   w          tr = sum_i Re Phi_n[i][i] (i ascending);  Phi_n' = Phi_n + loading (tr / C) I, 0 <= loading <= 1 (1e-6 is the
+ *              recommended value);  Phi_n' = L L^H by Cholesky, column by column, in double;  G = Phi_n'^-1 Phi_s by the two
+ *              triangular solves, a column at a time;  tau = sum_j Re G[j][j] (j ascending);  w = G[:, ref] / tau.  No
+ *              steering vector and no eigen-decomposition; w does not change when either mask's sum is scaled.
+ *              FALLBACK, w = e_ref (the reference channel passes through) and the bin counts in fallback_bins: tr = 0; a
+ *              pivot that is not positive and finite; tau not positive and finite; a part of w not finite.  A mask of all
+ *              ones or all zeros therefore returns the reference channel and says so.
+ *              w_out_dev: complex double [nclips][201][C].
+ *   y          y[t, k] = sum_c conj(w_c) X_c[t, k], channels ascending, four fma per channel in double, rounded ONCE to
+ *              complex float32.  The output is rows [F, 201] at foff: lm = log(max(|y|, 1e-5)) and ph = atan2(im, re) with
+ *              the analysis kernel's square root, log and atan2 (note the max: the analysis rows add 1e-5 instead).
+ *              loggain_dev (nullable, rows [F, 201]): lm + g in float32 -- nhans_mask_net's own last step.
+ *              y_out_dev of nhans_mvdr_apply (nullable): y itself, complex float32 [F, 201], before any log-gain.  The
+ *              beamformed signal is thus what every other signal here is: nhans_mask_net, nhans_istft, nhans_phase_refine,
+ *              nhans_fbank_rows and nhans_score_rows take the rows as they are.
+ *   record     NHANS_MVDR_FIELDS = 6 doubles per clip: frames, channels, ref, fallback_bins, energy_ref = sum |X_ref|^2,
+ *              energy_out = sum |y|^2 of the float32 y (before any log-gain).  energy_ref: per bin over the frames
+ *              ascending, then lane l of 64 sums bins l, l + 64, l + 128, l + 192 ascending and the 64 sums go through the
+ *              tree 32, ..., 1 of the scoring kernels.  energy_out: per frame a lane's bins l, l + 64, ... ascending and
+ *              the tree; then over the frames lane l sums frames l, l + 64, ... ascending and the tree.
+ *              nhans_mvdr_weights writes fields 0 ... 4 and NaN into energy_out; nhans_mvdr_apply writes energy_out alone
+ *              (records_dev nullable).  nhans_mvdr writes all six.
+ * Non-finite samples: the bins they reach fall back or not as the rules above say; their rows are unspecified.
+ * Every output has the same bits for a clip alone or in any batch, at any position, on every run, and through nhans_mvdr
+ * as through the three stage calls.  Inputs are only read; nothing is written outside the outputs.
+ * Launches: spectra 1 ("mvdr_spectra"), weights 2 ("mvdr_cov", "mvdr_solve"), filter 1 ("mvdr_apply") and with a record
+ * one more ("mvdr_energy").  nhans_mvdr keeps X (8 C bytes per bin and frame), the covariances and, unless asked for, w
+ * in the workspace.
+ * NHANS_EINVAL before anything is launched and with nothing written, the message naming the clip where there is one:
+ * nchannels outside 1 ... 8, ref outside 0 ... nchannels - 1, loading outside [0, 1] (or NaN), unknown flag bits, a NULL that
+ * is needed, nclips < 0, offsets that descend, a clip without a frame or with more than 5,000,000. */
+#define NHANS_MVDR_MAX_CHANNELS 8
+#define NHANS_MVDR_FIELDS 6
+#define NHANS_MVDR_LOGGAIN 1
+int nhans_mvdr_spectra(nhans_ctx* ctx, const float* planes_dev, const int64_t* sample_offsets_host, int nclips, int nchannels,
+                       float* x_out_dev, float* logmag_out_dev, float* phase_out_dev, void* stream);
+int nhans_mvdr_weights(nhans_ctx* ctx, const float* x_dev, const float* mask_dev, const int64_t* frame_offsets_host, int nclips,
+                       int nchannels, int ref, double loading, int flags, double* w_out_dev, double* cov_out_dev,
+                       double* records_out_dev, void* stream);
+int nhans_mvdr_apply(nhans_ctx* ctx, const float* x_dev, const double* w_dev, const float* loggain_dev,
+                     const int64_t* frame_offsets_host, int nclips, int nchannels, float* logmag_out_dev, float* phase_out_dev,
+                     float* y_out_dev, double* records_dev, void* stream);
+int nhans_mvdr(nhans_ctx* ctx, const float* planes_dev, const int64_t* sample_offsets_host, int nclips, int nchannels,
+               const float* mask_dev, int ref, double loading, int flags, const float* loggain_dev, float* logmag_out_dev,
+               float* phase_out_dev, double* w_out_dev, double* records_out_dev, void* stream);
+
 /* Profiling (option "profile" = 1): per-kernel launch counts, summed milliseconds, summed
  * algorithmic FLOPs / bytes ("flops": 2*M*K*N of the DIRECT convolution whichever form runs it) and the
  * FLOPs the matrix cores executed for them ("mfma_flops": three products per MAC in split-f16 mode, fewer

@@ -73,6 +73,9 @@ class Flags(object):
     stoi = False         # --stoi: with --score_against, also STOI and extended STOI (score.py: stoi_reference is the definition)
     phase_iters = 0      # --phase_iters N: Griffin-Lim iterations on the denoised rows before their iSTFT (include/nhans_hip.h: "phase_iters")
     phase_alpha = 0.0    # --phase_alpha A: their momentum, 0 <= A < 1
+    array = None         # --array mvdr: a multi-channel input keeps its channels and goes through Context.enhance_array (mask-driven MVDR)
+    array_ref = 0        # --array_ref R: the reference channel
+    array_post = "none"  # --array_post none|mask|net: what follows the beamformer
     lookahead_ms = 10 * spec.LOOKAHEAD   # --lookahead_ms: 10 ms per frame of look-ahead (include/nhans_hip.h: "lookahead"), 170 = all 17
 
 
@@ -118,6 +121,71 @@ def read_wav_any(in_path):
 
 def _reader():
     return read_wav_any if getattr(FLAGS, 'convert', False) else read_wav
+
+
+def read_wav_channels(in_path):
+    """--array: the input with its channels kept, int16-scale values [n, C] -- read_wav's contract, or with the converter
+    read_wav_any's steps, each without the mean over the channels."""
+    rate, samples = wavread(in_path)
+    if samples.ndim != 2 or samples.shape[1] < 2:
+        raise ValueError("%s: --array needs more than one channel" % in_path)
+    if not getattr(FLAGS, 'convert', False):
+        if rate != FLAGS.Fs:
+            raise AssertionError("%s: sample rate %d Hz, expected %d" % (in_path, rate, FLAGS.Fs))
+        if samples.dtype != np.int16:
+            raise AssertionError("%s: sample format %s, expected int16" % (in_path, samples.dtype))
+        return samples
+    if rate == FLAGS.Fs and samples.dtype == np.int16:
+        return samples
+    x = samples.astype(np.float64)
+    if samples.dtype == np.uint8:
+        x = (x - 128.0) * 256.0
+    elif samples.dtype == np.int32:
+        x = x / 65536.0
+    elif samples.dtype.kind == 'f':
+        x = x * 32768.0
+    if rate != FLAGS.Fs:
+        from math import gcd
+        from scipy.signal import resample_poly
+        g = gcd(int(FLAGS.Fs), int(rate))
+        x = resample_poly(x, FLAGS.Fs // g, rate // g, axis=0)
+    return np.clip(np.round(x), -32768, 32767).astype(np.int16)
+
+
+def handle_array_signals(mixedpath, a_path, b_path):
+    """--array: (ctx_a, ctx_b, mixed [n, C]) float32.  Every channel is divided by what the file is divided by today, the
+    peak of the channels' mean + 1e-6, so that the mean of the channels is today's signal; trimmed to whole frames."""
+    try:
+        x = read_wav_channels(mixedpath)
+        peak = np.max(np.abs(x.mean(axis=1))) if len(x) else 0
+        mixed = (x / (peak + 0.000001)).astype(np.float32)
+        spare = (len(mixed) - spec.WIN) % spec.HOP
+        mixed = mixed[:len(mixed) - spare] if spare else mixed
+        if len(mixed) < spec.WIN:
+            raise ValueError("%s: shorter than one %d-sample STFT window" % (mixedpath, spec.WIN))
+        return normalise(_read_context(a_path)), normalise(_read_context(b_path)), mixed
+    except Exception:
+        print('error in threads')
+        print(mixedpath, a_path, b_path)
+        return None
+
+
+def _array_kw():
+    return {"ref": int(FLAGS.array_ref), "post": FLAGS.array_post, "mask_from": "mean", "want_mixed": True}
+
+
+def _enhance_arrays(eng, mixes, ca, cb):
+    """--array: [(denoised, mixed_processed)] per clip; the clips of one channel count go through one enhance_array call."""
+    outs = [None] * len(mixes)
+    for C in sorted({m.shape[1] for m in mixes}):
+        idx = [i for i, m in enumerate(mixes) if m.shape[1] == C]
+        if not 0 <= int(FLAGS.array_ref) < C:
+            raise ValueError("--array_ref %d: the input has %d channels" % (FLAGS.array_ref, C))
+        res = eng.enhance_array([mixes[i] for i in idx], [ca[i] for i in idx], [cb[i] for i in idx], **_array_kw(), **_lookahead_kw(),
+                                **_phase_kw())
+        for k, i in enumerate(idx):
+            outs[i] = (res["denoised_wav"][k], res["mixed_wav"][k])
+    return outs
 
 
 def normalise(samples):
@@ -278,14 +346,18 @@ def _enhance_files(kind, mixedpath, ctx_a_path, ctx_b_path):
     resnet_block argument order."""
     import time
     t0 = time.perf_counter()
-    sig = handle_signals(mixedpath, ctx_a_path, ctx_b_path, kind)
+    sig = handle_array_signals(mixedpath, ctx_a_path, ctx_b_path) if getattr(FLAGS, "array", None) else \
+        handle_signals(mixedpath, ctx_a_path, ctx_b_path, kind)
     if sig is None:
         raise RuntimeError("could not read %s / %s / %s" % (mixedpath, ctx_a_path, ctx_b_path))
     ca, cb, mixed = sig
     t1 = time.perf_counter()
     eng = get_enhancer(kind)
     t2 = time.perf_counter()
-    if getattr(FLAGS, "online_ms", None):
+    if getattr(FLAGS, "array", None):
+        (den, mix), = _enhance_arrays(eng, [mixed], [ca], [cb])
+        res = {"denoised_wav": [den], "mixed_wav": [mix]}
+    elif getattr(FLAGS, "online_ms", None):
         res = _enhance_online(eng, mixedpath, ca, cb, FLAGS.online_ms, mixed if FLAGS.convert_on == "gpu" else None)
     else:
         res = eng.enhance([mixed], [ca], [cb], want_mixed=True, **_lookahead_kw(), **_phase_kw())
@@ -493,12 +565,14 @@ def apply_batch(kind, jobs):
     sigs = []
     for mixedpath, pospath, negpath, _ in jobs[lo:hi]:
         a_path, b_path = (pospath, negpath) if kind == spec.DENOISER else (negpath, pospath)
-        sigs.append(handle_signals(mixedpath, a_path, b_path, kind))    # None: unreadable triple, reported there, skipped
+        sigs.append(handle_array_signals(mixedpath, a_path, b_path) if getattr(FLAGS, "array", None) else
+                    handle_signals(mixedpath, a_path, b_path, kind))    # None: unreadable triple, reported there, skipped
     good = [s for s in sigs if s is not None]
     if world == 1 and not good:
         return 0
     eng = get_enhancer(kind)
-    done = iter(_enhance_in_calls(eng, [s[2] for s in good], [s[0] for s in good], [s[1] for s in good]))
+    done = iter((_enhance_arrays if getattr(FLAGS, "array", None) else _enhance_in_calls)(
+        eng, [s[2] for s in good], [s[0] for s in good], [s[1] for s in good]))
     outs = [None if s is None else next(done) for s in sigs]
     if world > 1:
         import torch.distributed as tdist
@@ -699,6 +773,43 @@ def phase_ceiling(engine, mixed, target, iters=(0, 8, 32), alpha=0.0):
     return out
 
 
+def array_ceiling(engine, x, target, mask, ref=0, loading=1e-6, edge=400):
+    """What a mask is worth on an array, with and without the beamformer, on the device: x float32 [n, C] (trimmed to
+    whole frames), target: the target's image at channel `ref`, mask: float32 [T, 201] in [0, 1] -> dict of four records
+    by score.FIELDS (Engine.score), each against the target over the clip without its first and last `edge` samples --
+    "ref": channel `ref` as it is; "mean": the mean of the channels (nhans_channel_mean: what a multi-channel file is
+    reduced to today); "mask": the mask alone on channel `ref` (its rows with the log of the mask added, nhans_istft);
+    "mvdr": the beamformer's rows (Engine.mvdr_device) through nhans_istft -- and "fallback_bins".  The edges are left
+    out because the first and last 240 samples lie under fewer than three frames and are not reconstructed by the
+    window pair, which would cost the two estimates that went through it and not the other two."""
+    import torch
+    from . import hip, mvdr
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    n, C = x.shape
+    T = int(engine.lib.nhans_num_frames(n))
+    if T < 1 or (T - 1) * spec.HOP + spec.WIN != n or len(target) != n:
+        raise ValueError("array_ceiling: clip and target of one length, trimmed to whole frames")
+    if n <= 2 * edge:
+        raise ValueError("array_ceiling: nothing left between the edges")
+    m = np.ascontiguousarray(mask, dtype=np.float32)
+    planes = torch.from_numpy(mvdr.planes(x)).to(engine.device)
+    mask_t = torch.from_numpy(m).to(engine.device)
+    bf = engine.mvdr_device(planes, [0, n], C, mask_t, ref=ref, loading=loading)
+    wav_bf, _ = engine.istft(bf["logmag"], bf["phase"], [0, T])
+    # the mask alone: one channel through the same filter is that channel (w = 1), with the log of the mask as its gain
+    gain = torch.from_numpy(np.log(np.maximum(mvdr.mask_values(m), 1e-8)).astype(np.float32)).to(engine.device)
+    one = engine.mvdr_device(planes[ref * n:(ref + 1) * n].contiguous(), [0, n], 1, mask_t, gain_t=gain)
+    wav_mask, _ = engine.istft(one["logmag"], one["phase"], [0, T])
+    mean = torch.empty(n, dtype=torch.float32, device=engine.device)
+    hip.check(engine.lib.nhans_channel_mean(engine.handle, hip.ptr(planes), C, n, hip.ptr(mean), engine._stream()))
+    cut = lambda w: np.ascontiguousarray(np.asarray(w, dtype=np.float32)[edge:n - edge])
+    est = [cut(x[:, ref]), cut(mean.cpu().numpy()), cut(wav_mask.cpu().numpy()), cut(wav_bf.cpu().numpy())]
+    recs = engine.score(est, [cut(target)] * 4)
+    out = dict(zip(("ref", "mean", "mask", "mvdr"), recs))
+    out["fallback_bins"] = int(bf["records"][0, 3].item())
+    return out
+
+
 def _eval_wav_path(dump_dir, modelname, step, triple, snr_pos, snr_neg, kind):
     base = [os.path.basename(p)[:-4] for p in triple]
     return os.path.join(dump_dir, '{}_{}_{}_{}_{}_{}_{}_{}.wav'.format(modelname, step, base[0], base[1], base[2], snr_pos, snr_neg, kind))
@@ -884,6 +995,13 @@ def _parse(argv, prog):
                    help='Griffin-Lim iterations on the denoised rows, from the mixture\'s phase, before the denoised file is rebuilt '
                         '(0 ... 256; default 0: the mixture\'s phase as it is; offline only)')
     p.add_argument('--phase_alpha', type=float, default=0.0, metavar='A', help='momentum of --phase_iters, 0 <= A < 1 (default 0)')
+    p.add_argument('--array', default=None, choices=['mvdr'],
+                   help='a multi-channel input keeps its channels: the network\'s mask, from the mean of the channels, picks the '
+                        'spatial covariances of speech and noise, and an MVDR beamformer is put on the channels on the device '
+                        '(file and directory mode; default: the mean of the channels, as always)')
+    p.add_argument('--array_ref', type=int, default=0, metavar='R', help='reference channel of --array (default 0)')
+    p.add_argument('--array_post', default='none', choices=['none', 'mask', 'net'],
+                   help='what follows the beamformer of --array: nothing, the same mask, or a second pass of the network (default none)')
     p.add_argument('--fbank_out', default=None, metavar='PATH.npy',
                    help='file mode only: also write the log-mel filterbank features of the denoised signal (float32 '
                         '[frames, n_mels], 25 ms / 10 ms frames, numpy.save) computed on the device from the network\'s '
@@ -981,6 +1099,29 @@ def _parse(argv, prog):
         if a.output_rate != 'input' or a.convert_on != 'gpu' or not a.convert:
             p.error('--highband needs --output_rate input --convert_on gpu (and no --no-convert): the band is added at the '
                     'input file\'s own rate, on the device')
+    if a.array is None:
+        if a.array_ref != 0 or a.array_post != 'none':
+            p.error('--array_ref and --array_post need --array mvdr')
+    else:
+        for flag, on in (('--online_ms', a.online_ms is not None), ('--convert_on gpu', a.convert_on == 'gpu'),
+                         ('--highband', a.highband is not None), ('--fbank_out', bool(a.fbank_out)),
+                         ('a sharded run', int(os.environ.get("WORLD_SIZE", "1")) > 1)):
+            if on:
+                p.error('--array does not go with %s' % flag)
+        names = [os.path.join(a.input, n) for n in sorted(os.listdir(a.input)) if n.lower().endswith('.wav')] \
+            if os.path.isdir(a.input) else [a.input]
+        for path in names:
+            try:
+                shape = wavread(path, mmap=True)[1].shape
+            except Exception:
+                continue                                     # (an unreadable input is reported where it is read)
+            C = shape[1] if len(shape) == 2 else 1
+            if C < 2:
+                p.error('--array needs inputs with more than one channel; %s is mono' % path)
+            if C > 8:
+                p.error('--array takes up to 8 channels; %s has %d' % (path, C))
+            if not 0 <= a.array_ref < C:
+                p.error('--array_ref must be in 0 ... %d for %s; got %d' % (C - 1, path, a.array_ref))
     if not 0 <= a.phase_iters <= 256:
         p.error('--phase_iters must be in 0 ... 256; got %d' % a.phase_iters)
     if not 0.0 <= a.phase_alpha < 1.0:

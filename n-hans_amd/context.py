@@ -2,11 +2,12 @@
 lite.LiteEngine both are, the f32 redo of work that saturated the f16x3 path, the device memory of either engine, and
 the ragged-batch helpers.  No torch at module level: the single-process command line (lite.py) imports this."""
 import ctypes
+import operator
 import warnings
 
 import numpy as np
 
-from . import hip, hiprt, score as score_mod, spec
+from . import hip, hiprt, mvdr as mvdr_mod, score as score_mod, spec
 
 
 class Context:
@@ -515,6 +516,173 @@ class Context:
             mem.free(*ins, *outs, rec)
         signals = {k: [g[off[j]:off[j + 1]] for j in range(nj)] for k, g in zip(names, got)}
         return signals, [dict(zip(mixing.RECORD_FIELDS, (float(v) for v in r))) for r in recs]
+
+    # ---- mask-driven MVDR beamforming (include/nhans_hip.h: nhans_mvdr_*) ---------------------------
+    def _array_clips(self, who, clips):
+        """[n_i, C] arrays -> (the float32 arrays, C, the flat planes of all clips, the per-channel sample offsets, the
+        frame offsets); every clip has a frame."""
+        xs = [np.asarray(x, dtype=np.float32) for x in clips]
+        if not xs or any(x.ndim != 2 for x in xs) or len({x.shape[1] for x in xs}) != 1:
+            raise ValueError("%s: a list of [n, C] arrays of one channel count C" % who)
+        C = xs[0].shape[1]
+        if not 1 <= C <= hip.MVDR_MAX_CHANNELS:
+            raise ValueError("%s: 1 ... %d channels, not %d" % (who, hip.MVDR_MAX_CHANNELS, C))
+        off = offsets(len(x) for x in xs)
+        nfr = [int(self.lib.nhans_num_frames(len(x))) for x in xs]
+        if any(t == 0 for t in nfr):
+            raise ValueError("%s: clip %d has fewer than %d samples: no STFT frame" % (who, nfr.index(0), spec.WIN))
+        pf = np.ascontiguousarray(np.concatenate([mvdr_mod.planes(x) for x in xs]))
+        return xs, C, pf, off, offsets(nfr)
+
+    def mvdr(self, clips, masks, ref=0, loading=mvdr_mod.LOADING, loggain=False, gains=None, stages=False):
+        """Lists of [n_i, C] float32 clips (one C) and of [T_i, 201] mask rows -- loggain=True: log-gain rows, what mask_net
+        writes as logits -- -> one dict per clip: "logmag" and "phase", float32 [T_i, 201]: the rows of the beamformed
+        signal y = w^H x (gains: a list of [T_i, 201] log-gains added to logmag); "w", complex128 [201, C]; "record" by
+        mvdr.FIELDS.  One upload, nhans_mvdr, one download.  stages=True: the three stage calls instead (the same bits),
+        and each dict gains "y" complex64 [T_i, 201] (the beamformed values before any gain), "X" complex64 [C, T_i, 201], "phi_s" and "phi_n" complex128 [201, C, C], and "chan_logmag" and
+        "chan_phase", float32 [C, T_i, 201]: the analysis rows of every channel."""
+        xs, C, pf, off, foff = self._array_clips("mvdr", clips)
+        n, F, B = len(xs), foff[-1], spec.BINS
+        rows_of = lambda lst: np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.float32).reshape(-1) for r in lst]))
+        for lst in (masks, gains):
+            if lst is not None and (len(lst) != n or any(np.shape(r) != (foff[i + 1] - foff[i], B) for i, r in enumerate(lst))):
+                raise ValueError("mvdr: one [T_i, %d] array of rows per clip" % B)
+        lib, mem = self.lib, Mem(self)
+        flags = hip.MVDR_LOGGAIN if loggain else 0
+        nf = hip.MVDR_FIELDS
+        ins = [mem.up(pf), mem.up(rows_of(masks)), mem.up(rows_of(gains)) if gains is not None else None]
+        lm, ph = mem.empty(F * B), mem.empty(F * B)
+        w, rec = mem.empty(n * B * C * 2, np.float64), mem.empty(n * nf, np.float64)
+        X = cov = clm = cph = yb = None
+        if stages:
+            X, clm, cph = mem.empty(2 * C * F * B), mem.empty(C * F * B), mem.empty(C * F * B)
+            cov, yb = mem.empty(n * 4 * C * C * B, np.float64), mem.empty(2 * F * B)
+        try:
+            s, so, fo = mem.stream(), hip.i64_array(off), hip.i64_array(foff)
+            if stages:
+                hip.check(lib.nhans_mvdr_spectra(self.handle, mem.p(ins[0]), so, n, C, mem.p(X), mem.p(clm), mem.p(cph), s))
+                hip.check(lib.nhans_mvdr_weights(self.handle, mem.p(X), mem.p(ins[1]), fo, n, C, int(ref), float(loading), flags,
+                                                 mem.p(w), mem.p(cov), mem.p(rec), s))
+                hip.check(lib.nhans_mvdr_apply(self.handle, mem.p(X), mem.p(w), mem.p(ins[2]), fo, n, C, mem.p(lm), mem.p(ph),
+                                               mem.p(yb), mem.p(rec), s))
+            else:
+                hip.check(lib.nhans_mvdr(self.handle, mem.p(ins[0]), so, n, C, mem.p(ins[1]), int(ref), float(loading), flags,
+                                         mem.p(ins[2]), mem.p(lm), mem.p(ph), mem.p(w), mem.p(rec), s))
+            self._sync()
+            g = lambda buf, cnt, dt=np.float32: np.array(mem.down(buf, cnt, dt), dtype=dt)
+            lm_h, ph_h = g(lm, F * B).reshape(F, B), g(ph, F * B).reshape(F, B)
+            w_h = g(w, n * B * C * 2, np.float64).view(np.complex128).reshape(n, B, C)
+            rec_h = g(rec, n * nf, np.float64).reshape(n, nf)
+            if stages:
+                X_h = g(X, 2 * C * F * B).view(np.complex64).reshape(C * F, B)
+                clm_h, cph_h = g(clm, C * F * B).reshape(C * F, B), g(cph, C * F * B).reshape(C * F, B)
+                cov_h = g(cov, n * 4 * C * C * B, np.float64).view(np.complex128).reshape(n, 2, C, C, B)
+                y_h = g(yb, 2 * F * B).view(np.complex64).reshape(F, B)
+        finally:
+            mem.free(*ins, lm, ph, w, rec, X, cov, clm, cph, yb)
+        res = []
+        for i in range(n):
+            a, b, T = foff[i], foff[i + 1], foff[i + 1] - foff[i]
+            d = {"logmag": lm_h[a:b], "phase": ph_h[a:b], "w": w_h[i], "record": mvdr_mod.record(rec_h[i])}
+            if stages:
+                ch = lambda r: r[C * a:C * b].reshape(C, T, B)
+                d.update(y=y_h[a:b], X=ch(X_h), chan_logmag=ch(clm_h), chan_phase=ch(cph_h),
+                         phi_s=np.ascontiguousarray(cov_h[i, 0].transpose(2, 0, 1)), phi_n=np.ascontiguousarray(cov_h[i, 1].transpose(2, 0, 1)))
+            res.append(d)
+        return res
+
+    def enhance_array(self, mixes, ctx_a, ctx_b, ref=0, mask_from="mean", post="none", loading=mvdr_mod.LOADING,
+                      lookahead=spec.LOOKAHEAD, phase_iters=0, phase_alpha=0.0, taps=False, want_mixed=False):
+        """Multi-channel clips through the network and an MVDR beamformer, on the device throughout.  mixes: a list of
+        [n_i, C] float32 arrays, normalised and trimmed to whole frames as enhance takes its mixtures; ctx_a, ctx_b: the
+        conditioning recordings, as for enhance.  The existing path runs on the mean of the channels (mask_from="mean":
+        nhans_channel_mean, the signal enhance is given today, bit for bit) or on channel mask_from=j; nhans_mask_net's
+        logits are the log-gain whose mask picks the covariances (nhans_mvdr, NHANS_MVDR_LOGGAIN, reference channel ref).
+        post: what follows the beamformer -- "none": its rows go to nhans_istft; "mask": the same log-gain is added to them
+        (in the filter's launch); "net": a second nhans_mask_net pass on them with the same embeddings.  phase_iters,
+        phase_alpha: nhans_phase_refine on the final rows from the beamformed phase.  lookahead as in enhance; a saturated
+        f16x3 batch is redone in f32 as everywhere.
+        -> dict: "denoised_wav", one float32 array of (T_i - 1) 160 + 400 samples per clip; "records", one dict by
+        mvdr.FIELDS per clip; want_mixed=True: plus "mixed_wav", the transform round trip of the signal the mask came from
+        (enhance's mixed_wav of that signal); taps=True: plus "logits", "bf_logmag", "bf_phase", "logmag" and "phase" (the rows that went
+        to nhans_istft), float32 [T_i, 201] per clip."""
+        if post not in ("none", "mask", "net"):
+            raise ValueError("enhance_array: post is 'none', 'mask' or 'net', not %r" % (post,))
+        if phase_iters and not 0 < int(phase_iters) <= hip.PHASE_MAX_ITERS:
+            raise ValueError("phase_iters 0 ... %d, not %r" % (hip.PHASE_MAX_ITERS, phase_iters))
+        xs, C, pf, off, foff = self._array_clips("enhance_array", mixes)
+        n, F, B = len(xs), foff[-1], spec.BINS
+        if not (len(ctx_a) == len(ctx_b) == n):
+            raise ValueError("enhance_array: one (a, b) pair of conditioning recordings per clip")
+        if not isinstance(mask_from, str):
+            try:
+                mask_from = operator.index(mask_from)
+            except TypeError:
+                mask_from = None
+        if mask_from != "mean" and not (isinstance(mask_from, int) and 0 <= mask_from < C):
+            raise ValueError("enhance_array: mask_from is 'mean' or a channel 0 ... %d" % (C - 1))
+        if not 0 <= int(ref) < C:
+            raise ValueError("enhance_array: ref 0 ... %d, not %r" % (C - 1, ref))
+        lib, mem = self.lib, Mem(self)
+        (af, aoff), (bf, boff) = flat(ctx_a), flat(ctx_b)
+        ooff = offsets((foff[i + 1] - foff[i] - 1) * spec.HOP + spec.WIN for i in range(n))
+        ins = [mem.up(pf), mem.up(af), mem.up(bf)]
+        mono = mem.empty(off[-1])
+        names = ("lm", "ph", "logits", "den", "blm", "bph", "den2", "rph")
+        r = {k: mem.empty(F * B) for k in names}
+        ctx_lm, emb = mem.empty(2 * n * spec.NOISE_WIN * B), mem.empty(2 * n * spec.EMB)
+        wav, rec = mem.empty(ooff[-1]), mem.empty(n * hip.MVDR_FIELDS, np.float64)
+        mixed_wav = mem.empty(ooff[-1]) if want_mixed else None
+
+        def at(buf, floats):
+            return ctypes.c_void_p(mem.p(buf).value + 4 * floats)
+
+        def run():
+            c, h, s = hip.check, self.handle, mem.stream()
+            fo = hip.i64_array(foff)
+            for i in range(n):          # the signal the mask comes from: the channels' mean, or one channel (a mean of one)
+                ni = off[i + 1] - off[i]
+                src, k = (at(ins[0], C * off[i]), C) if mask_from == "mean" else (at(ins[0], C * off[i] + mask_from * ni), 1)
+                c(lib.nhans_channel_mean(h, src, k, ni, at(mono, off[i]), s))
+            c(lib.nhans_stft_features(h, mem.p(mono), hip.i64_array(off), n, 0, mem.p(r["lm"]), mem.p(r["ph"]), s))
+            c(lib.nhans_stft_features(h, mem.p(ins[1]), hip.i64_array(aoff), n, spec.NOISE_WIN, mem.p(ctx_lm), None, s))
+            c(lib.nhans_stft_features(h, mem.p(ins[2]), hip.i64_array(boff), n, spec.NOISE_WIN, at(ctx_lm, n * spec.NOISE_WIN * B), None, s))
+            c(lib.nhans_embed(h, mem.p(ctx_lm), 2 * n, mem.p(emb), s))
+            c(lib.nhans_mask_net(h, mem.p(r["lm"]), fo, n, mem.p(emb), at(emb, n * spec.EMB), mem.p(r["logits"]), mem.p(r["den"]), s))
+            c(lib.nhans_mvdr(h, mem.p(ins[0]), hip.i64_array(off), n, C, mem.p(r["logits"]), int(ref), float(loading), hip.MVDR_LOGGAIN,
+                             mem.p(r["logits"]) if post == "mask" else None, mem.p(r["blm"]), mem.p(r["bph"]), None, mem.p(rec), s))
+            out_lm = r["blm"]
+            if post == "net":
+                c(lib.nhans_mask_net(h, mem.p(r["blm"]), fo, n, mem.p(emb), at(emb, n * spec.EMB), None, mem.p(r["den2"]), s))
+                out_lm = r["den2"]
+            out_ph = r["bph"]
+            if phase_iters:
+                c(lib.nhans_phase_refine(h, mem.p(out_lm), mem.p(r["bph"]), fo, n, int(phase_iters), float(phase_alpha), mem.p(r["rph"]),
+                                         None, s))
+                out_ph = r["rph"]
+            c(lib.nhans_istft(h, mem.p(out_lm), mem.p(out_ph), fo, n, hip.i64_array(ooff), mem.p(wav), s))
+            if want_mixed:
+                c(lib.nhans_istft(h, mem.p(r["lm"]), mem.p(r["ph"]), fo, n, hip.i64_array(ooff), mem.p(mixed_wav), s))
+            return out_lm, out_ph
+
+        try:
+            out_lm, out_ph = self._with_lookahead(lookahead, lambda: redo_saturated_in_f32(self, run))   # (take_status waits)
+            g = lambda buf, cnt, dt=np.float32: np.array(mem.down(buf, cnt, dt), dtype=dt)
+            wav_h = g(wav, ooff[-1])
+            mixed_h = g(mixed_wav, ooff[-1]) if want_mixed else None
+            rec_h = g(rec, n * hip.MVDR_FIELDS, np.float64).reshape(n, hip.MVDR_FIELDS)
+            tap = {}
+            if taps:
+                tap = {k: g(b, F * B).reshape(F, B) for k, b in (("logits", r["logits"]), ("bf_logmag", r["blm"]), ("bf_phase", r["bph"]),
+                                                               ("logmag", out_lm), ("phase", out_ph))}
+        finally:
+            mem.free(*ins, mono, *r.values(), ctx_lm, emb, wav, rec, mixed_wav)
+        res = {"denoised_wav": [wav_h[ooff[i]:ooff[i + 1]] for i in range(n)], "records": [mvdr_mod.record(v) for v in rec_h]}
+        if want_mixed:
+            res["mixed_wav"] = [mixed_h[ooff[i]:ooff[i + 1]] for i in range(n)]
+        for k, v in tap.items():
+            res[k] = [v[foff[i]:foff[i + 1]] for i in range(n)]
+        return res
 
     def _records_call(self, signals, nrec, nextra, call):
         """What the calls that return records share: the flat float32 `signals` uploaded as one buffer, one float64 output

@@ -323,6 +323,28 @@ void launch_phase_inc(const double* num, const double* den, const int64_t* frame
                       hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// Mask-driven MVDR beamforming (mvdr.hip; include/nhans_hip.h: nhans_mvdr_*).  X: complex rows, channel c of clip i at row
+// C foff[i] + c T_i; mask, gain and the output rows: [F, 201] at foff; phi: complex double [nclips][2][C][C][201] (Phi_s,
+// Phi_n); w: complex double [nclips][201][C]; rec: kMvdrFields doubles per clip.
+constexpr int kMvdrMaxChannels = 8, kMvdrFields = 6, kMvdrLogGain = 1;
+constexpr int kMvdrRun = 32;            // frames per workgroup of the filter
+// the channel-clips of t (nclips * C of them) -> X and, where asked, the analysis rows of every channel-clip
+void launch_mvdr_spectra(const float* wav, ClipTable t, const int* block_clip, const int* block_f0, int nblocks, const float* tw400,
+                         const float* window, float* X, float* logmag, float* phase, hipStream_t s);
+// the covariances into phi and each bin's sum |X_ref|^2 into eref [nclips][201]
+void launch_mvdr_cov(const float* X, const float* mask, const int64_t* frame_off_dev, int nclips, int C, int ref, int flags, double* phi,
+                     double* eref, hipStream_t s);
+// phi -> w and (nullable) rec: frames, channels, ref, fallback_bins, energy_ref, NaN
+void launch_mvdr_solve(const double* phi, const double* eref, const int64_t* frame_off_dev, int nclips, int C, int ref, double loading,
+                       double* w_out, double* rec_out, hipStream_t s);
+// the rows of y = w^H x (+ gain, nullable) over the (clip, first frame) runs of kMvdrRun frames; y (nullable): the complex
+// float32 values themselves, [F, 201]; eframe (nullable): a frame's sum |y|^2
+void launch_mvdr_apply(const float* X, const double* w, const float* gain, const int64_t* frame_off_dev, const int* block_clip,
+                       const int* block_f0, int nblocks, int C, float* logmag, float* phase, float* y, double* eframe, hipStream_t s);
+// rec[clip][5] = the sum of the clip's eframe: lane l of 64 sums frames l, l + 64, ... ascending, the 64 sums by wave_sum
+void launch_mvdr_energy(const double* eframe, const int64_t* frame_off_dev, int nclips, double* rec, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // Sample-rate conversion and the file front end (resample.hip; include/nhans_hip.h: nhans_resample*)
 // The filter of scipy.signal.resample_poly(x, L, M), designed on the host in double.  tab = the taps rounded to float32,
 // phase-minor: tab[j * L + p] = h[p + j * L] (0 beyond the last tap), padded to a multiple of 4 floats.

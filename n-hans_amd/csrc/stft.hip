@@ -36,6 +36,8 @@ namespace nhans {
 // built and taken out: it leaks float32 rounding of the louder frame into the quieter one, log(|X| + 1e-5)
 // amplifies that at silent bins -- 1.25e-4 instead of 7e-5 on the separator's context embeddings, past the 1e-4
 // bar.  The inverse transform below does pack two frames: there the leak is 1e-7 of a waveform sample.)
+// (The run walk, the staging and the store loop below are restated in phase.hip: phase_project_kernel and in mvdr.hip:
+// mvdr_spectra_kernel, whose rows tests/test_gpu_mvdr.py holds to this kernel's bit for bit: an edit here goes there too.)
 __global__ void __launch_bounds__(256) stft_features_kernel(
     const float* __restrict__ wav, ClipTable tab, const int* __restrict__ block_clip,
     const int* __restrict__ block_f0, int nblocks, const cplx* __restrict__ tw400g, const float* __restrict__ windowg,

@@ -181,6 +181,31 @@ class Engine(context.Context):
                                               hip.i64_array(frame_off), n, N, float(alpha), hip.ptr(out), hip.ptr(ic), self._stream()))
         return (out, ic[:n, :N].contiguous() if N else ic[:n, :0]) if inc else out
 
+    # ---- mask-driven MVDR beamforming (include/nhans_hip.h: nhans_mvdr_*) ------------------------------
+    def mvdr_device(self, planes_t, sample_off, channels, mask_t, ref=0, loading=1e-6, loggain=False, gain_t=None):
+        """The beamformer on tensors already in HBM.  planes_t: flat float32, clip i = `channels` planes of n_i = sample_off[i
+        + 1] - sample_off[i] samples from element channels * sample_off[i] on; mask_t: float32 [F, 201] rows at the clips'
+        frame offsets (loggain=True: a log-gain, mask_net's logits); gain_t (optional): float32 [F, 201] log-gain added to
+        the output -> dict of device tensors: "logmag" and "phase" float32 [F, 201], "w" complex128 [n, 201, channels],
+        "records" float64 [n, hip.MVDR_FIELDS] (mvdr.FIELDS names the columns), and "frame_off"."""
+        n, C = len(sample_off) - 1, int(channels)
+        foff = context.offsets(int(self.lib.nhans_num_frames(sample_off[i + 1] - sample_off[i])) for i in range(n))
+        F = foff[-1]
+        if planes_t.dtype != torch.float32 or planes_t.dim() != 1 or planes_t.numel() != C * sample_off[-1]:
+            raise ValueError("mvdr_device: a flat float32 tensor of %d planes per clip" % C)
+        for t in (mask_t, gain_t):
+            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (F, spec.BINS)):
+                raise ValueError("mvdr_device: float32 [%d, %d] rows" % (F, spec.BINS))
+        lm = torch.empty((max(F, 1), spec.BINS), dtype=torch.float32, device=self.device)
+        ph = torch.empty_like(lm)
+        w = torch.empty((max(n, 1), spec.BINS, max(C, 1)), dtype=torch.complex128, device=self.device)
+        rec = torch.empty((max(n, 1), hip.MVDR_FIELDS), dtype=torch.float64, device=self.device)
+        hip.check(self.lib.nhans_mvdr(self.handle, hip.ptr(planes_t.contiguous()), hip.i64_array(sample_off), n, C, hip.ptr(mask_t.contiguous()),
+                                      int(ref), float(loading), hip.MVDR_LOGGAIN if loggain else 0,
+                                      hip.ptr(gain_t.contiguous()) if gain_t is not None else None, hip.ptr(lm), hip.ptr(ph),
+                                      hip.ptr(torch.view_as_real(w)), hip.ptr(rec), self._stream()))
+        return {"logmag": lm[:F], "phase": ph[:F], "w": w[:n], "records": rec[:n], "frame_off": foff}
+
     def fbank_rows(self, rows_t, fb):
         """fb (fbank.Filterbank) applied to a device tensor of [n, 201] float32 log-magnitude rows -- mask_net's denoised
         rows, or stft_features' logmag for the unprocessed signal -- -> device tensor [n, fb.n_mels]."""

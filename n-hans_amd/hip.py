@@ -151,6 +151,11 @@ SIGNATURES = {
     "nhans_phase_set_alpha": (_int, [_vp, _dbl]),
     "nhans_phase_project": (_int, [_vp, _vp, _vp, _i64p, _int, _vp, _vp, _vp]),
     "nhans_phase_refine": (_int, [_vp, _vp, _vp, _i64p, _int, _int, _dbl, _vp, _vp, _vp]),
+    # mask-driven MVDR beamforming of multi-channel clips
+    "nhans_mvdr_spectra": (_int, [_vp, _vp, _i64p, _int, _int, _vp, _vp, _vp, _vp]),
+    "nhans_mvdr_weights": (_int, [_vp, _vp, _vp, _i64p, _int, _int, _int, _dbl, _int, _vp, _vp, _vp, _vp]),
+    "nhans_mvdr_apply": (_int, [_vp, _vp, _vp, _vp, _i64p, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "nhans_mvdr": (_int, [_vp, _vp, _i64p, _int, _int, _vp, _int, _dbl, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nhans_profile_json": (_int, [_vp, _str, _size]),
     "nhans_profile_reset": (_int, [_vp]),
 }
@@ -189,6 +194,8 @@ QUALITY_FRAME, QUALITY_HOP, QUALITY_ORDER, QUALITY_FFT, QUALITY_BINS = 480, 120,
 QUALITY_BANDS, QUALITY_MAX_BANDS = 25, 32
 QUALITY_LPC_TILE, QUALITY_BAND_TILE = 7, 2  # frames per workgroup of quality.hip's LPC and band launches (kQualityLpcTile, kQualityBandTile)
 PHASE_MAX_ITERS = 256
+MVDR_MAX_CHANNELS, MVDR_FIELDS, MVDR_LOGGAIN = 8, 6, 1
+MVDR_RUN = 32                               # frames per workgroup of mvdr.hip's filter (kMvdrRun)
 PHASE_RUN = 20                              # frames per run of phase.hip's projection (kPhaseRun)
 MIX_TILE = 2048                             # samples per workgroup and per staging buffer of mix.hip (kMixTile)
 STATUS_SATURATED = 1
